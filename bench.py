@@ -5,6 +5,9 @@ One "step" = one pass of the hot path (ring projection, range, curvature, labell
 compaction: lfx_extract_batch_device) over one batch of synthetic scans whose point records are
 already resident in HBM.  Workload at every N: HDL-64E-shaped 64-ring x 1800-column scans
 (BASELINE.json configs[2], the shape the metric is quoted on), `--batch` scans per step per GPU.
+The timed region is exactly `--steps` steps (`--repeats R`: R such regions, value = their median).
+`--dump-outputs DIR` writes what the last timed step computed (a seeded sample of its scans, see
+dump_outputs) so that two builds can be compared output for output; the inputs are seeded.
 
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -38,7 +41,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E 8.0 TB/s spec
 
 
 def parse():
@@ -60,8 +63,9 @@ def parse():
                     help="a driver that keeps the grid and writes invalid returns as (0, 0, 0): --drop-fraction of the records are zeroed "
                          "instead of removed and the context filters them (lfx_config.drop_zero_points, convert.py:162-163)")
     ap.add_argument("--shuffle", action="store_true", help="records in arbitrary order (the reference's documented input contract)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region (--steps steps between two fences) is run this many times; value = the median")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the timed region (--steps steps between two fences) is run this many times; value = the median "
+                         "(default 1: exactly --steps steps are timed)")
     ap.add_argument("--gather-dst", default="rotate",
                     help="destination rank of the per-step gather: 'rotate' (step k's clouds land whole on rank k mod N: consecutive "
                          "steps use different xGMI links) or a fixed rank (every sender is then bound by its ONE link to that rank: "
@@ -88,7 +92,13 @@ def parse():
     ap.add_argument("--no-second-region", action="store_true", help="N>1 with a rotating destination: skip the short second region that gathers to rank 0")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams (each with its own context and scratch) the steps alternate over")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (rank 0's context) as DIR/<name>.npy: a fixed, "
+                         "seeded sample of the batch's scans as a caller downloads them (lfx_download_scan), float32 / float64, at most 64 MB")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def kernels_sha256():
@@ -98,6 +108,45 @@ def kernels_sha256():
         with open(os.path.join(ROOT, "lidar_feature_extraction_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+DUMP_BYTES = 64 * 1000 * 1000          # --dump-outputs: the cap on the files it writes, headers included
+DUMP_SCANS = 16                         # ... and on the scans it samples
+DUMP_SEED = 20251015
+
+
+def dump_outputs(fx, stream, n_list, n_rings, out_dir):
+    """--dump-outputs: the results the context's last batch left on the device, downloaded as a caller downloads them
+    (lfx_download_scan), for a fixed sample of the batch's scans: a seeded permutation of the scan indices, cut to as many
+    scans as fit in DUMP_BYTES at their largest possible outputs (so the sample depends on the inputs alone).  Every array
+    holds the sampled scans' arrays back to back, in the order of scans.npy, whose rows are (scan index in the batch,
+    n_points, n_sorted, n_edge, n_surface, n_rings)."""
+    # per point at most: label (f32) + curvature (f64) + sorted index (f64) + one feature record (4 x f32) and its index (f64)
+    bound = [44 * int(n) + 32 * n_rings for n in n_list]
+    order = np.random.Generator(np.random.PCG64(DUMP_SEED)).permutation(len(n_list))
+    pick, total = [], 4096                  # (the .npy headers)
+    for j in order[:DUMP_SCANS]:
+        if total + bound[j] > DUMP_BYTES:
+            break
+        pick.append(int(j))
+        total += bound[j]
+    if not pick:
+        raise SystemExit("bench.py: --dump-outputs: one scan's outputs can exceed %d bytes" % DUMP_BYTES)
+    pick.sort()
+    cols = {"labels": np.float32, "curvature": np.float64, "sorted_index": np.float64, "ring_id": np.float64,
+            "ring_count": np.float64, "ring_offset": np.float64, "ring_status": np.float64, "edge_points": np.float32,
+            "edge_index": np.float64, "surface_points": np.float32, "surface_index": np.float64}
+    parts = {k: [] for k in cols}
+    rows = []
+    for j in pick:
+        g = fx.download(j, stream)
+        for k in cols:
+            parts[k].append(getattr(g, k))
+        rows.append((j, len(g.labels), len(g.sorted_index), len(g.edge_index), len(g.surface_index), len(g.ring_id)))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scans.npy"), np.array(rows, np.float64))
+    for k, t in cols.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.concatenate(parts[k]).astype(t))
 
 
 WORKLOADS = {(64, 1800): "hdl64-64x1800 (BASELINE.json configs[2])", (16, 1800): "vlp16-16x1800 (BASELINE.json configs[1])",
@@ -266,6 +315,7 @@ def main():
     pack_done = [None] * n_streams
     stream = streams[0].cuda_stream
     step_no = [0]
+    last_k = [0]                           # the context (and stream) of the last step: what --dump-outputs reads
 
     use_gather = (world > 1 and not a.no_gather) or a.force_gather
     gather_error = None
@@ -383,6 +433,7 @@ def main():
         step_no[0] += 1
         if will_gather and not use_gather:
             k = 0                      # (the gather was given up: one context, as without it)
+        last_k[0] = k
         if use_gather and pack_done[k] is not None:
             streams[k].wait_event(pack_done[k])        # this context's clouds of two steps ago have been packed
         fxs[k].extract_batch_device(d_points.data_ptr(), n_list, streams[k].cuda_stream)
@@ -488,6 +539,10 @@ def main():
         mark("comm stats")
         comm_stats = all_ranks(gather.comm_report())
     mark("host-side measurements")
+
+    # the last timed step's results, before anything else runs on its context (N > 1: rank 0's scans)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(fxs[last_k[0]], streams[last_k[0]].cuda_stream, n_list, a.rings, a.dump_outputs)
 
     # what THIS box gives right now (outside the timed region, ~50 ms): a plain float4 copy of 1 GiB and the shader clock
     # with every SIMD busy -- so that a slower box and a slower kernel can be told apart in one line of the driver's record

@@ -1,7 +1,8 @@
 """Pins the CPU oracle (oracle/lfx_oracle.cpp) against the reference's own unit-test vectors
-(tests/golden/reference_unit_vectors.json, restated from /root/reference/extraction/test/*.cpp)
-and, where the reference's own translation units build here (oracle/_ref), against that
-compiled reference code bit-for-bit on random inputs.  CPU only."""
+(tests/golden/reference_unit_vectors.json, restated from the reference's extraction/test/*.cpp)
+and against the reference's own translation units bit-for-bit on random inputs: compiled, where
+they build (oracle/_ref), and everywhere through the hashes of their outputs stored in
+tests/golden/reference_pieces_hashes.json.  CPU only."""
 import ctypes as C
 import math
 
@@ -244,7 +245,7 @@ def test_label_to_color(refvec):
 
 
 # ------------------------------------------------------------------ against compiled reference pieces
-needs_ref = pytest.mark.skipif(B.ref_pieces() is None, reason="oracle/_ref not built (no /root/reference here)")
+needs_ref = pytest.mark.skipif(B.ref_pieces() is None, reason="oracle/_ref not built (the reference's sources are not here; test_ref_pieces_stored_hashes stands in)")
 
 
 @needs_ref
@@ -291,6 +292,26 @@ def test_ref_pieces_bit_exact():
                 assert rc1 == rc2
                 if rc1 == 0:
                     assert b1.tolist() == b2.tolist()
+
+
+def test_ref_pieces_stored_hashes():
+    """The comparison above without the compiled pieces: the oracle's outputs on the same inputs hash as the reference
+    pieces' did (tests/golden/reference_pieces_hashes.json, written by tools/make_ref_pieces_hashes.py); where the pieces
+    are built, theirs must still hash so too."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import make_ref_pieces_hashes as M
+    want = json.load(open(M.PATH))["hashes"]
+    got = M.pieces()
+    if got["input"] != want["input"]:
+        pytest.skip("this numpy draws other inputs than the ones the hashes were made on")
+    for k, v in want.items():
+        assert got[k] == v, "%s: the oracle's outputs differ from the reference pieces' (oracle/lfx_oracle.cpp edited?)" % k
+    if B.ref_pieces() is not None:
+        assert M.pieces(B.ref_pieces()) == want, "the reference pieces no longer give the stored outputs: re-run tools/make_ref_pieces_hashes.py"
 
 
 # ------------------------------------------------------------------ helpers and error texts (SURVEY.md 8a row a16)

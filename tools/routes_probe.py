@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere: the repo root holds the packages
 from lidar_feature_extraction_amd import FeatureExtraction, make_scan, concat
 batch = 256
 clouds = [make_scan(64, 1800, seed=1234 + i, start_col=517) for i in range(16)]
