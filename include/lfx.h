@@ -31,7 +31,10 @@ extern "C" {
                                     * workgroup-per-ring kernel, whose labelling then walks the positions in reach (slow, same results) */
 #define LFX_MAX_RING_ID 65535       /* a ring id is the uint16 of PointXYZIR (point_type.hpp:62-86) */
 #define LFX_MAX_RINGS 256           /* distinct ring ids a context takes (every spinning lidar fielded today has fewer) */
-#define LFX_MAX_RING_POINTS 4608    /* points of one ring must fit one workgroup's LDS (25 B each); 6 blocks of the unit kernels' long form */
+#define LFX_MAX_RING_POINTS 4608    /* the longest ring the LDS-resident kernels take (25 B per point in one workgroup's LDS; 6 blocks
+                                     * of the unit kernels' long form), and the ring capacity of a context that names none */
+#define LFX_MAX_LONG_RING_POINTS 262144  /* the largest max_points_per_ring (2^18).  A context above LFX_MAX_RING_POINTS takes
+                                     * rings of up to its capacity, the longer ones in a kernel whose workspace is in HBM */
 
 /* The nine node parameters: extraction/include/lidar_feature_extraction/hyper_parameter.hpp:32-65
  * (same names, same units; the neighbour threshold is in DEGREES, converted as
@@ -80,8 +83,14 @@ typedef struct lfx_config {
                                    * older header keeps working.  0 is refused (an uninitialised struct).               */
   uint32_t max_points_per_scan;   /* capacity of one scan                                   */
   uint32_t max_batch;             /* scans per lfx_extract_batch* call                      */
-  uint32_t max_points_per_ring;   /* 0 = LFX_MAX_RING_POINTS; rounded up to a multiple of 64.  The sensor's real
-                                   * column count here lets the ring kernel run its smallest (fastest) variant */
+  uint32_t max_points_per_ring;   /* 0 = LFX_MAX_RING_POINTS; at most LFX_MAX_LONG_RING_POINTS and max_points_per_scan;
+                                   * rounded up to a multiple of 64 (cap).  The sensor's real column count here lets the
+                                   * ring kernel run its smallest (fastest) variant.  Above LFX_MAX_RING_POINTS (long rings:
+                                   * line-based sensors, slow spinning ones) the ring-major arrays take
+                                   * max_batch x max_rings x cap x 45 B (37 B without LFX_OUT_CURVATURE) -- set max_rings:
+                                   * 0 reserves 256 rings of cap points each -- plus up to 512 MB of workspace for the
+                                   * long-ring kernel; the context declines the holes form (grids with (0, 0, 0) records
+                                   * are bucketed) */
   uint32_t max_rings;             /* ring ids are 0 .. max_rings-1 (a sensor's ring count); 0 = 256 */
   uint32_t drop_zero_points;      /* 1: points with x = y = z = 0 are not part of the scan -- the filter the
                                    * upstream converter applies (point_type_converter/convert.py:162-163,192) */
@@ -552,7 +561,7 @@ int lfx_route_choice(const uint32_t report[LFX_ROUTE_REPORT_WORDS], uint32_t rep
                      int organised_possible, uint32_t batch, uint32_t max_rings, uint32_t choice[LFX_ROUTE_CHOICE_WORDS]);
 
 /* --- measurement ------------------------------------------------------------------------- */
-#define LFX_N_KERNELS 12  /* ring_scatter, ring_unit, ring_order, ring_unit (second pass), ring_extract (the bucketing route), ring_totals, feature_compact (compaction), ring_unit_org (organised scans), ring_cut (transforms of rotated / reversed rings), fallback_tail (the organised route's tail), grid_count (valid returns per ring and column piece of a grid with holes), batch_reset */
+#define LFX_N_KERNELS 13  /* ring_scatter, ring_unit, ring_order, ring_unit (second pass), ring_extract (the bucketing route), ring_totals, feature_compact (compaction), ring_unit_org (organised scans), ring_cut (transforms of rotated / reversed rings), fallback_tail (the organised route's tail), grid_count (valid returns per ring and column piece of a grid with holes), batch_reset, ring_long (rings longer than LFX_MAX_RING_POINTS) */
 int lfx_set_profiling(lfx_ctx *ctx, int enabled);
 /* Record the events around every n-th batch only (default 1).  The event pairs between the kernels of a batch
  * cost ~7 % of the device-resident throughput at 64x1800x256; sampled, the durations stay live and the cost goes. */

@@ -10,7 +10,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LFX_LIB_PATH") or os.path.join(_HERE, "_lib", "liblfx.so")   # override: A/B builds only
 
-LFX_N_KERNELS = 12
+LFX_N_KERNELS = 13
+MAX_RING_POINTS = 4608            # LFX_MAX_RING_POINTS: the longest ring the LDS-resident kernels take; the default ring capacity
+MAX_LONG_RING_POINTS = 262144     # LFX_MAX_LONG_RING_POINTS: the largest max_points_per_ring (longer rings: HBM workspace)
 MAX_RINGS = 256
 
 STAGE_LABEL, STAGE_OCCLUSION, STAGE_OUT_OF_RANGE, STAGE_PARALLEL_BEAM = 1, 2, 4, 8

@@ -26,7 +26,7 @@ std::string g_create_error;
 const char * kKernelNames[LFX_N_KERNELS] = {
   "ring_scatter_kernel", "ring_unit_kernel", "ring_order_kernel", "ring_unit_kernel(second pass)", "ring_extract_kernel",
   "ring_totals_kernel", "feature_compact_kernel", "ring_unit_org_kernel", "ring_cut_kernel", "fallback_tail_kernel", "grid_count_kernel",
-  "batch_reset_kernel"};
+  "batch_reset_kernel", "ring_long_kernel"};
 
 // IsNeighborXY compares acos(cos_angle) with the threshold (neighbor.hpp:44-48, math.cpp:45).
 // acos is monotone, so that test is a bound on cos_angle itself: the smallest double c with
@@ -157,6 +157,9 @@ uint32_t ring_threads_for(uint32_t cap)
 {
   return cap > 1024 ? 512u : 256u;
 }
+
+// HBM a context with long rings sets aside for ring_long_kernel's workspaces (one per workgroup, ring_lds_bytes(cap) each)
+constexpr size_t kLongWorkBudget = (size_t)512 << 20;
 
 // Which route a batch takes, from what earlier batches reported (RouteState::report = the counters block of the last
 // batch whose report has landed) and the state the choices before left behind.  No device, no context: the function the
@@ -327,6 +330,10 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   const bool canon = c->layout.step == 32 && c->layout.ox == 0 && c->layout.oy == 4 && c->layout.oz == 8 &&
     c->layout.oring == 20 && c->layout.rtype == LFX_FIELD_UINT16 && c->layout.be == 0 &&
     (reinterpret_cast<uintptr_t>(pts) & 15u) == 0;
+  if (c->long_slices != 0u) {
+    // the long list starts empty (the LDS-resident kernels fill it, ring_long_kernel reads it)
+    LFX_HIP(c, hipMemsetAsync(c->long_count.p, 0, 4, st));
+  }
   // ---- which route: the organised-scan kernel first (scans it cannot take fall back inside this call), or
   //      bucketing for every scan: choose_route() over what earlier batches reported.  A batch's last kernel writes its
   //      report into pinned memory unasked; it is read only once the event behind that kernel has passed (with two scans in
@@ -402,7 +409,8 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   }
   const lfx::RingExtractArgs ex{c->dev, c->cap, c->stage_flags, c->max_rings, pts, c->layout, c->scan_begin.p, c->ring_count.p, c->sxy.p, c->sz.p,
     c->sidx.p, c->label_s.p, (c->outputs & LFX_OUT_CURVATURE) ? c->curv_s.p : nullptr, c->rec_pts.p, c->rec_idx.p, c->ring_status.p,
-    c->unit_ne.p, c->unit_ns.p, c->unit_span.p, c->ring_flags.p};
+    c->unit_ne.p, c->unit_ns.p, c->unit_span.p, c->ring_flags.p, c->long_count.p, c->long_list.p,
+    (uint32_t)(c->long_list.n / 2u)};
   if (lazy) {
     // ---- the organised route's tail in one launch: the fall-back list is empty as a rule
     Timed t(c, 9, st);
@@ -476,6 +484,13 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
     hipLaunchKernelGGL(lfx::ring_extract_kernel, grid, dim3(c->ring_threads), c->ring_lds, st,
       ex, short_tail ? 2u : (c->fast_path ? 1u : 0u), short_tail ? fb_count : slow_count, short_tail ? c->fb_list.p : c->slow_list.p);
   }
+  }
+  if (c->long_slices != 0u) {
+    // rings longer than the LDS holds, whichever of the kernels above put them on the long list (its first read: the list's
+    // length; an empty list ends every workgroup there)
+    Timed t(c, 12, st);
+    hipLaunchKernelGGL(lfx::ring_long_kernel, dim3(c->long_slices), dim3(512), lfx::kLongSortLds, st, ex, c->long_work.p,
+      c->long_slice_bytes);
   }
   {
     // compaction: every scan of the batch, whoever labelled it.  Small batches: the compaction kernel finds every ring's
@@ -874,18 +889,23 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
   c->max_batch = config->max_batch;
   uint32_t ring_cap = config->max_points_per_ring ? config->max_points_per_ring : LFX_MAX_RING_POINTS;
   ring_cap = ring_cap > c->max_points ? c->max_points : ring_cap;
-  c->cap = ((ring_cap < 64 ? 64 : ring_cap) + 63u) & ~63u;
-  if (c->cap > LFX_MAX_RING_POINTS) {
+  if (ring_cap > LFX_MAX_LONG_RING_POINTS) {
     delete c;
-    g_create_error = "max_points_per_ring exceeds LFX_MAX_RING_POINTS";
+    g_create_error = "max_points_per_ring exceeds LFX_MAX_LONG_RING_POINTS (262144)";
     return LFX_ERR_INVALID_ARGUMENT;
   }
+  c->cap = ((ring_cap < 64 ? 64 : ring_cap) + 63u) & ~63u;
+  // Above LFX_MAX_RING_POINTS a ring no longer fits one workgroup's LDS: the LDS-resident kernels are laid out for
+  // LFX_MAX_RING_POINTS (lds_ring_cap) and hand longer rings to ring_long_kernel (workspace in HBM)
+  const bool long_rings = c->cap > LFX_MAX_RING_POINTS;
+  const uint32_t lds_cap = lfx::lds_ring_cap(c->cap);
   c->max_rings = config->max_rings ? (config->max_rings > lfx::kRings ? lfx::kRings : config->max_rings) : lfx::kRings;
-  c->ring_threads = ring_threads_for(c->cap);
+  c->ring_threads = ring_threads_for(lds_cap);
   {
     // longest span (owned positions + halo) a unit of a ring of `ring_cap` points can have:
     // block <= ceil((N - 2P) / B) + 1, plus a border of P for the first / last unit, plus 2 (P + 1) halo
-    const int P = c->dev.P, B = c->dev.B, N = (int)ring_cap;
+    // (a longer ring than the LDS-resident kernels take is never the unit kernels')
+    const int P = c->dev.P, B = c->dev.B, N = (int)(ring_cap < LFX_MAX_RING_POINTS ? ring_cap : LFX_MAX_RING_POINTS);
     const int span = (N - 2 * P + B - 1) / B + 1 + 3 * P + 2;
     const int ch = (span + 63) / 64;
     // (3 .. 6 chunks, or the long form for anything above -- blocks of up to 768 positions; longer ones are the
@@ -913,8 +933,8 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
   if (const char * dbg = LFX_DEBUG_ENV("UNIT_FLAGS")) {c->unit_flags = (uint32_t)std::atoi(dbg);}
   if (const char * dbg = LFX_DEBUG_ENV("UNIT_LDS_PAD")) {c->unit_lds_pad = (uint32_t)std::atoi(dbg);}
   if (const char * dbg = LFX_DEBUG_ENV("RING_THREADS")) {c->ring_threads = (uint32_t)std::atoi(dbg);}
-  c->ring_lds = lfx::ring_lds_bytes(c->cap);
-  c->order_lds = lfx::order_lds_bytes(c->cap);
+  c->ring_lds = lfx::ring_lds_bytes(lds_cap);
+  c->order_lds = lfx::order_lds_bytes(lds_cap);
   c->max_chunks = (c->max_points + lfx::kChunkPoints - 1) / lfx::kChunkPoints;
   c->total_cap = (size_t)c->max_points * c->max_batch;
   if (c->total_cap >= (1ull << 32)) {
@@ -946,10 +966,24 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
   ok(c->d_label.alloc(c->max_points)); ok(c->d_curv.alloc(c->max_points)); ok(c->d_sidx.alloc(c->max_points));
   ok(c->edge_pts.alloc(tc)); ok(c->surf_pts.alloc(tc)); ok(c->edge_idx.alloc(tc)); ok(c->surf_idx.alloc(tc));
   ok(c->unit_tab.alloc(2));
-  if (c->drop_zero && c->fused_possible) {
+  if (c->drop_zero && c->fused_possible && !long_rings) {
+    // (a context with long rings declines the holes form -- its count pass keeps a ring's pieces in 16-bit LDS counts --
+    // and takes grids with holes through bucketing)
     // the tables of the holes form of the organised route (grid_count_kernel): prefix rows and unit descriptors
     ok(c->cum16.alloc(nb * c->max_rings * lfx::cum_stride(c->cap) + 1024u));
     ok(c->hole_desc.alloc(nb * c->max_rings * (size_t)c->dev.B));
+  }
+  if (long_rings) {
+    // ring_long_kernel: the long list, its length, and one HBM workspace of ring_lds_bytes(cap) per workgroup -- as many
+    // workgroups as kLongWorkBudget holds (at least one, at most one per CU of the largest part, and never more than
+    // rings a batch can hold)
+    c->long_slice_bytes = (lfx::ring_lds_bytes(c->cap) + 255u) & ~(size_t)255u;
+    size_t slices = kLongWorkBudget / c->long_slice_bytes;
+    slices = slices < 1u ? 1u : (slices > 256u ? 256u : slices);
+    slices = slices > nb * c->max_rings ? nb * c->max_rings : slices;
+    c->long_slices = (uint32_t)slices;
+    ok(c->long_list.alloc(2 * tables)); ok(c->long_count.alloc(1));
+    ok(c->long_work.alloc(slices * c->long_slice_bytes));
   }
   if (c->fast_path) {
     // the unit kernels' record slots: 20 bytes per place (a point and its index), 64 or 128 places per unit, units back to back
@@ -1047,7 +1081,7 @@ void lfx_destroy(lfx_ctx * c)
   c->scan_begin.release(); c->scan_info.release(); c->scan_geom.release(); c->chunk_base.release();
   c->ring_count.release(); c->chunk_flags.release(); c->d_label.release(); c->d_curv.release(); c->d_sidx.release();
   c->ring_status.release(); c->ring_nedge.release(); c->ring_nsurf.release(); c->ring_ebase.release();
-  c->ring_sbase.release(); c->ring_flags.release(); c->counters.release(); c->scan_flags.release(); c->tail_ticket.release(); c->cum16.release(); c->hole_desc.release(); c->ring_slot.release(); c->slow_list.release(); c->defer_list.release(); c->redo_list.release(); c->fb_list.release(); c->xform.release(); c->unit_ne.release(); c->unit_ns.release(); c->unit_span.release();
+  c->ring_sbase.release(); c->ring_flags.release(); c->counters.release(); c->scan_flags.release(); c->tail_ticket.release(); c->cum16.release(); c->hole_desc.release(); c->long_list.release(); c->long_count.release(); c->long_work.release(); c->ring_slot.release(); c->slow_list.release(); c->defer_list.release(); c->redo_list.release(); c->fb_list.release(); c->xform.release(); c->unit_ne.release(); c->unit_ns.release(); c->unit_span.release();
   c->sxy.release(); c->sz.release(); c->sidx.release(); c->rec_pts.release(); c->rec_idx.release(); c->label_s.release();
   c->unit_tab.release();
   if (c->h_counters) {(void)hipHostFree(c->h_counters); c->h_counters = nullptr;}

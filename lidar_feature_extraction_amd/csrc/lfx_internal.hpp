@@ -195,6 +195,13 @@ struct lfx_ctx
   bool ids_given = false, organised_by_config = false;
   lfx_host::DevBuf<uint16_t> cum16;      // grid_count_kernel's prefix table (the holes form; contexts with the zero filter on)
   lfx_host::DevBuf<uint4> hole_desc;     // ... and its unit descriptors
+  // Contexts whose ring capacity is above LFX_MAX_RING_POINTS (long rings, ring_long_kernel): the long list ({entry, how}
+  // pairs, one per ring id and scan), its length (zeroed ahead of every batch) and the kernel's workspace, long_slices
+  // slices of long_slice_bytes in HBM.  Empty in every other context.
+  lfx_host::DevBuf<uint32_t> long_list, long_count;
+  lfx_host::DevBuf<uint8_t> long_work;
+  uint32_t long_slices = 0;
+  size_t long_slice_bytes = 0;
   // The batch's accumulators (counters, scan_flags, ring_nedge / ring_nsurf) exist twice: batch k uses set `parity`, its
   // compaction zeroes the other one over the scans the batch before last left dirty there (par_dirty).  aux_dirty: scans whose
   // bucketing-route tables (look-back flags, ring flags, ring transforms) a batch since the last reset may have touched.

@@ -44,6 +44,7 @@
 // own acos (lfx_api.hip: cos_bound()).
 #pragma once
 
+#include "../../include/lfx.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -265,5 +266,12 @@ __device__ inline void scan_falls_back(const UnitTables * __restrict__ tab, uint
 
 constexpr uint32_t kRecBytes = 20u;                       // per place: a 16-byte point and a 4-byte index
 constexpr uint32_t kUnitRecordsInSlot = 0x80000000u;      // in unit_span: written by the unit kernels, not by the workgroup-per-ring kernel
+// in unit_span: a ring the long-ring kernel took (ring_long_kernel), its records over the whole ring [0, N) as one segment --
+// N itself is ring_count's, not packed (the 15-bit end of the other forms holds no ring of 32 768 points or more)
+constexpr uint32_t kUnitWholeRing = 0x40000000u;
+
+// The longest ring the LDS-resident kernels take (ring_extract_kernel, ring_order_kernel, fallback_tail_kernel, the unit
+// kernels).  A context whose ring capacity is larger hands longer rings to ring_long_kernel (workspace in HBM).
+__host__ __device__ inline uint32_t lds_ring_cap(uint32_t cap) {return cap < LFX_MAX_RING_POINTS ? cap : (uint32_t)LFX_MAX_RING_POINTS;}
 
 }  // namespace lfx

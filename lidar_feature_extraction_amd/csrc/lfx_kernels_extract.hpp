@@ -1523,7 +1523,9 @@ __global__ __launch_bounds__(512) void ring_order_kernel(
       }
     }
   }
-  const uint32_t M = cap;                             // (a multiple of 64; the sorting networks need no power of two: bitonic_partner)
+  // (a multiple of 64; the sorting networks need no power of two: bitonic_partner.  A context whose ring capacity is above
+  // what the LDS holds lays the LDS out for LFX_MAX_RING_POINTS and passes longer rings on unsorted: ring_long_kernel's)
+  const uint32_t M = lds_ring_cap(cap);
   float * lx = reinterpret_cast<float *>(lds_raw);
   float * ly = lx + M;
   uint32_t * li = reinterpret_cast<uint32_t *>(ly + M);   // arrival index (tie-break)
@@ -1545,7 +1547,7 @@ __global__ __launch_bounds__(512) void ring_order_kernel(
     const size_t off = ring_base(s, slot, max_rings, cap);
     // (a ring this kernel already put in order is not sorted a second time: where the float predicate is not a
     // consistent order on nearly parallel points a second sort could differ)
-    const bool fixable = (reason & kDeferOrder) && !(reason & kRingSorted) && N >= 2 && (uint32_t)N <= cap;
+    const bool fixable = (reason & kDeferOrder) && !(reason & kRingSorted) && N >= 2 && (uint32_t)N <= M;
     if (fixable) {
       if (tid < 8) {cnt[tid] = tid == 1 || tid == 3 ? -1 : 0;}
       for (int i0 = 0; i0 < N; i0 += 4 * T) {           // twelve loads per thread in flight, then the LDS stores
@@ -1807,12 +1809,131 @@ struct RingExtractArgs
   uint32_t * __restrict__ rec_idx;
   uint8_t * __restrict__ ring_status;
   uint32_t * __restrict__ unit_ne, * __restrict__ unit_ns, * __restrict__ unit_span, * __restrict__ ring_flags;
+  // the long list (contexts whose ring capacity is above LFX_MAX_RING_POINTS; nullptr otherwise): rings longer than the LDS
+  // holds, as pairs {s * kRings + slot, sorted_already | mark << 1}, for ring_long_kernel
+  uint32_t * __restrict__ long_count, * __restrict__ long_list;
+  uint32_t long_cap;          // pairs the list has room for
 };
 
-// One ring (scan s, ring id slot) by the whole workgroup.  sorted_already: ring_order_kernel has put the ring in angle
-// order; mark: leave the ring's flag word saying the ring was taken here (the list routes; the fall-back tail leaves the
-// flags as it found them, so that no reset has to follow it).
-__device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw, uint32_t s, uint32_t slot, bool sorted_already, bool mark)
+// ------------------------------------------------------------------------------------------
+// Angle order of a LONG ring (ring_long_kernel; the same contract as angle_sort): w.x / w.y hold the ring as bucketed; a
+// ring strictly increasing under the predicate is left as it is.  Otherwise it is sorted by exactly angle_sort's total
+// order (sort_less: the predicate, then the arrival index) -- tiles of kLongTile points by the bitonic network in LDS, then
+// merge passes in HBM, each output position's source found by a merge-path search -- in scratch laid over the
+// workspace (2 x 12 N <= 25 cap bytes), written back to gxy / gidx, and w.x / w.y are refilled.  Returns true when a sort
+// was needed.
+constexpr uint32_t kLongTile = 4096;
+constexpr size_t kLongSortLds = (size_t)kLongTile * 12;
+
+__device__ inline bool long_sort(RingWork & w, int N, float2 * gxy, uint32_t * gidx, uint8_t * lds_raw)
+{
+  const int T = blockDim.x, tid = threadIdx.x;
+  int bad = 0;
+  for (int i = tid; i + 1 < N; i += T) {
+    bad |= !polar_less(w.x[i], w.y[i], w.x[i + 1], w.y[i + 1]);
+  }
+  if (!__syncthreads_or(bad)) {return false;}
+  float * ax = reinterpret_cast<float *>(w.base);
+  float * ay = ax + N;
+  uint32_t * ai = reinterpret_cast<uint32_t *>(ay + N);
+  float * bx = reinterpret_cast<float *>(ai + N);
+  float * by = bx + N;
+  uint32_t * bi = reinterpret_cast<uint32_t *>(by + N);
+  float * lx = reinterpret_cast<float *>(lds_raw);
+  float * ly = lx + kLongTile;
+  uint32_t * li = reinterpret_cast<uint32_t *>(ly + kLongTile);
+  // 1. tiles: the all-ascending network over each tile's n points (bitonic_partner: no power of two stored)
+  for (uint32_t t0 = 0; t0 < (uint32_t)N; t0 += kLongTile) {
+    const uint32_t n = (uint32_t)N - t0 < kLongTile ? (uint32_t)N - t0 : kLongTile;
+    for (uint32_t i = tid; i < n; i += T) {
+      const float2 v = gxy[t0 + i];
+      lx[i] = v.x;
+      ly[i] = v.y;
+      li[i] = gidx[t0 + i];
+    }
+    __syncthreads();
+    uint32_t M = 1;
+    while (M < n) {M <<= 1;}
+    for (uint32_t k = 2; k <= M; k <<= 1) {
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        for (uint32_t t = tid; t < M / 2; t += T) {
+          uint32_t i, p;
+          bitonic_partner(t, k, j, i, p);
+          if (p < n) {
+            const float x0 = lx[i], y0 = ly[i], x1 = lx[p], y1 = ly[p];
+            const uint32_t i0 = li[i], i1 = li[p];
+            if (sort_less(x1, y1, i1, x0, y0, i0)) {
+              lx[i] = x1; ly[i] = y1; li[i] = i1;
+              lx[p] = x0; ly[p] = y0; li[p] = i0;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (uint32_t i = tid; i < n; i += T) {
+      ax[t0 + i] = lx[i];
+      ay[t0 + i] = ly[i];
+      ai[t0 + i] = li[i];
+    }
+    __syncthreads();
+  }
+  // 2. merge passes: runs of `width` pairwise into runs of 2 width.  Thread t writes the output positions
+  // [t * per, (t + 1) * per): a binary search on the merge path where its range starts (again where it crosses into the
+  // next pair of runs), then a sequential merge.  sort_less is a strict total order: no ties to keep stable.
+  const uint32_t per = ((uint32_t)N + T - 1) / T;
+  for (uint32_t width = kLongTile; width < (uint32_t)N; width <<= 1) {
+    uint32_t o = tid * per;
+    const uint32_t o_end = o + per < (uint32_t)N ? o + per : (uint32_t)N;
+    while (o < o_end) {
+      const uint32_t lo = o / (2 * width) * (2 * width);
+      const uint32_t mid = lo + width < (uint32_t)N ? lo + width : (uint32_t)N;
+      const uint32_t hi = mid + width < (uint32_t)N ? mid + width : (uint32_t)N;
+      const uint32_t na = mid - lo, nb = hi - mid, d = o - lo;
+      uint32_t l = d > nb ? d - nb : 0u, h = d < na ? d : na;
+      while (l < h) {
+        const uint32_t m = (l + h) >> 1;
+        const uint32_t pa = lo + m, pb = mid + d - 1u - m;
+        if (sort_less(ax[pa], ay[pa], ai[pa], ax[pb], ay[pb], ai[pb])) {l = m + 1u;} else {h = m;}
+      }
+      uint32_t ia = lo + l, ib = mid + (d - l);
+      const uint32_t stop = o_end < hi ? o_end : hi;
+      for (; o < stop; o++) {
+        bool take_a = ib >= hi;
+        if (!take_a && ia < mid) {take_a = sort_less(ax[ia], ay[ia], ai[ia], ax[ib], ay[ib], ai[ib]);}
+        const uint32_t src = take_a ? ia++ : ib++;
+        bx[o] = ax[src];
+        by[o] = ay[src];
+        bi[o] = ai[src];
+      }
+    }
+    __syncthreads();                        // (global stores of the workgroup: visible to it after the barrier)
+    float * tx = ax; ax = bx; bx = tx;
+    float * ty = ay; ay = by; by = ty;
+    uint32_t * ti = ai; ai = bi; bi = ti;
+  }
+  for (int i = tid; i < N; i += T) {
+    gxy[i] = make_float2(ax[i], ay[i]);
+    gidx[i] = ai[i];
+  }
+  __syncthreads();
+  for (int i = tid; i < N; i += T) {
+    const float2 v = gxy[i];
+    w.x[i] = v.x;
+    w.y[i] = v.y;
+  }
+  __syncthreads();
+  return true;
+}
+
+// One ring (scan s, ring id slot) by the whole workgroup over a workspace of `wcap` positions: the LDS (LONG = false,
+// wcap = lds_ring_cap(cap)) or a slice of HBM (LONG: ring_long_kernel, wcap = cap; `lds_raw` is then the tile sort's LDS).
+// sorted_already: ring_order_kernel has put the ring in angle order; mark: leave the ring's flag word saying the ring was
+// taken here (the list routes; the fall-back tail leaves the flags as it found them, so that no reset has to follow it).
+template<bool LONG>
+__device__ inline void ring_body(
+  const RingExtractArgs & a, uint8_t * work, uint32_t wcap, uint8_t * lds_raw, uint32_t s, uint32_t slot, bool sorted_already,
+  bool mark)
 {
   const int T = blockDim.x, tid = threadIdx.x;
   const uint32_t cap = a.cap, max_rings = a.max_rings;
@@ -1822,7 +1943,7 @@ __device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw
   const size_t ui = ((size_t)s * kRings + slot) * kUnitMaxBlocks;
   uint8_t status = kOk;
   bool resorted = false;
-  RingWork w = carve(lds_raw, cap);
+  RingWork w = carve(work, wcap);
   if ((uint32_t)N > cap) {
     status = kTooLarge;
   } else {
@@ -1833,7 +1954,7 @@ __device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw
     }
     __syncthreads();
     if (!sorted_already) {
-      resorted = angle_sort(w, N, a.sxy + off, a.sidx + off);
+      resorted = LONG ? long_sort(w, N, a.sxy + off, a.sidx + off, lds_raw) : angle_sort(w, N, a.sxy + off, a.sidx + off);
     }
     status = process_ring(w, a.prm, N, a.stage_flags, nullptr, nullptr, nullptr);
   }
@@ -1841,7 +1962,7 @@ __device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw
   if (tid < kUnitMaxBlocks) {a.unit_ne[ui + tid] = 0; a.unit_ns[ui + tid] = 0; a.unit_span[ui + tid] = 0;}
   if (tid == 0) {
     if (mark) {a.ring_flags[s * kRings + slot] = 1u;}
-    a.unit_span[ui] = ((uint32_t)((uint32_t)N < cap ? N : (int)cap) << 16);
+    a.unit_span[ui] = LONG ? kUnitWholeRing : ((uint32_t)((uint32_t)N < cap ? N : (int)cap) << 16);
   }
   if (status != kOk) {
     // the ring contributes nothing (feature_extraction.cpp:116,154-156)
@@ -1869,7 +1990,7 @@ __device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw
       }
       if (k < nwords) {
         w.wbase[k] = ce + ie - ne;
-        w.wbase[cap / 64 + k] = cs + is - ns;
+        w.wbase[wcap / 64 + k] = cs + is - ns;
       }
       ce += __shfl(ie, 63);
       cs += __shfl(is, 63);
@@ -1898,13 +2019,33 @@ __device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw
       if (lab == kEdge) {
         at = off + w.wbase[i >> 6] + __popcll(w.featE[(i >> 6) + 1] & below);
       } else {
-        at = off + N - 1 - (w.wbase[cap / 64 + (i >> 6)] + __popcll(w.featS[(i >> 6) + 1] & below));
+        at = off + N - 1 - (w.wbase[wcap / 64 + (i >> 6)] + __popcll(w.featS[(i >> 6) + 1] & below));
       }
       a.rec_pts[at] = make_float4(x, y, z, (float)c);
       a.rec_idx[at] = orig;
     }
   }
   __syncthreads();
+}
+
+
+// A ring of the LDS-resident routes.  In a context whose ring capacity is above LFX_MAX_RING_POINTS a ring longer than the
+// LDS holds goes on the long list instead (ring_long_kernel takes it behind this launch).
+__device__ inline void extract_ring(const RingExtractArgs & a, uint8_t * lds_raw, uint32_t s, uint32_t slot, bool sorted_already, bool mark)
+{
+  const uint32_t lcap = lds_ring_cap(a.cap);
+  const uint32_t N = a.ring_count[s * kRings + slot];
+  if (N > lcap && N <= a.cap) {
+    if (threadIdx.x == 0) {
+      const uint32_t at = atomicAdd(a.long_count, 1u);
+      if (at < a.long_cap) {
+        a.long_list[2 * at] = s * kRings + slot;
+        a.long_list[2 * at + 1] = (sorted_already ? 1u : 0u) | (mark ? 2u : 0u);
+      }
+    }
+    return;
+  }
+  ring_body<false>(a, lds_raw, lcap, nullptr, s, slot, sorted_already, mark);
 }
 
 __global__ __launch_bounds__(512) void ring_extract_kernel(
@@ -1931,6 +2072,26 @@ __global__ __launch_bounds__(512) void ring_extract_kernel(
       if (slot >= max_rings || a.ring_count[s * kRings + slot] == 0u) {return;}
     }
     extract_ring(a, lds_raw, s, slot, use_list && (a.ring_flags[s * kRings + slot] & kRingSorted), true);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Long-ring kernel: the rings the LDS-resident kernels put on the long list (longer than LFX_MAX_RING_POINTS), one
+// workgroup per ring, the workgroup's RingWork in its own slice of `work` in HBM (ring_lds_bytes(cap) bytes, slices
+// 256-byte aligned) and the angle sort's tiles in LDS.  The phases are the LDS body's own (stencil_phase, block_check, the
+// labelling, mask_phase, the record emission), so labels and curvature are the same by construction; the waves of the
+// workgroup see each other's global stores across its barriers (workgroup-scope fence; not built for tgsplit).  Launched
+// only by contexts with such a capacity, behind the slow-path kernels and before the compaction; the grid is the number
+// of slices and loops over the list, whose length it reads first.
+__global__ __launch_bounds__(512) void ring_long_kernel(RingExtractArgs a, uint8_t * __restrict__ work, size_t slice_bytes)
+{
+  const uint32_t n_items = *a.long_count < a.long_cap ? *a.long_count : a.long_cap;
+  if (blockIdx.x >= n_items) {return;}
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  uint8_t * mine = work + (size_t)blockIdx.x * slice_bytes;
+  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const uint32_t e = a.long_list[2 * item], how = a.long_list[2 * item + 1];
+    ring_body<true>(a, mine, a.cap, lds_raw, e / kRings, e % kRings, (how & 1u) != 0u, (how & 2u) != 0u);
   }
 }
 
@@ -2209,7 +2370,7 @@ __global__ __launch_bounds__(256) void feature_compact_kernel(
         for (uint32_t v = 0; v + 1u < n_units; v++) {u += t >= (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)v) ? 1u : 0u;}
         const uint32_t ne = (uint32_t)__shfl((int)ne_k, (int)u), ns = (uint32_t)__shfl((int)ns_k, (int)u), span = (uint32_t)__shfl((int)span_k, (int)u);
         const uint32_t cum = (uint32_t)__shfl((int)excl, (int)u), ecum = (uint32_t)__shfl((int)e_excl, (int)u), scum = (uint32_t)__shfl((int)s_excl, (int)u);
-        const size_t first = off + (span & 0xFFFFu), last = off + ((span >> 16) & 0x7FFFu);
+        const size_t first = off + (span & 0xFFFFu), last = off + ((span & kUnitWholeRing) != 0u ? n_ring : ((span >> 16) & 0x7FFFu));
         const bool slots = (span & kUnitRecordsInSlot) != 0u;        // a unit of the unit kernels: the first slot_places records in its slot
         const uint32_t q = t - cum;                          // index inside unit u
         edge[i] = q < ne;

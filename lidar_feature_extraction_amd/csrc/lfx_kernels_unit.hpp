@@ -1109,9 +1109,10 @@ __device__ __forceinline__ void unit_body(
     return; \
   } while (0)
   LFX_STAMP(0);
-  // skip conditions and over-long rings are the slow path's business (it also reports them)
+  // skip conditions and over-long rings are the slow path's business (it also reports them); a ring longer than the
+  // LDS-resident kernels take is the long-ring kernel's, whatever its blocks (the span word below packs positions in 15 bits)
   // (ORG: the same for the four waves of the workgroup, which therefore leave together -- before the barrier)
-  if (N < 2 * P + 1 || N - 2 * P < B || (uint32_t)N > ring_cap) {
+  if (N < 2 * P + 1 || N - 2 * P < B || (uint32_t)N > lds_ring_cap(ring_cap)) {
     if (j == 0) {LFX_DEFER(kDeferOther);}
     return;
   }

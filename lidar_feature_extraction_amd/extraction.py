@@ -95,6 +95,9 @@ class FeatureExtraction:
     def __init__(self, params=None, device=0, max_points_per_scan=262144, max_batch=1,
                  max_points_per_ring=0, max_rings=0, drop_zero_points=False, layout=None, outputs=0, stream_hint=0, test_hooks=None,
                  ring_ids=None):
+        # max_points_per_ring: 0 = B.MAX_RING_POINTS; up to B.MAX_LONG_RING_POINTS (and max_points_per_scan).  Above
+        # B.MAX_RING_POINTS longer rings run in the long-ring kernel (HBM workspace); the ring-major arrays then take
+        # max_batch * max_rings * capacity * 45 bytes: give max_rings (0 reserves 256 rings)
         # test_hooks: the context comes from the test-hooks build of the library (B.HOOKS_LIB_PATH), the only one whose
         # lfx_create reads the LFX_DEBUG_* switches (tests and tools/ only).  None: that build exactly when such a switch is
         # set in the environment -- the shipped library would not see it
