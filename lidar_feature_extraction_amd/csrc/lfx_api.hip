@@ -1001,6 +1001,32 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
     e = hipHostMalloc(reinterpret_cast<void **>(&c->h_counters), 4 * (lfx::kCounters + 2), hipHostMallocDefault);
     if (e == hipSuccess) {std::memset(c->h_counters, 0, 4 * (lfx::kCounters + 2));}
   }
+  if (e == hipSuccess && LFX_DEBUG_ENV("POISON") != nullptr) {
+    // Tests of the write-before-read contract: every table below starts as a pattern no kernel writes, so that a
+    // batch that reads what it did not write gives wrong numbers instead of the zeros fresh memory tends to hold.  A poison
+    // value must never become an address or a copy size: float data gets a quiet NaN (the word 0x7FF80000 is one as a float
+    // and, doubled, as a double), counts a 1 (a stale count adds one record per unit read, far fewer than the scan's points:
+    // result_pack_kernel copies as many as scan_info says), and a table whose values are addresses or offsets is left as it is.
+    constexpr uint32_t kNaN = 0x7FF80000u;
+    auto d32 = [&](void * p, uint32_t v, size_t bytes) {if (p) {ok(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), (int)v, bytes / 4));}};
+    auto d8 = [&](void * p, uint8_t v, size_t bytes) {if (p) {ok(hipMemsetD8(reinterpret_cast<hipDeviceptr_t>(p), v, bytes));}};
+    // float data: the ring-major points and curvature, the workgroup-per-ring kernel's records, the unit kernels' record
+    // slots (their index plane too: feature indices only ever travel to the caller, no kernel here addresses by them), the
+    // feature clouds, the densified curvature
+    d32(c->sxy.p, kNaN, c->sxy.n * sizeof(float2)); d32(c->sz.p, kNaN, c->sz.n * sizeof(float));
+    d32(c->curv_s.p, kNaN, c->curv_s.n * sizeof(double)); d32(c->rec_pts.p, kNaN, c->rec_pts.n * sizeof(float4));
+    d32(c->rec32.p, kNaN, c->rec32.n * sizeof(float4)); d32(c->d_curv.p, kNaN, c->d_curv.n * sizeof(double));
+    d32(c->edge_pts.p, kNaN, c->edge_pts.n * sizeof(float4)); d32(c->surf_pts.p, kNaN, c->surf_pts.n * sizeof(float4));
+    // counts: the units' feature counts; a ring's status and the labels are bytes that only travel to the caller (0xFF is
+    // no label; the wire colours index by label & 7)
+    d32(c->unit_ne.p, 1u, c->unit_ne.n * 4); d32(c->unit_ns.p, 1u, c->unit_ns.n * 4);
+    d8(c->ring_status.p, 1u, c->ring_status.n); d8(c->label_s.p, 0xFFu, c->label_s.n); d8(c->d_label.p, 0xFFu, c->d_label.n);
+    // Left as they are, addresses and offsets without a clamp at every consumer: sidx (densify_kernel scatters through it),
+    // rec_idx (beside rec_pts, which carries the poison), edge_idx / surf_idx and d_sidx (handed to callers as indices),
+    // unit_span (the compaction's source positions), ring_ebase / ring_sbase (its destinations), cum16 and hole_desc (the
+    // holes form's loads), chunk_base, scan_geom, the entry lists (slow, defer, redo, fall-back, long) and long_work
+    // (ring_long_kernel's workspace, indices among its words).
+  }
   if (e == hipSuccess) {
     // everything a batch's kernels add to or OR into starts clean (and is left clean by the batch before, run_batch); the
     // tables every route writes before anyone reads them start at zero for the readers of a context that has run nothing

@@ -2337,8 +2337,10 @@ __global__ __launch_bounds__(256) void feature_compact_kernel(
       eb = b + e;
       fb = b + f;
       if (slot == max_rings - 1u) {
-        // (this ring's own totals: the sum of its units' counts, already here)
-        uint32_t oe = n_ring != 0u || by_ring ? ne_k : 0u, of = n_ring != 0u || by_ring ? ns_k : 0u;
+        // (this ring's own totals: the sum of its units' counts, already here -- for a ring that has points.  An empty slot's
+        // unit tables are nobody's: a holes scan's ring without a valid return has only dead units, which write nothing, and
+        // what the tables hold is an earlier batch's.  A plain organised scan has C > 0 points in every slot.)
+        uint32_t oe = n_ring != 0u ? ne_k : 0u, of = n_ring != 0u ? ns_k : 0u;
         oe = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_sum(oe), 63);
         of = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_sum(of), 63);
         if (lane == 0) {

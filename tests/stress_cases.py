@@ -75,9 +75,11 @@ def run_case(case, rng):
         want.append(w)
     try:
         for rep in range(2):                       # the second call may take another route (order pre-pass, path choice)
-            got = f.extract_batch(clouds)
-            for i in range(len(clouds)):
-                assert_scan_equal(got[i], want[i], "case %d: %dx%d P%d B%d %s rep%d scan%d seed%d" % (
+            # (the two clouds trade places between calls: no index sees the content it had in the batch before)
+            which = [rep % 2, 1 - rep % 2]
+            got = f.extract_batch([clouds[i] for i in which])
+            for k, i in enumerate(which):
+                assert_scan_equal(got[k], want[i], "case %d: %dx%d P%d B%d %s rep%d scan%d seed%d" % (
                     case, rings, cols, hp.padding, hp.n_blocks, order, rep, i, seed))
     finally:
         f.close()
@@ -94,9 +96,19 @@ def run_zeros_case(case, rng, rings, cols, hp, clouds, zeros, seed, exact_cap):
             lo = int(rng.integers(0, cols))
             width = int(rng.integers(1, max(2, cols // 3)))
             z |= (np.arange(len(c)) // rings >= lo) & (np.arange(len(c)) // rings < lo + width) & (rng.uniform(0.0, 1.0, len(c)) < 0.9)
+        masks.append(z)
+    # a third of the draws: one of the two clouds loses every return of a ring (the first, the last or any): a slot with
+    # returns at one index in one batch and without them in the next
+    gone = ""
+    if rng.integers(0, 3) == 0:
+        i = int(rng.integers(0, 2))
+        pick = int(rng.integers(0, 3))
+        r = 0 if pick == 0 else (rings - 1 if pick == 1 else int(rng.integers(0, rings)))
+        masks[i] = masks[i] | (clouds[i]["ring"] == r)
+        gone = " ring%d gone in scan%d" % (r, i)
+    for c, z in zip(clouds, masks):
         for f in ("x", "y", "z"):
             c[f][z] = 0.0
-        masks.append(z)
     import os
     by_scan = bool(rng.integers(0, 2))             # the count pass of large batches (one workgroup per scan), pinned on for these two scans
     if by_scan:
@@ -117,10 +129,11 @@ def run_zeros_case(case, rng, rings, cols, hp, clouds, zeros, seed, exact_cap):
         want.append(w)
     try:
         for rep in range(3):                       # (the route follows the report: plain form, holes form, the bucketing route)
-            got = f.extract_batch(clouds)
-            for i in range(len(clouds)):
-                assert_filtered_equal(got[i], want[i], keeps[i], masks[i], "case %d: %dx%d P%d B%d zeros %.2f%s%s rep%d scan%d seed%d[ties]" % (
-                    case, rings, cols, hp.padding, hp.n_blocks, fraction, " gap" if gap else "", " hinted" if hinted else "", rep, i, seed))
+            which = [rep % 2, 1 - rep % 2]         # (the clouds trade places between calls, as in run_case)
+            got = f.extract_batch([clouds[i] for i in which])
+            for k, i in enumerate(which):
+                assert_filtered_equal(got[k], want[i], keeps[i], masks[i], "case %d: %dx%d P%d B%d zeros %.2f%s%s%s rep%d scan%d seed%d[ties]" % (
+                    case, rings, cols, hp.padding, hp.n_blocks, fraction, " gap" if gap else "", " hinted" if hinted else "", gone, rep, i, seed))
     finally:
         f.close()
     return "zeros"

@@ -206,8 +206,10 @@ def test_alignment_texts_and_null_arguments(lib):
 
 def test_the_shipped_library_reads_no_debug_switch(lib):
     """The LFX_DEBUG_* switches (route pins, span variants, ablation flags) and the RCCL override exist in the test-hooks
-    build only (liblfx_testhooks.so, -DLFX_TEST_HOOKS): the shipped library does not even hold their names."""
+    build only (liblfx_testhooks.so, -DLFX_TEST_HOOKS): the shipped library does not even hold their names.  The poison
+    switch of the workspace tests (tests/test_stale_state_gpu.py) is one of them."""
     data = open(LB.LIB_PATH, "rb").read()
-    assert b"LFX_DEBUG_" not in data and b"LFX_RCCL_LIB" not in data
+    assert b"LFX_DEBUG_" not in data and b"LFX_RCCL_LIB" not in data and b"POISON" not in data
     hooks = open(LB.HOOKS_LIB_PATH, "rb").read()
     assert b"LFX_DEBUG_FUSED" in hooks and b"LFX_RCCL_LIB" in hooks
+    assert b"LFX_DEBUG_POISON" in hooks
