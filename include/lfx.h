@@ -504,6 +504,79 @@ int lfx_localize_host(lfx_ctx *ctx, const lfx_map *edge_map, const lfx_map *surf
                       float surface_leaf, const float *edge_points, uint32_t n_edge, const float *surface_points,
                       uint32_t n_surface, const double initial_pose[12], lfx_align_result *result, void *stream);
 
+/* --- scan-to-local-map odometry (the odometry row) -------------------------------------------------------- */
+/* Odometry<PoseUpdater, EdgeSurfaceMap, EdgeSurfaceScan> (localization/include/lidar_feature_localization/odometry.hpp:52-63)
+ * over EdgeSurfaceMap (edge_surface_map.hpp:38-76: two RecentScans, recent_scans.hpp:56-88), every cloud on the device.
+ * Update(scan): no scan added yet -> add the scan at the current pose; else align it against the merged last n_local_scans
+ * scans (GetRecent) from the current pose and take result.pose whatever the code, then add it transformed by that pose.
+ * The alignment is the problem Localizer::Update runs (lfx_localize_batch): edge rows against the window's edge map,
+ * surface rows of Downsample(scan_surface, surface_leaf) against the window's surface map, Optimizer::Run with
+ * n_neighbors / max_iter.  DEFINED DEVIATION: where a window map holds fewer than n_neighbors points (the reference reads
+ * nanoflann's uninitialised output there) the scan is not aligned: aligned = 0, the pose is carried over, the scan is added.
+ * The store: one linear device buffer per cloud, scans in insertion order, the window a contiguous suffix (so the map's
+ * "lower index" tie order is MergeClouds order); everything is kept while the capacity allows (GetAll); when the next scan
+ * would not fit, the scans older than the window are discarded (the window moved to the front); a scan that does not fit
+ * even then fails the call with pose, store and counts unchanged.  Added clouds hold the raw scan (not downsampled),
+ * transformed as pcl::transformPointCloud with an Affine3d does: each coordinate ((r0*x + r1*y) + r2*z) + t in double,
+ * rounded once to float, the 4th float of a record copied.  An odometry belongs to the device of the context that made it;
+ * it leaves the context's batch results as they were.  Poses: [R | t] row-major 3 x 4 doubles (point_to_map).
+ * Waits: the results and the pose are final when a call returns (the alignment waits for itself); the scan's addition to
+ * the store may still be queued on `stream` -- read the store after `stream`, and keep a caller's device clouds until
+ * `stream` has passed the call.  The next call, or the next window rebuild, waits for it where nothing has since. */
+#define LFX_ALIGN_NOT_RUN 6        /* odometry: the scan was not aligned (first scan, or a window map under n_neighbors points) */
+typedef struct lfx_odometry lfx_odometry;
+typedef struct lfx_odometry_config {
+  uint32_t n_local_scans;          /* GetRecent(n): 7 in app/odometry.cpp; >= 1 */
+  uint32_t n_neighbors;            /* N_NEIGHBORS: 15; in [3, 16] */
+  int32_t max_iter;                /* Optimizer's default: 20; >= 1 */
+  float surface_leaf;              /* Downsample leaf of the surface rows: 1.0 */
+  float edge_cell, surface_cell;   /* grid cell of the window maps (0: no grid), as lfx_map_create */
+  uint64_t edge_capacity_points, surface_capacity_points;   /* the device store, records of 4 floats; >= 1 */
+  double initial_pose[12];         /* Odometry's pose_ before the first scan: identity */
+} lfx_odometry_config;
+/* n_local_scans 7, n_neighbors 15, max_iter 20, surface_leaf 1.0, cells 1.0, capacities 2^22 points, identity */
+void lfx_odometry_default_config(lfx_odometry_config *config);
+typedef struct lfx_odometry_result {
+  lfx_align_result align;          /* what Optimizer::Run gave; not aligned: the carried pose, iteration 0, LFX_ALIGN_NOT_RUN */
+  uint32_t n_edge_map, n_surface_map;   /* window sizes the scan was aligned against (0, 0 for the first scan) */
+  int32_t aligned;                 /* 0: first scan, or a window map with fewer than n_neighbors points */
+} lfx_odometry_result;
+typedef struct lfx_odometry_store_view {
+  uint32_t n_scans;                /* scans retained in the store (GetAll) */
+  uint32_t n_window_scans;         /* the last min(n_local_scans, n_scans) of them (GetRecent) */
+  uint64_t n_added;                /* scans added since create */
+  uint64_t dropped_scans;          /* scans discarded to make room */
+  uint64_t compactions;            /* times the window was moved to the front of the store */
+  const float *edge_points;        /* device: the retained transformed edge clouds, n_edge records of 4 floats */
+  const float *surface_points;     /* device: the same for the surface clouds */
+  uint64_t n_edge, n_surface;
+  const float *edge_window;        /* device: the suffix the next scan is aligned against (GetRecent) */
+  const float *surface_window;
+  uint32_t n_edge_window, n_surface_window;
+  const uint32_t *edge_offsets;    /* host [n_scans + 1]: first record of every retained scan; valid until the next call */
+  const uint32_t *surface_offsets;
+  double pose[12];                 /* CurrentPose */
+} lfx_odometry_store_view;
+/* Allocates the store and the window maps' first buffers; synchronous. */
+int lfx_odometry_create(lfx_ctx *ctx, const lfx_odometry_config *config, lfx_odometry **out);
+void lfx_odometry_destroy(lfx_odometry *odometry);
+/* Odometry::Update for every scan of the last device batch, in batch order (n_scans = scans of the last batch, sizes
+ * results[n]).  The batch's surface clouds are downsampled once up front, and their counts read in one wait. */
+int lfx_odometry_update_batch(lfx_ctx *ctx, lfx_odometry *odometry, uint32_t n_scans, lfx_odometry_result *results, void *stream);
+/* Odometry::Update for one scan whose clouds (records of 4 floats) are on the device. */
+int lfx_odometry_update(lfx_ctx *ctx, lfx_odometry *odometry, const float *d_edge, uint32_t n_edge, const float *d_surface,
+                        uint32_t n_surface, lfx_odometry_result *result, void *stream);
+/* The same for clouds on the host (scan_edge / scan_surface as a subscriber receives them): staged through a device buffer
+ * of the odometry's own, grown when a scan needs more. */
+int lfx_odometry_update_host(lfx_ctx *ctx, lfx_odometry *odometry, const float *edge, uint32_t n_edge, const float *surface,
+                             uint32_t n_surface, lfx_odometry_result *result, void *stream);
+/* EdgeSurfaceMap::Add with a caller-given pose (poses from elsewhere); the current pose is left as it is.  Queued on `stream`. */
+int lfx_odometry_add(lfx_ctx *ctx, lfx_odometry *odometry, const double pose[12], const float *d_edge, uint32_t n_edge,
+                     const float *d_surface, uint32_t n_surface, void *stream);
+int lfx_odometry_pose(const lfx_odometry *odometry, double pose[12]);   /* CurrentPose */
+/* The store (GetAll), the window (GetRecent), per-scan offsets and what was dropped. */
+int lfx_odometry_view(const lfx_odometry *odometry, lfx_odometry_store_view *view);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

@@ -251,5 +251,62 @@ private:
   bool initialized_ = false;
 };
 
+// Scan-to-local-map odometry: Odometry<PoseUpdater, EdgeSurfaceMap, EdgeSurfaceScan> of the reference's localization package
+// (odometry.hpp:43-71; the node that would run it, OdometrySubscriber, subscriber.hpp:192-239) -- Update(scan) aligns the
+// scan against the last n_local_scans scans from the previous pose and adds it; CurrentPose().  The store and the window
+// maps live on the device of `fx`, which must outlive the odometry.  Poses are [R | t], row-major 3 x 4.
+class Odometry
+{
+public:
+  static lfx_odometry_config DefaultConfig() {lfx_odometry_config c; lfx_odometry_default_config(&c); return c;}
+  explicit Odometry(const FeatureExtraction & fx, const lfx_odometry_config & config = DefaultConfig())
+  : ctx_(fx.handle())
+  {
+    const int rc = lfx_odometry_create(ctx_, &config, &odometry_);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  ~Odometry() {lfx_odometry_destroy(odometry_);}
+  Odometry(const Odometry &) = delete;
+  Odometry & operator=(const Odometry &) = delete;
+
+  // Update with every scan the FeatureExtraction was last given, in order (their clouds are still on the device)
+  const std::vector<lfx_odometry_result> & Update()
+  {
+    lfx_device_view view{};
+    int rc = lfx_device_results(ctx_, &view);
+    if (rc == LFX_OK) {
+      results_.assign(view.batch, lfx_odometry_result{});
+      rc = lfx_odometry_update_batch(ctx_, odometry_, view.batch, results_.data(), nullptr);
+    }
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_;
+  }
+  // Update with clouds received from elsewhere (scan_edge / scan_surface as published: 4 floats per point)
+  const lfx_odometry_result & Update(const float * edge, std::uint32_t n_edge, const float * surface, std::uint32_t n_surface)
+  {
+    results_.assign(1, lfx_odometry_result{});
+    const int rc = lfx_odometry_update_host(ctx_, odometry_, edge, n_edge, surface, n_surface, results_.data(), nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_[0];
+  }
+  std::vector<double> CurrentPose() const
+  {
+    std::vector<double> pose(12);
+    lfx_odometry_pose(odometry_, pose.data());
+    return pose;
+  }
+  lfx_odometry_store_view View() const
+  {
+    lfx_odometry_store_view v{};
+    lfx_odometry_view(odometry_, &v);
+    return v;
+  }
+
+private:
+  lfx_ctx * ctx_;
+  lfx_odometry * odometry_ = nullptr;
+  std::vector<lfx_odometry_result> results_;
+};
+
 }  // namespace lfx
 #endif  // LFX_HPP_

@@ -80,6 +80,25 @@ class AlignResult(C.Structure):
                 ("code", C.c_int32)]
 
 
+class OdometryConfig(C.Structure):
+    """lfx_odometry_config (EdgeSurfaceMap(n_local_scans) + the problem Localizer::Update runs)."""
+    _fields_ = [("n_local_scans", C.c_uint32), ("n_neighbors", C.c_uint32), ("max_iter", C.c_int32), ("surface_leaf", C.c_float),
+                ("edge_cell", C.c_float), ("surface_cell", C.c_float), ("edge_capacity_points", C.c_uint64),
+                ("surface_capacity_points", C.c_uint64), ("initial_pose", C.c_double * 12)]
+
+
+class OdometryResult(C.Structure):
+    _fields_ = [("align", AlignResult), ("n_edge_map", C.c_uint32), ("n_surface_map", C.c_uint32), ("aligned", C.c_int32)]
+
+
+class OdometryStoreView(C.Structure):
+    _fields_ = [("n_scans", C.c_uint32), ("n_window_scans", C.c_uint32), ("n_added", C.c_uint64), ("dropped_scans", C.c_uint64),
+                ("compactions", C.c_uint64), ("edge_points", C.c_void_p), ("surface_points", C.c_void_p), ("n_edge", C.c_uint64),
+                ("n_surface", C.c_uint64), ("edge_window", C.c_void_p), ("surface_window", C.c_void_p), ("n_edge_window", C.c_uint32),
+                ("n_surface_window", C.c_uint32), ("edge_offsets", C.POINTER(C.c_uint32)), ("surface_offsets", C.POINTER(C.c_uint32)),
+                ("pose", C.c_double * 12)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -95,6 +114,8 @@ EXPORTS = [
     "lfx_map_create", "lfx_map_create_host", "lfx_map_destroy", "lfx_map_info", "lfx_map_nearest",
     "lfx_scan_to_map_residuals", "lfx_edge_residuals", "lfx_align_message", "lfx_scan_to_map_align", "lfx_align_point_pairs",
     "lfx_localize_batch", "lfx_localize_host",
+    "lfx_odometry_default_config", "lfx_odometry_create", "lfx_odometry_destroy", "lfx_odometry_update_batch", "lfx_odometry_update",
+    "lfx_odometry_update_host", "lfx_odometry_add", "lfx_odometry_pose", "lfx_odometry_view",
     "lfx_layout_from_fields", "lfx_pack_xyz", "lfx_pack_xyz12", "lfx_pack_colored", "lfx_pack_features", "lfx_download_scan", "lfx_stage_ring", "lfx_stage_convolution1d",
     "lfx_stage_ring_projection", "lfx_label_to_color", "lfx_color_points_by_label", "lfx_set_profiling", "lfx_set_profiling_interval", "lfx_kernel_times", "lfx_kernel_name",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
@@ -176,6 +197,17 @@ def load(test_hooks=False):
     L.lfx_localize_batch.argtypes = [vp, vp, vp, u32, i32, C.c_float, u32, pd, pres, vp]
     L.lfx_localize_host.argtypes = [vp, vp, vp, u32, i32, C.c_float, vp, u32, vp, u32, pd, pres, vp]
     L.lfx_downsample_surface.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.lfx_odometry_default_config.argtypes = [C.POINTER(OdometryConfig)]
+    L.lfx_odometry_default_config.restype = None
+    L.lfx_odometry_create.argtypes = [vp, C.POINTER(OdometryConfig), C.POINTER(vp)]
+    L.lfx_odometry_destroy.argtypes = [vp]
+    L.lfx_odometry_destroy.restype = None
+    L.lfx_odometry_update_batch.argtypes = [vp, vp, u32, C.POINTER(OdometryResult), vp]
+    L.lfx_odometry_update.argtypes = [vp, vp, vp, u32, vp, u32, C.POINTER(OdometryResult), vp]
+    L.lfx_odometry_update_host.argtypes = [vp, vp, vp, u32, vp, u32, C.POINTER(OdometryResult), vp]
+    L.lfx_odometry_add.argtypes = [vp, vp, pd, vp, u32, vp, u32, vp]
+    L.lfx_odometry_pose.argtypes = [vp, pd]
+    L.lfx_odometry_view.argtypes = [vp, C.POINTER(OdometryStoreView)]
     L.lfx_gather.argtypes = [vp, vp, i32, vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, vp]
     L.lfx_layout_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Layout)]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]

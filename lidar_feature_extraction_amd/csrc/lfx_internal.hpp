@@ -88,6 +88,17 @@ struct DevBuf
   }
 };
 
+// a device buffer that holds at least `need` elements, grown by half again when it must grow (its contents are not kept)
+template<typename T>
+hipError_t hold(DevBuf<T> & b, size_t need)
+{
+  if (b.p && b.n >= need) {return hipSuccess;}
+  b.release();
+  const hipError_t e = b.alloc(need + need / 2);
+  if (e != hipSuccess) {b.p = nullptr; b.n = 0;}
+  return e;
+}
+
 struct HostScan          // the per-ring lists of one scan (the large arrays live in the pinned result block)
 {
   std::vector<uint8_t> ring_status;
@@ -286,5 +297,19 @@ int voxel_downsample(
   lfx_ctx * c, const float * d_points, const uint32_t * d_begin, const uint32_t * d_count, uint32_t count_stride,
   uint32_t n_clouds, size_t total_points, float leaf, float * d_out, uint32_t * d_out_count, uint32_t * d_status, void * stream,
   bool unfiltered, const uint32_t * d_other_count, uint32_t * lengths);
+
+// lfx_localize.hip: a map rebuilt in place (lfx_odometry.hip's window maps) and the optimizer over clouds
+lfx_map * map_new(int device);
+uint32_t map_points(const lfx_map * m);
+int map_rebuild(lfx_ctx * c, lfx_map * m, const float * d_points, uint32_t n_points, float cell_size, const double lo[3],
+  const double hi[3], hipStream_t st);
+int align_clouds(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,
+  const float * d_edge_points, const uint32_t * d_edge_begin, const uint32_t * d_edge_count, uint32_t edge_count_stride,
+  uint32_t max_edge_points_per_cloud, size_t total_edge_points,
+  const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
+  uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
+  uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
+  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin);
 
 }  // namespace lfx_host

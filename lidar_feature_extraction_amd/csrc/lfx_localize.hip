@@ -13,10 +13,28 @@ struct lfx_map
   DevBuf<uint32_t> start;                // first point of every cell, + 1
   lfx::MapIndex index{};
   float cell = 0.f;
+  DevBuf<uint32_t> cell_count, partial;  // map_rebuild only: the build's scratch, kept between rebuilds
 };
 
 namespace
 {
+// the grid of a map over [lo, hi]: cubic cells of the asked size, grown until the grid has at most 2^25 cells
+void grid_of(const double lo[3], const double hi[3], float cell_size, double & h, int dims[3])
+{
+  h = (double)cell_size;
+  const double limit = 33554432.;
+  for (;;) {
+    double cells = 1.;
+    for (int a = 0; a < 3; a++) {
+      const double na = std::floor((hi[a] - lo[a]) / h) + 1.;
+      dims[a] = na > 2147483647. ? 2147483647 : (int)na;
+      cells *= na;
+    }
+    if (cells <= limit) {break;}
+    h *= std::max(1.05, std::cbrt(cells / limit));
+  }
+}
+
 void launch_rows(bool surface, const lfx::MapIndex & mi, const lfx::MapPose & P, uint32_t k, const float * d_points,
   const uint32_t * d_begin, const uint32_t * d_count, uint32_t count_stride, uint32_t n_clouds, uint32_t longest, double * d_residual,
   double * d_jacobian, const lfx::AlignState * states, hipStream_t st, const uint32_t * d_row_begin = nullptr)
@@ -83,20 +101,9 @@ int lfx_map_create(lfx_ctx * c, const float * d_points, uint32_t n_points, float
   for (int a = 0; a < 3; a++) {
     if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {return give_up(LFX_ERR_INVALID_ARGUMENT, "the map holds a point that is not finite");}
   }
-  // the grid: cubic cells of the asked size, grown until the grid has at most 2^25 cells
-  double h = (double)cell_size;
-  const double limit = 33554432.;
+  double h;
   int dims[3];
-  for (;;) {
-    double cells = 1.;
-    for (int a = 0; a < 3; a++) {
-      const double na = std::floor((hi[a] - lo[a]) / h) + 1.;
-      dims[a] = na > 2147483647. ? 2147483647 : (int)na;
-      cells *= na;
-    }
-    if (cells <= limit) {break;}
-    h *= std::max(1.05, std::cbrt(cells / limit));
-  }
+  grid_of(lo, hi, cell_size, h, dims);
   mi.ox = lo[0]; mi.oy = lo[1]; mi.oz = lo[2]; mi.h = h; mi.inv_h = 1. / h; mi.nx = dims[0]; mi.ny = dims[1]; mi.nz = dims[2];
   m->cell = (float)h;
   const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
@@ -129,7 +136,7 @@ void lfx_map_destroy(lfx_map * m)
 {
   if (!m) {return;}
   (void)hipSetDevice(m->device);
-  m->pts.release(); m->start.release();
+  m->pts.release(); m->start.release(); m->cell_count.release(); m->partial.release();
   delete m;
 }
 
@@ -180,6 +187,56 @@ int lfx_map_nearest(
 }
 
 }  // extern "C"
+
+namespace lfx_host
+{
+lfx_map * map_new(int device)
+{
+  lfx_map * m = new (std::nothrow) lfx_map();
+  if (m) {m->device = device;}
+  return m;
+}
+
+uint32_t map_points(const lfx_map * m) {return m->index.n;}
+
+// The index of lfx_map_create over n_points records at d_points, rebuilt in place: the map keeps its buffers (grown by half
+// again when they must grow), the bounds come from the caller ([lo, hi] of the points, as map_bounds_kernel would find
+// them), nothing is waited for.  The same grid, the same cells, the same kernels as lfx_map_create; n_points >= 1.
+int map_rebuild(lfx_ctx * c, lfx_map * m, const float * d_points, uint32_t n_points, float cell_size, const double lo[3],
+  const double hi[3], hipStream_t st)
+{
+  lfx::MapIndex & mi = m->index;
+  LFX_HIP(c, hold(m->pts, n_points));
+  mi.pts = m->pts.p; mi.start = nullptr; mi.n = n_points;
+  mi.ox = mi.oy = mi.oz = 0.; mi.h = 0.; mi.inv_h = 0.; mi.nx = mi.ny = mi.nz = 1;
+  const float4 * src = reinterpret_cast<const float4 *>(d_points);
+  if (cell_size == 0.f) {
+    LFX_HIP(c, hipMemcpyAsync(m->pts.p, src, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToDevice, st));
+    return LFX_OK;
+  }
+  double h;
+  int dims[3];
+  grid_of(lo, hi, cell_size, h, dims);
+  const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
+  const uint32_t n_blocks = (uint32_t)((cells + lfx::kScanItems - 1) / lfx::kScanItems);
+  LFX_HIP(c, hold(m->start, cells + 1));
+  LFX_HIP(c, hold(m->cell_count, cells));
+  LFX_HIP(c, hold(m->partial, (size_t)n_blocks + 1));
+  mi.ox = lo[0]; mi.oy = lo[1]; mi.oz = lo[2]; mi.h = h; mi.inv_h = 1. / h; mi.nx = dims[0]; mi.ny = dims[1]; mi.nz = dims[2];
+  m->cell = (float)h;
+  LFX_HIP(c, hipMemsetAsync(m->cell_count.p, 0, cells * sizeof(uint32_t), st));
+  const dim3 per_point((n_points + 255u) / 256u);
+  hipLaunchKernelGGL(lfx::map_count_kernel, per_point, dim3(256), 0, st, mi, src, m->cell_count.p);
+  hipLaunchKernelGGL(lfx::cell_block_sum_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, m->cell_count.p, cells, m->partial.p);
+  hipLaunchKernelGGL(lfx::cell_partial_scan_kernel, dim3(1), dim3(lfx::kScanThreads), 0, st, m->partial.p, n_blocks);
+  hipLaunchKernelGGL(lfx::cell_start_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, m->cell_count.p, cells, m->partial.p,
+    m->start.p, n_points);
+  hipLaunchKernelGGL(lfx::map_scatter_kernel, per_point, dim3(256), 0, st, mi, src, m->cell_count.p, m->start.p, m->pts.p);
+  LFX_HIP(c, hipGetLastError());
+  mi.start = m->start.p;
+  return LFX_OK;
+}
+}  // namespace lfx_host
 
 // ---------------------------------------------------------------------------- scan-to-map residuals
 extern "C" {
@@ -399,11 +456,14 @@ const char * lfx_align_message(int code)
     case LFX_ALIGN_MAX_ITERATION: return "The iteration reached the maximum value";
     case LFX_ALIGN_EMPTY_INPUT: return "The input data is empty";
     case LFX_ALIGN_NO_PLANE: return "No surface neighbourhood spans a plane";
+    case LFX_ALIGN_NOT_RUN: return "The scan was not aligned";
     default: return "unknown";
   }
 }
 
-namespace
+}  // extern "C"
+
+namespace lfx_host
 {
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,
@@ -437,7 +497,9 @@ int align_clouds(
   pr.rbegin3 = d_edge_row_begin; pr.rbegin1 = d_surface_row_begin;
   return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream));
 }
-}  // namespace
+}  // namespace lfx_host
+
+extern "C" {
 
 int lfx_scan_to_map_align(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,

@@ -1,0 +1,442 @@
+// lfx_odometry.hip -- scan-to-local-map odometry: Odometry::Update (odometry.hpp:52-63) over EdgeSurfaceMap
+// (edge_surface_map.hpp:38-76) with every cloud on the device (lfx_kernels_odometry.hpp).  The alignment is
+// lfx_localize_batch's (align_clouds, lfx_localize.hip); the window maps are lfx_map indexes rebuilt in place.
+#include "lfx_internal.hpp"
+#include "lfx_kernels_odometry.hpp"
+
+#include <algorithm>
+#include <array>
+
+using namespace lfx_host;
+
+namespace
+{
+struct Box                                   // bounds of one cloud of one scan (the store's coordinates)
+{
+  double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+  bool any = false;
+};
+}  // namespace
+
+struct lfx_odometry
+{
+  int device = 0;
+  lfx_odometry_config cfg{};
+  double pose[12] = {};                      // CurrentPose
+  // the store: transformed clouds, scans in insertion order; off_*[j] = first record of retained scan j, [n_scans] = end
+  DevBuf<float4> edge, surface;
+  std::vector<uint32_t> off_e{0u}, off_s{0u};
+  std::vector<std::array<Box, 2>> box;       // per retained scan: edge, surface
+  uint64_t added = 0, dropped = 0, compactions = 0;
+  lfx_map * emap = nullptr, * smap = nullptr;   // the window maps (map_rebuild)
+  DevBuf<uint32_t> bounds;                   // [2][6]: what odometry_append_kernel reduces into
+  // The work a call leaves queued behind it (the last append, the bounds' copy to the pinned block) is waited for by the
+  // next rebuild, or by the next call before it touches the scratch: `tail` is recorded behind it
+  hipEvent_t tail = nullptr;
+  bool tail_pending = false, bounds_queued = false;
+  DevBuf<uint32_t> words;                    // [0] 0 (begin / row begin of a single cloud), [1] n_edge, [2] n_surface, [3] downsampled, [4] status
+  DevBuf<float> down;                        // downsampled surface clouds of a batch, then their counts and statuses
+  DevBuf<float4> staged;                     // lfx_odometry_update_host: the two clouds, edge first
+  PinnedBuf pinned;                          // [12] bounds | [8] words | [batch][4] scan_info | [batch][2] lengths
+  uint32_t n_scans() const {return (uint32_t)box.size();}
+};
+
+namespace
+{
+constexpr size_t kPinBounds = 0, kPinWords = 12, kPinInfo = 20;
+
+double decode(uint32_t u)                     // odo_float_order back to the float it encodes
+{
+  const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+  float f;
+  std::memcpy(&f, &b, 4);
+  return (double)f;
+}
+
+uint32_t * pinned_words(lfx_odometry * o) {return reinterpret_cast<uint32_t *>(o->pinned.p);}
+
+// What lets a scan of (ne, ns) points in: 0 as it is, 1 after the scans older than the window are discarded, -1 not at all
+int room(const lfx_odometry * o, uint64_t ne, uint64_t ns)
+{
+  const uint32_t n = o->n_scans();
+  if (o->off_e[n] + ne <= o->cfg.edge_capacity_points && o->off_s[n] + ns <= o->cfg.surface_capacity_points) {return 0;}
+  const uint32_t w = std::min(o->cfg.n_local_scans, n);
+  const uint64_t ke = o->off_e[n] - o->off_e[n - w], ks = o->off_s[n] - o->off_s[n - w];
+  return (ke + ne <= o->cfg.edge_capacity_points && ks + ns <= o->cfg.surface_capacity_points) ? 1 : -1;
+}
+
+int no_room(lfx_ctx * c, uint64_t ne, uint64_t ns)
+{
+  return fail(c, LFX_ERR_INVALID_ARGUMENT, "the scan (" + std::to_string(ne) + " edge, " + std::to_string(ns) +
+           " surface points) does not fit the odometry's store beside its window");
+}
+
+// the window (the last n_local_scans scans) moved to the front of both stores; the scans before it are discarded.  Moved
+// in pieces no longer than the distance moved, so that no copy reads what another one of the same move writes.
+int compact(lfx_ctx * c, lfx_odometry * o, hipStream_t st)
+{
+  const uint32_t n = o->n_scans(), w = std::min(o->cfg.n_local_scans, n), gone = n - w;
+  auto move = [&](float4 * p, size_t from, size_t len) -> hipError_t {
+      for (size_t at = 0; from && at < len; at += from) {
+        const hipError_t e = hipMemcpyAsync(p + at, p + from + at, sizeof(float4) * std::min(from, len - at), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {return e;}
+      }
+      return hipSuccess;
+    };
+  const uint32_t ae = o->off_e[gone], as = o->off_s[gone];
+  LFX_HIP(c, move(o->edge.p, ae, o->off_e[n] - ae));
+  LFX_HIP(c, move(o->surface.p, as, o->off_s[n] - as));
+  o->off_e.erase(o->off_e.begin(), o->off_e.begin() + gone);
+  o->off_s.erase(o->off_s.begin(), o->off_s.begin() + gone);
+  for (auto & v : o->off_e) {v -= ae;}
+  for (auto & v : o->off_s) {v -= as;}
+  o->box.erase(o->box.begin(), o->box.begin() + gone);
+  o->dropped += gone;
+  o->compactions++;
+  return LFX_OK;
+}
+
+// the previous call's tail waited for, the last appended scan's bounds into its boxes (a wait only where nothing has
+// waited since)
+int settle(lfx_ctx * c, lfx_odometry * o)
+{
+  if (!o->tail_pending) {return LFX_OK;}
+  LFX_HIP(c, hipEventSynchronize(o->tail));
+  o->tail_pending = false;
+  if (!o->bounds_queued) {return LFX_OK;}
+  o->bounds_queued = false;
+  const uint32_t * h = pinned_words(o) + kPinBounds;
+  std::array<Box, 2> & b = o->box.back();
+  for (int k = 0; k < 2; k++) {
+    const uint32_t * v = h + 6 * k;
+    b[k].any = v[3] != 0u;
+    for (int a = 0; a < 3 && b[k].any; a++) {b[k].lo[a] = decode(~v[a]); b[k].hi[a] = decode(v[3 + a]);}
+  }
+  return LFX_OK;
+}
+
+// EdgeSurfaceMap::Add: both clouds transformed by `pose` behind the store's last scan (after a compaction where `how` says
+// so).  Nothing is waited for: the bounds are read by the next rebuild (settle)
+int append(lfx_ctx * c, lfx_odometry * o, int how, const double pose[12], const float4 * edge, uint32_t ne, const float4 * surface,
+  uint32_t ns, hipStream_t st)
+{
+  int rc = settle(c, o);                     // (the bounds table is about to be written again)
+  if (rc == LFX_OK && how == 1) {rc = compact(c, o, st);}
+  if (rc != LFX_OK) {return rc;}
+  const uint32_t n = o->n_scans(), at_e = o->off_e[n], at_s = o->off_s[n];
+  if (ne + ns) {
+    lfx::OdoPose P;
+    for (int i = 0; i < 12; i++) {P.m[i] = pose[i];}
+    const uint32_t ge = (ne + lfx::kAppendThreads - 1u) / lfx::kAppendThreads, gs = (ns + lfx::kAppendThreads - 1u) / lfx::kAppendThreads;
+    LFX_HIP(c, hipMemsetAsync(o->bounds.p, 0, 12 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(lfx::odometry_append_kernel, dim3(ge + gs), dim3(lfx::kAppendThreads), 0, st, P, edge, ne, surface, ns,
+      o->edge.p + at_e, o->surface.p + at_s, ge, o->bounds.p);
+    LFX_HIP(c, hipGetLastError());
+    LFX_HIP(c, hipMemcpyAsync(pinned_words(o) + kPinBounds, o->bounds.p, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
+  o->off_e.push_back(at_e + ne);
+  o->off_s.push_back(at_s + ns);
+  o->box.push_back(std::array<Box, 2>{});
+  LFX_HIP(c, hipEventRecord(o->tail, st));
+  o->tail_pending = true;
+  o->bounds_queued = ne + ns > 0;
+  o->added++;
+  return LFX_OK;
+}
+
+// one window map over the last w scans of a store
+int rebuild(lfx_ctx * c, lfx_odometry * o, int k, uint32_t w, hipStream_t st)
+{
+  const int rc = settle(c, o);
+  if (rc != LFX_OK) {return rc;}
+  const uint32_t n = o->n_scans();
+  const std::vector<uint32_t> & off = k ? o->off_s : o->off_e;
+  double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+  bool any = false;
+  for (uint32_t j = n - w; j < n; j++) {
+    const Box & b = o->box[j][k];
+    if (!b.any) {continue;}
+    for (int a = 0; a < 3; a++) {
+      lo[a] = any ? std::min(lo[a], b.lo[a]) : b.lo[a];
+      hi[a] = any ? std::max(hi[a], b.hi[a]) : b.hi[a];
+    }
+    any = true;
+  }
+  for (int a = 0; a < 3; a++) {
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the window holds a point that is not finite");}
+  }
+  const float4 * store = k ? o->surface.p : o->edge.p;
+  return map_rebuild(c, k ? o->smap : o->emap, reinterpret_cast<const float *>(store + off[n - w]), off[n] - off[n - w],
+           k ? o->cfg.surface_cell : o->cfg.edge_cell, lo, hi, st);
+}
+
+struct ScanIn                                // one scan as the append kernel and the alignment read it
+{
+  const float4 * edge = nullptr, * surface = nullptr;    // the raw clouds
+  uint32_t n_edge = 0, n_surface = 0;
+  const float * edge_points = nullptr;                   // the edge cloud as align_clouds addresses it
+  const uint32_t * edge_begin = nullptr, * edge_count = nullptr;
+  uint32_t edge_stride = 1;
+  const float * down_points = nullptr;                   // the downsampled surface cloud
+  const uint32_t * down_begin = nullptr, * down_count = nullptr;
+  uint32_t n_down = 0;
+};
+
+void not_aligned(const double pose[12], lfx_odometry_result * r)
+{
+  for (int i = 0; i < 12; i++) {r->align.pose[i] = pose[i];}
+  r->align.error = 0.; r->align.error_scale = 0.; r->align.iteration = 0; r->align.code = LFX_ALIGN_NOT_RUN;
+  r->aligned = 0;
+}
+
+// Odometry::Update for one scan
+int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result * result, hipStream_t st)
+{
+  const int how = room(o, in.n_edge, in.n_surface);
+  if (how < 0) {return no_room(c, in.n_edge, in.n_surface);}
+  lfx_odometry_result r{};
+  double pose[12];
+  std::memcpy(pose, o->pose, sizeof(pose));
+  const uint32_t n = o->n_scans(), w = std::min(o->cfg.n_local_scans, n), k = o->cfg.n_neighbors;
+  if (o->added == 0) {
+    not_aligned(pose, &r);                   // IsEmpty: the scan is added at the current pose
+  } else {
+    r.n_edge_map = o->off_e[n] - o->off_e[n - w];
+    r.n_surface_map = o->off_s[n] - o->off_s[n - w];
+    if (r.n_edge_map < k || r.n_surface_map < k) {
+      not_aligned(pose, &r);                 // (the reference would read nanoflann's uninitialised output)
+    } else {
+      int rc = rebuild(c, o, 0, w, st);
+      if (rc == LFX_OK) {rc = rebuild(c, o, 1, w, st);}
+      if (rc == LFX_OK) {
+        rc = align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_points, in.edge_begin, in.edge_count, in.edge_stride,
+          in.n_edge, in.n_edge, in.down_points, in.down_begin, in.down_count, 1, in.n_down, in.n_down, 1, o->pose, &r.align, st,
+          o->words.p, o->words.p);
+      }
+      if (rc != LFX_OK) {return rc;}
+      std::memcpy(pose, r.align.pose, sizeof(pose));    // pose_ = update(scan, pose_), whatever the code
+      r.aligned = 1;
+    }
+  }
+  const int rc = append(c, o, how, pose, in.edge, in.n_edge, in.surface, in.n_surface, st);
+  if (rc != LFX_OK) {return rc;}
+  std::memcpy(o->pose, pose, sizeof(pose));
+  *result = r;
+  return LFX_OK;
+}
+
+int check(lfx_ctx * c, const lfx_odometry * o)
+{
+  if (o->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the odometry lives on another device");}
+  return LFX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void lfx_odometry_default_config(lfx_odometry_config * cfg)
+{
+  if (!cfg) {return;}
+  *cfg = lfx_odometry_config{};
+  cfg->n_local_scans = 7;                    // app/odometry.cpp
+  cfg->n_neighbors = 15;                     // N_NEIGHBORS
+  cfg->max_iter = 20;                        // Optimizer's default
+  cfg->surface_leaf = 1.0f;
+  cfg->edge_cell = cfg->surface_cell = 1.0f;
+  cfg->edge_capacity_points = cfg->surface_capacity_points = (uint64_t)1 << 22;
+  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  std::memcpy(cfg->initial_pose, identity, sizeof(identity));
+}
+
+int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odometry ** out)
+{
+  if (!c || !cfg || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (cfg->n_local_scans == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_local_scans must be >= 1");}
+  if (cfg->n_neighbors < 3 || cfg->n_neighbors > 16) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [3, 16]");}
+  if (cfg->max_iter < 1) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be >= 1");}
+  if (!(cfg->surface_leaf > 0.f) || !std::isfinite(cfg->surface_leaf)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "surface_leaf must be > 0");}
+  if (!(cfg->edge_cell >= 0.f) || !std::isfinite(cfg->edge_cell) || !(cfg->surface_cell >= 0.f) || !std::isfinite(cfg->surface_cell)) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "edge_cell / surface_cell must be >= 0 (0: no grid)");
+  }
+  if (cfg->edge_capacity_points == 0 || cfg->surface_capacity_points == 0 || cfg->edge_capacity_points > 0xFFFFFFFFull ||
+    cfg->surface_capacity_points > 0xFFFFFFFFull)
+  {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "the store's capacities must be in [1, 2^32 - 1] points");
+  }
+  for (int i = 0; i < 12; i++) {
+    if (!std::isfinite(cfg->initial_pose[i])) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
+  }
+  LFX_HIP(c, hipSetDevice(c->device));
+  lfx_odometry * o = new (std::nothrow) lfx_odometry();
+  if (!o) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry");}
+  o->device = c->device;
+  o->cfg = *cfg;
+  std::memcpy(o->pose, cfg->initial_pose, sizeof(o->pose));
+  auto give_up = [&](int code, const std::string & why) {lfx_odometry_destroy(o); return fail(c, code, why);};
+  o->emap = map_new(c->device);
+  o->smap = map_new(c->device);
+  if (!o->emap || !o->smap) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the window maps");}
+  if (o->edge.alloc(cfg->edge_capacity_points) != hipSuccess) {o->edge.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the edge store");}
+  if (o->surface.alloc(cfg->surface_capacity_points) != hipSuccess) {o->surface.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the surface store");}
+  if (o->bounds.alloc(12) != hipSuccess) {o->bounds.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's bounds");}
+  if (o->words.alloc(8) != hipSuccess) {o->words.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's words");}
+  if (o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)std::max(c->max_batch, 1u))) != hipSuccess) {
+    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's pinned block");
+  }
+  if (hipEventCreateWithFlags(&o->tail, hipEventDisableTiming) != hipSuccess) {
+    o->tail = nullptr;
+    return give_up(LFX_ERR_HIP, "cannot create the odometry's event");
+  }
+  hipError_t e = hipMemset(o->words.p, 0, 8 * sizeof(uint32_t));
+  if (e == hipSuccess) {e = hipDeviceSynchronize();}
+  if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
+  *out = o;
+  return LFX_OK;
+}
+
+void lfx_odometry_destroy(lfx_odometry * o)
+{
+  if (!o) {return;}
+  (void)hipSetDevice(o->device);
+  if (o->tail) {(void)hipEventSynchronize(o->tail); (void)hipEventDestroy(o->tail);}
+  lfx_map_destroy(o->emap);
+  lfx_map_destroy(o->smap);
+  o->edge.release(); o->surface.release(); o->bounds.release(); o->words.release(); o->down.release(); o->staged.release();
+  o->pinned.release();
+  delete o;
+}
+
+int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, lfx_odometry_result * results, void * stream)
+{
+  if (!c || !o || !results) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
+  if (n_scans != c->last_batch) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
+             std::to_string(c->last_batch) + ")");
+  }
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t batch = c->last_batch;
+  const size_t total = c->h_scan_begin[batch];
+  if (hold(o->down, 4 * total + 2 * (size_t)batch) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");}
+  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
+  float * down = o->down.p;
+  uint32_t * down_count = reinterpret_cast<uint32_t *>(down + 4 * total), * down_status = down_count + batch;
+  uint32_t * info = pinned_words(o) + kPinInfo, * lengths = info + 4 * (size_t)batch;
+  void * d_lengths = nullptr;
+  LFX_HIP(c, hipHostGetDevicePointer(&d_lengths, lengths, 0));
+  // the batch's surface clouds downsampled once (as lfx_localize_batch does: a cloud PCL hands back unfiltered is copied),
+  // and every scan's counts: one wait for the whole batch
+  const int rc = voxel_downsample(c, reinterpret_cast<const float *>(c->surf_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoSurface, 4,
+    batch, total, o->cfg.surface_leaf, down, down_count, down_status, stream, true, c->scan_info.p + lfx::kInfoEdge,
+    static_cast<uint32_t *>(d_lengths));
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (uint32_t s = 0; s < batch; s++) {
+    ScanIn in;
+    const uint32_t b = c->h_scan_begin[s];
+    in.edge = c->edge_pts.p + b; in.n_edge = info[4 * s + lfx::kInfoEdge];
+    in.surface = c->surf_pts.p + b; in.n_surface = info[4 * s + lfx::kInfoSurface];
+    in.edge_points = reinterpret_cast<const float *>(c->edge_pts.p);
+    in.edge_begin = c->scan_begin.p + s; in.edge_count = c->scan_info.p + lfx::kInfoEdge + 4 * s; in.edge_stride = 4;
+    in.down_points = down; in.down_begin = c->scan_begin.p + s; in.down_count = down_count + s; in.n_down = lengths[2 * s + 1];
+    const int rc2 = step(c, o, in, results + s, st);
+    if (rc2 != LFX_OK) {return rc2;}
+  }
+  return LFX_OK;
+}
+
+int lfx_odometry_update(lfx_ctx * c, lfx_odometry * o, const float * d_edge, uint32_t n_edge, const float * d_surface,
+  uint32_t n_surface, lfx_odometry_result * result, void * stream)
+{
+  if (!c || !o || !result || (n_edge && !d_edge) || (n_surface && !d_surface)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hold(o->down, 4 * (size_t)n_surface + 4) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface cloud");}
+  // the words go out of the pinned block, which nothing writes again before this call's alignment has waited
+  uint32_t * words = pinned_words(o) + kPinWords;
+  words[0] = 0u; words[1] = n_edge; words[2] = n_surface; words[3] = 0u; words[4] = 0u;
+  LFX_HIP(c, hipMemcpyAsync(o->words.p, words, 5 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (n_surface) {
+    const int rc = voxel_downsample(c, d_surface, o->words.p, o->words.p + 2, 1, 1, n_surface, o->cfg.surface_leaf, o->down.p,
+      o->words.p + 3, o->words.p + 4, stream, true, o->words.p + 1, nullptr);
+    if (rc != LFX_OK) {return rc;}
+  }
+  // Nothing is waited for: the downsampled cloud's rows are sized by the cloud's own length (a bound; the kernels read the
+  // count on the device), as lfx_localize_batch sizes a few scans' rows
+  ScanIn in;
+  const float * any = o->down.p;                // (align_clouds wants a pointer for an empty cloud too)
+  in.edge = reinterpret_cast<const float4 *>(d_edge); in.n_edge = n_edge;
+  in.surface = reinterpret_cast<const float4 *>(d_surface); in.n_surface = n_surface;
+  in.edge_points = d_edge ? d_edge : any; in.edge_begin = o->words.p; in.edge_count = o->words.p + 1; in.edge_stride = 1;
+  in.down_points = o->down.p; in.down_begin = o->words.p; in.down_count = o->words.p + 3; in.n_down = n_surface;
+  return step(c, o, in, result, st);
+}
+
+int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, uint32_t n_edge, const float * surface,
+  uint32_t n_surface, lfx_odometry_result * result, void * stream)
+{
+  if (!c || !o || !result || (n_edge && !edge) || (n_surface && !surface)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hold(o->staged, (size_t)n_edge + n_surface + 1) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the scan's clouds");}
+  if (n_edge) {LFX_HIP(c, hipMemcpyAsync(o->staged.p, edge, sizeof(float4) * n_edge, hipMemcpyHostToDevice, st));}
+  if (n_surface) {LFX_HIP(c, hipMemcpyAsync(o->staged.p + n_edge, surface, sizeof(float4) * n_surface, hipMemcpyHostToDevice, st));}
+  return lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->staged.p), n_edge, reinterpret_cast<const float *>(o->staged.p + n_edge),
+           n_surface, result, stream);
+}
+
+int lfx_odometry_add(lfx_ctx * c, lfx_odometry * o, const double pose[12], const float * d_edge, uint32_t n_edge,
+  const float * d_surface, uint32_t n_surface, void * stream)
+{
+  if (!c || !o || !pose || (n_edge && !d_edge) || (n_surface && !d_surface)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int how = room(o, n_edge, n_surface);
+  if (how < 0) {return no_room(c, n_edge, n_surface);}
+  LFX_HIP(c, hipSetDevice(c->device));
+  return append(c, o, how, pose, reinterpret_cast<const float4 *>(d_edge), n_edge, reinterpret_cast<const float4 *>(d_surface), n_surface,
+           static_cast<hipStream_t>(stream));
+}
+
+int lfx_odometry_pose(const lfx_odometry * o, double pose[12])
+{
+  if (!o || !pose) {return LFX_ERR_INVALID_ARGUMENT;}
+  std::memcpy(pose, o->pose, sizeof(o->pose));
+  return LFX_OK;
+}
+
+int lfx_odometry_view(const lfx_odometry * o, lfx_odometry_store_view * v)
+{
+  if (!o || !v) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint32_t n = o->n_scans(), w = std::min(o->cfg.n_local_scans, n);
+  *v = lfx_odometry_store_view{};
+  v->n_scans = n;
+  v->n_window_scans = w;
+  v->n_added = o->added;
+  v->dropped_scans = o->dropped;
+  v->compactions = o->compactions;
+  v->edge_points = reinterpret_cast<const float *>(o->edge.p);
+  v->surface_points = reinterpret_cast<const float *>(o->surface.p);
+  v->n_edge = o->off_e[n];
+  v->n_surface = o->off_s[n];
+  v->edge_window = reinterpret_cast<const float *>(o->edge.p + o->off_e[n - w]);
+  v->surface_window = reinterpret_cast<const float *>(o->surface.p + o->off_s[n - w]);
+  v->n_edge_window = o->off_e[n] - o->off_e[n - w];
+  v->n_surface_window = o->off_s[n] - o->off_s[n - w];
+  v->edge_offsets = o->off_e.data();
+  v->surface_offsets = o->off_s.data();
+  std::memcpy(v->pose, o->pose, sizeof(o->pose));
+  return LFX_OK;
+}
+
+}  // extern "C"

@@ -283,6 +283,12 @@ class FeatureExtraction:
             C.c_void_p(int(stream))))
         return self._align_results(res)[0]
 
+    def odometry(self, **config):
+        """lfx_odometry_create: Odometry over EdgeSurfaceMap (odometry.hpp:52-63) on this context's device.  Keywords: the
+        fields of lfx_odometry_config (n_local_scans=7, n_neighbors=15, max_iter=20, surface_leaf=1.0, edge_cell=1.0,
+        surface_cell=1.0, edge_capacity_points, surface_capacity_points, initial_pose: 3 x 4)."""
+        return Odometry(self, **config)
+
     def set_ring_ids(self, ring_ids):
         """lfx_set_ring_ids: the sensor's ring ids for the device path (None: back to 0 .. max_rings-1)."""
         if ring_ids is None:
@@ -467,6 +473,98 @@ class ScanMap:
     def close(self):
         if self.handle:
             self._L.lfx_map_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Odometry:
+    """lfx_odometry: scan-to-local-map odometry -- Odometry<..., EdgeSurfaceMap, EdgeSurfaceScan> (odometry.hpp:52-63) with the
+    store and the window maps on the device.  Poses are 3 x 4 [R | t] (point_to_map)."""
+
+    def __init__(self, fx, **config):
+        self._fx = fx
+        self._L = fx._L
+        cfg = B.OdometryConfig()
+        self._L.lfx_odometry_default_config(C.byref(cfg))
+        for k, v in config.items():
+            if k == "initial_pose":
+                cfg.initial_pose[:] = [float(x) for x in np.asarray(v, np.float64).reshape(12)]
+            elif k in dict(B.OdometryConfig._fields_):
+                setattr(cfg, k, v)
+            else:
+                raise TypeError("unknown odometry setting %r" % k)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_odometry_create(fx._ctx, C.byref(cfg), C.byref(h)))
+        self.handle = h
+        self.config = {k: getattr(cfg, k) for k, _ in B.OdometryConfig._fields_ if k != "initial_pose"}
+
+    def _results(self, res):
+        out = []
+        for r, a in zip(res, self._fx._align_results([r.align for r in res])):
+            a.update(n_edge_map=r.n_edge_map, n_surface_map=r.n_surface_map, aligned=bool(r.aligned))
+            out.append(a)
+        return out
+
+    def update_batch(self, n_scans=None, stream=0):
+        """lfx_odometry_update_batch: Odometry::Update for every scan of the last device batch; one dict per scan (the
+        alignment's pose, error, error_scale, iteration, code, success, message, plus n_edge_map, n_surface_map, aligned)."""
+        n = int(self._fx.device_view().batch if n_scans is None else n_scans)
+        res = (B.OdometryResult * max(n, 1))()
+        B.check(self._fx._ctx, self._L.lfx_odometry_update_batch(self._fx._ctx, self.handle, n, res, C.c_void_p(int(stream))))
+        return self._results(res[:n])
+
+    def update(self, d_edge, n_edge, d_surface, n_surface, stream=0):
+        """lfx_odometry_update: Odometry::Update for one scan whose clouds (records of 4 floats) are on the device."""
+        res = (B.OdometryResult * 1)()
+        B.check(self._fx._ctx, self._L.lfx_odometry_update(
+            self._fx._ctx, self.handle, C.c_void_p(int(d_edge)), int(n_edge), C.c_void_p(int(d_surface)), int(n_surface), res,
+            C.c_void_p(int(stream))))
+        return self._results(res)[0]
+
+    def update_host(self, edge_points, surface_points, stream=0):
+        """lfx_odometry_update_host: the same for clouds ([n][4] float32) on the host."""
+        e = np.ascontiguousarray(edge_points, np.float32).reshape(-1, 4)
+        sf = np.ascontiguousarray(surface_points, np.float32).reshape(-1, 4)
+        res = (B.OdometryResult * 1)()
+        B.check(self._fx._ctx, self._L.lfx_odometry_update_host(
+            self._fx._ctx, self.handle, C.c_void_p(e.ctypes.data), len(e), C.c_void_p(sf.ctypes.data), len(sf), res,
+            C.c_void_p(int(stream))))
+        return self._results(res)[0]
+
+    def add(self, pose, d_edge, n_edge, d_surface, n_surface, stream=0):
+        """lfx_odometry_add: EdgeSurfaceMap::Add at a given pose (3 x 4); the current pose stays as it is."""
+        pm = np.ascontiguousarray(pose, np.float64).reshape(12)
+        B.check(self._fx._ctx, self._L.lfx_odometry_add(
+            self._fx._ctx, self.handle, pm.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(int(d_edge)), int(n_edge),
+            C.c_void_p(int(d_surface)), int(n_surface), C.c_void_p(int(stream))))
+
+    def pose(self):
+        """CurrentPose, 3 x 4."""
+        out = np.zeros(12, np.float64)
+        B.check(self._fx._ctx, self._L.lfx_odometry_pose(self.handle, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out.reshape(3, 4)
+
+    def view(self):
+        """lfx_odometry_view: device addresses and sizes of the store (GetAll) and the window (GetRecent), per-scan offsets
+        (numpy copies), scans added / dropped, compactions, the current pose."""
+        v = B.OdometryStoreView()
+        B.check(self._fx._ctx, self._L.lfx_odometry_view(self.handle, C.byref(v)))
+        n = v.n_scans
+        return dict(n_scans=n, n_window_scans=v.n_window_scans, n_added=v.n_added, dropped_scans=v.dropped_scans,
+                    compactions=v.compactions, edge_points=v.edge_points or 0, surface_points=v.surface_points or 0,
+                    n_edge=v.n_edge, n_surface=v.n_surface, edge_window=v.edge_window or 0, surface_window=v.surface_window or 0,
+                    n_edge_window=v.n_edge_window, n_surface_window=v.n_surface_window,
+                    edge_offsets=np.array(v.edge_offsets[:n + 1], np.uint32), surface_offsets=np.array(v.surface_offsets[:n + 1], np.uint32),
+                    pose=np.array(v.pose[:], np.float64).reshape(3, 4))
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_odometry_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -46,25 +46,34 @@ def _ray_circle(cx, cy, dx, dy, px, py, rad):
 
 def make_scan(rings=64, cols=1800, seed=1234, vfov_deg=15.0, sigma=0.01, n_pillars=14,
               drop_fraction=0.0, shuffle=False, start_col=0, reverse=False,
-              out_of_range=True, spikes=True):
+              out_of_range=True, spikes=True, sensor_pose=None):
     """Return one scan as a POINT_DTYPE array (rings*cols points, fewer with drop_fraction).
 
     drop_fraction  drop this share of points at random (ragged rings, as after the zero filter)
     shuffle        permute the points (forces the general ring projection, not the presorted one)
     start_col      rotate the firing sequence (scan starts at another azimuth)
     reverse        clockwise sensors: azimuth decreases with time
+    sensor_pose    (x, y, yaw): the sensor moved by (x, y) metres from its usual place in the same static room and turned
+                   by yaw radians about the vertical; rays are cast in the room, points are given in the sensor's frame.
+                   None (the default) is the usual place and gives the same bytes as before the keyword existed.
     """
     rng = np.random.Generator(np.random.PCG64(seed))
     az = -np.pi + 2.0 * np.pi * (np.arange(cols) + 0.5) / cols
     elev = np.deg2rad(np.linspace(-vfov_deg, vfov_deg, rings))
-    dx, dy = np.cos(az), np.sin(az)
-    cx, cy, h = 1.3, -0.7, 1.8                      # sensor position in the room, height over ground
-    r = _ray_room(cx, cy, dx, dy, -10.0, 10.0, -6.0, 6.0)
+    dx, dy = np.cos(az), np.sin(az)                 # ray directions in the sensor's frame
+    cx0, cy0, h = 1.3, -0.7, 1.8                    # the sensor's usual position in the room, height over ground
+    if sensor_pose is None:
+        cx, cy, wx, wy = cx0, cy0, dx, dy
+    else:
+        mx, my, yaw = (float(v) for v in sensor_pose)
+        cx, cy = cx0 + mx, cy0 + my
+        wx, wy = np.cos(az + yaw), np.sin(az + yaw)  # ... and in the room's
+    r = _ray_room(cx, cy, wx, wy, -10.0, 10.0, -6.0, 6.0)
     pr = np.random.Generator(np.random.PCG64(4242))  # the scene is the same for every seed
     for k in range(n_pillars):
         ang = 2.0 * np.pi * (k + 0.37) / n_pillars + pr.uniform(-0.1, 0.1)
         dist = pr.uniform(3.0, 5.5)
-        r = np.minimum(r, _ray_circle(cx, cy, dx, dy, cx + dist * np.cos(ang), cy + dist * np.sin(ang),
+        r = np.minimum(r, _ray_circle(cx, cy, wx, wy, cx0 + dist * np.cos(ang), cy0 + dist * np.sin(ang),
                                       pr.uniform(0.08, 0.2)))
     r2 = np.broadcast_to(r, (rings, cols)).copy()
     # downward beams hit the ground before the wall
@@ -108,6 +117,19 @@ def make_scan(rings=64, cols=1800, seed=1234, vfov_deg=15.0, sigma=0.01, n_pilla
 def make_batch(n_scans, rings=64, cols=1800, seed=1234, **kw):
     """n_scans scans with seeds seed, seed+1, ... (seeds 1234+scan_id)."""
     return [make_scan(rings, cols, seed + i, **kw) for i in range(n_scans)]
+
+
+def make_sequence(n_scans, rings=64, cols=1800, seed=1234, step=0.05, yaw_step_deg=0.5, **kw):
+    """A moving sensor in the static room: scan k is taken at (k * step, 0) metres from the usual place, turned by
+    k * yaw_step_deg degrees, with seed seed + k.  Returns (clouds, poses): poses[k] is the ground truth of what odometry
+    estimates, scan k's frame in scan 0's frame as 3 x 4 [R | t] (point_to_map, scan 0 = identity)."""
+    clouds, poses = [], []
+    for k in range(n_scans):
+        x, yaw = k * step, np.deg2rad(k * yaw_step_deg)
+        clouds.append(make_scan(rings, cols, seed + k, sensor_pose=(x, 0.0, yaw), **kw))
+        c, s = np.cos(yaw), np.sin(yaw)
+        poses.append(np.array([[c, -s, 0.0, x], [s, c, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0]], np.float64))
+    return clouds, np.stack(poses)
 
 
 def concat(clouds):
