@@ -23,8 +23,14 @@ different ranks use different links.
 
 Rank 0 prints ONE JSON line; "roofline" prices the dominant kernel against the HBM roof with the
 path's ALGORITHMIC bytes (25*N_pts + 16*(N_edge+N_surface) per scan), its duration
-measured live with HIP events on the launch stream; "cpu_baseline" is the CPU oracle (a port of
-the reference algorithm, oracle/) timed on this host on a bounded sample of the same scans.
+measured live with HIP events on the launch stream.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed region, --dump-outputs, the line.
+`--full` adds everything else, each measured after the headline's numbers are complete: "box" (the copy rate and clock
+of the device), "parity_spot_check" (one scan against the CPU oracle), "cpu_baseline" (the oracle, a port of the
+reference algorithm, oracle/, timed on this host on a bounded sample of the same scans), "end_to_end" (the host API),
+"consumer" (tools/localize_bench.py), "configs" (BASELINE.json's other configurations) and, N > 1, "comm_stats" and
+"gather_dst0" (a second region gathering to rank 0).  Without --full these keys are null or absent.
 """
 import argparse
 import hashlib
@@ -83,13 +89,18 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the rendezvous traffic (communicator id, agreements, barriers, the maximum "
                          "over ranks); gloo where the ranks share a GPU (rehearsal: a real RCCL communicator refuses that)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip BASELINE.json's other configurations (the \"configs\" list of the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else the line can carry: box calibration, parity spot "
+                         "check, CPU baseline, host API, consumer, BASELINE.json's other configurations; N > 1: comm_stats and the "
+                         "second region (default: the headline alone)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the host-side legs: cpu_baseline, end_to_end, consumer, configs")
+    ap.add_argument("--no-side-configs", action="store_true", help="--full without BASELINE.json's other configurations (the \"configs\" list of the line)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the per-step RCCL gather")
     ap.add_argument("--force-gather", action="store_true", help="run the pack + gather step even with one rank (rehearsal)")
     ap.add_argument("--warm-seconds", type=float, default=0.25, help="warm-up by the clock after the --warmup steps (0: steps only)")
-    ap.add_argument("--no-second-region", action="store_true", help="N>1 with a rotating destination: skip the short second region that gathers to rank 0")
+    ap.add_argument("--no-second-region", action="store_true", help="--full, N>1 with a rotating destination: skip the short second region that gathers to rank 0")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams (each with its own context and scratch) the steps alternate over")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -289,8 +300,13 @@ def main():
     n_pts = max(len(c) for c in clouds)
     valid = [((c["x"] != 0) | (c["y"] != 0) | (c["z"] != 0)) if a.drop_zero else np.ones(len(c), bool) for c in clouds]
     tiled = [clouds[j % n_unique] for j in range(a.batch)]
-    host = concat(tiled).view(np.uint8)
-    d_points = torch.from_numpy(host).to(dev)
+    # the batch is the distinct scans back to back, repeated (scan j = clouds[j % n_unique]): upload them once and tile them
+    # on the device, the same bytes without a host copy of the whole batch (3.8 GB at the default size)
+    one = concat(clouds).view(np.uint8)
+    d_one = torch.from_numpy(one).to(dev)
+    head = one.nbytes // sum(len(c) for c in clouds) * sum(len(c) for c in clouds[:a.batch % n_unique])
+    d_points = torch.cat([d_one] * (a.batch // n_unique) + [d_one[:head]])
+    del d_one
     n_list = np.array([len(c) for c in tiled], np.uint32)
     cap = max(a.cols, 64)          # the sensor's column count: no ring is longer
     # one context (= one set of device scratch) per stream.  --streams > 1 alternates consecutive
@@ -341,7 +357,7 @@ def main():
         # its exchange is worth more than none.
         gather, gather0, gather_error, id0 = None, None, None, None
         # (one id more than the lanes: the communicator of the second, fixed-destination region -- see "gather_dst0" below)
-        second_region = a.gather_dst == "rotate" and not a.no_second_region
+        second_region = a.full and a.gather_dst == "rotate" and not a.no_second_region
         n_ids = n_lanes + (1 if second_region else 0)
         idt = torch.zeros(128 * n_ids, dtype=torch.uint8, device=ddev)
         # every rank first checks that it CAN enter the collective initialisation (the RCCL library opens and has the
@@ -535,7 +551,7 @@ def main():
         return out_stats
 
     comm_stats, dst0 = None, None
-    if use_gather:
+    if use_gather and a.full:
         mark("comm stats")
         comm_stats = all_ranks(gather.comm_report())
     mark("host-side measurements")
@@ -547,13 +563,14 @@ def main():
     # what THIS box gives right now (outside the timed region, ~50 ms): a plain float4 copy of 1 GiB and the shader clock
     # with every SIMD busy -- so that a slower box and a slower kernel can be told apart in one line of the driver's record
     box = None
-    try:
-        copy_gbs, clock_mhz = fx.box_calibration(0, stream)
-        box = {"copy_gbs": round(copy_gbs, 1), "clock_mhz": round(clock_mhz, 1),
-               "note": "lfx_box_calibration right after the timed region: read + written bytes per second of a float4 copy of 1 GiB (best of 3); "
-                       "shader clock from a chain of dependent 32-bit adds, four waves per SIMD on every CU"}
-    except Exception as e:                 # noqa: BLE001
-        box = {"error": "%s: %s" % (type(e).__name__, e)}
+    if a.full:
+        try:
+            copy_gbs, clock_mhz = fx.box_calibration(0, stream)
+            box = {"copy_gbs": round(copy_gbs, 1), "clock_mhz": round(clock_mhz, 1),
+                   "note": "lfx_box_calibration right after the timed region: read + written bytes per second of a float4 copy of 1 GiB (best of 3); "
+                           "shader clock from a chain of dependent 32-bit adds, four waves per SIMD on every CU"}
+        except Exception as e:             # noqa: BLE001
+            box = {"error": "%s: %s" % (type(e).__name__, e)}
 
     kt = {}
     for f in fxs:
@@ -570,7 +587,7 @@ def main():
     for j in range(n_unique):
         g = fx.download(j, stream)
         feats.append(len(g.edge_index) + len(g.surface_index))
-        if j == 0 and rank == 0:
+        if j == 0 and rank == 0 and a.full:
             from oracle import binding as oracle          # checker only (never timed as the product)
             # (with the zero filter on, the reference sees the cloud without its (0, 0, 0) records: convert.py:162-163)
             keep = np.nonzero(valid[0])[0]
@@ -633,7 +650,7 @@ def main():
 
     # ---- CPU baseline: the oracle (port of the reference algorithm), 1 thread, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import binding as oracle
         seen = [np.ascontiguousarray(c[v]) for c, v in zip(clouds, valid)]      # what the reference node would be handed
         oracle.extract(seen[0], canonical_ties=False)   # warm
@@ -671,7 +688,7 @@ def main():
     #      kernels, densify, D2H, un-permute to the caller's point order) -- the latency a ROS callback would see.
     #      Reported beside `value`, never as it (device-resident and PCIe-inclusive separately).
     end_to_end = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from lidar_feature_extraction_amd import binding as LB
 
         piped = []
@@ -725,7 +742,7 @@ def main():
 
     # ---- the consumer of the two clouds: Localizer::Update on the device, one scan and a batch
     consumer = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.rings * a.cols <= 64 * 1800:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and a.rings * a.cols <= 64 * 1800:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         try:
             import localize_bench
@@ -759,7 +776,7 @@ def main():
     # ---- BASELINE.json's other single-GPU configurations and the stream the reference's own pipeline produces (invalid
     #      returns as (0, 0, 0) records, filtered), a few steps each, in the same run
     configs = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.no_side_configs and (a.rings, a.cols, a.batch) == (64, 1800, 1024):
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not a.no_side_configs and (a.rings, a.cols, a.batch) == (64, 1800, 1024):
         for f in fxs:
             f.close()
         fxs = []

@@ -1,6 +1,6 @@
 """bench.py --dump-outputs: what the last timed step computed, written as .npy files, is what the CPU oracle computes for the
 same seeded scans -- so that two builds of the library can be compared output for output through the bench itself.  And
---steps is the number of timed steps."""
+--steps is the number of timed steps, and a run without --full measures the headline alone."""
 import glob
 import json
 import os
@@ -20,6 +20,25 @@ def test_bench_refuses_zero_steps():
 
 
 @pytest.mark.gpu
+def test_a_plain_run_measures_the_headline_alone():
+    """Without --full the line holds the headline and the figures its own timed region gives; nothing that takes a run or a
+    check of its own (box calibration, the oracle, the host API, the consumer) is measured, the CPU baseline included."""
+    batch, steps = 24, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rings", "16", "--cols", "900", "--batch", str(batch),
+           "--unique", "5", "--steps", str(steps), "--warmup", "1", "--warm-seconds", "0"]
+    p = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=420)
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == 1 and d["unit"] == "scans/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] - batch * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-3
+    assert d["roofline"]["frac"] > 0 and d["roofline"]["kernel_us_per_launch"]
+    for k in ("box", "parity_spot_check", "cpu_baseline", "end_to_end", "consumer", "configs"):
+        assert d[k] is None, (k, d[k])
+
+
+@pytest.mark.gpu
 def test_bench_dump_outputs_match_the_oracle(tmp_path):
     from lidar_feature_extraction_amd import make_scan
     from oracle import binding as OB
@@ -27,7 +46,7 @@ def test_bench_dump_outputs_match_the_oracle(tmp_path):
     out = tmp_path / "dump"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rings", str(rings), "--cols", str(cols),
            "--batch", str(batch), "--unique", str(unique), "--steps", "2", "--warmup", "1", "--warm-seconds", "0",
-           "--no-cpu-baseline", "--dump-outputs", str(out)]
+           "--full", "--no-cpu-baseline", "--dump-outputs", str(out)]
     p = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=420)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]

@@ -49,7 +49,7 @@ def test_bench_runs_with_two_ranks(dst):
     base = dict(os.environ, WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                 LFX_RCCL_LIB=_shim(), LFX_LIB_PATH=os.path.join(ROOT, "lidar_feature_extraction_amd", "_lib", "liblfx_testhooks.so"))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--batch", "8", "--steps", "3", "--warmup", "1",
-           "--repeats", "2", "--no-cpu-baseline", "--dist-backend", "gloo", "--gather-dst", dst] + (["--gather-lanes", "2"] if lanes else [])
+           "--repeats", "2", "--full", "--no-cpu-baseline", "--dist-backend", "gloo", "--gather-dst", dst] + (["--gather-lanes", "2"] if lanes else [])
     procs = [subprocess.Popen(cmd, env=dict(base, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT)
              for r in range(world)]
     outs = [p.communicate(timeout=420) for p in procs]
@@ -121,7 +121,7 @@ def test_a_second_region_that_hangs_costs_only_itself():
                 LFX_RCCL_LIB=_shim(), LFX_LIB_PATH=os.path.join(ROOT, "lidar_feature_extraction_amd", "_lib", "liblfx_testhooks.so"))
     # steps before the second region: 1 warm-up + 2 x 3 timed = 7 (no warm-up by the clock); the region's own second step is step 8
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--batch", "8", "--steps", "3", "--warmup", "1",
-           "--repeats", "2", "--no-cpu-baseline", "--dist-backend", "gloo", "--warm-seconds", "0", "--watchdog-seconds", "20",
+           "--repeats", "2", "--full", "--no-cpu-baseline", "--dist-backend", "gloo", "--warm-seconds", "0", "--watchdog-seconds", "20",
            "--test-stall-rank", "1", "--test-stall-step", "8"]
     procs = [subprocess.Popen(cmd, env=dict(base, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT)
              for r in range(world)]

@@ -10,7 +10,7 @@ for mode in "--drop-zero" ""; do
   for b in 1024 256 128 64 48 32; do
     for st in 1 2 3; do
       steps=$(( 8192 / b )); [ $steps -lt 8 ] && steps=8
-      timeout -k 10 200 python bench.py --no-cpu-baseline --batch $b --unique 8 --steps $steps --warmup 4 --repeats 3 --streams $st \
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --batch $b --unique 8 --steps $steps --warmup 4 --repeats 3 --streams $st \
         --drop-fraction 0.05 $mode > gpurun_out/holes_tmp.json 2> gpurun_out/holes_err.txt || { echo "batch $b streams $st failed"; tail -3 gpurun_out/holes_err.txt; continue; }
       python - "$mode" $b $st <<'PY' | tee -a $OUT
 import json, sys

@@ -5,12 +5,13 @@
 # 9 300 -> 5).  Same instruction stream, same data, only the waves in flight differ.
 mkdir -p gpurun_out
 : > gpurun_out/occ8.txt
+export T=$(mktemp -d)          # the bench line and stderr of the current run
 for round in 1 2 3; do
   for pad in 0 2600 5400 9300; do
-    LFX_DEBUG_UNIT_LDS_PAD=$pad timeout -k 10 180 python bench.py --no-cpu-baseline --cols 1400 --steps 30 --warmup 5 > gpurun_out/occ_tmp.json 2> gpurun_out/occ_err.txt || { tail -3 gpurun_out/occ_err.txt; exit 1; }
+    LFX_DEBUG_UNIT_LDS_PAD=$pad timeout -k 10 180 python bench.py --full --no-cpu-baseline --cols 1400 --steps 30 --warmup 5 > $T/occ_tmp.json 2> $T/occ_err.txt || { tail -3 $T/occ_err.txt; exit 1; }
     python - $pad <<'PY' | tee -a gpurun_out/occ8.txt
-import json, sys
-d = json.loads(open("gpurun_out/occ_tmp.json").read().strip().splitlines()[-1])
+import json, os, sys
+d = json.loads(open(os.environ["T"] + "/occ_tmp.json").read().strip().splitlines()[-1])
 pad = int(sys.argv[1])
 wgs = (160 * 1024) // (18048 + pad)
 print("lds pad %5d  -> %d workgroups per CU   unit kernel %7.1f us   %8.0f scans/s   parity %s" % (pad, min(wgs, 8), d["roofline"]["kernel_us_per_launch"]["ring_unit_org_kernel"], d["value"], d["parity_spot_check"]))

@@ -3,7 +3,7 @@
 #   1. rocprofv3 --kernel-trace --stats of `python3 bench.py` (per-kernel durations)       -> kernel_stats.csv
 #   2. rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes (HBM traffic)      -> pmc_traffic.json
 #   3. rocprofv3 --pmc SQ_* (instruction mix, busy and wait cycles of the dominant kernel) -> sq_counters.json
-#   4. the plain bench line, CPU baseline included                                         -> bench.json
+#   4. the full bench line (--full), CPU baseline included                                 -> bench.json
 # (counter passes carry --kernel-trace only; never a trace domain beside --pmc)
 set -e
 OUT=${1:-gpurun_out/profile}
@@ -76,6 +76,6 @@ json.dump({"note": "rocprofv3 --pmc, two passes of eight SQ counters, mean per d
            "kernels": keep}, open(out + "/sq_counters.json", "w"), indent=1)
 print(json.dumps(hbm))
 PY
-timeout -k 10 400 python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench_err.txt
+timeout -k 10 400 python3 bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench_err.txt
 cat $OUT/bench.json
 rm -rf $OUT/trace $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq1 $OUT/pmc_sq2 $OUT/pmc_sq3 $OUT/pmc_sq4

@@ -9,7 +9,7 @@ try:
     d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print(d.get('value'), d.get('value_min'), d.get('value_max'), d['roofline']['frac'], d['roofline']['whole_path_frac'], d.get('parity_spot_check'), d.get('gather_ms_per_step'))
 except Exception as e: print('unreadable', e)
 ")"; }
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 run bench_rotated $B --start-col 517
 run bench_reversed $B --reverse
 run bench_ragged_5pct $B --drop-fraction 0.05

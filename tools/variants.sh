@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for i in 1 2; do
   for lib in "$@"; do
-    LFX_LIB_PATH=$PWD/lidar_feature_extraction_amd/_lib/$lib timeout -k 10 180 python bench.py --no-cpu-baseline --steps 40 --warmup 6 \
+    LFX_LIB_PATH=$PWD/lidar_feature_extraction_amd/_lib/$lib timeout -k 10 180 python bench.py --full --no-cpu-baseline --steps 40 --warmup 6 \
       > gpurun_out/var_tmp.json 2> gpurun_out/var_err.txt || { tail -5 gpurun_out/var_err.txt; exit 1; }
     python - $lib <<'PY'
 import json, sys
