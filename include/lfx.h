@@ -391,7 +391,17 @@ int lfx_gather(lfx_ctx *ctx, lfx_comm *comm, int dst, const float *d_edge, const
  * record d_begin[s] of d_out, cells in ascending cell index, d_out_count[s] records; d_status[s] = 1 where PCL gives
  * the cloud back unfiltered because the leaf is too small for its extent (nothing is written then).  PARITY UNPINNED:
  * VoxelGrid's arithmetic is PCL's, a third-party library that is neither under the reference tree nor in this image;
- * implemented from its published algorithm (PCL 1.12.1), points of a cell summed in input order.  Asynchronous. */
+ * implemented from its published algorithm (PCL 1.12.1), points of a cell summed in input order.  Asynchronous.
+ * Where PCL's arithmetic is undefined, these rules hold:
+ *   - a point whose x, y or z is not finite is skipped, as VoxelGrid does for a cloud not marked dense: it takes no part
+ *     in the bounds, the cells or the centroids; a cloud of such points only gives 0 cells and status 0;
+ *   - status 1 ("leaf too small") where, with inv = 1.0f / leaf, an axis's (max - min) * inv is not finite or does not
+ *     fit int64; where PCL's dx * dy * dz > INT_MAX (d = (int64)((max - min) * inv) + 1); where floor(min * inv) or
+ *     floor(max * inv) of an axis lies outside int32; or where the product of the div_b (floor(max * inv) -
+ *     floor(min * inv) + 1) exceeds 2^32.  The last is a deviation: PCL's index would wrap there and merge distinct
+ *     cells, and PCL filters the cloud;
+ *   - the cell index i0 + i1 * div_b[0] + i2 * div_b[0] * div_b[1] (i = floor(x * inv) - (float)min_b, in float as
+ *     PCL) is computed in unsigned 32-bit arithmetic: PCL's static_cast<unsigned>(int idx) without its signed overflow. */
 int lfx_voxel_downsample(lfx_ctx *ctx, const float *d_points, const uint32_t *d_begin, const uint32_t *d_count,
                          uint32_t count_stride, uint32_t n_clouds, size_t total_points, float leaf, float *d_out,
                          uint32_t *d_out_count, uint32_t *d_status, void *stream);

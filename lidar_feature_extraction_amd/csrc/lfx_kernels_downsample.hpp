@@ -16,39 +16,72 @@ namespace lfx
 // One workgroup per cloud: bounds -> cell index per point -> stable LSD radix sort of (cell, point) by 8-bit digits
 // (stable, so the points of a cell stay in input order: PCL leaves that order to an unstable sort, here it is defined)
 // -> cell heads -> one thread per cell sums its points in that order.  Scratch: two (key, value) arrays per point.
+// Points with a non-finite coordinate are skipped (the first radix pass leaves them out); limits and the index
+// arithmetic: voxel_geometry, voxel_key and lfx.h.
 constexpr int kVoxThreads = 1024, kVoxItems = 12;
+constexpr uint32_t kVoxSkip = 0xffffffffu;        // the value of a sort item that is not a finite point of the cloud
 
-// bounds of the cloud (per-wave minima and maxima in red[0..2][w], red[3..5][w]) -> geo: min cell x, y, z; multipliers of y, z;
-// radix passes; leaf too small
-__device__ inline void voxel_geometry(const float (*red)[kVoxThreads / 64], int W, float inv, int * geo)
+// bounds of the cloud's finite points (per-wave minima and maxima in red[0..2][w], red[3..5][w], counts in fin[w]) -> geo:
+// min cell x, y, z (int32); multipliers of y, z; radix passes; leaf too small; finite points.  The rules of lfx.h: PCL's
+// test of dx * dy * dz against INT_MAX (factor by factor: three extents of a few million cells overflow 64 bits), and
+// "leaf too small" as well where an extent is not finite or does not fit int64, where a bound's cell lies outside int32,
+// and where there are more than 2^32 cells (PCL's index would wrap and merge distinct cells)
+__device__ inline void voxel_geometry(const float (*red)[kVoxThreads / 64], const uint32_t * fin, int W, float inv, uint32_t * geo)
 {
   float lo[3], hi[3];
+  uint32_t nf = 0;
+  for (int w = 0; w < W; w++) {nf += fin[w];}
   for (int a = 0; a < 3; a++) {
     lo[a] = red[a][0]; hi[a] = red[3 + a][0];
     for (int w = 1; w < W; w++) {lo[a] = fminf(lo[a], red[a][w]); hi[a] = fmaxf(hi[a], red[3 + a][w]);}
   }
-  const long long dx = (long long)((hi[0] - lo[0]) * inv) + 1, dy = (long long)((hi[1] - lo[1]) * inv) + 1,
-    dz = (long long)((hi[2] - lo[2]) * inv) + 1;
-  // PCL: "leaf size is too small for the input dataset" (also catches non-finite bounds); factor by factor, three extents of
-  // a few million cells overflow 64 bits
-  const long long lim = 2147483647LL;
-  int bad = !(dx >= 1 && dy >= 1 && dz >= 1 && dx <= lim && dy <= lim && dz <= lim && dx * dy <= lim && dx * dy * dz <= lim);
-  int min_b[3], div_b[3];
+  bool bad = false;
+  long long d[3];
   for (int a = 0; a < 3; a++) {
-    min_b[a] = (int)floorf(lo[a] * inv);
-    div_b[a] = (int)floorf(hi[a] * inv) - min_b[a] + 1;
+    const float ext = (hi[a] - lo[a]) * inv;
+    const bool fits = ext >= 0.f && ext < 9223372036854775808.0f;
+    bad = bad || !fits;
+    d[a] = fits ? (long long)ext + 1 : 1;
   }
-  long long cells = 0;
-  if (!bad && div_b[0] > 0 && div_b[1] > 0 && div_b[2] > 0 && (long long)div_b[0] * div_b[1] <= lim) {
-    cells = (long long)div_b[0] * div_b[1] * div_b[2];
+  const long long lim = 2147483647LL;
+  bad = bad || d[0] > lim || d[1] > lim || d[2] > lim || d[0] * d[1] > lim || d[0] * d[1] * d[2] > lim;
+  int min_b[3];
+  long long div_b[3];
+  float top[3];                               // the largest per-axis term of a key, floor(hi * inv) - (float)min_b
+  for (int a = 0; a < 3; a++) {
+    const float fl = floorf(lo[a] * inv), fh = floorf(hi[a] * inv);
+    const bool fits = fl >= -2147483648.0f && fh < 2147483648.0f;
+    bad = bad || !fits;
+    min_b[a] = fits ? (int)fl : 0;
+    div_b[a] = fits ? (long long)fh - min_b[a] + 1 : 1;
+    top[a] = fits ? fh - (float)min_b[a] : 0.f;
   }
-  if (!(cells > 0 && cells <= lim)) {bad = 1;}
-  const uint32_t maxkey = bad ? 0u : (uint32_t)(cells - 1);
-  geo[0] = min_b[0]; geo[1] = min_b[1]; geo[2] = min_b[2];
-  geo[3] = div_b[0]; geo[4] = div_b[0] * div_b[1];
-  geo[5] = maxkey == 0u ? 1 : (32 - __clz((int)maxkey) + 7) / 8;
-  geo[6] = bad;
-  }
+  const long long cap = 4294967296LL;
+  bad = bad || div_b[1] > cap / div_b[0] || div_b[2] > cap / (div_b[0] * div_b[1]);
+  // the passes cover the largest key that occurs: the terms are monotone in the coordinates, so it is at most the sum of
+  // the largest terms (in float the terms can round past div_b - 1); a sum of 2^32 or more wraps, and all four bytes count
+  const unsigned long long kmax = bad ? 0ull :
+    (unsigned long long)top[0] + (unsigned long long)top[1] * div_b[0] + (unsigned long long)top[2] * (div_b[0] * div_b[1]);
+  geo[0] = (uint32_t)min_b[0]; geo[1] = (uint32_t)min_b[1]; geo[2] = (uint32_t)min_b[2];
+  geo[3] = (uint32_t)div_b[0]; geo[4] = (uint32_t)(div_b[0] * div_b[1]);
+  geo[5] = kmax >= (unsigned long long)cap ? 4u : kmax == 0ull ? 1u : (uint32_t)(64 - __clzll((long long)kmax) + 7) / 8u;
+  geo[6] = bad ? 1u : 0u;
+  geo[7] = nf;
+}
+
+__device__ inline bool voxel_finite(const float4 & p)
+{
+  return __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z);
+}
+
+// cell index of a finite point in unsigned 32-bit arithmetic: PCL's static_cast<unsigned>(int idx) without its signed
+// overflow.  Each term floor(x * inv) - (float)min_b is >= 0 and, within voxel_geometry's limits, below 2^32.
+__device__ inline uint32_t voxel_key(const float4 & p, float inv, const float * fb, uint32_t mul1, uint32_t mul2)
+{
+  const uint32_t i0 = (uint32_t)(floorf(p.x * inv) - fb[0]), i1 = (uint32_t)(floorf(p.y * inv) - fb[1]),
+    i2 = (uint32_t)(floorf(p.z * inv) - fb[2]);
+  return i0 + i1 * mul1 + i2 * mul2;
+}
 
 __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
   const float4 * __restrict__ pts, const uint32_t * __restrict__ begin, const uint32_t * __restrict__ count,
@@ -63,8 +96,8 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
   const uint32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t b = begin[s], n = count[(size_t)s * count_stride];
   __shared__ float red[6][W];
-  __shared__ int geo[8];                      // min cell x, y, z; multipliers of y, z; radix passes; leaf too small
-  __shared__ uint32_t hist[256], base[256], wtot[W];
+  __shared__ uint32_t geo[8];                 // min cell x, y, z (int32); multipliers of y, z; radix passes; leaf too small; finite points
+  __shared__ uint32_t hist[256], base[256], wtot[W];          // (wtot: the waves' finite points, later their cell heads)
   __shared__ uint16_t wcnt[W][256];
   extern __shared__ uint16_t table[];         // [tiles of the cloud][W][256], then the sorted points: the form for clouds of up to kVoxItems * T points
   auto finish = [&](uint32_t n_out, uint32_t st) __attribute__((always_inline)) {      // every thread calls it, at the end
@@ -96,13 +129,16 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
       const uint32_t i = (uint32_t)t * T + tid;
       p[t] = pts[b + (i < n ? i : 0u)];
     }
+    // (a point with a non-finite coordinate is skipped: PCL's VoxelGrid on a cloud that is not dense)
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    uint32_t fin = 0;
 #pragma unroll
     for (int t = 0; t < VI; t++) {
       const uint32_t i = (uint32_t)t * T + tid;
-      if (i < n) {
+      if (i < n && voxel_finite(p[t])) {
         mn[0] = fminf(mn[0], p[t].x); mn[1] = fminf(mn[1], p[t].y); mn[2] = fminf(mn[2], p[t].z);
         mx[0] = fmaxf(mx[0], p[t].x); mx[1] = fmaxf(mx[1], p[t].y); mx[2] = fmaxf(mx[2], p[t].z);
+        fin++;
       }
     }
 #pragma unroll
@@ -113,45 +149,53 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
       }
       if (lane == 0) {red[a][wave] = mn[a]; red[3 + a][wave] = mx[a];}
     }
+    for (int o = 32; o > 0; o >>= 1) {fin += __shfl_xor(fin, o);}
+    if (lane == 0) {wtot[wave] = fin;}
     __syncthreads();
-    if (tid == 0) {voxel_geometry(red, W, inv, geo);}
+    if (tid == 0) {voxel_geometry(red, wtot, W, inv, geo);}
     __syncthreads();
-    if (geo[6]) {
-      finish(0u, 1u);
+    const uint32_t nf = geo[7];
+    if (nf == 0u || geo[6]) {
+      finish(0u, nf == 0u ? 0u : 1u);
       return;
     }
-    const float fb0 = (float)geo[0], fb1 = (float)geo[1], fb2 = (float)geo[2];
-    const int mul1 = geo[3], mul2 = geo[4], passes = geo[5];
+    const float fb[3] = {(float)(int)geo[0], (float)(int)geo[1], (float)(int)geo[2]};
+    const uint32_t mul1 = geo[3], mul2 = geo[4];
+    const int passes = (int)geo[5];
+    // a skipped point (and a slot past the cloud) takes the value kVoxSkip: the first pass leaves it out, and the n_f finite
+    // points come out of it packed, in input order within a digit, as every pass keeps them
     uint32_t k[VI], v[VI];
 #pragma unroll
     for (int t = 0; t < VI; t++) {
-      const int i0 = (int)(floorf(p[t].x * inv) - fb0), i1 = (int)(floorf(p[t].y * inv) - fb1), i2 = (int)(floorf(p[t].z * inv) - fb2);
-      k[t] = (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
-      v[t] = (uint32_t)t * T + tid;
+      const uint32_t i = (uint32_t)t * T + tid;
+      const bool ok = i < n && voxel_finite(p[t]);
+      k[t] = ok ? voxel_key(p[t], inv, fb, mul1, mul2) : 0u;
+      v[t] = ok ? i : kVoxSkip;
     }
     uint32_t * ks = key_a, * kd = key_b, * vs = val_a, * vd = val_b;
     for (int pass = 0; pass < passes; pass++) {
       const int shift = 8 * pass;
+      const uint32_t items = pass == 0 ? n : nf;
       if (pass > 0) {                                            // what the previous pass wrote, all of it at once
 #pragma unroll
         for (int t = 0; t < VI; t++) {
           const uint32_t i = (uint32_t)t * T + tid;
-          k[t] = ks[b + (i < n ? i : 0u)]; v[t] = vs[b + (i < n ? i : 0u)];
+          k[t] = ks[b + (i < nf ? i : 0u)]; v[t] = i < nf ? vs[b + i] : kVoxSkip;
         }
       }
       // every tile's ranking at once: table[(tile, wave)][digit] = points of that digit in that wave of that tile (the waves'
       // ballots, as below), then ONE walk per digit over the (tile, wave) pairs in order turns the counts into the places
       // where each group starts inside its digit and leaves the digit's total -- four barriers per pass where a barrier-
       // ridden loop over the tiles took four per tile
-      const uint32_t n_tiles = (n + T - 1) / T;
+      const uint32_t n_tiles = (items + T - 1) / T;
       for (uint32_t z = tid; z < n_tiles * W * 128u; z += T) {reinterpret_cast<uint32_t *>(table)[z] = 0u;}
       __syncthreads();
       uint32_t rank[VI], dig[VI];
 #pragma unroll
       for (int t = 0; t < VI; t++) {
         rank[t] = 0u; dig[t] = 256u;
-        if ((uint32_t)t * T >= n) {continue;}                  // (the same in every thread)
-        const bool valid = (uint32_t)t * T + tid < n;
+        if ((uint32_t)t * T >= items) {continue;}              // (the same in every thread)
+        const bool valid = v[t] != kVoxSkip;
         const uint32_t d = valid ? (k[t] >> shift) & 255u : 256u;
         uint64_t peers = ~0ull;
 #pragma unroll
@@ -204,7 +248,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
     uint32_t kp[VI];
 #pragma unroll
     for (int t = 0; t < VI; t++) {
-      const uint32_t i = (uint32_t)t * T + tid, ii = i < n ? i : 0u;
+      const uint32_t i = (uint32_t)t * T + tid, ii = i < nf ? i : 0u;
       k[t] = ks[b + ii]; kp[t] = ks[b + (ii ? ii - 1u : 0u)]; v[t] = vs[b + ii];
     }
 #pragma unroll
@@ -214,7 +258,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
 #pragma unroll
     for (int t = 0; t < VI; t++) {
       const uint32_t i = (uint32_t)t * T + tid;
-      if (i < n) {sx_l[i] = p[t].x; sy_l[i] = p[t].y; sz_l[i] = p[t].z;}
+      if (i < nf) {sx_l[i] = p[t].x; sy_l[i] = p[t].y; sz_l[i] = p[t].z;}
     }
     // ---- cell heads, every tile at once: the waves' head counts per (tile, wave), one wave's prefix over them, then each
     // head's place; the places go to LDS when there are at most 2 047 cells (a scan's surface cloud has a few hundred)
@@ -222,7 +266,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
 #pragma unroll
     for (int t = 0; t < VI; t++) {
       const uint32_t i = (uint32_t)t * T + tid;
-      const bool head = i < n && (i == 0 || k[t] != kp[t]);
+      const bool head = i < nf && (i == 0 || k[t] != kp[t]);
       hm[t] = __ballot(head);
       if (lane == 0) {hist[t * W + wave] = (uint32_t)__popcll(hm[t]);}
     }
@@ -254,12 +298,12 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
         if (heads_in_lds) {heads_l[at] = i;} else {kd[b + at] = i;}
       }
     }
-    if (tid == 0) {if (heads_in_lds) {heads_l[m] = n;}}
+    if (tid == 0) {if (heads_in_lds) {heads_l[m] = nf;}}
     __syncthreads();
     // ---- centroids: the points of a cell in input order (AccumulatorXYZ: float sums, then / count), out of LDS: a cell of
     // a few hundred points near the sensor is a few hundred LDS reads for its thread, not as many trips to memory
     for (uint32_t c = tid; c < m; c += T) {
-      const uint32_t a = heads_in_lds ? heads_l[c] : kd[b + c], e = heads_in_lds ? heads_l[c + 1] : (c + 1 < m ? kd[b + c + 1] : n);
+      const uint32_t a = heads_in_lds ? heads_l[c] : kd[b + c], e = heads_in_lds ? heads_l[c + 1] : (c + 1 < m ? kd[b + c + 1] : nf);
       float sx = 0.f, sy = 0.f, sz = 0.f;
       for (uint32_t j = a; j < e; j++) {sx += sx_l[j]; sy += sy_l[j]; sz += sz_l[j];}
       const float cnt = (float)(e - a);
@@ -268,12 +312,15 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
     finish(m, 0u);
     return;
   }
-  // ---- bounds (getMinMax3D)
+  // ---- bounds of the finite points (getMinMax3D of a cloud that is not dense)
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  uint32_t fin = 0;
   for (uint32_t i = tid; i < n; i += T) {
     const float4 p = pts[b + i];
+    if (!voxel_finite(p)) {continue;}
     mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
     mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+    fin++;
   }
 #pragma unroll
   for (int a = 0; a < 3; a++) {
@@ -283,30 +330,37 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
     }
     if (lane == 0) {red[a][wave] = mn[a]; red[3 + a][wave] = mx[a];}
   }
+  for (int o = 32; o > 0; o >>= 1) {fin += __shfl_xor(fin, o);}
+  if (lane == 0) {wtot[wave] = fin;}
   __syncthreads();
-  if (tid == 0) {voxel_geometry(red, W, inv, geo);}
+  if (tid == 0) {voxel_geometry(red, wtot, W, inv, geo);}
   __syncthreads();
-  if (geo[6]) {
-    finish(0u, 1u);
+  const uint32_t nf = geo[7];
+  if (nf == 0u || geo[6]) {
+    finish(0u, nf == 0u ? 0u : 1u);
     return;
   }
-  const float fb0 = (float)geo[0], fb1 = (float)geo[1], fb2 = (float)geo[2];
-  const int mul1 = geo[3], mul2 = geo[4], passes = geo[5];
-  // ---- cell index per point
+  const float fb[3] = {(float)(int)geo[0], (float)(int)geo[1], (float)(int)geo[2]};
+  const uint32_t mul1 = geo[3], mul2 = geo[4];
+  const int passes = (int)geo[5];
+  // ---- cell index per point; a skipped point's value is kVoxSkip, and the first pass leaves it out
   for (uint32_t i = tid; i < n; i += T) {
     const float4 p = pts[b + i];
-    const int i0 = (int)(floorf(p.x * inv) - fb0), i1 = (int)(floorf(p.y * inv) - fb1), i2 = (int)(floorf(p.z * inv) - fb2);
-    key_a[b + i] = (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
-    val_a[b + i] = i;
+    const bool ok = voxel_finite(p);
+    key_a[b + i] = ok ? voxel_key(p, inv, fb, mul1, mul2) : 0u;
+    val_a[b + i] = ok ? i : kVoxSkip;
   }
   __syncthreads();
   // ---- stable LSD radix sort, 8 bits per pass
   uint32_t * ks = key_a, * kd = key_b, * vs = val_a, * vd = val_b;
   for (int pass = 0; pass < passes; pass++) {
     const int shift = 8 * pass;
+    const uint32_t items = pass == 0 ? n : nf;                // (the first pass packs the finite points)
     if (tid < 256) {hist[tid] = 0;}
     __syncthreads();
-    for (uint32_t i = tid; i < n; i += T) {atomicAdd(&hist[(ks[b + i] >> shift) & 255u], 1u);}
+    for (uint32_t i = tid; i < items; i += T) {
+      if (pass > 0 || vs[b + i] != kVoxSkip) {atomicAdd(&hist[(ks[b + i] >> shift) & 255u], 1u);}
+    }
     __syncthreads();
     if (tid < 64) {                                           // exclusive scan of the 256 bins by one wave, four bins per lane
       const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
@@ -319,12 +373,12 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
       base[4 * tid] = ex; base[4 * tid + 1] = ex + h0; base[4 * tid + 2] = ex + h0 + h1; base[4 * tid + 3] = ex + h0 + h1 + h2;
     }
     __syncthreads();
-    for (uint32_t t0 = 0; t0 < n; t0 += T) {
+    for (uint32_t t0 = 0; t0 < items; t0 += T) {
       for (int z = tid; z < W * 256; z += T) {(&wcnt[0][0])[z] = 0;}
       __syncthreads();
       const uint32_t i = t0 + tid;
-      const bool valid = i < n;
-      const uint32_t k = valid ? ks[b + i] : 0u, v = valid ? vs[b + i] : 0u;
+      const uint32_t k = i < items ? ks[b + i] : 0u, v = i < items ? vs[b + i] : kVoxSkip;
+      const bool valid = v != kVoxSkip;
       const uint32_t d = valid ? (k >> shift) & 255u : 256u;
       uint64_t peers = ~0ull;
 #pragma unroll
@@ -359,9 +413,9 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
   }
   // ---- cell heads: position of every cell's first point (kept in kd), number of cells
   uint32_t cells_before = 0;
-  for (uint32_t t0 = 0; t0 < n; t0 += T) {
+  for (uint32_t t0 = 0; t0 < nf; t0 += T) {
     const uint32_t i = t0 + tid;
-    const bool head = i < n && (i == 0 || ks[b + i] != ks[b + i - 1]);
+    const bool head = i < nf && (i == 0 || ks[b + i] != ks[b + i - 1]);
     const uint64_t hm = __ballot(head);
     if (lane == 0) {wtot[wave] = __popcll(hm);}
     __syncthreads();
@@ -378,7 +432,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_downsample_kernel(
   __syncthreads();
   // ---- centroids: the points of a cell in input order (AccumulatorXYZ: float sums, then / count)
   for (uint32_t c = tid; c < m; c += T) {
-    const uint32_t a = kd[b + c], e = c + 1 < m ? kd[b + c + 1] : n;
+    const uint32_t a = kd[b + c], e = c + 1 < m ? kd[b + c + 1] : nf;
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (uint32_t jdx = a; jdx < e; jdx++) {
       const float4 p = pts[b + vs[b + jdx]];

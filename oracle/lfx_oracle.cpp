@@ -633,44 +633,68 @@ int orc_ring_message(int status, int n, const orc_params * p, char * buf, size_t
   }
 }
 
-// pcl::VoxelGrid<PointXYZ>::applyFilter (PCL 1.12.1, filters/impl/voxel_grid.hpp), see lfx_oracle.h: PARITY UNPINNED
+// pcl::VoxelGrid<PointXYZ>::applyFilter (PCL 1.12.1, filters/impl/voxel_grid.hpp), see lfx_oracle.h: PARITY UNPINNED.
+// PCL's arithmetic where it is defined; where PCL's is undefined (conversions out of range, int overflow) the rules of
+// lfx.h (lfx_voxel_downsample), which voxel_downsample_kernel follows too.
 int orc_voxel_downsample(const float * points, int n, float leaf, float * out, int * n_out)
 {
   *n_out = 0;
-  if (n <= 0) {return 0;}
-  float mn[3] = {points[0], points[1], points[2]}, mx[3] = {points[0], points[1], points[2]};
-  for (int i = 1; i < n; i++) {                                  // getMinMax3D
+  // the cloud is not dense: a point with a non-finite coordinate takes no part (getMinMax3D and the index pass skip it)
+  std::vector<int> fin;
+  fin.reserve(n > 0 ? n : 0);
+  for (int i = 0; i < n; i++) {
+    if (std::isfinite(points[4 * i]) && std::isfinite(points[4 * i + 1]) && std::isfinite(points[4 * i + 2])) {fin.push_back(i);}
+  }
+  const int nf = static_cast<int>(fin.size());
+  if (nf == 0) {return 0;}
+  float mn[3] = {points[4 * fin[0]], points[4 * fin[0] + 1], points[4 * fin[0] + 2]}, mx[3] = {mn[0], mn[1], mn[2]};
+  for (int j = 1; j < nf; j++) {                                 // getMinMax3D
     for (int a = 0; a < 3; a++) {
-      mn[a] = std::min(mn[a], points[4 * i + a]);
-      mx[a] = std::max(mx[a], points[4 * i + a]);
+      mn[a] = std::min(mn[a], points[4 * fin[j] + a]);
+      mx[a] = std::max(mx[a], points[4 * fin[j] + a]);
     }
   }
   const float inv = 1.0f / leaf;                                 // inverse_leaf_size_ = Ones / leaf_size_
-  const long long dx = static_cast<long long>((mx[0] - mn[0]) * inv) + 1, dy = static_cast<long long>((mx[1] - mn[1]) * inv) + 1,
-    dz = static_cast<long long>((mx[2] - mn[2]) * inv) + 1;
-  // "Leaf size is too small for the input dataset": the product against INT_MAX, factor by factor (three extents of a few
-  // million cells overflow 64 bits: found by the sanitizer build, `make asan`)
+  // "Leaf size is too small for the input dataset": PCL's product of (int64)((max - min) * inv) + 1 against INT_MAX,
+  // factor by factor (three extents of a few million cells overflow 64 bits); an extent that is not finite or does not
+  // fit the conversion is too small a leaf as well
   const long long lim = 2147483647LL;
-  if (dx > lim || dy > lim || dz > lim || dx * dy > lim || dx * dy * dz > lim) {return 1;}
-  int min_b[3], div_b[3];
+  long long d[3];
   for (int a = 0; a < 3; a++) {
-    min_b[a] = static_cast<int>(std::floor(mn[a] * inv));
-    div_b[a] = static_cast<int>(std::floor(mx[a] * inv)) - min_b[a] + 1;
+    const float ext = (mx[a] - mn[a]) * inv;
+    if (!(ext >= 0.f && ext < 9223372036854775808.0f)) {return 1;}
+    d[a] = static_cast<long long>(ext) + 1;
   }
-  const int mul1 = div_b[0], mul2 = div_b[0] * div_b[1];
-  std::vector<std::pair<unsigned, int>> cells(n);
-  for (int i = 0; i < n; i++) {
-    const int i0 = static_cast<int>(std::floor(points[4 * i] * inv) - static_cast<float>(min_b[0]));
-    const int i1 = static_cast<int>(std::floor(points[4 * i + 1] * inv) - static_cast<float>(min_b[1]));
-    const int i2 = static_cast<int>(std::floor(points[4 * i + 2] * inv) - static_cast<float>(min_b[2]));
-    cells[i] = {static_cast<unsigned>(i0 + i1 * mul1 + i2 * mul2), i};
+  if (d[0] > lim || d[1] > lim || d[2] > lim || d[0] * d[1] > lim || d[0] * d[1] * d[2] > lim) {return 1;}
+  // min_b / max_b: floor of the bounds times inv, which must lie inside int32
+  int min_b[3];
+  long long div_b[3];
+  for (int a = 0; a < 3; a++) {
+    const float lo = std::floor(mn[a] * inv), hi = std::floor(mx[a] * inv);
+    if (!(lo >= -2147483648.0f && hi < 2147483648.0f)) {return 1;}
+    min_b[a] = static_cast<int>(lo);
+    div_b[a] = static_cast<long long>(hi) - min_b[a] + 1;
+  }
+  // more than 2^32 cells: PCL's index would wrap and merge distinct cells (a deviation: PCL filters such a cloud)
+  const long long cap = 4294967296LL;
+  if (div_b[1] > cap / div_b[0] || div_b[2] > cap / (div_b[0] * div_b[1])) {return 1;}
+  // the linear index in unsigned 32-bit arithmetic: PCL's static_cast<unsigned>(int idx) without the signed overflow.  Each
+  // per-axis term floor(x * inv) - (float)min_b is >= 0 and, with the limits above, below 2^32.
+  const uint32_t mul1 = static_cast<uint32_t>(div_b[0]), mul2 = static_cast<uint32_t>(div_b[0] * div_b[1]);
+  std::vector<std::pair<uint32_t, int>> cells(nf);
+  for (int j = 0; j < nf; j++) {
+    const float * p = points + 4 * fin[j];
+    const uint32_t i0 = static_cast<uint32_t>(std::floor(p[0] * inv) - static_cast<float>(min_b[0]));
+    const uint32_t i1 = static_cast<uint32_t>(std::floor(p[1] * inv) - static_cast<float>(min_b[1]));
+    const uint32_t i2 = static_cast<uint32_t>(std::floor(p[2] * inv) - static_cast<float>(min_b[2]));
+    cells[j] = {i0 + i1 * mul1 + i2 * mul2, fin[j]};
   }
   std::sort(cells.begin(), cells.end());                          // (cell, input index): canonical order inside a cell
   int m = 0;
-  for (int a = 0; a < n; ) {
+  for (int a = 0; a < nf; ) {
     int b = a;
     float sx = 0.f, sy = 0.f, sz = 0.f;                           // AccumulatorXYZ: Eigen::Vector3f sum
-    while (b < n && cells[b].first == cells[a].first) {
+    while (b < nf && cells[b].first == cells[a].first) {
       const float * p = points + 4 * cells[b].second;
       sx += p[0]; sy += p[1]; sz += p[2];
       b++;

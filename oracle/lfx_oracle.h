@@ -117,7 +117,8 @@ int orc_ring_message(int status, int n, const orc_params *p, char *buf, size_t l
  * inverse leaf size as float, cell index = floor(x * inv) - min cell, cells in ascending linear index, centroid =
  * float sum / count.  PCL leaves the order of the float sum inside a cell to an unstable sort; here (and in the HIP
  * path) it is ascending input index.  points / out: records of 4 floats (x, y, z, 1).  Returns 0, or 1 where PCL gives
- * up (leaf too small for the cloud's extent: index would overflow int). */
+ * up (leaf too small for the cloud's extent).  Non-finite points, the limits and the index arithmetic where PCL's is
+ * undefined: the rules of include/lfx.h (lfx_voxel_downsample). */
 int orc_voxel_downsample(const float *points, int n, float leaf, float *out /* capacity n */, int *n_out);
 /* --- localization: the scan-to-map residual build that consumes the two clouds; lfx_oracle_loc.cpp.
  * PARITY UNPINNED beyond the vectors of localization/test/test_edge.cpp, test_math.cpp (Eigen + nanoflann underneath). */

@@ -405,3 +405,82 @@ def test_voxel_downsample_known_answers():
     assert len(np.unique(got_cells, axis=0)) == n_out.value
     order = np.lexsort((uniq[:, 0], uniq[:, 1], uniq[:, 2]))             # x fastest, then y, then z
     assert np.array_equal(got_cells, uniq[order])
+
+
+def test_voxel_downsample_edge_clouds_against_the_restatement():
+    """Every edge cloud of tests/downsample_cases.py (limits of "leaf too small", cell boundaries, far coordinates, the
+    kernel's form and head switches, radix widths, non-finite points) through the oracle and through the independent
+    numpy float32 restatement of lfx.h's rules: status and centroids bit for bit.  Under the sanitizers
+    (test_oracle_sanitized.py) the same clouds drive the oracle's conversions and index arithmetic to their limits."""
+    from tests import downsample_cases as D
+    names = set()
+    for name, cloud, leaf in D.all_cases():
+        names.add(name)
+        rc, got = D.oracle(cloud, leaf)
+        st, want = D.restate(cloud, leaf)
+        assert rc == st, (name, rc, st)
+        assert got.tobytes() == want.tobytes(), name
+    assert len(names) > 100
+
+
+def test_voxel_downsample_limits_known_answers():
+    """The status rule of lfx.h on hand-checked clouds, so the restatement and the oracle cannot share a mistake."""
+    from tests import downsample_cases as D
+    cases = {name: (c, leaf) for name, c, leaf in D.limit_cases()}
+    f = np.float32
+    # PCL's dx * dy * dz = 1290^3 <= INT_MAX passes, but div_b = 1291 per axis: 1291^3 > INT_MAX cells, keys above INT_MAX
+    rc, out = D.oracle(*cases["straddle"])
+    assert rc == 0 and out.tolist() == [[0.5, 0.5, 0.5, 1], [float((f(1290.2) + f(1290.1)) / f(2))] * 3 + [1]]
+    st, _, key = D.geometry(*cases["straddle"])
+    assert st == 0 and int(key.max()) == 1290 + 1290 * 1291 + 1290 * 1291 * 1291 > 2 ** 31 - 1
+    expect = {"product_1290_cubed": 0, "product_1291_cubed": 1, "axis_int_max": 0, "axis_above_int_max": 1,
+              "div_product_below_2_32": 0, "div_product_2_32": 1, "div_product_above_2_32": 1, "leaf_1e-30": 1,
+              "leaf_1e-30_one_point": 1, "leaf_denormal_one_point": 1, "leaf_denormal_origin": 1, "leaf_flt_max": 0,
+              "leaf_inf": 0, "leaf_inf_huge_extent": 1, "leaf_flt_max_huge_extent": 1, "near_int_max_cell": 0,
+              "near_int_min_cell": 0}
+    for name, rc_want in expect.items():
+        assert D.oracle(*cases[name])[0] == rc_want, name
+    for name in cases:
+        if name.startswith("far_"):                     # |coordinate / leaf| = 3e9: a bound's cell outside int32
+            assert D.oracle(*cases[name])[0] == 1, name
+    # 2 x 2 x (2^30 - 63) cells: filtered, the largest key needs all four radix bytes
+    st, _, key = D.geometry(*cases["div_product_below_2_32"])
+    assert st == 0 and int(key.max()) >= 2 ** 31
+    # an infinite leaf: every point in one cell
+    rc, out = D.oracle(*cases["leaf_inf"])
+    assert rc == 0 and len(out) == 1
+
+
+def test_voxel_downsample_skips_non_finite_points():
+    """A point with a NaN or infinite coordinate takes no part: inserting such points anywhere leaves the output byte for
+    byte as it was; a cloud of only such points gives 0 cells and status 0."""
+    from tests import downsample_cases as D
+    rng = np.random.default_rng(23)
+    for n, leaf in ((1, 1.0), (300, 0.5), (5000, 0.25), (13000, 1.0)):
+        clean = D.cloud(rng.normal(0, 4, (n, 3)))
+        rc0, want = D.oracle(clean, leaf)
+        assert rc0 == 0
+        for count in (1, 5, 200):
+            rc, got = D.oracle(D.insert_nonfinite(rng, clean, count), leaf)
+            assert rc == 0 and got.tobytes() == want.tobytes(), (n, count)
+    for bad in (np.nan, np.inf, -np.inf):
+        rc, got = D.oracle(D.cloud(np.full((9, 3), bad)), 1.0)
+        assert rc == 0 and len(got) == 0
+    # a NaN first point used to poison the bounds and come back as a centroid
+    c = D.cloud([[np.nan, 0, 0], [0.5, 0.5, 0.5], [1.5, 0.5, 0.5]])
+    rc, got = D.oracle(c, 1.0)
+    assert rc == 0 and got.tolist() == [[0.5, 0.5, 0.5, 1], [1.5, 0.5, 0.5, 1]]
+
+
+def test_voxel_downsample_against_float64():
+    """Properties against float64, on clouds within the limits: one centroid per distinct float32 cell, in ascending
+    linear cell index, each within a count-scaled rounding bound of the float64 mean of its members."""
+    from tests import downsample_cases as D
+    rng = np.random.default_rng(29)
+    clouds = [(D.cloud(rng.normal(0, 8, (4000, 3))), 0.3), (D.cloud(rng.uniform(-50, 50, (13000, 3))), 2.0),
+              (D.cloud(rng.uniform(2.0, 2.9, (3000, 3))), 1.0), (D.cloud(1.0e5 + rng.normal(0, 0.5, (2000, 3))), 0.01)]
+    for cloud, leaf in clouds:
+        rc, got = D.oracle(cloud, leaf)
+        assert rc == 0
+        D.check_against_float64(cloud, leaf, got)
+
