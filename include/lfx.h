@@ -160,7 +160,8 @@ enum lfx_error {
   LFX_ERR_OUT_OF_MEMORY = -6,
   LFX_ERR_NO_RING_FIELD = -7,     /* the cloud has no "ring" field: RingIsAvailable (ring.cpp:36-44) is false and the
                                    * node shuts down (feature_extraction.cpp:103-108)            */
-  LFX_ERR_UNSUPPORTED_FIELD = -8  /* x / y / z missing or not FLOAT32, ring not an integer, field outside point_step */
+  LFX_ERR_UNSUPPORTED_FIELD = -8, /* x / y / z missing or not FLOAT32, ring not an integer, field outside point_step */
+  LFX_ERR_FILE = -9               /* a file cannot be opened, read or written, or it is not a PCD file lfx_pcd_read takes */
 };
 
 typedef struct lfx_ctx lfx_ctx;
@@ -586,6 +587,104 @@ int lfx_odometry_add(lfx_ctx *ctx, lfx_odometry *odometry, const double pose[12]
 int lfx_odometry_pose(const lfx_odometry *odometry, double pose[12]);   /* CurrentPose */
 /* The store (GetAll), the window (GetRecent), per-scan offsets and what was dropped. */
 int lfx_odometry_view(const lfx_odometry *odometry, lfx_odometry_store_view *view);
+/* EdgeSurfaceMap::Save(dirname) (edge_surface_map.hpp:66-70, through SaveMapIfNotEmpty, map_io.hpp:40-56): the store (GetAll)
+ * written as dirname/edge.pcd and dirname/surface.pcd with lfx_pcd_write, each only if that cloud is non-empty;
+ * written[0] / [1] = 1 where a file was written.  A store that has dropped scans (dropped_scans > 0) saves only the scans it
+ * kept.  Reads the store on `stream` (after the odometry's queued appends there); synchronous. */
+int lfx_odometry_save(lfx_ctx *ctx, const lfx_odometry *odometry, const char *dirname, int written[2], void *stream);
+
+/* --- map files (PCD) and the keyframe map builder (the mapping row) ---------------------------------------- */
+/* The mapping node (mapping/include/lidar_feature_mapping/map.hpp, mapping/src/mapping.cpp) builds a map from clouds and
+ * poses and writes it with pcl::io::save; the localization node reads maps with pcl::io::loadPCDFile<pcl::PointXYZ>
+ * (localization/app/localization.cpp:67-85).  These need no context and no device.
+ *
+ * lfx_pcd_read takes what loadPCDFile<pcl::PointXYZ> takes: v0.7 and v0.6 headers (# comment lines allowed; FIELDS, SIZE,
+ * TYPE, COUNT (optional, 1 each), WIDTH, HEIGHT, VIEWPOINT (parsed, not applied: PCL does not apply it either), POINTS,
+ * DATA; POINTS must be WIDTH x HEIGHT, an organised cloud is read in file order); DATA ascii (one point per line, values
+ * separated by white space; nan, inf and exponents), binary (records back to back, little-endian) and binary_compressed
+ * (uint32 compressed size, uint32 uncompressed size, one LZF block in liblzf's format holding one field after another).
+ * Fields are found by name; every field but x, y and z is skipped whatever its type and count (intensity, ring, curvature,
+ * rgb, normals, _ padding).  DEFINED DEVIATION: x, y and z must each be TYPE F, SIZE 4, COUNT 1, else
+ * LFX_ERR_UNSUPPORTED_FIELD (PCL loads zeros there with a warning).  An ascii line with the wrong number of values is
+ * LFX_ERR_FILE (PCL skips it with a warning).
+ * Output: records of 4 floats in file order, x, y, z and 1.0f (the 4th float of a pcl::PointXYZ).  points NULL: only the
+ * header is read, n_points = POINTS.  n_nonfinite (may be NULL) counts records with a non-finite coordinate; with
+ * drop_nonfinite set they are left out (lfx_map_create requires finite points), else kept.  capacity too small:
+ * LFX_ERR_CAPACITY with n_points = the records needed.  A file that cannot be read, or is not such a PCD file (truncated
+ * data, sizes that do not match, an LZF reference before the start of the output or a run past either end), is
+ * LFX_ERR_FILE; nothing is read or written out of bounds.  msg (may be NULL) gets one line naming the header line or the
+ * byte offset at fault. */
+int lfx_pcd_read(const char *path, float *points /* host [capacity][4] or NULL */, uint64_t capacity, int drop_nonfinite,
+                 uint64_t *n_points, uint64_t *n_nonfinite, char *msg, size_t msg_len);
+/* pcl::io::save(name, pcl::PointCloud<pcl::PointXYZ>): DATA binary, the header
+ *   # .PCD v0.7 - Point Cloud Data file format / VERSION 0.7 / FIELDS x y z / SIZE 4 4 4 / TYPE F F F / COUNT 1 1 1 /
+ *   WIDTH n / HEIGHT 1 / VIEWPOINT 0 0 0 1 0 0 0 / POINTS n / DATA binary
+ * (one line each, '\n'), then n x 12 bytes: x, y, z of every record (the 4th float is not written).  The header is this
+ * project's reading of PCL 1.12's PCDWriter::generateHeader; byte equality with a file PCL writes is UNPINNED (PCL is
+ * not available to build against).  The mapping node's own files carry extra curvature and ring columns (its PointType
+ * is PointXYZCR, mapping.cpp:56; zero for clouds taken from scan_edge); this writes x y z only, and lfx_pcd_read and
+ * loadPCDFile<PointXYZ> read either form.  n_points 0 is LFX_ERR_INVALID_ARGUMENT (PCL refuses an empty cloud; the
+ * reference's savers skip empty maps). */
+int lfx_pcd_write(const char *path, const float *points /* host [n][4] */, uint64_t n_points, char *msg, size_t msg_len);
+/* The two quantities PoseDiffIsSufficientlySmall (map.hpp:49-60) compares, with d = pose0.inverse() * pose1:
+ * translation = |d.translation()|, rotation = |Quaterniond(d.rotation()).vec()| (|sin(angle / 2)| of the relative
+ * rotation).  The test is translation < t_thr && rotation < r_thr.  Poses [R | t] row-major.  Eigen 3.4's arithmetic,
+ * restated in this order: inverse R0^T and -(R0^T t0); product R0^T R1 and R0^T t1 + (-(R0^T t0)); every 3-term sum as
+ * (a0 b0 + a1 b1) + a2 b2; rotation() of an Isometry is its linear part; the quaternion from the matrix as Eigen's
+ * (trace = (m00 + m11) + m22 > 0: s = 0.5 / sqrt(trace + 1), vec = (m21 - m12, m02 - m20, m10 - m01) * s; else the branch
+ * of the largest diagonal entry i, j = i+1, k = j+1 mod 3: t = sqrt(((mii - mjj) - mkk) + 1), q_i = 0.5 t, q_j = (mji +
+ * mij) * (0.5 / t), q_k = (mki + mik) * (0.5 / t)); norms as sqrt((x^2 + y^2) + z^2).  The decisions are pinned by the
+ * reference's vectors (test_map.cpp:34-65); bits against Eigen are UNPINNED (Eigen 3.3's rotation() ran a polar
+ * decomposition, which moves the last bits). */
+int lfx_pose_diff(const double pose0[12], const double pose1[12], double *translation, double *rotation);
+
+/* MapBuilder<PointType> (map.hpp:95-153) with its Map on the device: one mapper per map (an edge mapper and a surface
+ * mapper for the two files).  Per cloud, in order: empty -> LFX_KEYFRAME_EMPTY, nothing changes; else, where the map holds
+ * a point and lfx_pose_diff to the last added pose is below both thresholds -> LFX_KEYFRAME_TOO_CLOSE; else
+ * LFX_KEYFRAME_ADDED: the cloud, transformed by its pose, is appended to the map and becomes the last added pose.  The
+ * transform is odometry's (each coordinate ((r0*x + r1*y) + r2*z) + t in double, rounded once to float; the 4th float
+ * copied).  The map grows to max(need, 1.5 x capacity), capped at max_points; a call that would pass max_points returns
+ * LFX_ERR_CAPACITY, a failed allocation LFX_ERR_OUT_OF_MEMORY -- map, last pose, counters and outcomes untouched.
+ * Waits: outcomes and counters are final when a call returns; the append may still be queued on `stream` -- read the map
+ * (lfx_mapper_store_view.points) after `stream` has passed it, and keep a caller's device clouds until then.  Successive
+ * calls may use different streams: a growth copy and lfx_mapper_save are ordered behind the previous call's append. */
+typedef struct lfx_mapper lfx_mapper;
+typedef struct lfx_mapper_config {
+  double translation_threshold;      /* 1.0 (map.hpp:89) */
+  double rotation_threshold;         /* 0.1 (map.hpp:90): |sin(angle / 2)| of the relative rotation */
+  uint64_t initial_capacity_points;  /* records of 4 floats allocated at create: 2^20 */
+  uint64_t max_points;               /* the map never holds more: 2^32 - 1 (lfx_map_create takes uint32) */
+} lfx_mapper_config;
+void lfx_mapper_default_config(lfx_mapper_config *config);
+int lfx_mapper_create(lfx_ctx *ctx, const lfx_mapper_config *config, lfx_mapper **out);
+void lfx_mapper_destroy(lfx_mapper *mapper);
+#define LFX_KEYFRAME_ADDED 0
+#define LFX_KEYFRAME_EMPTY 1       /* "Empty cloud observed. Do nothing and continue" (map.hpp:118-121) */
+#define LFX_KEYFRAME_TOO_CLOSE 2   /* PoseDiffIsSufficientlySmall to the last added pose (map.hpp:123-129) */
+/* MapBuilder::Callback for n_clouds clouds on the device, in order.  Cloud s is d_count[s * count_stride] records of 4
+ * floats starting at record d_begin[s] of d_points (lfx_voxel_downsample's addressing: the last device batch's edge clouds
+ * are view.edge_points, view.scan_begin, view.scan_info + 2, 4; its surface clouds the same with + 3); total_points = the
+ * extent of d_points in records.  poses: host [n_clouds][12] ([R | t] row-major, finite); outcomes: host [n_clouds].  One
+ * wait (the counts and begins), then one kernel for every added cloud.  NULL pointers, n_clouds 0, count_stride 0,
+ * non-finite poses and clouds past total_points are LFX_ERR_INVALID_ARGUMENT. */
+int lfx_mapper_add(lfx_ctx *ctx, lfx_mapper *mapper, const float *d_points, const uint32_t *d_begin, const uint32_t *d_count,
+                   uint32_t count_stride, uint32_t n_clouds, size_t total_points, const double *poses /* host [n][12] */,
+                   uint8_t *outcomes /* host [n] */, void *stream);
+/* The same for one cloud on the host (the mapping node's subscriber), staged through a device buffer of the mapper's own. */
+int lfx_mapper_add_host(lfx_ctx *ctx, lfx_mapper *mapper, const float *points, uint32_t n_points, const double pose[12],
+                        uint8_t *outcome, void *stream);
+typedef struct lfx_mapper_store_view {
+  const float *points;               /* device: n_points records of 4 floats; valid until the next add (growth moves it) */
+  uint64_t n_points, capacity_points;
+  uint64_t n_added, n_empty, n_too_close;
+  int32_t has_pose;                  /* 0 until a cloud is added */
+  double last_pose[12];              /* prev_transform_: the pose of the last added cloud */
+} lfx_mapper_store_view;
+/* (the type is named as lfx_odometry_store_view is: a typedef may not share the function's name) */
+int lfx_mapper_view(const lfx_mapper *mapper, lfx_mapper_store_view *view);
+/* SaveMap (map.hpp:135-149): an empty map writes nothing, *written = 0 (the reference warns); else lfx_pcd_write of the
+ * map read on `stream`, *written = 1.  Synchronous. */
+int lfx_mapper_save(lfx_ctx *ctx, const lfx_mapper *mapper, const char *path, int *written, void *stream);
 
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device

@@ -80,6 +80,7 @@ public:
     cfg.outputs = outputs;
     const int rc = lfx_create(&ctx_, device, &params, &cfg);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(nullptr));}
+    max_points_ = max_points_per_scan;
   }
   ~FeatureExtraction()
   {
@@ -167,6 +168,8 @@ public:
     return out;
   }
   lfx_ctx * handle() const {return ctx_;}
+  // records the device clouds of the last scan may span (their buffers' extent: one scan of max_points_per_scan)
+  std::size_t CloudCapacity() const {return max_points_;}
 
 private:
   static void fill(
@@ -184,7 +187,28 @@ private:
   }
   lfx_ctx * ctx_ = nullptr;
   std::vector<void *> pinned_;
+  std::uint32_t max_points_ = 0;
 };
+
+// Map files (PCD) as pcl::io::loadPCDFile<pcl::PointXYZ> reads them and pcl::io::save writes them (lfx_pcd_read /
+// lfx_pcd_write): records of 4 floats, x, y, z, 1.0f.  No device.
+inline std::vector<float> ReadPcd(const std::string & path, bool drop_nonfinite = false)
+{
+  char msg[512];
+  std::uint64_t n = 0, bad = 0;
+  int rc = lfx_pcd_read(path.c_str(), nullptr, 0, drop_nonfinite ? 1 : 0, &n, &bad, msg, sizeof(msg));
+  std::vector<float> out(4 * static_cast<std::size_t>(n));
+  if (rc == LFX_OK) {rc = lfx_pcd_read(path.c_str(), out.data(), n, drop_nonfinite ? 1 : 0, &n, &bad, msg, sizeof(msg));}
+  if (rc != LFX_OK) {throw Error(rc, msg);}
+  out.resize(4 * static_cast<std::size_t>(n));
+  return out;
+}
+inline void WritePcd(const std::string & path, const std::vector<float> & points)
+{
+  char msg[512];
+  const int rc = lfx_pcd_write(path.c_str(), points.data(), points.size() / 4, msg, sizeof(msg));
+  if (rc != LFX_OK) {throw Error(rc, msg);}
+}
 
 // The consumer of the two clouds: Localizer of the reference's localization package (localization/include/
 // lidar_feature_localization/localizer.hpp:48-95) -- maps built once (there: two KD-trees in the problem's constructor),
@@ -210,6 +234,12 @@ public:
     const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     for (int i = 0; i < 12; i++) {last_.pose[i] = identity[i];}
   }
+  // The localization node's start (localization.cpp:78-85): both maps read from PCD files, records with a non-finite
+  // coordinate left out (lfx_map_create requires finite points).  The node runs max_iter 40 (localization.cpp:54).
+  Localizer(
+    const FeatureExtraction & fx, const std::string & edge_pcd_path, const std::string & surface_pcd_path,
+    int max_iter = 20, float cell_size = 1.0f)
+  : Localizer(fx, ReadPcd(edge_pcd_path, true), ReadPcd(surface_pcd_path, true), max_iter, cell_size) {}
   ~Localizer() {lfx_map_destroy(edge_); lfx_map_destroy(surface_);}
   Localizer(const Localizer &) = delete;
   Localizer & operator=(const Localizer &) = delete;
@@ -301,11 +331,81 @@ public:
     lfx_odometry_view(odometry_, &v);
     return v;
   }
+  // EdgeSurfaceMap::Save(dirname): dirname/edge.pcd and dirname/surface.pcd from the store, each only if non-empty
+  void Save(const std::string & dirname, int written[2] = nullptr) const
+  {
+    int w[2] = {0, 0};
+    const int rc = lfx_odometry_save(ctx_, odometry_, dirname.c_str(), w, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    if (written) {written[0] = w[0]; written[1] = w[1];}
+  }
 
 private:
   lfx_ctx * ctx_;
   lfx_odometry * odometry_ = nullptr;
   std::vector<lfx_odometry_result> results_;
+};
+
+// The keyframe map builder: MapBuilder<PointType> of the reference's mapping package (map.hpp:95-153; the node,
+// mapping.cpp) with its map on the device of `fx`, which must outlive the mapper.  One mapper per map: an edge mapper and a
+// surface mapper for the two files the localization node loads.  Poses are [R | t], row-major 3 x 4.
+class Mapper
+{
+public:
+  enum Which {kEdge = 2, kSurface = 3};     // the clouds of the last device batch (their count's word in scan_info)
+  static lfx_mapper_config DefaultConfig() {lfx_mapper_config c; lfx_mapper_default_config(&c); return c;}
+  explicit Mapper(const FeatureExtraction & fx, const lfx_mapper_config & config = DefaultConfig())
+  : fx_(fx)
+  {
+    const int rc = lfx_mapper_create(fx.handle(), &config, &mapper_);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx.handle()));}
+  }
+  ~Mapper() {lfx_mapper_destroy(mapper_);}
+  Mapper(const Mapper &) = delete;
+  Mapper & operator=(const Mapper &) = delete;
+
+  // MapBuilder::Callback for the edge or surface cloud of every scan the FeatureExtraction was last given (still on the
+  // device), one pose (12 doubles) per scan; the outcomes (LFX_KEYFRAME_*)
+  const std::vector<std::uint8_t> & Add(Which which, const std::vector<double> & poses)
+  {
+    lfx_device_view view{};
+    int rc = lfx_device_results(fx_.handle(), &view);
+    if (rc == LFX_OK && poses.size() != 12 * static_cast<std::size_t>(view.batch)) {rc = LFX_ERR_INVALID_ARGUMENT;}
+    if (rc == LFX_OK) {
+      outcomes_.assign(view.batch, 0);
+      rc = lfx_mapper_add(fx_.handle(), mapper_, which == kEdge ? view.edge_points : view.surface_points, view.scan_begin,
+        view.scan_info + which, 4, view.batch, fx_.CloudCapacity(), poses.data(), outcomes_.data(), nullptr);
+    }
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return outcomes_;
+  }
+  // MapBuilder::Callback for one cloud received from elsewhere (4 floats per point, as published)
+  std::uint8_t Add(const float * points, std::uint32_t n_points, const double pose[12])
+  {
+    std::uint8_t outcome = 0;
+    const int rc = lfx_mapper_add_host(fx_.handle(), mapper_, points, n_points, pose, &outcome, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return outcome;
+  }
+  lfx_mapper_store_view View() const
+  {
+    lfx_mapper_store_view v{};
+    lfx_mapper_view(mapper_, &v);
+    return v;
+  }
+  // SaveMap: false (and no file) for an empty map
+  bool Save(const std::string & path) const
+  {
+    int written = 0;
+    const int rc = lfx_mapper_save(fx_.handle(), mapper_, path.c_str(), &written, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return written != 0;
+  }
+
+private:
+  const FeatureExtraction & fx_;
+  lfx_mapper * mapper_ = nullptr;
+  std::vector<std::uint8_t> outcomes_;
 };
 
 }  // namespace lfx

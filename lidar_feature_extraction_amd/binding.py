@@ -99,6 +99,21 @@ class OdometryStoreView(C.Structure):
                 ("pose", C.c_double * 12)]
 
 
+class MapperConfig(C.Structure):
+    """lfx_mapper_config (MapBuilder's thresholds, map.hpp:89-90, and the map's capacity)."""
+    _fields_ = [("translation_threshold", C.c_double), ("rotation_threshold", C.c_double),
+                ("initial_capacity_points", C.c_uint64), ("max_points", C.c_uint64)]
+
+
+class MapperStoreView(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_uint64), ("capacity_points", C.c_uint64), ("n_added", C.c_uint64),
+                ("n_empty", C.c_uint64), ("n_too_close", C.c_uint64), ("has_pose", C.c_int32), ("last_pose", C.c_double * 12)]
+
+
+KEYFRAME_ADDED, KEYFRAME_EMPTY, KEYFRAME_TOO_CLOSE = 0, 1, 2
+ERR_CAPACITY, ERR_OUT_OF_MEMORY, ERR_UNSUPPORTED_FIELD, ERR_FILE = -4, -6, -8, -9
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -115,7 +130,9 @@ EXPORTS = [
     "lfx_scan_to_map_residuals", "lfx_edge_residuals", "lfx_align_message", "lfx_scan_to_map_align", "lfx_align_point_pairs",
     "lfx_localize_batch", "lfx_localize_host",
     "lfx_odometry_default_config", "lfx_odometry_create", "lfx_odometry_destroy", "lfx_odometry_update_batch", "lfx_odometry_update",
-    "lfx_odometry_update_host", "lfx_odometry_add", "lfx_odometry_pose", "lfx_odometry_view",
+    "lfx_odometry_update_host", "lfx_odometry_add", "lfx_odometry_pose", "lfx_odometry_view", "lfx_odometry_save",
+    "lfx_pcd_read", "lfx_pcd_write", "lfx_pose_diff", "lfx_mapper_default_config", "lfx_mapper_create", "lfx_mapper_destroy",
+    "lfx_mapper_add", "lfx_mapper_add_host", "lfx_mapper_view", "lfx_mapper_save",
     "lfx_layout_from_fields", "lfx_pack_xyz", "lfx_pack_xyz12", "lfx_pack_colored", "lfx_pack_features", "lfx_download_scan", "lfx_stage_ring", "lfx_stage_convolution1d",
     "lfx_stage_ring_projection", "lfx_label_to_color", "lfx_color_points_by_label", "lfx_set_profiling", "lfx_set_profiling_interval", "lfx_kernel_times", "lfx_kernel_name",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
@@ -208,6 +225,20 @@ def load(test_hooks=False):
     L.lfx_odometry_add.argtypes = [vp, vp, pd, vp, u32, vp, u32, vp]
     L.lfx_odometry_pose.argtypes = [vp, pd]
     L.lfx_odometry_view.argtypes = [vp, C.POINTER(OdometryStoreView)]
+    L.lfx_odometry_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
+    u64, p64 = C.c_uint64, C.POINTER(C.c_uint64)
+    L.lfx_pcd_read.argtypes = [C.c_char_p, vp, u64, i32, p64, p64, C.c_char_p, C.c_size_t]
+    L.lfx_pcd_write.argtypes = [C.c_char_p, vp, u64, C.c_char_p, C.c_size_t]
+    L.lfx_pose_diff.argtypes = [pd, pd, pd, pd]
+    L.lfx_mapper_default_config.argtypes = [C.POINTER(MapperConfig)]
+    L.lfx_mapper_default_config.restype = None
+    L.lfx_mapper_create.argtypes = [vp, C.POINTER(MapperConfig), C.POINTER(vp)]
+    L.lfx_mapper_destroy.argtypes = [vp]
+    L.lfx_mapper_destroy.restype = None
+    L.lfx_mapper_add.argtypes = [vp, vp, vp, vp, vp, u32, u32, C.c_size_t, pd, vp, vp]
+    L.lfx_mapper_add_host.argtypes = [vp, vp, vp, u32, pd, vp, vp]
+    L.lfx_mapper_view.argtypes = [vp, C.POINTER(MapperStoreView)]
+    L.lfx_mapper_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
     L.lfx_gather.argtypes = [vp, vp, i32, vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, vp]
     L.lfx_layout_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Layout)]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "lfx_kernels_transform.hpp"
+
 namespace lfx
 {
 
@@ -23,9 +25,7 @@ __device__ inline uint32_t odo_float_order(float f)
 
 constexpr int kAppendThreads = 256;
 
-// RecentScans::Add (recent_scans.hpp:67-73) for both clouds of one scan in one launch: pcl::transformPointCloud with an
-// Affine3d (PCL's generic Transformer<double>): every coordinate ((r0 * x + r1 * y) + r2 * z) + t in double, rounded once to
-// float (the unit is compiled with -ffp-contract=off: no fused multiply-add), the record's 4th float copied.  Workgroups
+// RecentScans::Add (recent_scans.hpp:67-73) for both clouds of one scan in one launch: pcl_transform_record.  Workgroups
 // [0, edge_blocks) take the edge cloud, the rest the surface cloud.  bounds [2][6] (edge, surface), zeroed before the launch:
 // words 0-2 the complement of the least x, y, z and words 3-5 the greatest, both by atomicMax over odo_float_order -- all
 // zero = no point.
@@ -39,12 +39,7 @@ __global__ __launch_bounds__(kAppendThreads) void odometry_append_kernel(
   uint32_t v[6] = {0u, 0u, 0u, 0u, 0u, 0u};
   if (i < n) {
     const float4 p = (surf ? surface_src : edge_src)[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    float4 q;
-    q.x = (float)(((P.m[0] * x + P.m[1] * y) + P.m[2] * z) + P.m[3]);
-    q.y = (float)(((P.m[4] * x + P.m[5] * y) + P.m[6] * z) + P.m[7]);
-    q.z = (float)(((P.m[8] * x + P.m[9] * y) + P.m[10] * z) + P.m[11]);
-    q.w = p.w;
+    const float4 q = pcl_transform_record(P.m, p);
     (surf ? surface_dst : edge_dst)[i] = q;
     v[0] = ~odo_float_order(q.x); v[1] = ~odo_float_order(q.y); v[2] = ~odo_float_order(q.z);
     v[3] = odo_float_order(q.x); v[4] = odo_float_order(q.y); v[5] = odo_float_order(q.z);

@@ -129,6 +129,7 @@ class FeatureExtraction:
             self._ctx = C.c_void_p()
             raise B.LfxError(rc, (self._L.lfx_last_error(None) or b"").decode())
         self.max_batch = max_batch
+        self.max_points_per_scan = max_points_per_scan
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:
@@ -289,6 +290,12 @@ class FeatureExtraction:
         surface_cell=1.0, edge_capacity_points, surface_capacity_points, initial_pose: 3 x 4)."""
         return Odometry(self, **config)
 
+    def mapper(self, **config):
+        """lfx_mapper_create: MapBuilder (map.hpp:95-153) with its map on this context's device.  Keywords: the fields of
+        lfx_mapper_config (translation_threshold=1.0, rotation_threshold=0.1, initial_capacity_points=2^20,
+        max_points=2^32 - 1)."""
+        return Mapper(self, **config)
+
     def set_ring_ids(self, ring_ids):
         """lfx_set_ring_ids: the sensor's ring ids for the device path (None: back to 0 .. max_rings-1)."""
         if ring_ids is None:
@@ -443,6 +450,66 @@ def layout_from_fields(fields, point_step, is_bigendian=False):
 
 
 
+def _msg_buffer():
+    return C.create_string_buffer(512)
+
+
+def read_pcd(path, drop_nonfinite=False, with_count=False):
+    """lfx_pcd_read: the records ([n, 4] float32: x, y, z, 1.0) of a PCD file as pcl::io::loadPCDFile<pcl::PointXYZ> reads
+    it (ascii, binary, binary_compressed).  drop_nonfinite: leave out records with a non-finite coordinate.  with_count:
+    return (records, records with a non-finite coordinate).  Raises LfxError (LFX_ERR_FILE, LFX_ERR_UNSUPPORTED_FIELD)
+    with the reader's message.  No device."""
+    L = B.load()
+    n, bad, msg = C.c_uint64(0), C.c_uint64(0), _msg_buffer()
+    rc = L.lfx_pcd_read(os.fsencode(path), None, 0, int(bool(drop_nonfinite)), C.byref(n), C.byref(bad), msg, len(msg))
+    if rc != 0:
+        raise B.LfxError(rc, msg.value.decode(errors="replace"))
+    out = np.zeros((max(int(n.value), 1), 4), np.float32)
+    rc = L.lfx_pcd_read(os.fsencode(path), C.c_void_p(out.ctypes.data), len(out), int(bool(drop_nonfinite)), C.byref(n), C.byref(bad),
+                        msg, len(msg))
+    if rc != 0:
+        raise B.LfxError(rc, msg.value.decode(errors="replace"))
+    out = out[:int(n.value)]
+    return (out, int(bad.value)) if with_count else out
+
+
+def write_pcd(path, points):
+    """lfx_pcd_write: records ([n, 4] or [n, 3] float32) as pcl::io::save writes a PointCloud<PointXYZ> (DATA binary).  No device."""
+    p = np.asarray(points, np.float32)
+    if p.ndim == 2 and p.shape[1] == 3:
+        p = np.hstack([p, np.ones((len(p), 1), np.float32)])
+    p = np.ascontiguousarray(p, np.float32).reshape(-1, 4)
+    msg = _msg_buffer()
+    rc = B.load().lfx_pcd_write(os.fsencode(path), C.c_void_p(p.ctypes.data), len(p), msg, len(msg))
+    if rc != 0:
+        raise B.LfxError(rc, msg.value.decode(errors="replace"))
+
+
+def pose_diff(pose0, pose1):
+    """lfx_pose_diff: (|d.translation()|, |Quaterniond(d.rotation()).vec()|) with d = pose0^-1 pose1 -- the two quantities
+    PoseDiffIsSufficientlySmall (map.hpp:49-60) compares.  Poses 3 x 4 [R | t].  No device."""
+    a = np.ascontiguousarray(pose0, np.float64).reshape(12)
+    b = np.ascontiguousarray(pose1, np.float64).reshape(12)
+    t, r = C.c_double(0), C.c_double(0)
+    pd = C.POINTER(C.c_double)
+    rc = B.load().lfx_pose_diff(a.ctypes.data_as(pd), b.ctypes.data_as(pd), C.byref(t), C.byref(r))
+    if rc != 0:
+        raise B.LfxError(rc, "invalid argument")
+    return t.value, r.value
+
+
+def _download(L, ptr, n_records, stream=0):
+    """n_records records of 4 floats from device address ptr (the HIP runtime liblfx.so is bound to)."""
+    out = np.zeros((int(n_records), 4), np.float32)
+    if n_records:
+        L.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.hipStreamSynchronize.argtypes = [C.c_void_p]
+        if L.hipMemcpyAsync(out.ctypes.data, int(ptr), out.nbytes, 2, C.c_void_p(int(stream))) != 0 or \
+                L.hipStreamSynchronize(C.c_void_p(int(stream))) != 0:
+            raise B.LfxError(-3, "cannot copy the map to the host")
+    return out
+
+
 class ScanMap:
     """lfx_map: the index a scan is matched against -- the place of the reference's KDTreeEigen (kdtree.hpp:50-71)."""
 
@@ -458,6 +525,12 @@ class ScanMap:
             B.check(fx._ctx, self._L.lfx_map_create(fx._ctx, C.c_void_p(int(d_points)), int(n_points), float(cell_size), C.byref(h),
                                                     C.c_void_p(int(stream))))
         self.handle = h
+
+    @classmethod
+    def from_pcd(cls, fx, path, cell_size=1.0, stream=0):
+        """A map from a PCD file, as the localization node loads its maps (localization.cpp:78-85): read with
+        lfx_pcd_read, records with a non-finite coordinate left out (lfx_map_create requires finite points)."""
+        return cls(fx, 0, 0, cell_size, stream, host_points=read_pcd(path, drop_nonfinite=True))
 
     def info(self):
         n, cell, dims = C.c_uint32(), C.c_float(), (C.c_int32 * 3)()
@@ -562,9 +635,104 @@ class Odometry:
                     edge_offsets=np.array(v.edge_offsets[:n + 1], np.uint32), surface_offsets=np.array(v.surface_offsets[:n + 1], np.uint32),
                     pose=np.array(v.pose[:], np.float64).reshape(3, 4))
 
+    def save(self, dirname, stream=0):
+        """lfx_odometry_save: EdgeSurfaceMap::Save(dirname) -- dirname/edge.pcd and dirname/surface.pcd from the store, each only
+        if non-empty.  Returns (edge written, surface written)."""
+        w = (C.c_int32 * 2)()
+        B.check(self._fx._ctx, self._L.lfx_odometry_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
+        return bool(w[0]), bool(w[1])
+
     def close(self):
         if self.handle:
             self._L.lfx_odometry_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mapper:
+    """lfx_mapper: MapBuilder<PointType> (map.hpp:95-153) with its map on the device -- per cloud: empty -> EMPTY; the pose too
+    close to the last added pose (PoseDiffIsSufficientlySmall) -> TOO_CLOSE; else ADDED, the cloud transformed by its pose
+    appended to the map.  Poses are 3 x 4 [R | t].  Outcomes: binding.KEYFRAME_ADDED / _EMPTY / _TOO_CLOSE."""
+
+    def __init__(self, fx, **config):
+        self._fx = fx
+        self._L = fx._L
+        cfg = B.MapperConfig()
+        self._L.lfx_mapper_default_config(C.byref(cfg))
+        for k, v in config.items():
+            if k not in dict(B.MapperConfig._fields_):
+                raise TypeError("unknown mapper setting %r" % k)
+            setattr(cfg, k, v)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_mapper_create(fx._ctx, C.byref(cfg), C.byref(h)))
+        self.handle = h
+        self.config = {k: getattr(cfg, k) for k, _ in B.MapperConfig._fields_}
+
+    @staticmethod
+    def _poses(poses, n):
+        pm = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if len(pm) != 12 * n:
+            raise ValueError("expected %d poses of 3 x 4" % n)
+        return pm
+
+    def add(self, d_points, d_begin, d_count, count_stride, n_clouds, total_points, poses, stream=0):
+        """lfx_mapper_add: MapBuilder::Callback for n_clouds device clouds (cloud s: d_count[s * count_stride] records from
+        record d_begin[s] of d_points); poses [n][3][4].  Returns the outcomes (uint8 [n])."""
+        n = int(n_clouds)
+        pm = self._poses(poses, n)
+        out = np.zeros(max(n, 1), np.uint8)
+        B.check(self._fx._ctx, self._L.lfx_mapper_add(
+            self._fx._ctx, self.handle, C.c_void_p(int(d_points)), C.c_void_p(int(d_begin)), C.c_void_p(int(d_count)), int(count_stride),
+            n, int(total_points), pm.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(out.ctypes.data), C.c_void_p(int(stream))))
+        return out[:n]
+
+    def add_batch(self, which, poses, stream=0):
+        """The edge ('edge') or surface ('surface') clouds of the last device batch, one pose per scan."""
+        if which not in ("edge", "surface"):
+            raise ValueError("which must be 'edge' or 'surface'")
+        v = self._fx.device_view()
+        pts = v.edge_points if which == "edge" else v.surface_points
+        info = int(v.scan_info) + 4 * (2 if which == "edge" else 3)
+        # (the batch's clouds lie inside the context's cloud buffers: max_points_per_scan x max_batch records)
+        return self.add(pts, v.scan_begin, info, 4, v.batch, self._fx.max_points_per_scan * self._fx.max_batch, poses, stream)
+
+    def add_host(self, points, pose, stream=0):
+        """lfx_mapper_add_host: one cloud ([n, 4] float32) on the host.  Returns its outcome."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        pm = self._poses(pose, 1)
+        out = C.c_uint8(0)
+        B.check(self._fx._ctx, self._L.lfx_mapper_add_host(
+            self._fx._ctx, self.handle, C.c_void_p(p.ctypes.data if len(p) else 0), len(p), pm.ctypes.data_as(C.POINTER(C.c_double)),
+            C.byref(out), C.c_void_p(int(stream))))
+        return int(out.value)
+
+    def view(self):
+        """lfx_mapper_view: the map's device address and size, the counters, the last added pose."""
+        v = B.MapperStoreView()
+        B.check(self._fx._ctx, self._L.lfx_mapper_view(self.handle, C.byref(v)))
+        return dict(points=v.points or 0, n_points=v.n_points, capacity_points=v.capacity_points, n_added=v.n_added,
+                    n_empty=v.n_empty, n_too_close=v.n_too_close, has_pose=bool(v.has_pose),
+                    last_pose=np.array(v.last_pose[:], np.float64).reshape(3, 4))
+
+    def points(self, stream=0):
+        """The map ([n, 4] float32) copied to the host after `stream`."""
+        v = self.view()
+        return _download(self._L, v["points"], v["n_points"], stream)
+
+    def save(self, path, stream=0):
+        """lfx_mapper_save: SaveMap -- nothing for an empty map.  Returns whether a file was written."""
+        w = C.c_int32(0)
+        B.check(self._fx._ctx, self._L.lfx_mapper_save(self._fx._ctx, self.handle, os.fsencode(path), C.byref(w), C.c_void_p(int(stream))))
+        return bool(w.value)
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_mapper_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
