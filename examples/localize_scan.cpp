@@ -1,13 +1,17 @@
 // localize_scan.cpp -- the consumer's side without ROS: lfx::Localizer (the drop-in for the reference's Localizer,
 // localization/include/lidar_feature_localization/localizer.hpp:48-95) over the two clouds of a scan.
 //
-//   localize_scan EDGE_MAP SURFACE_MAP SCAN RINGS COLS OUT [host]
+//   localize_scan EDGE_MAP SURFACE_MAP SCAN RINGS COLS OUT [host] [--report]
 //     EDGE_MAP, SURFACE_MAP   raw records of 4 floats (x, y, z, -)
 //     SCAN                    raw 32-byte PointXYZIR records (point_type.hpp:62-86)
 //     OUT                     two results, each 12 doubles pose [R | t], error, error_scale (doubles), iteration, code
 //                             (int32): first Update() on the extraction's own device clouds, then (with "host") Update on
 //                             the clouds as a separate consumer would receive them
+//     --report                the first Update also fills an lfx_align_report, printed as: the six standard deviations in the
+//                             order of geometry_msgs/PoseWithCovariance (x y z, rotation about X Y Z), rank, degenerate and
+//                             the shares of edge and surface residuals with weight 1
 //   The initial pose is a fixed small offset from the identity; tests/test_cpp_host.py compares with the CPU oracle.
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -59,9 +63,23 @@ int main(int argc, char ** argv)
     // the node's order of things: features of the scan, then the pose from them
     const lfx_scan_result view = extraction.ExtractFeaturesView(cloud.data(), cloud.size());
     localizer.Init(initial);
-    const bool ok = localizer.Update();
+    bool report = false;
+    for (int a = 7; a < argc; a++) {report = report || std::string(argv[a]) == "--report";}
+    lfx_align_report rep{};
+    const bool ok = report ? localizer.Update(&rep) : localizer.Update();
     put(out, localizer.Result());
     std::printf("update %s: iteration %d, %s\n", ok ? "succeeded" : "failed", localizer.Result().iteration, lfx_align_message(localizer.Result().code));
+    if (report && !rep.valid) {
+      std::printf("report: none (%s)\n", lfx_align_message(localizer.Result().code));
+    } else if (report) {
+      double ros[36];
+      lfx::CovarianceRos(localizer.Result().pose, rep.covariance, ros);
+      std::printf("report: std");
+      for (int a = 0; a < 6; a++) {std::printf(" %.17g", std::sqrt(ros[7 * a]));}
+      std::printf(" rank %d degenerate %d inliers %.17g %.17g\n", rep.rank, rep.degenerate,
+        rep.n_edge ? static_cast<double>(rep.n_edge_inliers) / rep.n_edge : 0.,
+        rep.n_surface ? static_cast<double>(rep.n_surface_inliers) / rep.n_surface : 0.);
+    }
     if (argc > 7 && std::string(argv[7]) == "host") {
       // scan_edge / scan_surface as a separate consumer gets them: x, y, z of the feature points, 4 floats per point
       std::vector<float> edge(view.edge_points, view.edge_points + 4 * static_cast<std::size_t>(view.n_edge));

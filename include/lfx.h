@@ -515,6 +515,61 @@ int lfx_localize_host(lfx_ctx *ctx, const lfx_map *edge_map, const lfx_map *surf
                       float surface_leaf, const float *edge_points, uint32_t n_edge, const float *surface_points,
                       uint32_t n_surface, const double initial_pose[12], lfx_align_result *result, void *stream);
 
+/* --- how good a pose is: the report of an alignment --------------------------------------------------------------------- */
+/* The reference's optimizer computes D = sum J^T J and A = sum w J^T J in every iteration (optimizer.cpp:40-72), asks D one
+ * yes / no question (IsDegenerate(D, 0.1), degenerate.cpp:32-37) and throws both away; its node publishes a constant
+ * covariance (subscriber.hpp:158-169).  The *_report calls below run the plain call (the results are the same bits) and then
+ * fill one record per scan AT THE POSE THE ALIGNMENT RETURNED (result.pose): one more Problem::Make there -- search and rows,
+ * the kernels the iterations use, the pose handed over as lfx_scan_to_map_residuals hands it over, so that entry point
+ * gives the rows the report was made from -- and one reduction.  The pose does not move.  Scans whose code is a success or
+ * LFX_ALIGN_MAX_ITERATION get a report; for the others (and where H holds a NaN or an eigen-solve does not settle) valid is
+ * 0 and every other byte of the record is 0.  w_i are the weights the optimizer would use at this pose:
+ * HuberDerivative(e_i / (Scale(e) + 1e-16)), k = 1.345, e_i = r_i . r_i, the three rows of an edge residual sharing one
+ * weight (ComputeErrors / NormalizeErrorScale / ComputeWeights, optimizer.cpp:100-128).  The residuals mix units (an edge
+ * residual is a cross product, a surface one a distance), as they do in the reference's cost: sigma2 is the variance of that
+ * mixture.  The covariance is the Gauss-Newton one: it knows nothing of the map's own noise, of wrong associations or of
+ * the robust scale's variance (DESIGN.md section 7 has the calibration measured on the synthetic room).  Sums are taken in a
+ * fixed order: the same inputs give the same bytes. */
+typedef struct lfx_align_report {
+  double information[36];   /* H = M^T (sum_i w_i J_i^T J_i) M, 6 x 6 row-major, in the optimizer's own coordinates dx
+                               (optimizer.cpp:87-98): dx[0:3] the rotation increment applied as q <- q * AngleAxis(dx[0:3])
+                               (the scan's frame), dx[3:6] the translation increment in the map frame; M = MakeM(q) */
+  double eigenvalues[6];    /* of H, ascending */
+  double eigenvectors[36];  /* row k: the unit eigenvector of eigenvalues[k]; sign: its largest-magnitude component > 0 */
+  double covariance[36];    /* sigma2 * sum_k v_k v_k^T / max(eigenvalues[k], floor),  floor = 1e-9 * eigenvalues[5]: finite,
+                               and LARGE along a direction the scan does not constrain */
+  double sigma2;            /* sum_i w_i e_i / (sum_i w_i dim_i - 6): weighted residual variance; dim_i = 3 for an edge
+                               residual and 1 for a surface one; NaN where the denominator is <= 0 */
+  double min_eigenvalue_d;  /* smallest eigenvalue of the 7 x 7 D = sum_i J_i^T J_i: what IsDegenerate compares with 0.1 */
+  double error, error_scale;/* sum_i e_i and Scale(e) (robust.cpp:37-51) at this pose */
+  double rms_edge, rms_surface;          /* sqrt(mean e_i) per kind; 0 where the kind has no row */
+  uint32_t n_edge, n_surface;            /* residuals of each kind */
+  uint32_t n_edge_inliers, n_surface_inliers;   /* those with w_i == 1 (HuberDerivative's first branch) */
+  uint32_t n_surface_no_plane;           /* surface rows that are zero rows (see LFX_ALIGN_NO_PLANE) */
+  int32_t rank;                          /* number of eigenvalues[k] > floor */
+  int32_t degenerate;                    /* IsDegenerate(D, 0.1): the update the optimizer would refuse here */
+  int32_t valid;                         /* 0: no report (empty input, LFX_ALIGN_EMPTY_INPUT / NO_PLANE / NOT_RUN, a NaN in H) */
+} lfx_align_report;
+/* The three calls above with one more argument: reports, host, [n_clouds] ([n_scans]; one record for lfx_localize_host). */
+int lfx_scan_to_map_align_report(lfx_ctx *ctx, const lfx_map *edge_map, const lfx_map *surface_map, uint32_t n_neighbors, int max_iter,
+                                 const float *d_edge_points, const uint32_t *d_edge_begin, const uint32_t *d_edge_count,
+                                 uint32_t edge_count_stride, uint32_t max_edge_points_per_cloud, size_t total_edge_points,
+                                 const float *d_surface_points, const uint32_t *d_surface_begin, const uint32_t *d_surface_count,
+                                 uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
+                                 uint32_t n_clouds, const double *initial_poses, lfx_align_result *results,
+                                 lfx_align_report *reports, void *stream);
+int lfx_localize_batch_report(lfx_ctx *ctx, const lfx_map *edge_map, const lfx_map *surface_map, uint32_t n_neighbors, int max_iter,
+                              float surface_leaf, uint32_t n_scans, const double *initial_poses, lfx_align_result *results,
+                              lfx_align_report *reports, void *stream);
+int lfx_localize_host_report(lfx_ctx *ctx, const lfx_map *edge_map, const lfx_map *surface_map, uint32_t n_neighbors, int max_iter,
+                             float surface_leaf, const float *edge_points, uint32_t n_edge, const float *surface_points,
+                             uint32_t n_surface, const double initial_pose[12], lfx_align_result *result,
+                             lfx_align_report *report, void *stream);
+/* A report's covariance as geometry_msgs/PoseWithCovariance orders it (x, y, z, rotation about the fixed X, Y, Z axes):
+ * out = T C T^T with T = [[0, I], [R, 0]], R the rotation of `pose` (a rotation increment d in the scan's frame is R d in the
+ * map frame).  Host only, no context; every sum of three terms is (a0 b0 + a1 b1) + a2 b2, unfused; out may be covariance. */
+int lfx_align_covariance_ros(const double pose[12], const double covariance[36], double out[36]);
+
 /* --- scan-to-local-map odometry (the odometry row) -------------------------------------------------------- */
 /* Odometry<PoseUpdater, EdgeSurfaceMap, EdgeSurfaceScan> (localization/include/lidar_feature_localization/odometry.hpp:52-63)
  * over EdgeSurfaceMap (edge_surface_map.hpp:38-76: two RecentScans, recent_scans.hpp:56-88), every cloud on the device.
@@ -585,6 +640,11 @@ int lfx_odometry_update_host(lfx_ctx *ctx, lfx_odometry *odometry, const float *
 int lfx_odometry_add(lfx_ctx *ctx, lfx_odometry *odometry, const double pose[12], const float *d_edge, uint32_t n_edge,
                      const float *d_surface, uint32_t n_surface, void *stream);
 int lfx_odometry_pose(const lfx_odometry *odometry, double pose[12]);   /* CurrentPose */
+/* Reports (lfx_align_report) of the scans the update* calls align: off by default.  lfx_odometry_reports copies those of the
+ * LAST update* call, one per scan in its order (valid 0 for a scan that was not aligned), at most `capacity` of them, and
+ * sets *n to how many there are (0 while reports are off). */
+int lfx_odometry_set_reports(lfx_odometry *odometry, int on);
+int lfx_odometry_reports(const lfx_odometry *odometry, lfx_align_report *out, uint32_t capacity, uint32_t *n);
 /* The store (GetAll), the window (GetRecent), per-scan offsets and what was dropped. */
 int lfx_odometry_view(const lfx_odometry *odometry, lfx_odometry_store_view *view);
 /* EdgeSurfaceMap::Save(dirname) (edge_surface_map.hpp:66-70, through SaveMapIfNotEmpty, map_io.hpp:40-56): the store (GetAll)

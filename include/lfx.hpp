@@ -210,6 +210,14 @@ inline void WritePcd(const std::string & path, const std::vector<float> & points
   if (rc != LFX_OK) {throw Error(rc, msg);}
 }
 
+// A report's covariance (lfx_align_report::covariance: rotation increment in the scan's frame, then translation in the map
+// frame) in the order of geometry_msgs/PoseWithCovariance: x, y, z, rotation about the fixed X, Y, Z axes.  No device.
+inline void CovarianceRos(const double pose[12], const double covariance[36], double out[36])
+{
+  const int rc = lfx_align_covariance_ros(pose, covariance, out);
+  if (rc != LFX_OK) {throw Error(rc, "lfx_align_covariance_ros: a null pointer");}
+}
+
 // The consumer of the two clouds: Localizer of the reference's localization package (localization/include/
 // lidar_feature_localization/localizer.hpp:48-95) -- maps built once (there: two KD-trees in the problem's constructor),
 // Init(pose), Update(scan) -> success, Get() -> pose.  Poses are [R | t], row-major 3 x 4.
@@ -252,23 +260,36 @@ public:
   bool IsInitialized() const {return initialized_;}
   const double * Get() const {return last_.pose;}
   const lfx_align_result & Result() const {return last_;}      // OptimizationResult of the last Update
+  // How good that pose is (information matrix, covariance, degeneracy, inliers), if the last Update was given a report to
+  // fill; valid == 0 otherwise.  The reference's node publishes a constant here (subscriber.hpp:158-169).
+  const lfx_align_report & LastReport() const {return report_;}
 
   // Update with the scan the FeatureExtraction was last given (its clouds are still on the device: nothing is copied)
-  bool Update()
+  bool Update() {return Update(static_cast<lfx_align_report *>(nullptr));}
+  // (with a report: one more search and row build at the returned pose and one reduction; the pose is the same bits)
+  bool Update(lfx_align_report * report)
   {
     lfx_align_result r{};
-    const int rc = lfx_localize_batch(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, 1u, last_.pose, &r, nullptr);
+    report_ = lfx_align_report{};
+    const int rc = report ?
+      lfx_localize_batch_report(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, 1u, last_.pose, &r, &report_, nullptr) :
+      lfx_localize_batch(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, 1u, last_.pose, &r, nullptr);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     last_ = r;
+    if (report) {*report = report_;}
     return LFX_ALIGN_SUCCESS(r.code);
   }
   // Update with clouds received from elsewhere (scan_edge / scan_surface as published: 4 floats per point)
-  bool Update(const float * edge, std::uint32_t n_edge, const float * surface, std::uint32_t n_surface)
+  bool Update(const float * edge, std::uint32_t n_edge, const float * surface, std::uint32_t n_surface, lfx_align_report * report = nullptr)
   {
     lfx_align_result r{};
-    const int rc = lfx_localize_host(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, edge, n_edge, surface, n_surface, last_.pose, &r, nullptr);
+    report_ = lfx_align_report{};
+    const int rc = report ?
+      lfx_localize_host_report(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, edge, n_edge, surface, n_surface, last_.pose, &r, &report_, nullptr) :
+      lfx_localize_host(ctx_, edge_, surface_, kNeighbors, max_iter_, 1.0f, edge, n_edge, surface, n_surface, last_.pose, &r, nullptr);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     last_ = r;
+    if (report) {*report = report_;}
     return LFX_ALIGN_SUCCESS(r.code);
   }
 
@@ -278,6 +299,7 @@ private:
   int max_iter_;
   lfx_map * edge_ = nullptr, * surface_ = nullptr;
   lfx_align_result last_{};
+  lfx_align_report report_{};
   bool initialized_ = false;
 };
 
@@ -318,6 +340,22 @@ public:
     const int rc = lfx_odometry_update_host(ctx_, odometry_, edge, n_edge, surface, n_surface, results_.data(), nullptr);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     return results_[0];
+  }
+  // Reports of the scans the Update calls align (off by default): Reports() = those of the last Update, one per scan,
+  // valid == 0 for a scan that was not aligned
+  void SetReports(bool on)
+  {
+    const int rc = lfx_odometry_set_reports(odometry_, on ? 1 : 0);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  std::vector<lfx_align_report> Reports() const
+  {
+    std::uint32_t n = 0;
+    int rc = lfx_odometry_reports(odometry_, nullptr, 0, &n);
+    std::vector<lfx_align_report> out(n);
+    if (rc == LFX_OK && n) {rc = lfx_odometry_reports(odometry_, out.data(), n, &n);}
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return out;
   }
   std::vector<double> CurrentPose() const
   {

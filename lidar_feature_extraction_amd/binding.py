@@ -80,6 +80,15 @@ class AlignResult(C.Structure):
                 ("code", C.c_int32)]
 
 
+class AlignReport(C.Structure):
+    """lfx_align_report: information matrix, its eigen-decomposition, covariance, degeneracy and fit counts at result.pose."""
+    _fields_ = [("information", C.c_double * 36), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36),
+                ("covariance", C.c_double * 36), ("sigma2", C.c_double), ("min_eigenvalue_d", C.c_double), ("error", C.c_double),
+                ("error_scale", C.c_double), ("rms_edge", C.c_double), ("rms_surface", C.c_double), ("n_edge", C.c_uint32),
+                ("n_surface", C.c_uint32), ("n_edge_inliers", C.c_uint32), ("n_surface_inliers", C.c_uint32),
+                ("n_surface_no_plane", C.c_uint32), ("rank", C.c_int32), ("degenerate", C.c_int32), ("valid", C.c_int32)]
+
+
 class OdometryConfig(C.Structure):
     """lfx_odometry_config (EdgeSurfaceMap(n_local_scans) + the problem Localizer::Update runs)."""
     _fields_ = [("n_local_scans", C.c_uint32), ("n_neighbors", C.c_uint32), ("max_iter", C.c_int32), ("surface_leaf", C.c_float),
@@ -129,6 +138,8 @@ EXPORTS = [
     "lfx_map_create", "lfx_map_create_host", "lfx_map_destroy", "lfx_map_info", "lfx_map_nearest",
     "lfx_scan_to_map_residuals", "lfx_edge_residuals", "lfx_align_message", "lfx_scan_to_map_align", "lfx_align_point_pairs",
     "lfx_localize_batch", "lfx_localize_host",
+    "lfx_scan_to_map_align_report", "lfx_localize_batch_report", "lfx_localize_host_report", "lfx_align_covariance_ros",
+    "lfx_odometry_set_reports", "lfx_odometry_reports",
     "lfx_odometry_default_config", "lfx_odometry_create", "lfx_odometry_destroy", "lfx_odometry_update_batch", "lfx_odometry_update",
     "lfx_odometry_update_host", "lfx_odometry_add", "lfx_odometry_pose", "lfx_odometry_view", "lfx_odometry_save",
     "lfx_pcd_read", "lfx_pcd_write", "lfx_pose_diff", "lfx_mapper_default_config", "lfx_mapper_create", "lfx_mapper_destroy",
@@ -213,6 +224,13 @@ def load(test_hooks=False):
     L.lfx_align_point_pairs.argtypes = [vp, vp, vp, vp, vp, u32, C.c_size_t, u32, i32, pd, pres, vp]
     L.lfx_localize_batch.argtypes = [vp, vp, vp, u32, i32, C.c_float, u32, pd, pres, vp]
     L.lfx_localize_host.argtypes = [vp, vp, vp, u32, i32, C.c_float, vp, u32, vp, u32, pd, pres, vp]
+    prep = C.POINTER(AlignReport)
+    L.lfx_scan_to_map_align_report.argtypes = L.lfx_scan_to_map_align.argtypes[:-1] + [prep, vp]
+    L.lfx_localize_batch_report.argtypes = [vp, vp, vp, u32, i32, C.c_float, u32, pd, pres, prep, vp]
+    L.lfx_localize_host_report.argtypes = [vp, vp, vp, u32, i32, C.c_float, vp, u32, vp, u32, pd, pres, prep, vp]
+    L.lfx_align_covariance_ros.argtypes = [pd, pd, pd]
+    L.lfx_odometry_set_reports.argtypes = [vp, C.c_int]
+    L.lfx_odometry_reports.argtypes = [vp, prep, u32, C.POINTER(u32)]
     L.lfx_downsample_surface.argtypes = [vp, C.c_float, vp, vp, vp, vp]
     L.lfx_odometry_default_config.argtypes = [C.POINTER(OdometryConfig)]
     L.lfx_odometry_default_config.restype = None

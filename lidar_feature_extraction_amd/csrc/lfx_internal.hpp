@@ -310,6 +310,6 @@ int align_clouds(
   const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
   uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
   uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
-  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin);
+  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin, lfx_align_report * reports = nullptr);
 
 }  // namespace lfx_host

@@ -2,6 +2,7 @@
 // (lfx_kernels_localize.hpp).
 #include "lfx_internal.hpp"
 #include "lfx_kernels_localize.hpp"
+#include "lfx_kernels_report.hpp"
 
 using namespace lfx_host;
 
@@ -33,6 +34,33 @@ void grid_of(const double lo[3], const double hi[3], float cell_size, double & h
     if (cells <= limit) {break;}
     h *= std::max(1.05, std::cbrt(cells / limit));
   }
+}
+
+// Eigen::Quaterniond(Matrix3d) of a pose's rotation (the branch on the trace, then on the largest diagonal entry), on the
+// host: what lfx_scan_to_map_residuals hands its kernels beside pose[12], and what the report pass of run_align is given
+void map_pose_of(const double pose[12], lfx::MapPose & P)
+{
+  for (int i = 0; i < 12; i++) {P.m[i] = pose[i];}
+  auto M = [&](int r, int col) {return pose[4 * r + col];};
+  double q[3], w, t = M(0, 0) + M(1, 1) + M(2, 2);
+  if (t > 0.) {
+    t = std::sqrt(t + 1.0);
+    w = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (M(2, 1) - M(1, 2)) * t; q[1] = (M(0, 2) - M(2, 0)) * t; q[2] = (M(1, 0) - M(0, 1)) * t;
+  } else {
+    int i = 0;
+    if (M(1, 1) > M(0, 0)) {i = 1;}
+    if (M(2, 2) > M(i, i)) {i = 2;}
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = std::sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    w = (M(k, j) - M(j, k)) * t;
+    q[j] = (M(j, i) + M(i, j)) * t;
+    q[k] = (M(k, i) + M(i, k)) * t;
+  }
+  P.qw = w; P.qx = q[0]; P.qy = q[1]; P.qz = q[2];
 }
 
 void launch_rows(bool surface, const lfx::MapIndex & mi, const lfx::MapPose & P, uint32_t k, const float * d_points,
@@ -258,30 +286,7 @@ int lfx_scan_to_map_residuals(
   if (max_points_per_cloud == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   lfx::MapPose P;
-  for (int i = 0; i < 12; i++) {P.m[i] = pose[i];}
-  {
-    // Eigen::Quaterniond(Matrix3d): the branch on the trace, then on the largest diagonal entry
-    auto M = [&](int r, int col) {return pose[4 * r + col];};
-    double q[3], w, t = M(0, 0) + M(1, 1) + M(2, 2);
-    if (t > 0.) {
-      t = std::sqrt(t + 1.0);
-      w = 0.5 * t;
-      t = 0.5 / t;
-      q[0] = (M(2, 1) - M(1, 2)) * t; q[1] = (M(0, 2) - M(2, 0)) * t; q[2] = (M(1, 0) - M(0, 1)) * t;
-    } else {
-      int i = 0;
-      if (M(1, 1) > M(0, 0)) {i = 1;}
-      if (M(2, 2) > M(i, i)) {i = 2;}
-      const int j = (i + 1) % 3, k = (j + 1) % 3;
-      t = std::sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
-      q[i] = 0.5 * t;
-      t = 0.5 / t;
-      w = (M(k, j) - M(j, k)) * t;
-      q[j] = (M(j, i) + M(i, j)) * t;
-      q[k] = (M(k, i) + M(i, k)) * t;
-    }
-    P.qw = w; P.qx = q[0]; P.qy = q[1]; P.qz = q[2];
-  }
+  map_pose_of(pose, P);
   launch_rows(kind == LFX_RESIDUAL_SURFACE, map->index, P, n_neighbors, d_points, d_begin, d_count, count_stride, n_clouds,
     max_points_per_cloud, d_residual, d_jacobian, nullptr, static_cast<hipStream_t>(stream));
   LFX_HIP(c, hipGetLastError());
@@ -326,8 +331,9 @@ struct AlignProblem                     // what Problem::Make reads, per kind
 };
 
 int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_iter, const double * initial_poses,
-  lfx_align_result * results, hipStream_t st)
+  lfx_align_result * results, hipStream_t st, lfx_align_report * reports = nullptr)
 {
+  static_assert(sizeof(lfx::AlignReport) == sizeof(lfx_align_report), "the device's record is lfx_align_report");
   static_assert(sizeof(lfx::AlignState) % 8 == 0, "AlignState is an array of doubles' worth");
   if (n_clouds > 65535u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "at most 65535 scans per alignment call");}   // (a launch's y extent)
   const size_t state_d = sizeof(lfx::AlignState) / 8 * (size_t)n_clouds;
@@ -335,7 +341,9 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   const size_t partial_d = (size_t)n_clouds * lfx::kAlignSlices * lfx::kAlignTile;
   const size_t nbr_d = (size_t)lfx::kNearestMax / 2 * rows;                   // the searches' results: 16 words per row
   const size_t reach_d = rows;                                               // and how far each row's 16th neighbour was
-  const size_t need = state_d + 24 * pr.total3 + 8 * pr.total1 + rows + partial_d + nbr_d + reach_d + (n_clouds + 1) / 2 + 9;
+  const bool report = reports != nullptr && pr.X == nullptr;
+  const size_t sums_d = report ? sizeof(lfx::ReportSums) / 8 * (size_t)n_clouds : 0;
+  const size_t need = state_d + 24 * pr.total3 + 8 * pr.total1 + rows + partial_d + nbr_d + reach_d + (n_clouds + 1) / 2 + 9 + sums_d;
   if (c->align_scratch.n < need) {
     c->align_scratch.release();
     if (c->align_scratch.alloc(need) != hipSuccess) {
@@ -354,11 +362,15 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   uint32_t * nbr3 = reinterpret_cast<uint32_t *>(w), * nbr1 = nbr3 + (size_t)lfx::kNearestMax * pr.total3; w += nbr_d;
   double * reach3 = w, * reach1 = w + pr.total3; w += reach_d;
   uint32_t * d_tickets = reinterpret_cast<uint32_t *>(w); w += (n_clouds + 1) / 2;
-  uint32_t * d_active = reinterpret_cast<uint32_t *>(w);
+  uint32_t * d_active = reinterpret_cast<uint32_t *>(w); w += 9;
+  lfx::ReportSums * d_sums = reinterpret_cast<lfx::ReportSums *>(w);
   // Pinned host memory, read and written by the kernels themselves: [the caller's poses | a result record per scan].  No
   // copy is queued in either direction; the thread that ends a scan's iterations writes its record.
   const size_t pose_bytes = 96 * (size_t)n_clouds;
-  LFX_HIP(c, c->h_align.reserve(pose_bytes + sizeof(lfx::AlignOut) * (size_t)n_clouds));
+  // (with reports, behind those: [the report pass's poses | a report per scan | its done word])
+  const size_t out_bytes = sizeof(lfx::AlignOut) * (size_t)n_clouds;
+  const size_t report_bytes = report ? (sizeof(lfx::ReportPose) + sizeof(lfx::AlignReport) + 8) * (size_t)n_clouds : 0;
+  LFX_HIP(c, c->h_align.reserve(pose_bytes + out_bytes + report_bytes));
   std::memcpy(c->h_align.p, initial_poses, pose_bytes);
   volatile lfx::AlignOut * out = reinterpret_cast<volatile lfx::AlignOut *>(c->h_align.p + pose_bytes);
   void * d_pinned = nullptr;
@@ -368,7 +380,7 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   hipLaunchKernelGGL(lfx::align_begin_kernel, dim3((n_clouds + 63u) / 64u), dim3(64), 0, st, states, d_initial, n_clouds, d_active,
     d_tickets, d_out);
   const lfx::MapPose none{};
-  auto iteration = [&](int iter) {
+  auto make_rows = [&](int iter) {                  // Problem::Make at the states' poses
       if (pr.X) {
         if (pr.longest3) {
           hipLaunchKernelGGL(lfx::pair_rows_kernel, dim3((pr.longest3 + 127u) / 128u, n_clouds), dim3(128), 0, st, pr.X, pr.Y,
@@ -401,8 +413,11 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
           }
         }
       }
-      // (the step kernels only address rows)
-      const uint32_t * rb3 = pr.rbegin3 ? pr.rbegin3 : pr.begin3, * rb1 = pr.rbegin1 ? pr.rbegin1 : pr.begin1;
+    };
+  // (the step kernels only address rows)
+  const uint32_t * rb3 = pr.rbegin3 ? pr.rbegin3 : pr.begin3, * rb1 = pr.rbegin1 ? pr.rbegin1 : pr.begin1;
+  auto iteration = [&](int iter) {
+      make_rows(iter);
       hipLaunchKernelGGL(lfx::align_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, iter, r3, rb3, pr.count3,
         pr.stride3, r1, rb1, pr.count1, pr.stride1, d_weights, d_active, d_out);
       hipLaunchKernelGGL(lfx::align_update_kernel, dim3(lfx::kAlignSlices, n_clouds), dim3(lfx::kAlignThreads), 0, st, states, iter,
@@ -441,6 +456,55 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
     needed = std::max(needed, std::min(out[s].iteration + 1, max_iter));
   }
   c->align_guess = needed;
+  if (!reports) {return LFX_OK;}
+  // The reports: one more Problem::Make at the poses that were returned -- each handed over as lfx_scan_to_map_residuals
+  // hands a pose to the same row kernels, so the rows are the ones a caller gets there -- for the scans that have a pose to
+  // speak of, then the two report kernels.  The step kernels are not run: nothing moves.
+  std::memset(reports, 0, sizeof(lfx_align_report) * (size_t)n_clouds);
+  if (!report) {return LFX_OK;}
+  uint8_t * h_rep = c->h_align.p + pose_bytes + out_bytes;
+  lfx::ReportPose * h_pose = reinterpret_cast<lfx::ReportPose *>(h_rep);
+  volatile lfx::AlignReport * h_report = reinterpret_cast<volatile lfx::AlignReport *>(h_rep + sizeof(lfx::ReportPose) * (size_t)n_clouds);
+  volatile int32_t * h_done = reinterpret_cast<volatile int32_t *>(h_rep + (sizeof(lfx::ReportPose) + sizeof(lfx::AlignReport)) * (size_t)n_clouds);
+  uint32_t to_run = 0;
+  for (uint32_t s = 0; s < n_clouds; s++) {
+    const int code = results[s].code;
+    const bool run = LFX_ALIGN_SUCCESS(code) || code == LFX_ALIGN_MAX_ITERATION;
+    map_pose_of(results[s].pose, h_pose[s].pose);
+    h_pose[s].run = run ? 1 : 0; h_pose[s].pad = 0;
+    h_done[s] = run ? 0 : 1;
+    to_run += run ? 1u : 0u;
+  }
+  if (to_run == 0) {return LFX_OK;}
+  uint8_t * d_rep = static_cast<uint8_t *>(d_pinned) + pose_bytes + out_bytes;
+  hipLaunchKernelGGL(lfx::report_begin_kernel, dim3((n_clouds + 63u) / 64u), dim3(64), 0, st, states,
+    reinterpret_cast<const lfx::ReportPose *>(d_rep), n_clouds, d_tickets);
+  make_rows(1);                                       // (not the first search of these queries: it starts from the last one's reach)
+  hipLaunchKernelGGL(lfx::align_report_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, r3, rb3, pr.count3,
+    pr.stride3, r1, J1, rb1, pr.count1, pr.stride1, d_weights, d_sums);
+  hipLaunchKernelGGL(lfx::align_report_kernel, dim3(lfx::kAlignSlices, n_clouds), dim3(lfx::kAlignThreads), 0, st, states, r3, J3, rb3,
+    pr.count3, pr.stride3, r1, J1, rb1, pr.count1, pr.stride1, d_weights, d_sums, d_partials, d_tickets,
+    reinterpret_cast<lfx::AlignReport *>(d_rep + sizeof(lfx::ReportPose) * (size_t)n_clouds),
+    reinterpret_cast<int32_t *>(d_rep + (sizeof(lfx::ReportPose) + sizeof(lfx::AlignReport)) * (size_t)n_clouds));
+  LFX_HIP(c, hipGetLastError());
+  {
+    auto all_done = [&]() {
+        for (uint32_t s = 0; s < n_clouds; s++) {if (h_done[s] == 0) {return false;}}
+        return true;
+      };
+    hipError_t q = hipErrorNotReady;
+    for (uint32_t spins = 0; q == hipErrorNotReady; spins++) {      // (the wait on the records, as above)
+      if (all_done() || (spins & 63u) == 63u) {q = hipStreamQuery(st);}
+      if (spins > (1u << 24)) {q = hipStreamSynchronize(st);}
+    }
+    LFX_HIP(c, q);
+    if (!all_done()) {return fail(c, LFX_ERR_HIP, "the alignment's reports were not written");}   // (cannot happen)
+  }
+  for (uint32_t s = 0; s < n_clouds; s++) {
+    if (h_pose[s].run && h_report[s].valid) {
+      std::memcpy(&reports[s], const_cast<lfx::AlignReport *>(&h_report[s]), sizeof(lfx_align_report));
+    }
+  }
   return LFX_OK;
 }
 }  // namespace
@@ -472,7 +536,7 @@ int align_clouds(
   const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
   uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
   uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
-  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin)
+  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin, lfx_align_report * reports)
 {
   if (!c || !edge_map || !surface_map || !d_edge_points || !d_edge_begin || !d_edge_count || !d_surface_points ||
     !d_surface_begin || !d_surface_count || !initial_poses || !results || n_clouds == 0 || edge_count_stride == 0 ||
@@ -495,7 +559,7 @@ int align_clouds(
   pr.longest1 = max_surface_points_per_cloud; pr.total1 = total_surface_points;
   pr.n_neighbors = n_neighbors;
   pr.rbegin3 = d_edge_row_begin; pr.rbegin1 = d_surface_row_begin;
-  return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream));
+  return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream), reports);
 }
 }  // namespace lfx_host
 
@@ -511,7 +575,21 @@ int lfx_scan_to_map_align(
 {
   return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge_points, d_edge_begin, d_edge_count, edge_count_stride,
            max_edge_points_per_cloud, total_edge_points, d_surface_points, d_surface_begin, d_surface_count, surface_count_stride,
-           max_surface_points_per_cloud, total_surface_points, n_clouds, initial_poses, results, stream, nullptr, nullptr);
+           max_surface_points_per_cloud, total_surface_points, n_clouds, initial_poses, results, stream, nullptr, nullptr, nullptr);
+}
+
+int lfx_scan_to_map_align_report(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,
+  const float * d_edge_points, const uint32_t * d_edge_begin, const uint32_t * d_edge_count, uint32_t edge_count_stride,
+  uint32_t max_edge_points_per_cloud, size_t total_edge_points,
+  const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
+  uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
+  uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, lfx_align_report * reports, void * stream)
+{
+  if (!reports) {return LFX_ERR_INVALID_ARGUMENT;}
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge_points, d_edge_begin, d_edge_count, edge_count_stride,
+           max_edge_points_per_cloud, total_edge_points, d_surface_points, d_surface_begin, d_surface_count, surface_count_stride,
+           max_surface_points_per_cloud, total_surface_points, n_clouds, initial_poses, results, stream, nullptr, nullptr, reports);
 }
 
 int lfx_align_point_pairs(
@@ -528,9 +606,14 @@ int lfx_align_point_pairs(
   return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream));
 }
 
-int lfx_localize_batch(
+}  // extern "C"
+
+namespace
+{
+// lfx_localize_batch and lfx_localize_host, with or without the reports
+int localize_batch(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
-  uint32_t n_scans, const double * initial_poses, lfx_align_result * results, void * stream)
+  uint32_t n_scans, const double * initial_poses, lfx_align_result * results, lfx_align_report * reports, void * stream)
 {
   if (!c || !initial_poses || !results) {return LFX_ERR_INVALID_ARGUMENT;}
   if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
@@ -577,7 +660,7 @@ int lfx_localize_batch(
     const uint32_t guess1 = c->loc_guess[1] ? c->loc_guess[1] + c->loc_guess[1] / 8u : 2048u;
     const int ra = align_clouds(c, edge_map, surface_map, n_neighbors, max_iter,
       reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4, guess3, total,
-      down, c->scan_begin.p, down_count, 1, guess1, total, batch, initial_poses, results, stream, nullptr, nullptr);
+      down, c->scan_begin.p, down_count, 1, guess1, total, batch, initial_poses, results, stream, nullptr, nullptr, reports);
     if (ra == LFX_OK) {remember();}
     return ra;
   }
@@ -600,13 +683,13 @@ int lfx_localize_batch(
   LFX_HIP(c, hipStreamSynchronize(st));              // (run_align lays its own records over the pinned block)
   return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter,
            reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4, longest_edge, rows3,
-           down, c->scan_begin.p, down_count, 1, longest_surface, rows1, batch, initial_poses, results, stream, d_row3, d_row1);
+           down, c->scan_begin.p, down_count, 1, longest_surface, rows1, batch, initial_poses, results, stream, d_row3, d_row1, reports);
 }
 
-int lfx_localize_host(
+int localize_host(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
   const float * edge_points, uint32_t n_edge, const float * surface_points, uint32_t n_surface, const double initial_pose[12],
-  lfx_align_result * result, void * stream)
+  lfx_align_result * result, lfx_align_report * report, void * stream)
 {
   if (!c || !edge_map || !surface_map || !initial_pose || !result || (n_edge && !edge_points) || (n_surface && !surface_points)) {
     return LFX_ERR_INVALID_ARGUMENT;
@@ -644,8 +727,45 @@ int lfx_localize_host(
   } else {
     LFX_HIP(c, hipStreamSynchronize(st));             // the words have left the pinned block: the alignment stages through it too
   }
-  return lfx_scan_to_map_align(c, edge_map, surface_map, n_neighbors, max_iter, d_edge, d_words, d_words + 1, 1, n_edge, ne,
-           d_down, d_words, d_words + 3, 1, n_down, ns, 1, initial_pose, result, stream);
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge, d_words, d_words + 1, 1, n_edge, ne,
+           d_down, d_words, d_words + 3, 1, n_down, ns, 1, initial_pose, result, stream, nullptr, nullptr, report);
+}
+}  // namespace
+
+extern "C" {
+
+int lfx_localize_batch(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
+  uint32_t n_scans, const double * initial_poses, lfx_align_result * results, void * stream)
+{
+  return localize_batch(c, edge_map, surface_map, n_neighbors, max_iter, surface_leaf, n_scans, initial_poses, results, nullptr, stream);
+}
+
+int lfx_localize_batch_report(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
+  uint32_t n_scans, const double * initial_poses, lfx_align_result * results, lfx_align_report * reports, void * stream)
+{
+  if (!reports) {return LFX_ERR_INVALID_ARGUMENT;}
+  return localize_batch(c, edge_map, surface_map, n_neighbors, max_iter, surface_leaf, n_scans, initial_poses, results, reports, stream);
+}
+
+int lfx_localize_host(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
+  const float * edge_points, uint32_t n_edge, const float * surface_points, uint32_t n_surface, const double initial_pose[12],
+  lfx_align_result * result, void * stream)
+{
+  return localize_host(c, edge_map, surface_map, n_neighbors, max_iter, surface_leaf, edge_points, n_edge, surface_points, n_surface,
+           initial_pose, result, nullptr, stream);
+}
+
+int lfx_localize_host_report(
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, float surface_leaf,
+  const float * edge_points, uint32_t n_edge, const float * surface_points, uint32_t n_surface, const double initial_pose[12],
+  lfx_align_result * result, lfx_align_report * report, void * stream)
+{
+  if (!report) {return LFX_ERR_INVALID_ARGUMENT;}
+  return localize_host(c, edge_map, surface_map, n_neighbors, max_iter, surface_leaf, edge_points, n_edge, surface_points, n_surface,
+           initial_pose, result, report, stream);
 }
 
 }  // extern "C"

@@ -38,6 +38,8 @@ struct lfx_odometry
   DevBuf<float> down;                        // downsampled surface clouds of a batch, then their counts and statuses
   DevBuf<float4> staged;                     // lfx_odometry_update_host: the two clouds, edge first
   PinnedBuf pinned;                          // [12] bounds | [8] words | [batch][4] scan_info | [batch][2] lengths
+  bool reports_on = false;                   // lfx_odometry_set_reports
+  std::vector<lfx_align_report> reports;     // the scans of the last update* call (a scan that was not aligned: all zero)
   uint32_t n_scans() const {return (uint32_t)box.size();}
 };
 
@@ -190,7 +192,7 @@ void not_aligned(const double pose[12], lfx_odometry_result * r)
 }
 
 // Odometry::Update for one scan
-int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result * result, hipStream_t st)
+int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result * result, hipStream_t st, lfx_align_report * report)
 {
   const int how = room(o, in.n_edge, in.n_surface);
   if (how < 0) {return no_room(c, in.n_edge, in.n_surface);}
@@ -211,7 +213,7 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
       if (rc == LFX_OK) {
         rc = align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_points, in.edge_begin, in.edge_count, in.edge_stride,
           in.n_edge, in.n_edge, in.down_points, in.down_begin, in.down_count, 1, in.n_down, in.n_down, 1, o->pose, &r.align, st,
-          o->words.p, o->words.p);
+          o->words.p, o->words.p, report);
       }
       if (rc != LFX_OK) {return rc;}
       std::memcpy(pose, r.align.pose, sizeof(pose));    // pose_ = update(scan, pose_), whatever the code
@@ -321,6 +323,7 @@ int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, l
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint32_t batch = c->last_batch;
   const size_t total = c->h_scan_begin[batch];
+  o->reports.assign(o->reports_on ? batch : 0u, lfx_align_report{});
   if (hold(o->down, 4 * total + 2 * (size_t)batch) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");}
   LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
   float * down = o->down.p;
@@ -344,7 +347,7 @@ int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, l
     in.edge_points = reinterpret_cast<const float *>(c->edge_pts.p);
     in.edge_begin = c->scan_begin.p + s; in.edge_count = c->scan_info.p + lfx::kInfoEdge + 4 * s; in.edge_stride = 4;
     in.down_points = down; in.down_begin = c->scan_begin.p + s; in.down_count = down_count + s; in.n_down = lengths[2 * s + 1];
-    const int rc2 = step(c, o, in, results + s, st);
+    const int rc2 = step(c, o, in, results + s, st, o->reports_on ? &o->reports[s] : nullptr);
     if (rc2 != LFX_OK) {return rc2;}
   }
   return LFX_OK;
@@ -377,7 +380,8 @@ int lfx_odometry_update(lfx_ctx * c, lfx_odometry * o, const float * d_edge, uin
   in.surface = reinterpret_cast<const float4 *>(d_surface); in.n_surface = n_surface;
   in.edge_points = d_edge ? d_edge : any; in.edge_begin = o->words.p; in.edge_count = o->words.p + 1; in.edge_stride = 1;
   in.down_points = o->down.p; in.down_begin = o->words.p; in.down_count = o->words.p + 3; in.n_down = n_surface;
-  return step(c, o, in, result, st);
+  o->reports.assign(o->reports_on ? 1u : 0u, lfx_align_report{});
+  return step(c, o, in, result, st, o->reports_on ? &o->reports[0] : nullptr);
 }
 
 int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, uint32_t n_edge, const float * surface,
@@ -406,6 +410,23 @@ int lfx_odometry_add(lfx_ctx * c, lfx_odometry * o, const double pose[12], const
   LFX_HIP(c, hipSetDevice(c->device));
   return append(c, o, how, pose, reinterpret_cast<const float4 *>(d_edge), n_edge, reinterpret_cast<const float4 *>(d_surface), n_surface,
            static_cast<hipStream_t>(stream));
+}
+
+int lfx_odometry_set_reports(lfx_odometry * o, int on)
+{
+  if (!o) {return LFX_ERR_INVALID_ARGUMENT;}
+  o->reports_on = on != 0;
+  if (!o->reports_on) {o->reports.clear();}
+  return LFX_OK;
+}
+
+int lfx_odometry_reports(const lfx_odometry * o, lfx_align_report * out, uint32_t capacity, uint32_t * n)
+{
+  if (!o || !n || (capacity && !out)) {return LFX_ERR_INVALID_ARGUMENT;}
+  *n = (uint32_t)o->reports.size();
+  const uint32_t take = std::min(capacity, *n);
+  if (take) {std::memcpy(out, o->reports.data(), sizeof(lfx_align_report) * take);}
+  return LFX_OK;
 }
 
 int lfx_odometry_pose(const lfx_odometry * o, double pose[12])

@@ -414,4 +414,28 @@ int lfx_pose_diff(const double pose0[12], const double pose1[12], double * trans
   return LFX_OK;
 }
 
+// A report's covariance in the order of geometry_msgs/PoseWithCovariance (include/lfx.h): out = T C T^T, T = [[0, I], [R, 0]].
+// Every sum of three terms is (a0 b0 + a1 b1) + a2 b2 (this file is built with contraction off).
+int lfx_align_covariance_ros(const double pose[12], const double covariance[36], double out[36])
+{
+  if (!pose || !covariance || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  auto R = [&](int r, int c) {return pose[4 * r + c];};
+  double tc[36];                                      // T C: rows 0-2 = C's translation rows, rows 3-5 = R times its rotation rows
+  for (int c = 0; c < 6; c++) {
+    for (int i = 0; i < 3; i++) {
+      tc[6 * i + c] = covariance[6 * (3 + i) + c];
+      tc[6 * (3 + i) + c] = (R(i, 0) * covariance[c] + R(i, 1) * covariance[6 + c]) + R(i, 2) * covariance[12 + c];
+    }
+  }
+  double res[36];                                     // (out may be covariance)
+  for (int r = 0; r < 6; r++) {
+    for (int j = 0; j < 3; j++) {
+      res[6 * r + j] = tc[6 * r + 3 + j];
+      res[6 * r + 3 + j] = (tc[6 * r] * R(j, 0) + tc[6 * r + 1] * R(j, 1)) + tc[6 * r + 2] * R(j, 2);
+    }
+  }
+  std::memcpy(out, res, sizeof(res));
+  return LFX_OK;
+}
+
 }  // extern "C"

@@ -237,19 +237,40 @@ class FeatureExtraction:
                             message=self._L.lfx_align_message(r.code).decode()))
         return out
 
+    @staticmethod
+    def _align_reports(reps):
+        """lfx_align_report records as dicts: 6 x 6 matrices as arrays, the rest as numbers; `raw` keeps the record's bytes."""
+        out = []
+        for r in reps:
+            d = dict(information=np.array(r.information[:], np.float64).reshape(6, 6), eigenvalues=np.array(r.eigenvalues[:], np.float64),
+                     eigenvectors=np.array(r.eigenvectors[:], np.float64).reshape(6, 6),
+                     covariance=np.array(r.covariance[:], np.float64).reshape(6, 6), raw=bytes(r))
+            for k in ("sigma2", "min_eigenvalue_d", "error", "error_scale", "rms_edge", "rms_surface", "n_edge", "n_surface",
+                      "n_edge_inliers", "n_surface_inliers", "n_surface_no_plane", "rank"):
+                d[k] = getattr(r, k)
+            d["degenerate"] = bool(r.degenerate)
+            d["valid"] = bool(r.valid)
+            out.append(d)
+        return out
+
     def scan_to_map_align(self, edge_map, surface_map, n_neighbors, max_iter, d_edge_points,
                           d_edge_begin, d_edge_count, edge_count_stride, max_edge, total_edge, d_surface_points, d_surface_begin,
-                          d_surface_count, surface_count_stride, max_surface, total_surface, initial_poses, stream=0):
+                          d_surface_count, surface_count_stride, max_surface, total_surface, initial_poses, stream=0, report=False):
         """lfx_scan_to_map_align: Optimizer<LOAMOptimizationProblem>::Run (optimizer.hpp:79-123) per scan; initial_poses
-        [n][3][4]; returns one dict per scan (pose, error, error_scale, iteration, code, success, message)."""
+        [n][3][4]; returns one dict per scan (pose, error, error_scale, iteration, code, success, message).  report=True:
+        lfx_scan_to_map_align_report, returns (results, reports)."""
         poses = np.ascontiguousarray(initial_poses, np.float64).reshape(-1, 12)
         res = (B.AlignResult * len(poses))()
         v = lambda a: C.c_void_p(int(a))   # noqa: E731
-        B.check(self._ctx, self._L.lfx_scan_to_map_align(
-            self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter),
-            v(d_edge_points), v(d_edge_begin), v(d_edge_count), int(edge_count_stride), int(max_edge), int(total_edge),
-            v(d_surface_points), v(d_surface_begin), v(d_surface_count), int(surface_count_stride), int(max_surface),
-            int(total_surface), len(poses), poses.ctypes.data_as(C.POINTER(C.c_double)), res, v(stream)))
+        args = [self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter),
+                v(d_edge_points), v(d_edge_begin), v(d_edge_count), int(edge_count_stride), int(max_edge), int(total_edge),
+                v(d_surface_points), v(d_surface_begin), v(d_surface_count), int(surface_count_stride), int(max_surface),
+                int(total_surface), len(poses), poses.ctypes.data_as(C.POINTER(C.c_double)), res]
+        if report:
+            reps = (B.AlignReport * len(poses))()
+            B.check(self._ctx, self._L.lfx_scan_to_map_align_report(*args, reps, v(stream)))
+            return self._align_results(res), self._align_reports(reps)
+        B.check(self._ctx, self._L.lfx_scan_to_map_align(*args, v(stream)))
         return self._align_results(res)
 
     def align_point_pairs(self, d_source, d_target, d_begin, d_count, max_points, total_points, max_iter, initial_poses, stream=0):
@@ -262,22 +283,38 @@ class FeatureExtraction:
             int(max_iter), poses.ctypes.data_as(C.POINTER(C.c_double)), res, v(stream)))
         return self._align_results(res)
 
-    def localize_batch(self, edge_map, surface_map, initial_poses, n_neighbors=15, max_iter=20, surface_leaf=1.0, stream=0):
-        """lfx_localize_batch: Localizer::Update (localizer.hpp:71-80) for every scan of the last device batch."""
+    def localize_batch(self, edge_map, surface_map, initial_poses, n_neighbors=15, max_iter=20, surface_leaf=1.0, stream=0,
+                       report=False):
+        """lfx_localize_batch: Localizer::Update (localizer.hpp:71-80) for every scan of the last device batch.  report=True:
+        lfx_localize_batch_report, returns (results, reports)."""
         poses = np.ascontiguousarray(initial_poses, np.float64).reshape(-1, 12)
         res = (B.AlignResult * len(poses))()
+        if report:
+            reps = (B.AlignReport * len(poses))()
+            B.check(self._ctx, self._L.lfx_localize_batch_report(
+                self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter), float(surface_leaf), len(poses),
+                poses.ctypes.data_as(C.POINTER(C.c_double)), res, reps, C.c_void_p(int(stream))))
+            return self._align_results(res), self._align_reports(reps)
         B.check(self._ctx, self._L.lfx_localize_batch(
             self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter), float(surface_leaf), len(poses),
             poses.ctypes.data_as(C.POINTER(C.c_double)), res, C.c_void_p(int(stream))))
         return self._align_results(res)
 
     def localize_host(self, edge_map, surface_map, edge_points, surface_points, initial_pose, n_neighbors=15, max_iter=20,
-                      surface_leaf=1.0, stream=0):
-        """lfx_localize_host: Localizer::Update for one scan whose clouds ([n][4] float32) are on the host."""
+                      surface_leaf=1.0, stream=0, report=False):
+        """lfx_localize_host: Localizer::Update for one scan whose clouds ([n][4] float32) are on the host.  report=True:
+        lfx_localize_host_report, returns (result, report)."""
         e = np.ascontiguousarray(edge_points, np.float32).reshape(-1, 4)
         sf = np.ascontiguousarray(surface_points, np.float32).reshape(-1, 4)
         pose = np.ascontiguousarray(initial_pose, np.float64).reshape(12)
         res = (B.AlignResult * 1)()
+        if report:
+            reps = (B.AlignReport * 1)()
+            B.check(self._ctx, self._L.lfx_localize_host_report(
+                self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter), float(surface_leaf),
+                C.c_void_p(e.ctypes.data), len(e), C.c_void_p(sf.ctypes.data), len(sf), pose.ctypes.data_as(C.POINTER(C.c_double)),
+                res, reps, C.c_void_p(int(stream))))
+            return self._align_results(res)[0], self._align_reports(reps)[0]
         B.check(self._ctx, self._L.lfx_localize_host(
             self._ctx, edge_map.handle, surface_map.handle, int(n_neighbors), int(max_iter), float(surface_leaf),
             C.c_void_p(e.ctypes.data), len(e), C.c_void_p(sf.ctypes.data), len(sf), pose.ctypes.data_as(C.POINTER(C.c_double)), res,
@@ -498,6 +535,20 @@ def pose_diff(pose0, pose1):
     return t.value, r.value
 
 
+def covariance_ros(pose, covariance):
+    """lfx_align_covariance_ros: a report's 6 x 6 covariance (rotation increment in the scan's frame first, then the translation
+    in the map frame) in the order of geometry_msgs/PoseWithCovariance (x, y, z, rotation about the fixed X, Y, Z axes):
+    T C T^T with T = [[0, I], [R, 0]], R the rotation of `pose` (3 x 4).  No device."""
+    a = np.ascontiguousarray(pose, np.float64).reshape(12)
+    c = np.ascontiguousarray(covariance, np.float64).reshape(36)
+    out = np.zeros(36, np.float64)
+    pd = C.POINTER(C.c_double)
+    rc = B.load().lfx_align_covariance_ros(a.ctypes.data_as(pd), c.ctypes.data_as(pd), out.ctypes.data_as(pd))
+    if rc != 0:
+        raise B.LfxError(rc, "invalid argument")
+    return out.reshape(6, 6)
+
+
 def _download(L, ptr, n_records, stream=0):
     """n_records records of 4 floats from device address ptr (the HIP runtime liblfx.so is bound to)."""
     out = np.zeros((int(n_records), 4), np.float32)
@@ -559,7 +610,7 @@ class Odometry:
     """lfx_odometry: scan-to-local-map odometry -- Odometry<..., EdgeSurfaceMap, EdgeSurfaceScan> (odometry.hpp:52-63) with the
     store and the window maps on the device.  Poses are 3 x 4 [R | t] (point_to_map)."""
 
-    def __init__(self, fx, **config):
+    def __init__(self, fx, reports=False, **config):
         self._fx = fx
         self._L = fx._L
         cfg = B.OdometryConfig()
@@ -575,6 +626,21 @@ class Odometry:
         B.check(fx._ctx, self._L.lfx_odometry_create(fx._ctx, C.byref(cfg), C.byref(h)))
         self.handle = h
         self.config = {k: getattr(cfg, k) for k, _ in B.OdometryConfig._fields_ if k != "initial_pose"}
+        if reports:
+            self.set_reports(True)
+
+    def set_reports(self, on):
+        """lfx_odometry_set_reports: keep an lfx_align_report per scan of every update* call (off by default)."""
+        B.check(self._fx._ctx, self._L.lfx_odometry_set_reports(self.handle, int(bool(on))))
+
+    def reports(self):
+        """lfx_odometry_reports: the reports of the scans of the last update* call, one dict per scan (valid False for a scan
+        that was not aligned); empty while reports are off."""
+        n = C.c_uint32(0)
+        B.check(self._fx._ctx, self._L.lfx_odometry_reports(self.handle, None, 0, C.byref(n)))
+        reps = (B.AlignReport * max(n.value, 1))()
+        B.check(self._fx._ctx, self._L.lfx_odometry_reports(self.handle, reps, n.value, C.byref(n)))
+        return FeatureExtraction._align_reports(reps[:n.value])
 
     def _results(self, res):
         out = []

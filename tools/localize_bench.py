@@ -1,7 +1,10 @@
 """tools/localize_bench.py -- time of lfx_localize_batch (Localizer::Update for a batch of scans) on the
 GPU box, beside the CPU restatement (oracle, exhaustive neighbour search, one core) on a few scans.
 
-  python3 tools/localize_bench.py [--rings 64] [--cols 1800] [--batch 64] [--map-scans 40] [--cell 1.0] [--steps 5]
+  python3 tools/localize_bench.py [--rings 64] [--cols 1800] [--batch 64] [--map-scans 40] [--cell 1.0] [--steps 5] [--report]
+
+--report also times lfx_localize_batch_report (the same call with an lfx_align_report per scan) against the plain call, in
+this process and on these inputs, the two taking turns: "report" in the output.
 
 The maps are the edge / surface features of `map-scans` other scans of the synthetic scene, each moved to a pose of its own
 along a track (so that the map is larger than one scan's surroundings, as a localizer's map is)."""
@@ -17,10 +20,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(rings=64, cols=1800, batch=64, map_scans=40, cell=1.0, steps=5, max_iter=20, cpu_scans=0, whole_map=False, device=0, kd_scans=0):
+def run(rings=64, cols=1800, batch=64, map_scans=40, cell=1.0, steps=5, max_iter=20, cpu_scans=0, whole_map=False, device=0, kd_scans=0,
+        report=False):
     """The measurement as a function (bench.py reports it beside the extraction numbers)."""
     return _measure(argparse.Namespace(rings=rings, cols=cols, batch=batch, map_scans=map_scans, cell=cell, steps=steps, max_iter=max_iter,
-                                       cpu_scans=cpu_scans, whole_map=whole_map, device=device, kd_scans=kd_scans))
+                                       cpu_scans=cpu_scans, whole_map=whole_map, device=device, kd_scans=kd_scans, report=report))
 
 
 def main():
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--cpu-scans", type=int, default=2)
     ap.add_argument("--whole-map", action="store_true", help="also time maps without a grid")
     ap.add_argument("--kd-scans", type=int, default=2, help="scans of the KD-tree host baseline (scipy.spatial.cKDTree, one thread)")
+    ap.add_argument("--report", action="store_true", help="also time the call with reports against the plain call")
     a = ap.parse_args()
     a.device = 0
     print(json.dumps(_measure(a)))
@@ -114,6 +119,28 @@ def _measure(a):
     out["codes"] = {str(c): int(sum(r["code"] == c for r in res)) for c in range(5)}
     out["pose_error_after"] = float(np.median([np.abs(r["pose"][:, 3] - [3.0 * (i % a.map_scans), 0.5 * ((i % a.map_scans) % 5), 0]).max()
                                                for i, r in enumerate(res)]))
+    if getattr(a, "report", False):
+        # the plain call and the call with reports take turns (the same clocks, the same box, the same inputs); medians
+        fx.extract_batch_device(d.data_ptr(), n_points, stream)
+        fx.localize_batch(emap, smap, poses, 15, a.max_iter, 1.0, stream, report=True)     # warm-up (its scratch, its pinned block)
+        torch.cuda.synchronize()
+        t_plain, t_rep = [], []
+        for _ in range(max(a.steps, 3)):
+            t0 = time.perf_counter()
+            plain = fx.localize_batch(emap, smap, poses, 15, a.max_iter, 1.0, stream)
+            t1 = time.perf_counter()
+            with_rep, reps = fx.localize_batch(emap, smap, poses, 15, a.max_iter, 1.0, stream, report=True)
+            t2 = time.perf_counter()
+            t_plain.append(t1 - t0)
+            t_rep.append(t2 - t1)
+        tp, tr = float(np.median(t_plain)), float(np.median(t_rep))
+        out["report"] = {
+            "plain_ms_per_scan": round(1e3 * tp / a.batch, 4), "report_ms_per_scan": round(1e3 * tr / a.batch, 4), "ratio": round(tr / tp, 3),
+            "repeats": len(t_plain), "same_results": all(x["pose"].tobytes() == y["pose"].tobytes() for x, y in zip(plain, with_rep)),
+            "valid": int(sum(r["valid"] for r in reps)), "degenerate": int(sum(r["degenerate"] for r in reps)),
+            "rank_min": int(min(r["rank"] for r in reps if r["valid"])) if any(r["valid"] for r in reps) else None,
+            "edge_inlier_share": float(np.mean([r["n_edge_inliers"] / max(r["n_edge"], 1) for r in reps])),
+            "surface_inlier_share": float(np.mean([r["n_surface_inliers"] / max(r["n_surface"], 1) for r in reps]))}
     if a.whole_map:
         em0, sm0 = fx.make_map(d_emap.data_ptr(), len(edge_map), 0.0, stream), fx.make_map(d_smap.data_ptr(), len(surf_map), 0.0, stream)
         res0, t_whole = timed(em0, sm0, max(1, a.steps // 3))
