@@ -161,7 +161,8 @@ enum lfx_error {
   LFX_ERR_NO_RING_FIELD = -7,     /* the cloud has no "ring" field: RingIsAvailable (ring.cpp:36-44) is false and the
                                    * node shuts down (feature_extraction.cpp:103-108)            */
   LFX_ERR_UNSUPPORTED_FIELD = -8, /* x / y / z missing or not FLOAT32, ring not an integer, field outside point_step */
-  LFX_ERR_FILE = -9               /* a file cannot be opened, read or written, or it is not a PCD file lfx_pcd_read takes */
+  LFX_ERR_FILE = -9,              /* a file cannot be opened, read or written, or it is not a PCD file lfx_pcd_read takes */
+  LFX_ERR_NO_TIME_FIELD = -10     /* the cloud has no per-point time field (lfx_time_field_from_fields) */
 };
 
 typedef struct lfx_ctx lfx_ctx;
@@ -745,6 +746,76 @@ int lfx_mapper_view(const lfx_mapper *mapper, lfx_mapper_store_view *view);
 /* SaveMap (map.hpp:135-149): an empty map writes nothing, *written = 0 (the reference warns); else lfx_pcd_write of the
  * map read on `stream`, *written = 1.  Synchronous. */
 int lfx_mapper_save(lfx_ctx *ctx, const lfx_mapper *mapper, const char *path, int *written, void *stream);
+
+/* --- de-skew: the sensor's motion during a sweep taken out of the feature clouds ------------------------------------------ */
+/* A spinning lidar reports every point in the sensor frame of its own firing time; everything above treats a scan as one
+ * instant.  No reference counterpart (the reference has an unused imu_integration package beside its pipeline); the model
+ * is LOAM's.  A sweep has a start time t0, an end time t1 != t0 and a MOTION D = [R_D | t_D] (3 x 4 row-major doubles): the
+ * sensor frame at t1 expressed in the sensor frame at t0 (D = P0^-1 P1 for world poses P0, P1).  A point measured at time t
+ * has alpha = (t - t0) * (1 / (t1 - t0)), not clamped; the sensor frame at alpha, in the frame at t0, is
+ * M(alpha) = [Exp(alpha w) | alpha v], w = Log(R_D) (angle-axis vector), v = t_D: the rotation along the geodesic, the
+ * translation linear.  M(1) = D.
+ *   LFX_DESKEW_TO_START  p' = Exp(alpha w) p + alpha v
+ *   LFX_DESKEW_TO_END    p' = R_D^T (Exp(alpha w) p + alpha v - t_D)
+ * Arithmetic: double from the float record, unfused; theta and w as lfx_motion_twist gives them, k = w / theta,
+ * a = alpha * theta, c = cos a, s = sin a, kxp = k x p, kdp = (kx px + ky py) + kz pz,
+ * r = (p c + kxp s) + k (kdp (1 - c)); where theta < 1e-8 (zero included) r = p + alpha (w x p); m = r + alpha v; TO_START
+ * rounds m once to float; TO_END takes u = m - t_D and rounds (R_D[0][i] u0 + R_D[1][i] u1) + R_D[2][i] u2 once to float.
+ * The record's 4th float (the curvature) is copied.  A record whose alpha is not finite is copied unchanged. */
+#define LFX_TIME_FROM_INDEX 0u   /* alpha = index / n_points of the scan: the records arrive in firing order */
+#define LFX_TIME_FROM_FIELD 1u   /* t = (double)value * scale, read from the point record */
+typedef struct lfx_time_field {
+  uint32_t source;                 /* LFX_TIME_FROM_* */
+  uint32_t offset;                 /* of the field inside a point record (FROM_FIELD) */
+  uint32_t datatype;               /* LFX_FIELD_FLOAT32, LFX_FIELD_FLOAT64 or LFX_FIELD_UINT32 (FROM_FIELD) */
+  uint32_t big_endian;
+  double scale;                    /* seconds per unit of the field */
+} lfx_time_field;
+typedef struct lfx_sweep { double t0, t1; double motion[12]; } lfx_sweep;   /* t0, t1 unused with LFX_TIME_FROM_INDEX */
+#define LFX_DESKEW_TO_START 0
+#define LFX_DESKEW_TO_END 1
+/* The time channel of a message's field list: the first field named t, time, timestamp, time_stamp or offset_time with
+ * count 1.  FLOAT32 / FLOAT64 get scale 1.0 (seconds), UINT32 gets 1e-9 (nanoseconds: Ouster's t, Livox's offset_time).
+ * LFX_ERR_NO_TIME_FIELD where there is none; LFX_ERR_UNSUPPORTED_FIELD for another datatype or a field past point_step.
+ * Host only. */
+int lfx_time_field_from_fields(const lfx_point_field *fields, uint32_t n_fields, uint32_t point_step, int is_bigendian,
+                               lfx_time_field *out);
+/* Motions, host only, no context, in lfx_pose_diff's arithmetic (every 3-term sum (a0 b0 + a1 b1) + a2 b2, unfused):
+ *   lfx_motion_between  motion = pose0^-1 pose1 (the product lfx_pose_diff forms); two poses of equal values give the
+ *                       identity itself (R^T R as it rounds is not), so that a sensor at rest changes no bit of a cloud
+ *   lfx_motion_twist    w = Log(R_D) and theta = |w| as the de-skew kernel is given them: the quaternion of the matrix as
+ *                       lfx_pose_diff states it (q_w = 0.5 sqrt(trace + 1) in the first branch, (m_kj - m_jk) * (0.5 / t) in
+ *                       the second), n = |vec|, theta = 2 atan2(n, q_w), w = vec * (theta / n); n == 0: w = 0, theta = 0
+ *   lfx_motion_scale    out = [Exp(ratio w) | ratio t_D] (a sweep shorter than the scan period), the rotation as the kernel
+ *                       forms it: R = c I + s [k]x + (1 - c) k k^T with a = ratio * theta; theta < 1e-8: I + ratio [w]x */
+int lfx_motion_between(const double pose0[12], const double pose1[12], double motion[12]);
+int lfx_motion_twist(const double motion[12], double w[3], double *theta);
+int lfx_motion_scale(const double motion[12], double ratio, double out[12]);
+/* De-skew every edge and surface record of the last device batch, scan s by sweeps[s] (host, [n_scans]).  Outputs laid out
+ * like lfx_device_view::edge_points / surface_points; BOTH NULL: in place, so that lfx_localize_batch,
+ * lfx_odometry_update_batch, lfx_mapper_add, the lfx_pack_* calls and lfx_download_scan see de-skewed clouds.  The firing time
+ * of a feature record comes from its edge_index / surface_index entry (the original index within the scan):
+ * LFX_TIME_FROM_INDEX divides it by the scan's point count; LFX_TIME_FROM_FIELD reads the field from that record of the
+ * batch's input points, which must still be alive (as for lfx_pack_colored).  Asynchronous on `stream`, one launch for the
+ * batch, the counts read on the device.  LFX_ERR_INVALID_ARGUMENT: no batch yet, n_scans not the last batch's, NULL time /
+ * sweeps, an unknown source / datatype / to, a field past the context's point_step, non-finite motion or times, t1 == t0
+ * with LFX_TIME_FROM_FIELD, exactly one output NULL, outputs that are the context's own clouds (lfx_device_view::edge_points /
+ * surface_points: NULL, NULL is the way to de-skew in place), and any de-skew of a batch that has already been de-skewed in
+ * place (the next extraction lifts that). */
+int lfx_deskew_batch(lfx_ctx *ctx, const lfx_time_field *time, const lfx_sweep *sweeps, uint32_t n_scans, int to,
+                     float *d_edge_out, float *d_surface_out, void *stream);
+/* lfx_odometry_update_batch with every scan corrected by its own constant-velocity prediction.  The odometry remembers the
+ * poses of the last two scans its update* calls processed (lfx_odometry_add does not count).  Per scan of the last device
+ * batch, in order: D = Pa^-1 Pb (lfx_motion_between; identity while fewer than two exist), the sweep's motion
+ * lfx_motion_scale(D, sweep_ratio), the scan's two clouds de-skewed (as lfx_deskew_batch, out of place) into a buffer of
+ * the odometry's own, then exactly lfx_odometry_update on those clouds (downsample after de-skew, align from the current
+ * pose, append the de-skewed raw clouds).  sweep_times: host [n_scans][2] = t0, t1 per scan; NULL with LFX_TIME_FROM_INDEX.
+ * The batch's clouds in the context stay raw.  Refused with LFX_ERR_INVALID_ARGUMENT: what lfx_odometry_update_batch and
+ * lfx_deskew_batch refuse, a batch that has already been de-skewed in place (its clouds would be corrected twice), a
+ * non-finite sweep_ratio, NULL sweep_times with LFX_TIME_FROM_FIELD. */
+int lfx_odometry_update_batch_deskewed(lfx_ctx *ctx, lfx_odometry *odometry, const lfx_time_field *time,
+                                       const double *sweep_times, double sweep_ratio, int to, uint32_t n_scans,
+                                       lfx_odometry_result *results, void *stream);
 
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device

@@ -167,6 +167,19 @@ public:
     if (rc != LFX_OK) {throw Error(rc, "invalid label");}
     return out;
   }
+  // The sensor's motion during the sweep taken out of the clouds of the scans this object was last given (lfx_deskew_batch),
+  // in place: what Localizer::Update(), Odometry::Update() and Mapper::Add read afterwards is de-skewed.  sweeps: one per
+  // scan (t0, t1 and the motion: the sensor frame at the sweep's end in its frame at the start); time: where a record's
+  // firing time comes from (TimeField::FromIndex(), TimeField::FromFields(...)); to: LFX_DESKEW_TO_END or _TO_START.
+  // d_edge_out / d_surface_out: device buffers laid out like the context's clouds for the out-of-place form (both, or
+  // neither); stream: a hipStream_t the call is queued on.
+  void Deskew(
+    const lfx_time_field & time, const std::vector<lfx_sweep> & sweeps, int to = LFX_DESKEW_TO_END, float * d_edge_out = nullptr,
+    float * d_surface_out = nullptr, void * stream = nullptr) const
+  {
+    const int rc = lfx_deskew_batch(ctx_, &time, sweeps.data(), static_cast<std::uint32_t>(sweeps.size()), to, d_edge_out, d_surface_out, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
   lfx_ctx * handle() const {return ctx_;}
   // records the device clouds of the last scan may span (their buffers' extent: one scan of max_points_per_scan)
   std::size_t CloudCapacity() const {return max_points_;}
@@ -188,6 +201,22 @@ private:
   lfx_ctx * ctx_ = nullptr;
   std::vector<void *> pinned_;
   std::uint32_t max_points_ = 0;
+};
+
+// Where a point's firing time comes from (lfx_time_field): its index in the scan, or the time channel of a PointCloud2
+// field list (the first field named t, time, timestamp, time_stamp or offset_time).  No device.
+struct TimeField
+{
+  static lfx_time_field FromIndex() {return lfx_time_field{LFX_TIME_FROM_INDEX, 0u, 0u, 0u, 1.0};}
+  static lfx_time_field FromFields(const std::vector<lfx_point_field> & fields, std::uint32_t point_step, bool is_bigendian = false)
+  {
+    lfx_time_field out{};
+    const int rc = lfx_time_field_from_fields(fields.data(), static_cast<std::uint32_t>(fields.size()), point_step, is_bigendian ? 1 : 0, &out);
+    if (rc != LFX_OK) {
+      throw Error(rc, rc == LFX_ERR_NO_TIME_FIELD ? "the cloud has no per-point time field" : "the time field must be FLOAT32, FLOAT64 or UINT32 inside point_step");
+    }
+    return out;
+  }
 };
 
 // Map files (PCD) as pcl::io::loadPCDFile<pcl::PointXYZ> reads them and pcl::io::save writes them (lfx_pcd_read /
@@ -329,6 +358,25 @@ public:
     if (rc == LFX_OK) {
       results_.assign(view.batch, lfx_odometry_result{});
       rc = lfx_odometry_update_batch(ctx_, odometry_, view.batch, results_.data(), nullptr);
+    }
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_;
+  }
+  // The same with every scan de-skewed by its own constant-velocity prediction first (lfx_odometry_update_batch_deskewed):
+  // the motion between the last two poses, scaled by sweep_ratio (sweep time over scan period).  sweep_times: t0, t1 per
+  // scan with a time field; empty with TimeField::FromIndex()
+  const std::vector<lfx_odometry_result> & UpdateBatchDeskewed(
+    const lfx_time_field & time, const std::vector<double> & sweep_times = {}, double sweep_ratio = 1.0, int to = LFX_DESKEW_TO_END)
+  {
+    lfx_device_view view{};
+    int rc = lfx_device_results(ctx_, &view);
+    if (rc == LFX_OK && !sweep_times.empty() && sweep_times.size() != 2 * static_cast<std::size_t>(view.batch)) {
+      throw Error(LFX_ERR_INVALID_ARGUMENT, "sweep_times must hold t0, t1 per scan");
+    }
+    if (rc == LFX_OK) {
+      results_.assign(view.batch, lfx_odometry_result{});
+      rc = lfx_odometry_update_batch_deskewed(ctx_, odometry_, &time, sweep_times.empty() ? nullptr : sweep_times.data(), sweep_ratio, to,
+        view.batch, results_.data(), nullptr);
     }
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     return results_;

@@ -121,6 +121,22 @@ class MapperStoreView(C.Structure):
 
 KEYFRAME_ADDED, KEYFRAME_EMPTY, KEYFRAME_TOO_CLOSE = 0, 1, 2
 ERR_CAPACITY, ERR_OUT_OF_MEMORY, ERR_UNSUPPORTED_FIELD, ERR_FILE = -4, -6, -8, -9
+ERR_INVALID_ARGUMENT, ERR_NO_TIME_FIELD = -1, -10
+
+
+class TimeField(C.Structure):
+    """lfx_time_field: where a record's firing time comes from (its index in the scan, or a field of the point record)."""
+    _fields_ = [("source", C.c_uint32), ("offset", C.c_uint32), ("datatype", C.c_uint32), ("big_endian", C.c_uint32),
+                ("scale", C.c_double)]
+
+
+class Sweep(C.Structure):
+    """lfx_sweep: start and end time of a sweep and the sensor's motion over it (the frame at t1 in the frame at t0)."""
+    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("motion", C.c_double * 12)]
+
+
+TIME_FROM_INDEX, TIME_FROM_FIELD = 0, 1
+DESKEW_TO_START, DESKEW_TO_END = 0, 1
 
 
 class DeviceView(C.Structure):
@@ -146,6 +162,8 @@ EXPORTS = [
     "lfx_mapper_add", "lfx_mapper_add_host", "lfx_mapper_view", "lfx_mapper_save",
     "lfx_layout_from_fields", "lfx_pack_xyz", "lfx_pack_xyz12", "lfx_pack_colored", "lfx_pack_features", "lfx_download_scan", "lfx_stage_ring", "lfx_stage_convolution1d",
     "lfx_stage_ring_projection", "lfx_label_to_color", "lfx_color_points_by_label", "lfx_set_profiling", "lfx_set_profiling_interval", "lfx_kernel_times", "lfx_kernel_name",
+    "lfx_time_field_from_fields", "lfx_motion_between", "lfx_motion_twist", "lfx_motion_scale", "lfx_deskew_batch",
+    "lfx_odometry_update_batch_deskewed",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -259,6 +277,13 @@ def load(test_hooks=False):
     L.lfx_mapper_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
     L.lfx_gather.argtypes = [vp, vp, i32, vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, vp]
     L.lfx_layout_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Layout)]
+    L.lfx_time_field_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(TimeField)]
+    L.lfx_motion_between.argtypes = [pd, pd, pd]
+    L.lfx_motion_twist.argtypes = [pd, pd, pd]
+    L.lfx_motion_scale.argtypes = [pd, C.c_double, pd]
+    L.lfx_deskew_batch.argtypes = [vp, C.POINTER(TimeField), C.POINTER(Sweep), u32, i32, vp, vp, vp]
+    L.lfx_odometry_update_batch_deskewed.argtypes = [vp, vp, C.POINTER(TimeField), pd, C.c_double, i32, u32,
+                                                     C.POINTER(OdometryResult), vp]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_xyz12.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_colored.argtypes = [vp, vp, vp, C.c_size_t, vp]

@@ -314,6 +314,7 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   }
   c->last_batch = batch;
   c->last_points = d_points;
+  c->deskewed_in_place = false;              // (lfx_deskew_batch: a fresh batch may be de-skewed)
   c->profile_now = c->profiling && (c->batch_no++ % c->profile_every) == 0u;
   // this batch's set of accumulators (lfx_kernels_common.hpp kParityCounters); the other one is zeroed by this batch's
   // compaction for the batch after it
@@ -816,6 +817,29 @@ int lfx_layout_from_fields(
   return LFX_OK;
 }
 
+int lfx_time_field_from_fields(
+  const lfx_point_field * fields, uint32_t n_fields, uint32_t point_step, int is_bigendian, lfx_time_field * out)
+{
+  if (!out || (!fields && n_fields) || point_step == 0) {return LFX_ERR_INVALID_ARGUMENT;}
+  static const char * const names[] = {"t", "time", "timestamp", "time_stamp", "offset_time"};
+  const lfx_point_field * ft = nullptr;
+  for (uint32_t i = 0; i < n_fields && !ft; i++) {
+    const lfx_point_field & f = fields[i];
+    if (!f.name) {return LFX_ERR_INVALID_ARGUMENT;}
+    for (const char * n : names) {
+      if (f.count == 1u && !std::strcmp(f.name, n)) {ft = &f;}
+    }
+  }
+  if (!ft) {return LFX_ERR_NO_TIME_FIELD;}
+  const bool is_float = ft->datatype == LFX_FIELD_FLOAT32 || ft->datatype == LFX_FIELD_FLOAT64;
+  if ((!is_float && ft->datatype != LFX_FIELD_UINT32) || (uint64_t)ft->offset + field_size(ft->datatype) > point_step) {
+    return LFX_ERR_UNSUPPORTED_FIELD;
+  }
+  // seconds in a floating-point field; nanoseconds in an integer one (Ouster's t, Livox's offset_time)
+  *out = lfx_time_field{LFX_TIME_FROM_FIELD, ft->offset, ft->datatype, is_bigendian ? 1u : 0u, is_float ? 1.0 : 1e-9};
+  return LFX_OK;
+}
+
 int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const lfx_config * caller_config)
 {
   if (!out) {return LFX_ERR_INVALID_ARGUMENT;}
@@ -1116,6 +1140,10 @@ void lfx_destroy(lfx_ctx * c)
   c->staging.release();
   c->h_in.release(); c->h_out.release(); c->vox_scratch.release(); c->align_scratch.release(); c->align_surface.release(); c->h_align.release(); c->h_loc.release();
   if (c->h_status) {(void)hipHostFree(c->h_status); c->h_status = nullptr;}
+  for (auto & ev : c->deskew_copied) {
+    if (ev) {(void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); ev = nullptr;}
+  }
+  c->h_deskew.release(); c->d_deskew.release();
   if (c->copy_stream) {(void)hipStreamSynchronize(c->copy_stream);}
   for (auto & sl : c->slots) {
     sl.in.release(); sl.hin.release(); sl.hout.release();

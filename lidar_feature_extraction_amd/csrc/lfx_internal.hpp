@@ -236,6 +236,17 @@ struct lfx_ctx
   int align_guess = 4;                             // iterations the previous alignment needed: so many are queued before the host looks
   uint32_t loc_guess[2] = {0u, 0u};                // longest edge / downsampled surface cloud of the previous lfx_localize_batch
 
+  // lfx_deskew_batch (lfx_deskew.hip): the per-scan constants go out through kDeskewSlots blocks of pinned memory, each with
+  // a table of its own on the device and an event behind the kernel that reads it, so that a call never rewrites a block or a
+  // table still in use, whichever streams the calls are on; allocated on first use.  deskewed_in_place: the last batch's clouds have been de-skewed in place (a second
+  // de-skew would correct them twice); run_batch lifts it
+  static constexpr uint32_t kDeskewSlots = 8;
+  lfx_host::PinnedBuf h_deskew;
+  lfx_host::DevBuf<double> d_deskew;
+  hipEvent_t deskew_copied[kDeskewSlots] = {};
+  uint32_t deskew_next = 0;
+  bool deskewed_in_place = false;
+
   hipStream_t stream = nullptr;          // used by the synchronous host entry points
   std::vector<uint32_t> h_scan_begin;    // of the last batch
   std::vector<uint32_t> h_scan_geom;     // [batch][kGeomStride]: columns per ring and block boundaries of every scan (organised-scan kernel)
@@ -297,6 +308,11 @@ int voxel_downsample(
   lfx_ctx * c, const float * d_points, const uint32_t * d_begin, const uint32_t * d_count, uint32_t count_stride,
   uint32_t n_clouds, size_t total_points, float leaf, float * d_out, uint32_t * d_out_count, uint32_t * d_status, void * stream,
   bool unfiltered, const uint32_t * d_other_count, uint32_t * lengths);
+
+// lfx_deskew.hip: scans first .. first + n - 1 of the last batch de-skewed by sweeps[0 .. n - 1] into buffers laid out like
+// the context's clouds (lfx_deskew_batch's checks; lfx_odometry_update_batch_deskewed takes one scan at a time)
+int deskew_scans(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * sweeps, uint32_t first, uint32_t n, int to,
+  float4 * edge_out, float4 * surf_out, hipStream_t st);
 
 // lfx_localize.hip: a map rebuilt in place (lfx_odometry.hip's window maps) and the optimizer over clouds
 lfx_map * map_new(int device);

@@ -1,0 +1,117 @@
+// lfx_kernels_deskew.hpp -- the sensor's motion during a sweep taken out of the two feature clouds (include/lfx.h, the de-skew
+// section; no reference counterpart, LOAM's model).  One kernel body, the source of a record's firing time a template
+// parameter; the arithmetic is the header's, in double, unfused.
+#pragma once
+
+#include "lfx_kernels_common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace lfx
+{
+
+// The constants of one scan's sweep, a row of doubles the host writes (lfx_deskew.hip).  A workgroup reads the row of
+// blockIdx.y only: the addresses are the same for every lane, so the loads go through the scalar cache and the values
+// live in scalar registers.
+enum
+{
+  kDskK = 0,        // k = w / theta (0 where theta < 1e-8)
+  kDskTheta = 3,
+  kDskW = 4,        // w: the small-angle form reads it
+  kDskV = 7,        // v = t_D
+  kDskR = 10,       // R_D, row-major 3 x 3
+  kDskT0 = 19,
+  kDskInvDt = 20,   // 1 / (t1 - t0)
+  kDskScale = 21,   // seconds per unit of the time field
+  kDskStride = 24
+};
+enum { kDskFromIndex = 0, kDskF32 = 1, kDskF64 = 2, kDskU32 = 3 };
+constexpr int kDeskewThreads = 256;
+
+struct DeskewArgs
+{
+  const uint32_t * scan_begin, * scan_info;
+  const double * table;                 // [scans of the launch][kDskStride]
+  const float4 * edge_in, * surf_in;    // (may be the outputs: in place)
+  const uint32_t * edge_idx, * surf_idx;
+  float4 * edge_out, * surf_out;
+  const uint8_t * pts;                  // the batch's input records (a field source only)
+  uint32_t step, off, be;
+  uint32_t first;                       // the launch covers scans first .. first + gridDim.y - 1
+  uint32_t to_end;
+};
+
+// grid (chunks, scans) as feature_pack_kernel's; a grid-stride walk over the scan's n_edge + n_surface records, one float4
+// load and one float4 store per record, its index from the list beside it.  No LDS, no atomics.
+template<int SRC>
+__global__ __launch_bounds__(kDeskewThreads) void deskew_kernel(const DeskewArgs A)
+{
+  const uint32_t s = A.first + blockIdx.y;
+  const uint32_t ne = A.scan_info[s * 4 + kInfoEdge], ns = A.scan_info[s * 4 + kInfoSurface];
+  const uint32_t b0 = A.scan_begin[s], n = A.scan_begin[s + 1] - b0;
+  const size_t b = b0;
+  const double * __restrict__ T = A.table + (size_t)blockIdx.y * kDskStride;
+  const double kx = T[kDskK], ky = T[kDskK + 1], kz = T[kDskK + 2], theta = T[kDskTheta];
+  const double wx = T[kDskW], wy = T[kDskW + 1], wz = T[kDskW + 2];
+  const double vx = T[kDskV], vy = T[kDskV + 1], vz = T[kDskV + 2];
+  const double t0 = T[kDskT0], inv_dt = T[kDskInvDt], scale = T[kDskScale];
+  // (read here, ahead of the loop's stores, which the compiler must take to alias the table: scalar loads, as the rest)
+  const double r00 = T[kDskR + 0], r01 = T[kDskR + 1], r02 = T[kDskR + 2], r10 = T[kDskR + 3], r11 = T[kDskR + 4], r12 = T[kDskR + 5],
+    r20 = T[kDskR + 6], r21 = T[kDskR + 7], r22 = T[kDskR + 8];
+  const bool small = theta < 1e-8;      // the same for every record of the scan
+  const double dn = (double)n;
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < ne + ns; k += gridDim.x * blockDim.x) {
+    const bool edge = k < ne;
+    const uint32_t q = edge ? k : k - ne;
+    const float4 rec = (edge ? A.edge_in : A.surf_in)[b + q];
+    const uint32_t idx = (edge ? A.edge_idx : A.surf_idx)[b + q];
+    double alpha;
+    if (SRC == kDskFromIndex) {
+      alpha = (double)idx / dn;
+    } else if (idx >= n) {
+      alpha = __builtin_nan("");        // (no record of the scan: nothing is read, the record is copied)
+    } else {
+      const uint8_t * f = A.pts + (b + idx) * A.step + A.off;
+      double value;
+      if (SRC == kDskF64) {
+        uint64_t u = *reinterpret_cast<const uint64_t *>(f);
+        if (A.be) {u = __builtin_bswap64(u);}
+        value = __longlong_as_double((long long)u);
+      } else {
+        uint32_t u = *reinterpret_cast<const uint32_t *>(f);
+        if (A.be) {u = __builtin_bswap32(u);}
+        value = SRC == kDskF32 ? (double)__uint_as_float(u) : (double)u;
+      }
+      alpha = (value * scale - t0) * inv_dt;
+    }
+    float4 out = rec;
+    if (isfinite(alpha)) {
+      const double px = (double)rec.x, py = (double)rec.y, pz = (double)rec.z;
+      double rx, ry, rz;
+      if (small) {
+        rx = px + alpha * (wy * pz - wz * py);
+        ry = py + alpha * (wz * px - wx * pz);
+        rz = pz + alpha * (wx * py - wy * px);
+      } else {
+        const double a = alpha * theta, c = cos(a), sn = sin(a);
+        const double cx = ky * pz - kz * py, cy = kz * px - kx * pz, cz = kx * py - ky * px;
+        const double kdp = (kx * px + ky * py) + kz * pz, g = kdp * (1.0 - c);
+        rx = (px * c + cx * sn) + kx * g;
+        ry = (py * c + cy * sn) + ky * g;
+        rz = (pz * c + cz * sn) + kz * g;
+      }
+      const double mx = rx + alpha * vx, my = ry + alpha * vy, mz = rz + alpha * vz;
+      if (A.to_end) {
+        const double u0 = mx - vx, u1 = my - vy, u2 = mz - vz;
+        out.x = (float)((r00 * u0 + r10 * u1) + r20 * u2);
+        out.y = (float)((r01 * u0 + r11 * u1) + r21 * u2);
+        out.z = (float)((r02 * u0 + r12 * u1) + r22 * u2);
+      } else {
+        out.x = (float)mx; out.y = (float)my; out.z = (float)mz;
+      }
+    }
+    (edge ? A.edge_out : A.surf_out)[b + q] = out;
+  }
+}
+
+}  // namespace lfx

@@ -40,6 +40,11 @@ struct lfx_odometry
   PinnedBuf pinned;                          // [12] bounds | [8] words | [batch][4] scan_info | [batch][2] lengths
   bool reports_on = false;                   // lfx_odometry_set_reports
   std::vector<lfx_align_report> reports;     // the scans of the last update* call (a scan that was not aligned: all zero)
+  // lfx_odometry_update_batch_deskewed: the poses of the last two scans the update* calls processed ([0] the older one),
+  // and the de-skewed clouds of the batch at hand, laid out like the context's
+  double recent[2][12] = {};
+  uint32_t n_recent = 0;
+  DevBuf<float4> dsk_edge, dsk_surface;
   uint32_t n_scans() const {return (uint32_t)box.size();}
 };
 
@@ -223,6 +228,9 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
   const int rc = append(c, o, how, pose, in.edge, in.n_edge, in.surface, in.n_surface, st);
   if (rc != LFX_OK) {return rc;}
   std::memcpy(o->pose, pose, sizeof(pose));
+  std::memcpy(o->recent[0], o->recent[1], sizeof(pose));
+  std::memcpy(o->recent[1], pose, sizeof(pose));
+  o->n_recent = std::min(o->n_recent + 1u, 2u);
   *result = r;
   return LFX_OK;
 }
@@ -303,7 +311,7 @@ void lfx_odometry_destroy(lfx_odometry * o)
   if (o->tail) {(void)hipEventSynchronize(o->tail); (void)hipEventDestroy(o->tail);}
   lfx_map_destroy(o->emap);
   lfx_map_destroy(o->smap);
-  o->edge.release(); o->surface.release(); o->bounds.release(); o->words.release(); o->down.release(); o->staged.release();
+  o->edge.release(); o->surface.release(); o->bounds.release(); o->words.release(); o->down.release(); o->staged.release(); o->dsk_edge.release(); o->dsk_surface.release();
   o->pinned.release();
   delete o;
 }
@@ -382,6 +390,54 @@ int lfx_odometry_update(lfx_ctx * c, lfx_odometry * o, const float * d_edge, uin
   in.down_points = o->down.p; in.down_begin = o->words.p; in.down_count = o->words.p + 3; in.n_down = n_surface;
   o->reports.assign(o->reports_on ? 1u : 0u, lfx_align_report{});
   return step(c, o, in, result, st, o->reports_on ? &o->reports[0] : nullptr);
+}
+
+int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_time_field * time, const double * sweep_times,
+  double sweep_ratio, int to, uint32_t n_scans, lfx_odometry_result * results, void * stream)
+{
+  if (!c || !o || !results || !time) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
+  if (n_scans != c->last_batch) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
+             std::to_string(c->last_batch) + ")");
+  }
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
+  if (!std::isfinite(sweep_ratio)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_ratio must be finite");}
+  if (time->source != LFX_TIME_FROM_INDEX && !sweep_times) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_times is required with a time field");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t batch = c->last_batch;
+  const size_t total = c->h_scan_begin[batch];
+  if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
+  }
+  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
+  uint32_t * info = pinned_words(o) + kPinInfo;
+  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  // (lfx_odometry_update below writes the pinned block's words and bounds, not the batch's scan_info behind them)
+  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
+  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
+  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  for (uint32_t s = 0; s < batch; s++) {
+    lfx_sweep sw{};
+    double D[12];
+    if (o->n_recent < 2u) {std::memcpy(D, identity, sizeof(D));} else {lfx_motion_between(o->recent[0], o->recent[1], D);}
+    lfx_motion_scale(D, sweep_ratio, sw.motion);
+    if (sweep_times) {sw.t0 = sweep_times[2 * s]; sw.t1 = sweep_times[2 * s + 1];}
+    int rc = deskew_scans(c, time, &sw, s, 1, to, o->dsk_edge.p, o->dsk_surface.p, st);
+    if (rc != LFX_OK) {return rc;}
+    const uint32_t b = c->h_scan_begin[s];
+    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
+      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
+    if (rc != LFX_OK) {return rc;}
+    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
+  }
+  o->reports = reports;
+  return LFX_OK;
 }
 
 int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, uint32_t n_edge, const float * surface,

@@ -414,6 +414,92 @@ int lfx_pose_diff(const double pose0[12], const double pose1[12], double * trans
   return LFX_OK;
 }
 
+// The motions of the de-skew section (include/lfx.h): pose0^-1 pose1 as lfx_pose_diff forms it, its angle-axis vector, a
+// fraction of it.
+int lfx_motion_between(const double pose0[12], const double pose1[12], double motion[12])
+{
+  if (!pose0 || !pose1 || !motion) {return LFX_ERR_INVALID_ARGUMENT;}
+  auto R0 = [&](int r, int c) {return pose0[4 * r + c];};
+  auto R1 = [&](int r, int c) {return pose1[4 * r + c];};
+  double out[12];                                     // (motion may be one of the poses)
+  bool same = true;
+  for (int i = 0; i < 12; i++) {same = same && pose0[i] == pose1[i];}
+  if (same) {
+    // a sensor that has not moved: the identity itself, not R0^T R0 as it rounds (de-skew by it changes no bit)
+    const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::memcpy(motion, identity, sizeof(identity));
+    return LFX_OK;
+  }
+  for (int r = 0; r < 3; r++) {
+    const double inv_t = -((R0(0, r) * pose0[3] + R0(1, r) * pose0[7]) + R0(2, r) * pose0[11]);
+    out[4 * r + 3] = ((R0(0, r) * pose1[3] + R0(1, r) * pose1[7]) + R0(2, r) * pose1[11]) + inv_t;
+    for (int c = 0; c < 3; c++) {out[4 * r + c] = (R0(0, r) * R1(0, c) + R0(1, r) * R1(1, c)) + R0(2, r) * R1(2, c);}
+  }
+  std::memcpy(motion, out, sizeof(out));
+  return LFX_OK;
+}
+
+int lfx_motion_twist(const double motion[12], double w[3], double * theta)
+{
+  if (!motion || !w || !theta) {return LFX_ERR_INVALID_ARGUMENT;}
+  auto m = [&](int r, int c) {return motion[4 * r + c];};
+  // Quaterniond(R_D), Shoemake's algorithm as Eigen writes it (lfx_pose_diff), with its scalar part
+  double q[3], qw;
+  const double tr = (m(0, 0) + m(1, 1)) + m(2, 2);
+  if (tr > 0.0) {
+    const double t = std::sqrt(tr + 1.0);
+    qw = 0.5 * t;
+    const double s = 0.5 / t;
+    q[0] = (m(2, 1) - m(1, 2)) * s;
+    q[1] = (m(0, 2) - m(2, 0)) * s;
+    q[2] = (m(1, 0) - m(0, 1)) * s;
+  } else {
+    int i = 0;
+    if (m(1, 1) > m(0, 0)) {i = 1;}
+    if (m(2, 2) > m(i, i)) {i = 2;}
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    const double t = std::sqrt(((m(i, i) - m(j, j)) - m(k, k)) + 1.0);
+    q[i] = 0.5 * t;
+    const double s = 0.5 / t;
+    qw = (m(k, j) - m(j, k)) * s;
+    q[j] = (m(j, i) + m(i, j)) * s;
+    q[k] = (m(k, i) + m(i, k)) * s;
+  }
+  const double n = std::sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
+  if (n == 0.0) {
+    w[0] = w[1] = w[2] = 0.0;
+    *theta = 0.0;
+    return LFX_OK;
+  }
+  const double th = 2.0 * std::atan2(n, qw), f = th / n;
+  w[0] = q[0] * f; w[1] = q[1] * f; w[2] = q[2] * f;
+  *theta = th;
+  return LFX_OK;
+}
+
+int lfx_motion_scale(const double motion[12], double ratio, double out[12])
+{
+  if (!motion || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  double w[3], theta;
+  lfx_motion_twist(motion, w, &theta);
+  double res[12];                                     // (out may be motion)
+  if (theta < 1e-8) {
+    const double x = ratio * w[0], y = ratio * w[1], z = ratio * w[2];
+    const double r[9] = {1.0, 0.0 - z, y, z, 1.0, 0.0 - x, 0.0 - y, x, 1.0};   // (0 - 0: no negative zero for the identity)
+    for (int i = 0; i < 3; i++) {for (int j = 0; j < 3; j++) {res[4 * i + j] = r[3 * i + j];}}
+  } else {
+    const double k[3] = {w[0] / theta, w[1] / theta, w[2] / theta};
+    const double a = ratio * theta, c = std::cos(a), s = std::sin(a), v = 1.0 - c;
+    const double hat[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) {res[4 * i + j] = ((i == j ? c : 0.0) + hat[3 * i + j] * s) + k[i] * (k[j] * v);}
+    }
+  }
+  for (int i = 0; i < 3; i++) {res[4 * i + 3] = ratio * motion[4 * i + 3];}
+  std::memcpy(out, res, sizeof(res));
+  return LFX_OK;
+}
+
 // A report's covariance in the order of geometry_msgs/PoseWithCovariance (include/lfx.h): out = T C T^T, T = [[0, I], [R, 0]].
 // Every sum of three terms is (a0 b0 + a1 b1) + a2 b2 (this file is built with contraction off).
 int lfx_align_covariance_ros(const double pose[12], const double covariance[36], double out[36])

@@ -389,6 +389,20 @@ class FeatureExtraction:
             self._ctx, C.c_void_p(int(d_colored_out)), C.c_void_p(int(d_offsets_out)), int(capacity_points),
             C.c_void_p(int(stream))))
 
+    def deskew(self, time, sweeps, to="end", out=None, stream=0):
+        """lfx_deskew_batch: the sensor's motion during each sweep taken out of the last device batch's edge and surface
+        clouds.  time: None or "index" (a record's firing time is its index in the scan over the scan's point count), or
+        a B.TimeField (time_field_from_fields); sweeps: one per scan, a 3 x 4 motion (the sensor frame at the sweep's end in
+        its frame at the start; index times) or (t0, t1, motion); to: "end" or "start", the frame the points are carried to;
+        out: None = in place (every later call on this batch sees the de-skewed clouds), or (d_edge_out, d_surface_out),
+        device addresses of buffers laid out like device_view().edge_points / surface_points.  Asynchronous on `stream`."""
+        tf = _time_field(time)
+        sw, n = _sweeps(sweeps)
+        e, s = (0, 0) if out is None else out
+        B.check(self._ctx, self._L.lfx_deskew_batch(
+            self._ctx, C.byref(tf), sw, n, _deskew_to(to), C.c_void_p(int(e) or None), C.c_void_p(int(s) or None),
+            C.c_void_p(int(stream))), self._L)
+
     def download(self, scan, stream=0):
         r = B.ScanResult()
         B.check(self._ctx, self._L.lfx_download_scan(self._ctx, scan, C.c_void_p(int(stream)), C.byref(r)), self._L)
@@ -485,6 +499,81 @@ def layout_from_fields(fields, point_step, is_bigendian=False):
         raise B.LfxError(rc, {-7: "the cloud has no ring field", -8: "x / y / z must be FLOAT32 and ring an integer field inside point_step"}.get(rc, "invalid field list"))
     return out
 
+
+
+def _time_field(time):
+    if time is None or (isinstance(time, str) and time == "index"):
+        return B.TimeField(B.TIME_FROM_INDEX, 0, 0, 0, 1.0)
+    if isinstance(time, B.TimeField):
+        return time
+    raise TypeError("time must be None, 'index' or a binding.TimeField")
+
+
+def _deskew_to(to):
+    if to in ("end", "start"):
+        return B.DESKEW_TO_END if to == "end" else B.DESKEW_TO_START
+    return int(to)
+
+
+def _sweeps(sweeps):
+    out = (B.Sweep * max(len(sweeps), 1))()
+    for i, s in enumerate(sweeps):
+        if isinstance(s, B.Sweep):
+            out[i] = s
+            continue
+        if isinstance(s, (tuple, list)) and len(s) == 3 and np.ndim(s[0]) == 0:
+            out[i].t0, out[i].t1, m = float(s[0]), float(s[1]), s[2]
+        else:
+            m = s
+        out[i].motion[:] = [float(x) for x in np.asarray(m, np.float64).reshape(12)]
+    return out, len(sweeps)
+
+
+def time_field_from_fields(fields, point_step, is_bigendian=False):
+    """lfx_time_field_from_fields: the per-point time channel of a PointCloud2 field list (iterable of (name, offset,
+    datatype, count)) -> binding.TimeField for deskew(): the first field named t, time, timestamp, time_stamp or
+    offset_time with count 1; seconds in FLOAT32 / FLOAT64, nanoseconds in UINT32.  Raises LfxError (ERR_NO_TIME_FIELD,
+    ERR_UNSUPPORTED_FIELD).  No device."""
+    arr = (B.PointField * max(len(fields), 1))(*[B.PointField(n.encode(), o, t, c) for (n, o, t, c) in fields])
+    out = B.TimeField()
+    rc = B.load().lfx_time_field_from_fields(arr, len(fields), point_step, int(bool(is_bigendian)), C.byref(out))
+    if rc != 0:
+        raise B.LfxError(rc, {-10: "the cloud has no per-point time field",
+                              -8: "the time field must be FLOAT32, FLOAT64 or UINT32 inside point_step"}.get(rc, "invalid field list"))
+    return out
+
+
+def _pd(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def motion_between(pose0, pose1):
+    """lfx_motion_between: pose0^-1 pose1 (3 x 4 [R | t]): the sensor's frame at pose1 expressed in its frame at pose0.  No device."""
+    a = np.ascontiguousarray(pose0, np.float64).reshape(12)
+    b = np.ascontiguousarray(pose1, np.float64).reshape(12)
+    out = np.zeros(12, np.float64)
+    if B.load().lfx_motion_between(_pd(a), _pd(b), _pd(out)) != 0:
+        raise B.LfxError(-1, "invalid argument")
+    return out.reshape(3, 4)
+
+
+def motion_twist(motion):
+    """lfx_motion_twist: (w, theta) of a motion's rotation -- the angle-axis vector Log(R) and its length, as the de-skew
+    kernel is given them.  No device."""
+    m = np.ascontiguousarray(motion, np.float64).reshape(12)
+    w, th = np.zeros(3, np.float64), C.c_double(0)
+    if B.load().lfx_motion_twist(_pd(m), _pd(w), C.byref(th)) != 0:
+        raise B.LfxError(-1, "invalid argument")
+    return w, th.value
+
+
+def motion_scale(motion, ratio):
+    """lfx_motion_scale: [Exp(ratio w) | ratio t] of a motion [Exp(w) | t] (a sweep shorter than the scan period).  No device."""
+    m = np.ascontiguousarray(motion, np.float64).reshape(12)
+    out = np.zeros(12, np.float64)
+    if B.load().lfx_motion_scale(_pd(m), float(ratio), _pd(out)) != 0:
+        raise B.LfxError(-1, "invalid argument")
+    return out.reshape(3, 4)
 
 
 def _msg_buffer():
@@ -655,6 +744,22 @@ class Odometry:
         n = int(self._fx.device_view().batch if n_scans is None else n_scans)
         res = (B.OdometryResult * max(n, 1))()
         B.check(self._fx._ctx, self._L.lfx_odometry_update_batch(self._fx._ctx, self.handle, n, res, C.c_void_p(int(stream))))
+        return self._results(res[:n])
+
+    def update_batch_deskewed(self, time=None, sweep_times=None, sweep_ratio=1.0, to="end", n_scans=None, stream=0):
+        """lfx_odometry_update_batch_deskewed: update_batch with every scan de-skewed by its own constant-velocity prediction
+        (the motion between the last two poses, scaled by sweep_ratio) before it is aligned and added.  time as
+        FeatureExtraction.deskew takes it; sweep_times: [n][2] = t0, t1 per scan with a time field.  The batch's clouds in
+        the context stay raw."""
+        n = int(self._fx.device_view().batch if n_scans is None else n_scans)
+        tf = _time_field(time)
+        st = None if sweep_times is None else np.ascontiguousarray(sweep_times, np.float64).reshape(-1)
+        if st is not None and len(st) != 2 * n:
+            raise ValueError("expected %d pairs of sweep times" % n)
+        res = (B.OdometryResult * max(n, 1))()
+        B.check(self._fx._ctx, self._L.lfx_odometry_update_batch_deskewed(
+            self._fx._ctx, self.handle, C.byref(tf), None if st is None else _pd(st), float(sweep_ratio), _deskew_to(to), n, res,
+            C.c_void_p(int(stream))))
         return self._results(res[:n])
 
     def update(self, d_edge, n_edge, d_surface, n_surface, stream=0):

@@ -132,6 +132,80 @@ def make_sequence(n_scans, rings=64, cols=1800, seed=1234, step=0.05, yaw_step_d
     return clouds, np.stack(poses)
 
 
+def _exp_so3(w):
+    """Rotation matrices of angle-axis vectors w [..., 3] (Rodrigues)."""
+    w = np.asarray(w, np.float64)
+    th = np.linalg.norm(w, axis=-1)[..., None, None]
+    K = np.zeros(w.shape[:-1] + (3, 3))
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -w[..., 2], w[..., 1], w[..., 2]
+    K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -w[..., 0], -w[..., 1], w[..., 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.where(th > 1e-12, np.sin(th) / th, 1.0)
+        b = np.where(th > 1e-12, (1.0 - np.cos(th)) / (th * th), 0.5)
+    return np.eye(3) + a * K + b * (K @ K)
+
+
+def _log_so3(R):
+    """The angle-axis vector of a rotation matrix (angles below pi)."""
+    R = np.asarray(R, np.float64)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = 0.5 * np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0)
+    th = np.arctan2(s, c)
+    return np.zeros(3) if s < 1e-300 else v * (th / (2.0 * s))
+
+
+def make_sweep(rings=16, cols=900, seed=1234, pose0=None, motion=None, sigma=0.01, vfov_deg=15.0, n_pillars=14,
+               t0=0.0, period=0.1, ceiling=3.0):
+    """One sweep of a sensor that MOVES while it fires: point i (column-major, i = column * rings + ring) is measured at
+    alpha = i / n of the sweep, from the pose P0 M(alpha), M(alpha) = [Exp(alpha w) | alpha v] with [Exp(w) | v] = motion
+    (the sensor frame at the sweep's end in its frame at the start: LOAM's model, include/lfx.h's de-skew section).  Rays
+    are cast in 3-D in a closed box room (make_scan's 20 m x 12 m walls, the floor at z = 0, a ceiling) with make_scan's
+    vertical pillars, Gaussian noise of sigma along the ray; every point is given in the sensor frame of its own time.
+
+    pose0   the sensor's world pose at the start, 3 x 4 [R | t]; None: make_scan's usual place, 1.8 m over the floor
+    motion  3 x 4; None: the identity (a static scan)
+    Returns (records, world, alpha): POINT_DTYPE records (the point's time t0 + alpha * period also as a float32 at byte 24,
+    in the record's padding), the measured points in the world [n, 3] float64, alpha [n] float64."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = rings * cols
+    P0 = np.array([[1, 0, 0, 1.3], [0, 1, 0, -0.7], [0, 0, 1, 1.8]], np.float64) if pose0 is None else np.asarray(pose0, np.float64).reshape(3, 4)
+    D = np.eye(4)[:3] if motion is None else np.asarray(motion, np.float64).reshape(3, 4)
+    w, v = _log_so3(D[:, :3]), D[:, 3]
+    alpha = np.arange(n, dtype=np.float64) / n
+    col, ring = np.arange(n) // rings, np.arange(n) % rings
+    az = -np.pi + 2.0 * np.pi * (col + 0.5) / cols
+    el = np.deg2rad(np.linspace(-vfov_deg, vfov_deg, rings))[ring]
+    d_s = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)     # unit rays, sensor frame
+    Rm = P0[:, :3] @ _exp_so3(alpha[:, None] * w[None, :])                                       # world rotation at alpha
+    o = (alpha[:, None] * v[None, :]) @ P0[:, :3].T + P0[:, 3]                                  # world position at alpha
+    d = np.einsum("nij,nj->ni", Rm, d_s)
+    lo, hi = np.array([-10.0, -6.0, 0.0]), np.array([10.0, 6.0, float(ceiling)])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tb = np.where(d > 0, (hi - o) / d, np.where(d < 0, (lo - o) / d, np.inf))
+    t = tb.min(axis=1)
+    pr = np.random.Generator(np.random.PCG64(4242))      # make_scan's pillars
+    a2 = d[:, 0] ** 2 + d[:, 1] ** 2
+    for k in range(n_pillars):
+        ang = 2.0 * np.pi * (k + 0.37) / n_pillars + pr.uniform(-0.1, 0.1)
+        dist = pr.uniform(3.0, 5.5)
+        rad = pr.uniform(0.08, 0.2)
+        ox, oy = o[:, 0] - (1.3 + dist * np.cos(ang)), o[:, 1] - (-0.7 + dist * np.sin(ang))
+        b = ox * d[:, 0] + oy * d[:, 1]
+        disc = b * b - a2 * (ox * ox + oy * oy - rad * rad)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tp = (-b - np.sqrt(np.where(disc > 0, disc, np.nan))) / a2
+        t = np.minimum(t, np.where((disc > 0) & (tp > 0), tp, np.inf))
+    t = np.maximum(t + sigma * rng.standard_normal(n), 0.02)
+    pts = np.zeros(n, POINT_DTYPE)
+    local = t[:, None] * d_s
+    pts["x"], pts["y"], pts["z"] = local[:, 0].astype(np.float32), local[:, 1].astype(np.float32), local[:, 2].astype(np.float32)
+    pts["pad"] = 1.0
+    pts["intensity"] = rng.uniform(0.0, 255.0, n).astype(np.float32)
+    pts["ring"] = ring.astype(np.uint16)
+    pts.view(np.uint8).reshape(n, POINT_DTYPE.itemsize)[:, 24:28] = (t0 + alpha * period).astype("<f4").view(np.uint8).reshape(n, 4)
+    return np.ascontiguousarray(pts), o + t[:, None] * d, alpha
+
+
 def concat(clouds):
     """Back-to-back copy of several scans, keeping the 32-byte record layout (np.concatenate would
     repack the fields)."""
