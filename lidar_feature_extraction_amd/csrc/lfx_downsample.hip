@@ -19,12 +19,8 @@ int voxel_downsample(
   }
   if (!(leaf > 0.f)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "leaf size must be > 0");}
   LFX_HIP(c, hipSetDevice(c->device));
-  if (c->vox_scratch.n < 4 * total_points) {          // (key, value) x 2 per point, grown on demand
-    c->vox_scratch.release();
-    if (c->vox_scratch.alloc(4 * total_points) != hipSuccess) {
-      c->vox_scratch.n = 0;
-      return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the sort scratch of the voxel grid");
-    }
+  if (hold(c->vox_scratch, 4 * total_points, true) != hipSuccess) {          // (key, value) x 2 per point, grown on demand
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the sort scratch of the voxel grid");
   }
   uint32_t * w = c->vox_scratch.p;
   // the small-cloud form's ranking table (96 KB), then its sorted points (144 KB) in LDS: more than a kernel gets without asking

@@ -88,13 +88,14 @@ struct DevBuf
   }
 };
 
-// a device buffer that holds at least `need` elements, grown by half again when it must grow (its contents are not kept)
+// a device buffer that holds at least `need` elements, grown by half again when it must grow -- or, `exact`, to `need` and
+// no further: the buffers that are the library's largest at 1 024 scans -- (its contents are not kept)
 template<typename T>
-hipError_t hold(DevBuf<T> & b, size_t need)
+hipError_t hold(DevBuf<T> & b, size_t need, bool exact = false)
 {
-  if (b.p && b.n >= need) {return hipSuccess;}
+  if (b.n >= need && (b.p || need == 0)) {return hipSuccess;}
   b.release();
-  const hipError_t e = b.alloc(need + need / 2);
+  const hipError_t e = b.alloc(exact ? need : need + need / 2);
   if (e != hipSuccess) {b.p = nullptr; b.n = 0;}
   return e;
 }
@@ -303,6 +304,18 @@ inline int fail(lfx_ctx * ctx, int code, const std::string & msg)
   return code;
 }
 
+// the calls that work on the last batch: the caller's arrays are sized by ITS count (one pose after a batch of 16 would be
+// read and written 15 entries too far)
+inline int check_last_batch(lfx_ctx * c, uint32_t n_scans)
+{
+  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
+  if (n_scans != c->last_batch) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
+             std::to_string(c->last_batch) + ")");
+  }
+  return LFX_OK;
+}
+
 // lfx_downsample.hip: lfx_voxel_downsample with the extras of lfx_localize_batch
 int voxel_downsample(
   lfx_ctx * c, const float * d_points, const uint32_t * d_begin, const uint32_t * d_count, uint32_t count_stride,
@@ -316,16 +329,23 @@ int deskew_scans(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * swe
 
 // lfx_localize.hip: a map rebuilt in place (lfx_odometry.hip's window maps) and the optimizer over clouds
 lfx_map * map_new(int device);
-uint32_t map_points(const lfx_map * m);
 int map_rebuild(lfx_ctx * c, lfx_map * m, const float * d_points, uint32_t n_points, float cell_size, const double lo[3],
   const double hi[3], hipStream_t st);
+// one kind of cloud of a set of scans, as the alignment is handed it (device pointers; lfx_scan_to_map_align's arguments)
+struct CloudSpan
+{
+  const float * points = nullptr;          // records of 4 floats
+  const uint32_t * begin = nullptr, * count = nullptr;   // cloud s: count[s * count_stride] records from record begin[s]
+  uint32_t count_stride = 1, longest = 0;  // (longest: what the launches are sized by)
+  // where each cloud's ROWS start in the residuals and Jacobians ([n_clouds]); null: where its points start.  total counts
+  // rows: with compact row starts the scratch is sized by the clouds' real lengths, not by the layout the points happen to
+  // lie in (lfx_localize_batch: scan s's clouds start at its first input point)
+  size_t total = 0;
+  const uint32_t * row_begin = nullptr;
+};
 int align_clouds(
-  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,
-  const float * d_edge_points, const uint32_t * d_edge_begin, const uint32_t * d_edge_count, uint32_t edge_count_stride,
-  uint32_t max_edge_points_per_cloud, size_t total_edge_points,
-  const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
-  uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
-  uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
-  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin, lfx_align_report * reports = nullptr);
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
+  const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
+  lfx_align_report * reports = nullptr);
 
 }  // namespace lfx_host

@@ -82,6 +82,21 @@ __device__ inline uint32_t load_ring(const uint8_t * p, uint32_t rtype, uint32_t
   }
 }
 
+// unsigned ints that order like the floats (bounds by atomicMin / atomicMax: map_bounds_kernel, odometry_append_kernel),
+// and the host's way back
+__device__ inline uint32_t float_order(float f)
+{
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline double float_of_order(uint32_t u)
+{
+  const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+  float f;
+  __builtin_memcpy(&f, &b, 4);
+  return (double)f;
+}
+
 struct Params
 {
   int P;                 // convolution_padding

@@ -644,6 +644,16 @@ struct RowsOfKind
   double * reach;                          // [rows] the distance of each row's last neighbour at the previous iteration, squared
 };
 
+// ... and what the step and report kernels read of them, which only address rows (a kernel's arguments are fetched a cache
+// line at a time: two whole RowsOfKind made every one of those kernels some 0.4 us longer)
+struct StepRows
+{
+  const double * residual, * jacobian;
+  const uint32_t * row_begin, * count;     // (row_begin: never null here; count: null = no rows of this kind)
+  uint32_t count_stride;
+};
+inline StepRows step_rows(const RowsOfKind & R) {return {R.residual, R.jacobian, R.row_begin ? R.row_begin : R.begin, R.count, R.count_stride};}
+
 __device__ __forceinline__ D3 to_map(const MapPose & P, D3 p)
 {
   return {P.m[0] * p.x + P.m[1] * p.y + P.m[2] * p.z + P.m[3], P.m[4] * p.x + P.m[5] * p.y + P.m[6] * p.z + P.m[7],
@@ -737,12 +747,6 @@ __global__ __launch_bounds__(kRowThreads) void rows_from_neighbours_kernel(
 // Building a MapIndex (lfx_map_create): bounds, points per cell, the cells' first points by an exclusive scan, then the
 // points into their cells.  The order of the points inside a cell is whatever the atomics give; nothing depends on it
 // (the search orders equal distances by the original index, which travels in the w of every sorted point).
-__device__ inline uint32_t float_order(float f)         // unsigned ints that order like the floats
-{
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void map_bounds_kernel(const float4 * __restrict__ pts, uint32_t n, uint32_t * __restrict__ bounds /* min xyz, max xyz */)
 {
   uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
@@ -903,25 +907,6 @@ __global__ __launch_bounds__(128) void map_nearest_kernel(
       if (indices) {indices[o] = GRID ? __float_as_uint(m4.w) : idx[j];}
     }
   }
-}
-
-// lfx_localize_batch: where voxel_downsample_kernel gave a cloud back unfiltered (status 1, nothing written), Downsample
-// returns the input cloud (downsample.hpp:37-51 -> pcl::VoxelGrid::applyFilter), so the rows are built from all its points.
-__global__ void downsample_passthrough_kernel(
-  const float4 * __restrict__ pts, const uint32_t * __restrict__ begin, const uint32_t * __restrict__ count, uint32_t count_stride,
-  float4 * __restrict__ out, uint32_t * __restrict__ out_count, const uint32_t * __restrict__ status,
-  const uint32_t * __restrict__ edge_count, uint32_t * __restrict__ lengths /* pinned host memory or null: [scans][2] */)
-{
-  const uint32_t s = blockIdx.x;
-  const uint32_t n = count[(size_t)s * count_stride], b = begin[s];
-  // (what the next call sizes its launches by: this scan's edge points and downsampled surface points)
-  if (lengths && threadIdx.x == 0) {lengths[2 * s] = edge_count[(size_t)s * count_stride]; lengths[2 * s + 1] = status[s] == 0u ? out_count[s] : n;}
-  if (status[s] == 0u) {return;}
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const float4 p = pts[b + i];
-    out[b + i] = make_float4(p.x, p.y, p.z, 1.f);
-  }
-  if (threadIdx.x == 0) {out_count[s] = n;}
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1221,20 +1206,43 @@ __device__ inline void solve_update(const double (&q)[4], const double * D, cons
   for (int a = 0; a < 3; a++) {dt[a] = dx[3 + a];}
 }
 
-// One iteration of Optimizer::Run after Problem::Make, in two kernels.  Rows of scan s: n3 = count3[s * stride3] residuals of
-// dimension 3 (r3 / J3 from record begin3[s]: the edge rows, or the point pairs), then n1 = count1[...] of dimension 1
-// (the surface rows; count1 may be null).  weights: one double per row, rows of scan s from begin3[s] + begin1[s] (also the
-// selection's keys when a scan has more than kAlignKeysLds rows).
-//
+// One iteration of Optimizer::Run after Problem::Make, in two kernels.  The step and report kernels take the rows as two
+// StepRows (residual, jacobian, count, count_stride and where the rows begin): of scan s, n3 = e.count[s * stride]
+// residuals of dimension 3 (the edge rows, or the point pairs), then n1 = f.count[...] of dimension 1 (the surface rows;
+// f.count may be null).  weights: one double per row, rows of scan s from b3 + b1, where its rows of either kind begin (also
+// the selection's keys when a scan has more than kAlignKeysLds rows).  All four kernels start with step_extents.
+struct StepExtents
+{
+  int32_t done;
+  uint32_t n3, b3, n1, b1;                // rows of dimension 3 and where they begin; the same of dimension 1 (0, 0 without)
+};
+// (the scan's state and extents asked for together, whether or not there are rows of dimension 1: one round trip, not four)
+__device__ __forceinline__ StepExtents step_extents(const AlignState & st, const StepRows & e, const StepRows & f, uint32_t s)
+{
+  const uint32_t * c1 = f.count ? f.count + (size_t)s * f.count_stride : e.count, * s1 = f.count ? f.row_begin + s : e.row_begin;
+  const int32_t done = st.done;
+  const uint32_t n3 = e.count[(size_t)s * e.count_stride], b3 = e.row_begin[s], n1 = *c1, b1 = *s1;
+  return {done, n3, b3, f.count ? n1 : 0u, f.count ? b1 : 0u};
+}
+
+// ComputeErrors (optimizer.cpp:99-107): the error of row i of a scan
+__device__ __forceinline__ double row_error(const StepExtents & x, const double * r3, const double * r1, uint32_t i)
+{
+  if (i < x.n3) {
+    const double * r = r3 + 3 * ((size_t)x.b3 + i);
+    return r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  }
+  const double r = r1[(size_t)x.b1 + (i - x.n3)];
+  return r * r;
+}
+
 // align_scale_kernel, one workgroup of 1024 threads per scan: ComputeErrors, the error of the scan, Scale, ComputeWeights, and
 // the two stopping tests that need nothing else (optimizer.hpp:97-108).  A scan of up to kAlignKeysLds rows keeps each
 // thread's errors in registers -- all their loads in flight at once, read once -- and the selection's keys in LDS.
 constexpr int kScaleThreads = 1024, kScaleItems = kAlignKeysLds / kScaleThreads;
 __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
-  AlignState * __restrict__ states, int iter,
-  const double * __restrict__ r3, const uint32_t * __restrict__ begin3, const uint32_t * __restrict__ count3, uint32_t stride3,
-  const double * __restrict__ r1, const uint32_t * __restrict__ begin1, const uint32_t * __restrict__ count1, uint32_t stride1,
-  double * __restrict__ weights, uint32_t * __restrict__ active, AlignOut * __restrict__ out)
+  AlignState * __restrict__ states, int iter, StepRows e, StepRows f, double * __restrict__ weights,
+  uint32_t * __restrict__ active, AlignOut * __restrict__ out)
 {
   constexpr int T = kScaleThreads, E = kScaleItems;
   static_assert(kAlignKeysLds % kScaleThreads == 0, "whole items per thread");
@@ -1243,12 +1251,10 @@ __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
   AlignState & st = states[s];
   __shared__ __attribute__((aligned(8))) uint32_t sh[kSelectWords];
   __shared__ double part[T / 64];
-  // (the scan's state and extents asked for together, whether or not there are rows of dimension 1)
-  const int32_t done = st.done;
-  const uint32_t * c1 = count1 ? count1 + (size_t)s * stride1 : count3, * s1 = count1 ? begin1 + s : begin3;
-  const uint32_t n3 = count3[(size_t)s * stride3], b3 = begin3[s], n1_ = *c1, b1_ = *s1;
-  if (done) {return;}
-  const uint32_t n1 = count1 ? n1_ : 0u, b1 = count1 ? b1_ : 0u, n = n3 + n1;
+  const StepExtents x = step_extents(st, e, f, s);
+  if (x.done) {return;}
+  const double * r3 = e.residual, * r1 = f.residual;
+  const uint32_t n3 = x.n3, b3 = x.b3, n1 = x.n1, b1 = x.b1, n = n3 + n1;
   if (n == 0u) {                                            // EmptyInput (optimization_result.hpp:46-50)
     if (tid == 0) {align_finish(st, out[s], iter, 0., 0., kAlignEmpty, active);}
     return;
@@ -1266,14 +1272,6 @@ __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
   __shared__ double keys_lds[kAlignKeysLds];
   const bool small = n <= (uint32_t)kAlignKeysLds;
   double * key = small ? keys_lds : w_out;                   // (a longer scan: the keys pass through the weights' place)
-  auto row_error = [&](uint32_t i) {                         // ComputeErrors (optimizer.cpp:99-107)
-      if (i < n3) {
-        const double * r = r3 + 3 * ((size_t)b3 + i);
-        return r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      }
-      const double r = r1[(size_t)b1 + (i - n3)];
-      return r * r;
-    };
   if (tid < 256) {sh[tid] = 0u;}                              // (the selection's bins; the barrier after the keys covers this)
   double e_reg[E];
   double esum = 0.;
@@ -1297,7 +1295,7 @@ __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
       if (i < n) {key[i] = e_reg[k]; esum += e_reg[k];}
     }
   } else {
-    for (uint32_t i = tid; i < n; i += T) {const double e = row_error(i); key[i] = e; esum += e;}
+    for (uint32_t i = tid; i < n; i += T) {const double err = row_error(x, r3, r1, i); key[i] = err; esum += err;}
   }
   __syncthreads();
   // Scale (robust.cpp:36-50): b * median(|e - median(e)|)
@@ -1323,7 +1321,7 @@ __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
     }
   } else {
     for (uint32_t i = tid; i < n; i += T) {
-      const double en = row_error(i) / (scale + 1e-16);
+      const double en = row_error(x, r3, r1, i) / (scale + 1e-16);
       w_out[i] = en < 1.345 * 1.345 ? 1. : 1.345 / sqrt(en);
     }
   }
@@ -1362,35 +1360,26 @@ __global__ __launch_bounds__(kScaleThreads) void align_scale_kernel(
 // C[row = (lane >> 4) + 4 reg][col = lane & 15], i.e. element reg * 64 + lane of a wave's result is C[16 row + col].)
 constexpr int kAlignSlices = 16, kAlignTile = 256;
 typedef double lfx_f64x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(kAlignThreads) void align_update_kernel(
-  AlignState * __restrict__ states, int iter, int max_iter,
-  const double * __restrict__ r3, const double * __restrict__ J3, const uint32_t * __restrict__ begin3,
-  const uint32_t * __restrict__ count3, uint32_t stride3,
-  const double * __restrict__ r1, const double * __restrict__ J1, const uint32_t * __restrict__ begin1,
-  const uint32_t * __restrict__ count1, uint32_t stride1, const double * __restrict__ weights, double * __restrict__ partials,
-  uint32_t * __restrict__ tickets, uint32_t * __restrict__ active, AlignOut * __restrict__ out)
+// The sums themselves, for align_update_kernel and align_report_kernel: workgroup g of scan s adds its share of the rows; the
+// one that draws the scan's last ticket (true is returned to it alone) finds the 16 x 16 tile of the sums in total[], every
+// thread past the barrier behind it.
+__device__ __forceinline__ bool normal_equation_sums(const StepExtents & ext, const StepRows & e, const StepRows & f,
+  const double * __restrict__ weights, double * __restrict__ partials, uint32_t * __restrict__ tickets, uint32_t s, uint32_t g,
+  double * total /* LDS, [kAlignTile] */)
 {
   constexpr int T = kAlignThreads, W = T / 64, NS = kAlignTile, G = kAlignSlices;
   static_assert(T == NS, "one thread per element of the tile in the sums across waves and slices");
-  const uint32_t s = blockIdx.y, g = blockIdx.x;
   const int tid = threadIdx.x;
-  AlignState & st = states[s];
   __shared__ double part[W][NS];
-  __shared__ double total[NS];
   __shared__ uint32_t last;
-  // (the scan's state and extents asked for together, whether or not there are rows of dimension 1: one round trip, not four)
-  const int32_t done = st.done;
-  const uint32_t * c1 = count1 ? count1 + (size_t)s * stride1 : count3, * s1 = count1 ? begin1 + s : begin3;
-  const uint32_t n3 = count3[(size_t)s * stride3], b3 = begin3[s], n1_ = *c1, b1_ = *s1;
-  if (done) {return;}
-  const uint32_t n1 = count1 ? n1_ : 0u, b1 = count1 ? b1_ : 0u;
+  const uint32_t n3 = ext.n3, b3 = ext.b3, n1 = ext.n1, b1 = ext.b1;
   const double * key = weights + (size_t)b3 + b1;
   const uint32_t wave = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6), lane = (uint32_t)tid & 63u;
   lfx_f64x4 acc = {0., 0., 0., 0.};
   {
     const uint32_t m3 = 3u * n3, m_all = m3 + n1, groups = (m_all + 3u) / 4u;
-    const double * Je = J3 + 21 * (size_t)b3, * re = r3 + 3 * (size_t)b3;
-    const double * Js = J1 + 7 * (size_t)b1, * rs = r1 + (size_t)b1;
+    const double * Je = e.jacobian + 21 * (size_t)b3, * re = e.residual + 3 * (size_t)b3;
+    const double * Js = f.jacobian + 7 * (size_t)b1, * rs = f.residual + (size_t)b1;
     const uint32_t k = lane >> 4, c = lane & 15u;
     const bool plain = c < 7u, weighted = c >= 8u && c < 15u;
     const uint32_t jc = plain ? c : (weighted ? c - 8u : 0u);          // the column of J this lane reads
@@ -1406,8 +1395,8 @@ __global__ __launch_bounds__(kAlignThreads) void align_update_kernel(
         const bool edge = mm < m3;
         const double * J = edge ? Je + 7 * (size_t)mm : Js + 7 * (size_t)(mm - m3);
         const double * R = edge ? re + mm : rs + (mm - m3);
-        // (every lane loads -- a lane with nothing to fetch reads row 0 -- and what it read is masked afterwards: loads under
-        // a condition are waited for one by one)
+        // (every lane loads -- a lane with nothing to fetch reads row 0, which exists: there is a group -- and what it read is
+        // masked afterwards: loads under a condition are waited for one by one)
         x[u] = *(c == 7u ? R : J + jc);                               // J[m][c] | r[m] | J[m][c - 8]
         wv[u] = key[edge ? mm / 3u : n3 + (mm - m3)];
         x[u] = live && c != 15u ? x[u] : 0.;
@@ -1438,7 +1427,7 @@ __global__ __launch_bounds__(kAlignThreads) void align_update_kernel(
   __syncthreads();
   if (tid == 0) {last = __hip_atomic_fetch_add(&tickets[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)G - 1u ? 1u : 0u;}
   __syncthreads();
-  if (last == 0u) {return;}
+  if (last == 0u) {return false;}
   {
     double * all = partials + (size_t)s * G * NS;
     double v = 0.;
@@ -1447,7 +1436,20 @@ __global__ __launch_bounds__(kAlignThreads) void align_update_kernel(
     total[tid] = v;
   }
   __syncthreads();
-  if (tid != 0) {return;}
+  return true;
+}
+
+__global__ __launch_bounds__(kAlignThreads) void align_update_kernel(
+  AlignState * __restrict__ states, int iter, int max_iter, StepRows e, StepRows f, const double * __restrict__ weights,
+  double * __restrict__ partials, uint32_t * __restrict__ tickets, uint32_t * __restrict__ active, AlignOut * __restrict__ out)
+{
+  const uint32_t s = blockIdx.y;
+  AlignState & st = states[s];
+  __shared__ double total[kAlignTile];
+  const StepExtents x = step_extents(st, e, f, s);
+  if (x.done) {return;}
+  if (!normal_equation_sums(x, e, f, weights, partials, tickets, s, blockIdx.x, total)) {return;}
+  if (threadIdx.x != 0) {return;}
   tickets[s] = 0u;                                           // for the next iteration
   const double error = st.cur_error, scale = st.cur_scale;   // (both have passed align_scale_kernel's tests)
   double D[49], A[49], b[7];

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "lfx_kernels_common.hpp"
 #include "lfx_kernels_transform.hpp"
 
 namespace lfx
@@ -16,18 +17,11 @@ struct OdoPose
   double m[12];                           // point_to_map, [R | t] row-major
 };
 
-// unsigned ints that order like the floats (map_bounds_kernel's encoding, lfx_kernels_localize.hpp)
-__device__ inline uint32_t odo_float_order(float f)
-{
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 constexpr int kAppendThreads = 256;
 
 // RecentScans::Add (recent_scans.hpp:67-73) for both clouds of one scan in one launch: pcl_transform_record.  Workgroups
 // [0, edge_blocks) take the edge cloud, the rest the surface cloud.  bounds [2][6] (edge, surface), zeroed before the launch:
-// words 0-2 the complement of the least x, y, z and words 3-5 the greatest, both by atomicMax over odo_float_order -- all
+// words 0-2 the complement of the least x, y, z and words 3-5 the greatest, both by atomicMax over float_order -- all
 // zero = no point.
 __global__ __launch_bounds__(kAppendThreads) void odometry_append_kernel(
   OdoPose P, const float4 * __restrict__ edge_src, uint32_t n_edge, const float4 * __restrict__ surface_src, uint32_t n_surface,
@@ -41,8 +35,8 @@ __global__ __launch_bounds__(kAppendThreads) void odometry_append_kernel(
     const float4 p = (surf ? surface_src : edge_src)[i];
     const float4 q = pcl_transform_record(P.m, p);
     (surf ? surface_dst : edge_dst)[i] = q;
-    v[0] = ~odo_float_order(q.x); v[1] = ~odo_float_order(q.y); v[2] = ~odo_float_order(q.z);
-    v[3] = odo_float_order(q.x); v[4] = odo_float_order(q.y); v[5] = odo_float_order(q.z);
+    v[0] = ~float_order(q.x); v[1] = ~float_order(q.y); v[2] = ~float_order(q.z);
+    v[3] = float_order(q.x); v[4] = float_order(q.y); v[5] = float_order(q.z);
   }
 #pragma unroll
   for (int a = 0; a < 6; a++) {

@@ -56,13 +56,10 @@ __global__ void report_begin_kernel(AlignState * __restrict__ states, const Repo
 }
 
 // ComputeErrors / NormalizeErrorScale / ComputeWeights (optimizer.cpp:100-128) at the report's pose: the weights of the
-// scan's residuals into `weights` (rows of scan s from begin3[s] + begin1[s], as align_scale_kernel leaves them), the sums
+// scan's residuals into `weights` (rows of scan s from b3 + b1, as align_scale_kernel leaves them), the sums
 // over residuals into sums[s].  Sums in a fixed tree order.
 __global__ __launch_bounds__(kScaleThreads) void align_report_scale_kernel(
-  const AlignState * __restrict__ states,
-  const double * __restrict__ r3, const uint32_t * __restrict__ begin3, const uint32_t * __restrict__ count3, uint32_t stride3,
-  const double * __restrict__ r1, const double * __restrict__ J1, const uint32_t * __restrict__ begin1,
-  const uint32_t * __restrict__ count1, uint32_t stride1, double * __restrict__ weights, ReportSums * __restrict__ sums)
+  const AlignState * __restrict__ states, StepRows e, StepRows f, double * __restrict__ weights, ReportSums * __restrict__ sums)
 {
   constexpr int T = kScaleThreads, W = T / 64;
   const uint32_t s = blockIdx.x;
@@ -71,24 +68,18 @@ __global__ __launch_bounds__(kScaleThreads) void align_report_scale_kernel(
   __shared__ double keys_lds[kAlignKeysLds];
   __shared__ double part[W][4];
   __shared__ uint32_t cnt[W][3];
-  if (states[s].done) {return;}
-  const uint32_t n3 = count3[(size_t)s * stride3], b3 = begin3[s], n1 = count1[(size_t)s * stride1], b1 = begin1[s], n = n3 + n1;
+  const StepExtents x = step_extents(states[s], e, f, s);
+  if (x.done) {return;}
+  const double * r3 = e.residual, * r1 = f.residual, * J1 = f.jacobian;
+  const uint32_t n3 = x.n3, b3 = x.b3, n1 = x.n1, b1 = x.b1, n = n3 + n1;
   if (n == 0u) {
     if (tid == 0) {sums[s] = ReportSums{};}
     return;
   }
   double * w_out = weights + (size_t)b3 + b1;
   double * key = n <= (uint32_t)kAlignKeysLds ? keys_lds : w_out;     // (a longer scan: the keys pass through the weights' place)
-  auto row_error = [&](uint32_t i) {
-      if (i < n3) {
-        const double * r = r3 + 3 * ((size_t)b3 + i);
-        return r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      }
-      const double r = r1[(size_t)b1 + (i - n3)];
-      return r * r;
-    };
   if (tid < 256) {sh[tid] = 0u;}
-  for (uint32_t i = tid; i < n; i += T) {key[i] = row_error(i);}
+  for (uint32_t i = tid; i < n; i += T) {key[i] = row_error(x, r3, r1, i);}
   __syncthreads();
   const double median = workgroup_median(key, n, sh);
   for (uint32_t i = tid; i < n; i += T) {key[i] = fabs(key[i] - median);}
@@ -98,16 +89,16 @@ __global__ __launch_bounds__(kScaleThreads) void align_report_scale_kernel(
   double se3 = 0., se1 = 0., swe = 0., swd = 0.;
   uint32_t in3 = 0, in1 = 0, zero = 0;
   for (uint32_t i = tid; i < n; i += T) {
-    const double e = row_error(i), en = e / (scale + 1e-16);
+    const double err = row_error(x, r3, r1, i), en = err / (scale + 1e-16);
     const bool inlier = en < 1.345 * 1.345;
     const double w = inlier ? 1. : 1.345 / sqrt(en);
     w_out[i] = w;
-    swe += w * e;
+    swe += w * err;
     if (i < n3) {
-      se3 += e; swd += 3. * w; in3 += inlier ? 1u : 0u;
+      se3 += err; swd += 3. * w; in3 += inlier ? 1u : 0u;
     } else {
       const double * J = J1 + 7 * ((size_t)b1 + (i - n3));
-      se1 += e; swd += w; in1 += inlier ? 1u : 0u;
+      se1 += err; swd += w; in1 += inlier ? 1u : 0u;
       zero += J[4] == 0. && J[5] == 0. && J[6] == 0. ? 1u : 0u;
     }
   }
@@ -325,91 +316,25 @@ __device__ __forceinline__ bool report_finish_h(const double * total, const MapP
   return ok;
 }
 
-// The sums of the report, kAlignSlices workgroups per scan (blockIdx.y): four rows at a time through
-// v_mfma_f64_16x16x4_f64 with the left operand [J | 0 | w J | 0]^T and the right operand [J | r | 0], as align_update_kernel
-// takes them (its comment has the operand and result lanes): D in rows 0-6 and A in rows 8-14 of the 16 x 16 tile.  The
-// waves' tiles are added in wave order; the slice's tile leaves in write-through stores at agent scope, the wave waits for
-// them, one thread takes the ticket, and the workgroup that draws the last one adds the slices in slice order with loads
-// at agent scope (cdna_hip_programming.md Guideline 16) and completes the record.  out / out_done: pinned host memory.
+// The sums of the report, kAlignSlices workgroups per scan (blockIdx.y): normal_equation_sums as align_update_kernel takes
+// them (its comment has the operand and result lanes), D in rows 0-6 and A in rows 8-14 of the 16 x 16 tile; the workgroup
+// that draws the last ticket completes the record.  out / out_done: pinned host memory.
 __global__ __launch_bounds__(kAlignThreads) void align_report_kernel(
-  const AlignState * __restrict__ states,
-  const double * __restrict__ r3, const double * __restrict__ J3, const uint32_t * __restrict__ begin3,
-  const uint32_t * __restrict__ count3, uint32_t stride3,
-  const double * __restrict__ r1, const double * __restrict__ J1, const uint32_t * __restrict__ begin1,
-  const uint32_t * __restrict__ count1, uint32_t stride1, const double * __restrict__ weights,
+  const AlignState * __restrict__ states, StepRows e, StepRows f, const double * __restrict__ weights,
   const ReportSums * __restrict__ sums, double * __restrict__ partials, uint32_t * __restrict__ tickets,
   AlignReport * __restrict__ out, int32_t * __restrict__ out_done)
 {
-  constexpr int T = kAlignThreads, W = T / 64, NS = kAlignTile, G = kAlignSlices;
-  static_assert(T == NS, "one thread per element of the tile in the sums across waves and slices");
-  const uint32_t s = blockIdx.y, g = blockIdx.x;
+  const uint32_t s = blockIdx.y;
   const int tid = threadIdx.x;
-  __shared__ double part[W][NS];
-  __shared__ double total[NS];
-  __shared__ uint32_t last;
-  const int32_t done = states[s].done;
-  const uint32_t n3 = count3[(size_t)s * stride3], b3 = begin3[s], n1 = count1[(size_t)s * stride1], b1 = begin1[s];
-  if (done) {return;}
-  const double * key = weights + (size_t)b3 + b1;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6), lane = (uint32_t)tid & 63u;
-  lfx_f64x4 acc = {0., 0., 0., 0.};
-  {
-    const uint32_t m3 = 3u * n3, m_all = m3 + n1, groups = (m_all + 3u) / 4u;
-    const double * Je = J3 + 21 * (size_t)b3, * re = r3 + 3 * (size_t)b3;
-    const double * Js = J1 + 7 * (size_t)b1, * rs = r1 + (size_t)b1;
-    const uint32_t k = lane >> 4, c = lane & 15u;
-    const bool plain = c < 7u, weighted = c >= 8u && c < 15u;
-    const uint32_t jc = plain ? c : (weighted ? c - 8u : 0u);
-    constexpr int U = 12;
-    for (uint32_t g0 = g * W + wave; g0 < groups; g0 += U * G * W) {
-      double x[U], wv[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint32_t m = 4u * (g0 + (uint32_t)u * G * W) + k;
-        const bool live = m < m_all;
-        const uint32_t mm = live ? m : 0u;
-        const bool edge = mm < m3;
-        const double * J = edge ? Je + 7 * (size_t)mm : Js + 7 * (size_t)(mm - m3);
-        const double * R = edge ? re + mm : rs + (mm - m3);
-        // (every lane loads -- a lane with nothing to fetch reads row 0, which exists: there is a group -- and what it read is masked)
-        x[u] = *(c == 7u ? R : J + jc);
-        wv[u] = key[edge ? mm / 3u : n3 + (mm - m3)];
-        x[u] = live && c != 15u ? x[u] : 0.;
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const double a = plain ? x[u] : (weighted ? wv[u] * x[u] : 0.);
-        const double b = weighted ? 0. : x[u];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++) {part[wave][64 * r + lane] = acc[r];}
-  __syncthreads();
-  double * mine = partials + ((size_t)s * G + g) * NS;
-  {
-    double v = 0.;
-    for (int wv = 0; wv < W; wv++) {v += part[wv][tid];}
-    __hip_atomic_store(&mine[tid], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {last = __hip_atomic_fetch_add(&tickets[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)G - 1u ? 1u : 0u;}
-  __syncthreads();
-  if (last == 0u) {return;}
-  {
-    double * all = partials + (size_t)s * G * NS;
-    double v = 0.;
-#pragma unroll
-    for (int k = 0; k < G; k++) {v += __hip_atomic_load(&all[(size_t)k * NS + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);}
-    total[tid] = v;
-  }
-  __syncthreads();
+  __shared__ double total[kAlignTile];
+  __shared__ uint32_t d_ok;
+  const StepExtents x = step_extents(states[s], e, f, s);
+  if (x.done) {return;}
+  if (!normal_equation_sums(x, e, f, weights, partials, tickets, s, blockIdx.x, total)) {return;}
   const ReportSums sm = sums[s];
   const bool rows = sm.n_edge + sm.n_surface != 0u;
   if (tid == 64) {                                           // (wave 1: D's eigenvalues beside H's)
-    last = rows && report_finish_d(total, out[s]) ? 1u : 0u;
+    d_ok = rows && report_finish_d(total, out[s]) ? 1u : 0u;
     __threadfence_system();
   }
   bool ok = false;
@@ -417,7 +342,7 @@ __global__ __launch_bounds__(kAlignThreads) void align_report_kernel(
   __syncthreads();
   if (tid != 0) {return;}
   tickets[s] = 0u;
-  out[s].valid = ok && last != 0u ? 1 : 0;                   // (0: the host leaves the caller's record all zero)
+  out[s].valid = ok && d_ok != 0u ? 1 : 0;                   // (0: the host leaves the caller's record all zero)
   __threadfence_system();
   *reinterpret_cast<volatile int32_t *>(&out_done[s]) = 1;
 }

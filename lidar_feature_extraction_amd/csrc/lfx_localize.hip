@@ -36,6 +36,40 @@ void grid_of(const double lo[3], const double hi[3], float cell_size, double & h
   }
 }
 
+// The index of map m over the n_points >= 1 records at src (m->pts holds that many): a grid of cells of cell_size over
+// [lo, hi], the bounds of the points as map_bounds_kernel finds them -- points per cell, the cells' first points by an
+// exclusive scan, the points into their cells -- or, cell_size 0, a copy of the points.  The cells' starts and the build's
+// scratch are held as hold() holds them (`exact`: no larger than needed).  Nothing is waited for.
+hipError_t build_index(lfx_map * m, const float4 * src, uint32_t n_points, float cell_size, const double lo[3], const double hi[3],
+  DevBuf<uint32_t> & cell_count, DevBuf<uint32_t> & partial, bool exact, hipStream_t st)
+{
+  lfx::MapIndex & mi = m->index;
+  mi.pts = m->pts.p; mi.start = nullptr; mi.n = n_points;
+  mi.ox = mi.oy = mi.oz = 0.; mi.h = 0.; mi.inv_h = 0.; mi.nx = mi.ny = mi.nz = 1;
+  if (cell_size == 0.f) {return hipMemcpyAsync(m->pts.p, src, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToDevice, st);}
+  double h;
+  int dims[3];
+  grid_of(lo, hi, cell_size, h, dims);
+  const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
+  const uint32_t n_blocks = (uint32_t)((cells + lfx::kScanItems - 1) / lfx::kScanItems);
+  hipError_t e = hold(m->start, cells + 1, exact);
+  if (e == hipSuccess) {e = hold(cell_count, cells, exact);}
+  if (e == hipSuccess) {e = hold(partial, (size_t)n_blocks + 1, exact);}
+  if (e == hipSuccess) {e = hipMemsetAsync(cell_count.p, 0, cells * sizeof(uint32_t), st);}
+  if (e != hipSuccess) {return e;}
+  mi.ox = lo[0]; mi.oy = lo[1]; mi.oz = lo[2]; mi.h = h; mi.inv_h = 1. / h; mi.nx = dims[0]; mi.ny = dims[1]; mi.nz = dims[2];
+  m->cell = (float)h;
+  const dim3 per_point((n_points + 255u) / 256u);
+  hipLaunchKernelGGL(lfx::map_count_kernel, per_point, dim3(256), 0, st, mi, src, cell_count.p);
+  hipLaunchKernelGGL(lfx::cell_block_sum_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, cell_count.p, cells, partial.p);
+  hipLaunchKernelGGL(lfx::cell_partial_scan_kernel, dim3(1), dim3(lfx::kScanThreads), 0, st, partial.p, n_blocks);
+  hipLaunchKernelGGL(lfx::cell_start_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, cell_count.p, cells, partial.p, m->start.p, n_points);
+  hipLaunchKernelGGL(lfx::map_scatter_kernel, per_point, dim3(256), 0, st, mi, src, cell_count.p, m->start.p, m->pts.p);
+  e = hipGetLastError();
+  if (e == hipSuccess) {mi.start = m->start.p;}
+  return e;
+}
+
 // Eigen::Quaterniond(Matrix3d) of a pose's rotation (the branch on the trace, then on the largest diagonal entry), on the
 // host: what lfx_scan_to_map_residuals hands its kernels beside pose[12], and what the report pass of run_align is given
 void map_pose_of(const double pose[12], lfx::MapPose & P)
@@ -63,15 +97,13 @@ void map_pose_of(const double pose[12], lfx::MapPose & P)
   P.qw = w; P.qx = q[0]; P.qy = q[1]; P.qz = q[2];
 }
 
-void launch_rows(bool surface, const lfx::MapIndex & mi, const lfx::MapPose & P, uint32_t k, const float * d_points,
-  const uint32_t * d_begin, const uint32_t * d_count, uint32_t count_stride, uint32_t n_clouds, uint32_t longest, double * d_residual,
-  double * d_jacobian, const lfx::AlignState * states, hipStream_t st, const uint32_t * d_row_begin = nullptr)
+void launch_rows(bool surface, const lfx::RowsOfKind & R, const lfx::MapPose & P, uint32_t k, uint32_t n_clouds, uint32_t longest,
+  const lfx::AlignState * states, hipStream_t st)
 {
-  const bool wave = mi.start != nullptr;              // a grid: one query per wave; no grid: one per thread, the map through LDS
+  const bool wave = R.mi.start != nullptr;            // a grid: one query per wave; no grid: one per thread, the map through LDS
   const dim3 grid(wave ? longest : (longest + 127u) / 128u, n_clouds), block(wave ? 64 : 128);
-  const float4 * pts = reinterpret_cast<const float4 *>(d_points);
-#define LFX_ROWS(S, M) hipLaunchKernelGGL((lfx::scan_to_map_kernel<S, M>), grid, block, 0, st, mi, P, k, pts, d_begin, d_count, \
-    count_stride, d_residual, d_jacobian, states, d_row_begin)
+#define LFX_ROWS(S, M) hipLaunchKernelGGL((lfx::scan_to_map_kernel<S, M>), grid, block, 0, st, R.mi, P, k, R.pts, R.begin, R.count, \
+    R.count_stride, R.residual, R.jacobian, states, R.row_begin)
   if (wave) {
     if (surface) {LFX_ROWS(true, lfx::kSearchGridWave);} else {LFX_ROWS(false, lfx::kSearchGridWave);}
   } else {
@@ -94,68 +126,33 @@ int lfx_map_create(lfx_ctx * c, const float * d_points, uint32_t n_points, float
   m->device = c->device;
   auto give_up = [&](int code, const char * why) {lfx_map_destroy(m); return fail(c, code, why);};
   if (m->pts.alloc(n_points) != hipSuccess) {m->pts.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's points");}
-  lfx::MapIndex & mi = m->index;
-  mi.pts = m->pts.p; mi.start = nullptr; mi.n = n_points;
-  mi.ox = mi.oy = mi.oz = 0.; mi.h = 0.; mi.inv_h = 0.; mi.nx = mi.ny = mi.nz = 1;
   const float4 * src = reinterpret_cast<const float4 *>(d_points);
-  if (cell_size == 0.f) {
-    hipError_t e = hipMemcpyAsync(m->pts.p, src, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToDevice, st);
+  double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+  if (cell_size != 0.f) {                              // bounds of the map
+    uint32_t * d_bounds = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d_bounds), 6 * sizeof(uint32_t)) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's bounds");}
+    const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+    uint32_t got[6];
+    hipError_t e = hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      const uint32_t blocks = std::min<uint32_t>((n_points + 255u) / 256u, 2048u);
+      hipLaunchKernelGGL(lfx::map_bounds_kernel, dim3(blocks), dim3(256), 0, st, src, n_points, d_bounds);
+      e = hipMemcpyAsync(got, d_bounds, sizeof(got), hipMemcpyDeviceToHost, st);
+    }
     if (e == hipSuccess) {e = hipStreamSynchronize(st);}
+    (void)hipFree(d_bounds);
     if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
-    *out = m;
-    return LFX_OK;
+    for (int a = 0; a < 3; a++) {
+      lo[a] = lfx::float_of_order(got[a]); hi[a] = lfx::float_of_order(got[3 + a]);
+      if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {return give_up(LFX_ERR_INVALID_ARGUMENT, "the map holds a point that is not finite");}
+    }
   }
-  // bounds of the map
-  uint32_t * d_bounds = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(&d_bounds), 6 * sizeof(uint32_t)) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's bounds");}
-  const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-  uint32_t got[6];
-  hipError_t e = hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    const uint32_t blocks = std::min<uint32_t>((n_points + 255u) / 256u, 2048u);
-    hipLaunchKernelGGL(lfx::map_bounds_kernel, dim3(blocks), dim3(256), 0, st, src, n_points, d_bounds);
-    e = hipMemcpyAsync(got, d_bounds, sizeof(got), hipMemcpyDeviceToHost, st);
-  }
-  if (e == hipSuccess) {e = hipStreamSynchronize(st);}
-  (void)hipFree(d_bounds);
-  if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
-  auto back = [](uint32_t u) {
-      const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-      float f;
-      std::memcpy(&f, &b, 4);
-      return (double)f;
-    };
-  const double lo[3] = {back(got[0]), back(got[1]), back(got[2])}, hi[3] = {back(got[3]), back(got[4]), back(got[5])};
-  for (int a = 0; a < 3; a++) {
-    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {return give_up(LFX_ERR_INVALID_ARGUMENT, "the map holds a point that is not finite");}
-  }
-  double h;
-  int dims[3];
-  grid_of(lo, hi, cell_size, h, dims);
-  mi.ox = lo[0]; mi.oy = lo[1]; mi.oz = lo[2]; mi.h = h; mi.inv_h = 1. / h; mi.nx = dims[0]; mi.ny = dims[1]; mi.nz = dims[2];
-  m->cell = (float)h;
-  const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
-  const uint32_t n_blocks = (uint32_t)((cells + lfx::kScanItems - 1) / lfx::kScanItems);
-  DevBuf<uint32_t> cell_count, partial;
-  if (m->start.alloc(cells + 1) != hipSuccess) {m->start.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's cells");}
-  if (cell_count.alloc(cells) != hipSuccess || partial.alloc(n_blocks + 1) != hipSuccess) {
-    cell_count.release(); partial.release();
-    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's cells");
-  }
-  e = hipMemsetAsync(cell_count.p, 0, cells * sizeof(uint32_t), st);
-  if (e == hipSuccess) {
-    const dim3 per_point((n_points + 255u) / 256u);
-    hipLaunchKernelGGL(lfx::map_count_kernel, per_point, dim3(256), 0, st, mi, src, cell_count.p);
-    hipLaunchKernelGGL(lfx::cell_block_sum_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, cell_count.p, cells, partial.p);
-    hipLaunchKernelGGL(lfx::cell_partial_scan_kernel, dim3(1), dim3(lfx::kScanThreads), 0, st, partial.p, n_blocks);
-    hipLaunchKernelGGL(lfx::cell_start_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, cell_count.p, cells, partial.p, m->start.p, n_points);
-    hipLaunchKernelGGL(lfx::map_scatter_kernel, per_point, dim3(256), 0, st, mi, src, cell_count.p, m->start.p, m->pts.p);
-    e = hipGetLastError();
-  }
+  DevBuf<uint32_t> cell_count, partial;                // the build's scratch, this call's own
+  hipError_t e = build_index(m, src, n_points, cell_size, lo, hi, cell_count, partial, true, st);
   if (e == hipSuccess) {e = hipStreamSynchronize(st);}
   cell_count.release(); partial.release();
+  if (e == hipErrorOutOfMemory) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's cells");}
   if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
-  mi.start = m->start.p;
   *out = m;
   return LFX_OK;
 }
@@ -225,43 +222,14 @@ lfx_map * map_new(int device)
   return m;
 }
 
-uint32_t map_points(const lfx_map * m) {return m->index.n;}
-
 // The index of lfx_map_create over n_points records at d_points, rebuilt in place: the map keeps its buffers (grown by half
 // again when they must grow), the bounds come from the caller ([lo, hi] of the points, as map_bounds_kernel would find
 // them), nothing is waited for.  The same grid, the same cells, the same kernels as lfx_map_create; n_points >= 1.
 int map_rebuild(lfx_ctx * c, lfx_map * m, const float * d_points, uint32_t n_points, float cell_size, const double lo[3],
   const double hi[3], hipStream_t st)
 {
-  lfx::MapIndex & mi = m->index;
   LFX_HIP(c, hold(m->pts, n_points));
-  mi.pts = m->pts.p; mi.start = nullptr; mi.n = n_points;
-  mi.ox = mi.oy = mi.oz = 0.; mi.h = 0.; mi.inv_h = 0.; mi.nx = mi.ny = mi.nz = 1;
-  const float4 * src = reinterpret_cast<const float4 *>(d_points);
-  if (cell_size == 0.f) {
-    LFX_HIP(c, hipMemcpyAsync(m->pts.p, src, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToDevice, st));
-    return LFX_OK;
-  }
-  double h;
-  int dims[3];
-  grid_of(lo, hi, cell_size, h, dims);
-  const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
-  const uint32_t n_blocks = (uint32_t)((cells + lfx::kScanItems - 1) / lfx::kScanItems);
-  LFX_HIP(c, hold(m->start, cells + 1));
-  LFX_HIP(c, hold(m->cell_count, cells));
-  LFX_HIP(c, hold(m->partial, (size_t)n_blocks + 1));
-  mi.ox = lo[0]; mi.oy = lo[1]; mi.oz = lo[2]; mi.h = h; mi.inv_h = 1. / h; mi.nx = dims[0]; mi.ny = dims[1]; mi.nz = dims[2];
-  m->cell = (float)h;
-  LFX_HIP(c, hipMemsetAsync(m->cell_count.p, 0, cells * sizeof(uint32_t), st));
-  const dim3 per_point((n_points + 255u) / 256u);
-  hipLaunchKernelGGL(lfx::map_count_kernel, per_point, dim3(256), 0, st, mi, src, m->cell_count.p);
-  hipLaunchKernelGGL(lfx::cell_block_sum_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, m->cell_count.p, cells, m->partial.p);
-  hipLaunchKernelGGL(lfx::cell_partial_scan_kernel, dim3(1), dim3(lfx::kScanThreads), 0, st, m->partial.p, n_blocks);
-  hipLaunchKernelGGL(lfx::cell_start_kernel, dim3(n_blocks), dim3(lfx::kScanThreads), 0, st, m->cell_count.p, cells, m->partial.p,
-    m->start.p, n_points);
-  hipLaunchKernelGGL(lfx::map_scatter_kernel, per_point, dim3(256), 0, st, mi, src, m->cell_count.p, m->start.p, m->pts.p);
-  LFX_HIP(c, hipGetLastError());
-  mi.start = m->start.p;
+  LFX_HIP(c, build_index(m, reinterpret_cast<const float4 *>(d_points), n_points, cell_size, lo, hi, m->cell_count, m->partial, false, st));
   return LFX_OK;
 }
 }  // namespace lfx_host
@@ -287,8 +255,9 @@ int lfx_scan_to_map_residuals(
   LFX_HIP(c, hipSetDevice(c->device));
   lfx::MapPose P;
   map_pose_of(pose, P);
-  launch_rows(kind == LFX_RESIDUAL_SURFACE, map->index, P, n_neighbors, d_points, d_begin, d_count, count_stride, n_clouds,
-    max_points_per_cloud, d_residual, d_jacobian, nullptr, static_cast<hipStream_t>(stream));
+  const lfx::RowsOfKind R{map->index, reinterpret_cast<const float4 *>(d_points), d_begin, d_count, count_stride, d_residual, d_jacobian,
+    nullptr, nullptr, nullptr};
+  launch_rows(kind == LFX_RESIDUAL_SURFACE, R, P, n_neighbors, n_clouds, max_points_per_cloud, nullptr, static_cast<hipStream_t>(stream));
   LFX_HIP(c, hipGetLastError());
   return LFX_OK;
 }
@@ -313,22 +282,29 @@ int lfx_edge_residuals(
 // ---------------------------------------------------------------------------- the optimizer around the rows
 namespace
 {
-struct AlignProblem                     // what Problem::Make reads, per kind
+struct AlignProblem                     // what Problem::Make reads
 {
-  // rows of dimension 3: the edge clouds, or the point pairs
-  const lfx_map * edge_map = nullptr;
-  const float * edge_points = nullptr; const double * X = nullptr, * Y = nullptr;
-  const uint32_t * begin3 = nullptr, * count3 = nullptr; uint32_t stride3 = 1, longest3 = 0; size_t total3 = 0;
-  // rows of dimension 1: the downsampled surface clouds
-  const lfx_map * surface_map = nullptr;
-  const float * surface_points = nullptr;
-  const uint32_t * begin1 = nullptr, * count1 = nullptr; uint32_t stride1 = 1, longest1 = 0; size_t total1 = 0;
+  // rows of dimension 3: the edge clouds against their map, or the point pairs X, Y (then `edge` holds begin, count, longest
+  // and total alone); rows of dimension 1: the downsampled surface clouds against theirs
+  const lfx_map * edge_map = nullptr, * surface_map = nullptr;
+  CloudSpan edge, surface;
+  const double * X = nullptr, * Y = nullptr;
   uint32_t n_neighbors = 0;
-  // where each cloud's ROWS start in r3 / J3 and r1 / J1 (device, [n_clouds]); null: where its points start.  total3 /
-  // total1 count rows: with compact row starts the scratch is sized by the clouds' real lengths, not by the layout the
-  // points happen to lie in (lfx_localize_batch: scan s's clouds start at its first input point)
-  const uint32_t * rbegin3 = nullptr, * rbegin1 = nullptr;
 };
+
+// The host's wait for records the kernels write into pinned memory: on the records themselves first (the thread that ends a
+// scan sets its done word behind a system-scope fence; a blocking wait on the stream wakes 30-50 us late, a third of what a
+// whole scan's alignment takes), then until the stream has drained what was queued behind them
+template<typename AllDone>
+hipError_t wait_for_records(AllDone all_done, hipStream_t st)
+{
+  hipError_t q = hipErrorNotReady;
+  for (uint32_t spins = 0; q == hipErrorNotReady; spins++) {
+    if (all_done() || (spins & 63u) == 63u) {q = hipStreamQuery(st);}
+    if (spins > (1u << 24)) {q = hipStreamSynchronize(st);}         // (seconds: something else holds the stream)
+  }
+  return q;
+}
 
 int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_iter, const double * initial_poses,
   lfx_align_result * results, hipStream_t st, lfx_align_report * reports = nullptr)
@@ -337,30 +313,26 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   static_assert(sizeof(lfx::AlignState) % 8 == 0, "AlignState is an array of doubles' worth");
   if (n_clouds > 65535u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "at most 65535 scans per alignment call");}   // (a launch's y extent)
   const size_t state_d = sizeof(lfx::AlignState) / 8 * (size_t)n_clouds;
-  const size_t rows = pr.total3 + pr.total1;
+  const size_t total3 = pr.edge.total, total1 = pr.surface.total, rows = total3 + total1;
   const size_t partial_d = (size_t)n_clouds * lfx::kAlignSlices * lfx::kAlignTile;
   const size_t nbr_d = (size_t)lfx::kNearestMax / 2 * rows;                   // the searches' results: 16 words per row
   const size_t reach_d = rows;                                               // and how far each row's 16th neighbour was
   const bool report = reports != nullptr && pr.X == nullptr;
   const size_t sums_d = report ? sizeof(lfx::ReportSums) / 8 * (size_t)n_clouds : 0;
-  const size_t need = state_d + 24 * pr.total3 + 8 * pr.total1 + rows + partial_d + nbr_d + reach_d + (n_clouds + 1) / 2 + 9 + sums_d;
-  if (c->align_scratch.n < need) {
-    c->align_scratch.release();
-    if (c->align_scratch.alloc(need) != hipSuccess) {
-      c->align_scratch.n = 0;
-      return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the rows of the scan-to-map alignment");
-    }
+  const size_t need = state_d + 24 * total3 + 8 * total1 + rows + partial_d + nbr_d + reach_d + (n_clouds + 1) / 2 + 9 + sums_d;
+  if (hold(c->align_scratch, need, true) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the rows of the scan-to-map alignment");
   }
   double * w = c->align_scratch.p;
   lfx::AlignState * states = reinterpret_cast<lfx::AlignState *>(w); w += state_d;
-  double * r3 = w; w += 3 * pr.total3;
-  double * J3 = w; w += 21 * pr.total3;
-  double * r1 = w; w += pr.total1;
-  double * J1 = w; w += 7 * pr.total1;
+  double * r3 = w; w += 3 * total3;
+  double * J3 = w; w += 21 * total3;
+  double * r1 = w; w += total1;
+  double * J1 = w; w += 7 * total1;
   double * d_weights = w; w += rows;
   double * d_partials = w; w += partial_d;
-  uint32_t * nbr3 = reinterpret_cast<uint32_t *>(w), * nbr1 = nbr3 + (size_t)lfx::kNearestMax * pr.total3; w += nbr_d;
-  double * reach3 = w, * reach1 = w + pr.total3; w += reach_d;
+  uint32_t * nbr3 = reinterpret_cast<uint32_t *>(w), * nbr1 = nbr3 + (size_t)lfx::kNearestMax * total3; w += nbr_d;
+  double * reach3 = w, * reach1 = w + total3; w += reach_d;
   uint32_t * d_tickets = reinterpret_cast<uint32_t *>(w); w += (n_clouds + 1) / 2;
   uint32_t * d_active = reinterpret_cast<uint32_t *>(w); w += 9;
   lfx::ReportSums * d_sums = reinterpret_cast<lfx::ReportSums *>(w);
@@ -379,50 +351,43 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   lfx::AlignOut * d_out = reinterpret_cast<lfx::AlignOut *>(static_cast<uint8_t *>(d_pinned) + pose_bytes);
   hipLaunchKernelGGL(lfx::align_begin_kernel, dim3((n_clouds + 63u) / 64u), dim3(64), 0, st, states, d_initial, n_clouds, d_active,
     d_tickets, d_out);
+  // the rows of either kind, as every kernel from here on is handed them (the point pairs: no map, no points, no surface rows)
   const lfx::MapPose none{};
+  const lfx::MapIndex no_map{};
+  auto rows_of = [&](const lfx_map * m, const CloudSpan & k, double * r, double * J, uint32_t * nbr, double * reach) {
+      return lfx::RowsOfKind{m ? m->index : no_map, reinterpret_cast<const float4 *>(k.points), k.begin, k.count, k.count_stride, r, J,
+               k.row_begin, nbr, reach};
+    };
+  const lfx::RowsOfKind e = rows_of(pr.edge_map, pr.edge, r3, J3, nbr3, reach3), f = rows_of(pr.surface_map, pr.surface, r1, J1, nbr1, reach1);
+  const lfx::StepRows e_rows = lfx::step_rows(e), f_rows = lfx::step_rows(f);          // (the step kernels only address rows)
+  const uint32_t longest3 = pr.edge.longest, longest1 = pr.surface.longest;
   auto make_rows = [&](int iter) {                  // Problem::Make at the states' poses
       if (pr.X) {
-        if (pr.longest3) {
-          hipLaunchKernelGGL(lfx::pair_rows_kernel, dim3((pr.longest3 + 127u) / 128u, n_clouds), dim3(128), 0, st, pr.X, pr.Y,
-            pr.begin3, pr.count3, r3, J3, states);
+        if (longest3) {
+          hipLaunchKernelGGL(lfx::pair_rows_kernel, dim3((longest3 + 127u) / 128u, n_clouds), dim3(128), 0, st, pr.X, pr.Y,
+            e.begin, e.count, r3, J3, states);
+        }
+      } else if (e.mi.start && f.mi.start) {
+        // both maps have grids: the searches of both kinds in one launch, one wave per query; then the rows, one thread per query
+        if (longest3 + longest1) {
+          const uint32_t w3 = (longest3 + lfx::kSearchWaves - 1u) / lfx::kSearchWaves, w1 = (longest1 + lfx::kSearchWaves - 1u) / lfx::kSearchWaves;
+          hipLaunchKernelGGL(lfx::map_search_kernel, dim3(w3 + w1, n_clouds), dim3(64 * lfx::kSearchWaves), 0, st, e, f, w3,
+            pr.n_neighbors, states, iter);
+          const uint32_t g3 = (longest3 + lfx::kRowThreads - 1u) / lfx::kRowThreads, g1 = (longest1 + lfx::kRowThreads - 1u) / lfx::kRowThreads;
+          hipLaunchKernelGGL(lfx::rows_from_neighbours_kernel, dim3(g3 + g1, n_clouds), dim3(lfx::kRowThreads), 0, st, e, f, g3,
+            pr.n_neighbors, states);
         }
       } else {
-        const bool both_grids = pr.edge_map->index.start && pr.surface_map->index.start;
-        if (both_grids) {
-          // the searches of both kinds in one launch, one wave per query; then the rows, one thread per query
-          const lfx::RowsOfKind e{pr.edge_map->index, reinterpret_cast<const float4 *>(pr.edge_points), pr.begin3, pr.count3, pr.stride3, r3, J3,
-            pr.rbegin3, nbr3, reach3};
-          const lfx::RowsOfKind f{pr.surface_map->index, reinterpret_cast<const float4 *>(pr.surface_points), pr.begin1, pr.count1, pr.stride1,
-            r1, J1, pr.rbegin1, nbr1, reach1};
-          if (pr.longest3 + pr.longest1) {
-            const uint32_t w3 = (pr.longest3 + lfx::kSearchWaves - 1u) / lfx::kSearchWaves, w1 = (pr.longest1 + lfx::kSearchWaves - 1u) / lfx::kSearchWaves;
-            hipLaunchKernelGGL(lfx::map_search_kernel, dim3(w3 + w1, n_clouds), dim3(64 * lfx::kSearchWaves), 0, st, e, f, w3,
-              pr.n_neighbors, states, iter);
-            const uint32_t g3 = (pr.longest3 + lfx::kRowThreads - 1u) / lfx::kRowThreads, g1 = (pr.longest1 + lfx::kRowThreads - 1u) / lfx::kRowThreads;
-            hipLaunchKernelGGL(lfx::rows_from_neighbours_kernel, dim3(g3 + g1, n_clouds), dim3(lfx::kRowThreads), 0, st, e, f, g3,
-              pr.n_neighbors, states);
-          }
-        } else {
-          if (pr.longest3) {
-            launch_rows(false, pr.edge_map->index, none, pr.n_neighbors, pr.edge_points, pr.begin3, pr.count3, pr.stride3, n_clouds,
-              pr.longest3, r3, J3, states, st, pr.rbegin3);
-          }
-          if (pr.longest1) {
-            launch_rows(true, pr.surface_map->index, none, pr.n_neighbors, pr.surface_points, pr.begin1, pr.count1, pr.stride1, n_clouds,
-              pr.longest1, r1, J1, states, st, pr.rbegin1);
-          }
-        }
+        if (longest3) {launch_rows(false, e, none, pr.n_neighbors, n_clouds, longest3, states, st);}
+        if (longest1) {launch_rows(true, f, none, pr.n_neighbors, n_clouds, longest1, states, st);}
       }
     };
-  // (the step kernels only address rows)
-  const uint32_t * rb3 = pr.rbegin3 ? pr.rbegin3 : pr.begin3, * rb1 = pr.rbegin1 ? pr.rbegin1 : pr.begin1;
   auto iteration = [&](int iter) {
       make_rows(iter);
-      hipLaunchKernelGGL(lfx::align_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, iter, r3, rb3, pr.count3,
-        pr.stride3, r1, rb1, pr.count1, pr.stride1, d_weights, d_active, d_out);
+      hipLaunchKernelGGL(lfx::align_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, iter, e_rows, f_rows,
+        d_weights, d_active, d_out);
       hipLaunchKernelGGL(lfx::align_update_kernel, dim3(lfx::kAlignSlices, n_clouds), dim3(lfx::kAlignThreads), 0, st, states, iter,
-        max_iter, r3, J3, rb3, pr.count3, pr.stride3, r1, J1, rb1, pr.count1, pr.stride1, d_weights, d_partials, d_tickets,
-        d_active, d_out);
+        max_iter, e_rows, f_rows, d_weights, d_partials, d_tickets, d_active, d_out);
     };
   // As many iterations as the previous call needed are queued at once (a finished scan's kernels return at once, but a launch
   // is a launch); only then does the host look -- at the records in its own memory -- and, where a scan still iterates,
@@ -431,18 +396,11 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   for (;;) {
     for (; launched < target; launched++) {iteration(launched);}
     LFX_HIP(c, hipGetLastError());
-    // the wait: on the records themselves first (the thread that ends a scan sets `done` behind a system-scope fence; a
-    // blocking wait on the stream wakes 30-50 us late, a third of what a whole scan's alignment takes), then until the stream
-    // has drained what was queued behind them
     auto all_done = [&]() {
         for (uint32_t s = 0; s < n_clouds; s++) {if (out[s].done == 0) {return false;}}
         return true;
       };
-    hipError_t q = hipErrorNotReady;
-    for (uint32_t spins = 0; q == hipErrorNotReady; spins++) {
-      if (all_done() || (spins & 63u) == 63u) {q = hipStreamQuery(st);}
-      if (spins > (1u << 24)) {q = hipStreamSynchronize(st);}         // (seconds: something else holds the stream)
-    }
+    const hipError_t q = wait_for_records(all_done, st);
     LFX_HIP(c, q);
     if (all_done()) {break;}
     if (launched >= max_iter) {return fail(c, LFX_ERR_HIP, "the alignment did not finish within its iterations");}   // (cannot happen)
@@ -480,26 +438,19 @@ int run_align(lfx_ctx * c, const AlignProblem & pr, uint32_t n_clouds, int max_i
   hipLaunchKernelGGL(lfx::report_begin_kernel, dim3((n_clouds + 63u) / 64u), dim3(64), 0, st, states,
     reinterpret_cast<const lfx::ReportPose *>(d_rep), n_clouds, d_tickets);
   make_rows(1);                                       // (not the first search of these queries: it starts from the last one's reach)
-  hipLaunchKernelGGL(lfx::align_report_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, r3, rb3, pr.count3,
-    pr.stride3, r1, J1, rb1, pr.count1, pr.stride1, d_weights, d_sums);
-  hipLaunchKernelGGL(lfx::align_report_kernel, dim3(lfx::kAlignSlices, n_clouds), dim3(lfx::kAlignThreads), 0, st, states, r3, J3, rb3,
-    pr.count3, pr.stride3, r1, J1, rb1, pr.count1, pr.stride1, d_weights, d_sums, d_partials, d_tickets,
+  hipLaunchKernelGGL(lfx::align_report_scale_kernel, dim3(n_clouds), dim3(lfx::kScaleThreads), 0, st, states, e_rows, f_rows, d_weights, d_sums);
+  hipLaunchKernelGGL(lfx::align_report_kernel, dim3(lfx::kAlignSlices, n_clouds), dim3(lfx::kAlignThreads), 0, st, states, e_rows, f_rows,
+    d_weights, d_sums, d_partials, d_tickets,
     reinterpret_cast<lfx::AlignReport *>(d_rep + sizeof(lfx::ReportPose) * (size_t)n_clouds),
     reinterpret_cast<int32_t *>(d_rep + (sizeof(lfx::ReportPose) + sizeof(lfx::AlignReport)) * (size_t)n_clouds));
   LFX_HIP(c, hipGetLastError());
-  {
-    auto all_done = [&]() {
-        for (uint32_t s = 0; s < n_clouds; s++) {if (h_done[s] == 0) {return false;}}
-        return true;
-      };
-    hipError_t q = hipErrorNotReady;
-    for (uint32_t spins = 0; q == hipErrorNotReady; spins++) {      // (the wait on the records, as above)
-      if (all_done() || (spins & 63u) == 63u) {q = hipStreamQuery(st);}
-      if (spins > (1u << 24)) {q = hipStreamSynchronize(st);}
-    }
-    LFX_HIP(c, q);
-    if (!all_done()) {return fail(c, LFX_ERR_HIP, "the alignment's reports were not written");}   // (cannot happen)
-  }
+  auto all_reported = [&]() {
+      for (uint32_t s = 0; s < n_clouds; s++) {if (h_done[s] == 0) {return false;}}
+      return true;
+    };
+  const hipError_t q = wait_for_records(all_reported, st);
+  LFX_HIP(c, q);
+  if (!all_reported()) {return fail(c, LFX_ERR_HIP, "the alignment's reports were not written");}   // (cannot happen)
   for (uint32_t s = 0; s < n_clouds; s++) {
     if (h_pose[s].run && h_report[s].valid) {
       std::memcpy(&reports[s], const_cast<lfx::AlignReport *>(&h_report[s]), sizeof(lfx_align_report));
@@ -530,17 +481,13 @@ const char * lfx_align_message(int code)
 namespace lfx_host
 {
 int align_clouds(
-  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter,
-  const float * d_edge_points, const uint32_t * d_edge_begin, const uint32_t * d_edge_count, uint32_t edge_count_stride,
-  uint32_t max_edge_points_per_cloud, size_t total_edge_points,
-  const float * d_surface_points, const uint32_t * d_surface_begin, const uint32_t * d_surface_count,
-  uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
-  uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
-  const uint32_t * d_edge_row_begin, const uint32_t * d_surface_row_begin, lfx_align_report * reports)
+  lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
+  const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
+  lfx_align_report * reports)
 {
-  if (!c || !edge_map || !surface_map || !d_edge_points || !d_edge_begin || !d_edge_count || !d_surface_points ||
-    !d_surface_begin || !d_surface_count || !initial_poses || !results || n_clouds == 0 || edge_count_stride == 0 ||
-    surface_count_stride == 0)
+  if (!c || !edge_map || !surface_map || !edge.points || !edge.begin || !edge.count || !surface.points ||
+    !surface.begin || !surface.count || !initial_poses || !results || n_clouds == 0 || edge.count_stride == 0 ||
+    surface.count_stride == 0)
   {
     return LFX_ERR_INVALID_ARGUMENT;
   }
@@ -551,14 +498,9 @@ int align_clouds(
   if (edge_map->device != c->device || surface_map->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a map lives on another device");}
   LFX_HIP(c, hipSetDevice(c->device));
   AlignProblem pr;
-  pr.edge_map = edge_map; pr.edge_points = d_edge_points;
-  pr.begin3 = d_edge_begin; pr.count3 = d_edge_count; pr.stride3 = edge_count_stride; pr.longest3 = max_edge_points_per_cloud;
-  pr.total3 = total_edge_points;
-  pr.surface_map = surface_map; pr.surface_points = d_surface_points;
-  pr.begin1 = d_surface_begin; pr.count1 = d_surface_count; pr.stride1 = surface_count_stride;
-  pr.longest1 = max_surface_points_per_cloud; pr.total1 = total_surface_points;
+  pr.edge_map = edge_map; pr.surface_map = surface_map;
+  pr.edge = edge; pr.surface = surface;
   pr.n_neighbors = n_neighbors;
-  pr.rbegin3 = d_edge_row_begin; pr.rbegin1 = d_surface_row_begin;
   return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream), reports);
 }
 }  // namespace lfx_host
@@ -573,9 +515,10 @@ int lfx_scan_to_map_align(
   uint32_t surface_count_stride, uint32_t max_surface_points_per_cloud, size_t total_surface_points,
   uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream)
 {
-  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge_points, d_edge_begin, d_edge_count, edge_count_stride,
-           max_edge_points_per_cloud, total_edge_points, d_surface_points, d_surface_begin, d_surface_count, surface_count_stride,
-           max_surface_points_per_cloud, total_surface_points, n_clouds, initial_poses, results, stream, nullptr, nullptr, nullptr);
+  const CloudSpan edge{d_edge_points, d_edge_begin, d_edge_count, edge_count_stride, max_edge_points_per_cloud, total_edge_points};
+  const CloudSpan surface{d_surface_points, d_surface_begin, d_surface_count, surface_count_stride, max_surface_points_per_cloud,
+    total_surface_points};
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, n_clouds, initial_poses, results, stream);
 }
 
 int lfx_scan_to_map_align_report(
@@ -587,9 +530,10 @@ int lfx_scan_to_map_align_report(
   uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, lfx_align_report * reports, void * stream)
 {
   if (!reports) {return LFX_ERR_INVALID_ARGUMENT;}
-  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge_points, d_edge_begin, d_edge_count, edge_count_stride,
-           max_edge_points_per_cloud, total_edge_points, d_surface_points, d_surface_begin, d_surface_count, surface_count_stride,
-           max_surface_points_per_cloud, total_surface_points, n_clouds, initial_poses, results, stream, nullptr, nullptr, reports);
+  const CloudSpan edge{d_edge_points, d_edge_begin, d_edge_count, edge_count_stride, max_edge_points_per_cloud, total_edge_points};
+  const CloudSpan surface{d_surface_points, d_surface_begin, d_surface_count, surface_count_stride, max_surface_points_per_cloud,
+    total_surface_points};
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, n_clouds, initial_poses, results, stream, reports);
 }
 
 int lfx_align_point_pairs(
@@ -601,8 +545,8 @@ int lfx_align_point_pairs(
   if (max_iter < 1) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be >= 1");}
   LFX_HIP(c, hipSetDevice(c->device));
   AlignProblem pr;
-  pr.X = d_source; pr.Y = d_target; pr.begin3 = d_begin; pr.count3 = d_count; pr.stride3 = 1; pr.longest3 = max_points_per_cloud;
-  pr.total3 = total_points;
+  pr.X = d_source; pr.Y = d_target;
+  pr.edge = CloudSpan{nullptr, d_begin, d_count, 1, max_points_per_cloud, total_points};
   return run_align(c, pr, n_clouds, max_iter, initial_poses, results, static_cast<hipStream_t>(stream));
 }
 
@@ -616,22 +560,14 @@ int localize_batch(
   uint32_t n_scans, const double * initial_poses, lfx_align_result * results, lfx_align_report * reports, void * stream)
 {
   if (!c || !initial_poses || !results) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  // the caller's arrays are sized by ITS count: one pose after a batch of 16 would be read and written 15 entries too far
-  if (n_scans != c->last_batch) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
-             std::to_string(c->last_batch) + ")");
-  }
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
   LFX_HIP(c, hipSetDevice(c->device));
   const uint32_t batch = c->last_batch;
   const size_t total = c->h_scan_begin[batch];
-  const size_t need = 4 * total + 4 * (size_t)batch;        // the clouds, then counts, status and the two tables of row starts
-  if (c->align_surface.n < need) {
-    c->align_surface.release();
-    if (c->align_surface.alloc(need) != hipSuccess) {
-      c->align_surface.n = 0;
-      return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");
-    }
+  // the clouds, then counts, status and the two tables of row starts
+  if (hold(c->align_surface, 4 * total + 4 * (size_t)batch, true) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");
   }
   float * down = c->align_surface.p;
   uint32_t * down_count = reinterpret_cast<uint32_t *>(down + 4 * total), * down_status = down_count + batch;
@@ -655,12 +591,13 @@ int localize_batch(
       for (uint32_t s = 0; s < batch; s++) {e = std::max(e, (uint32_t)lengths[2 * s]); f = std::max(f, (uint32_t)lengths[2 * s + 1]);}
       c->loc_guess[0] = e; c->loc_guess[1] = f;
     };
+  CloudSpan edge{reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4};
+  CloudSpan surface{down, c->scan_begin.p, down_count, 1};
   if (by_bound) {
-    const uint32_t guess3 = c->loc_guess[0] ? c->loc_guess[0] + c->loc_guess[0] / 8u : 4096u;
-    const uint32_t guess1 = c->loc_guess[1] ? c->loc_guess[1] + c->loc_guess[1] / 8u : 2048u;
-    const int ra = align_clouds(c, edge_map, surface_map, n_neighbors, max_iter,
-      reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4, guess3, total,
-      down, c->scan_begin.p, down_count, 1, guess1, total, batch, initial_poses, results, stream, nullptr, nullptr, reports);
+    edge.longest = c->loc_guess[0] ? c->loc_guess[0] + c->loc_guess[0] / 8u : 4096u;
+    surface.longest = c->loc_guess[1] ? c->loc_guess[1] + c->loc_guess[1] / 8u : 2048u;
+    edge.total = surface.total = total;
+    const int ra = align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, batch, initial_poses, results, stream, reports);
     if (ra == LFX_OK) {remember();}
     return ra;
   }
@@ -670,20 +607,16 @@ int localize_batch(
   LFX_HIP(c, hipStreamSynchronize(st));
   LFX_HIP(c, c->h_align.reserve(8 * (size_t)batch));
   uint32_t * rows = reinterpret_cast<uint32_t *>(c->h_align.p);
-  uint32_t longest_edge = 0, longest_surface = 0;
-  size_t rows3 = 0, rows1 = 0;
   for (uint32_t s = 0; s < batch; s++) {
-    rows[s] = (uint32_t)rows3; rows[batch + s] = (uint32_t)rows1;
-    rows3 += lengths[2 * s]; rows1 += lengths[2 * s + 1];
-    longest_edge = std::max(longest_edge, (uint32_t)lengths[2 * s]);
-    longest_surface = std::max(longest_surface, (uint32_t)lengths[2 * s + 1]);
+    rows[s] = (uint32_t)edge.total; rows[batch + s] = (uint32_t)surface.total;
+    edge.total += lengths[2 * s]; surface.total += lengths[2 * s + 1];
   }
-  c->loc_guess[0] = longest_edge; c->loc_guess[1] = longest_surface;
+  remember();
+  edge.longest = c->loc_guess[0]; surface.longest = c->loc_guess[1];
+  edge.row_begin = d_row3; surface.row_begin = d_row1;
   LFX_HIP(c, hipMemcpyAsync(d_row3, rows, sizeof(uint32_t) * 2 * batch, hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipStreamSynchronize(st));              // (run_align lays its own records over the pinned block)
-  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter,
-           reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4, longest_edge, rows3,
-           down, c->scan_begin.p, down_count, 1, longest_surface, rows1, batch, initial_poses, results, stream, d_row3, d_row1, reports);
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, batch, initial_poses, results, stream, reports);
 }
 
 int localize_host(
@@ -698,13 +631,8 @@ int localize_host(
   hipStream_t st = static_cast<hipStream_t>(stream);
   // [edge | surface | downsampled surface] records of 4 floats, then begin / count words
   const size_t ne = n_edge, ns = n_surface, words = 8;
-  const size_t need = 4 * (ne + 2 * ns + 2) + words;
-  if (c->align_surface.n < need) {
-    c->align_surface.release();
-    if (c->align_surface.alloc(need) != hipSuccess) {
-      c->align_surface.n = 0;
-      return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the scan's clouds");
-    }
+  if (hold(c->align_surface, 4 * (ne + 2 * ns + 2) + words, true) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the scan's clouds");
   }
   float * d_edge = c->align_surface.p, * d_surface = d_edge + 4 * (ne + 1), * d_down = d_surface + 4 * (ns + 1);
   uint32_t * d_words = reinterpret_cast<uint32_t *>(d_down + 4 * ns);
@@ -717,18 +645,18 @@ int localize_host(
   uint32_t n_down = 0;
   if (n_surface) {
     LFX_HIP(c, hipMemcpyAsync(d_surface, surface_points, sizeof(float) * 4 * ns, hipMemcpyHostToDevice, st));
-    const int rc = lfx_voxel_downsample(c, d_surface, d_words, d_words + 2, 1, 1, ns, surface_leaf, d_down, d_words + 3, d_words + 4, stream);
+    // (where PCL gives the cloud back unfiltered the launch copies it, as for lfx_localize_batch)
+    const int rc = voxel_downsample(c, d_surface, d_words, d_words + 2, 1, 1, ns, surface_leaf, d_down, d_words + 3, d_words + 4, stream,
+      true, d_words + 1, nullptr);
     if (rc != LFX_OK) {return rc;}
-    hipLaunchKernelGGL(lfx::downsample_passthrough_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const float4 *>(d_surface),
-      d_words, d_words + 2, 1u, reinterpret_cast<float4 *>(d_down), d_words + 3, d_words + 4, d_words + 1, static_cast<uint32_t *>(nullptr));
     LFX_HIP(c, hipMemcpyAsync(h_words + 3, d_words + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     LFX_HIP(c, hipStreamSynchronize(st));
     n_down = h_words[3];
   } else {
     LFX_HIP(c, hipStreamSynchronize(st));             // the words have left the pinned block: the alignment stages through it too
   }
-  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, d_edge, d_words, d_words + 1, 1, n_edge, ne,
-           d_down, d_words, d_words + 3, 1, n_down, ns, 1, initial_pose, result, stream, nullptr, nullptr, report);
+  const CloudSpan edge{d_edge, d_words, d_words + 1, 1, n_edge, ne}, surface{d_down, d_words, d_words + 3, 1, n_down, ns};
+  return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, 1, initial_pose, result, stream, report);
 }
 }  // namespace
 

@@ -52,14 +52,6 @@ namespace
 {
 constexpr size_t kPinBounds = 0, kPinWords = 12, kPinInfo = 20;
 
-double decode(uint32_t u)                     // odo_float_order back to the float it encodes
-{
-  const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-  float f;
-  std::memcpy(&f, &b, 4);
-  return (double)f;
-}
-
 uint32_t * pinned_words(lfx_odometry * o) {return reinterpret_cast<uint32_t *>(o->pinned.p);}
 
 // What lets a scan of (ne, ns) points in: 0 as it is, 1 after the scans older than the window are discarded, -1 not at all
@@ -117,7 +109,7 @@ int settle(lfx_ctx * c, lfx_odometry * o)
   for (int k = 0; k < 2; k++) {
     const uint32_t * v = h + 6 * k;
     b[k].any = v[3] != 0u;
-    for (int a = 0; a < 3 && b[k].any; a++) {b[k].lo[a] = decode(~v[a]); b[k].hi[a] = decode(v[3 + a]);}
+    for (int a = 0; a < 3 && b[k].any; a++) {b[k].lo[a] = lfx::float_of_order(~v[a]); b[k].hi[a] = lfx::float_of_order(v[3 + a]);}
   }
   return LFX_OK;
 }
@@ -181,13 +173,14 @@ struct ScanIn                                // one scan as the append kernel an
 {
   const float4 * edge = nullptr, * surface = nullptr;    // the raw clouds
   uint32_t n_edge = 0, n_surface = 0;
-  const float * edge_points = nullptr;                   // the edge cloud as align_clouds addresses it
-  const uint32_t * edge_begin = nullptr, * edge_count = nullptr;
-  uint32_t edge_stride = 1;
-  const float * down_points = nullptr;                   // the downsampled surface cloud
-  const uint32_t * down_begin = nullptr, * down_count = nullptr;
-  uint32_t n_down = 0;
+  CloudSpan edge_cloud, down_cloud;                      // the edge cloud and the downsampled surface cloud as align_clouds addresses them
 };
+
+// one cloud of n points (or a bound on them) whose rows start at row 0 (the odometry's words hold a 0 first)
+CloudSpan single_cloud(const lfx_odometry * o, const float * points, const uint32_t * begin, const uint32_t * count, uint32_t stride, uint32_t n)
+{
+  return CloudSpan{points, begin, count, stride, n, n, o->words.p};
+}
 
 void not_aligned(const double pose[12], lfx_odometry_result * r)
 {
@@ -216,9 +209,7 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
       int rc = rebuild(c, o, 0, w, st);
       if (rc == LFX_OK) {rc = rebuild(c, o, 1, w, st);}
       if (rc == LFX_OK) {
-        rc = align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_points, in.edge_begin, in.edge_count, in.edge_stride,
-          in.n_edge, in.n_edge, in.down_points, in.down_begin, in.down_count, 1, in.n_down, in.n_down, 1, o->pose, &r.align, st,
-          o->words.p, o->words.p, report);
+        rc = align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_cloud, in.down_cloud, 1, o->pose, &r.align, st, report);
       }
       if (rc != LFX_OK) {return rc;}
       std::memcpy(pose, r.align.pose, sizeof(pose));    // pose_ = update(scan, pose_), whatever the code
@@ -319,11 +310,8 @@ void lfx_odometry_destroy(lfx_odometry * o)
 int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, lfx_odometry_result * results, void * stream)
 {
   if (!c || !o || !results) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  if (n_scans != c->last_batch) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
-             std::to_string(c->last_batch) + ")");
-  }
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
   const int rs = settle(c, o);
@@ -352,9 +340,9 @@ int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, l
     const uint32_t b = c->h_scan_begin[s];
     in.edge = c->edge_pts.p + b; in.n_edge = info[4 * s + lfx::kInfoEdge];
     in.surface = c->surf_pts.p + b; in.n_surface = info[4 * s + lfx::kInfoSurface];
-    in.edge_points = reinterpret_cast<const float *>(c->edge_pts.p);
-    in.edge_begin = c->scan_begin.p + s; in.edge_count = c->scan_info.p + lfx::kInfoEdge + 4 * s; in.edge_stride = 4;
-    in.down_points = down; in.down_begin = c->scan_begin.p + s; in.down_count = down_count + s; in.n_down = lengths[2 * s + 1];
+    in.edge_cloud = single_cloud(o, reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p + s,
+      c->scan_info.p + lfx::kInfoEdge + 4 * s, 4, in.n_edge);
+    in.down_cloud = single_cloud(o, down, c->scan_begin.p + s, down_count + s, 1, lengths[2 * s + 1]);
     const int rc2 = step(c, o, in, results + s, st, o->reports_on ? &o->reports[s] : nullptr);
     if (rc2 != LFX_OK) {return rc2;}
   }
@@ -386,8 +374,8 @@ int lfx_odometry_update(lfx_ctx * c, lfx_odometry * o, const float * d_edge, uin
   const float * any = o->down.p;                // (align_clouds wants a pointer for an empty cloud too)
   in.edge = reinterpret_cast<const float4 *>(d_edge); in.n_edge = n_edge;
   in.surface = reinterpret_cast<const float4 *>(d_surface); in.n_surface = n_surface;
-  in.edge_points = d_edge ? d_edge : any; in.edge_begin = o->words.p; in.edge_count = o->words.p + 1; in.edge_stride = 1;
-  in.down_points = o->down.p; in.down_begin = o->words.p; in.down_count = o->words.p + 3; in.n_down = n_surface;
+  in.edge_cloud = single_cloud(o, d_edge ? d_edge : any, o->words.p, o->words.p + 1, 1, n_edge);
+  in.down_cloud = single_cloud(o, o->down.p, o->words.p, o->words.p + 3, 1, n_surface);
   o->reports.assign(o->reports_on ? 1u : 0u, lfx_align_report{});
   return step(c, o, in, result, st, o->reports_on ? &o->reports[0] : nullptr);
 }
@@ -396,11 +384,8 @@ int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_
   double sweep_ratio, int to, uint32_t n_scans, lfx_odometry_result * results, void * stream)
 {
   if (!c || !o || !results || !time) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  if (n_scans != c->last_batch) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
-             std::to_string(c->last_batch) + ")");
-  }
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
   if (!std::isfinite(sweep_ratio)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_ratio must be finite");}

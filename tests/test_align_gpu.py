@@ -266,7 +266,8 @@ def test_localize_calls_in_a_row_and_both_ways_of_sizing_the_rows():
 
 def test_localize_batch_with_a_leaf_too_small_for_the_cloud():
     """PCL's VoxelGrid hands a cloud back unfiltered when the leaf is too small for its extent (downsample.hpp:37-51): the rows
-    are then built from every surface point.  lfx_localize_batch does that copy inside its Downsample launch."""
+    are then built from every surface point.  lfx_localize_batch does that copy inside its Downsample launch, and so does
+    lfx_localize_host with the same clouds handed over from the host."""
     import torch
     from lidar_feature_extraction_amd import FeatureExtraction, concat
     rng = np.random.default_rng(5)
@@ -288,6 +289,8 @@ def test_localize_batch_with_a_leaf_too_small_for_the_cloud():
     assert len(down) == len(want[0]["surface_points"])                  # unfiltered
     w = _oracle_scan(edge_map, surf_map, k, want[0]["edge_points"], down, pose, max_iter)
     _same_result(got, w, "unfiltered", pose_tol=1e-6, rel=1e-5)
+    host = fx.localize_host(emap, smap, want[0]["edge_points"], want[0]["surface_points"], pose, k, max_iter, leaf, stream)
+    _same_result(host, w, "unfiltered, from the host", pose_tol=1e-6, rel=1e-5)
     fx.close()
 
 
