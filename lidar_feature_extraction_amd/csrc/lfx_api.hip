@@ -23,7 +23,7 @@ namespace
 
 std::string g_create_error;
 
-const char * kKernelNames[LFX_N_KERNELS] = {
+const char * kKernelNames[LFX_N_KERNELS] = {           // (in the order of KernelSlot, lfx_internal.hpp)
   "ring_scatter_kernel", "ring_unit_kernel", "ring_order_kernel", "ring_unit_kernel(second pass)", "ring_extract_kernel",
   "ring_totals_kernel", "feature_compact_kernel", "ring_unit_org_kernel", "ring_cut_kernel", "fallback_tail_kernel", "grid_count_kernel",
   "batch_reset_kernel", "ring_long_kernel"};
@@ -80,7 +80,7 @@ hipEvent_t take_event(lfx_ctx * c)
 
 struct Timed
 {
-  Timed(lfx_ctx * c, int k, hipStream_t s)
+  Timed(lfx_ctx * c, KernelSlot k, hipStream_t s)
   : c_(c), k_(k), s_(s)
   {
     if (c_->profile_now) {
@@ -152,6 +152,9 @@ lfx::Params device_params(const lfx_params & p)
   d.max_range = p.max_range;
   return d;
 }
+
+// an LFX_DEBUG_* switch that pins a choice to 0 or 1; -1 where it is not set (RoutePins)
+int debug_pin(const char * value) {return value ? (std::atoi(value) != 0 ? 1 : 0) : -1;}
 
 uint32_t ring_threads_for(uint32_t cap)
 {
@@ -263,7 +266,6 @@ int install_ring_ids(lfx_ctx * c, const uint16_t * ids, uint32_t n, bool given)
     return LFX_OK;
   }
   if (!c->ring_slot.p && c->ring_slot.alloc(65536) != hipSuccess) {
-    c->ring_slot.p = nullptr;
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the ring id table");
   }
   std::vector<uint16_t> table(65536, (uint16_t)0xFFFFu);
@@ -272,6 +274,21 @@ int install_ring_ids(lfx_ctx * c, const uint16_t * ids, uint32_t n, bool given)
   c->slot_id = v;
   c->fused_possible = false;               // (the organised-scan kernel reads ring r at column offset r)
   return LFX_OK;
+}
+
+// PointXYZIR records (point_type.hpp:62-86): the layout the organised-scan kernel and the CANON forms of the others read
+bool canonical_layout(const lfx::Layout & L)
+{
+  return L.step == 32 && L.ox == 0 && L.oy == 4 && L.oz == 8 && L.oring == 20 && L.rtype == LFX_FIELD_UINT16 && L.be == 0;
+}
+
+// One of the two sets of accumulators a batch adds into (lfx_ctx::parity; lfx_kernels_common.hpp kParityCounters)
+struct AccSet { uint32_t * counters, * scan_flags, * ring_nedge, * ring_nsurf; };
+AccSet acc_set(const lfx_ctx * c, uint32_t par)
+{
+  const size_t tables = (size_t)c->max_batch * lfx::kRings;
+  return {c->counters.p + par * lfx::kParityCounters, c->scan_flags.p + (size_t)par * c->max_batch, c->ring_nedge.p + par * tables,
+    c->ring_nsurf.p + par * tables};
 }
 
 // Launch the kernels for `batch` scans whose records lie back to back at d_points.
@@ -319,18 +336,14 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   // this batch's set of accumulators (lfx_kernels_common.hpp kParityCounters); the other one is zeroed by this batch's
   // compaction for the batch after it
   const uint32_t par = c->parity;
-  const size_t tables = (size_t)c->max_batch * lfx::kRings;
-  uint32_t * counters = c->counters.p + par * lfx::kParityCounters;
-  uint32_t * scan_flags = c->scan_flags.p + (size_t)par * c->max_batch;
-  uint32_t * ring_nedge = c->ring_nedge.p + par * tables, * ring_nsurf = c->ring_nsurf.p + par * tables;
+  const AccSet acc = acc_set(c, par), other = acc_set(c, par ^ 1u);
+  uint32_t * const counters = acc.counters;
   const lfx::UnitTables * unit_tab = c->unit_tab.p + par;
   uint32_t * defer_count = counters + lfx::kCntDefer, * redo_count = counters + lfx::kCntRedo,
     * slow_count = counters + lfx::kCntSlow, * fb_count = counters + lfx::kCntFallback;
   const uint8_t * pts = static_cast<const uint8_t *>(d_points);
   const uint32_t chunks = (longest + lfx::kChunkPoints - 1) / lfx::kChunkPoints;
-  const bool canon = c->layout.step == 32 && c->layout.ox == 0 && c->layout.oy == 4 && c->layout.oz == 8 &&
-    c->layout.oring == 20 && c->layout.rtype == LFX_FIELD_UINT16 && c->layout.be == 0 &&
-    (reinterpret_cast<uintptr_t>(pts) & 15u) == 0;
+  const bool canon = canonical_layout(c->layout) && (reinterpret_cast<uintptr_t>(pts) & 15u) == 0;
   if (c->long_slices != 0u) {
     // the long list starts empty (the LDS-resident kernels fill it, ring_long_kernel reads it)
     LFX_HIP(c, hipMemsetAsync(c->long_count.p, 0, 4, st));
@@ -369,7 +382,7 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   const bool lazy = fused && short_tail && !choice.xform;
   if (!lazy || c->aux_dirty != 0u) {
     const uint32_t n_aux = c->aux_dirty > batch ? c->aux_dirty : batch;
-    Timed t(c, 11, st);
+    Timed t(c, kSlotReset, st);
     hipLaunchKernelGGL(lfx::batch_reset_kernel, dim3(64), dim3(256), 0, st,
       c->chunk_flags.p, n_aux * c->max_chunks, c->ring_flags.p, n_aux * (uint32_t)lfx::kRings, counters, c->fb_list.p, batch,
       fused ? 0u : 1u, c->xform.p);
@@ -379,30 +392,31 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
   if (fused) {
     const bool xf = choice.xform;
     if (xf) {
-      Timed t(c, 8, st);
+      Timed t(c, kSlotCut, st);
       hipLaunchKernelGGL(lfx::ring_cut_kernel, dim3(batch), dim3(lfx::kCutThreads), 0, st,
         pts, c->scan_begin.p, c->max_rings, c->cap, c->xform.p, counters);
     }
     const uint32_t groups = (c->max_rings + 3u) / 4u;
     if (holes) {
       // the count pass of the holes form: valid returns per ring and piece of 16 columns, every ring's length
-      Timed t(c, 10, st);
+      Timed t(c, kSlotGridCount, st);
       // (a workgroup per scan, reading its records as they lie, where the batch fills the device with those; else a
       // workgroup per ring group and scan)
       const uint32_t row_words = c->cap / lfx::kPieceCols + 1u;
       const size_t count_lds = ((size_t)c->max_rings * row_words + 2u * groups * (size_t)c->dev.B) * 4u;
+      auto count_pass = [&](auto kernel, dim3 grid, uint32_t threads, size_t lds, auto... more) {
+          hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st,
+            pts, c->scan_begin.p, c->scan_geom.p, c->max_rings, lfx::cum_stride(c->cap), c->cum16.p, c->ring_count.p, unit_tab, counters,
+            c->hole_desc.p, c->cap, 64u * c->unit_chunks, 4u * (uint32_t)lfx::holes_loads((int)c->unit_chunks), more...);
+        };
       if (batch >= c->scan_count_from && count_lds <= 144u * 1024u) {
-        hipLaunchKernelGGL(lfx::scan_count_kernel, dim3(batch), dim3(lfx::kScanCountThreads), count_lds, st,
-          pts, c->scan_begin.p, c->scan_geom.p, c->max_rings, lfx::cum_stride(c->cap), c->cum16.p, c->ring_count.p, unit_tab, counters,
-          c->hole_desc.p, c->cap, 64u * c->unit_chunks, 4u * (uint32_t)lfx::holes_loads((int)c->unit_chunks), row_words);
+        count_pass(lfx::scan_count_kernel, dim3(batch), lfx::kScanCountThreads, count_lds, row_words);
       } else {
-      hipLaunchKernelGGL(lfx::grid_count_kernel, dim3(groups, batch), dim3(256), 0, st,
-        pts, c->scan_begin.p, c->scan_geom.p, c->max_rings, lfx::cum_stride(c->cap), c->cum16.p, c->ring_count.p, unit_tab, counters,
-        c->hole_desc.p, c->cap, 64u * c->unit_chunks, 4u * (uint32_t)lfx::holes_loads((int)c->unit_chunks));
+        count_pass(lfx::grid_count_kernel, dim3(groups, batch), 256u, 0);
       }
     }
     {
-      Timed t(c, 7, st);
+      Timed t(c, kSlotUnitOrg, st);
       const UnitOrgArgs a{c->dev, c->cap, c->unit_flags, c->max_rings, c->drop_zero, pts, c->scan_begin.p, c->ring_count.p, unit_tab,
         c->xform.p, c->scan_geom.p};
       launch_unit_org(c->unit_variant, (int)c->unit_chunks, xf, holes, dim3(groups, (uint32_t)c->dev.B, batch), c->unit_lds_pad, st, a);
@@ -412,11 +426,11 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
     c->sidx.p, c->label_s.p, (c->outputs & LFX_OUT_CURVATURE) ? c->curv_s.p : nullptr, c->rec_pts.p, c->rec_idx.p, c->ring_status.p,
     c->unit_ne.p, c->unit_ns.p, c->unit_span.p, c->ring_flags.p, c->long_count.p, c->long_list.p,
     (uint32_t)(c->long_list.n / 2u)};
+  const lfx::ScatterArgs sc{pts, c->layout, c->scan_begin.p, c->chunk_base.p, c->chunk_flags.p, c->ring_count.p, c->scan_info.p, acc.scan_flags,
+    c->sxy.p, c->sz.p, c->sidx.p, c->max_chunks, c->max_rings, c->cap, c->drop_zero};
   if (lazy) {
     // ---- the organised route's tail in one launch: the fall-back list is empty as a rule
-    Timed t(c, 9, st);
-    const lfx::ScatterArgs sc{pts, c->layout, c->scan_begin.p, c->chunk_base.p, c->chunk_flags.p, c->ring_count.p, c->scan_info.p, scan_flags,
-      c->sxy.p, c->sz.p, c->sidx.p, c->max_chunks, c->max_rings, c->cap, c->drop_zero};
+    Timed t(c, kSlotTail, st);
     const uint32_t turns = (batch + lfx::kTailMaxTurns - 1u) / lfx::kTailMaxTurns;
     // (two rows of workgroups, not the eight the list routes guess: this route is only taken while nothing has been falling
     // back, the rows walk a list that turns out longer, and 1 024 workgroups of 80 KB of LDS that read one word and leave
@@ -429,67 +443,64 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
       hipLaunchKernelGGL(lfx::fallback_tail_kernel<false>, grid, dim3(lfx::kChunkThreads), c->ring_lds, st, sc, ex, fb_count, c->fb_list.p, c->tail_ticket.p);
     }
   } else {
-  // ---- the bucketing route, over the scans on the fall-back list
-  {
-    Timed t(c, 0, st);
-    auto kern = &lfx::ring_scatter_kernel<false>;
-    if (canon) {kern = &lfx::ring_scatter_kernel<true>;}
-    if (fb_grid == batch) {                            // a row per scan: the form without the loop over list entries
-      kern = canon ? &lfx::ring_scatter_kernel<true, true> : &lfx::ring_scatter_kernel<false, true>;
-    }
-    hipLaunchKernelGGL(kern, dim3(chunks, fb_grid), dim3(lfx::kChunkThreads), 0, st,
-      pts, c->layout, c->scan_begin.p, c->chunk_base.p, c->chunk_flags.p, c->ring_count.p, c->scan_info.p, scan_flags,
-      c->sxy.p, c->sz.p, c->sidx.p, c->max_chunks, c->max_rings, c->cap, c->drop_zero, fb_count, c->fb_list.p,
-      c->slot_id.empty() ? nullptr : c->ring_slot.p);
-  }
-  // the near-empty launches of the bucketing route are kept small while the organised-scan kernel takes the stream
-  const uint32_t list_grid = fused ? (c->slow_grid < 4u * fb_grid ? c->slow_grid : 4u * fb_grid) : c->slow_grid;
-  if (c->fast_path && !short_tail) {
-    c->pre_order = choice.pre_order;
-    if (c->pre_order) {
-      Timed t(c, 2, st);
-      hipLaunchKernelGGL(lfx::ring_order_kernel, dim3(fused ? list_grid : 4 * c->slow_grid), dim3(512), c->order_lds, st,
-        c->cap, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, c->ring_flags.p, defer_count,
-        c->defer_list.p, redo_count, c->redo_list.p, slow_count, c->slow_list.p, 1u, counters + lfx::kCntPreFixed, 0u,
-        fb_count, c->fb_list.p, 0u);
-    }
+    // ---- the bucketing route, over the scans on the fall-back list
     {
-      Timed t(c, 1, st);
-      const uint32_t units = c->max_rings * (uint32_t)c->dev.B;
-      // the looping form only where the list's length is a guess (behind the organised-scan kernel)
-      const UnitArgs a{c->dev, c->cap, c->unit_flags, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, unit_tab,
-        defer_count, c->defer_list.p, fb_count, c->fb_list.p, 0u};
-      launch_unit(c->unit_variant, false, (int)c->unit_chunks, fused, dim3((units + lfx::kUnitWaves - 1) / lfx::kUnitWaves, fb_grid),
-        c->unit_lds_pad, st, a);
+      Timed t(c, kSlotScatter, st);
+      auto kern = &lfx::ring_scatter_kernel<false>;
+      if (canon) {kern = &lfx::ring_scatter_kernel<true>;}
+      if (fb_grid == batch) {                            // a row per scan: the form without the loop over list entries
+        kern = canon ? &lfx::ring_scatter_kernel<true, true> : &lfx::ring_scatter_kernel<false, true>;
+      }
+      hipLaunchKernelGGL(kern, dim3(chunks, fb_grid), dim3(lfx::kChunkThreads), 0, st,
+        sc.pts, sc.L, sc.scan_begin, sc.chunk_base, sc.chunk_flags, sc.ring_count, sc.scan_info, sc.scan_flags,
+        sc.sxy, sc.sz, sc.sidx, sc.max_chunks, sc.max_rings, sc.cap, sc.drop_zero, fb_count, c->fb_list.p,
+        c->slot_id.empty() ? nullptr : c->ring_slot.p);
     }
-    const uint32_t redo_cap = choice.redo_cap;
-    {
+    // the near-empty launches of the bucketing route are kept small while the organised-scan kernel takes the stream
+    const uint32_t list_grid = fused ? (c->slow_grid < 4u * fb_grid ? c->slow_grid : 4u * fb_grid) : c->slow_grid;
+    if (c->fast_path && !short_tail) {
+      // (all_rings 1: BEFORE the unit kernel, over every ring of the scans on the fall-back list; 0: over the rings the first
+      // unit pass deferred, list_cover the list entries that pass was launched for)
+      auto order_pass = [&](uint32_t grid, uint32_t all_rings, uint32_t redo_cap, uint32_t list_cover) {
+          Timed t(c, kSlotOrder, st);
+          hipLaunchKernelGGL(lfx::ring_order_kernel, dim3(grid), dim3(512), c->order_lds, st,
+            c->cap, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, c->ring_flags.p, defer_count,
+            c->defer_list.p, redo_count, c->redo_list.p, slow_count, c->slow_list.p, all_rings, counters + lfx::kCntPreFixed, redo_cap,
+            fb_count, c->fb_list.p, list_cover);
+        };
+      c->pre_order = choice.pre_order;
+      if (c->pre_order) {order_pass(fused ? list_grid : 4 * c->slow_grid, 1u, 0u, 0u);}
+      {
+        Timed t(c, kSlotUnit, st);
+        const uint32_t units = c->max_rings * (uint32_t)c->dev.B;
+        // the looping form only where the list's length is a guess (behind the organised-scan kernel)
+        const UnitArgs a{c->dev, c->cap, c->unit_flags, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, unit_tab,
+          defer_count, c->defer_list.p, fb_count, c->fb_list.p, 0u};
+        launch_unit(c->unit_variant, false, (int)c->unit_chunks, fused, dim3((units + lfx::kUnitWaves - 1) / lfx::kUnitWaves, fb_grid),
+          c->unit_lds_pad, st, a);
+      }
+      const uint32_t redo_cap = choice.redo_cap;
       // rings out of angle order: repaired in place, then a second pass of the unit kernel over them
-      Timed t(c, 2, st);
-      hipLaunchKernelGGL(lfx::ring_order_kernel, dim3(list_grid), dim3(512), c->order_lds, st,
-        c->cap, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, c->ring_flags.p, defer_count,
-        c->defer_list.p, redo_count, c->redo_list.p, slow_count, c->slow_list.p, 0u, counters + lfx::kCntPreFixed, redo_cap,
-        fb_count, c->fb_list.p, 0xFFFFFFFFu /* the first unit pass covers the whole list (it loops where it has to) */);
+      order_pass(list_grid, 0u, redo_cap, 0xFFFFFFFFu /* the first unit pass covers the whole list (it loops where it has to) */);
+      {
+        Timed t(c, kSlotUnitSecond, st);
+        const uint32_t units = redo_cap * (uint32_t)c->dev.B;
+        const UnitArgs a{c->dev, c->cap, c->unit_flags, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, unit_tab,
+          slow_count, c->slow_list.p, redo_count, c->redo_list.p, redo_cap};
+        launch_unit(c->unit_variant, true, (int)c->unit_chunks, false, dim3((units + lfx::kUnitWaves - 1) / lfx::kUnitWaves), c->unit_lds_pad, st, a);
+      }
     }
     {
-      Timed t(c, 3, st);
-      const uint32_t units = redo_cap * (uint32_t)c->dev.B;
-      const UnitArgs a{c->dev, c->cap, c->unit_flags, c->max_rings, c->ring_count.p, c->sxy.p, c->sz.p, c->sidx.p, unit_tab,
-        slow_count, c->slow_list.p, redo_count, c->redo_list.p, redo_cap};
-      launch_unit(c->unit_variant, true, (int)c->unit_chunks, false, dim3((units + lfx::kUnitWaves - 1) / lfx::kUnitWaves), c->unit_lds_pad, st, a);
+      Timed t(c, kSlotExtract, st);
+      const dim3 grid = c->fast_path ? dim3(list_grid) : dim3(c->max_rings, batch);
+      hipLaunchKernelGGL(lfx::ring_extract_kernel, grid, dim3(c->ring_threads), c->ring_lds, st,
+        ex, short_tail ? 2u : (c->fast_path ? 1u : 0u), short_tail ? fb_count : slow_count, short_tail ? c->fb_list.p : c->slow_list.p);
     }
-  }
-  {
-    Timed t(c, 4, st);
-    const dim3 grid = c->fast_path ? dim3(list_grid) : dim3(c->max_rings, batch);
-    hipLaunchKernelGGL(lfx::ring_extract_kernel, grid, dim3(c->ring_threads), c->ring_lds, st,
-      ex, short_tail ? 2u : (c->fast_path ? 1u : 0u), short_tail ? fb_count : slow_count, short_tail ? c->fb_list.p : c->slow_list.p);
-  }
   }
   if (c->long_slices != 0u) {
     // rings longer than the LDS holds, whichever of the kernels above put them on the long list (its first read: the list's
     // length; an empty list ends every workgroup there)
-    Timed t(c, 12, st);
+    Timed t(c, kSlotLong, st);
     hipLaunchKernelGGL(lfx::ring_long_kernel, dim3(c->long_slices), dim3(512), lfx::kLongSortLds, st, ex, c->long_work.p,
       c->long_slice_bytes);
   }
@@ -501,21 +512,21 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
     // batch; a scan that route gave up is summed from its unit tables inside the compaction kernel.
     const bool self_totals = (fused || (uint64_t)batch * c->max_rings <= 8192u) && c->totals_env != 1;
     if (!self_totals) {
-      Timed t(c, 5, st);
+      Timed t(c, kSlotTotals, st);
       hipLaunchKernelGGL(lfx::ring_totals_kernel, dim3(batch), dim3(lfx::kRings), 0, st,
-        c->scan_info.p, c->ring_count.p, c->unit_ne.p, c->unit_ns.p, ring_nedge, ring_nsurf,
+        c->scan_info.p, c->ring_count.p, c->unit_ne.p, c->unit_ns.p, acc.ring_nedge, acc.ring_nsurf,
         c->ring_ebase.p, c->ring_sbase.p, n_units, c->max_rings);
     }
     c->batch_serial = c->batch_serial + 1u == 0u ? 1u : c->batch_serial + 1u;
     {
-      Timed t(c, 6, st);
+      // (the last five arguments: the OTHER set, zeroed here for the batch after this one over the scans left dirty in it)
+      Timed t(c, kSlotCompact, st);
       hipLaunchKernelGGL(lfx::feature_compact_kernel, dim3((c->max_rings + 3) / 4, batch), dim3(256), 0, st,
         n_units, c->cap, c->scan_begin.p, c->ring_count.p, self_totals ? nullptr : c->ring_ebase.p, c->ring_sbase.p, c->unit_ne.p,
         c->unit_ns.p, c->unit_span.p, c->rec_pts.p, c->rec_idx.p, c->edge_pts.p, c->edge_idx.p, c->surf_pts.p,
-        c->surf_idx.p, c->max_rings, c->scan_info.p, counters, c->h_counters, c->batch_serial, ring_nedge, ring_nsurf, c->rec32.p, c->slot_places,
-        scan_flags, c->ring_count.p, batch, fused ? 1u : 0u,
-        c->counters.p + (par ^ 1u) * lfx::kParityCounters, c->scan_flags.p + (size_t)(par ^ 1u) * c->max_batch,
-        c->ring_nedge.p + (par ^ 1u) * tables, c->ring_nsurf.p + (par ^ 1u) * tables, c->par_dirty[par ^ 1u]);
+        c->surf_idx.p, c->max_rings, c->scan_info.p, counters, c->h_counters, c->batch_serial, acc.ring_nedge, acc.ring_nsurf, c->rec32.p,
+        c->slot_places, acc.scan_flags, c->ring_count.p, batch, fused ? 1u : 0u,
+        other.counters, other.scan_flags, other.ring_nedge, other.ring_nsurf, c->par_dirty[par ^ 1u]);
     }
     // (this batch's set is dirty over its scans from here on; the other one is clean once the compaction has run)
     c->par_dirty[par ^ 1u] = 0u;
@@ -566,11 +577,11 @@ int fetch_queue(lfx_ctx * c, uint32_t first, uint32_t count, hipStream_t st, uin
     // ring-major (fixed capacity per ring) -> the caller's point order (labels, curvature) and the dense list of
     // angle-sorted indices, rings ascending; points that are in no ring (zero filter, over-long ring) stay Default / 0.
     // All scans of the range in one launch and one copy per array (the buffers grow to the largest range asked for).
-    if (c->d_label.n < P) {
+    if (c->d_sidx.n < P) {                   // (the last of the three to grow: its length stands for all of them)
       LFX_HIP(c, hipStreamSynchronize(st));
+      // (all three go before the first grows: the old three and the new never lie side by side)
       c->d_label.release(); c->d_curv.release(); c->d_sidx.release();
       if (c->d_label.alloc(P) != hipSuccess || c->d_curv.alloc(P) != hipSuccess || c->d_sidx.alloc(P) != hipSuccess) {
-        c->d_label.n = 0;
         return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the per-point output buffers");
       }
     }
@@ -942,18 +953,17 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
   // (a padding beyond the kernels' 32-position windows: the workgroup-per-ring kernel for every ring, lfx_kernels_extract.hpp label_pass_wide)
   c->fast_path = c->dev.B <= lfx::kUnitMaxBlocks && c->dev.P <= lfx::kWindowPadding && LFX_DEBUG_ENV("NO_FAST_PATH") == nullptr;
   // the organised-scan kernel needs to know the sensor's ring count (max_rings given) and reads PointXYZIR records
-  c->fused_possible = c->fast_path && config->max_rings != 0 && c->max_points < (1u << 27) && c->layout.step == 32 && c->layout.ox == 0 &&
-    c->layout.oy == 4 && c->layout.oz == 8 && c->layout.oring == 20 && c->layout.rtype == LFX_FIELD_UINT16 && c->layout.be == 0;
+  c->fused_possible = c->fast_path && config->max_rings != 0 && c->max_points < (1u << 27) && canonical_layout(c->layout);
   c->organised_by_config = c->fused_possible;
-  if (const char * dbg = LFX_DEBUG_ENV("FUSED")) {c->route_pins.fused = std::atoi(dbg) != 0 ? 1 : 0;}
-  if (const char * dbg = LFX_DEBUG_ENV("TOTALS_KERNEL")) {c->totals_env = std::atoi(dbg) != 0 ? 1 : 0;}
-  if (const char * dbg = LFX_DEBUG_ENV("SHORT_TAIL")) {c->route_pins.short_tail = std::atoi(dbg) != 0 ? 1 : 0;}
-  if (const char * dbg = LFX_DEBUG_ENV("XFORM")) {c->route_pins.xform = std::atoi(dbg) != 0 ? 1 : 0;}
-  if (const char * dbg = LFX_DEBUG_ENV("HOLES")) {c->route_pins.holes = std::atoi(dbg) != 0 ? 1 : 0;}
+  c->route_pins.fused = debug_pin(LFX_DEBUG_ENV("FUSED"));
+  c->totals_env = debug_pin(LFX_DEBUG_ENV("TOTALS_KERNEL"));
+  c->route_pins.short_tail = debug_pin(LFX_DEBUG_ENV("SHORT_TAIL"));
+  c->route_pins.xform = debug_pin(LFX_DEBUG_ENV("XFORM"));
+  c->route_pins.holes = debug_pin(LFX_DEBUG_ENV("HOLES"));
   if (const char * dbg = LFX_DEBUG_ENV("SCAN_COUNT_FROM")) {c->scan_count_from = (uint32_t)std::atoi(dbg);}      // batch from which the count pass is one workgroup per scan
   c->slow_grid = 1024;
   if (const char * dbg = LFX_DEBUG_ENV("REDO_CAP")) {c->route_pins.redo_cap = (uint32_t)std::atoi(dbg);}
-  if (const char * dbg = LFX_DEBUG_ENV("PRE_ORDER")) {c->route_pins.pre_order = std::atoi(dbg) != 0 ? 1 : 0;}
+  c->route_pins.pre_order = debug_pin(LFX_DEBUG_ENV("PRE_ORDER"));
   if (const char * dbg = LFX_DEBUG_ENV("UNIT_FLAGS")) {c->unit_flags = (uint32_t)std::atoi(dbg);}
   if (const char * dbg = LFX_DEBUG_ENV("UNIT_LDS_PAD")) {c->unit_lds_pad = (uint32_t)std::atoi(dbg);}
   if (const char * dbg = LFX_DEBUG_ENV("RING_THREADS")) {c->ring_threads = (uint32_t)std::atoi(dbg);}
@@ -1068,11 +1078,12 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
       t.rec_pts = c->rec_pts.p; t.rec_idx = c->rec_idx.p; t.ring_status = c->ring_status.p;
       t.unit_ne = c->unit_ne.p; t.unit_ns = c->unit_ns.p; t.unit_span = c->unit_span.p; t.ring_flags = c->ring_flags.p;
       t.scan_info = c->scan_info.p;
-      t.fb_count = c->counters.p + par * lfx::kParityCounters + lfx::kCntFallback;
+      const AccSet acc = acc_set(c, par);
+      t.fb_count = acc.counters + lfx::kCntFallback;
       t.fb_list = c->fb_list.p;
-      t.scan_flags = c->scan_flags.p + (size_t)par * nb;
+      t.scan_flags = acc.scan_flags;
       t.sidx = c->sidx.p; t.cum16 = c->cum16.p; t.hole_desc = c->hole_desc.p;
-      t.ring_nedge = c->ring_nedge.p + par * tables; t.ring_nsurf = c->ring_nsurf.p + par * tables;
+      t.ring_nedge = acc.ring_nedge; t.ring_nsurf = acc.ring_nsurf;
       t.rec32 = c->rec32.p; t.prm = c->dev;
       e = hipMemcpy(c->unit_tab.p + par, &t, sizeof(t), hipMemcpyHostToDevice);
     }
@@ -1080,28 +1091,16 @@ int lfx_create(lfx_ctx ** out, int device_id, const lfx_params * params, const l
   if (e == hipSuccess) {e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);}
   // (the attribute is per function, not per context: always the worst case, so that contexts of different ring
   // capacities can live side by side)
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::ring_extract_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx::ring_lds_bytes(LFX_MAX_RING_POINTS));
-  }
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::scan_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-  }
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::fallback_tail_kernel<true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx::ring_lds_bytes(LFX_MAX_RING_POINTS));
-  }
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::fallback_tail_kernel<false>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx::ring_lds_bytes(LFX_MAX_RING_POINTS));
-  }
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::ring_order_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx::order_lds_bytes(LFX_MAX_RING_POINTS));
-  }
-  if (e == hipSuccess) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::ring_stage_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx::ring_lds_bytes(LFX_MAX_RING_POINTS));
+  const size_t ring_lds_max = lfx::ring_lds_bytes(LFX_MAX_RING_POINTS);
+  const struct {const void * kernel; size_t lds;} dynamic_lds[] = {
+    {reinterpret_cast<const void *>(lfx::ring_extract_kernel), ring_lds_max},
+    {reinterpret_cast<const void *>(lfx::scan_count_kernel), 144 * 1024},
+    {reinterpret_cast<const void *>(lfx::fallback_tail_kernel<true>), ring_lds_max},
+    {reinterpret_cast<const void *>(lfx::fallback_tail_kernel<false>), ring_lds_max},
+    {reinterpret_cast<const void *>(lfx::ring_order_kernel), lfx::order_lds_bytes(LFX_MAX_RING_POINTS)},
+    {reinterpret_cast<const void *>(lfx::ring_stage_kernel), ring_lds_max}};
+  for (const auto & k : dynamic_lds) {
+    if (e == hipSuccess) {e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);}
   }
   if (e != hipSuccess) {
     g_create_error = std::string("device setup failed: ") + hipGetErrorString(e);
@@ -1126,34 +1125,24 @@ void lfx_destroy(lfx_ctx * c)
   if (!c) {return;}
   (void)hipSetDevice(c->device);
   if (c->stream) {(void)hipStreamSynchronize(c->stream);}
+  if (c->copy_stream) {(void)hipStreamSynchronize(c->copy_stream);}
   for (auto & sp : c->spans) {(void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b);}
   for (auto & ev : c->free_events) {(void)hipEventDestroy(ev);}
-  c->scan_begin.release(); c->scan_info.release(); c->scan_geom.release(); c->chunk_base.release();
-  c->ring_count.release(); c->chunk_flags.release(); c->d_label.release(); c->d_curv.release(); c->d_sidx.release();
-  c->ring_status.release(); c->ring_nedge.release(); c->ring_nsurf.release(); c->ring_ebase.release();
-  c->ring_sbase.release(); c->ring_flags.release(); c->counters.release(); c->scan_flags.release(); c->tail_ticket.release(); c->cum16.release(); c->hole_desc.release(); c->long_list.release(); c->long_count.release(); c->long_work.release(); c->ring_slot.release(); c->slow_list.release(); c->defer_list.release(); c->redo_list.release(); c->fb_list.release(); c->xform.release(); c->unit_ne.release(); c->unit_ns.release(); c->unit_span.release();
-  c->sxy.release(); c->sz.release(); c->sidx.release(); c->rec_pts.release(); c->rec_idx.release(); c->label_s.release();
-  c->unit_tab.release();
-  if (c->h_counters) {(void)hipHostFree(c->h_counters); c->h_counters = nullptr;}
-  c->rec32.release();
-  c->curv_s.release(); c->edge_pts.release(); c->surf_pts.release(); c->edge_idx.release(); c->surf_idx.release();
-  c->staging.release();
-  c->h_in.release(); c->h_out.release(); c->vox_scratch.release(); c->align_scratch.release(); c->align_surface.release(); c->h_align.release(); c->h_loc.release();
-  if (c->h_status) {(void)hipHostFree(c->h_status); c->h_status = nullptr;}
   for (auto & ev : c->deskew_copied) {
-    if (ev) {(void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); ev = nullptr;}
+    if (ev) {(void)hipEventSynchronize(ev); (void)hipEventDestroy(ev);}
   }
-  c->h_deskew.release(); c->d_deskew.release();
-  if (c->copy_stream) {(void)hipStreamSynchronize(c->copy_stream);}
   for (auto & sl : c->slots) {
-    sl.in.release(); sl.hin.release(); sl.hout.release();
     if (sl.uploaded) {(void)hipEventDestroy(sl.uploaded);}
     if (sl.done) {(void)hipEventDestroy(sl.done);}
     delete static_cast<FetchPlan *>(sl.plan);
   }
   if (c->copy_stream) {(void)hipStreamDestroy(c->copy_stream);}
   if (c->stream) {(void)hipStreamDestroy(c->stream);}
+  // the buffers go with the context; the two raw pinned blocks behind them, as ever (a batch's last kernel writes h_counters)
+  uint32_t * const h_counters = c->h_counters, * const h_status = c->h_status;
   delete c;
+  if (h_counters) {(void)hipHostFree(h_counters);}
+  if (h_status) {(void)hipHostFree(h_status);}
 }
 
 int lfx_extract_batch_device(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uint32_t batch, void * stream)
@@ -1383,7 +1372,6 @@ int lfx_extract_submit(lfx_ctx * c, const void * points, size_t n_points, uint64
   }
   const size_t bytes = n_points * c->layout.step;
   if (!sl.in.p && sl.in.alloc((size_t)c->max_points * c->layout.step) != hipSuccess) {
-    sl.in.p = nullptr;
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the slot's input buffer");
   }
   if (sl.hin.bytes < bytes) {
@@ -1438,42 +1426,37 @@ int lfx_stage_ring(
   LFX_HIP(c, hipSetDevice(c->device));
   const lfx::Params dp = device_params(*pp);
   const uint32_t cap = ((n < 64 ? 64 : n) + 63u) & ~63u;
-  float * dx = nullptr, * dy = nullptr;
-  int32_t * dg = nullptr, * dstat = nullptr;
-  double * dci = nullptr, * dri = nullptr, * dr = nullptr, * dc = nullptr;
-  uint8_t * dl = nullptr, * dlab = nullptr;
-  auto cleanup = [&] {
-      (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dg); (void)hipFree(dstat); (void)hipFree(dci); (void)hipFree(dri);
-      (void)hipFree(dr); (void)hipFree(dc); (void)hipFree(dl); (void)hipFree(dlab);
-    };
+  DevBuf<float> dx, dy;
+  DevBuf<int32_t> dg, dstat;
+  DevBuf<double> dci, dri, dr, dc;
+  DevBuf<uint8_t> dl, dlab;
   hipError_t e = hipSuccess;
   auto ok = [&](hipError_t r) {if (e == hipSuccess) {e = r;}};
-  ok(hipMalloc(&dx, n * 4)); ok(hipMalloc(&dy, n * 4)); ok(hipMalloc(&dstat, 4));
-  ok(hipMalloc(&dr, n * 8)); ok(hipMalloc(&dc, n * 8)); ok(hipMalloc(&dl, n)); ok(hipMalloc(&dlab, n));
-  if (groups) {ok(hipMalloc(&dg, n * 4));}
-  if (curvature_in) {ok(hipMalloc(&dci, n * 8));}
-  if (range_in) {ok(hipMalloc(&dri, n * 8));}
+  ok(dx.alloc(n)); ok(dy.alloc(n)); ok(dstat.alloc(1));
+  ok(dr.alloc(n)); ok(dc.alloc(n)); ok(dl.alloc(n)); ok(dlab.alloc(n));
+  if (groups) {ok(dg.alloc(n));}
+  if (curvature_in) {ok(dci.alloc(n));}
+  if (range_in) {ok(dri.alloc(n));}
   if (e == hipSuccess) {
-    ok(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-    ok(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-    if (groups) {ok(hipMemcpy(dg, groups, n * 4, hipMemcpyHostToDevice));}
-    if (curvature_in) {ok(hipMemcpy(dci, curvature_in, n * 8, hipMemcpyHostToDevice));}
-    if (range_in) {ok(hipMemcpy(dri, range_in, n * 8, hipMemcpyHostToDevice));}
+    ok(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
+    ok(hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice));
+    if (groups) {ok(hipMemcpy(dg.p, groups, n * 4, hipMemcpyHostToDevice));}
+    if (curvature_in) {ok(hipMemcpy(dci.p, curvature_in, n * 8, hipMemcpyHostToDevice));}
+    if (range_in) {ok(hipMemcpy(dri.p, range_in, n * 8, hipMemcpyHostToDevice));}
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(lfx::ring_stage_kernel, dim3(1), dim3(256), lfx::ring_lds_bytes(cap), c->stream,
-      dp, cap, flags, (int)n, dx, dy, dg, dci, dri, dr, dc, dl, dlab, dstat);
+      dp, cap, flags, (int)n, dx.p, dy.p, dg.p, dci.p, dri.p, dr.p, dc.p, dl.p, dlab.p, dstat.p);
     ok(hipGetLastError());
     ok(hipStreamSynchronize(c->stream));
   }
   if (e == hipSuccess) {
-    if (range_out) {ok(hipMemcpy(range_out, dr, n * 8, hipMemcpyDeviceToHost));}
-    if (curvature_out) {ok(hipMemcpy(curvature_out, dc, n * 8, hipMemcpyDeviceToHost));}
-    if (link_out && n > 1) {ok(hipMemcpy(link_out, dl, n - 1, hipMemcpyDeviceToHost));}
-    if (labels_out) {ok(hipMemcpy(labels_out, dlab, n, hipMemcpyDeviceToHost));}
-    if (ring_status_out) {ok(hipMemcpy(ring_status_out, dstat, 4, hipMemcpyDeviceToHost));}
+    if (range_out) {ok(hipMemcpy(range_out, dr.p, n * 8, hipMemcpyDeviceToHost));}
+    if (curvature_out) {ok(hipMemcpy(curvature_out, dc.p, n * 8, hipMemcpyDeviceToHost));}
+    if (link_out && n > 1) {ok(hipMemcpy(link_out, dl.p, n - 1, hipMemcpyDeviceToHost));}
+    if (labels_out) {ok(hipMemcpy(labels_out, dlab.p, n, hipMemcpyDeviceToHost));}
+    if (ring_status_out) {ok(hipMemcpy(ring_status_out, dstat.p, 4, hipMemcpyDeviceToHost));}
   }
-  cleanup();
   if (e != hipSuccess) {return fail(c, LFX_ERR_HIP, std::string("lfx_stage_ring: ") + hipGetErrorString(e));}
   return LFX_OK;
 }
@@ -1485,20 +1468,19 @@ int lfx_stage_convolution1d(lfx_ctx * c, const double * input, uint32_t n, const
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "Input array size " + std::to_string(n) + " cannot be smaller than weight size " + std::to_string(m));
   }
   LFX_HIP(c, hipSetDevice(c->device));
-  double * di = nullptr, * dw = nullptr, * dout = nullptr;
+  DevBuf<double> di, dw, dout;
   hipError_t e = hipSuccess;
   auto ok = [&](hipError_t r) {if (e == hipSuccess) {e = r;}};
-  ok(hipMalloc(&di, n * 8)); ok(hipMalloc(&dw, m * 8)); ok(hipMalloc(&dout, n * 8));
+  ok(di.alloc(n)); ok(dw.alloc(m)); ok(dout.alloc(n));
   if (e == hipSuccess) {
-    ok(hipMemcpy(di, input, n * 8, hipMemcpyHostToDevice));
-    ok(hipMemcpy(dw, weight, m * 8, hipMemcpyHostToDevice));
+    ok(hipMemcpy(di.p, input, n * 8, hipMemcpyHostToDevice));
+    ok(hipMemcpy(dw.p, weight, m * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(lfx::convolution1d_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream,
-      di, (int)n, dw, (int)m, dout);
+      di.p, (int)n, dw.p, (int)m, dout.p);
     ok(hipGetLastError());
     ok(hipStreamSynchronize(c->stream));
-    ok(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+    ok(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));
   }
-  (void)hipFree(di); (void)hipFree(dw); (void)hipFree(dout);
   if (e != hipSuccess) {return fail(c, LFX_ERR_HIP, std::string("lfx_stage_convolution1d: ") + hipGetErrorString(e));}
   return LFX_OK;
 }

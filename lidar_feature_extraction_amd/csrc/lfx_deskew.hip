@@ -72,7 +72,6 @@ int deskew_scans(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * swe
       for (auto & ev : c->deskew_copied) {
         if (ev) {(void)hipEventDestroy(ev); ev = nullptr;}
       }
-      c->d_deskew.release();
       return fail(c, LFX_ERR_OUT_OF_MEMORY, std::string("cannot set up the de-skew table: ") + hipGetErrorString(e));
     }
   }

@@ -12,6 +12,8 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "lfx_kernels_common.hpp"
@@ -71,22 +73,38 @@ inline void launch_unit(int variant, bool second, int chunks, bool loop, dim3 gr
   }
 }
 
+// Device memory with one owner: freed when the owner goes, moved but never copied.  alloc gives back what the buffer held
+// before it asks for more, and a buffer whose alloc failed is empty ({nullptr, 0}).
 template<typename T>
 struct DevBuf
 {
   T * p = nullptr;
   size_t n = 0;
-  hipError_t alloc(size_t count)
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf & operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf && o) noexcept : p(o.p), n(o.n) {o.p = nullptr; o.n = 0;}
+  DevBuf & operator=(DevBuf && o) noexcept
   {
-    n = count;
-    return hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T) + 16);
+    if (this != &o) {release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0;}
+    return *this;
+  }
+  ~DevBuf() {release();}
+  hipError_t alloc(size_t count)       // (16 spare bytes behind the elements)
+  {
+    release();
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T) + 16);
+    if (e == hipSuccess) {n = count;} else {p = nullptr;}
+    return e;
   }
   void release()
   {
     if (p) {(void)hipFree(p);}
     p = nullptr;
+    n = 0;
   }
 };
+static_assert(!std::is_copy_constructible_v<DevBuf<float>> && !std::is_copy_assignable_v<DevBuf<float>>, "a device buffer has one owner");
 
 // a device buffer that holds at least `need` elements, grown by half again when it must grow -- or, `exact`, to `need` and
 // no further: the buffers that are the library's largest at 1 024 scans -- (its contents are not kept)
@@ -94,10 +112,7 @@ template<typename T>
 hipError_t hold(DevBuf<T> & b, size_t need, bool exact = false)
 {
   if (b.n >= need && (b.p || need == 0)) {return hipSuccess;}
-  b.release();
-  const hipError_t e = b.alloc(exact ? need : need + need / 2);
-  if (e != hipSuccess) {b.p = nullptr; b.n = 0;}
-  return e;
+  return b.alloc(exact ? need : need + need / 2);
 }
 
 struct HostScan          // the per-ring lists of one scan (the large arrays live in the pinned result block)
@@ -107,21 +122,31 @@ struct HostScan          // the per-ring lists of one scan (the large arrays liv
   std::vector<uint16_t> ring_id;
 };
 
-// Pinned host memory that only ever grows (the results handed to the caller stay valid until the next call).
+// Pinned host memory that only ever grows (the results handed to the caller stay valid until the next call); owned as a
+// DevBuf is.
 struct PinnedBuf
 {
   uint8_t * p = nullptr;
   size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf & operator=(const PinnedBuf &) = delete;
+  PinnedBuf(PinnedBuf && o) noexcept : p(o.p), bytes(o.bytes) {o.p = nullptr; o.bytes = 0;}
+  PinnedBuf & operator=(PinnedBuf && o) noexcept
+  {
+    if (this != &o) {release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0;}
+    return *this;
+  }
+  ~PinnedBuf() {release();}
   hipError_t reserve(size_t need)
   {
     if (need <= bytes) {return hipSuccess;}
     // (growing is rare; a copy queued on the old block by a call that returned early with an error must not outlive it)
-    if (p) {(void)hipDeviceSynchronize(); (void)hipHostFree(p);}
-    p = nullptr;
-    bytes = 0;
+    if (p) {(void)hipDeviceSynchronize();}
+    release();
     const size_t want = need + need / 4 + 4096;
     const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault);
-    if (e == hipSuccess) {bytes = want;}
+    if (e == hipSuccess) {bytes = want;} else {p = nullptr;}
     return e;
   }
   void release()
@@ -131,6 +156,16 @@ struct PinnedBuf
     bytes = 0;
   }
 };
+static_assert(!std::is_copy_constructible_v<PinnedBuf> && !std::is_copy_assignable_v<PinnedBuf>, "a pinned block has one owner");
+
+// The kernel slots of lfx_kernel_times, in the order of the comment on LFX_N_KERNELS (lfx.h); kKernelNames (lfx_api.hip) is
+// written in this order
+enum KernelSlot : int
+{
+  kSlotScatter, kSlotUnit, kSlotOrder, kSlotUnitSecond, kSlotExtract, kSlotTotals, kSlotCompact, kSlotUnitOrg, kSlotCut, kSlotTail,
+  kSlotGridCount, kSlotReset, kSlotLong, kSlotCount
+};
+static_assert(kSlotCount == LFX_N_KERNELS, "a slot per kernel of lfx_kernel_times");
 
 }  // namespace lfx_host
 

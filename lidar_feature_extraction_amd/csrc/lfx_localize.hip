@@ -125,22 +125,21 @@ int lfx_map_create(lfx_ctx * c, const float * d_points, uint32_t n_points, float
   if (!m) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map");}
   m->device = c->device;
   auto give_up = [&](int code, const char * why) {lfx_map_destroy(m); return fail(c, code, why);};
-  if (m->pts.alloc(n_points) != hipSuccess) {m->pts.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's points");}
+  if (m->pts.alloc(n_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's points");}
   const float4 * src = reinterpret_cast<const float4 *>(d_points);
   double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
   if (cell_size != 0.f) {                              // bounds of the map
-    uint32_t * d_bounds = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d_bounds), 6 * sizeof(uint32_t)) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's bounds");}
+    DevBuf<uint32_t> d_bounds;
+    if (d_bounds.alloc(6) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's bounds");}
     const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     uint32_t got[6];
-    hipError_t e = hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(d_bounds.p, init, sizeof(init), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
       const uint32_t blocks = std::min<uint32_t>((n_points + 255u) / 256u, 2048u);
-      hipLaunchKernelGGL(lfx::map_bounds_kernel, dim3(blocks), dim3(256), 0, st, src, n_points, d_bounds);
-      e = hipMemcpyAsync(got, d_bounds, sizeof(got), hipMemcpyDeviceToHost, st);
+      hipLaunchKernelGGL(lfx::map_bounds_kernel, dim3(blocks), dim3(256), 0, st, src, n_points, d_bounds.p);
+      e = hipMemcpyAsync(got, d_bounds.p, sizeof(got), hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) {e = hipStreamSynchronize(st);}
-    (void)hipFree(d_bounds);
     if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
     for (int a = 0; a < 3; a++) {
       lo[a] = lfx::float_of_order(got[a]); hi[a] = lfx::float_of_order(got[3 + a]);
@@ -150,7 +149,6 @@ int lfx_map_create(lfx_ctx * c, const float * d_points, uint32_t n_points, float
   DevBuf<uint32_t> cell_count, partial;                // the build's scratch, this call's own
   hipError_t e = build_index(m, src, n_points, cell_size, lo, hi, cell_count, partial, true, st);
   if (e == hipSuccess) {e = hipStreamSynchronize(st);}
-  cell_count.release(); partial.release();
   if (e == hipErrorOutOfMemory) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map's cells");}
   if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
   *out = m;
@@ -161,7 +159,6 @@ void lfx_map_destroy(lfx_map * m)
 {
   if (!m) {return;}
   (void)hipSetDevice(m->device);
-  m->pts.release(); m->start.release(); m->cell_count.release(); m->partial.release();
   delete m;
 }
 
@@ -173,10 +170,8 @@ int lfx_map_create_host(lfx_ctx * c, const float * points, uint32_t n_points, fl
   if (staged.alloc(4 * (size_t)n_points) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the map's points");}
   hipError_t e = hipMemcpyAsync(staged.p, points, sizeof(float) * 4 * (size_t)n_points, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream));
   if (e == hipSuccess) {e = hipStreamSynchronize(static_cast<hipStream_t>(stream));}
-  if (e != hipSuccess) {staged.release(); return fail(c, LFX_ERR_HIP, hipGetErrorString(e));}
-  const int rc = lfx_map_create(c, staged.p, n_points, cell_size, out, stream);
-  staged.release();
-  return rc;
+  if (e != hipSuccess) {return fail(c, LFX_ERR_HIP, hipGetErrorString(e));}
+  return lfx_map_create(c, staged.p, n_points, cell_size, out, stream);
 }
 
 int lfx_map_info(const lfx_map * m, uint32_t * n_points, float * cell_size, int32_t dims[3])

@@ -99,19 +99,11 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
       return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot grow the map to " + std::to_string(want) + " records");
     }
     // (the previous call's append may be queued on another stream: the copy reads the map behind it)
-    if (m->upload_pending) {
-      const hipError_t e = hipStreamWaitEvent(st, m->uploaded, 0);
-      if (e != hipSuccess) {grown.release(); LFX_HIP(c, e);}
-    }
-    if (m->n) {
-      const hipError_t e = hipMemcpyAsync(grown.p, m->map.p, sizeof(float4) * m->n, hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) {grown.release(); LFX_HIP(c, e);}
-    }
+    if (m->upload_pending) {LFX_HIP(c, hipStreamWaitEvent(st, m->uploaded, 0));}
+    if (m->n) {LFX_HIP(c, hipMemcpyAsync(grown.p, m->map.p, sizeof(float4) * m->n, hipMemcpyDeviceToDevice, st));}
     // (growth is rare: the copy has read the old map before it goes)
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {grown.release(); LFX_HIP(c, e);}
-    m->map.release();
-    m->map = grown;
+    LFX_HIP(c, hipStreamSynchronize(st));
+    m->map = std::move(grown);
   }
   if (!added.empty()) {
     const size_t na = added.size();
@@ -119,9 +111,8 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
       DevBuf<lfx::MapAppendEntry> t;
       if (t.alloc(na + na / 2) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's table");}
       const int rs = settle(c, m);           // (the previous append may still read the old table)
-      if (rs != LFX_OK) {t.release(); return rs;}
-      m->table.release();
-      m->table = t;
+      if (rs != LFX_OK) {return rs;}
+      m->table = std::move(t);
     }
     const size_t bytes = sizeof(lfx::MapAppendEntry) * na;
     LFX_HIP(c, m->pinned.reserve(m->pin_table + bytes));
@@ -199,8 +190,8 @@ int lfx_mapper_create(lfx_ctx * c, const lfx_mapper_config * cfg, lfx_mapper ** 
   m->device = c->device;
   m->cfg = *cfg;
   auto give_up = [&](int code, const std::string & why) {lfx_mapper_destroy(m); return fail(c, code, why);};
-  if (m->map.alloc(cfg->initial_capacity_points) != hipSuccess) {m->map = DevBuf<float4>{}; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map");}
-  if (m->table.alloc(kInitialEntries) != hipSuccess) {m->table = DevBuf<lfx::MapAppendEntry>{}; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's table");}
+  if (m->map.alloc(cfg->initial_capacity_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the map");}
+  if (m->table.alloc(kInitialEntries) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's table");}
   // room for the counts and begins of kInitialEntries clouds at stride 4 (a device batch's scan_info): a batch of up to 64
   // scans allocates nothing in a call that fits the map
   m->pin_table = round64(readback_bytes(kInitialEntries, 4));
@@ -220,8 +211,6 @@ void lfx_mapper_destroy(lfx_mapper * m)
   if (!m) {return;}
   (void)hipSetDevice(m->device);
   if (m->uploaded) {(void)hipEventSynchronize(m->uploaded); (void)hipEventDestroy(m->uploaded);}
-  m->map.release(); m->table.release(); m->staged.release();
-  m->pinned.release();
   delete m;
 }
 

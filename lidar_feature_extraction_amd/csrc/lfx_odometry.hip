@@ -277,10 +277,10 @@ int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odomet
   o->emap = map_new(c->device);
   o->smap = map_new(c->device);
   if (!o->emap || !o->smap) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the window maps");}
-  if (o->edge.alloc(cfg->edge_capacity_points) != hipSuccess) {o->edge.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the edge store");}
-  if (o->surface.alloc(cfg->surface_capacity_points) != hipSuccess) {o->surface.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the surface store");}
-  if (o->bounds.alloc(12) != hipSuccess) {o->bounds.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's bounds");}
-  if (o->words.alloc(8) != hipSuccess) {o->words.p = nullptr; return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's words");}
+  if (o->edge.alloc(cfg->edge_capacity_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the edge store");}
+  if (o->surface.alloc(cfg->surface_capacity_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the surface store");}
+  if (o->bounds.alloc(12) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's bounds");}
+  if (o->words.alloc(8) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's words");}
   if (o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)std::max(c->max_batch, 1u))) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's pinned block");
   }
@@ -302,8 +302,6 @@ void lfx_odometry_destroy(lfx_odometry * o)
   if (o->tail) {(void)hipEventSynchronize(o->tail); (void)hipEventDestroy(o->tail);}
   lfx_map_destroy(o->emap);
   lfx_map_destroy(o->smap);
-  o->edge.release(); o->surface.release(); o->bounds.release(); o->words.release(); o->down.release(); o->staged.release(); o->dsk_edge.release(); o->dsk_surface.release();
-  o->pinned.release();
   delete o;
 }
 
