@@ -817,6 +817,69 @@ int lfx_odometry_update_batch_deskewed(lfx_ctx *ctx, lfx_odometry *odometry, con
                                        const double *sweep_times, double sweep_ratio, int to, uint32_t n_scans,
                                        lfx_odometry_result *results, void *stream);
 
+/* De-skew along a TRAJECTORY: the sensor's poses within the sweep, as an IMU, a wheel odometer or a fused pose stream gives
+ * them (10 - 40 per 0.1 s sweep), in place of one constant motion.
+ * Model: between knots j and j + 1 the rotation runs along the geodesic and the position along the straight line.  With
+ * beta = (t - times[j]) * (1 / (times[j+1] - times[j])) the pose is
+ *   P(t) = [R_j Exp(beta Log(R_j^T R_{j+1})) | p_j + beta (p_{j+1} - p_j)].
+ * The segment of a time t is j = clamp(#{knots with times[k] <= t} - 1, 0, n_knots - 2): a time on a knot belongs to the
+ * segment that starts there; a time before the first knot extrapolates the first segment, one after the last knot the last
+ * segment; beta is not clamped (as alpha is not).  A record measured at t becomes P(t_ref)^-1 P(t) p.
+ * Arithmetic, host (lfx_trajectory_segments; the motion helpers' arithmetic, every 3-term sum (a0 b0 + a1 b1) + a2 b2,
+ * unfused): P_ref is the knot's pose itself where t_ref equals a knot time, else with j, beta of t_ref
+ *   P_ref = [R_j * rot(lfx_motion_scale(lfx_motion_between(P_j, P_{j+1}), beta)) | p_j + beta (p_{j+1} - p_j)];
+ * Q_j = lfx_motion_between(P_ref, P_j) for every knot; per segment D_j = lfx_motion_between(Q_j, Q_{j+1}),
+ * (w_j, theta_j) = lfx_motion_twist(D_j), k_j = w_j / theta_j (0 where theta_j < 1e-8), A_j the rotation of Q_j, q_j its
+ * translation, dq_j = q_{j+1} - q_j.  A segment's row of the table, 24 doubles:
+ *   [0..2] k_j   [3] theta_j   [4..6] w_j   [7..15] A_j row-major   [16..18] q_j   [19..21] dq_j   [22] times[j]
+ *   [23] 1 / (times[j+1] - times[j])
+ * Arithmetic, device, per record: double from the float record, unfused; r is the rotation step of the constant-motion
+ * de-skew above with beta, k_j, theta_j, w_j (a = beta * theta_j, r = (p c + kxp s) + k (kdp (1 - c)); where
+ * theta_j < 1e-8, r = p + beta (w_j x p));
+ *   out_i = ((A_j[i][0] r0 + A_j[i][1] r1) + A_j[i][2] r2) + (q_j[i] + beta * dq_j[i]), rounded once to float.
+ * The 4th float is copied.  A record whose time is not finite (its beta is not) is copied unchanged; with
+ * LFX_TIME_FROM_FIELD and an index outside the scan nothing is read and the record is copied.
+ * Consequence: with two knots and t_ref = times[0], Q_0 is the identity itself and the result equals
+ * lfx_deskew_batch(..., LFX_DESKEW_TO_START) with motion = lfx_motion_between(P_0, P_1), t0 = times[0], t1 = times[1]
+ * (times 0, 1 with LFX_TIME_FROM_INDEX), value for value. */
+#define LFX_MAX_TRAJECTORY_KNOTS 64
+#define LFX_TRAJECTORY_SEGMENT_DOUBLES 24
+typedef struct lfx_trajectory {
+  uint32_t n_knots;        /* 2 .. LFX_MAX_TRAJECTORY_KNOTS */
+  const double *times;     /* host [n_knots], finite, strictly ascending: seconds with LFX_TIME_FROM_FIELD, fractions of
+                              the sweep (index / n_points of the scan) with LFX_TIME_FROM_INDEX */
+  const double *poses;     /* host [n_knots][12]: the sensor's pose at times[j], [R | t] row-major, all in ONE fixed frame */
+  double t_ref;            /* the records are brought to the sensor frame at this time (same unit; may lie outside the knots) */
+} lfx_trajectory;
+/* Host only, no context: the table the kernel is given, [n_knots - 1][24] doubles in the order above.
+ * LFX_ERR_INVALID_ARGUMENT: NULL arguments, n_knots outside 2 .. 64, NULL times / poses, times that are not finite or not
+ * strictly ascending, a non-finite pose entry or t_ref. */
+int lfx_trajectory_segments(const lfx_trajectory *trajectory, double *segments_out);
+/* Host only: knots from gyro samples.  P_0 = identity; R_{j+1} = R_j E_j (3-term sums as above), E_j the rotation
+ * lfx_motion_scale forms for the angle-axis vector phi = (0.5 * ((rate_j - bias) + (rate_{j+1} - bias))) * (t_{j+1} - t_j)
+ * (theta = |phi| < 1e-8: I + [phi]x); p_j = velocity * (t_j - t_0) (constant, in the frame of the first sample).  bias and
+ * velocity may be NULL (0).  LFX_ERR_INVALID_ARGUMENT: n < 2, NULL times / rates / poses_out, times that are not finite or
+ * not strictly ascending, a non-finite rate, bias or velocity. */
+int lfx_trajectory_from_gyro(const double *times, const double *rates /* [n][3] rad/s, sensor frame */, uint32_t n,
+                             const double bias[3], const double velocity[3], double *poses_out /* [n][12] */);
+/* lfx_deskew_batch along trajectories[s] (host, [n_scans]; the scans of one batch may have different knot counts): its
+ * contract in every respect not named here.  Asynchronous on `stream`, one launch for the batch, the counts read on the
+ * device; outputs laid out like the view's clouds, BOTH NULL: in place, which sets the same "already de-skewed in place"
+ * mark (either de-skew call, lfx_odometry_update_batch_deskewed and lfx_odometry_update_batch_trajectory then refuse the
+ * batch until the next extraction); the outputs may not be the context's own clouds.  Refused as well, with
+ * LFX_ERR_INVALID_ARGUMENT and before anything is queued: what lfx_trajectory_segments refuses. */
+int lfx_deskew_batch_trajectory(lfx_ctx *ctx, const lfx_time_field *time, const lfx_trajectory *trajectories /* host [n_scans] */,
+                                uint32_t n_scans, float *d_edge_out, float *d_surface_out, void *stream);
+/* lfx_odometry_update_batch_deskewed with the caller's trajectories in place of the prediction (a caller with a pose source
+ * needs no seeding).  Per scan, in order: that scan alone de-skewed out of place (as lfx_deskew_batch_trajectory) into the
+ * odometry's own de-skew buffers, then exactly lfx_odometry_update on those clouds.  The batch's clouds in the context stay
+ * raw.  Refused: what lfx_odometry_update_batch and lfx_deskew_batch_trajectory refuse, and a batch that has already been
+ * de-skewed in place.  Every trajectory of the batch is checked before the first scan is touched: a call refused for
+ * trajectories[s], whichever s, has aligned and added nothing. */
+int lfx_odometry_update_batch_trajectory(lfx_ctx *ctx, lfx_odometry *odometry, const lfx_time_field *time,
+                                         const lfx_trajectory *trajectories, uint32_t n_scans,
+                                         lfx_odometry_result *results, void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

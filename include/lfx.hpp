@@ -59,6 +59,43 @@ struct Features
   std::vector<RingInfo> rings;
 };
 
+// The sensor's poses within one sweep (lfx_trajectory; include/lfx.h, the de-skew section): 2 .. 64 knots with strictly
+// ascending times, every pose [R | t] row-major in ONE fixed frame; the records are brought to the sensor frame at t_ref.
+struct Trajectory
+{
+  std::vector<double> times;      // [k]: seconds with a time field, fractions of the sweep with TimeField::FromIndex()
+  std::vector<double> poses;      // [k][12]
+  double t_ref = 0.0;
+  // Knots from gyro samples (lfx_trajectory_from_gyro): rates [k][3] rad/s in the sensor frame, the first pose the identity
+  static Trajectory FromGyro(
+    const std::vector<double> & times, const std::vector<double> & rates, double t_ref, const double * bias = nullptr,
+    const double * velocity = nullptr)
+  {
+    Trajectory out;
+    out.times = times;
+    out.poses.assign(12 * times.size(), 0.0);
+    out.t_ref = t_ref;
+    if (rates.size() != 3 * times.size() ||
+      lfx_trajectory_from_gyro(times.data(), rates.data(), static_cast<std::uint32_t>(times.size()), bias, velocity, out.poses.data()) != LFX_OK)
+    {
+      throw Error(LFX_ERR_INVALID_ARGUMENT, "invalid gyro samples");
+    }
+    return out;
+  }
+  // (points into this object: valid while it lives unchanged)
+  lfx_trajectory View() const
+  {
+    if (poses.size() != 12 * times.size()) {throw Error(LFX_ERR_INVALID_ARGUMENT, "a trajectory holds 12 pose values per time");}
+    return lfx_trajectory{static_cast<std::uint32_t>(times.size()), times.data(), poses.data(), t_ref};
+  }
+};
+inline std::vector<lfx_trajectory> Views(const std::vector<Trajectory> & trajectories)
+{
+  std::vector<lfx_trajectory> out;
+  for (const Trajectory & t : trajectories) {out.push_back(t.View());}
+  return out;
+}
+
 class FeatureExtraction
 {
 public:
@@ -178,6 +215,16 @@ public:
     float * d_surface_out = nullptr, void * stream = nullptr) const
   {
     const int rc = lfx_deskew_batch(ctx_, &time, sweeps.data(), static_cast<std::uint32_t>(sweeps.size()), to, d_edge_out, d_surface_out, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  // The same along the sensor's poses within each sweep (lfx_deskew_batch_trajectory), one trajectory per scan: for a
+  // caller with an IMU, a wheel odometer or a pose stream
+  void DeskewTrajectory(
+    const lfx_time_field & time, const std::vector<Trajectory> & trajectories, float * d_edge_out = nullptr,
+    float * d_surface_out = nullptr, void * stream = nullptr) const
+  {
+    const std::vector<lfx_trajectory> views = Views(trajectories);
+    const int rc = lfx_deskew_batch_trajectory(ctx_, &time, views.data(), static_cast<std::uint32_t>(views.size()), d_edge_out, d_surface_out, stream);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
   }
   lfx_ctx * handle() const {return ctx_;}
@@ -378,6 +425,16 @@ public:
       rc = lfx_odometry_update_batch_deskewed(ctx_, odometry_, &time, sweep_times.empty() ? nullptr : sweep_times.data(), sweep_ratio, to,
         view.batch, results_.data(), nullptr);
     }
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_;
+  }
+  // The same with every scan de-skewed along the caller's trajectory of it (lfx_odometry_update_batch_trajectory)
+  const std::vector<lfx_odometry_result> & UpdateBatchTrajectory(const lfx_time_field & time, const std::vector<Trajectory> & trajectories)
+  {
+    const std::vector<lfx_trajectory> views = Views(trajectories);
+    results_.assign(views.size(), lfx_odometry_result{});
+    const int rc = lfx_odometry_update_batch_trajectory(ctx_, odometry_, &time, views.data(), static_cast<std::uint32_t>(views.size()),
+      results_.data(), nullptr);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     return results_;
   }

@@ -135,6 +135,12 @@ class Sweep(C.Structure):
     _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("motion", C.c_double * 12)]
 
 
+class Trajectory(C.Structure):
+    """lfx_trajectory: the sensor's poses at n_knots times within a sweep and the time the records are brought to."""
+    _fields_ = [("n_knots", C.c_uint32), ("times", C.POINTER(C.c_double)), ("poses", C.POINTER(C.c_double)), ("t_ref", C.c_double)]
+
+
+MAX_TRAJECTORY_KNOTS, TRAJECTORY_SEGMENT_DOUBLES = 64, 24
 TIME_FROM_INDEX, TIME_FROM_FIELD = 0, 1
 DESKEW_TO_START, DESKEW_TO_END = 0, 1
 
@@ -164,6 +170,7 @@ EXPORTS = [
     "lfx_stage_ring_projection", "lfx_label_to_color", "lfx_color_points_by_label", "lfx_set_profiling", "lfx_set_profiling_interval", "lfx_kernel_times", "lfx_kernel_name",
     "lfx_time_field_from_fields", "lfx_motion_between", "lfx_motion_twist", "lfx_motion_scale", "lfx_deskew_batch",
     "lfx_odometry_update_batch_deskewed",
+    "lfx_trajectory_segments", "lfx_trajectory_from_gyro", "lfx_deskew_batch_trajectory", "lfx_odometry_update_batch_trajectory",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -284,6 +291,11 @@ def load(test_hooks=False):
     L.lfx_deskew_batch.argtypes = [vp, C.POINTER(TimeField), C.POINTER(Sweep), u32, i32, vp, vp, vp]
     L.lfx_odometry_update_batch_deskewed.argtypes = [vp, vp, C.POINTER(TimeField), pd, C.c_double, i32, u32,
                                                      C.POINTER(OdometryResult), vp]
+    L.lfx_trajectory_segments.argtypes = [C.POINTER(Trajectory), pd]
+    L.lfx_trajectory_from_gyro.argtypes = [pd, pd, u32, pd, pd, pd]
+    L.lfx_deskew_batch_trajectory.argtypes = [vp, C.POINTER(TimeField), C.POINTER(Trajectory), u32, vp, vp, vp]
+    L.lfx_odometry_update_batch_trajectory.argtypes = [vp, vp, C.POINTER(TimeField), C.POINTER(Trajectory), u32,
+                                                       C.POINTER(OdometryResult), vp]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_xyz12.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_colored.argtypes = [vp, vp, vp, C.c_size_t, vp]

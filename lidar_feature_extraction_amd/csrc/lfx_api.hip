@@ -1131,6 +1131,9 @@ void lfx_destroy(lfx_ctx * c)
   for (auto & ev : c->deskew_copied) {
     if (ev) {(void)hipEventSynchronize(ev); (void)hipEventDestroy(ev);}
   }
+  for (auto & ts : c->trajectory_slots) {
+    if (ts.used) {(void)hipEventSynchronize(ts.used); (void)hipEventDestroy(ts.used);}
+  }
   for (auto & sl : c->slots) {
     if (sl.uploaded) {(void)hipEventDestroy(sl.uploaded);}
     if (sl.done) {(void)hipEventDestroy(sl.done);}

@@ -282,6 +282,16 @@ struct lfx_ctx
   hipEvent_t deskew_copied[kDeskewSlots] = {};
   uint32_t deskew_next = 0;
   bool deskewed_in_place = false;
+  // lfx_deskew_batch_trajectory: the segment tables travel the same way, but every slot's pinned block and device table are
+  // sized by the calls that used it (segments of the call, not max_batch x 63 rows) and grow on demand
+  struct TrajectorySlot
+  {
+    lfx_host::PinnedBuf h;
+    lfx_host::DevBuf<double> d;
+    hipEvent_t used = nullptr;           // recorded behind the kernel that read d
+  };
+  TrajectorySlot trajectory_slots[kDeskewSlots];
+  uint32_t trajectory_next = 0;
 
   hipStream_t stream = nullptr;          // used by the synchronous host entry points
   std::vector<uint32_t> h_scan_begin;    // of the last batch
@@ -360,6 +370,11 @@ int voxel_downsample(
 // lfx_deskew.hip: scans first .. first + n - 1 of the last batch de-skewed by sweeps[0 .. n - 1] into buffers laid out like
 // the context's clouds (lfx_deskew_batch's checks; lfx_odometry_update_batch_deskewed takes one scan at a time)
 int deskew_scans(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * sweeps, uint32_t first, uint32_t n, int to,
+  float4 * edge_out, float4 * surf_out, hipStream_t st);
+// what is refused about trajectories[0 .. n - 1], nothing touched (lfx_odometry_update_batch_trajectory asks before its first scan)
+int check_trajectories(lfx_ctx * c, const lfx_trajectory * trajectories, uint32_t n);
+// deskew_scans along trajectories[0 .. n - 1] (lfx_deskew_batch_trajectory's checks; lfx_odometry_update_batch_trajectory)
+int deskew_scans_trajectory(lfx_ctx * c, const lfx_time_field * time, const lfx_trajectory * trajectories, uint32_t first, uint32_t n,
   float4 * edge_out, float4 * surf_out, hipStream_t st);
 
 // lfx_localize.hip: a map rebuilt in place (lfx_odometry.hip's window maps) and the optimizer over clouds

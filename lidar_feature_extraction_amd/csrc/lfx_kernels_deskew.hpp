@@ -114,4 +114,118 @@ __global__ __launch_bounds__(kDeskewThreads) void deskew_kernel(const DeskewArgs
   }
 }
 
+// De-skew along a trajectory (include/lfx.h): the constants are a segment's, chosen per record by its time, so they cannot
+// sit in scalar registers.  A segment's row as lfx_trajectory_segments writes it:
+enum
+{
+  kTrjK = 0, kTrjTheta = 3, kTrjW = 4,
+  kTrjA = 7,        // the rotation of Q_j, row-major 3 x 3
+  kTrjQ = 16,       // its translation
+  kTrjDq = 19,      // q_{j+1} - q_j
+  kTrjTime = 22,    // times[j]
+  kTrjInvDt = 23,   // 1 / (times[j+1] - times[j])
+  kTrjStride = 24,
+  kTrjSegments = 64 // LDS columns per field (LFX_MAX_TRAJECTORY_KNOTS - 1 = 63 are used)
+};
+
+struct TrajectoryArgs
+{
+  const uint32_t * scan_begin, * scan_info;
+  const uint32_t * seg_begin;           // [scans of the launch + 1]: scan y's rows are seg_begin[y] .. seg_begin[y + 1] - 1
+  const double * table;                 // [segments of the launch][kTrjStride]
+  const float4 * edge_in, * surf_in;    // (may be the outputs: in place)
+  const uint32_t * edge_idx, * surf_idx;
+  float4 * edge_out, * surf_out;
+  const uint8_t * pts;                  // the batch's input records (a field source only)
+  uint32_t step, off, be;
+  uint32_t first;                       // the launch covers scans first .. first + gridDim.y - 1
+  double scale;                         // seconds per unit of the time field
+};
+
+// grid and walk as deskew_kernel's.  The scan's table is staged in LDS once per workgroup, ahead of the loop and of any
+// store, FIELD-major [kTrjStride][kTrjSegments]: a 64-bit LDS read banks on (address / 4) mod 64 within 32 lanes, so lanes
+// of one segment broadcast and lanes of different segments fall on different banks (a segment-major row of 192 bytes would
+// put every segment on one of four offsets).  The segment comes from a fixed six-step search over the knot times in LDS
+// whose predicate is exactly times[k] <= t.  No atomics.
+template<int SRC>
+__global__ __launch_bounds__(kDeskewThreads) void deskew_trajectory_kernel(const TrajectoryArgs A)
+{
+  __shared__ double seg[kTrjStride * kTrjSegments];
+  const uint32_t s = A.first + blockIdx.y;
+  const uint32_t ne = A.scan_info[s * 4 + kInfoEdge], ns = A.scan_info[s * 4 + kInfoSurface];
+  if (blockIdx.x * blockDim.x >= ne + ns) {return;}      // (the whole workgroup: nothing to stage for)
+  const uint32_t b0 = A.scan_begin[s], n = A.scan_begin[s + 1] - b0;
+  const size_t b = b0;
+  const uint32_t g0 = A.seg_begin[blockIdx.y];
+  const uint32_t nseg = min(A.seg_begin[blockIdx.y + 1] - g0, (uint32_t)kTrjSegments - 1u);   // (the host refuses more)
+  const double * __restrict__ T = A.table + (size_t)g0 * kTrjStride;
+  for (uint32_t i = threadIdx.x; i < nseg * kTrjStride; i += blockDim.x) {
+    const uint32_t j = i / kTrjStride, f = i - j * kTrjStride;
+    seg[f * kTrjSegments + j] = T[i];
+  }
+  __syncthreads();
+  const double * times = seg + kTrjTime * kTrjSegments;
+  const double dn = (double)n;
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < ne + ns; k += gridDim.x * blockDim.x) {
+    const bool edge = k < ne;
+    const uint32_t q = edge ? k : k - ne;
+    const float4 rec = (edge ? A.edge_in : A.surf_in)[b + q];
+    const uint32_t idx = (edge ? A.edge_idx : A.surf_idx)[b + q];
+    double t;
+    if (SRC == kDskFromIndex) {
+      t = (double)idx / dn;
+    } else if (idx >= n) {
+      t = __builtin_nan("");            // (no record of the scan: nothing is read, the record is copied)
+    } else {
+      const uint8_t * f = A.pts + (b + idx) * A.step + A.off;
+      double value;
+      if (SRC == kDskF64) {
+        uint64_t u = *reinterpret_cast<const uint64_t *>(f);
+        if (A.be) {u = __builtin_bswap64(u);}
+        value = __longlong_as_double((long long)u);
+      } else {
+        uint32_t u = *reinterpret_cast<const uint32_t *>(f);
+        if (A.be) {u = __builtin_bswap32(u);}
+        value = SRC == kDskF32 ? (double)__uint_as_float(u) : (double)u;
+      }
+      t = value * A.scale;
+    }
+    // knots with times[k] <= t among the segments' start times (the last knot never starts a segment); a NaN counts none
+    uint32_t pos = 0;
+#pragma unroll
+    for (uint32_t step = kTrjSegments / 2; step; step >>= 1) {
+      const uint32_t cand = pos + step;             // (at most 63: times[cand - 1] lies inside the array)
+      const double tk = times[cand - 1];
+      pos = ((cand <= nseg) & (tk <= t)) ? cand : pos;
+    }
+    const uint32_t j = (pos ? pos : 1u) - 1u;
+    const double beta = (t - times[j]) * seg[kTrjInvDt * kTrjSegments + j];
+    float4 out = rec;
+    if (isfinite(beta)) {
+      auto F = [&](int f) {return seg[f * kTrjSegments + j];};
+      const double px = (double)rec.x, py = (double)rec.y, pz = (double)rec.z;
+      const double theta = F(kTrjTheta);
+      double rx, ry, rz;
+      if (theta < 1e-8) {               // (per segment: the lanes diverge here)
+        const double wx = F(kTrjW), wy = F(kTrjW + 1), wz = F(kTrjW + 2);
+        rx = px + beta * (wy * pz - wz * py);
+        ry = py + beta * (wz * px - wx * pz);
+        rz = pz + beta * (wx * py - wy * px);
+      } else {
+        const double kx = F(kTrjK), ky = F(kTrjK + 1), kz = F(kTrjK + 2);
+        const double a = beta * theta, c = cos(a), sn = sin(a);
+        const double cx = ky * pz - kz * py, cy = kz * px - kx * pz, cz = kx * py - ky * px;
+        const double kdp = (kx * px + ky * py) + kz * pz, g = kdp * (1.0 - c);
+        rx = (px * c + cx * sn) + kx * g;
+        ry = (py * c + cy * sn) + ky * g;
+        rz = (pz * c + cz * sn) + kz * g;
+      }
+      out.x = (float)(((F(kTrjA + 0) * rx + F(kTrjA + 1) * ry) + F(kTrjA + 2) * rz) + (F(kTrjQ + 0) + beta * F(kTrjDq + 0)));
+      out.y = (float)(((F(kTrjA + 3) * rx + F(kTrjA + 4) * ry) + F(kTrjA + 5) * rz) + (F(kTrjQ + 1) + beta * F(kTrjDq + 1)));
+      out.z = (float)(((F(kTrjA + 6) * rx + F(kTrjA + 7) * ry) + F(kTrjA + 8) * rz) + (F(kTrjQ + 2) + beta * F(kTrjDq + 2)));
+    }
+    (edge ? A.edge_out : A.surf_out)[b + q] = out;
+  }
+}
+
 }  // namespace lfx

@@ -423,6 +423,46 @@ int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_
   return LFX_OK;
 }
 
+// lfx_odometry_update_batch_deskewed with the caller's trajectories in place of the prediction.  Every trajectory is checked
+// before the first scan is touched: a refusal leaves the store as it was.
+int lfx_odometry_update_batch_trajectory(lfx_ctx * c, lfx_odometry * o, const lfx_time_field * time, const lfx_trajectory * trajectories,
+  uint32_t n_scans, lfx_odometry_result * results, void * stream)
+{
+  if (!c || !o || !results || !time || !trajectories) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
+  if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
+  const int rt = check_trajectories(c, trajectories, n_scans);
+  if (rt != LFX_OK) {return rt;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t batch = c->last_batch;
+  const size_t total = c->h_scan_begin[batch];
+  if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
+  }
+  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
+  uint32_t * info = pinned_words(o) + kPinInfo;
+  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
+  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
+  for (uint32_t s = 0; s < batch; s++) {
+    int rc = deskew_scans_trajectory(c, time, trajectories + s, s, 1, o->dsk_edge.p, o->dsk_surface.p, st);
+    if (rc != LFX_OK) {return rc;}
+    const uint32_t b = c->h_scan_begin[s];
+    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
+      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
+    if (rc != LFX_OK) {return rc;}
+    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
+  }
+  o->reports = reports;
+  return LFX_OK;
+}
+
 int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, uint32_t n_edge, const float * surface,
   uint32_t n_surface, lfx_odometry_result * result, void * stream)
 {

@@ -3,6 +3,7 @@
 // under AddressSanitizer and UndefinedBehaviorSanitizer.
 #include "../../include/lfx.h"
 
+#include <algorithm>
 #include <cctype>
 #include <cerrno>
 #include <cmath>
@@ -477,12 +478,9 @@ int lfx_motion_twist(const double motion[12], double w[3], double * theta)
   return LFX_OK;
 }
 
-int lfx_motion_scale(const double motion[12], double ratio, double out[12])
+// the rotation of the angle-axis vector ratio * w (theta = |w|) into res's 3 x 3, as the de-skew kernels form it
+static void rotation_of(const double w[3], double theta, double ratio, double res[12])
 {
-  if (!motion || !out) {return LFX_ERR_INVALID_ARGUMENT;}
-  double w[3], theta;
-  lfx_motion_twist(motion, w, &theta);
-  double res[12];                                     // (out may be motion)
   if (theta < 1e-8) {
     const double x = ratio * w[0], y = ratio * w[1], z = ratio * w[2];
     const double r[9] = {1.0, 0.0 - z, y, z, 1.0, 0.0 - x, 0.0 - y, x, 1.0};   // (0 - 0: no negative zero for the identity)
@@ -495,8 +493,115 @@ int lfx_motion_scale(const double motion[12], double ratio, double out[12])
       for (int j = 0; j < 3; j++) {res[4 * i + j] = ((i == j ? c : 0.0) + hat[3 * i + j] * s) + k[i] * (k[j] * v);}
     }
   }
+}
+
+int lfx_motion_scale(const double motion[12], double ratio, double out[12])
+{
+  if (!motion || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  double w[3], theta;
+  lfx_motion_twist(motion, w, &theta);
+  double res[12];                                     // (out may be motion)
+  rotation_of(w, theta, ratio, res);
   for (int i = 0; i < 3; i++) {res[4 * i + 3] = ratio * motion[4 * i + 3];}
   std::memcpy(out, res, sizeof(res));
+  return LFX_OK;
+}
+
+// The trajectories of the de-skew section (include/lfx.h): the segment table of one, knots from gyro samples.
+namespace
+{
+bool finite_run(const double * v, size_t n)
+{
+  for (size_t i = 0; i < n; i++) {
+    if (!std::isfinite(v[i])) {return false;}
+  }
+  return true;
+}
+
+bool ascending_times(const double * t, uint32_t n)
+{
+  if (!finite_run(t, n)) {return false;}
+  for (uint32_t i = 1; i < n; i++) {
+    if (!(t[i] > t[i - 1])) {return false;}
+  }
+  return true;
+}
+
+// the rotation of pose a times that of b, every sum (a0 b0 + a1 b1) + a2 b2, into out's 3 x 3
+void rotate(const double a[12], const double b[12], double out[12])
+{
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) {out[4 * r + c] = (a[4 * r] * b[c] + a[4 * r + 1] * b[4 + c]) + a[4 * r + 2] * b[8 + c];}
+  }
+}
+}  // namespace
+
+int lfx_trajectory_segments(const lfx_trajectory * tr, double * segments_out)
+{
+  if (!tr || !segments_out || !tr->times || !tr->poses) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint32_t n = tr->n_knots;
+  if (n < 2u || n > LFX_MAX_TRAJECTORY_KNOTS) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!ascending_times(tr->times, n) || !finite_run(tr->poses, 12 * (size_t)n) || !std::isfinite(tr->t_ref)) {return LFX_ERR_INVALID_ARGUMENT;}
+  const double * t = tr->times, * P = tr->poses;
+  // the reference pose: a knot's own where t_ref is a knot time, else the model's at t_ref
+  double ref[12];
+  uint32_t at = 0;                                    // knots with times[k] <= t_ref
+  while (at < n && t[at] <= tr->t_ref) {at++;}
+  if (at > 0u && t[at - 1] == tr->t_ref) {
+    std::memcpy(ref, P + 12 * (size_t)(at - 1), sizeof(ref));
+  } else {
+    const uint32_t j = std::min(std::max(at, 1u) - 1u, n - 2u);
+    const double * a = P + 12 * (size_t)j, * b = a + 12;
+    const double beta = (tr->t_ref - t[j]) * (1.0 / (t[j + 1] - t[j]));
+    double D[12], S[12];
+    lfx_motion_between(a, b, D);
+    lfx_motion_scale(D, beta, S);
+    rotate(a, S, ref);
+    for (int i = 0; i < 3; i++) {ref[4 * i + 3] = a[4 * i + 3] + beta * (b[4 * i + 3] - a[4 * i + 3]);}
+  }
+  double Q[2][12];                                    // Q_j and Q_{j+1}, swapped as the segments go by
+  lfx_motion_between(ref, P, Q[0]);
+  for (uint32_t j = 0; j + 1 < n; j++) {
+    const double * q0 = Q[j & 1u];
+    double * q1 = Q[(j + 1u) & 1u], * T = segments_out + (size_t)LFX_TRAJECTORY_SEGMENT_DOUBLES * j;
+    lfx_motion_between(ref, P + 12 * (size_t)(j + 1), q1);
+    double D[12], w[3], theta;
+    lfx_motion_between(q0, q1, D);
+    lfx_motion_twist(D, w, &theta);
+    for (int a = 0; a < 3; a++) {
+      T[a] = theta < 1e-8 ? 0.0 : w[a] / theta;
+      T[4 + a] = w[a];
+      for (int c = 0; c < 3; c++) {T[7 + 3 * a + c] = q0[4 * a + c];}
+      T[16 + a] = q0[4 * a + 3];
+      T[19 + a] = q1[4 * a + 3] - q0[4 * a + 3];
+    }
+    T[3] = theta;
+    T[22] = t[j];
+    T[23] = 1.0 / (t[j + 1] - t[j]);
+  }
+  return LFX_OK;
+}
+
+int lfx_trajectory_from_gyro(const double * times, const double * rates, uint32_t n, const double bias[3], const double velocity[3],
+  double * poses_out)
+{
+  if (!times || !rates || !poses_out || n < 2u) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!ascending_times(times, n) || !finite_run(rates, 3 * (size_t)n)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if ((bias && !finite_run(bias, 3)) || (velocity && !finite_run(velocity, 3))) {return LFX_ERR_INVALID_ARGUMENT;}
+  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  std::memcpy(poses_out, identity, sizeof(identity));
+  for (uint32_t j = 0; j + 1 < n; j++) {
+    const double * r0 = rates + 3 * (size_t)j, * r1 = r0 + 3, * a = poses_out + 12 * (size_t)j;
+    double * b = poses_out + 12 * (size_t)(j + 1), phi[3], E[12];
+    const double dt = times[j + 1] - times[j];
+    for (int i = 0; i < 3; i++) {
+      const double bi = bias ? bias[i] : 0.0;
+      phi[i] = (0.5 * ((r0[i] - bi) + (r1[i] - bi))) * dt;
+    }
+    rotation_of(phi, std::sqrt((phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2]), 1.0, E);
+    rotate(a, E, b);
+    for (int i = 0; i < 3; i++) {b[4 * i + 3] = velocity ? velocity[i] * (times[j + 1] - times[0]) : 0.0;}
+  }
   return LFX_OK;
 }
 

@@ -403,6 +403,17 @@ class FeatureExtraction:
             self._ctx, C.byref(tf), sw, n, _deskew_to(to), C.c_void_p(int(e) or None), C.c_void_p(int(s) or None),
             C.c_void_p(int(stream))), self._L)
 
+    def deskew_trajectory(self, time, trajectories, out=None, stream=0):
+        """lfx_deskew_batch_trajectory: deskew() along the sensor's poses within each sweep.  trajectories: one per scan,
+        (times [k], poses [k][3][4], t_ref) or a dict with those names: the sensor's pose, in one fixed frame, at 2 .. 64
+        strictly ascending times (seconds with a time field, fractions of the sweep with index times); the records are
+        brought to the sensor frame at t_ref.  time, out, stream: as deskew() takes them."""
+        tf = _time_field(time)
+        tr, n, _keep = _trajectories(trajectories)
+        e, s = (0, 0) if out is None else out
+        B.check(self._ctx, self._L.lfx_deskew_batch_trajectory(
+            self._ctx, C.byref(tf), tr, n, C.c_void_p(int(e) or None), C.c_void_p(int(s) or None), C.c_void_p(int(stream))), self._L)
+
     def download(self, scan, stream=0):
         r = B.ScanResult()
         B.check(self._ctx, self._L.lfx_download_scan(self._ctx, scan, C.c_void_p(int(stream)), C.byref(r)), self._L)
@@ -529,6 +540,21 @@ def _sweeps(sweeps):
     return out, len(sweeps)
 
 
+def _trajectories(trajectories):
+    """(lfx_trajectory array, count, the arrays it points into: the caller keeps them alive over the call)."""
+    out = (B.Trajectory * max(len(trajectories), 1))()
+    keep = []
+    for i, tr in enumerate(trajectories):
+        times, poses, t_ref = (tr["times"], tr["poses"], tr["t_ref"]) if isinstance(tr, dict) else tr
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if len(p) != 12 * len(t):
+            raise ValueError("trajectory %d: %d times but %d pose values" % (i, len(t), len(p)))
+        keep += [t, p]
+        out[i].n_knots, out[i].times, out[i].poses, out[i].t_ref = len(t), _pd(t), _pd(p), float(t_ref)
+    return out, len(trajectories), keep
+
+
 def time_field_from_fields(fields, point_step, is_bigendian=False):
     """lfx_time_field_from_fields: the per-point time channel of a PointCloud2 field list (iterable of (name, offset,
     datatype, count)) -> binding.TimeField for deskew(): the first field named t, time, timestamp, time_stamp or
@@ -574,6 +600,32 @@ def motion_scale(motion, ratio):
     if B.load().lfx_motion_scale(_pd(m), float(ratio), _pd(out)) != 0:
         raise B.LfxError(-1, "invalid argument")
     return out.reshape(3, 4)
+
+
+def trajectory_segments(times, poses, t_ref):
+    """lfx_trajectory_segments: the table the trajectory de-skew kernel is given, [n_knots - 1][24] doubles (include/lfx.h
+    names the columns).  Raises LfxError where lfx_deskew_batch_trajectory would refuse the trajectory.  No device."""
+    tr, _, _keep = _trajectories([(times, poses, t_ref)])
+    n = int(tr[0].n_knots)
+    out = np.zeros((max(n, 2) - 1, B.TRAJECTORY_SEGMENT_DOUBLES), np.float64)
+    if n > B.MAX_TRAJECTORY_KNOTS or B.load().lfx_trajectory_segments(tr, _pd(out)) != 0:
+        raise B.LfxError(-1, "invalid trajectory")
+    return out
+
+
+def trajectory_from_gyro(times, rates, bias=None, velocity=None):
+    """lfx_trajectory_from_gyro: knot poses [n][3][4] from gyro samples (rates [n][3] rad/s in the sensor frame at times [n]),
+    the first pose the identity; bias [3] is taken off the rates, velocity [3] is constant in the first sample's frame.  No device."""
+    t = np.ascontiguousarray(times, np.float64).reshape(-1)
+    r = np.ascontiguousarray(rates, np.float64).reshape(-1)
+    if len(r) != 3 * len(t):
+        raise ValueError("%d times but %d rate values" % (len(t), len(r)))
+    b = None if bias is None else np.ascontiguousarray(bias, np.float64).reshape(3)
+    v = None if velocity is None else np.ascontiguousarray(velocity, np.float64).reshape(3)
+    out = np.zeros((max(len(t), 1), 3, 4), np.float64)
+    if B.load().lfx_trajectory_from_gyro(_pd(t), _pd(r), len(t), None if b is None else _pd(b), None if v is None else _pd(v), _pd(out)) != 0:
+        raise B.LfxError(-1, "invalid gyro samples")
+    return out
 
 
 def _msg_buffer():
@@ -760,6 +812,18 @@ class Odometry:
         B.check(self._fx._ctx, self._L.lfx_odometry_update_batch_deskewed(
             self._fx._ctx, self.handle, C.byref(tf), None if st is None else _pd(st), float(sweep_ratio), _deskew_to(to), n, res,
             C.c_void_p(int(stream))))
+        return self._results(res[:n])
+
+    def update_batch_trajectory(self, time, trajectories, n_scans=None, stream=0):
+        """lfx_odometry_update_batch_trajectory: update_batch with every scan de-skewed along the caller's trajectory of it
+        (FeatureExtraction.deskew_trajectory's arguments) before it is aligned and added.  The batch's clouds in the context
+        stay raw."""
+        tf = _time_field(time)
+        tr, n_tr, _keep = _trajectories(trajectories)
+        n = int(n_tr if n_scans is None else n_scans)
+        res = (B.OdometryResult * max(n, 1))()
+        B.check(self._fx._ctx, self._L.lfx_odometry_update_batch_trajectory(
+            self._fx._ctx, self.handle, C.byref(tf), tr, n, res, C.c_void_p(int(stream))))
         return self._results(res[:n])
 
     def update(self, d_edge, n_edge, d_surface, n_surface, stream=0):

@@ -154,30 +154,14 @@ def _log_so3(R):
     return np.zeros(3) if s < 1e-300 else v * (th / (2.0 * s))
 
 
-def make_sweep(rings=16, cols=900, seed=1234, pose0=None, motion=None, sigma=0.01, vfov_deg=15.0, n_pillars=14,
-               t0=0.0, period=0.1, ceiling=3.0):
-    """One sweep of a sensor that MOVES while it fires: point i (column-major, i = column * rings + ring) is measured at
-    alpha = i / n of the sweep, from the pose P0 M(alpha), M(alpha) = [Exp(alpha w) | alpha v] with [Exp(w) | v] = motion
-    (the sensor frame at the sweep's end in its frame at the start: LOAM's model, include/lfx.h's de-skew section).  Rays
-    are cast in 3-D in a closed box room (make_scan's 20 m x 12 m walls, the floor at z = 0, a ceiling) with make_scan's
-    vertical pillars, Gaussian noise of sigma along the ray; every point is given in the sensor frame of its own time.
-
-    pose0   the sensor's world pose at the start, 3 x 4 [R | t]; None: make_scan's usual place, 1.8 m over the floor
-    motion  3 x 4; None: the identity (a static scan)
-    Returns (records, world, alpha): POINT_DTYPE records (the point's time t0 + alpha * period also as a float32 at byte 24,
-    in the record's padding), the measured points in the world [n, 3] float64, alpha [n] float64."""
-    rng = np.random.Generator(np.random.PCG64(seed))
+def _cast_sweep(rng, rings, cols, Rm, o, sigma, vfov_deg, n_pillars, ceiling):
+    """make_sweep's room seen from the world rotations Rm [n, 3, 3] and positions o [n, 3] of the sensor at every point's
+    time: (records without a time, the measured points in the world)."""
     n = rings * cols
-    P0 = np.array([[1, 0, 0, 1.3], [0, 1, 0, -0.7], [0, 0, 1, 1.8]], np.float64) if pose0 is None else np.asarray(pose0, np.float64).reshape(3, 4)
-    D = np.eye(4)[:3] if motion is None else np.asarray(motion, np.float64).reshape(3, 4)
-    w, v = _log_so3(D[:, :3]), D[:, 3]
-    alpha = np.arange(n, dtype=np.float64) / n
     col, ring = np.arange(n) // rings, np.arange(n) % rings
     az = -np.pi + 2.0 * np.pi * (col + 0.5) / cols
     el = np.deg2rad(np.linspace(-vfov_deg, vfov_deg, rings))[ring]
     d_s = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)     # unit rays, sensor frame
-    Rm = P0[:, :3] @ _exp_so3(alpha[:, None] * w[None, :])                                       # world rotation at alpha
-    o = (alpha[:, None] * v[None, :]) @ P0[:, :3].T + P0[:, 3]                                  # world position at alpha
     d = np.einsum("nij,nj->ni", Rm, d_s)
     lo, hi = np.array([-10.0, -6.0, 0.0]), np.array([10.0, 6.0, float(ceiling)])
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -202,8 +186,74 @@ def make_sweep(rings=16, cols=900, seed=1234, pose0=None, motion=None, sigma=0.0
     pts["pad"] = 1.0
     pts["intensity"] = rng.uniform(0.0, 255.0, n).astype(np.float32)
     pts["ring"] = ring.astype(np.uint16)
+    return pts, o + t[:, None] * d
+
+
+def make_sweep(rings=16, cols=900, seed=1234, pose0=None, motion=None, sigma=0.01, vfov_deg=15.0, n_pillars=14,
+               t0=0.0, period=0.1, ceiling=3.0):
+    """One sweep of a sensor that MOVES while it fires: point i (column-major, i = column * rings + ring) is measured at
+    alpha = i / n of the sweep, from the pose P0 M(alpha), M(alpha) = [Exp(alpha w) | alpha v] with [Exp(w) | v] = motion
+    (the sensor frame at the sweep's end in its frame at the start: LOAM's model, include/lfx.h's de-skew section).  Rays
+    are cast in 3-D in a closed box room (make_scan's 20 m x 12 m walls, the floor at z = 0, a ceiling) with make_scan's
+    vertical pillars, Gaussian noise of sigma along the ray; every point is given in the sensor frame of its own time.
+
+    pose0   the sensor's world pose at the start, 3 x 4 [R | t]; None: make_scan's usual place, 1.8 m over the floor
+    motion  3 x 4; None: the identity (a static scan)
+    Returns (records, world, alpha): POINT_DTYPE records (the point's time t0 + alpha * period also as a float32 at byte 24,
+    in the record's padding), the measured points in the world [n, 3] float64, alpha [n] float64."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = rings * cols
+    P0 = np.array([[1, 0, 0, 1.3], [0, 1, 0, -0.7], [0, 0, 1, 1.8]], np.float64) if pose0 is None else np.asarray(pose0, np.float64).reshape(3, 4)
+    D = np.eye(4)[:3] if motion is None else np.asarray(motion, np.float64).reshape(3, 4)
+    w, v = _log_so3(D[:, :3]), D[:, 3]
+    alpha = np.arange(n, dtype=np.float64) / n
+    Rm = P0[:, :3] @ _exp_so3(alpha[:, None] * w[None, :])                                       # world rotation at alpha
+    o = (alpha[:, None] * v[None, :]) @ P0[:, :3].T + P0[:, 3]                                  # world position at alpha
+    pts, world = _cast_sweep(rng, rings, cols, Rm, o, sigma, vfov_deg, n_pillars, ceiling)
     pts.view(np.uint8).reshape(n, POINT_DTYPE.itemsize)[:, 24:28] = (t0 + alpha * period).astype("<f4").view(np.uint8).reshape(n, 4)
-    return np.ascontiguousarray(pts), o + t[:, None] * d, alpha
+    return np.ascontiguousarray(pts), world, alpha
+
+
+def trajectory_poses(times, poses, t):
+    """The sensor's pose at every time of t [n] along a trajectory (include/lfx.h, the de-skew section): between knots j and
+    j + 1 the rotation along the geodesic, the position along the straight line; j = clamp(#{times[k] <= t} - 1, 0, k - 2),
+    so the first and the last segment extrapolate.  Returns (R [n, 3, 3], p [n, 3])."""
+    times = np.asarray(times, np.float64).reshape(-1)
+    P = np.asarray(poses, np.float64).reshape(-1, 3, 4)
+    t = np.asarray(t, np.float64).reshape(-1)
+    j = np.clip(np.searchsorted(times[:-1], t, side="right") - 1, 0, len(times) - 2)
+    beta = (t - times[j]) * (1.0 / (times[j + 1] - times[j]))
+    w = np.stack([_log_so3(P[k, :, :3].T @ P[k + 1, :, :3]) for k in range(len(times) - 1)])
+    R = P[j, :, :3] @ _exp_so3(beta[:, None] * w[j])
+    p = P[j, :, 3] + beta[:, None] * (P[j + 1, :, 3] - P[j, :, 3])
+    return R, p
+
+
+def make_sweep_trajectory(rings=16, cols=900, seed=1234, times=(0.0, 1.0), poses=None, t0=None, period=None, time_dtype="f32",
+                          sigma=0.01, vfov_deg=15.0, n_pillars=14, ceiling=3.0):
+    """make_sweep with the sensor's pose at a point's time taken from a trajectory (trajectory_poses): point i is measured
+    at t0 + (i / n) * period (default: from the first knot's time over the span of the knots), from the world pose the knots
+    times [k], poses [k][3][4] give for that time.
+
+    time_dtype  "f32": the point's time as a float32 at byte 24, as make_sweep stores it; "f64": as a double at bytes 24 - 31
+                (a knot time can then be stored exactly)
+    Returns (records, world, t): POINT_DTYPE records, the measured points in the world [n, 3] float64, the times [n] float64."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = rings * cols
+    times = np.asarray(times, np.float64).reshape(-1)
+    t0 = times[0] if t0 is None else float(t0)
+    period = times[-1] - times[0] if period is None else float(period)
+    t = t0 + (np.arange(n, dtype=np.float64) / n) * period
+    Rm, o = trajectory_poses(times, poses, t)
+    pts, world = _cast_sweep(rng, rings, cols, Rm, o, sigma, vfov_deg, n_pillars, ceiling)
+    raw = pts.view(np.uint8).reshape(n, POINT_DTYPE.itemsize)
+    if time_dtype == "f64":
+        raw[:, 24:32] = t.astype("<f8").view(np.uint8).reshape(n, 8)
+    elif time_dtype == "f32":
+        raw[:, 24:28] = t.astype("<f4").view(np.uint8).reshape(n, 4)
+    else:
+        raise ValueError("time_dtype must be 'f32' or 'f64'")
+    return np.ascontiguousarray(pts), world, t
 
 
 def concat(clouds):
