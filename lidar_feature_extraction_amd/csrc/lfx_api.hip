@@ -1128,11 +1128,8 @@ void lfx_destroy(lfx_ctx * c)
   if (c->copy_stream) {(void)hipStreamSynchronize(c->copy_stream);}
   for (auto & sp : c->spans) {(void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b);}
   for (auto & ev : c->free_events) {(void)hipEventDestroy(ev);}
-  for (auto & ev : c->deskew_copied) {
-    if (ev) {(void)hipEventSynchronize(ev); (void)hipEventDestroy(ev);}
-  }
-  for (auto & ts : c->trajectory_slots) {
-    if (ts.used) {(void)hipEventSynchronize(ts.used); (void)hipEventDestroy(ts.used);}
+  for (auto & ds : c->deskew_slots) {
+    if (ds.used) {(void)hipEventSynchronize(ds.used); (void)hipEventDestroy(ds.used);}
   }
   for (auto & sl : c->slots) {
     if (sl.uploaded) {(void)hipEventDestroy(sl.uploaded);}

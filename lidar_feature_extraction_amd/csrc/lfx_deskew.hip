@@ -1,7 +1,8 @@
 // lfx_deskew.hip -- lfx_deskew_batch, lfx_deskew_batch_trajectory: the sensor's motion during a sweep taken out of the last
 // device batch's feature clouds (include/lfx.h, the de-skew section; lfx_kernels_deskew.hpp).  The per-scan constants (per
-// segment, along a trajectory) are worked out here, on the host, by the helpers of lfx_pcd.cpp and travel as one table of
-// doubles per call.
+// segment, along a trajectory) are worked out here, on the host, by the pose arithmetic of lfx_pose.cpp, and travel as one
+// table of doubles per call (lfx_deskew_rows.hpp).  Both calls share their checks, the ring of slots the tables go out
+// through and the launch; each writes its own rows.
 #include "lfx_internal.hpp"
 #include "lfx_kernels_deskew.hpp"
 
@@ -9,14 +10,6 @@ using namespace lfx_host;
 
 namespace
 {
-bool finite_all(const double * v, int n)
-{
-  for (int i = 0; i < n; i++) {
-    if (!std::isfinite(v[i])) {return false;}
-  }
-  return true;
-}
-
 // where a record's firing time comes from: the kernels' template parameter, or what lfx_deskew_batch refuses about `time`
 int time_source(lfx_ctx * c, const lfx_time_field * time, int & src)
 {
@@ -38,16 +31,69 @@ int time_source(lfx_ctx * c, const lfx_time_field * time, int & src)
   return LFX_OK;
 }
 
-template<int SRC>
-void launch(dim3 grid, hipStream_t st, const lfx::DeskewArgs & a)
+// What both calls refuse about the batch, the range of scans, the outputs and `time`, and the source of the times.
+// `motions`: the sweeps or the trajectories, named by `required`; a call without a `to` passes a valid one.
+int check_call(lfx_ctx * c, const lfx_time_field * time, const void * motions, const char * required, uint32_t first, uint32_t n, int to,
+  const float4 * edge_out, const float4 * surf_out, int & src)
 {
-  hipLaunchKernelGGL(lfx::deskew_kernel<SRC>, grid, dim3(lfx::kDeskewThreads), 0, st, a);
+  if (!time || !motions) {return fail(c, LFX_ERR_INVALID_ARGUMENT, required);}
+  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
+  if (n == 0 || first >= c->last_batch || n > c->last_batch - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "scans outside the last batch");}
+  if (to != LFX_DESKEW_TO_START && to != LFX_DESKEW_TO_END) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "to must be LFX_DESKEW_TO_START or LFX_DESKEW_TO_END");}
+  if (!edge_out || !surf_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "both outputs, or neither (in place)");}
+  return time_source(c, time, src);
 }
 
-template<int SRC>
-void launch_trajectory(dim3 grid, hipStream_t st, const lfx::TrajectoryArgs & a)
+// The ring's next slot with room for `doubles` on both sides, the kernel that read it last (kDeskewSlots calls ago, on
+// whichever stream: long done) waited for.  Without the memory: LFX_ERR_OUT_OF_MEMORY, the runtime's word for it as the
+// error text, for the caller to put its own in front of.  A failure leaves the slot valid, with an event and what memory it
+// had or none, and the ring where it was.
+int take_slot(lfx_ctx * c, size_t doubles, lfx_ctx::DeskewSlot *& slot)
 {
-  hipLaunchKernelGGL(lfx::deskew_trajectory_kernel<SRC>, grid, dim3(lfx::kDeskewThreads), 0, st, a);
+  LFX_HIP(c, hipSetDevice(c->device));
+  slot = &c->deskew_slots[c->deskew_next];
+  if (!slot->used) {LFX_HIP(c, hipEventCreateWithFlags(&slot->used, hipEventDisableTiming));}
+  LFX_HIP(c, hipEventSynchronize(slot->used));
+  hipError_t e = slot->h.reserve(sizeof(double) * doubles);
+  if (e == hipSuccess) {e = hold(slot->d, doubles);}
+  if (e != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, hipGetErrorString(e));}
+  c->deskew_next = (c->deskew_next + 1u) % lfx_ctx::kDeskewSlots;
+  return LFX_OK;
+}
+
+lfx::DeskewRecords records_of(const lfx_ctx * c, const lfx_time_field * time, const double * table, uint32_t first, float4 * edge_out,
+  float4 * surf_out)
+{
+  lfx::DeskewRecords r{};
+  r.scan_begin = c->scan_begin.p; r.scan_info = c->scan_info.p; r.table = table;
+  r.edge_in = c->edge_pts.p; r.surf_in = c->surf_pts.p; r.edge_idx = c->edge_idx.p; r.surf_idx = c->surf_idx.p;
+  r.edge_out = edge_out; r.surf_out = surf_out;
+  r.pts = static_cast<const uint8_t *>(c->last_points);
+  r.step = c->layout.step; r.off = time->offset; r.be = time->big_endian ? 1u : 0u;
+  r.first = first;
+  return r;
+}
+
+// a kernel's four forms, by the source of the times
+template<typename Args>
+using Forms = void (*[4])(Args);
+static_assert(lfx::kDskFromIndex == 0 && lfx::kDskF32 == 1 && lfx::kDskF64 == 2 && lfx::kDskU32 == 3, "the order of a kernel's forms");
+const Forms<lfx::DeskewArgs> kConstantForms = {lfx::deskew_kernel<0>, lfx::deskew_kernel<1>, lfx::deskew_kernel<2>, lfx::deskew_kernel<3>};
+const Forms<lfx::TrajectoryArgs> kTrajectoryForms = {lfx::deskew_trajectory_kernel<0>, lfx::deskew_trajectory_kernel<1>,
+  lfx::deskew_trajectory_kernel<2>, lfx::deskew_trajectory_kernel<3>};
+
+// The slot's pinned block out to its device table, the kernel over n scans behind it, the slot's event behind the kernel:
+// the event guards the device table as well as the pinned block.
+template<typename Args>
+int launch(lfx_ctx * c, const Forms<Args> & forms, int src, uint32_t n, const Args & a, lfx_ctx::DeskewSlot & slot, size_t doubles, hipStream_t st)
+{
+  LFX_HIP(c, hipMemcpyAsync(slot.d.p, slot.h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
+  // (a scan of 64 x 1800 has about 14 k feature records: 8 workgroups walk them in 7 steps; a few scans get more)
+  const dim3 grid(n >= 32u ? 8u : 32u, n);
+  hipLaunchKernelGGL(forms[src], grid, dim3(lfx::kDeskewThreads), 0, st, a);
+  LFX_HIP(c, hipGetLastError());
+  LFX_HIP(c, hipEventRecord(slot.used, st));
+  return LFX_OK;
 }
 }  // namespace
 
@@ -59,78 +105,36 @@ namespace lfx_host
 int deskew_scans(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * sweeps, uint32_t first, uint32_t n, int to,
   float4 * edge_out, float4 * surf_out, hipStream_t st)
 {
-  if (!time || !sweeps) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "time and sweeps are required");}
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  if (n == 0 || first >= c->last_batch || n > c->last_batch - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "scans outside the last batch");}
-  if (to != LFX_DESKEW_TO_START && to != LFX_DESKEW_TO_END) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "to must be LFX_DESKEW_TO_START or LFX_DESKEW_TO_END");}
-  if (!edge_out || !surf_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "both outputs, or neither (in place)");}
   int src;
-  const int rt = time_source(c, time, src);
+  const int rt = check_call(c, time, sweeps, "time and sweeps are required", first, n, to, edge_out, surf_out, src);
   if (rt != LFX_OK) {return rt;}
   for (uint32_t s = 0; s < n; s++) {
-    if (!finite_all(sweeps[s].motion, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweeps[" + std::to_string(s) + "].motion is not finite");}
+    if (!lfx::finite_run(sweeps[s].motion, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweeps[" + std::to_string(s) + "].motion is not finite");}
     if (src != lfx::kDskFromIndex) {
       if (!std::isfinite(sweeps[s].t0) || !std::isfinite(sweeps[s].t1)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweeps[" + std::to_string(s) + "]: t0 / t1 not finite");}
       if (sweeps[s].t1 == sweeps[s].t0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweeps[" + std::to_string(s) + "]: t1 == t0");}
     }
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  // the table's blocks: pinned and device, kDeskewSlots of max_batch rows each
-  const size_t rows = std::max(c->max_batch, 1u), block = rows * lfx::kDskStride;
-  if (!c->d_deskew.p) {
-    // all of it or none: a call that fails here leaves nothing half made for the next one to trip over
-    hipError_t e = c->h_deskew.reserve(sizeof(double) * block * lfx_ctx::kDeskewSlots);
-    for (auto & ev : c->deskew_copied) {
-      if (e == hipSuccess && !ev) {e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);}
-    }
-    if (e == hipSuccess) {e = c->d_deskew.alloc(block * lfx_ctx::kDeskewSlots);}
-    if (e != hipSuccess) {
-      for (auto & ev : c->deskew_copied) {
-        if (ev) {(void)hipEventDestroy(ev); ev = nullptr;}
-      }
-      return fail(c, LFX_ERR_OUT_OF_MEMORY, std::string("cannot set up the de-skew table: ") + hipGetErrorString(e));
-    }
-  }
-  const uint32_t slot = c->deskew_next;
-  c->deskew_next = (slot + 1u) % lfx_ctx::kDeskewSlots;
-  LFX_HIP(c, hipEventSynchronize(c->deskew_copied[slot]));     // (the kernel queued eight calls ago, on whichever stream: long done)
-  double * h = reinterpret_cast<double *>(c->h_deskew.p) + slot * block, * d = c->d_deskew.p + slot * block;
+  const size_t doubles = (size_t)n * lfx::kDskStride;
+  lfx_ctx::DeskewSlot * slot;
+  const int rs = take_slot(c, doubles, slot);
+  if (rs != LFX_OK) {return rs == LFX_ERR_OUT_OF_MEMORY ? fail(c, rs, "cannot set up the de-skew table: " + c->err) : rs;}
   for (uint32_t s = 0; s < n; s++) {
     const lfx_sweep & sw = sweeps[s];
-    double * T = h + (size_t)s * lfx::kDskStride, w[3], theta;
+    double * T = reinterpret_cast<double *>(slot->h.p) + (size_t)s * lfx::kDskStride, w[3], theta;
     lfx_motion_twist(sw.motion, w, &theta);
+    lfx::write_twist(T, w, theta);
     for (int a = 0; a < 3; a++) {
-      T[lfx::kDskK + a] = theta < 1e-8 ? 0.0 : w[a] / theta;
-      T[lfx::kDskW + a] = w[a];
       T[lfx::kDskV + a] = sw.motion[4 * a + 3];
       for (int j = 0; j < 3; j++) {T[lfx::kDskR + 3 * a + j] = sw.motion[4 * a + j];}
     }
-    T[lfx::kDskTheta] = theta;
     T[lfx::kDskT0] = src == lfx::kDskFromIndex ? 0.0 : sw.t0;
     T[lfx::kDskInvDt] = src == lfx::kDskFromIndex ? 1.0 : 1.0 / (sw.t1 - sw.t0);
     T[lfx::kDskScale] = src == lfx::kDskFromIndex ? 1.0 : time->scale;
-    T[22] = T[23] = 0.0;
+    T[lfx::kDskScale + 1] = T[lfx::kDskScale + 2] = 0.0;       // (the row's spare doubles)
   }
-  LFX_HIP(c, hipMemcpyAsync(d, h, sizeof(double) * n * lfx::kDskStride, hipMemcpyHostToDevice, st));
-  lfx::DeskewArgs a{};
-  a.scan_begin = c->scan_begin.p; a.scan_info = c->scan_info.p; a.table = d;
-  a.edge_in = c->edge_pts.p; a.surf_in = c->surf_pts.p; a.edge_idx = c->edge_idx.p; a.surf_idx = c->surf_idx.p;
-  a.edge_out = edge_out; a.surf_out = surf_out;
-  a.pts = static_cast<const uint8_t *>(c->last_points);
-  a.step = c->layout.step; a.off = time->offset; a.be = time->big_endian ? 1u : 0u;
-  a.first = first; a.to_end = to == LFX_DESKEW_TO_END ? 1u : 0u;
-  // (a scan of 64 x 1800 has about 14 k feature records: 8 workgroups walk them in 7 steps; a few scans get more)
-  const dim3 grid(n >= 32u ? 8u : 32u, n);
-  switch (src) {
-    case lfx::kDskF32: launch<lfx::kDskF32>(grid, st, a); break;
-    case lfx::kDskF64: launch<lfx::kDskF64>(grid, st, a); break;
-    case lfx::kDskU32: launch<lfx::kDskU32>(grid, st, a); break;
-    default: launch<lfx::kDskFromIndex>(grid, st, a); break;
-  }
-  LFX_HIP(c, hipGetLastError());
-  // behind the kernel, not the copy: the event guards the slot's device table as well as its pinned block
-  LFX_HIP(c, hipEventRecord(c->deskew_copied[slot], st));
-  return LFX_OK;
+  const lfx::DeskewArgs a{records_of(c, time, slot->d.p, first, edge_out, surf_out), to == LFX_DESKEW_TO_END ? 1u : 0u};
+  return launch(c, kConstantForms, src, n, a, *slot, doubles, st);
 }
 
 // What lfx_deskew_batch_trajectory refuses about trajectories[0 .. n - 1] (what lfx_trajectory_segments refuses about each),
@@ -142,9 +146,7 @@ int check_trajectories(lfx_ctx * c, const lfx_trajectory * trajectories, uint32_
     if (tr.n_knots < 2u || tr.n_knots > LFX_MAX_TRAJECTORY_KNOTS || !tr.times || !tr.poses) {
       return fail(c, LFX_ERR_INVALID_ARGUMENT, "trajectories[" + std::to_string(s) + "]: 2 .. 64 knots with times and poses");
     }
-    bool ok = finite_all(tr.times, (int)tr.n_knots) && finite_all(tr.poses, 12 * (int)tr.n_knots) && std::isfinite(tr.t_ref);
-    for (uint32_t k = 1; ok && k < tr.n_knots; k++) {ok = tr.times[k] > tr.times[k - 1];}
-    if (!ok) {
+    if (!lfx::ascending_times(tr.times, tr.n_knots) || !lfx::finite_run(tr.poses, 12 * (size_t)tr.n_knots) || !std::isfinite(tr.t_ref)) {
       return fail(c, LFX_ERR_INVALID_ARGUMENT, "trajectories[" + std::to_string(s) +
                "]: times must be finite and strictly ascending, poses and t_ref finite");
     }
@@ -157,28 +159,20 @@ int check_trajectories(lfx_ctx * c, const lfx_trajectory * trajectories, uint32_
 int deskew_scans_trajectory(lfx_ctx * c, const lfx_time_field * time, const lfx_trajectory * trajectories, uint32_t first, uint32_t n,
   float4 * edge_out, float4 * surf_out, hipStream_t st)
 {
-  if (!time || !trajectories) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "time and trajectories are required");}
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  if (n == 0 || first >= c->last_batch || n > c->last_batch - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "scans outside the last batch");}
-  if (!edge_out || !surf_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "both outputs, or neither (in place)");}
   int src;
-  const int rt = time_source(c, time, src);
+  const int rt = check_call(c, time, trajectories, "time and trajectories are required", first, n, LFX_DESKEW_TO_START, edge_out, surf_out, src);
   if (rt != LFX_OK) {return rt;}
   const int rk = check_trajectories(c, trajectories, n);
   if (rk != LFX_OK) {return rk;}
   size_t segments = 0;
   for (uint32_t s = 0; s < n; s++) {segments += trajectories[s].n_knots - 1u;}
-  LFX_HIP(c, hipSetDevice(c->device));
   // this call's block: the rows of every scan's segments, then where each scan's rows begin
-  lfx_ctx::TrajectorySlot & slot = c->trajectory_slots[c->trajectory_next];
-  const size_t doubles = segments * lfx::kTrjStride + (n + 2u) / 2u;
-  if (!slot.used) {LFX_HIP(c, hipEventCreateWithFlags(&slot.used, hipEventDisableTiming));}
-  LFX_HIP(c, hipEventSynchronize(slot.used));                  // (the kernel queued eight calls ago, on whichever stream: long done)
-  if (slot.h.reserve(sizeof(double) * doubles) != hipSuccess || hold(slot.d, doubles) != hipSuccess) {
-    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot set up the trajectory table");
-  }
-  double * h = reinterpret_cast<double *>(slot.h.p);
-  uint32_t * begin = reinterpret_cast<uint32_t *>(h + segments * lfx::kTrjStride);
+  const size_t rows = segments * lfx::kTrjStride, doubles = rows + (n + 2u) / 2u;
+  lfx_ctx::DeskewSlot * slot;
+  const int rs = take_slot(c, doubles, slot);
+  if (rs != LFX_OK) {return rs == LFX_ERR_OUT_OF_MEMORY ? fail(c, rs, "cannot set up the trajectory table") : rs;}
+  double * h = reinterpret_cast<double *>(slot->h.p);
+  uint32_t * begin = reinterpret_cast<uint32_t *>(h + rows);
   uint32_t at = 0;
   for (uint32_t s = 0; s < n; s++) {
     begin[s] = at;
@@ -188,40 +182,23 @@ int deskew_scans_trajectory(lfx_ctx * c, const lfx_time_field * time, const lfx_
     at += trajectories[s].n_knots - 1u;
   }
   begin[n] = at;
-  c->trajectory_next = (c->trajectory_next + 1u) % lfx_ctx::kDeskewSlots;
-  LFX_HIP(c, hipMemcpyAsync(slot.d.p, h, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
-  lfx::TrajectoryArgs a{};
-  a.scan_begin = c->scan_begin.p; a.scan_info = c->scan_info.p;
-  a.table = slot.d.p; a.seg_begin = reinterpret_cast<const uint32_t *>(slot.d.p + segments * lfx::kTrjStride);
-  a.edge_in = c->edge_pts.p; a.surf_in = c->surf_pts.p; a.edge_idx = c->edge_idx.p; a.surf_idx = c->surf_idx.p;
-  a.edge_out = edge_out; a.surf_out = surf_out;
-  a.pts = static_cast<const uint8_t *>(c->last_points);
-  a.step = c->layout.step; a.off = time->offset; a.be = time->big_endian ? 1u : 0u;
-  a.first = first; a.scale = src == lfx::kDskFromIndex ? 1.0 : time->scale;
-  const dim3 grid(n >= 32u ? 8u : 32u, n);                    // (as deskew_scans)
-  switch (src) {
-    case lfx::kDskF32: launch_trajectory<lfx::kDskF32>(grid, st, a); break;
-    case lfx::kDskF64: launch_trajectory<lfx::kDskF64>(grid, st, a); break;
-    case lfx::kDskU32: launch_trajectory<lfx::kDskU32>(grid, st, a); break;
-    default: launch_trajectory<lfx::kDskFromIndex>(grid, st, a); break;
-  }
-  LFX_HIP(c, hipGetLastError());
-  LFX_HIP(c, hipEventRecord(slot.used, st));                   // behind the kernel: the event guards the device table too
-  return LFX_OK;
+  const lfx::TrajectoryArgs a{reinterpret_cast<const uint32_t *>(slot->d.p + rows), records_of(c, time, slot->d.p, first, edge_out, surf_out),
+    src == lfx::kDskFromIndex ? 1.0 : time->scale};
+  return launch(c, kTrajectoryForms, src, n, a, *slot, doubles, st);
 }
 
 }  // namespace lfx_host
 
 namespace
 {
-// what both batch de-skews check about the batch and the outputs
-int check_batch_outputs(lfx_ctx * c, uint32_t n_scans, const float * d_edge_out, const float * d_surface_out)
+// What both batch calls do around `scans(edge_out, surf_out)`, their de-skew of the whole batch: the checks of the batch and
+// the outputs ahead of it, the in-place mark behind it.
+template<typename Scans>
+int deskew_batch(lfx_ctx * c, uint32_t n_scans, float * d_edge_out, float * d_surface_out, Scans scans)
 {
-  if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
-  if (n_scans != c->last_batch) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_scans (" + std::to_string(n_scans) + ") is not the number of scans of the last batch (" +
-             std::to_string(c->last_batch) + ")");
-  }
+  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
   if ((d_edge_out == nullptr) != (d_surface_out == nullptr)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "both outputs, or neither (in place)");}
   if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
   if (d_edge_out && (d_edge_out == reinterpret_cast<float *>(c->edge_pts.p) || d_surface_out == reinterpret_cast<float *>(c->surf_pts.p) ||
@@ -229,32 +206,25 @@ int check_batch_outputs(lfx_ctx * c, uint32_t n_scans, const float * d_edge_out,
   {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the outputs are the context's own clouds: pass NULL for both to de-skew in place");
   }
-  return LFX_OK;
+  const bool in_place = d_edge_out == nullptr;
+  const int rc = scans(in_place ? c->edge_pts.p : reinterpret_cast<float4 *>(d_edge_out), in_place ? c->surf_pts.p : reinterpret_cast<float4 *>(d_surface_out));
+  if (rc == LFX_OK && in_place) {c->deskewed_in_place = true;}
+  return rc;
 }
 }  // namespace
 
 extern "C" int lfx_deskew_batch_trajectory(lfx_ctx * c, const lfx_time_field * time, const lfx_trajectory * trajectories, uint32_t n_scans,
   float * d_edge_out, float * d_surface_out, void * stream)
 {
-  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
-  const int rb = check_batch_outputs(c, n_scans, d_edge_out, d_surface_out);
-  if (rb != LFX_OK) {return rb;}
-  const bool in_place = d_edge_out == nullptr;
-  const int rc = deskew_scans_trajectory(c, time, trajectories, 0, n_scans, in_place ? c->edge_pts.p : reinterpret_cast<float4 *>(d_edge_out),
-    in_place ? c->surf_pts.p : reinterpret_cast<float4 *>(d_surface_out), static_cast<hipStream_t>(stream));
-  if (rc == LFX_OK && in_place) {c->deskewed_in_place = true;}
-  return rc;
+  return deskew_batch(c, n_scans, d_edge_out, d_surface_out, [&](float4 * edge, float4 * surf) {
+             return deskew_scans_trajectory(c, time, trajectories, 0, n_scans, edge, surf, static_cast<hipStream_t>(stream));
+           });
 }
 
 extern "C" int lfx_deskew_batch(lfx_ctx * c, const lfx_time_field * time, const lfx_sweep * sweeps, uint32_t n_scans, int to,
   float * d_edge_out, float * d_surface_out, void * stream)
 {
-  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
-  const int rb = check_batch_outputs(c, n_scans, d_edge_out, d_surface_out);
-  if (rb != LFX_OK) {return rb;}
-  const bool in_place = d_edge_out == nullptr;
-  const int rc = deskew_scans(c, time, sweeps, 0, n_scans, to, in_place ? c->edge_pts.p : reinterpret_cast<float4 *>(d_edge_out),
-    in_place ? c->surf_pts.p : reinterpret_cast<float4 *>(d_surface_out), static_cast<hipStream_t>(stream));
-  if (rc == LFX_OK && in_place) {c->deskewed_in_place = true;}
-  return rc;
+  return deskew_batch(c, n_scans, d_edge_out, d_surface_out, [&](float4 * edge, float4 * surf) {
+             return deskew_scans(c, time, sweeps, 0, n_scans, to, edge, surf, static_cast<hipStream_t>(stream));
+           });
 }

@@ -272,26 +272,21 @@ struct lfx_ctx
   int align_guess = 4;                             // iterations the previous alignment needed: so many are queued before the host looks
   uint32_t loc_guess[2] = {0u, 0u};                // longest edge / downsampled surface cloud of the previous lfx_localize_batch
 
-  // lfx_deskew_batch (lfx_deskew.hip): the per-scan constants go out through kDeskewSlots blocks of pinned memory, each with
-  // a table of its own on the device and an event behind the kernel that reads it, so that a call never rewrites a block or a
-  // table still in use, whichever streams the calls are on; allocated on first use.  deskewed_in_place: the last batch's clouds have been de-skewed in place (a second
+  // lfx_deskew_batch, lfx_deskew_batch_trajectory (lfx_deskew.hip): a call's table of constants goes out through the next of
+  // a ring of kDeskewSlots slots, each a pinned block, a device table and an event behind the kernel that reads it, so that a
+  // call never rewrites a block or a table still in use, whichever streams the calls are on.  A slot is sized by the calls
+  // that took it and grows on demand.  deskewed_in_place: the last batch's clouds have been de-skewed in place (a second
   // de-skew would correct them twice); run_batch lifts it
   static constexpr uint32_t kDeskewSlots = 8;
-  lfx_host::PinnedBuf h_deskew;
-  lfx_host::DevBuf<double> d_deskew;
-  hipEvent_t deskew_copied[kDeskewSlots] = {};
-  uint32_t deskew_next = 0;
-  bool deskewed_in_place = false;
-  // lfx_deskew_batch_trajectory: the segment tables travel the same way, but every slot's pinned block and device table are
-  // sized by the calls that used it (segments of the call, not max_batch x 63 rows) and grow on demand
-  struct TrajectorySlot
+  struct DeskewSlot
   {
     lfx_host::PinnedBuf h;
     lfx_host::DevBuf<double> d;
     hipEvent_t used = nullptr;           // recorded behind the kernel that read d
   };
-  TrajectorySlot trajectory_slots[kDeskewSlots];
-  uint32_t trajectory_next = 0;
+  DeskewSlot deskew_slots[kDeskewSlots];
+  uint32_t deskew_next = 0;
+  bool deskewed_in_place = false;
 
   hipStream_t stream = nullptr;          // used by the synchronous host entry points
   std::vector<uint32_t> h_scan_begin;    // of the last batch

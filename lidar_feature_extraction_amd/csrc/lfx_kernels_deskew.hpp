@@ -4,104 +4,113 @@
 #pragma once
 
 #include "lfx_kernels_common.hpp"
+#include "lfx_deskew_rows.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lfx
 {
 
-// The constants of one scan's sweep, a row of doubles the host writes (lfx_deskew.hip).  A workgroup reads the row of
-// blockIdx.y only: the addresses are the same for every lane, so the loads go through the scalar cache and the values
-// live in scalar registers.
-enum
-{
-  kDskK = 0,        // k = w / theta (0 where theta < 1e-8)
-  kDskTheta = 3,
-  kDskW = 4,        // w: the small-angle form reads it
-  kDskV = 7,        // v = t_D
-  kDskR = 10,       // R_D, row-major 3 x 3
-  kDskT0 = 19,
-  kDskInvDt = 20,   // 1 / (t1 - t0)
-  kDskScale = 21,   // seconds per unit of the time field
-  kDskStride = 24
-};
+// The constants of one scan's sweep are a row of doubles the host writes (lfx_deskew_rows.hpp).  A workgroup of the constant
+// motion reads the row of blockIdx.y only: the addresses are the same for every lane, so the loads go through the scalar
+// cache and the values live in scalar registers.
 enum { kDskFromIndex = 0, kDskF32 = 1, kDskF64 = 2, kDskU32 = 3 };
+enum { kTrjSegments = 64 };             // LDS columns per field (LFX_MAX_TRAJECTORY_KNOTS - 1 = 63 are used)
 constexpr int kDeskewThreads = 256;
 
-struct DeskewArgs
+// what both kernels are told about the batch's records
+struct DeskewRecords
 {
   const uint32_t * scan_begin, * scan_info;
-  const double * table;                 // [scans of the launch][kDskStride]
+  const double * table;                 // [scans of the launch][kDskStride], or [segments of the launch][kTrjStride]
   const float4 * edge_in, * surf_in;    // (may be the outputs: in place)
   const uint32_t * edge_idx, * surf_idx;
   float4 * edge_out, * surf_out;
   const uint8_t * pts;                  // the batch's input records (a field source only)
   uint32_t step, off, be;
   uint32_t first;                       // the launch covers scans first .. first + gridDim.y - 1
+};
+
+struct DeskewArgs
+{
+  DeskewRecords rec;
   uint32_t to_end;
 };
+
+// The firing time of record idx of the scan of n records that starts at record b: idx / n, or the time field's value times
+// `scale`.  NaN for an index that is no record of the scan: nothing is read, and the caller copies the record.
+template<int SRC>
+__device__ __forceinline__ double record_time(const DeskewRecords & A, size_t b, uint32_t idx, uint32_t n, double dn, double scale)
+{
+  if (SRC == kDskFromIndex) {return (double)idx / dn;}
+  if (idx >= n) {return __builtin_nan("");}
+  const uint8_t * f = A.pts + (b + idx) * A.step + A.off;
+  double value;
+  if (SRC == kDskF64) {
+    uint64_t u = *reinterpret_cast<const uint64_t *>(f);
+    if (A.be) {u = __builtin_bswap64(u);}
+    value = __longlong_as_double((long long)u);
+  } else {
+    uint32_t u = *reinterpret_cast<const uint32_t *>(f);
+    if (A.be) {u = __builtin_bswap32(u);}
+    value = SRC == kDskF32 ? (double)__uint_as_float(u) : (double)u;
+  }
+  return value * scale;
+}
+
+// p rotated by the fraction f of the twist whose row row(field) reads (kRowK, kRowTheta, kRowW): w only in the small-angle
+// form, k only in Rodrigues'.
+template<typename Row>
+__device__ __forceinline__ void rotate_by_fraction(Row row, double f, double px, double py, double pz, double & rx, double & ry, double & rz)
+{
+  const double theta = row(kRowTheta);
+  if (theta < 1e-8) {
+    const double wx = row(kRowW), wy = row(kRowW + 1), wz = row(kRowW + 2);
+    rx = px + f * (wy * pz - wz * py);
+    ry = py + f * (wz * px - wx * pz);
+    rz = pz + f * (wx * py - wy * px);
+  } else {
+    const double kx = row(kRowK), ky = row(kRowK + 1), kz = row(kRowK + 2);
+    const double a = f * theta, c = cos(a), sn = sin(a);
+    const double cx = ky * pz - kz * py, cy = kz * px - kx * pz, cz = kx * py - ky * px;
+    const double kdp = (kx * px + ky * py) + kz * pz, g = kdp * (1.0 - c);
+    rx = (px * c + cx * sn) + kx * g;
+    ry = (py * c + cy * sn) + ky * g;
+    rz = (pz * c + cz * sn) + kz * g;
+  }
+}
 
 // grid (chunks, scans) as feature_pack_kernel's; a grid-stride walk over the scan's n_edge + n_surface records, one float4
 // load and one float4 store per record, its index from the list beside it.  No LDS, no atomics.
 template<int SRC>
-__global__ __launch_bounds__(kDeskewThreads) void deskew_kernel(const DeskewArgs A)
+__global__ __launch_bounds__(kDeskewThreads) void deskew_kernel(const DeskewArgs args)
 {
+  const DeskewRecords & A = args.rec;
   const uint32_t s = A.first + blockIdx.y;
   const uint32_t ne = A.scan_info[s * 4 + kInfoEdge], ns = A.scan_info[s * 4 + kInfoSurface];
   const uint32_t b0 = A.scan_begin[s], n = A.scan_begin[s + 1] - b0;
   const size_t b = b0;
   const double * __restrict__ T = A.table + (size_t)blockIdx.y * kDskStride;
-  const double kx = T[kDskK], ky = T[kDskK + 1], kz = T[kDskK + 2], theta = T[kDskTheta];
-  const double wx = T[kDskW], wy = T[kDskW + 1], wz = T[kDskW + 2];
+  // (all of the row is read here, ahead of the loop's stores, which the compiler must take to alias the table: scalar loads)
+  const double twist[kRowW + 3] = {T[kRowK], T[kRowK + 1], T[kRowK + 2], T[kRowTheta], T[kRowW], T[kRowW + 1], T[kRowW + 2]};
   const double vx = T[kDskV], vy = T[kDskV + 1], vz = T[kDskV + 2];
   const double t0 = T[kDskT0], inv_dt = T[kDskInvDt], scale = T[kDskScale];
-  // (read here, ahead of the loop's stores, which the compiler must take to alias the table: scalar loads, as the rest)
   const double r00 = T[kDskR + 0], r01 = T[kDskR + 1], r02 = T[kDskR + 2], r10 = T[kDskR + 3], r11 = T[kDskR + 4], r12 = T[kDskR + 5],
     r20 = T[kDskR + 6], r21 = T[kDskR + 7], r22 = T[kDskR + 8];
-  const bool small = theta < 1e-8;      // the same for every record of the scan
   const double dn = (double)n;
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < ne + ns; k += gridDim.x * blockDim.x) {
     const bool edge = k < ne;
     const uint32_t q = edge ? k : k - ne;
     const float4 rec = (edge ? A.edge_in : A.surf_in)[b + q];
     const uint32_t idx = (edge ? A.edge_idx : A.surf_idx)[b + q];
-    double alpha;
-    if (SRC == kDskFromIndex) {
-      alpha = (double)idx / dn;
-    } else if (idx >= n) {
-      alpha = __builtin_nan("");        // (no record of the scan: nothing is read, the record is copied)
-    } else {
-      const uint8_t * f = A.pts + (b + idx) * A.step + A.off;
-      double value;
-      if (SRC == kDskF64) {
-        uint64_t u = *reinterpret_cast<const uint64_t *>(f);
-        if (A.be) {u = __builtin_bswap64(u);}
-        value = __longlong_as_double((long long)u);
-      } else {
-        uint32_t u = *reinterpret_cast<const uint32_t *>(f);
-        if (A.be) {u = __builtin_bswap32(u);}
-        value = SRC == kDskF32 ? (double)__uint_as_float(u) : (double)u;
-      }
-      alpha = (value * scale - t0) * inv_dt;
-    }
+    const double t = record_time<SRC>(A, b, idx, n, dn, scale);
+    const double alpha = SRC == kDskFromIndex ? t : (t - t0) * inv_dt;
     float4 out = rec;
     if (isfinite(alpha)) {
-      const double px = (double)rec.x, py = (double)rec.y, pz = (double)rec.z;
-      double rx, ry, rz;
-      if (small) {
-        rx = px + alpha * (wy * pz - wz * py);
-        ry = py + alpha * (wz * px - wx * pz);
-        rz = pz + alpha * (wx * py - wy * px);
-      } else {
-        const double a = alpha * theta, c = cos(a), sn = sin(a);
-        const double cx = ky * pz - kz * py, cy = kz * px - kx * pz, cz = kx * py - ky * px;
-        const double kdp = (kx * px + ky * py) + kz * pz, g = kdp * (1.0 - c);
-        rx = (px * c + cx * sn) + kx * g;
-        ry = (py * c + cy * sn) + ky * g;
-        rz = (pz * c + cz * sn) + kz * g;
-      }
+      double rx, ry, rz;                  // (the branch on theta is the same for every record of the scan)
+      rotate_by_fraction([&](int f) {return twist[f];}, alpha, (double)rec.x, (double)rec.y, (double)rec.z, rx, ry, rz);
       const double mx = rx + alpha * vx, my = ry + alpha * vy, mz = rz + alpha * vz;
-      if (A.to_end) {
+      if (args.to_end) {
         const double u0 = mx - vx, u1 = my - vy, u2 = mz - vz;
         out.x = (float)((r00 * u0 + r10 * u1) + r20 * u2);
         out.y = (float)((r01 * u0 + r11 * u1) + r21 * u2);
@@ -115,30 +124,11 @@ __global__ __launch_bounds__(kDeskewThreads) void deskew_kernel(const DeskewArgs
 }
 
 // De-skew along a trajectory (include/lfx.h): the constants are a segment's, chosen per record by its time, so they cannot
-// sit in scalar registers.  A segment's row as lfx_trajectory_segments writes it:
-enum
-{
-  kTrjK = 0, kTrjTheta = 3, kTrjW = 4,
-  kTrjA = 7,        // the rotation of Q_j, row-major 3 x 3
-  kTrjQ = 16,       // its translation
-  kTrjDq = 19,      // q_{j+1} - q_j
-  kTrjTime = 22,    // times[j]
-  kTrjInvDt = 23,   // 1 / (times[j+1] - times[j])
-  kTrjStride = 24,
-  kTrjSegments = 64 // LDS columns per field (LFX_MAX_TRAJECTORY_KNOTS - 1 = 63 are used)
-};
-
+// sit in scalar registers.
 struct TrajectoryArgs
 {
-  const uint32_t * scan_begin, * scan_info;
   const uint32_t * seg_begin;           // [scans of the launch + 1]: scan y's rows are seg_begin[y] .. seg_begin[y + 1] - 1
-  const double * table;                 // [segments of the launch][kTrjStride]
-  const float4 * edge_in, * surf_in;    // (may be the outputs: in place)
-  const uint32_t * edge_idx, * surf_idx;
-  float4 * edge_out, * surf_out;
-  const uint8_t * pts;                  // the batch's input records (a field source only)
-  uint32_t step, off, be;
-  uint32_t first;                       // the launch covers scans first .. first + gridDim.y - 1
+  DeskewRecords rec;
   double scale;                         // seconds per unit of the time field
 };
 
@@ -148,16 +138,17 @@ struct TrajectoryArgs
 // put every segment on one of four offsets).  The segment comes from a fixed six-step search over the knot times in LDS
 // whose predicate is exactly times[k] <= t.  No atomics.
 template<int SRC>
-__global__ __launch_bounds__(kDeskewThreads) void deskew_trajectory_kernel(const TrajectoryArgs A)
+__global__ __launch_bounds__(kDeskewThreads) void deskew_trajectory_kernel(const TrajectoryArgs args)
 {
+  const DeskewRecords & A = args.rec;
   __shared__ double seg[kTrjStride * kTrjSegments];
   const uint32_t s = A.first + blockIdx.y;
   const uint32_t ne = A.scan_info[s * 4 + kInfoEdge], ns = A.scan_info[s * 4 + kInfoSurface];
   if (blockIdx.x * blockDim.x >= ne + ns) {return;}      // (the whole workgroup: nothing to stage for)
   const uint32_t b0 = A.scan_begin[s], n = A.scan_begin[s + 1] - b0;
   const size_t b = b0;
-  const uint32_t g0 = A.seg_begin[blockIdx.y];
-  const uint32_t nseg = min(A.seg_begin[blockIdx.y + 1] - g0, (uint32_t)kTrjSegments - 1u);   // (the host refuses more)
+  const uint32_t g0 = args.seg_begin[blockIdx.y];
+  const uint32_t nseg = min(args.seg_begin[blockIdx.y + 1] - g0, (uint32_t)kTrjSegments - 1u);   // (the host refuses more)
   const double * __restrict__ T = A.table + (size_t)g0 * kTrjStride;
   for (uint32_t i = threadIdx.x; i < nseg * kTrjStride; i += blockDim.x) {
     const uint32_t j = i / kTrjStride, f = i - j * kTrjStride;
@@ -171,25 +162,7 @@ __global__ __launch_bounds__(kDeskewThreads) void deskew_trajectory_kernel(const
     const uint32_t q = edge ? k : k - ne;
     const float4 rec = (edge ? A.edge_in : A.surf_in)[b + q];
     const uint32_t idx = (edge ? A.edge_idx : A.surf_idx)[b + q];
-    double t;
-    if (SRC == kDskFromIndex) {
-      t = (double)idx / dn;
-    } else if (idx >= n) {
-      t = __builtin_nan("");            // (no record of the scan: nothing is read, the record is copied)
-    } else {
-      const uint8_t * f = A.pts + (b + idx) * A.step + A.off;
-      double value;
-      if (SRC == kDskF64) {
-        uint64_t u = *reinterpret_cast<const uint64_t *>(f);
-        if (A.be) {u = __builtin_bswap64(u);}
-        value = __longlong_as_double((long long)u);
-      } else {
-        uint32_t u = *reinterpret_cast<const uint32_t *>(f);
-        if (A.be) {u = __builtin_bswap32(u);}
-        value = SRC == kDskF32 ? (double)__uint_as_float(u) : (double)u;
-      }
-      t = value * A.scale;
-    }
+    const double t = record_time<SRC>(A, b, idx, n, dn, args.scale);
     // knots with times[k] <= t among the segments' start times (the last knot never starts a segment); a NaN counts none
     uint32_t pos = 0;
 #pragma unroll
@@ -203,23 +176,8 @@ __global__ __launch_bounds__(kDeskewThreads) void deskew_trajectory_kernel(const
     float4 out = rec;
     if (isfinite(beta)) {
       auto F = [&](int f) {return seg[f * kTrjSegments + j];};
-      const double px = (double)rec.x, py = (double)rec.y, pz = (double)rec.z;
-      const double theta = F(kTrjTheta);
-      double rx, ry, rz;
-      if (theta < 1e-8) {               // (per segment: the lanes diverge here)
-        const double wx = F(kTrjW), wy = F(kTrjW + 1), wz = F(kTrjW + 2);
-        rx = px + beta * (wy * pz - wz * py);
-        ry = py + beta * (wz * px - wx * pz);
-        rz = pz + beta * (wx * py - wy * px);
-      } else {
-        const double kx = F(kTrjK), ky = F(kTrjK + 1), kz = F(kTrjK + 2);
-        const double a = beta * theta, c = cos(a), sn = sin(a);
-        const double cx = ky * pz - kz * py, cy = kz * px - kx * pz, cz = kx * py - ky * px;
-        const double kdp = (kx * px + ky * py) + kz * pz, g = kdp * (1.0 - c);
-        rx = (px * c + cx * sn) + kx * g;
-        ry = (py * c + cy * sn) + ky * g;
-        rz = (pz * c + cz * sn) + kz * g;
-      }
+      double rx, ry, rz;                  // (theta is the segment's: the lanes diverge in here)
+      rotate_by_fraction(F, beta, (double)rec.x, (double)rec.y, (double)rec.z, rx, ry, rz);
       out.x = (float)(((F(kTrjA + 0) * rx + F(kTrjA + 1) * ry) + F(kTrjA + 2) * rz) + (F(kTrjQ + 0) + beta * F(kTrjDq + 0)));
       out.y = (float)(((F(kTrjA + 3) * rx + F(kTrjA + 4) * ry) + F(kTrjA + 5) * rz) + (F(kTrjQ + 1) + beta * F(kTrjDq + 1)));
       out.z = (float)(((F(kTrjA + 6) * rx + F(kTrjA + 7) * ry) + F(kTrjA + 8) * rz) + (F(kTrjQ + 2) + beta * F(kTrjDq + 2)));

@@ -231,6 +231,41 @@ int check(lfx_ctx * c, const lfx_odometry * o)
   if (o->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the odometry lives on another device");}
   return LFX_OK;
 }
+
+// What the de-skewing batch calls do once their arguments are checked: every scan of the last batch through
+// lfx_odometry_update, its clouds de-skewed just ahead of it by queue(s), which queues scan s's de-skew into dsk_edge /
+// dsk_surface (laid out like the context's clouds) on the stream.
+template<typename Queue>
+int update_deskewed(lfx_ctx * c, lfx_odometry * o, lfx_odometry_result * results, void * stream, Queue queue)
+{
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rs = settle(c, o);
+  if (rs != LFX_OK) {return rs;}
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t batch = c->last_batch;
+  const size_t total = c->h_scan_begin[batch];
+  if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
+  }
+  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
+  uint32_t * info = pinned_words(o) + kPinInfo;
+  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  // (lfx_odometry_update below writes the pinned block's words and bounds, not the batch's scan_info behind them)
+  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
+  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
+  for (uint32_t s = 0; s < batch; s++) {
+    int rc = queue(s);
+    if (rc != LFX_OK) {return rc;}
+    const uint32_t b = c->h_scan_begin[s];
+    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
+      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
+    if (rc != LFX_OK) {return rc;}
+    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
+  }
+  o->reports = reports;
+  return LFX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -388,39 +423,16 @@ int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_
   if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
   if (!std::isfinite(sweep_ratio)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_ratio must be finite");}
   if (time->source != LFX_TIME_FROM_INDEX && !sweep_times) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_times is required with a time field");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint32_t batch = c->last_batch;
-  const size_t total = c->h_scan_begin[batch];
-  if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
-    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
-  }
-  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
-  uint32_t * info = pinned_words(o) + kPinInfo;
-  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  // (lfx_odometry_update below writes the pinned block's words and bounds, not the batch's scan_info behind them)
-  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
-  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
-  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  for (uint32_t s = 0; s < batch; s++) {
-    lfx_sweep sw{};
-    double D[12];
-    if (o->n_recent < 2u) {std::memcpy(D, identity, sizeof(D));} else {lfx_motion_between(o->recent[0], o->recent[1], D);}
-    lfx_motion_scale(D, sweep_ratio, sw.motion);
-    if (sweep_times) {sw.t0 = sweep_times[2 * s]; sw.t1 = sweep_times[2 * s + 1];}
-    int rc = deskew_scans(c, time, &sw, s, 1, to, o->dsk_edge.p, o->dsk_surface.p, st);
-    if (rc != LFX_OK) {return rc;}
-    const uint32_t b = c->h_scan_begin[s];
-    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
-      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
-    if (rc != LFX_OK) {return rc;}
-    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
-  }
-  o->reports = reports;
-  return LFX_OK;
+  // (recent[] is read per scan: the scan before has been through its update by then)
+  return update_deskewed(c, o, results, stream, [&](uint32_t s) {
+             const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+             lfx_sweep sw{};
+             double D[12];
+             if (o->n_recent < 2u) {std::memcpy(D, identity, sizeof(D));} else {lfx_motion_between(o->recent[0], o->recent[1], D);}
+             lfx_motion_scale(D, sweep_ratio, sw.motion);
+             if (sweep_times) {sw.t0 = sweep_times[2 * s]; sw.t1 = sweep_times[2 * s + 1];}
+             return deskew_scans(c, time, &sw, s, 1, to, o->dsk_edge.p, o->dsk_surface.p, static_cast<hipStream_t>(stream));
+           });
 }
 
 // lfx_odometry_update_batch_deskewed with the caller's trajectories in place of the prediction.  Every trajectory is checked
@@ -435,32 +447,9 @@ int lfx_odometry_update_batch_trajectory(lfx_ctx * c, lfx_odometry * o, const lf
   if (c->deskewed_in_place) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch has already been de-skewed in place");}
   const int rt = check_trajectories(c, trajectories, n_scans);
   if (rt != LFX_OK) {return rt;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint32_t batch = c->last_batch;
-  const size_t total = c->h_scan_begin[batch];
-  if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
-    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
-  }
-  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
-  uint32_t * info = pinned_words(o) + kPinInfo;
-  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
-  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
-  for (uint32_t s = 0; s < batch; s++) {
-    int rc = deskew_scans_trajectory(c, time, trajectories + s, s, 1, o->dsk_edge.p, o->dsk_surface.p, st);
-    if (rc != LFX_OK) {return rc;}
-    const uint32_t b = c->h_scan_begin[s];
-    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
-      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
-    if (rc != LFX_OK) {return rc;}
-    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
-  }
-  o->reports = reports;
-  return LFX_OK;
+  return update_deskewed(c, o, results, stream, [&](uint32_t s) {
+             return deskew_scans_trajectory(c, time, trajectories + s, s, 1, o->dsk_edge.p, o->dsk_surface.p, static_cast<hipStream_t>(stream));
+           });
 }
 
 int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, uint32_t n_edge, const float * surface,

@@ -1,6 +1,5 @@
-// lfx_pcd.cpp -- map files (PCD) and the keyframe test of the mapping node, on the host only: lfx_pcd_read,
-// lfx_pcd_write, lfx_pose_diff (include/lfx.h).  Plain C++ with no HIP header: tests/test_map_files.py builds it on its own
-// under AddressSanitizer and UndefinedBehaviorSanitizer.
+// lfx_pcd.cpp -- map files (PCD), on the host only: lfx_pcd_read, lfx_pcd_write (include/lfx.h).  Plain C++ with no HIP
+// header: tests/test_map_files.py builds it on its own under AddressSanitizer and UndefinedBehaviorSanitizer.
 #include "../../include/lfx.h"
 
 #include <algorithm>
@@ -375,257 +374,6 @@ int lfx_pcd_write(const char * path, const float * points, uint64_t n_points, ch
   }
   ok = (std::fclose(f) == 0) && ok;
   if (!ok) {say(msg, msg_len, std::string("cannot write ") + path); return LFX_ERR_FILE;}
-  return LFX_OK;
-}
-
-// PoseDiffIsSufficientlySmall's two quantities (map.hpp:49-60) in Eigen 3.4's order of operations (include/lfx.h)
-int lfx_pose_diff(const double pose0[12], const double pose1[12], double * translation, double * rotation)
-{
-  if (!pose0 || !pose1 || !translation || !rotation) {return LFX_ERR_INVALID_ARGUMENT;}
-  auto R0 = [&](int r, int c) {return pose0[4 * r + c];};
-  auto R1 = [&](int r, int c) {return pose1[4 * r + c];};
-  double m[3][3], t[3];
-  for (int r = 0; r < 3; r++) {
-    // (R0^T)(r, k) = R0(k, r)
-    const double inv_t = -((R0(0, r) * pose0[3] + R0(1, r) * pose0[7]) + R0(2, r) * pose0[11]);
-    t[r] = ((R0(0, r) * pose1[3] + R0(1, r) * pose1[7]) + R0(2, r) * pose1[11]) + inv_t;
-    for (int c = 0; c < 3; c++) {m[r][c] = (R0(0, r) * R1(0, c) + R0(1, r) * R1(1, c)) + R0(2, r) * R1(2, c);}
-  }
-  *translation = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-  // Quaterniond(d.rotation()): Shoemake's algorithm as Eigen writes it (q.vec() only)
-  double q[3];
-  const double tr = (m[0][0] + m[1][1]) + m[2][2];
-  if (tr > 0.0) {
-    const double s = 0.5 / std::sqrt(tr + 1.0);
-    q[0] = (m[2][1] - m[1][2]) * s;
-    q[1] = (m[0][2] - m[2][0]) * s;
-    q[2] = (m[1][0] - m[0][1]) * s;
-  } else {
-    int i = 0;
-    if (m[1][1] > m[0][0]) {i = 1;}
-    if (m[2][2] > m[i][i]) {i = 2;}
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    const double s0 = std::sqrt(((m[i][i] - m[j][j]) - m[k][k]) + 1.0);
-    q[i] = 0.5 * s0;
-    const double s = 0.5 / s0;
-    q[j] = (m[j][i] + m[i][j]) * s;
-    q[k] = (m[k][i] + m[i][k]) * s;
-  }
-  *rotation = std::sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
-  return LFX_OK;
-}
-
-// The motions of the de-skew section (include/lfx.h): pose0^-1 pose1 as lfx_pose_diff forms it, its angle-axis vector, a
-// fraction of it.
-int lfx_motion_between(const double pose0[12], const double pose1[12], double motion[12])
-{
-  if (!pose0 || !pose1 || !motion) {return LFX_ERR_INVALID_ARGUMENT;}
-  auto R0 = [&](int r, int c) {return pose0[4 * r + c];};
-  auto R1 = [&](int r, int c) {return pose1[4 * r + c];};
-  double out[12];                                     // (motion may be one of the poses)
-  bool same = true;
-  for (int i = 0; i < 12; i++) {same = same && pose0[i] == pose1[i];}
-  if (same) {
-    // a sensor that has not moved: the identity itself, not R0^T R0 as it rounds (de-skew by it changes no bit)
-    const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    std::memcpy(motion, identity, sizeof(identity));
-    return LFX_OK;
-  }
-  for (int r = 0; r < 3; r++) {
-    const double inv_t = -((R0(0, r) * pose0[3] + R0(1, r) * pose0[7]) + R0(2, r) * pose0[11]);
-    out[4 * r + 3] = ((R0(0, r) * pose1[3] + R0(1, r) * pose1[7]) + R0(2, r) * pose1[11]) + inv_t;
-    for (int c = 0; c < 3; c++) {out[4 * r + c] = (R0(0, r) * R1(0, c) + R0(1, r) * R1(1, c)) + R0(2, r) * R1(2, c);}
-  }
-  std::memcpy(motion, out, sizeof(out));
-  return LFX_OK;
-}
-
-int lfx_motion_twist(const double motion[12], double w[3], double * theta)
-{
-  if (!motion || !w || !theta) {return LFX_ERR_INVALID_ARGUMENT;}
-  auto m = [&](int r, int c) {return motion[4 * r + c];};
-  // Quaterniond(R_D), Shoemake's algorithm as Eigen writes it (lfx_pose_diff), with its scalar part
-  double q[3], qw;
-  const double tr = (m(0, 0) + m(1, 1)) + m(2, 2);
-  if (tr > 0.0) {
-    const double t = std::sqrt(tr + 1.0);
-    qw = 0.5 * t;
-    const double s = 0.5 / t;
-    q[0] = (m(2, 1) - m(1, 2)) * s;
-    q[1] = (m(0, 2) - m(2, 0)) * s;
-    q[2] = (m(1, 0) - m(0, 1)) * s;
-  } else {
-    int i = 0;
-    if (m(1, 1) > m(0, 0)) {i = 1;}
-    if (m(2, 2) > m(i, i)) {i = 2;}
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    const double t = std::sqrt(((m(i, i) - m(j, j)) - m(k, k)) + 1.0);
-    q[i] = 0.5 * t;
-    const double s = 0.5 / t;
-    qw = (m(k, j) - m(j, k)) * s;
-    q[j] = (m(j, i) + m(i, j)) * s;
-    q[k] = (m(k, i) + m(i, k)) * s;
-  }
-  const double n = std::sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
-  if (n == 0.0) {
-    w[0] = w[1] = w[2] = 0.0;
-    *theta = 0.0;
-    return LFX_OK;
-  }
-  const double th = 2.0 * std::atan2(n, qw), f = th / n;
-  w[0] = q[0] * f; w[1] = q[1] * f; w[2] = q[2] * f;
-  *theta = th;
-  return LFX_OK;
-}
-
-// the rotation of the angle-axis vector ratio * w (theta = |w|) into res's 3 x 3, as the de-skew kernels form it
-static void rotation_of(const double w[3], double theta, double ratio, double res[12])
-{
-  if (theta < 1e-8) {
-    const double x = ratio * w[0], y = ratio * w[1], z = ratio * w[2];
-    const double r[9] = {1.0, 0.0 - z, y, z, 1.0, 0.0 - x, 0.0 - y, x, 1.0};   // (0 - 0: no negative zero for the identity)
-    for (int i = 0; i < 3; i++) {for (int j = 0; j < 3; j++) {res[4 * i + j] = r[3 * i + j];}}
-  } else {
-    const double k[3] = {w[0] / theta, w[1] / theta, w[2] / theta};
-    const double a = ratio * theta, c = std::cos(a), s = std::sin(a), v = 1.0 - c;
-    const double hat[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) {res[4 * i + j] = ((i == j ? c : 0.0) + hat[3 * i + j] * s) + k[i] * (k[j] * v);}
-    }
-  }
-}
-
-int lfx_motion_scale(const double motion[12], double ratio, double out[12])
-{
-  if (!motion || !out) {return LFX_ERR_INVALID_ARGUMENT;}
-  double w[3], theta;
-  lfx_motion_twist(motion, w, &theta);
-  double res[12];                                     // (out may be motion)
-  rotation_of(w, theta, ratio, res);
-  for (int i = 0; i < 3; i++) {res[4 * i + 3] = ratio * motion[4 * i + 3];}
-  std::memcpy(out, res, sizeof(res));
-  return LFX_OK;
-}
-
-// The trajectories of the de-skew section (include/lfx.h): the segment table of one, knots from gyro samples.
-namespace
-{
-bool finite_run(const double * v, size_t n)
-{
-  for (size_t i = 0; i < n; i++) {
-    if (!std::isfinite(v[i])) {return false;}
-  }
-  return true;
-}
-
-bool ascending_times(const double * t, uint32_t n)
-{
-  if (!finite_run(t, n)) {return false;}
-  for (uint32_t i = 1; i < n; i++) {
-    if (!(t[i] > t[i - 1])) {return false;}
-  }
-  return true;
-}
-
-// the rotation of pose a times that of b, every sum (a0 b0 + a1 b1) + a2 b2, into out's 3 x 3
-void rotate(const double a[12], const double b[12], double out[12])
-{
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) {out[4 * r + c] = (a[4 * r] * b[c] + a[4 * r + 1] * b[4 + c]) + a[4 * r + 2] * b[8 + c];}
-  }
-}
-}  // namespace
-
-int lfx_trajectory_segments(const lfx_trajectory * tr, double * segments_out)
-{
-  if (!tr || !segments_out || !tr->times || !tr->poses) {return LFX_ERR_INVALID_ARGUMENT;}
-  const uint32_t n = tr->n_knots;
-  if (n < 2u || n > LFX_MAX_TRAJECTORY_KNOTS) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (!ascending_times(tr->times, n) || !finite_run(tr->poses, 12 * (size_t)n) || !std::isfinite(tr->t_ref)) {return LFX_ERR_INVALID_ARGUMENT;}
-  const double * t = tr->times, * P = tr->poses;
-  // the reference pose: a knot's own where t_ref is a knot time, else the model's at t_ref
-  double ref[12];
-  uint32_t at = 0;                                    // knots with times[k] <= t_ref
-  while (at < n && t[at] <= tr->t_ref) {at++;}
-  if (at > 0u && t[at - 1] == tr->t_ref) {
-    std::memcpy(ref, P + 12 * (size_t)(at - 1), sizeof(ref));
-  } else {
-    const uint32_t j = std::min(std::max(at, 1u) - 1u, n - 2u);
-    const double * a = P + 12 * (size_t)j, * b = a + 12;
-    const double beta = (tr->t_ref - t[j]) * (1.0 / (t[j + 1] - t[j]));
-    double D[12], S[12];
-    lfx_motion_between(a, b, D);
-    lfx_motion_scale(D, beta, S);
-    rotate(a, S, ref);
-    for (int i = 0; i < 3; i++) {ref[4 * i + 3] = a[4 * i + 3] + beta * (b[4 * i + 3] - a[4 * i + 3]);}
-  }
-  double Q[2][12];                                    // Q_j and Q_{j+1}, swapped as the segments go by
-  lfx_motion_between(ref, P, Q[0]);
-  for (uint32_t j = 0; j + 1 < n; j++) {
-    const double * q0 = Q[j & 1u];
-    double * q1 = Q[(j + 1u) & 1u], * T = segments_out + (size_t)LFX_TRAJECTORY_SEGMENT_DOUBLES * j;
-    lfx_motion_between(ref, P + 12 * (size_t)(j + 1), q1);
-    double D[12], w[3], theta;
-    lfx_motion_between(q0, q1, D);
-    lfx_motion_twist(D, w, &theta);
-    for (int a = 0; a < 3; a++) {
-      T[a] = theta < 1e-8 ? 0.0 : w[a] / theta;
-      T[4 + a] = w[a];
-      for (int c = 0; c < 3; c++) {T[7 + 3 * a + c] = q0[4 * a + c];}
-      T[16 + a] = q0[4 * a + 3];
-      T[19 + a] = q1[4 * a + 3] - q0[4 * a + 3];
-    }
-    T[3] = theta;
-    T[22] = t[j];
-    T[23] = 1.0 / (t[j + 1] - t[j]);
-  }
-  return LFX_OK;
-}
-
-int lfx_trajectory_from_gyro(const double * times, const double * rates, uint32_t n, const double bias[3], const double velocity[3],
-  double * poses_out)
-{
-  if (!times || !rates || !poses_out || n < 2u) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (!ascending_times(times, n) || !finite_run(rates, 3 * (size_t)n)) {return LFX_ERR_INVALID_ARGUMENT;}
-  if ((bias && !finite_run(bias, 3)) || (velocity && !finite_run(velocity, 3))) {return LFX_ERR_INVALID_ARGUMENT;}
-  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  std::memcpy(poses_out, identity, sizeof(identity));
-  for (uint32_t j = 0; j + 1 < n; j++) {
-    const double * r0 = rates + 3 * (size_t)j, * r1 = r0 + 3, * a = poses_out + 12 * (size_t)j;
-    double * b = poses_out + 12 * (size_t)(j + 1), phi[3], E[12];
-    const double dt = times[j + 1] - times[j];
-    for (int i = 0; i < 3; i++) {
-      const double bi = bias ? bias[i] : 0.0;
-      phi[i] = (0.5 * ((r0[i] - bi) + (r1[i] - bi))) * dt;
-    }
-    rotation_of(phi, std::sqrt((phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2]), 1.0, E);
-    rotate(a, E, b);
-    for (int i = 0; i < 3; i++) {b[4 * i + 3] = velocity ? velocity[i] * (times[j + 1] - times[0]) : 0.0;}
-  }
-  return LFX_OK;
-}
-
-// A report's covariance in the order of geometry_msgs/PoseWithCovariance (include/lfx.h): out = T C T^T, T = [[0, I], [R, 0]].
-// Every sum of three terms is (a0 b0 + a1 b1) + a2 b2 (this file is built with contraction off).
-int lfx_align_covariance_ros(const double pose[12], const double covariance[36], double out[36])
-{
-  if (!pose || !covariance || !out) {return LFX_ERR_INVALID_ARGUMENT;}
-  auto R = [&](int r, int c) {return pose[4 * r + c];};
-  double tc[36];                                      // T C: rows 0-2 = C's translation rows, rows 3-5 = R times its rotation rows
-  for (int c = 0; c < 6; c++) {
-    for (int i = 0; i < 3; i++) {
-      tc[6 * i + c] = covariance[6 * (3 + i) + c];
-      tc[6 * (3 + i) + c] = (R(i, 0) * covariance[c] + R(i, 1) * covariance[6 + c]) + R(i, 2) * covariance[12 + c];
-    }
-  }
-  double res[36];                                     // (out may be covariance)
-  for (int r = 0; r < 6; r++) {
-    for (int j = 0; j < 3; j++) {
-      res[6 * r + j] = tc[6 * r + 3 + j];
-      res[6 * r + 3 + j] = (tc[6 * r] * R(j, 0) + tc[6 * r + 1] * R(j, 1)) + tc[6 * r + 2] * R(j, 2);
-    }
-  }
-  std::memcpy(out, res, sizeof(res));
   return LFX_OK;
 }
 

@@ -267,7 +267,7 @@ def test_helpers_under_sanitizers(tmp_path):
     exe = tmp_path / "trajectory_asan"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off",
                            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "lfx_pcd.cpp"), str(drv), "-o", str(exe)])
+                           "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "lfx_pose.cpp"), str(drv), "-o", str(exe)])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     p = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env, timeout=300)
     out = p.stdout.decode(errors="replace")
