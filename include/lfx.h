@@ -303,25 +303,35 @@ int lfx_layout_from_fields(const lfx_point_field *fields, uint32_t n_fields, uin
 /* The last device batch's edge and surface clouds as pcl::PointXYZ wire records (point_step 16:
  * x, y, z, 1.0f -- what ToPointXYZ + toROSMsg publish as scan_edge / scan_surface,
  * feature_extraction.cpp:163-170), packed back to back in scan order exactly as lfx_pack_features
- * does (same offsets table). */
+ * does (same offsets table).
+ * A short capacity_points (all four lfx_pack_* calls): records at or past capacity_points are not written -- nothing is
+ * stored beyond [capacity_points] records of any output buffer -- while the offsets table is complete, the counts of every
+ * scan and the totals as if everything had fitted.  A caller compares entry [batch] (for the surface cloud [2*batch+1])
+ * with its capacity: a larger entry means the payload was cut there, and a second call with room for it gets all of it.
+ * capacity_points above 2^32 - 1 counts as 2^32 - 1 (a batch holds fewer records than that). */
 int lfx_pack_xyz(lfx_ctx *ctx, float *d_edge_out, float *d_surface_out, uint32_t *d_offsets_out,
                  size_t capacity_points, void *stream);
 /* The same clouds as tight x, y, z triples (12 bytes per point, [capacity_points][3] floats): the least that has
- * to cross xGMI when the clouds of several GPUs are gathered to one (gather.py, bench.py). */
+ * to cross xGMI when the clouds of several GPUs are gathered to one (gather.py, bench.py).  A short capacity_points: as
+ * lfx_pack_xyz -- no float at or past 3 * capacity_points is written, the table is complete. */
 int lfx_pack_xyz12(lfx_ctx *ctx, float *d_edge_out, float *d_surface_out, uint32_t *d_offsets_out,
                    size_t capacity_points, void *stream);
 /* colored_scan (feature_extraction.cpp:153,161) of the last device batch as pcl::PointXYZRGB wire records
  * (point_step 32: x, y, z, 1.0f | rgb bit-cast to float, 0, 0, 0; rgb = 0xFF<<24 | r<<16 | g<<8 | b with the
  * table of color_points.cpp:39-68): for every scan the points of each ring that was labelled (status
  * LFX_RING_OK), rings ascending, angle ascending -- the reference appends ring by ring and skips a ring it
- * abandons.  d_offsets_out u32 [batch+1]: exclusive prefix of the per-scan point counts. */
+ * abandons.  d_offsets_out u32 [batch+1]: exclusive prefix of the per-scan point counts (entry [batch] = total).
+ * d_colored_out [capacity_points][8] floats.  A short capacity_points: as lfx_pack_xyz -- no record at or past it is
+ * written, the table is complete, the caller compares entry [batch] with its capacity. */
 int lfx_pack_colored(lfx_ctx *ctx, float *d_colored_out, uint32_t *d_offsets_out, size_t capacity_points,
                      void *stream);
 /* Pack the last device batch's edge and surface clouds back to back, in scan order, into
  * caller-provided DEVICE buffers (what one rank hands to the multi-GPU gather):
  * d_edge_out / d_surface_out [capacity_points][4] floats (16-byte aligned); d_offsets_out u32
  * [2][batch+1]: exclusive prefix of the per-scan edge counts, then of the surface counts
- * (entry [batch] = total).  Asynchronous on `stream`. */
+ * (entry [batch] = total).  Asynchronous on `stream`.  A short capacity_points: as lfx_pack_xyz -- records at or past it
+ * are not written (each cloud against its own offsets), the table is complete, the caller compares entries [batch] and
+ * [2*batch+1] with its capacity. */
 int lfx_pack_features(lfx_ctx *ctx, float *d_edge_out, float *d_surface_out, uint32_t *d_offsets_out,
                       size_t capacity_points, void *stream);
 /* Copy scan `scan` of the last device batch to host memory (synchronises the stream). */

@@ -385,6 +385,16 @@ def test_organised_scan_kernel_zero_point_filter_and_colored_scan():
         rgb = np.zeros(3, np.uint8)
         assert LB.load().lfx_label_to_color(int(v), rgb.ctypes.data_as(LB.C.POINTER(LB.C.c_uint8))) == 0
         assert np.all((rgba[lab == v] >> 16) & 255 == rgb[0]) and np.all(rgba[lab == v] & 255 == rgb[2])
+        assert np.all((rgba[lab == v] >> 8) & 255 == rgb[1])          # (Edge and EdgeNeighbor differ in green alone)
+    # both scans' slices, every word of every record, through the restatement of the payloads (tests/wire_cases.py)
+    from tests import wire_cases as W
+    filtered = np.ascontiguousarray(z[keep])
+    exp = W.batch_expect([W.scan_piece(c, want_c), W.scan_piece(filtered, want_z)])
+    assert np.array_equal(coffs.view(np.uint32), exp.colored_offsets)
+    assert coffs[2] > coffs[1] and len(exp.colored) == coffs[2]
+    words = col.view(np.uint32)
+    assert np.array_equal(words[coffs[0]:coffs[1]], exp.colored[coffs[0]:coffs[1]]), "the organised scan's colored_scan"
+    assert np.array_equal(words[coffs[1]:coffs[2]], exp.colored[coffs[1]:coffs[2]]), "the second scan's colored_scan"
     f.close()
 
 
