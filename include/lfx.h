@@ -890,6 +890,79 @@ int lfx_odometry_update_batch_trajectory(lfx_ctx *ctx, lfx_odometry *odometry, c
                                          const lfx_trajectory *trajectories, uint32_t n_scans,
                                          lfx_odometry_result *results, void *stream);
 
+/* --- place recognition: scan-context descriptors and a place index ----------------------------------------------------- */
+/* "Where am I in this map?"  No reference counterpart; the model is Scan Context (Kim and Kim, IROS 2018): a scan gives one
+ * R x S matrix, the largest height in every polar cell around the sensor; two matrices are compared under every column
+ * shift, and the best shift is the yaw between the two visits.  The index below compares a query with EVERY entry (no
+ * KD-tree prefilter).
+ *
+ * Tables (lfx_scan_context_tables, host only, the ONLY source: the device is given exactly these values):
+ *   sector_cos[m], sector_sin[m] = cos, sin of -pi + (2 pi) * m / S in double, the angle formed as
+ *                                  -M_PI + ((2.0 * M_PI) * (double)m) / (double)S;
+ *   ring_r2[j] = e * e with e = ((double)max_radius * (double)j) / (double)R, j = 0 .. R.
+ * Per record (x, y, z read as floats through the context's lfx_layout: any point_step, offsets, byte order), in double,
+ * unfused:
+ *   - a record with a non-finite x, y or z is skipped;
+ *   - r2 = x*x + y*y (the products of two floats are exact in double); a record with r2 < min_radius^2 (the square of the
+ *     float in double, exact) or r2 >= ring_r2[R] is skipped -- with min_radius > 0 that leaves the (0, 0, 0) records out;
+ *   - ring = #{ j in 1 .. R-1 : r2 >= ring_r2[j] };
+ *   - cross_m = sector_cos[m]*y - sector_sin[m]*x: two rounded products and one subtraction (a fused form gives other bits);
+ *     where y >= 0 (-0.0 included): sector = S/2 + #{ m in S/2+1 .. S-1 : cross_m >= 0 },
+ *     otherwise:                    sector = #{ m in 1 .. S/2-1 : cross_m >= 0 }.
+ *     The counts are the definition; no atan2 is involved (sector m covers the azimuths [-pi + 2 pi m / S, -pi + 2 pi (m+1) / S)).
+ * Cell [ring][sector] holds zmax, the largest z of its records (float order; -0.0 and +0.0 give the same cell value); the
+ * value written is v = zmax + sensor_height in float where v > 0, else +0.0f; a cell without a record is +0.0f. */
+typedef struct lfx_scan_context_config {
+  uint32_t n_rings;      /* R, radial cells: 20;  1 .. 40            */
+  uint32_t n_sectors;    /* S, azimuth cells: 60; even, 4 .. 120     */
+  float max_radius;      /* 80.0  */
+  float min_radius;      /* 0.1; >= 0, < max_radius */
+  float sensor_height;   /* 2.0: added to z so that the ground is near 0 */
+} lfx_scan_context_config;
+#define LFX_SCAN_CONTEXT_MAX_RINGS 40
+#define LFX_SCAN_CONTEXT_MAX_SECTORS 120
+void lfx_scan_context_default_config(lfx_scan_context_config *config);
+/* host only, no context: the tables the kernel is given.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, R or S out of range, S
+ * odd, radii that are not finite, negative or not min_radius < max_radius, a non-finite sensor_height. */
+int lfx_scan_context_tables(const lfx_scan_context_config *config, double *sector_cos /*[S]*/, double *sector_sin /*[S]*/,
+                            double *ring_r2 /*[R+1]*/);
+/* Descriptors of every scan of the last device batch, from the batch's INPUT records (which must still be alive, as for
+ * lfx_pack_colored): d_desc_out [n_scans][R][S] floats, row = ring.  Every cell is written on every call.  Asynchronous on
+ * `stream`, the counts read on the device.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, what lfx_scan_context_tables refuses,
+ * no batch yet, n_scans not the last batch's, the batch's input records not known. */
+int lfx_scan_context_batch(lfx_ctx *ctx, const lfx_scan_context_config *config, uint32_t n_scans, float *d_desc_out, void *stream);
+
+/* The place index: descriptors of one config on the device, in insertion order, each with its column norms (computed once,
+ * at the add).  Distance of a query q and an entry c under the column shift s, in double:
+ *   nq[j] = sqrt(sum_i q[i][j]^2), summed in the order i = 0 .. R-1 (nc the same for the entry);
+ *   g(j, s) = sum_i q[i][j] * c[i][(j + s) mod S], in the same order (the products are exact in double);
+ *   a column pair j counts where nq[j] > 0 and nc[(j + s) mod S] > 0;
+ *   d(s) = 1 - (sum_j g(j, s) / (nq[j] * nc[(j + s) mod S])) / n_valid, j ascending over the pairs that count; no pair: 1.
+ * The entry's distance is the least d(s), its shift the lowest s that reaches it; yaw = shift * (2 pi / S) for
+ * shift <= S / 2, (shift - S) * (2 pi / S) above: in (-pi, pi].  CONVENTION: a sensor that revisits the entry's place turned
+ * by +yaw about z (counter-clockwise seen from above) gives this shift; the initial pose of the revisit is the entry's pose
+ * times Rz(yaw).  Matches come in ascending distance, equal distances by the lower entry: the same inputs give the same
+ * bytes.  Descriptors must be finite (what lfx_scan_context_batch writes is); an entry whose distance to a query is NaN is
+ * never a match.  An index belongs to the device of the context that made it. */
+typedef struct lfx_place_db lfx_place_db;
+typedef struct lfx_place_match { uint32_t entry; uint32_t shift; double distance; double yaw; } lfx_place_match;
+#define LFX_PLACE_MAX_MATCHES 16
+int lfx_place_db_create(lfx_ctx *ctx, const lfx_scan_context_config *config, uint32_t capacity, lfx_place_db **out);
+void lfx_place_db_destroy(lfx_place_db *db);
+/* Appends n descriptors ([n][R][S] floats) from the device / from the host; entry = insertion order.  Beyond the capacity:
+ * LFX_ERR_CAPACITY, the index unchanged.  Queued on `stream`; a query on another stream is ordered behind the last add. */
+int lfx_place_db_add(lfx_ctx *ctx, lfx_place_db *db, const float *d_desc, uint32_t n, void *stream);
+int lfx_place_db_add_host(lfx_ctx *ctx, lfx_place_db *db, const float *desc, uint32_t n, void *stream);
+int lfx_place_db_size(const lfx_place_db *db, uint32_t *n);
+/* Entries first .. first + count - 1 to host memory ([count][R][S] floats).  Synchronous. */
+int lfx_place_db_download(lfx_ctx *ctx, const lfx_place_db *db, uint32_t first, uint32_t count, float *desc_out /*host*/, void *stream);
+/* For each of n_queries descriptors on the device, the k (1 .. 16) best of entries [first, first + count): matches host
+ * [n_queries][k].  first / count let a loop-closure caller leave out its most recent keyframes; count may be 0.  With fewer
+ * than k entries in the range the remaining matches are entry = UINT32_MAX, shift = 0, distance = +inf, yaw = 0.
+ * Synchronous.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, n_queries 0, k outside 1 .. 16, a range past the index's size. */
+int lfx_place_db_query(lfx_ctx *ctx, const lfx_place_db *db, const float *d_desc, uint32_t n_queries, uint32_t first,
+                       uint32_t count, uint32_t k, lfx_place_match *matches, void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

@@ -227,6 +227,30 @@ public:
     const int rc = lfx_deskew_batch_trajectory(ctx_, &time, views.data(), static_cast<std::uint32_t>(views.size()), d_edge_out, d_surface_out, stream);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
   }
+  // The scan-context descriptors of the scans this object was last given (lfx_scan_context_batch), from their input records:
+  // d_desc_out [n_scans][R][S] floats in memory the device writes -- device memory, or a pinned block of this object
+  // (PinnedFloats), which the host then reads once `stream` has passed the call.
+  static lfx_scan_context_config DefaultScanContextConfig() {lfx_scan_context_config c; lfx_scan_context_default_config(&c); return c;}
+  void ScanContext(const lfx_scan_context_config & config, std::uint32_t n_scans, float * d_desc_out, void * stream = nullptr) const
+  {
+    const int rc = lfx_scan_context_batch(ctx_, &config, n_scans, d_desc_out, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  // lfx_batch_status: waits for `stream` and throws if a scan this object was last given carries an error bit.  The wait a
+  // caller needs between ScanContext (queued, reads the scans' input records) and the next scan it hands over.
+  void BatchStatus(void * stream = nullptr) const
+  {
+    const int rc = lfx_batch_status(ctx_, stream, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  float * PinnedFloats(std::size_t count)
+  {
+    void * p = nullptr;
+    const int rc = lfx_host_alloc(ctx_, count * sizeof(float), &p);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    pinned_.push_back(p);
+    return static_cast<float *>(p);
+  }
   lfx_ctx * handle() const {return ctx_;}
   // records the device clouds of the last scan may span (their buffers' extent: one scan of max_points_per_scan)
   std::size_t CloudCapacity() const {return max_points_;}
@@ -549,6 +573,70 @@ private:
   const FeatureExtraction & fx_;
   lfx_mapper * mapper_ = nullptr;
   std::vector<std::uint8_t> outcomes_;
+};
+
+// The place index (lfx_place_db): scan-context descriptors of one config on the device of `fx`, which must outlive it, each
+// compared with a query under every column shift.  For start-up relocalisation (index the keyframes of a map, query with
+// the first scan) and for loop detection (index the keyframes as the mapper adds them; query the range that leaves the most
+// recent ones out).  A match's yaw: the revisit's initial pose is the entry's pose times Rz(yaw).
+class PlaceDb
+{
+public:
+  PlaceDb(const FeatureExtraction & fx, const lfx_scan_context_config & config, std::uint32_t capacity)
+  : fx_(fx), config_(config)
+  {
+    const int rc = lfx_place_db_create(fx.handle(), &config, capacity, &db_);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx.handle()));}
+  }
+  ~PlaceDb() {lfx_place_db_destroy(db_);}
+  PlaceDb(const PlaceDb &) = delete;
+  PlaceDb & operator=(const PlaceDb &) = delete;
+
+  const lfx_scan_context_config & Config() const {return config_;}
+  // n descriptors the device reads (device memory, or a pinned block); entry = insertion order
+  void Add(const float * d_desc, std::uint32_t n, void * stream = nullptr)
+  {
+    const int rc = lfx_place_db_add(fx_.handle(), db_, d_desc, n, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  // the same from pageable host memory (descriptors kept in a file)
+  void AddHost(const std::vector<float> & desc, std::uint32_t n, void * stream = nullptr)
+  {
+    const int rc = desc.size() == static_cast<std::size_t>(n) * config_.n_rings * config_.n_sectors ?
+      lfx_place_db_add_host(fx_.handle(), db_, desc.data(), n, stream) : LFX_ERR_INVALID_ARGUMENT;
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  std::uint32_t Size() const
+  {
+    std::uint32_t n = 0;
+    lfx_place_db_size(db_, &n);
+    return n;
+  }
+  std::vector<float> Download(std::uint32_t first, std::uint32_t count, void * stream = nullptr) const
+  {
+    std::vector<float> out(static_cast<std::size_t>(count) * config_.n_rings * config_.n_sectors);
+    const int rc = lfx_place_db_download(fx_.handle(), db_, first, count, out.data(), stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return out;
+  }
+  // per query the k best of entries [first, first + count): [n_queries][k], ascending distance
+  std::vector<lfx_place_match> Query(
+    const float * d_desc, std::uint32_t n_queries, std::uint32_t k, std::uint32_t first, std::uint32_t count, void * stream = nullptr) const
+  {
+    std::vector<lfx_place_match> out(static_cast<std::size_t>(n_queries) * k);
+    const int rc = lfx_place_db_query(fx_.handle(), db_, d_desc, n_queries, first, count, k, out.data(), stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return out;
+  }
+  std::vector<lfx_place_match> Query(const float * d_desc, std::uint32_t n_queries, std::uint32_t k = 1) const
+  {
+    return Query(d_desc, n_queries, k, 0, Size());
+  }
+
+private:
+  const FeatureExtraction & fx_;
+  lfx_scan_context_config config_;
+  lfx_place_db * db_ = nullptr;
 };
 
 }  // namespace lfx

@@ -145,6 +145,21 @@ TIME_FROM_INDEX, TIME_FROM_FIELD = 0, 1
 DESKEW_TO_START, DESKEW_TO_END = 0, 1
 
 
+class ScanContextConfig(C.Structure):
+    """lfx_scan_context_config: the polar grid of a scan-context descriptor (R rings x S sectors out to max_radius)."""
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("max_radius", C.c_float), ("min_radius", C.c_float),
+                ("sensor_height", C.c_float)]
+
+
+class PlaceMatch(C.Structure):
+    """lfx_place_match: one entry of a place index as a query sees it."""
+    _fields_ = [("entry", C.c_uint32), ("shift", C.c_uint32), ("distance", C.c_double), ("yaw", C.c_double)]
+
+
+SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, PLACE_MAX_MATCHES = 40, 120, 16
+PLACE_NO_ENTRY = 0xFFFFFFFF
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -171,6 +186,9 @@ EXPORTS = [
     "lfx_time_field_from_fields", "lfx_motion_between", "lfx_motion_twist", "lfx_motion_scale", "lfx_deskew_batch",
     "lfx_odometry_update_batch_deskewed",
     "lfx_trajectory_segments", "lfx_trajectory_from_gyro", "lfx_deskew_batch_trajectory", "lfx_odometry_update_batch_trajectory",
+    "lfx_scan_context_default_config", "lfx_scan_context_tables", "lfx_scan_context_batch", "lfx_place_db_create",
+    "lfx_place_db_destroy", "lfx_place_db_add", "lfx_place_db_add_host", "lfx_place_db_size", "lfx_place_db_download",
+    "lfx_place_db_query",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -296,6 +314,19 @@ def load(test_hooks=False):
     L.lfx_deskew_batch_trajectory.argtypes = [vp, C.POINTER(TimeField), C.POINTER(Trajectory), u32, vp, vp, vp]
     L.lfx_odometry_update_batch_trajectory.argtypes = [vp, vp, C.POINTER(TimeField), C.POINTER(Trajectory), u32,
                                                        C.POINTER(OdometryResult), vp]
+    psc = C.POINTER(ScanContextConfig)
+    L.lfx_scan_context_default_config.argtypes = [psc]
+    L.lfx_scan_context_default_config.restype = None
+    L.lfx_scan_context_tables.argtypes = [psc, pd, pd, pd]
+    L.lfx_scan_context_batch.argtypes = [vp, psc, u32, vp, vp]
+    L.lfx_place_db_create.argtypes = [vp, psc, u32, C.POINTER(vp)]
+    L.lfx_place_db_destroy.argtypes = [vp]
+    L.lfx_place_db_destroy.restype = None
+    L.lfx_place_db_add.argtypes = [vp, vp, vp, u32, vp]
+    L.lfx_place_db_add_host.argtypes = [vp, vp, vp, u32, vp]
+    L.lfx_place_db_size.argtypes = [vp, C.POINTER(u32)]
+    L.lfx_place_db_download.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_place_db_query.argtypes = [vp, vp, vp, u32, u32, u32, u32, C.POINTER(PlaceMatch), vp]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_xyz12.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_colored.argtypes = [vp, vp, vp, C.c_size_t, vp]

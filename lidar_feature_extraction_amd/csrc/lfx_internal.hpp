@@ -288,6 +288,27 @@ struct lfx_ctx
   uint32_t deskew_next = 0;
   bool deskewed_in_place = false;
 
+  // lfx_scan_context_batch (lfx_place.hip): a call's tables go out as the de-skew's do, through the next of a ring of slots,
+  // each a pinned block, a device table, the call's cell keys ([scans][R * S] u32) and an event behind the kernels that use
+  // them.  A slot owns its event (the context's destruction waits for it and lets it go).
+  static constexpr uint32_t kPlaceSlots = 4;
+  struct PlaceSlot
+  {
+    lfx_host::PinnedBuf h;
+    lfx_host::DevBuf<double> d;
+    lfx_host::DevBuf<uint32_t> keys;
+    hipEvent_t used = nullptr;           // recorded behind the kernel that turned keys into the caller's floats
+    PlaceSlot() = default;
+    PlaceSlot(const PlaceSlot &) = delete;
+    PlaceSlot & operator=(const PlaceSlot &) = delete;
+    ~PlaceSlot()
+    {
+      if (used) {(void)hipEventSynchronize(used); (void)hipEventDestroy(used);}
+    }
+  };
+  PlaceSlot place_slots[kPlaceSlots];
+  uint32_t place_next = 0;
+
   hipStream_t stream = nullptr;          // used by the synchronous host entry points
   std::vector<uint32_t> h_scan_begin;    // of the last batch
   std::vector<uint32_t> h_scan_geom;     // [batch][kGeomStride]: columns per ring and block boundaries of every scan (organised-scan kernel)

@@ -1,0 +1,294 @@
+// lfx_place.hip -- place recognition (include/lfx.h, the place recognition section; lfx_kernels_place.hpp):
+// lfx_scan_context_batch, the descriptors of the last device batch's scans from its input records, and lfx_place_db, the
+// index that compares query descriptors with every entry under every column shift.  The descriptor's tables come from
+// lfx_scan_context_tables (lfx_pose.cpp) and from nowhere else.
+#include "lfx_internal.hpp"
+#include "lfx_kernels_place.hpp"
+
+#include <cstdint>
+
+using namespace lfx_host;
+
+struct lfx_place_db
+{
+  int device = 0;
+  lfx_scan_context_config cfg{};
+  uint32_t capacity = 0, n = 0;
+  DevBuf<float> desc;                        // [capacity][R][S]
+  DevBuf<double> norms;                      // [capacity][S]
+  DevBuf<float> staged;                      // lfx_place_db_add_host: the descriptors on their way up
+  // a query's workspace: the queries' norms, the least distance and its shift per (query, entry), the matches
+  mutable DevBuf<double> query_norms, best_distance;
+  mutable DevBuf<uint32_t> best_shift;
+  mutable DevBuf<lfx::PlaceMatchDevice> matches;
+  mutable PinnedBuf h_matches;
+  hipEvent_t added = nullptr;                // recorded behind the last add's copy and norms
+  bool add_pending = false;
+};
+
+namespace
+{
+uint32_t cells_of(const lfx_scan_context_config & cfg) {return cfg.n_rings * cfg.n_sectors;}
+
+int check_db(lfx_ctx * c, const lfx_place_db * db)
+{
+  if (db->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the place index lives on another device");}
+  return LFX_OK;
+}
+
+// the config's tables as the kernel takes them (sc_table_doubles), or what lfx_scan_context_tables refuses
+int write_tables(lfx_ctx * c, const lfx_scan_context_config * cfg, double * out)
+{
+  // (checked here first: the arrays below are sized by R and S)
+  if (cfg->n_rings < 1u || cfg->n_rings > LFX_SCAN_CONTEXT_MAX_RINGS || cfg->n_sectors < 4u || cfg->n_sectors > LFX_SCAN_CONTEXT_MAX_SECTORS) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_rings must be in 1 .. 40 and n_sectors even, in 4 .. 120");
+  }
+  const uint32_t R = cfg->n_rings, S = cfg->n_sectors;
+  if (lfx_scan_context_tables(cfg, out, out + S, out + 2u * S) != LFX_OK) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "the scan-context config is refused: n_sectors even, radii finite with 0 <= min_radius < max_radius, "
+             "sensor_height finite");
+  }
+  out[2u * S + R + 1u] = (double)cfg->min_radius * (double)cfg->min_radius;
+  return LFX_OK;
+}
+
+// the ring's next slot with room for the call's table and keys, the kernels that used it last waited for; a failure leaves
+// the ring where it was
+int take_slot(lfx_ctx * c, size_t doubles, size_t keys, lfx_ctx::PlaceSlot *& slot)
+{
+  LFX_HIP(c, hipSetDevice(c->device));
+  slot = &c->place_slots[c->place_next];
+  if (!slot->used) {LFX_HIP(c, hipEventCreateWithFlags(&slot->used, hipEventDisableTiming));}
+  LFX_HIP(c, hipEventSynchronize(slot->used));
+  hipError_t e = slot->h.reserve(sizeof(double) * doubles);
+  if (e == hipSuccess) {e = hold(slot->d, doubles);}
+  if (e == hipSuccess) {e = hold(slot->keys, keys);}
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, std::string("cannot set up the scan-context tables: ") + hipGetErrorString(e));
+  }
+  c->place_next = (c->place_next + 1u) % lfx_ctx::kPlaceSlots;
+  return LFX_OK;
+}
+
+// place_compare_kernel may ask for more dynamic LDS than a kernel gets unasked (82 KB at R = 40, S = 120)
+int allow_compare_lds(lfx_ctx * c)
+{
+  LFX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::place_compare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (int)lfx::place_compare_lds(LFX_SCAN_CONTEXT_MAX_RINGS, LFX_SCAN_CONTEXT_MAX_SECTORS)));
+  return LFX_OK;
+}
+
+int launch_norms(lfx_ctx * c, const float * d_desc, double * d_norms, uint32_t n, const lfx_scan_context_config & cfg, hipStream_t st)
+{
+  const size_t threads = (size_t)n * cfg.n_sectors;
+  hipLaunchKernelGGL(lfx::place_norms_kernel, dim3((uint32_t)((threads + lfx::kPlaceThreads - 1) / lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
+    d_desc, d_norms, n, cfg.n_rings, cfg.n_sectors);
+  LFX_HIP(c, hipGetLastError());
+  return LFX_OK;
+}
+
+// n descriptors on the device appended: all or nothing
+int add_device(lfx_ctx * c, lfx_place_db * db, const float * d_desc, uint32_t n, hipStream_t st)
+{
+  const size_t cells = cells_of(db->cfg);
+  float * dst = db->desc.p + (size_t)db->n * cells;
+  // (the add before may be queued on another stream: the event below then stands for both)
+  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  // (hipMemcpyDefault: d_desc may be pinned host memory, lfx_host_alloc, which a kernel writes as it writes device memory)
+  LFX_HIP(c, hipMemcpyAsync(dst, d_desc, sizeof(float) * cells * n, hipMemcpyDefault, st));
+  const int rc = launch_norms(c, dst, db->norms.p + (size_t)db->n * db->cfg.n_sectors, n, db->cfg, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipEventRecord(db->added, st));
+  db->add_pending = true;
+  db->n += n;
+  return LFX_OK;
+}
+
+int check_add(lfx_ctx * c, const lfx_place_db * db, uint32_t n)
+{
+  if (check_db(c, db) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (n > db->capacity - db->n) {
+    return fail(c, LFX_ERR_CAPACITY, "the place index holds " + std::to_string(db->n) + " of " + std::to_string(db->capacity) + " entries: no room for " +
+             std::to_string(n) + " more");
+  }
+  return LFX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32_t n_scans, float * d_desc_out, void * stream)
+{
+  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!cfg || !d_desc_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "config and d_desc_out are required");}
+  double table[2 * LFX_SCAN_CONTEXT_MAX_SECTORS + LFX_SCAN_CONTEXT_MAX_RINGS + 2];
+  const int rt = write_tables(c, cfg, table);
+  if (rt != LFX_OK) {return rt;}
+  const int rb = check_last_batch(c, n_scans);
+  if (rb != LFX_OK) {return rb;}
+  if (!c->last_points) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch's input points are not known");}
+  const uint32_t R = cfg->n_rings, S = cfg->n_sectors;
+  const size_t doubles = lfx::sc_table_doubles(R, S), total = (size_t)n_scans * R * S;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  lfx_ctx::PlaceSlot * slot;
+  const int rs = take_slot(c, doubles, total, slot);
+  if (rs != LFX_OK) {return rs;}
+  std::memcpy(slot->h.p, table, sizeof(double) * doubles);
+  LFX_HIP(c, hipMemcpyAsync(slot->d.p, slot->h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemsetAsync(slot->keys.p, 0, sizeof(uint32_t) * total, st));
+  lfx::ScanContextArgs a{};
+  a.pts = static_cast<const uint8_t *>(c->last_points);
+  a.L = c->layout;
+  a.scan_begin = c->scan_begin.p;
+  a.table = slot->d.p;
+  a.keys = slot->keys.p;
+  a.R = R; a.S = S;
+  const lfx::Layout & L = c->layout;
+  const bool xyz16 = L.step == 32u && L.ox == 0u && L.oy == 4u && L.oz == 8u && !L.be && (reinterpret_cast<uintptr_t>(a.pts) & 15u) == 0u;
+  // (a scan of 64 x 1800 has 115 k records: 32 workgroups walk them in 15 steps; large batches fill the device with fewer)
+  const dim3 grid(n_scans >= 32u ? 8u : 32u, n_scans);
+  hipLaunchKernelGGL(xyz16 ? lfx::scan_context_kernel<true> : lfx::scan_context_kernel<false>, grid, dim3(lfx::kPlaceThreads), 0, st, a);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::scan_context_finish_kernel, dim3((uint32_t)((total + lfx::kPlaceThreads - 1) / lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
+    slot->keys.p, d_desc_out, total, cfg->sensor_height);
+  LFX_HIP(c, hipGetLastError());
+  LFX_HIP(c, hipEventRecord(slot->used, st));
+  return LFX_OK;
+}
+
+int lfx_place_db_create(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32_t capacity, lfx_place_db ** out)
+{
+  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!cfg || !out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "config and out are required");}
+  double table[2 * LFX_SCAN_CONTEXT_MAX_SECTORS + LFX_SCAN_CONTEXT_MAX_RINGS + 2];
+  const int rt = write_tables(c, cfg, table);
+  if (rt != LFX_OK) {return rt;}
+  if (capacity == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "capacity must be >= 1");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int ra = allow_compare_lds(c);
+  if (ra != LFX_OK) {return ra;}
+  lfx_place_db * db = new (std::nothrow) lfx_place_db();
+  if (!db) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the place index");}
+  db->device = c->device;
+  db->cfg = *cfg;
+  db->capacity = capacity;
+  auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_place_db_destroy(db); return fail(c, code, why);};
+  if (db->desc.alloc((size_t)capacity * cells_of(*cfg)) != hipSuccess || db->norms.alloc((size_t)capacity * cfg->n_sectors) != hipSuccess) {
+    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the place index's descriptors");
+  }
+  if (hipEventCreateWithFlags(&db->added, hipEventDisableTiming) != hipSuccess) {
+    db->added = nullptr;
+    return give_up(LFX_ERR_HIP, "cannot create the place index's event");
+  }
+  *out = db;
+  return LFX_OK;
+}
+
+void lfx_place_db_destroy(lfx_place_db * db)
+{
+  if (!db) {return;}
+  (void)hipSetDevice(db->device);
+  if (db->added) {(void)hipEventSynchronize(db->added); (void)hipEventDestroy(db->added);}
+  delete db;
+}
+
+int lfx_place_db_add(lfx_ctx * c, lfx_place_db * db, const float * d_desc, uint32_t n, void * stream)
+{
+  if (!c || !db || (n && !d_desc)) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int rc = check_add(c, db, n);
+  if (rc != LFX_OK || n == 0) {return rc;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  return add_device(c, db, d_desc, n, static_cast<hipStream_t>(stream));
+}
+
+int lfx_place_db_add_host(lfx_ctx * c, lfx_place_db * db, const float * desc, uint32_t n, void * stream)
+{
+  if (!c || !db || (n && !desc)) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int rc = check_add(c, db, n);
+  if (rc != LFX_OK || n == 0) {return rc;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // (the add before may still read the staged descriptors, on whichever stream)
+  if (db->add_pending) {LFX_HIP(c, hipEventSynchronize(db->added)); db->add_pending = false;}
+  const size_t floats = (size_t)n * cells_of(db->cfg);
+  if (hold(db->staged, floats) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the descriptors");}
+  LFX_HIP(c, hipMemcpyAsync(db->staged.p, desc, sizeof(float) * floats, hipMemcpyHostToDevice, st));
+  // (pageable memory has been read when the copy returns; a pinned block must not be rewritten before `stream` passes it)
+  return add_device(c, db, db->staged.p, n, st);
+}
+
+int lfx_place_db_size(const lfx_place_db * db, uint32_t * n)
+{
+  if (!db || !n) {return LFX_ERR_INVALID_ARGUMENT;}
+  *n = db->n;
+  return LFX_OK;
+}
+
+int lfx_place_db_download(lfx_ctx * c, const lfx_place_db * db, uint32_t first, uint32_t count, float * desc_out, void * stream)
+{
+  if (!c || !db || (count && !desc_out)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_db(c, db) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (first > db->n || count > db->n - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "entries outside the place index");}
+  if (count == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  const size_t cells = cells_of(db->cfg);
+  LFX_HIP(c, hipMemcpyAsync(desc_out, db->desc.p + (size_t)first * cells, sizeof(float) * cells * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  return LFX_OK;
+}
+
+int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_desc, uint32_t n_queries, uint32_t first, uint32_t count,
+  uint32_t k, lfx_place_match * matches, void * stream)
+{
+  if (!c || !db || !d_desc || !matches) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_db(c, db) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (n_queries == 0 || n_queries > 65535u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_queries must be in 1 .. 65535");}
+  if (k < 1u || k > LFX_PLACE_MAX_MATCHES) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "k must be in 1 .. 16");}
+  if (first > db->n || count > db->n - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "entries outside the place index");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t R = db->cfg.n_rings, S = db->cfg.n_sectors;
+  const size_t cells = (size_t)R * S, pairs = (size_t)n_queries * count, n_matches = (size_t)n_queries * k;
+  if (hold(db->query_norms, (size_t)n_queries * S) != hipSuccess || hold(db->best_distance, pairs) != hipSuccess ||
+    hold(db->best_shift, pairs) != hipSuccess || hold(db->matches, n_matches) != hipSuccess ||
+    db->h_matches.reserve(sizeof(lfx::PlaceMatchDevice) * n_matches) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
+  }
+  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  lfx_scan_context_config cfg = db->cfg;
+  const int rn = launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st);
+  if (rn != LFX_OK) {return rn;}
+  if (count) {
+    lfx::PlaceCompareArgs a{};
+    a.query = d_desc; a.query_norms = db->query_norms.p;
+    a.entries = db->desc.p + (size_t)first * cells; a.entry_norms = db->norms.p + (size_t)first * S;
+    a.best_distance = db->best_distance.p; a.best_shift = db->best_shift.p;
+    a.count = count; a.R = R; a.S = S;
+    a.tile = lfx::place_tile(S, pairs);
+    const dim3 grid((count + a.tile - 1u) / a.tile, n_queries);
+    hipLaunchKernelGGL(lfx::place_compare_kernel, grid, dim3(lfx::kPlaceThreads), (uint32_t)lfx::place_compare_lds(R, S), st, a);
+    LFX_HIP(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(lfx::place_select_kernel, dim3(n_queries), dim3(lfx::kPlaceThreads), 0, st, db->best_distance.p, db->best_shift.p, count, first, k,
+    db->matches.p);
+  LFX_HIP(c, hipGetLastError());
+  LFX_HIP(c, hipMemcpyAsync(db->h_matches.p, db->matches.p, sizeof(lfx::PlaceMatchDevice) * n_matches, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  const lfx::PlaceMatchDevice * got = reinterpret_cast<const lfx::PlaceMatchDevice *>(db->h_matches.p);
+  const double step = (2.0 * M_PI) / (double)S;
+  for (size_t i = 0; i < n_matches; i++) {
+    lfx_place_match & m = matches[i];
+    m.entry = got[i].entry;
+    m.shift = got[i].shift;
+    m.distance = got[i].distance;
+    m.yaw = got[i].entry == UINT32_MAX ? 0.0 : (2u * got[i].shift <= S ? (double)got[i].shift * step : ((double)got[i].shift - (double)S) * step);
+  }
+  return LFX_OK;
+}
+
+}  // extern "C"

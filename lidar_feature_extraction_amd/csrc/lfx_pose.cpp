@@ -242,4 +242,35 @@ int lfx_align_covariance_ros(const double pose[12], const double covariance[36],
   return LFX_OK;
 }
 
+// Scan-context descriptors (include/lfx.h, the place recognition section): the defaults, and the tables the kernel is given.
+void lfx_scan_context_default_config(lfx_scan_context_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_scan_context_config{};
+  config->n_rings = 20;
+  config->n_sectors = 60;
+  config->max_radius = 80.0f;
+  config->min_radius = 0.1f;
+  config->sensor_height = 2.0f;
+}
+
+int lfx_scan_context_tables(const lfx_scan_context_config * config, double * sector_cos, double * sector_sin, double * ring_r2)
+{
+  if (!config || !sector_cos || !sector_sin || !ring_r2) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint32_t R = config->n_rings, S = config->n_sectors;
+  if (R < 1u || R > LFX_SCAN_CONTEXT_MAX_RINGS || S < 4u || S > LFX_SCAN_CONTEXT_MAX_SECTORS || (S & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(config->max_radius) || !std::isfinite(config->min_radius) || !std::isfinite(config->sensor_height)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!(config->min_radius >= 0.0f) || !(config->min_radius < config->max_radius)) {return LFX_ERR_INVALID_ARGUMENT;}
+  for (uint32_t m = 0; m < S; m++) {
+    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)S;
+    sector_cos[m] = std::cos(angle);
+    sector_sin[m] = std::sin(angle);
+  }
+  for (uint32_t j = 0; j <= R; j++) {
+    const double e = ((double)config->max_radius * (double)j) / (double)R;
+    ring_r2[j] = e * e;
+  }
+  return LFX_OK;
+}
+
 }  // extern "C"

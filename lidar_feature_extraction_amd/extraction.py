@@ -130,6 +130,7 @@ class FeatureExtraction:
             raise B.LfxError(rc, (self._L.lfx_last_error(None) or b"").decode())
         self.max_batch = max_batch
         self.max_points_per_scan = max_points_per_scan
+        self.device = device
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:
@@ -414,6 +415,26 @@ class FeatureExtraction:
         B.check(self._ctx, self._L.lfx_deskew_batch_trajectory(
             self._ctx, C.byref(tf), tr, n, C.c_void_p(int(e) or None), C.c_void_p(int(s) or None), C.c_void_p(int(stream))), self._L)
 
+    def scan_context(self, config=None, out=None, stream=0):
+        """lfx_scan_context_batch: the scan-context descriptor of every scan of the last device batch, from the batch's input
+        records (which must still be alive).  config: None (the defaults: 20 rings x 60 sectors out to 80 m), a dict of
+        lfx_scan_context_config's fields or a B.ScanContextConfig; out: None = a new float32 device tensor [n_scans][R][S] is
+        returned, or the device address of such a buffer (nothing is returned).  Asynchronous on `stream`."""
+        cfg = scan_context_config(config)
+        n = int(self.device_view().batch)
+        made = None
+        if out is None:
+            import torch
+            made = torch.empty((n, cfg.n_rings, cfg.n_sectors), dtype=torch.float32, device=torch.device("cuda", self.device))
+            out = made.data_ptr()
+        B.check(self._ctx, self._L.lfx_scan_context_batch(self._ctx, C.byref(cfg), n, C.c_void_p(int(out) or None),
+                                                          C.c_void_p(int(stream))), self._L)
+        return made
+
+    def place_db(self, capacity, config=None):
+        """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
+        return PlaceDb(self, capacity, config)
+
     def download(self, scan, stream=0):
         r = B.ScanResult()
         B.check(self._ctx, self._L.lfx_download_scan(self._ctx, scan, C.c_void_p(int(stream)), C.byref(r)), self._L)
@@ -626,6 +647,35 @@ def trajectory_from_gyro(times, rates, bias=None, velocity=None):
     if B.load().lfx_trajectory_from_gyro(_pd(t), _pd(r), len(t), None if b is None else _pd(b), None if v is None else _pd(v), _pd(out)) != 0:
         raise B.LfxError(-1, "invalid gyro samples")
     return out
+
+
+def scan_context_config(config=None, **fields):
+    """lfx_scan_context_config: the defaults (lfx_scan_context_default_config) with the given fields replaced.  config: None,
+    a dict of fields, or a B.ScanContextConfig (copied)."""
+    cfg = B.ScanContextConfig()
+    if isinstance(config, B.ScanContextConfig):
+        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        config = None
+    else:
+        B.load().lfx_scan_context_default_config(C.byref(cfg))
+    for k, v in dict(config or {}, **fields).items():
+        if k not in dict(B.ScanContextConfig._fields_):
+            raise TypeError("unknown scan-context setting %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def scan_context_tables(config=None):
+    """lfx_scan_context_tables: (sector_cos [S], sector_sin [S], ring_r2 [R + 1]), float64 -- the tables the descriptor kernel is
+    given, and the only source of them.  Host only."""
+    cfg = scan_context_config(config)
+    S, R = int(cfg.n_sectors), int(cfg.n_rings)
+    # (sized for any config: a refused one must not write past the arrays before it is refused -- it writes nothing)
+    cs, sn, r2 = np.zeros(max(S, 1)), np.zeros(max(S, 1)), np.zeros(R + 1)
+    rc = B.load().lfx_scan_context_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(r2))
+    if rc != 0:
+        raise B.LfxError(rc, "the scan-context config is refused")
+    return cs[:S], sn[:S], r2
 
 
 def _msg_buffer():
@@ -968,6 +1018,77 @@ class Mapper:
     def close(self):
         if self.handle:
             self._L.lfx_mapper_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlaceDb:
+    """lfx_place_db: scan-context descriptors of one config on the device, compared with a query under every column shift.
+    Entries are numbered in insertion order.  A match is a dict: entry (None where the range held fewer than k entries),
+    shift, distance, yaw -- a sensor that revisits the entry's place turned by +yaw about z gives that shift, so the revisit's
+    initial pose is the entry's pose times Rz(yaw)."""
+
+    def __init__(self, fx, capacity, config=None):
+        self._fx = fx
+        self._L = fx._L
+        self.config = scan_context_config(config)
+        self.shape = (int(self.config.n_rings), int(self.config.n_sectors))
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_place_db_create(fx._ctx, C.byref(self.config), int(capacity), C.byref(h)), self._L)
+        self.handle = h
+        self.capacity = int(capacity)
+
+    def add(self, d_desc, n, stream=0):
+        """lfx_place_db_add: n descriptors ([n][R][S] float32) at device address d_desc (or a device tensor), appended."""
+        ptr = d_desc.data_ptr() if hasattr(d_desc, "data_ptr") else int(d_desc)
+        B.check(self._fx._ctx, self._L.lfx_place_db_add(self._fx._ctx, self.handle, C.c_void_p(ptr or None), int(n), C.c_void_p(int(stream))),
+                self._L)
+
+    def add_host(self, desc, stream=0):
+        """lfx_place_db_add_host: descriptors ([n][R][S] float32) on the host, appended."""
+        d = np.ascontiguousarray(desc, np.float32).reshape((-1,) + self.shape)
+        B.check(self._fx._ctx, self._L.lfx_place_db_add_host(
+            self._fx._ctx, self.handle, C.c_void_p(d.ctypes.data if len(d) else None), len(d), C.c_void_p(int(stream))), self._L)
+
+    def __len__(self):
+        n = C.c_uint32(0)
+        B.check(self._fx._ctx, self._L.lfx_place_db_size(self.handle, C.byref(n)), self._L)
+        return int(n.value)
+
+    def download(self, first=0, count=None, stream=0):
+        """lfx_place_db_download: entries first .. first + count - 1 ([count][R][S] float32) on the host."""
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0),) + self.shape, np.float32)
+        B.check(self._fx._ctx, self._L.lfx_place_db_download(
+            self._fx._ctx, self.handle, int(first), count, C.c_void_p(out.ctypes.data if out.size else None), C.c_void_p(int(stream))), self._L)
+        return out
+
+    def query_raw(self, d_desc, n_queries, k=1, first=0, count=None, stream=0):
+        """lfx_place_db_query as it returns: a B.PlaceMatch array [n_queries * k]."""
+        ptr = d_desc.data_ptr() if hasattr(d_desc, "data_ptr") else int(d_desc)
+        count = len(self) - int(first) if count is None else int(count)
+        res = (B.PlaceMatch * max(int(n_queries) * int(k), 1))()
+        B.check(self._fx._ctx, self._L.lfx_place_db_query(
+            self._fx._ctx, self.handle, C.c_void_p(ptr or None), int(n_queries), int(first), count, int(k), res, C.c_void_p(int(stream))),
+            self._L)
+        return res
+
+    def query(self, d_desc, n_queries, k=1, first=0, count=None, stream=0):
+        """The k (1 .. 16) best of entries [first, first + count) for each of n_queries descriptors on the device: a list per
+        query of k dicts, ascending distance, equal distances by the lower entry.  Synchronous."""
+        res = self.query_raw(d_desc, n_queries, k, first, count, stream)
+        k = int(k)
+        return [[dict(entry=None if m.entry == B.PLACE_NO_ENTRY else int(m.entry), shift=int(m.shift), distance=float(m.distance),
+                      yaw=float(m.yaw)) for m in res[q * k:(q + 1) * k]] for q in range(int(n_queries))]
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_place_db_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
