@@ -757,6 +757,108 @@ int lfx_mapper_view(const lfx_mapper *mapper, lfx_mapper_store_view *view);
  * map read on `stream`, *written = 1.  Synchronous. */
 int lfx_mapper_save(lfx_ctx *ctx, const lfx_mapper *mapper, const char *path, int *written, void *stream);
 
+/* --- the rolling voxel map: one point per voxel in a window that follows the vehicle ------------------------------------- */
+/* The map LOAM's mapping stage keeps (no reference counterpart): bounded in memory, cheap to insert into and to cut a local
+ * map from.  Two stores, LFX_ROLLING_EDGE and LFX_ROLLING_SURFACE, each a direct-mapped, tagged voxel array with a leaf size
+ * and a window of dims[3] voxels (any positive sizes; their product at most 2^31); 32 bytes per voxel (key, stamp, point).
+ *   voxel    v_a = (int32)floorf(p_a * inv), inv = 1.0f / leaf in float (as lfx_voxel_downsample).  A point with a coordinate
+ *            that is not finite or with |floorf(..)| >= 2^20 on an axis is dropped and counted as nonfinite.
+ *   key      1 << 63 | (vx & 0x1FFFFF) | (vy & 0x1FFFFF) << 21 | (vz & 0x1FFFFF) << 42; 0 = never written.
+ *   slot     s_a = v_a mod dims_a (non-negative); slot = (s_z * dims_y + s_y) * dims_x + s_x.
+ *   window   origin o[3] in voxels, o_a <= v_a < o_a + dims_a; o_a = -(dims_a / 2) at create.  Moving it is host arithmetic:
+ *            nothing on the device is touched.
+ *   live     voxel v is live iff it lies in the window and keys[slot(v)] == key(v).  A slot that holds another voxel's key
+ *            reads as empty and is overwritten by an insert.  A voxel that left the window and comes back is live again
+ *            unless another voxel has taken its slot meanwhile.  Inside the window voxel -> slot is injective.
+ *   insert   every record transformed by its cloud's pose (the odometry's and the mapper's transform: same bits).  Outside
+ *            the window: dropped, counted as outside.  In a live voxel: counted as merged, the stored point stays.  Among the
+ *            records of one call in the same voxel that is not live the one of the lowest rank is stored, all four floats
+ *            (inserted), and the others count as merged; rank is (cloud index, index in the cloud), whatever order d_begin
+ *            is in and however the device schedules the call.  inserted + merged + outside + nonfinite = records given.
+ *   extract  the box lo .. hi (metres) is the voxels voxel(lo) .. voxel(hi) inclusive per axis ((float)lo_a through the voxel
+ *            rule, clamped to [-2^20, 2^20 - 1]), clipped to the window; its live voxels' points in ascending (vz, vy, vx),
+ *            x fastest.  hi < lo on an axis: no points.
+ * Calls on one map are ordered behind its last insert whichever streams they use; an insert behind an extraction on another
+ * stream is the caller's to order.  The map must be used with a context of the device it was created on. */
+typedef struct lfx_rolling_map lfx_rolling_map;
+#define LFX_ROLLING_EDGE 0
+#define LFX_ROLLING_SURFACE 1
+typedef struct lfx_rolling_map_config {
+  float edge_leaf, surface_leaf;           /* metres: 0.2, 0.4 */
+  uint32_t edge_dims[3], surface_dims[3];  /* voxels: 512, 512, 128 and 256, 256, 64 (102.4 x 102.4 x 25.6 m each; 1.2 GB) */
+  /* lfx_rolling_map_update_batch: */
+  float match_half_extent[3];              /* metres: the box around a scan's pose it is aligned against: 50, 50, 12.8 */
+  uint32_t n_neighbors;                    /* 15; in [3, 16] */
+  int32_t max_iter;                        /* 20 */
+  float scan_surface_leaf;                 /* Downsample of a scan's surface cloud before its rows: 1.0 */
+  float edge_cell, surface_cell;           /* grids of the two box maps, as lfx_map_create: 1.0 (0: no grid) */
+  double initial_pose[12];                 /* identity */
+} lfx_rolling_map_config;
+void lfx_rolling_map_default_config(lfx_rolling_map_config *config);
+/* A leaf <= 0 or not finite, a dimension of 0, a window of more than 2^31 voxels, n_neighbors outside [3, 16], max_iter < 1, a
+ * negative extent or cell and an initial pose that is not finite are LFX_ERR_INVALID_ARGUMENT; a failed allocation is
+ * LFX_ERR_OUT_OF_MEMORY with nothing left allocated. */
+int lfx_rolling_map_create(lfx_ctx *ctx, const lfx_rolling_map_config *config, lfx_rolling_map **out);
+void lfx_rolling_map_destroy(lfx_rolling_map *map);
+/* Both windows centred on `center` (metres): o_a = voxel((float)center_a) - dims_a / 2 per kind.  O(1), no device work.  A
+ * centre that is not finite or has no voxel is LFX_ERR_INVALID_ARGUMENT. */
+int lfx_rolling_map_recenter(lfx_rolling_map *map, const double center[3]);
+/* n_clouds device clouds into the store of `kind`, addressed as lfx_mapper_add's (cloud s: d_count[s * count_stride] records
+ * from record d_begin[s] of d_points; total_points the extent of d_points in records); poses: host [n_clouds][12], finite.
+ * One wait (the counts and begins), then two launches; they may still be queued on `stream` when the call returns.  A call
+ * of more than 2^32 - 2 records is LFX_ERR_CAPACITY. */
+int lfx_rolling_map_insert(lfx_ctx *ctx, lfx_rolling_map *map, int kind, const float *d_points, const uint32_t *d_begin,
+                           const uint32_t *d_count, uint32_t count_stride, uint32_t n_clouds, size_t total_points,
+                           const double *poses /* host [n][12] */, void *stream);
+/* The same for one cloud on the host, staged through a device buffer of the map's own; the cloud has been read on return. */
+int lfx_rolling_map_insert_host(lfx_ctx *ctx, lfx_rolling_map *map, int kind, const float *points, uint32_t n_points,
+                                const double pose[12], void *stream);
+/* The live voxels of a box as records of 4 floats to d_out (the lfx_pack_* convention: nothing is written at or past
+ * capacity_points, *n_points is the full need; d_out may be NULL with capacity 0).  Waits: *n_points is final on return. */
+int lfx_rolling_map_extract(lfx_ctx *ctx, const lfx_rolling_map *map, int kind, const double lo[3], const double hi[3],
+                            float *d_out, uint64_t capacity_points, uint64_t *n_points /* host */, void *stream);
+typedef struct lfx_rolling_map_view_t {    /* [0] the edge store, [1] the surface store */
+  float leaf[2];
+  uint32_t dims[2][3];
+  int32_t origin[2][3];
+  uint64_t n_inserted[2], n_merged[2], n_outside[2], n_nonfinite[2];   /* records, summed since create */
+  uint64_t n_live[2];                      /* live voxels in the window now (a count pass over the window) */
+  double pose[12], correction[12];         /* lfx_rolling_map_update_batch's current pose and C (map <- odometry frame) */
+} lfx_rolling_map_view_t;
+/* (the type is named apart from the function, as lfx_mapper_store_view is)  Waits for the counters and the count passes. */
+int lfx_rolling_map_view(lfx_ctx *ctx, const lfx_rolling_map *map, lfx_rolling_map_view_t *view, void *stream);
+/* edge.pcd and surface.pcd of the whole windows under dirname through lfx_pcd_write, as lfx_odometry_save: an empty store
+ * writes no file (written[k] = 0).  With lfx_pcd_read and lfx_rolling_map_insert_host at the identity pose this seeds a map
+ * of the same leaves from disk: a stored point is its own voxel's representative (the 4th float comes back as 1).
+ * Synchronous. */
+int lfx_rolling_map_save(lfx_ctx *ctx, const lfx_rolling_map *map, const char *dirname, int written[2], void *stream);
+/* LOAM's mapping stage for every scan k of the last device batch, in order (n_scans = the batch's size).  odometry_poses:
+ * host [n_scans][12], the scans' poses in an odometry's frame (lfx_odometry_update_batch's results), or NULL.
+ *   1  initial = C x odom_k; C (map <- odometry frame) is the identity at create.  With NULL the initial pose is the current
+ *      pose (config.initial_pose at create).  Poses compose in double, every 3-term sum as (a0 b0 + a1 b1) + a2 b2, the
+ *      translation's as that sum + t; the inverse of a pose is [R^T | -(R^T t)] with the same sums.
+ *   2  with t the initial translation: if for either kind on any axis |voxel(t_a) - (o_a + dims_a / 2)| > dims_a / 4, both
+ *      windows are recentred at t (recentered 1).
+ *   3  the boxes t -+ match_half_extent are extracted from both stores and indexed as lfx_map_create does (cells edge_cell /
+ *      surface_cell); the scan's surface cloud is downsampled by scan_surface_leaf, once per batch up front.
+ *   4  a box under n_neighbors points: the scan is not aligned (aligned 0, LFX_ALIGN_NOT_RUN), pose = initial, both raw
+ *      clouds inserted at it (inserted 1).
+ *   5  else the alignment of lfx_scan_to_map_align from the initial pose (aligned 1).  LFX_ALIGN_SUCCESS(code): pose = the
+ *      result's, C = pose x odom_k^-1, both raw clouds inserted at the pose (inserted 1).
+ *   6  otherwise the current pose becomes the initial pose, C stays and nothing is inserted (inserted 0).
+ * The context's batch results stay as they were.  Results are final on return; the last insert may still be queued on
+ * `stream`.  An initial pose that is not finite or whose translation has no voxel is LFX_ERR_INVALID_ARGUMENT. */
+typedef struct lfx_rolling_map_result {
+  lfx_align_result align;
+  double initial_pose[12];
+  uint32_t n_edge_map, n_surface_map;      /* points of the two boxes the scan was aligned against */
+  int32_t aligned, inserted, recentered;
+} lfx_rolling_map_result;
+int lfx_rolling_map_update_batch(lfx_ctx *ctx, lfx_rolling_map *map, uint32_t n_scans, const double *odometry_poses /* host [n][12] or NULL */,
+                                 lfx_rolling_map_result *results, void *stream);
+/* The current pose: the pose of the last scan lfx_rolling_map_update_batch went through. */
+int lfx_rolling_map_pose(const lfx_rolling_map *map, double pose[12]);
+
 /* --- de-skew: the sensor's motion during a sweep taken out of the feature clouds ------------------------------------------ */
 /* A spinning lidar reports every point in the sensor frame of its own firing time; everything above treats a scan as one
  * instant.  No reference counterpart (the reference has an unused imu_integration package beside its pipeline); the model

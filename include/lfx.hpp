@@ -575,6 +575,102 @@ private:
   std::vector<std::uint8_t> outcomes_;
 };
 
+// The rolling voxel map (lfx_rolling_map): one point per voxel in a window that follows the vehicle, an edge store and a
+// surface store on the device of `fx`, which must outlive it -- the map LOAM's mapping stage keeps.  Update() aligns every
+// scan the FeatureExtraction was last given against the boxes cut out around its initial pose and inserts it at the result;
+// fed an Odometry's poses of the same scans it corrects them against everything the window still holds.  Poses are
+// [R | t], row-major 3 x 4.
+class RollingMap
+{
+public:
+  enum Kind {kEdge = LFX_ROLLING_EDGE, kSurface = LFX_ROLLING_SURFACE};
+  static lfx_rolling_map_config DefaultConfig() {lfx_rolling_map_config c; lfx_rolling_map_default_config(&c); return c;}
+  explicit RollingMap(const FeatureExtraction & fx, const lfx_rolling_map_config & config = DefaultConfig())
+  : ctx_(fx.handle())
+  {
+    const int rc = lfx_rolling_map_create(ctx_, &config, &map_);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  ~RollingMap() {lfx_rolling_map_destroy(map_);}
+  RollingMap(const RollingMap &) = delete;
+  RollingMap & operator=(const RollingMap &) = delete;
+  RollingMap(RollingMap && o) noexcept : ctx_(o.ctx_), map_(o.map_), results_(std::move(o.results_)) {o.map_ = nullptr;}
+  RollingMap & operator=(RollingMap && o) noexcept
+  {
+    if (this != &o) {
+      lfx_rolling_map_destroy(map_);
+      ctx_ = o.ctx_; map_ = o.map_; results_ = std::move(o.results_);
+      o.map_ = nullptr;
+    }
+    return *this;
+  }
+
+  // lfx_rolling_map_update_batch for every scan the FeatureExtraction was last given; odometry_poses: 12 doubles per scan
+  // (an Odometry's results for the same scans), or empty: every scan starts from the current pose
+  const std::vector<lfx_rolling_map_result> & Update(const std::vector<double> & odometry_poses = {})
+  {
+    lfx_device_view view{};
+    int rc = lfx_device_results(ctx_, &view);
+    if (rc == LFX_OK && !odometry_poses.empty() && odometry_poses.size() != 12 * static_cast<std::size_t>(view.batch)) {
+      throw Error(LFX_ERR_INVALID_ARGUMENT, "odometry_poses must hold 12 doubles per scan");
+    }
+    if (rc == LFX_OK) {
+      results_.assign(view.batch, lfx_rolling_map_result{});
+      rc = lfx_rolling_map_update_batch(ctx_, map_, view.batch, odometry_poses.empty() ? nullptr : odometry_poses.data(), results_.data(),
+        nullptr);
+    }
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_;
+  }
+  void Recenter(const double center[3])
+  {
+    const int rc = lfx_rolling_map_recenter(map_, center);
+    if (rc != LFX_OK) {throw Error(rc, "the centre must be finite and have a voxel");}
+  }
+  // one cloud received from elsewhere (4 floats per point) into the edge or the surface store at `pose`
+  void Insert(Kind kind, const float * points, std::uint32_t n_points, const double pose[12])
+  {
+    const int rc = lfx_rolling_map_insert_host(ctx_, map_, kind, points, n_points, pose, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  // the live voxels of the box lo .. hi (metres) of one store into device memory of the caller's (d_out: capacity_points
+  // records of 4 floats, or null with capacity 0), ascending (vz, vy, vx); returns how many the box holds
+  std::uint64_t Extract(Kind kind, const double lo[3], const double hi[3], float * d_out, std::uint64_t capacity_points) const
+  {
+    std::uint64_t n = 0;
+    const int rc = lfx_rolling_map_extract(ctx_, map_, kind, lo, hi, d_out, capacity_points, &n, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return n;
+  }
+  std::vector<double> CurrentPose() const
+  {
+    std::vector<double> pose(12);
+    lfx_rolling_map_pose(map_, pose.data());
+    return pose;
+  }
+  lfx_rolling_map_view_t View() const
+  {
+    lfx_rolling_map_view_t v{};
+    const int rc = lfx_rolling_map_view(ctx_, map_, &v, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return v;
+  }
+  // dirname/edge.pcd and dirname/surface.pcd of the whole windows, each only if non-empty
+  void Save(const std::string & dirname, int written[2] = nullptr) const
+  {
+    int w[2] = {0, 0};
+    const int rc = lfx_rolling_map_save(ctx_, map_, dirname.c_str(), w, nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    if (written) {written[0] = w[0]; written[1] = w[1];}
+  }
+  lfx_rolling_map * handle() const {return map_;}
+
+private:
+  lfx_ctx * ctx_;
+  lfx_rolling_map * map_ = nullptr;
+  std::vector<lfx_rolling_map_result> results_;
+};
+
 // The place index (lfx_place_db): scan-context descriptors of one config on the device of `fx`, which must outlive it, each
 // compared with a query under every column shift.  For start-up relocalisation (index the keyframes of a map, query with
 // the first scan) and for loop detection (index the keyframes as the mapper adds them; query the range that leaves the most

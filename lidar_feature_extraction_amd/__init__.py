@@ -5,6 +5,7 @@ mirror of the reference node's operator.  Importing this package does not need a
 `FeatureExtraction` does, and raises if the library or the device is missing (no CPU fallback).
 """
 from .extraction import FeatureExtraction, HyperParameters, Odometry, ScanFeatures, LABEL_NAMES, RING_STATUS_NAMES, layout_from_fields  # noqa: F401
+from .extraction import RollingMap  # noqa: F401
 from .extraction import Mapper, ScanMap, read_pcd, write_pcd, pose_diff, covariance_ros  # noqa: F401
 from .extraction import time_field_from_fields, motion_between, motion_twist, motion_scale  # noqa: F401
 from .extraction import trajectory_segments, trajectory_from_gyro  # noqa: F401

@@ -119,6 +119,28 @@ class MapperStoreView(C.Structure):
                 ("n_empty", C.c_uint64), ("n_too_close", C.c_uint64), ("has_pose", C.c_int32), ("last_pose", C.c_double * 12)]
 
 
+class RollingMapConfig(C.Structure):
+    """lfx_rolling_map_config: leaf size (m) and window dimensions (voxels) of the edge and the surface store."""
+    _fields_ = [("edge_leaf", C.c_float), ("surface_leaf", C.c_float), ("edge_dims", C.c_uint32 * 3),
+                ("surface_dims", C.c_uint32 * 3), ("match_half_extent", C.c_float * 3), ("n_neighbors", C.c_uint32),
+                ("max_iter", C.c_int32), ("scan_surface_leaf", C.c_float), ("edge_cell", C.c_float), ("surface_cell", C.c_float),
+                ("initial_pose", C.c_double * 12)]
+
+
+class RollingMapResult(C.Structure):
+    _fields_ = [("align", AlignResult), ("initial_pose", C.c_double * 12), ("n_edge_map", C.c_uint32), ("n_surface_map", C.c_uint32),
+                ("aligned", C.c_int32), ("inserted", C.c_int32), ("recentered", C.c_int32)]
+
+
+class RollingMapView(C.Structure):
+    """lfx_rolling_map_view_t: per store ([0] edge, [1] surface) leaf, dims, origin, the counters and the live voxels."""
+    _fields_ = [("leaf", C.c_float * 2), ("dims", (C.c_uint32 * 3) * 2), ("origin", (C.c_int32 * 3) * 2),
+                ("n_inserted", C.c_uint64 * 2), ("n_merged", C.c_uint64 * 2), ("n_outside", C.c_uint64 * 2),
+                ("n_nonfinite", C.c_uint64 * 2), ("n_live", C.c_uint64 * 2), ("pose", C.c_double * 12),
+                ("correction", C.c_double * 12)]
+
+
+ROLLING_EDGE, ROLLING_SURFACE = 0, 1
 KEYFRAME_ADDED, KEYFRAME_EMPTY, KEYFRAME_TOO_CLOSE = 0, 1, 2
 ERR_CAPACITY, ERR_OUT_OF_MEMORY, ERR_UNSUPPORTED_FIELD, ERR_FILE = -4, -6, -8, -9
 ERR_INVALID_ARGUMENT, ERR_NO_TIME_FIELD = -1, -10
@@ -181,6 +203,9 @@ EXPORTS = [
     "lfx_odometry_update_host", "lfx_odometry_add", "lfx_odometry_pose", "lfx_odometry_view", "lfx_odometry_save",
     "lfx_pcd_read", "lfx_pcd_write", "lfx_pose_diff", "lfx_mapper_default_config", "lfx_mapper_create", "lfx_mapper_destroy",
     "lfx_mapper_add", "lfx_mapper_add_host", "lfx_mapper_view", "lfx_mapper_save",
+    "lfx_rolling_map_default_config", "lfx_rolling_map_create", "lfx_rolling_map_destroy", "lfx_rolling_map_recenter",
+    "lfx_rolling_map_insert", "lfx_rolling_map_insert_host", "lfx_rolling_map_extract", "lfx_rolling_map_view",
+    "lfx_rolling_map_save", "lfx_rolling_map_update_batch", "lfx_rolling_map_pose",
     "lfx_layout_from_fields", "lfx_pack_xyz", "lfx_pack_xyz12", "lfx_pack_colored", "lfx_pack_features", "lfx_download_scan", "lfx_stage_ring", "lfx_stage_convolution1d",
     "lfx_stage_ring_projection", "lfx_label_to_color", "lfx_color_points_by_label", "lfx_set_profiling", "lfx_set_profiling_interval", "lfx_kernel_times", "lfx_kernel_name",
     "lfx_time_field_from_fields", "lfx_motion_between", "lfx_motion_twist", "lfx_motion_scale", "lfx_deskew_batch",
@@ -300,6 +325,19 @@ def load(test_hooks=False):
     L.lfx_mapper_add_host.argtypes = [vp, vp, vp, u32, pd, vp, vp]
     L.lfx_mapper_view.argtypes = [vp, C.POINTER(MapperStoreView)]
     L.lfx_mapper_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
+    L.lfx_rolling_map_default_config.argtypes = [C.POINTER(RollingMapConfig)]
+    L.lfx_rolling_map_default_config.restype = None
+    L.lfx_rolling_map_create.argtypes = [vp, C.POINTER(RollingMapConfig), C.POINTER(vp)]
+    L.lfx_rolling_map_destroy.argtypes = [vp]
+    L.lfx_rolling_map_destroy.restype = None
+    L.lfx_rolling_map_recenter.argtypes = [vp, pd]
+    L.lfx_rolling_map_insert.argtypes = [vp, vp, i32, vp, vp, vp, u32, u32, C.c_size_t, pd, vp]
+    L.lfx_rolling_map_insert_host.argtypes = [vp, vp, i32, vp, u32, pd, vp]
+    L.lfx_rolling_map_extract.argtypes = [vp, vp, i32, pd, pd, vp, u64, p64, vp]
+    L.lfx_rolling_map_view.argtypes = [vp, vp, C.POINTER(RollingMapView), vp]
+    L.lfx_rolling_map_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
+    L.lfx_rolling_map_update_batch.argtypes = [vp, vp, u32, pd, C.POINTER(RollingMapResult), vp]
+    L.lfx_rolling_map_pose.argtypes = [vp, pd]
     L.lfx_gather.argtypes = [vp, vp, i32, vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, vp]
     L.lfx_layout_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Layout)]
     L.lfx_time_field_from_fields.argtypes = [C.POINTER(PointField), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(TimeField)]

@@ -334,6 +334,13 @@ class FeatureExtraction:
         max_points=2^32 - 1)."""
         return Mapper(self, **config)
 
+    def rolling_map(self, **config):
+        """lfx_rolling_map_create: a rolling voxel map on this context's device.  Keywords: the fields of
+        lfx_rolling_map_config (edge_leaf=0.2, surface_leaf=0.4, edge_dims=(512, 512, 128), surface_dims=(256, 256, 64),
+        match_half_extent=(50, 50, 12.8), n_neighbors=15, max_iter=20, scan_surface_leaf=1.0, edge_cell=1.0, surface_cell=1.0,
+        initial_pose: 3 x 4)."""
+        return RollingMap(self, **config)
+
     def set_ring_ids(self, ring_ids):
         """lfx_set_ring_ids: the sensor's ring ids for the device path (None: back to 0 .. max_rings-1)."""
         if ring_ids is None:
@@ -1018,6 +1025,144 @@ class Mapper:
     def close(self):
         if self.handle:
             self._L.lfx_mapper_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RollingMap:
+    """lfx_rolling_map: one point per voxel in a window that follows the vehicle, an edge store and a surface store (kind:
+    'edge' / 'surface' or binding.ROLLING_EDGE / ROLLING_SURFACE).  Inserts keep the first point of a voxel (lowest (cloud,
+    index) of the call that first reaches it); extract cuts a box out in ascending (vz, vy, vx).  Poses are 3 x 4 [R | t]."""
+
+    KINDS = {"edge": B.ROLLING_EDGE, "surface": B.ROLLING_SURFACE}
+
+    def __init__(self, fx, **config):
+        self._fx = fx
+        self._L = fx._L
+        cfg = B.RollingMapConfig()
+        self._L.lfx_rolling_map_default_config(C.byref(cfg))
+        for k, v in config.items():
+            if k not in dict(B.RollingMapConfig._fields_):
+                raise TypeError("unknown rolling map setting %r" % k)
+            if k.endswith("_dims"):
+                v = (C.c_uint32 * 3)(*[int(x) for x in v])
+            elif k == "match_half_extent":
+                v = (C.c_float * 3)(*[float(x) for x in v])
+            elif k == "initial_pose":
+                v = (C.c_double * 12)(*[float(x) for x in np.asarray(v, np.float64).reshape(12)])
+            setattr(cfg, k, v)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_rolling_map_create(fx._ctx, C.byref(cfg), C.byref(h)))
+        self.handle = h
+        self.config = {k: (tuple(getattr(cfg, k)) if hasattr(getattr(cfg, k), "__len__") else getattr(cfg, k))
+                       for k, _ in B.RollingMapConfig._fields_ if k != "initial_pose"}
+
+    @classmethod
+    def _kind(cls, kind):
+        return cls.KINDS[kind] if isinstance(kind, str) else int(kind)
+
+    def recenter(self, center):
+        """lfx_rolling_map_recenter: both windows centred on `center` (m).  No device work."""
+        ctr = np.ascontiguousarray(center, np.float64).reshape(3)
+        rc = self._L.lfx_rolling_map_recenter(self.handle, ctr.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise B.LfxError(rc, "the centre must be finite and have a voxel")
+
+    def insert(self, kind, d_points, d_begin, d_count, count_stride, n_clouds, total_points, poses, stream=0):
+        """lfx_rolling_map_insert: n_clouds device clouds (lfx_mapper_add's addressing), poses [n][3][4]."""
+        n = int(n_clouds)
+        pm = Mapper._poses(poses, n)
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_insert(
+            self._fx._ctx, self.handle, self._kind(kind), C.c_void_p(int(d_points)), C.c_void_p(int(d_begin)), C.c_void_p(int(d_count)),
+            int(count_stride), n, int(total_points), pm.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(int(stream))))
+
+    def insert_batch(self, kind, poses, stream=0):
+        """The edge or surface clouds of the last device batch, one pose per scan."""
+        k = self._kind(kind)
+        v = self._fx.device_view()
+        pts = v.edge_points if k == B.ROLLING_EDGE else v.surface_points
+        info = int(v.scan_info) + 4 * (2 if k == B.ROLLING_EDGE else 3)
+        self.insert(k, pts, v.scan_begin, info, 4, v.batch, self._fx.max_points_per_scan * self._fx.max_batch, poses, stream)
+
+    def insert_host(self, kind, points, pose=None, stream=0):
+        """lfx_rolling_map_insert_host: one cloud ([n, 4] float32) on the host (pose: identity)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        pm = Mapper._poses(np.eye(4)[:3] if pose is None else pose, 1)
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_insert_host(
+            self._fx._ctx, self.handle, self._kind(kind), C.c_void_p(p.ctypes.data if len(p) else 0), len(p),
+            pm.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(int(stream))))
+
+    def extract_device(self, kind, lo, hi, d_out, capacity_points, stream=0):
+        """lfx_rolling_map_extract into device memory (d_out: an address, capacity_points records of 4 floats).  Returns the
+        number of live voxels in the box, whatever the capacity."""
+        lo_, hi_ = (np.ascontiguousarray(a, np.float64).reshape(3) for a in (lo, hi))
+        n = C.c_uint64(0)
+        pd = C.POINTER(C.c_double)
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_extract(
+            self._fx._ctx, self.handle, self._kind(kind), lo_.ctypes.data_as(pd), hi_.ctypes.data_as(pd), C.c_void_p(int(d_out)),
+            int(capacity_points), C.byref(n), C.c_void_p(int(stream))))
+        return int(n.value)
+
+    def extract(self, kind, lo, hi, stream=0):
+        """The live voxels of the box lo .. hi (m) as [n, 4] float32 on the host, ascending (vz, vy, vx)."""
+        import torch
+        n = self.extract_device(kind, lo, hi, 0, 0, stream)
+        if n == 0:
+            return np.zeros((0, 4), np.float32)
+        out = torch.empty((n, 4), dtype=torch.float32, device=torch.device("cuda", self._fx.device))
+        self.extract_device(kind, lo, hi, out.data_ptr(), n, stream)
+        return _download(self._L, out.data_ptr(), n, stream)
+
+    def view(self, stream=0):
+        """lfx_rolling_map_view: per kind leaf, dims, origin, the counters summed since create and the live voxels."""
+        v = B.RollingMapView()
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_view(self._fx._ctx, self.handle, C.byref(v), C.c_void_p(int(stream))))
+        out = {name: dict(leaf=v.leaf[k], dims=tuple(v.dims[k]), origin=tuple(v.origin[k]), inserted=v.n_inserted[k],
+                          merged=v.n_merged[k], outside=v.n_outside[k], nonfinite=v.n_nonfinite[k], live=v.n_live[k])
+               for name, k in self.KINDS.items()}
+        out["pose"] = np.array(v.pose[:], np.float64).reshape(3, 4)
+        out["correction"] = np.array(v.correction[:], np.float64).reshape(3, 4)
+        return out
+
+    def update_batch(self, odometry_poses=None, n_scans=None, stream=0):
+        """lfx_rolling_map_update_batch: LOAM's mapping stage for every scan of the last device batch -- the scan aligned
+        against the boxes cut out of both stores around C x odometry_poses[k] (or the current pose), then inserted at the
+        result.  One dict per scan: the alignment's fields plus initial_pose, n_edge_map, n_surface_map, aligned, inserted,
+        recentered."""
+        n = int(self._fx.device_view().batch if n_scans is None else n_scans)
+        poses = None if odometry_poses is None else Mapper._poses(odometry_poses, n)
+        res = (B.RollingMapResult * max(n, 1))()
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_update_batch(
+            self._fx._ctx, self.handle, n, None if poses is None else poses.ctypes.data_as(C.POINTER(C.c_double)), res,
+            C.c_void_p(int(stream))))
+        out = []
+        for r, a in zip(res[:n], self._fx._align_results([r.align for r in res[:n]])):
+            a.update(initial_pose=np.array(r.initial_pose[:], np.float64).reshape(3, 4), n_edge_map=r.n_edge_map,
+                     n_surface_map=r.n_surface_map, aligned=bool(r.aligned), inserted=bool(r.inserted), recentered=bool(r.recentered))
+            out.append(a)
+        return out
+
+    def pose(self):
+        """lfx_rolling_map_pose: the current pose (3 x 4)."""
+        p = np.zeros(12, np.float64)
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_pose(self.handle, p.ctypes.data_as(C.POINTER(C.c_double))))
+        return p.reshape(3, 4)
+
+    def save(self, dirname, stream=0):
+        """lfx_rolling_map_save: edge.pcd and surface.pcd of the whole windows under dirname.  Returns (edge written,
+        surface written)."""
+        w = (C.c_int32 * 2)()
+        B.check(self._fx._ctx, self._L.lfx_rolling_map_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
+        return bool(w[0]), bool(w[1])
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_rolling_map_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
