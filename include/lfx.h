@@ -273,6 +273,10 @@ int lfx_extract_batch(lfx_ctx *ctx, const void *const *points, const size_t *n_p
 int lfx_extract_batch_device(lfx_ctx *ctx, const void *d_points, const uint32_t *n_points, uint32_t batch,
                              void *stream);
 int lfx_device_results(const lfx_ctx *ctx, lfx_device_view *view);
+/* Input records of the last batch the context ran, whichever entry point ran it (lfx_extract, lfx_extract_submit,
+ * lfx_extract_batch, lfx_extract_batch_device): the view's scan_begin[batch] as the device holds it, from the host's copy --
+ * no device work, no wait.  What a caller sizes per-record outputs by (lfx_segment_batch).  0 before the first batch. */
+int lfx_batch_points(const lfx_ctx *ctx, uint64_t *n_points);
 /* What lfx_extract reports through its return code, for callers of the device-resident path: waits for `stream`,
  * reads the last batch's scan_info and returns LFX_ERR_RING_ID / LFX_ERR_HIP if any scan carries an error bit
  * (the clouds of such a scan are not to be used), else LFX_OK.  first_bad (may be NULL): index of the first such scan. */
@@ -1064,6 +1068,88 @@ int lfx_place_db_download(lfx_ctx *ctx, const lfx_place_db *db, uint32_t first, 
  * Synchronous.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, n_queries 0, k outside 1 .. 16, a range past the index's size. */
 int lfx_place_db_query(lfx_ctx *ctx, const lfx_place_db *db, const float *d_desc, uint32_t n_queries, uint32_t first,
                        uint32_t count, uint32_t k, lfx_place_match *matches, void *stream);
+
+/* --- segmentation: ground, clusters and clutter from a range image; feature clouds filtered by it ----------------------- */
+/* "Is this feature on the road, on an object, or on a leaf?"  No reference counterpart; the model is LeGO-LOAM's image
+ * projection (Shan and Englot, IROS 2018): the sweep becomes an H x W range image, the ground is found by the slope between
+ * vertically adjacent cells, the rest is clustered by connected components under an angle test, and clusters too small to be
+ * objects are clutter.  Edge features are then taken from clusters only, surface features from the ground and from clusters
+ * (lfx_pack_features_segmented).
+ *
+ * Tables (lfx_segment_tables, host only, the ONLY source: the device is given exactly these values):
+ *   col_cos[m], col_sin[m] = cos, sin of -M_PI + ((2.0 * M_PI) * (double)m) / (double)W, m = 0 .. W-1;
+ *   consts = sin, cos of (2.0 * M_PI) / (double)W (the angle between adjacent columns), then sin, cos of (double)row_step.
+ * All arithmetic below is in double, unfused, on the floats read through the context's lfx_layout.
+ *
+ * Projection.  Record i of a scan (i: its index in the scan's input):
+ *   - skipped if x, y or z is not finite, or if its row -- its ring slot as the extraction defines it: the ring id, with
+ *     lfx_config.ring_ids / lfx_set_ring_ids the id's rank -- is >= H or unknown to the context;
+ *   - skipped if x*x + y*y == 0;
+ *   - r = sqrt((x*x + y*y) + z*z); skipped if r < (double)min_range or r >= (double)max_range (the (0, 0, 0) records go here
+ *     at the latest);
+ *   - column: m0 = y >= 0.0f ? W/2 : 0;  cross(m) = col_cos[m]*y - col_sin[m]*x (two rounded products, one subtraction);
+ *       lo = 0, hi = W/2 - 1; while (lo < hi) { mid = (lo + hi + 1) >> 1; if (cross(m0 + mid) >= 0) lo = mid; else hi = mid - 1; }
+ *     column = m0 + lo.  The bisection is the definition; no atan2 is involved.
+ *   Cell (row, column) is won by the record with the least (float)r, equal floats by the lower i; the cell has that record's
+ *   x, y, z and r.  A cell without a record is empty.
+ * Ground.  For a column c and a row i, ground_first_row <= i < ground_last_row, with (i, c) and (i+1, c) both occupied:
+ *   dx, dy, dz the differences of the floats in double; if dz*dz <= g2 * (dx*dx + dy*dy), g2 = (double)ground_tan *
+ *   (double)ground_tan, both cells are ground.  (A sensor whose ring 0 is the top beam gives the upper slots.)
+ * Clusters.  Nodes: the occupied cells that are not ground.  Edges: (row, c) - (row, (c+1) mod W) with the column step's sin
+ *   and cos -- the seam pair (W-1, 0) counts once -- and (row, c) - (row+1, c) with the row step's.  An edge joins its cells
+ *   iff d2 * sin_a > (double)segment_tan * (d1 - d2 * cos_a), d1 = max(r_a, r_b), d2 = min(r_a, r_b).  A cell's LABEL is the
+ *   least cell index row * W + column of its connected component.  A component is a SEGMENT if its size is >=
+ *   segment_min_points, or if its size is >= small_min_points and row_max - row_min + 1 >= small_min_rows; otherwise CLUTTER.
+ * Per record: a skipped record is LFX_SEG_NONE; every other record takes the class of its cell, whether or not it won the
+ *   cell; its id is the cell's label for LFX_SEG_SEGMENT and LFX_SEG_CLUTTER, 0xFFFFFFFF for LFX_SEG_NONE and LFX_SEG_GROUND.
+ * Every output byte is the same whatever the schedule. */
+#define LFX_SEG_NONE 0
+#define LFX_SEG_GROUND 1
+#define LFX_SEG_SEGMENT 2
+#define LFX_SEG_CLUTTER 3
+#define LFX_SEG_EDGE_MASK_DEFAULT (1u << LFX_SEG_SEGMENT)
+#define LFX_SEG_SURFACE_MASK_DEFAULT ((1u << LFX_SEG_GROUND) | (1u << LFX_SEG_SEGMENT))
+#define LFX_SEGMENT_MAX_ROWS 128
+#define LFX_SEGMENT_MAX_COLUMNS 4096
+typedef struct lfx_segment_config {
+  uint32_t n_rows;              /* H: 16; 1 .. 128, at most the context's max_rings */
+  uint32_t n_columns;           /* W: 1800; even, 4 .. 4096 */
+  float row_step;               /* 0.034906585 (2 degrees): radians between adjacent rows; > 0, finite */
+  float min_range, max_range;   /* 1.0, 100.0; 0 < min_range < max_range, finite */
+  uint32_t ground_first_row, ground_last_row;   /* 0, 7; first <= last < H: the pairs (i, i+1), first <= i < last, are tested */
+  float ground_tan;             /* 0.17632698 (tan 10 degrees); >= 0, finite */
+  float segment_tan;            /* 1.7320508 (tan 60 degrees); > 0, finite */
+  uint32_t segment_min_points;  /* 30; >= 1 */
+  uint32_t small_min_points, small_min_rows;    /* 5, 3; >= 1 */
+} lfx_segment_config;
+void lfx_segment_default_config(lfx_segment_config *config);
+/* host only, no context: the tables the kernels are given.  LFX_ERR_INVALID_ARGUMENT: NULL arguments and every field outside
+ * the ranges above. */
+int lfx_segment_tables(const lfx_segment_config *config, double *col_cos /*[W]*/, double *col_sin /*[W]*/, double consts[4]);
+/* Class and id of every input record of every scan of the last device batch, from the batch's INPUT records (which must
+ * still be alive, as for lfx_scan_context_batch).  d_class_out (u8) and d_id_out (u32, may be NULL) are addressed by
+ * scan_begin[s] + i with the view's scan_begin; d_counts_out (may be NULL) u32 [n_scans][4], the scan's records by class.
+ * Every element of every scan is written on every call.  Asynchronous on `stream`, the counts read on the device.  The
+ * images live in a workspace of the context that grows on demand up to LFX_SEGMENT_BUDGET_CELLS cells; a batch whose images
+ * exceed that is processed in chunks of whole scans, in stream order (calls on different streams are ordered one behind the
+ * other: they share the workspace).  LFX_ERR_INVALID_ARGUMENT, before anything is queued: NULL ctx, config or d_class_out,
+ * what lfx_segment_tables refuses, n_rows above the context's max_rings, no batch yet, n_scans not the last batch's, the
+ * batch's input records not known (a defensive check: every entry point that runs a batch records where its records lie, so
+ * no sequence of calls reaches it today).  The call never waits for `stream`: the tables of the configs seen last are kept
+ * on the device, and a new config's go up from a pinned block of their own. */
+#define LFX_SEGMENT_BUDGET_CELLS (1u << 24)
+int lfx_segment_batch(lfx_ctx *ctx, const lfx_segment_config *config, uint32_t n_scans, uint8_t *d_class_out,
+                      uint32_t *d_id_out, uint32_t *d_counts_out, void *stream);
+/* lfx_pack_features with a filter: a feature record is kept iff bit (1 << class) of its ORIGINAL point (the view's
+ * edge_index / surface_index into d_class, which lfx_segment_batch wrote for this batch) is set in its cloud's mask; the order
+ * is kept.  The same [2][batch+1] offsets table (of what is kept), the same rule for a short capacity_points, the same cap at
+ * 2^32 - 1.  d_counts_out (may be NULL) u32 [2][batch]: the kept records per scan, so that (d_offsets_out, d_counts_out,
+ * count_stride 1) -- for the surface cloud (d_offsets_out + batch + 1, d_counts_out + batch, 1) -- are the (d_begin, d_count)
+ * of lfx_mapper_add and lfx_rolling_map_insert.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, no batch yet, a mask with a bit
+ * above 3. */
+int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t edge_mask, uint32_t surface_mask,
+                                float *d_edge_out, float *d_surface_out, uint32_t *d_offsets_out, uint32_t *d_counts_out,
+                                size_t capacity_points, void *stream);
 
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device

@@ -236,6 +236,36 @@ public:
     const int rc = lfx_scan_context_batch(ctx_, &config, n_scans, d_desc_out, stream);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
   }
+  // Ground, clusters and clutter (lfx_segment_batch): the class (LFX_SEG_*) and the cluster id of every input record of the
+  // scans this object was last given, through a range image per scan; d_class_out (one byte per record), d_id_out and
+  // d_counts_out ([n_scans][4], either may be null) in memory the device writes, addressed by the view's scan_begin.
+  // lfx_batch_points: the input records of the scans this object was last given -- what d_class_out / d_id_out are sized by
+  std::uint64_t BatchPoints() const
+  {
+    std::uint64_t n = 0;
+    lfx_batch_points(ctx_, &n);
+    return n;
+  }
+  static lfx_segment_config DefaultSegmentConfig() {lfx_segment_config c; lfx_segment_default_config(&c); return c;}
+  void Segment(
+    const lfx_segment_config & config, std::uint32_t n_scans, std::uint8_t * d_class_out, std::uint32_t * d_id_out = nullptr,
+    std::uint32_t * d_counts_out = nullptr, void * stream = nullptr) const
+  {
+    const int rc = lfx_segment_batch(ctx_, &config, n_scans, d_class_out, d_id_out, d_counts_out, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
+  // lfx_pack_features through a class mask (lfx_pack_features_segmented): the features whose original point has a class of the
+  // cloud's mask, in order; d_offsets_out [2][batch + 1] and d_counts_out [2][batch] (may be null) are the begin / count
+  // tables Mapper::Add and RollingMap::Insert take.
+  void PackFeaturesSegmented(
+    const std::uint8_t * d_class, float * d_edge_out, float * d_surface_out, std::uint32_t * d_offsets_out, std::size_t capacity_points,
+    std::uint32_t * d_counts_out = nullptr, std::uint32_t edge_mask = LFX_SEG_EDGE_MASK_DEFAULT,
+    std::uint32_t surface_mask = LFX_SEG_SURFACE_MASK_DEFAULT, void * stream = nullptr) const
+  {
+    const int rc = lfx_pack_features_segmented(ctx_, d_class, edge_mask, surface_mask, d_edge_out, d_surface_out, d_offsets_out, d_counts_out,
+      capacity_points, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+  }
   // lfx_batch_status: waits for `stream` and throws if a scan this object was last given carries an error bit.  The wait a
   // caller needs between ScanContext (queued, reads the scans' input records) and the next scan it hands over.
   void BatchStatus(void * stream = nullptr) const
@@ -467,6 +497,15 @@ public:
   {
     results_.assign(1, lfx_odometry_result{});
     const int rc = lfx_odometry_update_host(ctx_, odometry_, edge, n_edge, surface, n_surface, results_.data(), nullptr);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
+    return results_[0];
+  }
+  // Update with one scan's clouds in memory the device reads (lfx_odometry_update): device buffers, or pinned blocks a kernel
+  // has filled -- the filtered clouds of FeatureExtraction::PackFeaturesSegmented, for one
+  const lfx_odometry_result & UpdateDevice(const float * d_edge, std::uint32_t n_edge, const float * d_surface, std::uint32_t n_surface)
+  {
+    results_.assign(1, lfx_odometry_result{});
+    const int rc = lfx_odometry_update(ctx_, odometry_, d_edge, n_edge, d_surface, n_surface, results_.data(), nullptr);
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(ctx_));}
     return results_[0];
   }

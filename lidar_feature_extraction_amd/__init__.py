@@ -10,4 +10,5 @@ from .extraction import Mapper, ScanMap, read_pcd, write_pcd, pose_diff, covaria
 from .extraction import time_field_from_fields, motion_between, motion_twist, motion_scale  # noqa: F401
 from .extraction import trajectory_segments, trajectory_from_gyro  # noqa: F401
 from .extraction import PlaceDb, scan_context_config, scan_context_tables  # noqa: F401
+from .extraction import segment_config, segment_tables  # noqa: F401
 from .synth import POINT_DTYPE, SENSORS, make_scan, make_batch, make_sequence, make_sweep, make_sweep_trajectory, concat  # noqa: F401

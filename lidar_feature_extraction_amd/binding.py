@@ -182,6 +182,20 @@ SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, PLACE_MAX_MATCHES = 40, 120, 1
 PLACE_NO_ENTRY = 0xFFFFFFFF
 
 
+class SegmentConfig(C.Structure):
+    """lfx_segment_config: the range image (H rows x W columns) and the thresholds of the ground, join and size tests."""
+    _fields_ = [("n_rows", C.c_uint32), ("n_columns", C.c_uint32), ("row_step", C.c_float), ("min_range", C.c_float),
+                ("max_range", C.c_float), ("ground_first_row", C.c_uint32), ("ground_last_row", C.c_uint32), ("ground_tan", C.c_float),
+                ("segment_tan", C.c_float), ("segment_min_points", C.c_uint32), ("small_min_points", C.c_uint32),
+                ("small_min_rows", C.c_uint32)]
+
+
+SEG_NONE, SEG_GROUND, SEG_SEGMENT, SEG_CLUTTER = 0, 1, 2, 3
+SEG_EDGE_MASK_DEFAULT, SEG_SURFACE_MASK_DEFAULT = 1 << SEG_SEGMENT, (1 << SEG_GROUND) | (1 << SEG_SEGMENT)
+SEG_NO_ID = 0xFFFFFFFF
+SEGMENT_MAX_ROWS, SEGMENT_MAX_COLUMNS, SEGMENT_BUDGET_CELLS = 128, 4096, 1 << 24
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -192,7 +206,7 @@ class DeviceView(C.Structure):
 EXPORTS = [
     "lfx_default_params", "lfx_launch_params", "lfx_create", "lfx_destroy", "lfx_last_error",
     "lfx_status_string", "lfx_ring_message", "lfx_range_message", "lfx_extract", "lfx_extract_submit", "lfx_extract_wait", "lfx_extract_batch", "lfx_extract_batch_device",
-    "lfx_device_results", "lfx_batch_status", "lfx_scan_routes", "lfx_host_alloc", "lfx_host_free", "lfx_comm_unique_id", "lfx_comm_create",
+    "lfx_device_results", "lfx_batch_points", "lfx_batch_status", "lfx_scan_routes", "lfx_host_alloc", "lfx_host_free", "lfx_comm_unique_id", "lfx_comm_create",
     "lfx_comm_destroy", "lfx_comm_stats", "lfx_gather_counts", "lfx_gather_payload", "lfx_gather", "lfx_voxel_downsample", "lfx_downsample_surface",
     "lfx_map_create", "lfx_map_create_host", "lfx_map_destroy", "lfx_map_info", "lfx_map_nearest",
     "lfx_scan_to_map_residuals", "lfx_edge_residuals", "lfx_align_message", "lfx_scan_to_map_align", "lfx_align_point_pairs",
@@ -214,6 +228,7 @@ EXPORTS = [
     "lfx_scan_context_default_config", "lfx_scan_context_tables", "lfx_scan_context_batch", "lfx_place_db_create",
     "lfx_place_db_destroy", "lfx_place_db_add", "lfx_place_db_add_host", "lfx_place_db_size", "lfx_place_db_download",
     "lfx_place_db_query",
+    "lfx_segment_default_config", "lfx_segment_tables", "lfx_segment_batch", "lfx_pack_features_segmented",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -261,6 +276,7 @@ def load(test_hooks=False):
     L.lfx_extract_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), u32, C.POINTER(ScanResult)]
     L.lfx_extract_batch_device.argtypes = [vp, vp, C.POINTER(u32), u32, vp]
     L.lfx_device_results.argtypes = [vp, C.POINTER(DeviceView)]
+    L.lfx_batch_points.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.lfx_batch_status.argtypes = [vp, vp, C.POINTER(u32)]
     L.lfx_scan_routes.argtypes = [vp, vp, vp]
     L.lfx_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -365,6 +381,12 @@ def load(test_hooks=False):
     L.lfx_place_db_size.argtypes = [vp, C.POINTER(u32)]
     L.lfx_place_db_download.argtypes = [vp, vp, u32, u32, vp, vp]
     L.lfx_place_db_query.argtypes = [vp, vp, vp, u32, u32, u32, u32, C.POINTER(PlaceMatch), vp]
+    pseg = C.POINTER(SegmentConfig)
+    L.lfx_segment_default_config.argtypes = [pseg]
+    L.lfx_segment_default_config.restype = None
+    L.lfx_segment_tables.argtypes = [pseg, pd, pd, pd]
+    L.lfx_segment_batch.argtypes = [vp, pseg, u32, vp, vp, vp, vp]
+    L.lfx_pack_features_segmented.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_xyz.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_xyz12.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.lfx_pack_colored.argtypes = [vp, vp, vp, C.c_size_t, vp]

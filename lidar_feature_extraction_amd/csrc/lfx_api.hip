@@ -1172,6 +1172,14 @@ int lfx_device_results(const lfx_ctx * c, lfx_device_view * v)
   return LFX_OK;
 }
 
+int lfx_batch_points(const lfx_ctx * c, uint64_t * n_points)
+{
+  if (!c || !n_points) {return LFX_ERR_INVALID_ARGUMENT;}
+  // (uploaded_begin, not h_scan_begin: a batch refused for its size has rewritten the latter and left the device's alone)
+  *n_points = c->last_batch && c->uploaded_begin.size() > c->last_batch ? c->uploaded_begin[c->last_batch] : 0u;
+  return LFX_OK;
+}
+
 int lfx_batch_status(lfx_ctx * c, void * stream, uint32_t * first_bad)
 {
   if (!c) {return LFX_ERR_INVALID_ARGUMENT;}

@@ -309,6 +309,37 @@ struct lfx_ctx
   PlaceSlot place_slots[kPlaceSlots];
   uint32_t place_next = 0;
 
+  // lfx_segment_batch, lfx_pack_features_segmented (lfx_segment.hip): the range images of one chunk of scans (at most
+  // LFX_SEGMENT_BUDGET_CELLS cells, grown on demand), the filtered pack's counts, and an event behind the last call that used
+  // any of it: the next call's stream waits for it, so that calls on different streams take the workspace one behind the other.
+  // The tables of the kSegTables configs seen last stay on the device, each with the pinned block it went up from; a slot
+  // is refilled (its block rewritten) only after the event has passed, so no call waits for its stream.
+  struct SegmentWork
+  {
+    static constexpr uint32_t kSegTables = 4;
+    struct Table
+    {
+      lfx_host::DevBuf<double> d;
+      lfx_host::PinnedBuf h;
+      uint32_t columns = 0;              // 0: empty
+      float row_step = 0.0f;
+    };
+    lfx_host::DevBuf<uint64_t> image;
+    lfx_host::DevBuf<float4> cell;
+    lfx_host::DevBuf<uint32_t> parent, csize, crowmax, pack_counts;
+    Table tables[kSegTables];
+    uint32_t table_next = 0;             // the slot the next unseen config takes
+    hipEvent_t used = nullptr;
+    SegmentWork() = default;
+    SegmentWork(const SegmentWork &) = delete;
+    SegmentWork & operator=(const SegmentWork &) = delete;
+    ~SegmentWork()
+    {
+      if (used) {(void)hipEventSynchronize(used); (void)hipEventDestroy(used);}
+    }
+  };
+  SegmentWork seg;
+
   hipStream_t stream = nullptr;          // used by the synchronous host entry points
   std::vector<uint32_t> h_scan_begin;    // of the last batch
   std::vector<uint32_t> h_scan_geom;     // [batch][kGeomStride]: columns per ring and block boundaries of every scan (organised-scan kernel)
@@ -409,6 +440,11 @@ struct CloudSpan
   size_t total = 0;
   const uint32_t * row_begin = nullptr;
 };
+// lfx_wire.hip: the [2][batch + 1] offsets table of lfx_pack_features from two arrays of per-scan counts `stride` words apart
+// (feature_offsets_kernel; lfx_pack_features_segmented hands it its own counts)
+void launch_feature_offsets(const uint32_t * edge_counts, const uint32_t * surface_counts, uint32_t stride, uint32_t batch,
+  uint32_t * d_offsets, hipStream_t st);
+
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
   const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,

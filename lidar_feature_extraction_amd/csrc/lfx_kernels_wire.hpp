@@ -10,16 +10,18 @@ namespace lfx
 
 // ------------------------------------------------------------------------------------------
 // Batch-level packing for the multi-GPU gather: exclusive prefix of the per-scan feature counts
-// (one workgroup walks the batch), then a copy of every scan's clouds to its packed offset.
+// (one workgroup walks the batch), then a copy of every scan's clouds to its packed offset.  The counts: two arrays, scan k's
+// at [k * stride] (scan_info's edge and surface columns, stride 4; the filtered pack's own counts, stride 1).
 __global__ __launch_bounds__(256) void feature_offsets_kernel(
-  const uint32_t * __restrict__ scan_info, uint32_t batch, uint32_t * __restrict__ offsets /* [2][batch+1] */)
+  const uint32_t * __restrict__ edge_counts, const uint32_t * __restrict__ surface_counts, uint32_t stride, uint32_t batch,
+  uint32_t * __restrict__ offsets /* [2][batch+1] */)
 {
   __shared__ uint32_t part[2][256];
   const uint32_t tid = threadIdx.x;
   const uint32_t per = (batch + 255) / 256;
   const uint32_t lo = tid * per, hi = (lo + per < batch) ? lo + per : batch;
   uint32_t e = 0, s = 0;
-  for (uint32_t k = lo; k < hi; k++) {e += scan_info[k * 4 + kInfoEdge]; s += scan_info[k * 4 + kInfoSurface];}
+  for (uint32_t k = lo; k < hi; k++) {e += edge_counts[(size_t)k * stride]; s += surface_counts[(size_t)k * stride];}
   part[0][tid] = e;
   part[1][tid] = s;
   __syncthreads();
@@ -34,8 +36,8 @@ __global__ __launch_bounds__(256) void feature_offsets_kernel(
   for (uint32_t k = lo; k < hi; k++) {
     offsets[k] = ce;
     offsets[batch + 1 + k] = cs;
-    ce += scan_info[k * 4 + kInfoEdge];
-    cs += scan_info[k * 4 + kInfoSurface];
+    ce += edge_counts[(size_t)k * stride];
+    cs += surface_counts[(size_t)k * stride];
   }
   if (tid == 255) {
     offsets[batch] = part[0][255];

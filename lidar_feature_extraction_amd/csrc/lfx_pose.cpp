@@ -273,4 +273,45 @@ int lfx_scan_context_tables(const lfx_scan_context_config * config, double * sec
   return LFX_OK;
 }
 
+// Scan segmentation (include/lfx.h, the segmentation section): the defaults, and the tables the kernels are given.
+void lfx_segment_default_config(lfx_segment_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_segment_config{};
+  config->n_rows = 16;
+  config->n_columns = 1800;
+  config->row_step = 0.034906585f;
+  config->min_range = 1.0f;
+  config->max_range = 100.0f;
+  config->ground_first_row = 0;
+  config->ground_last_row = 7;
+  config->ground_tan = 0.17632698f;
+  config->segment_tan = 1.7320508f;
+  config->segment_min_points = 30;
+  config->small_min_points = 5;
+  config->small_min_rows = 3;
+}
+
+int lfx_segment_tables(const lfx_segment_config * config, double * col_cos, double * col_sin, double consts[4])
+{
+  if (!config || !col_cos || !col_sin || !consts) {return LFX_ERR_INVALID_ARGUMENT;}
+  const lfx_segment_config & c = *config;
+  const uint32_t H = c.n_rows, W = c.n_columns;
+  if (H < 1u || H > LFX_SEGMENT_MAX_ROWS || W < 4u || W > LFX_SEGMENT_MAX_COLUMNS || (W & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.row_step) || !(c.row_step > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.min_range) || !std::isfinite(c.max_range) || !(c.min_range > 0.0f) || !(c.min_range < c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!(c.ground_first_row <= c.ground_last_row) || !(c.ground_last_row < H)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.ground_tan) || !(c.ground_tan >= 0.0f) || !std::isfinite(c.segment_tan) || !(c.segment_tan > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.segment_min_points < 1u || c.small_min_points < 1u || c.small_min_rows < 1u) {return LFX_ERR_INVALID_ARGUMENT;}
+  for (uint32_t m = 0; m < W; m++) {
+    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)W;
+    col_cos[m] = std::cos(angle);
+    col_sin[m] = std::sin(angle);
+  }
+  const double col_step = (2.0 * M_PI) / (double)W, row_step = (double)c.row_step;
+  consts[0] = std::sin(col_step); consts[1] = std::cos(col_step);
+  consts[2] = std::sin(row_step); consts[3] = std::cos(row_step);
+  return LFX_OK;
+}
+
 }  // extern "C"

@@ -5,6 +5,12 @@
 
 using namespace lfx_host;
 
+void lfx_host::launch_feature_offsets(const uint32_t * edge_counts, const uint32_t * surface_counts, uint32_t stride, uint32_t batch,
+  uint32_t * d_offsets, hipStream_t st)
+{
+  hipLaunchKernelGGL(lfx::feature_offsets_kernel, dim3(1), dim3(256), 0, st, edge_counts, surface_counts, stride, batch, d_offsets);
+}
+
 extern "C" {
 
 namespace
@@ -65,7 +71,7 @@ int pack_clouds(
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint32_t batch = c->last_batch;
   const uint32_t capacity = capacity_points > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity_points;
-  hipLaunchKernelGGL(lfx::feature_offsets_kernel, dim3(1), dim3(256), 0, st, c->scan_info.p, batch, d_offsets_out);
+  launch_feature_offsets(c->scan_info.p + lfx::kInfoEdge, c->scan_info.p + lfx::kInfoSurface, 4u, batch, d_offsets_out, st);
   hipLaunchKernelGGL(lfx::feature_pack_kernel, dim3(8, batch), dim3(256), 0, st,
     c->scan_begin.p, c->scan_info.p, d_offsets_out, batch, c->edge_pts.p, c->surf_pts.p,
     reinterpret_cast<float4 *>(d_edge_out), reinterpret_cast<float4 *>(d_surface_out), capacity, xyz_wire);

@@ -438,6 +438,71 @@ class FeatureExtraction:
                                                           C.c_void_p(int(stream))), self._L)
         return made
 
+    def batch_points(self):
+        """lfx_batch_points: the input records of the last batch the context ran, whichever call ran it (0: none yet)."""
+        n = C.c_uint64(0)
+        B.check(self._ctx, self._L.lfx_batch_points(self._ctx, C.byref(n)), self._L)
+        return int(n.value)
+
+    def segment(self, config=None, classes=None, ids=None, counts=None, stream=0):
+        """lfx_segment_batch: every input record of the last batch (whose records must still be alive) classed as
+        B.SEG_NONE / SEG_GROUND / SEG_SEGMENT / SEG_CLUTTER through a range image, with its cluster's id.  config: None
+        (the defaults: 16 x 1800), a dict of lfx_segment_config's fields or a B.SegmentConfig; classes (uint8, one per record),
+        ids (one per record) and counts ([n_scans][4]) -- the library's uint32 in int32 tensors: B.SEG_NO_ID reads as -1 --:
+        device tensors to write into, addressed by the view's scan_begin; None = new ones, sized by batch_points(); ids /
+        counts False = not wanted (the library is handed NULL and None comes back in its place).  A tensor with fewer elements
+        than the batch has records (counts: than 4 per scan) is refused.  Returns (classes, ids, counts).  Asynchronous on
+        `stream`."""
+        import torch
+        cfg = segment_config(config)
+        n = int(self.device_view().batch)
+        dev = torch.device("cuda", self.device)
+        total = self.batch_points()
+        if classes is None:
+            classes = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+        if ids is None:
+            ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)[:total]
+        elif ids is False:
+            ids = None
+        if counts is None:
+            counts = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)[:n]
+        elif counts is False:
+            counts = None
+        for name, t, need, size in (("classes", classes, total, 1), ("ids", ids, total, 4), ("counts", counts, 4 * n, 4)):
+            if t is not None and (t.numel() < need or t.element_size() != size or not t.is_contiguous()):
+                raise B.LfxError(B.ERR_INVALID_ARGUMENT, "%s must be a contiguous tensor of at least %d elements of %d byte(s): the last "
+                                 "batch has %d records in %d scans" % (name, need, size, total, n))
+        ptr = lambda t: C.c_void_p((t.data_ptr() or None) if t is not None else None)
+        B.check(self._ctx, self._L.lfx_segment_batch(self._ctx, C.byref(cfg), n, ptr(classes), ptr(ids), ptr(counts), C.c_void_p(int(stream))),
+                self._L)
+        return classes, ids, counts
+
+    def pack_features_segmented(self, classes, edge_mask=B.SEG_EDGE_MASK_DEFAULT, surface_mask=B.SEG_SURFACE_MASK_DEFAULT,
+                                capacity=None, counts=False, stream=0):
+        """lfx_pack_features_segmented: pack_features through a class mask -- a feature is kept iff bit 1 << class of its
+        original point (classes: segment()'s uint8 device tensor for this batch) is set in its cloud's mask.  capacity: records
+        per output buffer (None: room for every feature of the batch).  Returns (edge [capacity][4] float32, surface, offsets
+        uint32-as-int32 [2][batch + 1]) and, with counts=True, the kept records per scan, [2][batch], as a fourth -- device
+        tensors.  Asynchronous on `stream`."""
+        import torch
+        n = int(self.device_view().batch)
+        dev = torch.device("cuda", self.device)
+        total = self.batch_points()
+        if classes.numel() < total or classes.element_size() != 1:
+            raise B.LfxError(B.ERR_INVALID_ARGUMENT, "classes must hold one byte for each of the last batch's %d records" % total)
+        if capacity is None:
+            capacity = max(total, 1)
+        capacity = int(capacity)
+        edge = torch.empty((max(capacity, 1), 4), dtype=torch.float32, device=dev)
+        surface = torch.empty((max(capacity, 1), 4), dtype=torch.float32, device=dev)
+        offsets = torch.empty((2, n + 1), dtype=torch.int32, device=dev)
+        kept = torch.empty((2, max(n, 1)), dtype=torch.int32, device=dev)[:, :n] if counts else None
+        B.check(self._ctx, self._L.lfx_pack_features_segmented(
+            self._ctx, C.c_void_p(classes.data_ptr() or None), int(edge_mask), int(surface_mask), C.c_void_p(edge.data_ptr()),
+            C.c_void_p(surface.data_ptr()), C.c_void_p(offsets.data_ptr()), C.c_void_p(kept.data_ptr() if counts else None),
+            capacity, C.c_void_p(int(stream))), self._L)
+        return (edge, surface, offsets, kept) if counts else (edge, surface, offsets)
+
     def place_db(self, capacity, config=None):
         """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
         return PlaceDb(self, capacity, config)
@@ -683,6 +748,35 @@ def scan_context_tables(config=None):
     if rc != 0:
         raise B.LfxError(rc, "the scan-context config is refused")
     return cs[:S], sn[:S], r2
+
+
+def segment_config(config=None, **fields):
+    """lfx_segment_config: the defaults (lfx_segment_default_config) with the given fields replaced.  config: None, a dict of
+    fields, or a B.SegmentConfig (copied)."""
+    cfg = B.SegmentConfig()
+    if isinstance(config, B.SegmentConfig):
+        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        config = None
+    else:
+        B.load().lfx_segment_default_config(C.byref(cfg))
+    for k, v in dict(config or {}, **fields).items():
+        if k not in dict(B.SegmentConfig._fields_):
+            raise TypeError("unknown segmentation setting %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def segment_tables(config=None):
+    """lfx_segment_tables: (col_cos [W], col_sin [W], consts [4]), float64 -- the tables the segmentation kernels are given, and
+    the only source of them.  Host only."""
+    cfg = segment_config(config)
+    W = int(cfg.n_columns)
+    # (sized for any config: a refused one writes nothing)
+    cs, sn, consts = np.zeros(max(W, 1)), np.zeros(max(W, 1)), np.zeros(4)
+    rc = B.load().lfx_segment_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(consts))
+    if rc != 0:
+        raise B.LfxError(rc, "the segmentation config is refused")
+    return cs[:W], sn[:W], consts
 
 
 def _msg_buffer():
