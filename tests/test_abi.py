@@ -57,17 +57,25 @@ def test_invalid_arguments_are_rejected_before_any_device_work(lib):
     cfg0 = LB.Config(C.sizeof(LB.Config), 0, 1, 0, 0, 0, LB.Layout(0, 0, 0, 0, 0))
     assert lib.lfx_create(C.byref(ctx), 0, C.byref(p), C.byref(cfg0)) == -1
     # struct_size: an uninitialised struct (0) and one too short to hold the two capacities are refused by name; a caller
-    # built against an OLDER header (a shorter struct: here without outputs and stream_hint) is taken -- what it does not
-    # know reads as zero -- and gets as far as the device check
+    # built against an OLDER header (a shorter struct) is taken -- what it does not know reads as zero -- and gets as far
+    # as the device check.  Two older headers: the one without outputs and stream_hint, and the one with them (zero) but
+    # without ring_ids and n_ring_ids; every byte behind the struct's end is 0xFF, garbage that must not be read.
     for size in (0, 8):
         bad = LB.Config(size, 1000, 1, 0, 0, 0, LB.Layout(0, 0, 0, 0, 0))
         assert lib.lfx_create(C.byref(ctx), 0, C.byref(p), C.byref(bad)) == -1
         assert b"struct_size" in lib.lfx_last_error(None)
-    older = LB.Config(C.sizeof(LB.Config) - 8, 1000, 1, 0, 0, 0, LB.Layout(0, 0, 0, 0, 0), 0xFFFFFFFF, 0xFFFFFFFF)      # garbage behind its end
-    rc = lib.lfx_create(C.byref(ctx), 0, C.byref(p), C.byref(older))
-    assert rc in (0, -2) and b"stream_hint" not in lib.lfx_last_error(None), (rc, lib.lfx_last_error(None))
-    if rc == 0:
-        lib.lfx_destroy(ctx)
+    assert LB.Config.outputs.offset < LB.Config.ring_ids.offset < C.sizeof(LB.Config)
+    assert LB.Config.stream_hint.offset + 4 <= LB.Config.ring_ids.offset
+    for size in (LB.Config.outputs.offset, LB.Config.ring_ids.offset):
+        older = LB.Config(size, 1000, 1, 0, 0, 0, LB.Layout(0, 0, 0, 0, 0))
+        C.memset(C.addressof(older) + size, 0xFF, C.sizeof(LB.Config) - size)
+        assert older.n_ring_ids == 0xFFFFFFFF and older.struct_size == size and older.max_points_per_scan == 1000
+        assert (older.outputs, older.stream_hint) == ((0xFFFFFFFF, 0xFFFFFFFF) if size == LB.Config.outputs.offset else (0, 0))
+        rc = lib.lfx_create(C.byref(ctx), 0, C.byref(p), C.byref(older))
+        err = lib.lfx_last_error(None)
+        assert rc in (0, -2) and b"stream_hint" not in err and b"ring_ids" not in err and b"outputs" not in err, (size, rc, err)
+        if rc == 0:
+            lib.lfx_destroy(ctx)
     assert lib.lfx_status_string(5).decode().startswith("two adjacent points")
     assert lib.lfx_kernel_name(1) == b"ring_unit_kernel"
 
