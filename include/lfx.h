@@ -1151,6 +1151,108 @@ int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t e
                                 float *d_edge_out, float *d_surface_out, uint32_t *d_offsets_out, uint32_t *d_counts_out,
                                 size_t capacity_points, void *stream);
 
+/* --- pose graph: past poses corrected by loop closures, optimised on the device ------------------------------------------ */
+/* The problem.  NODE k: a pose [R | t], 12 doubles row-major.  Its increment is delta = (a, b), ordered as
+ * lfx_align_report.information orders it: R <- R Exp(a), t <- t + b -- the rotation first and in the node's own frame, the
+ * translation in the world frame.  Node 0 is always fixed; others may be flagged fixed (lfx_pose_graph_set_fixed).
+ * EDGE (i, j, Z = [R_Z | t_Z], Omega 6 x 6 row-major symmetric positive definite, flags): Z measures T_i^-1 T_j.  Its residual
+ * r = (phi, t_E):
+ *   R_E = R_Z^T R_i^T R_j,  d = R_i^T (t_j - t_i),  t_E = R_Z^T (d - t_Z),  phi = Log(R_E)
+ *   Log: v = (R21 - R12, R02 - R20, R10 - R01) / 2, theta = atan2(|v|, (trace - 1) / 2), phi = v theta / |v|, and phi = v
+ *   where |v| < 1e-10.  Valid for theta < 3 rad.
+ * Its Jacobians dr / d delta_i and dr / d delta_j, with Jri = J_r^-1(phi) = I + [phi]x / 2 + c [phi]x^2,
+ * c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), c = 1 / 12 + theta^2 / 720 for theta < 1e-4:
+ *   A_j = [[Jri, 0], [0, R_Z^T R_i^T]]      A_i = [[-Jri R_j^T R_i, 0], [R_Z^T [d]x, -R_Z^T R_i^T]]
+ * COST chi^2 = sum of rho_e.  An edge without LFX_EDGE_ROBUST has rho = r^T Omega r and weight w = 1.  With the flag, Huber
+ * on s = sqrt(r^T Omega r) with the config's huber_delta: s <= delta has rho = s^2, w = 1; beyond it rho = 2 delta s -
+ * delta^2, w = delta / s.  Omega enters the normal equations as w Omega.
+ * ITERATION: Gauss-Newton, (H + lambda I) delta = -g over the free nodes (H = sum A^T w Omega A, g = sum A^T w Omega r), then
+ * the increment above; lambda = damping.  It stops when max |delta| < tolerance or after max_iter steps.  If the final chi^2
+ * exceeds the initial one (by more than its rounding, 1e-12 max(1, chi^2): a consistent graph starts and ends at 1e-30),
+ * or is not a number, the initial poses are restored: LFX_POSE_GRAPH_DIVERGED.  Rotations stay
+ * orthonormal, |R^T R - I| <= 1e-12 after any number of iterations: every step re-orthonormalises the rotation it moved,
+ * R <- R (3 I - R^T R) / 2 (one step of the polar iteration; no quaternion is kept).
+ * THE SOLVER: the chain is the first edge with j == i + 1 for each i; every other edge is a loop edge --
+ * backward edges, duplicates and edges between distant nodes among them.  P = lambda I + the chain edges' blocks is block-
+ * tridiagonal in node order (a fixed node has the identity and no coupling); with J the loop edges' rows H = P + J^T W J, and
+ * the step is exact: y0 = P^-1 (-g), Y = P^-1 J^T, S = W^-1 + J Y, delta = y0 - Y S^-1 (J y0), S formed and factored in the
+ * rows whitened by the loop edges' information.  A missing chain edge leaves P block-diagonal there; lambda and the loops
+ * hold it.  A pivot that is not positive (an information matrix that is not positive definite) refuses the call:
+ * LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE, the poses untouched.  No floating-point atomic is used: the same graph gives the
+ * same bytes, however its edges were split over calls of lfx_pose_graph_add_edges. */
+#define LFX_EDGE_ROBUST 1u
+#define LFX_POSE_GRAPH_CONVERGED 0              /* max |delta| < tolerance                                   */
+#define LFX_POSE_GRAPH_MAX_ITERATIONS 1         /* max_iter steps taken, the last one not below the tolerance */
+#define LFX_POSE_GRAPH_DIVERGED 2               /* the initial poses were restored                           */
+#define LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE 3  /* the poses are untouched                                   */
+#define LFX_POSE_GRAPH_MAX_LOOP_EDGES 10000u
+typedef struct lfx_pose_graph lfx_pose_graph;
+typedef struct lfx_pose_graph_config {
+  uint32_t max_nodes;        /* >= 1 */
+  uint32_t max_edges;        /* >= 1 */
+  uint32_t max_loop_edges;   /* 512; <= LFX_POSE_GRAPH_MAX_LOOP_EDGES.  The workspace holds 6 max_nodes (6 max_loop_edges + 1) doubles */
+  uint32_t max_iter;         /* 10; 1 .. 1000 */
+  double damping;            /* 1e-6; >= 0, finite */
+  double tolerance;          /* 1e-9; >= 0, finite */
+  double huber_delta;        /* 3.0; > 0, finite */
+} lfx_pose_graph_config;
+typedef struct lfx_pose_graph_edge {
+  uint32_t i, j;             /* i != j, both nodes of the graph */
+  uint32_t flags;            /* 0 or LFX_EDGE_ROBUST */
+  uint32_t reserved;         /* 0 */
+  double z[12];              /* Z = T_i^-1 T_j (lfx_motion_between(pose_i, pose_j)) */
+  double information[36];    /* Omega, symmetric to 1e-9 of its largest entry */
+} lfx_pose_graph_edge;
+typedef struct lfx_pose_graph_result {
+  int32_t code;              /* LFX_POSE_GRAPH_* */
+  int32_t iterations;        /* steps taken */
+  double chi2_initial, chi2_final, max_step;   /* max_step: max |delta| of the last step */
+  uint32_t n_chain, n_loop, n_robust_downweighted;   /* edges with w < 1 at the final poses */
+  uint32_t reserved;
+} lfx_pose_graph_result;
+typedef struct lfx_pose_graph_info_t {
+  uint32_t n_nodes, n_edges, n_chain, n_loop;   /* n_chain / n_loop: of the edges added so far */
+  uint64_t device_bytes;                        /* everything lfx_pose_graph_create allocated on the device */
+} lfx_pose_graph_info_t;
+/* max_nodes = max_edges = 0 (the caller sets both), max_loop_edges 512, max_iter 10, damping 1e-6, tolerance 1e-9, huber_delta 3 */
+void lfx_pose_graph_default_config(lfx_pose_graph_config *config);
+/* Allocates everything the graph will ever use; no later call allocates device memory.  A config outside the ranges above is
+ * LFX_ERR_INVALID_ARGUMENT, a failed allocation LFX_ERR_OUT_OF_MEMORY with nothing left allocated. */
+int lfx_pose_graph_create(lfx_ctx *ctx, const lfx_pose_graph_config *config, lfx_pose_graph **out);
+void lfx_pose_graph_destroy(lfx_pose_graph *graph);
+int lfx_pose_graph_info(const lfx_pose_graph *graph, lfx_pose_graph_info_t *info);
+/* n poses on the host ([n][12]) appended as nodes; *first_id (may be NULL) = the id of the first.  A pose that is not finite is
+ * LFX_ERR_INVALID_ARGUMENT, more nodes than max_nodes LFX_ERR_CAPACITY: nothing changed, nothing queued. */
+int lfx_pose_graph_add_nodes(lfx_ctx *ctx, lfx_pose_graph *graph, const double *poses, uint32_t n, uint32_t *first_id, void *stream);
+/* Node `node` held where it is (fixed != 0) or free again.  Node 0 stays fixed whatever is asked. */
+int lfx_pose_graph_set_fixed(lfx_ctx *ctx, lfx_pose_graph *graph, uint32_t node, int fixed, void *stream);
+/* n edges on the host appended.  Checked before anything is touched: i == j, an id that is not a node, flags beyond
+ * LFX_EDGE_ROBUST, Z or Omega not finite, Omega not symmetric are LFX_ERR_INVALID_ARGUMENT; more edges than max_edges, or more
+ * loop edges than max_loop_edges, LFX_ERR_CAPACITY. */
+int lfx_pose_graph_add_edges(lfx_ctx *ctx, lfx_pose_graph *graph, const lfx_pose_graph_edge *edges, uint32_t n, void *stream);
+/* Gauss-Newton to the config's tolerance; synchronous (the host reads one small record per iteration).  Returns LFX_OK
+ * whenever the optimiser ran, whatever result->code says; a graph without edges is LFX_ERR_INVALID_ARGUMENT.  Ordered behind
+ * every earlier call on this graph, whichever streams they used. */
+int lfx_pose_graph_optimize(lfx_ctx *ctx, lfx_pose_graph *graph, lfx_pose_graph_result *result, void *stream);
+/* Nodes first .. first + count - 1 copied to the host ([count][12]); synchronous. */
+int lfx_pose_graph_poses(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t first, uint32_t count, double *poses_out, void *stream);
+/* The same range overwritten from the host (a new initial guess; poses that are not finite are refused). */
+int lfx_pose_graph_set_poses(lfx_ctx *ctx, lfx_pose_graph *graph, uint32_t first, uint32_t count, const double *poses, void *stream);
+/* The poses where they live: *d_poses = [n_nodes][12] doubles on the device.  The ADDRESS is valid until the graph is
+ * destroyed.  The CONTENTS are current behind `stream` once the graph's earlier calls have passed (the call queues that wait
+ * on `stream`), and stay so until the next call that writes the graph (add_nodes, set_poses, optimize): nothing orders that
+ * call behind the caller's reads, so the reader must have finished, or must order the writing call's stream behind its own
+ * work itself, before the graph is written again.  What a map rebuild from corrected poses reads. */
+int lfx_pose_graph_view(lfx_ctx *ctx, const lfx_pose_graph *graph, const double **d_poses, uint32_t *n_nodes, void *stream);
+/* Per edge, at the poses the last lfx_pose_graph_optimize left: rho[e] and w[e] (either may be NULL), first .. first + count - 1.
+ * A false loop closure under LFX_EDGE_ROBUST shows as the smallest w.  LFX_ERR_INVALID_ARGUMENT before the first optimise or
+ * when nodes, edges or poses were written since. */
+int lfx_pose_graph_edge_chi2(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t first, uint32_t count, double *rho, double *w, void *stream);
+/* An alignment report's information (lfx_align_report.information: a in the scan's frame, b in the map frame) in an edge's
+ * residual coordinates: Omega = B H B^T, B = blkdiag(I, R_j^T), pose_j the scan's pose the report was made at.  Host only;
+ * every sum of three terms is (a0 b0 + a1 b1) + a2 b2.  out may be report_information. */
+int lfx_pose_graph_edge_information(const double pose_j[12], const double report_information[36], double out[36]);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.
@@ -1208,9 +1310,10 @@ int lfx_route_choice(const uint32_t report[LFX_ROUTE_REPORT_WORDS], uint32_t rep
                      int organised_possible, uint32_t batch, uint32_t max_rings, uint32_t choice[LFX_ROUTE_CHOICE_WORDS]);
 
 /* --- measurement ------------------------------------------------------------------------- */
-#define LFX_N_KERNELS 13  /* ring_scatter, ring_unit, ring_order, ring_unit (second pass), ring_extract (the bucketing route), ring_totals, feature_compact (compaction), ring_unit_org (organised scans), ring_cut (transforms of rotated / reversed rings), fallback_tail (the organised route's tail), grid_count (valid returns per ring and column piece of a grid with holes), batch_reset, ring_long (rings longer than LFX_MAX_RING_POINTS) */
+#define LFX_N_KERNELS 24  /* ring_scatter, ring_unit, ring_order, ring_unit (second pass), ring_extract (the bucketing route), ring_totals, feature_compact (compaction), ring_unit_org (organised scans), ring_cut (transforms of rotated / reversed rings), fallback_tail (the organised route's tail), grid_count (valid returns per ring and column piece of a grid with holes), batch_reset, ring_long (rings longer than LFX_MAX_RING_POINTS), then the pose graph's: linearize, node (gradient and P's blocks), reduce, chain_factor, chain_solve, s_assemble, s_diag, s_panel, s_update, s_solve, step */
 int lfx_set_profiling(lfx_ctx *ctx, int enabled);
-/* Record the events around every n-th batch only (default 1).  The event pairs between the kernels of a batch
+/* Record the events around every n-th batch only (default 1; the pose graph's kernels have no batches and are timed in
+ * every lfx_pose_graph_optimize while profiling is on).  The event pairs between the kernels of a batch
  * cost ~7 % of the device-resident throughput at 64x1800x256; sampled, the durations stay live and the cost goes. */
 int lfx_set_profiling_interval(lfx_ctx *ctx, uint32_t every_n_batches);
 /* Sum of HIP-event durations per kernel since profiling was enabled, and launches counted. */

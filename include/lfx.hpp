@@ -774,5 +774,98 @@ private:
   lfx_place_db * db_ = nullptr;
 };
 
+// The pose graph (lfx_pose_graph): keyframe poses as nodes, odometry steps and loop closures as edges, optimised on the
+// device of `fx`, which must outlive it.  Poses are 12 doubles [R | t] row-major; node 0 is fixed.  An edge's information
+// comes from an alignment report through EdgeInformation, its measurement from lfx_motion_between.
+class PoseGraph
+{
+public:
+  static lfx_pose_graph_config DefaultConfig(std::uint32_t max_nodes, std::uint32_t max_edges)
+  {
+    lfx_pose_graph_config c;
+    lfx_pose_graph_default_config(&c);
+    c.max_nodes = max_nodes;
+    c.max_edges = max_edges;
+    return c;
+  }
+  PoseGraph(const FeatureExtraction & fx, const lfx_pose_graph_config & config)
+  : fx_(fx)
+  {
+    Check(lfx_pose_graph_create(fx.handle(), &config, &graph_));
+  }
+  ~PoseGraph() {lfx_pose_graph_destroy(graph_);}
+  PoseGraph(const PoseGraph &) = delete;
+  PoseGraph & operator=(const PoseGraph &) = delete;
+
+  // report_information in an edge's residual coordinates (lfx_pose_graph_edge_information)
+  static std::vector<double> EdgeInformation(const double pose_j[12], const double report_information[36])
+  {
+    std::vector<double> out(36);
+    if (lfx_pose_graph_edge_information(pose_j, report_information, out.data()) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "null argument");}
+    return out;
+  }
+  // poses: n x 12 doubles; the id of the first node added
+  std::uint32_t AddNodes(const std::vector<double> & poses, void * stream = nullptr)
+  {
+    std::uint32_t first = 0;
+    Check(poses.size() % 12u == 0u ? lfx_pose_graph_add_nodes(fx_.handle(), graph_, poses.data(), static_cast<std::uint32_t>(poses.size() / 12u), &first, stream) :
+      LFX_ERR_INVALID_ARGUMENT);
+    return first;
+  }
+  void SetFixed(std::uint32_t node, bool fixed = true, void * stream = nullptr) {Check(lfx_pose_graph_set_fixed(fx_.handle(), graph_, node, fixed ? 1 : 0, stream));}
+  void AddEdges(const std::vector<lfx_pose_graph_edge> & edges, void * stream = nullptr)
+  {
+    Check(lfx_pose_graph_add_edges(fx_.handle(), graph_, edges.data(), static_cast<std::uint32_t>(edges.size()), stream));
+  }
+  lfx_pose_graph_result Optimize(void * stream = nullptr)
+  {
+    lfx_pose_graph_result r;
+    Check(lfx_pose_graph_optimize(fx_.handle(), graph_, &r, stream));
+    return r;
+  }
+  std::vector<double> Poses(std::uint32_t first, std::uint32_t count, void * stream = nullptr) const
+  {
+    std::vector<double> out(static_cast<std::size_t>(count) * 12u);
+    Check(lfx_pose_graph_poses(fx_.handle(), graph_, first, count, out.data(), stream));
+    return out;
+  }
+  std::vector<double> Poses() const {return Poses(0, Info().n_nodes);}
+  void SetPoses(std::uint32_t first, const std::vector<double> & poses, void * stream = nullptr)
+  {
+    Check(poses.size() % 12u == 0u ? lfx_pose_graph_set_poses(fx_.handle(), graph_, first, static_cast<std::uint32_t>(poses.size() / 12u), poses.data(), stream) :
+      LFX_ERR_INVALID_ARGUMENT);
+  }
+  // the poses on the device ([n_nodes][12] doubles), current behind `stream`
+  const double * View(std::uint32_t * n_nodes, void * stream = nullptr) const
+  {
+    const double * p = nullptr;
+    Check(lfx_pose_graph_view(fx_.handle(), graph_, &p, n_nodes, stream));
+    return p;
+  }
+  // per edge rho and w at the poses the last Optimize left
+  void EdgeChi2(std::vector<double> & rho, std::vector<double> & w, void * stream = nullptr) const
+  {
+    const std::uint32_t n = Info().n_edges;
+    rho.resize(n);
+    w.resize(n);
+    Check(lfx_pose_graph_edge_chi2(fx_.handle(), graph_, 0, n, rho.data(), w.data(), stream));
+  }
+  lfx_pose_graph_info_t Info() const
+  {
+    lfx_pose_graph_info_t i;
+    lfx_pose_graph_info(graph_, &i);
+    return i;
+  }
+  lfx_pose_graph * handle() const {return graph_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_pose_graph * graph_ = nullptr;
+};
+
 }  // namespace lfx
 #endif  // LFX_HPP_

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LFX_LIB_PATH") or os.path.join(_HERE, "_lib", "liblfx.so")   # override: A/B builds only
 
-LFX_N_KERNELS = 13
+LFX_N_KERNELS = 24
 MAX_RING_POINTS = 4608            # LFX_MAX_RING_POINTS: the longest ring the LDS-resident kernels take; the default ring capacity
 MAX_LONG_RING_POINTS = 262144     # LFX_MAX_LONG_RING_POINTS: the largest max_points_per_ring (longer rings: HBM workspace)
 MAX_RINGS = 256
@@ -196,6 +196,36 @@ SEG_NO_ID = 0xFFFFFFFF
 SEGMENT_MAX_ROWS, SEGMENT_MAX_COLUMNS, SEGMENT_BUDGET_CELLS = 128, 4096, 1 << 24
 
 
+class PoseGraphConfig(C.Structure):
+    """lfx_pose_graph_config: the capacities a pose graph is allocated for and the optimiser's settings."""
+    _fields_ = [("max_nodes", C.c_uint32), ("max_edges", C.c_uint32), ("max_loop_edges", C.c_uint32), ("max_iter", C.c_uint32),
+                ("damping", C.c_double), ("tolerance", C.c_double), ("huber_delta", C.c_double)]
+
+
+class PoseGraphEdge(C.Structure):
+    """lfx_pose_graph_edge: Z = T_i^-1 T_j with its information in the residual's coordinates."""
+    _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("z", C.c_double * 12),
+                ("information", C.c_double * 36)]
+
+
+class PoseGraphResult(C.Structure):
+    _fields_ = [("code", C.c_int32), ("iterations", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),
+                ("max_step", C.c_double), ("n_chain", C.c_uint32), ("n_loop", C.c_uint32), ("n_robust_downweighted", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PoseGraphInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_edges", C.c_uint32), ("n_chain", C.c_uint32), ("n_loop", C.c_uint32),
+                ("device_bytes", C.c_uint64)]
+
+
+EDGE_ROBUST = 1
+POSE_GRAPH_CONVERGED, POSE_GRAPH_MAX_ITERATIONS, POSE_GRAPH_DIVERGED, POSE_GRAPH_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3
+POSE_GRAPH_MAX_LOOP_EDGES = 10000
+POSE_GRAPH_EDGE_DTYPE = [("i", "<u4"), ("j", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("z", "<f8", 12), ("information", "<f8", 36)]
+"""lfx_pose_graph_edge as a numpy record (400 bytes)."""
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -229,6 +259,9 @@ EXPORTS = [
     "lfx_place_db_destroy", "lfx_place_db_add", "lfx_place_db_add_host", "lfx_place_db_size", "lfx_place_db_download",
     "lfx_place_db_query",
     "lfx_segment_default_config", "lfx_segment_tables", "lfx_segment_batch", "lfx_pack_features_segmented",
+    "lfx_pose_graph_default_config", "lfx_pose_graph_create", "lfx_pose_graph_destroy", "lfx_pose_graph_info", "lfx_pose_graph_add_nodes",
+    "lfx_pose_graph_set_fixed", "lfx_pose_graph_add_edges", "lfx_pose_graph_optimize", "lfx_pose_graph_poses", "lfx_pose_graph_set_poses",
+    "lfx_pose_graph_view", "lfx_pose_graph_edge_chi2", "lfx_pose_graph_edge_information",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -399,6 +432,22 @@ def load(test_hooks=False):
     L.lfx_color_points_by_label.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.lfx_set_profiling.argtypes = [vp, i32]
     L.lfx_set_profiling_interval.argtypes = [vp, C.c_uint32]
+    ppg = C.POINTER(PoseGraphConfig)
+    L.lfx_pose_graph_default_config.argtypes = [ppg]
+    L.lfx_pose_graph_default_config.restype = None
+    L.lfx_pose_graph_create.argtypes = [vp, ppg, C.POINTER(vp)]
+    L.lfx_pose_graph_destroy.argtypes = [vp]
+    L.lfx_pose_graph_destroy.restype = None
+    L.lfx_pose_graph_info.argtypes = [vp, C.POINTER(PoseGraphInfo)]
+    L.lfx_pose_graph_add_nodes.argtypes = [vp, vp, vp, u32, C.POINTER(u32), vp]
+    L.lfx_pose_graph_set_fixed.argtypes = [vp, vp, u32, i32, vp]
+    L.lfx_pose_graph_add_edges.argtypes = [vp, vp, vp, u32, vp]
+    L.lfx_pose_graph_optimize.argtypes = [vp, vp, C.POINTER(PoseGraphResult), vp]
+    L.lfx_pose_graph_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_pose_graph_set_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_pose_graph_view.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(u32), vp]
+    L.lfx_pose_graph_edge_chi2.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.lfx_pose_graph_edge_information.argtypes = [vp, vp, vp]
     L.lfx_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.lfx_kernel_name.argtypes = [i32]
     L.lfx_kernel_name.restype = C.c_char_p

@@ -26,7 +26,10 @@ std::string g_create_error;
 const char * kKernelNames[LFX_N_KERNELS] = {           // (in the order of KernelSlot, lfx_internal.hpp)
   "ring_scatter_kernel", "ring_unit_kernel", "ring_order_kernel", "ring_unit_kernel(second pass)", "ring_extract_kernel",
   "ring_totals_kernel", "feature_compact_kernel", "ring_unit_org_kernel", "ring_cut_kernel", "fallback_tail_kernel", "grid_count_kernel",
-  "batch_reset_kernel", "ring_long_kernel"};
+  "batch_reset_kernel", "ring_long_kernel",
+  "pose_graph_linearize_kernel", "pose_graph_node_kernel", "pose_graph_reduce_kernel", "pose_graph_chain_factor_kernel",
+  "pose_graph_chain_solve_kernel", "pose_graph_s_assemble_kernel", "pose_graph_s_diag_kernel", "pose_graph_s_panel_kernel",
+  "pose_graph_s_update_kernel", "pose_graph_s_solve_kernel", "pose_graph_step_kernel"};
 
 // IsNeighborXY compares acos(cos_angle) with the threshold (neighbor.hpp:44-48, math.cpp:45).
 // acos is monotone, so that test is a bound on cos_angle itself: the smallest double c with
@@ -66,40 +69,10 @@ std::string & lfx_host::create_error() {return g_create_error;}
 namespace
 {
 
-hipEvent_t take_event(lfx_ctx * c)
-{
-  if (!c->free_events.empty()) {
-    hipEvent_t e = c->free_events.back();
-    c->free_events.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
-struct Timed
+struct Timed : TimedSpan                 // a batch's launches: timed in the batches lfx_set_profiling_interval samples
 {
   Timed(lfx_ctx * c, KernelSlot k, hipStream_t s)
-  : c_(c), k_(k), s_(s)
-  {
-    if (c_->profile_now) {
-      a_ = take_event(c_);
-      b_ = take_event(c_);
-      (void)hipEventRecord(a_, s_);
-    }
-  }
-  ~Timed()
-  {
-    if (c_->profile_now) {
-      (void)hipEventRecord(b_, s_);
-      c_->spans.push_back({a_, b_, k_});
-    }
-  }
-  lfx_ctx * c_;
-  int k_;
-  hipStream_t s_;
-  hipEvent_t a_ = nullptr, b_ = nullptr;
+  : TimedSpan(c, c->profile_now, k, s) {}
 };
 
 int drain_spans(lfx_ctx * c)

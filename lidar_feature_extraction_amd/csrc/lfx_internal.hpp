@@ -163,7 +163,9 @@ static_assert(!std::is_copy_constructible_v<PinnedBuf> && !std::is_copy_assignab
 enum KernelSlot : int
 {
   kSlotScatter, kSlotUnit, kSlotOrder, kSlotUnitSecond, kSlotExtract, kSlotTotals, kSlotCompact, kSlotUnitOrg, kSlotCut, kSlotTail,
-  kSlotGridCount, kSlotReset, kSlotLong, kSlotCount
+  kSlotGridCount, kSlotReset, kSlotLong,
+  kSlotPgLinearize, kSlotPgNode, kSlotPgReduce, kSlotPgChainFactor, kSlotPgChainSolve, kSlotPgAssemble, kSlotPgDiag, kSlotPgPanel, kSlotPgUpdate,
+  kSlotPgSolve, kSlotPgStep, kSlotCount
 };
 static_assert(kSlotCount == LFX_N_KERNELS, "a slot per kernel of lfx_kernel_times");
 
@@ -380,6 +382,47 @@ namespace lfx_host
 {
 
 std::string & create_error();          // what lfx_last_error(NULL) reports (lfx_api.hip)
+
+// lfx_kernel_times: a pair of events around one launch (or a few) on `s`, kept in the context's spans until they are drained,
+// where `on`; events are reused.  The extraction's batches pass profile_now (lfx_set_profiling_interval samples batches); the
+// pose graph has no batches and passes profiling.
+inline hipEvent_t take_event(lfx_ctx * c)
+{
+  if (!c->free_events.empty()) {
+    hipEvent_t e = c->free_events.back();
+    c->free_events.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  (void)hipEventCreate(&e);
+  return e;
+}
+struct TimedSpan
+{
+  TimedSpan(lfx_ctx * c, bool on, int k, hipStream_t s)
+  : c_(c), on_(on), k_(k), s_(s)
+  {
+    if (on_) {
+      a_ = take_event(c_);
+      b_ = take_event(c_);
+      (void)hipEventRecord(a_, s_);
+    }
+  }
+  ~TimedSpan()
+  {
+    if (on_) {
+      (void)hipEventRecord(b_, s_);
+      c_->spans.push_back({a_, b_, k_});
+    }
+  }
+  TimedSpan(const TimedSpan &) = delete;
+  TimedSpan & operator=(const TimedSpan &) = delete;
+  lfx_ctx * c_;
+  bool on_;
+  int k_;
+  hipStream_t s_;
+  hipEvent_t a_ = nullptr, b_ = nullptr;
+};
 
 #define LFX_HIP(ctx, call) \
   do { \

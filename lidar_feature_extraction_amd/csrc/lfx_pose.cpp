@@ -242,6 +242,31 @@ int lfx_align_covariance_ros(const double pose[12], const double covariance[36],
   return LFX_OK;
 }
 
+// A report's information in a pose-graph edge's residual coordinates (include/lfx.h): out = B H B^T, B = blkdiag(I, R^T).
+// Every sum of three terms is (a0 b0 + a1 b1) + a2 b2.
+int lfx_pose_graph_edge_information(const double pose_j[12], const double report_information[36], double out[36])
+{
+  if (!pose_j || !report_information || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  auto R = [&](int r, int c) {return pose_j[4 * r + c];};
+  const double * H = report_information;
+  double bh[36];                                      // B H: rows 0-2 = H's rotation rows, rows 3-5 = R^T times its translation rows
+  for (int c = 0; c < 6; c++) {
+    for (int i = 0; i < 3; i++) {
+      bh[6 * i + c] = H[6 * i + c];
+      bh[6 * (3 + i) + c] = (R(0, i) * H[18 + c] + R(1, i) * H[24 + c]) + R(2, i) * H[30 + c];
+    }
+  }
+  double res[36];                                     // (out may be report_information)
+  for (int r = 0; r < 6; r++) {
+    for (int j = 0; j < 3; j++) {
+      res[6 * r + j] = bh[6 * r + j];
+      res[6 * r + 3 + j] = (bh[6 * r + 3] * R(0, j) + bh[6 * r + 4] * R(1, j)) + bh[6 * r + 5] * R(2, j);
+    }
+  }
+  std::memcpy(out, res, sizeof(res));
+  return LFX_OK;
+}
+
 // Scan-context descriptors (include/lfx.h, the place recognition section): the defaults, and the tables the kernel is given.
 void lfx_scan_context_default_config(lfx_scan_context_config * config)
 {

@@ -1,0 +1,553 @@
+// lfx_posegraph.hip -- the pose graph (include/lfx.h, the pose graph section; lfx_kernels_posegraph.hpp): nodes and edges
+// kept on the device, Gauss-Newton over them with the chain-and-loop solver.  The host keeps what it needs to check a call
+// before anything is queued (the edges' ends, which nodes are fixed) and builds the node -> (edge, side) incidence lists,
+// stable by edge id, whenever edges were added.  Everything is allocated by lfx_pose_graph_create.
+#include "lfx_internal.hpp"
+#include "lfx_kernels_posegraph.hpp"
+
+#include <algorithm>
+#include <cstdint>
+
+using namespace lfx_host;
+
+static_assert(sizeof(lfx::PgEdge) == sizeof(lfx_pose_graph_edge) && sizeof(lfx::PgEdge) == 400, "an edge goes up as the caller wrote it, but for one word");
+static_assert(lfx::kPgEdgeRobust == LFX_EDGE_ROBUST, "the kernels' flag is the header's");
+
+struct lfx_pose_graph
+{
+  int device = 0;
+  lfx_pose_graph_config cfg{};
+  uint32_t n_nodes = 0, n_edges = 0, n_chain = 0, n_loop = 0, ldy_cap = 0;
+  uint64_t device_bytes = 0;
+  // the host's copy of the topology
+  std::vector<uint32_t> edge_i, edge_j, edge_loop, chain_edge;
+  std::vector<uint8_t> fixed;
+  bool topology_stale = true;            // edges or nodes were added since the lists went up
+  bool linearised = false;               // lin holds the edges' values at the poses the last optimise left
+  // what goes up: rewritten only once the graph's last queued call has passed
+  std::vector<lfx::PgEdge> stage_edges;
+  std::vector<uint32_t> stage_lists;
+  mutable std::vector<double> stage_lin;
+  DevBuf<double> poses, backup, lin, loop_j, grad, diag, off, fac_l, fac_m, y, s, z, step_max;
+  DevBuf<uint8_t> d_fixed;
+  DevBuf<lfx::PgEdge> edges;
+  DevBuf<uint32_t> node_begin, inc, d_chain_edge, loop_edge, status;
+  DevBuf<lfx::PgRecord> record;
+  PinnedBuf h_record;
+  PinnedBuf h_poses;                     // poses on their way up ([max_nodes][12]): pinned, so that the copy is queued and the call returns
+  mutable hipEvent_t tail = nullptr;     // recorded behind the last call that touched the graph, on its stream
+  mutable bool pending = false;
+};
+
+namespace
+{
+
+struct Timed : TimedSpan                 // whenever profiling is on: the sampling interval counts batches, and there are none here
+{
+  Timed(lfx_ctx * c, KernelSlot k, hipStream_t s)
+  : TimedSpan(c, c->profiling, k, s) {}
+};
+
+bool finite_all(const double * v, size_t n)
+{
+  for (size_t i = 0; i < n; i++) {
+    if (!std::isfinite(v[i])) {return false;}
+  }
+  return true;
+}
+
+int check_graph(lfx_ctx * c, const lfx_pose_graph * g)
+{
+  if (g->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph lives on another device");}
+  return LFX_OK;
+}
+
+// `st` behind the graph's last call; after the call's own work: done()
+int order_behind(lfx_ctx * c, const lfx_pose_graph * g, hipStream_t st)
+{
+  if (g->pending) {LFX_HIP(c, hipStreamWaitEvent(st, g->tail, 0));}
+  return LFX_OK;
+}
+int done(lfx_ctx * c, const lfx_pose_graph * g, hipStream_t st)
+{
+  LFX_HIP(c, hipEventRecord(g->tail, st));
+  g->pending = true;
+  return LFX_OK;
+}
+// the host's staging vectors may be rewritten
+int settle(lfx_ctx * c, const lfx_pose_graph * g)
+{
+  if (g->pending) {LFX_HIP(c, hipEventSynchronize(g->tail)); g->pending = false;}
+  return LFX_OK;
+}
+
+uint32_t ldy_of(uint32_t n_loop) {return (6u * n_loop + 1u + 7u) & ~7u;}
+
+lfx::PgArgs args_of(lfx_pose_graph * g)
+{
+  lfx::PgArgs a{};
+  a.poses = g->poses.p; a.fixed = g->d_fixed.p; a.edges = g->edges.p; a.lin = g->lin.p; a.loop_j = g->loop_j.p;
+  a.node_begin = g->node_begin.p; a.inc = g->inc.p; a.chain_edge = g->d_chain_edge.p; a.loop_edge = g->loop_edge.p;
+  a.grad = g->grad.p; a.diag = g->diag.p; a.off = g->off.p; a.fac_l = g->fac_l.p; a.fac_m = g->fac_m.p;
+  a.y = g->y.p; a.s = g->s.p; a.z = g->z.p; a.step_max = g->step_max.p; a.status = g->status.p; a.record = g->record.p;
+  a.n_nodes = g->n_nodes; a.n_edges = g->n_edges; a.n_loop = g->n_loop; a.ldy = ldy_of(g->n_loop);
+  a.huber_delta = g->cfg.huber_delta; a.damping = g->cfg.damping;
+  return a;
+}
+
+// the lists the kernels walk: node_begin [N + 1], inc [2 E], chain_edge [N], loop_edge [L], one block
+int upload_topology(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
+{
+  const uint32_t N = g->n_nodes, E = g->n_edges, L = g->n_loop;
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  std::vector<uint32_t> & w = g->stage_lists;
+  w.assign((size_t)N + 1u + 2u * (size_t)E + N + L, 0u);
+  uint32_t * begin = w.data(), * inc = begin + N + 1u, * chain = inc + 2u * (size_t)E, * loops = chain + N;
+  for (uint32_t e = 0; e < E; e++) {begin[g->edge_i[e] + 1u]++; begin[g->edge_j[e] + 1u]++;}
+  for (uint32_t k = 0; k < N; k++) {begin[k + 1u] += begin[k];}
+  std::vector<uint32_t> at(begin, begin + N);
+  for (uint32_t e = 0; e < E; e++) {              // ascending e: every node's list is in edge order
+    inc[at[g->edge_i[e]]++] = 2u * e;
+    inc[at[g->edge_j[e]]++] = 2u * e + 1u;
+    if (g->edge_loop[e] != lfx::kPgNone) {loops[g->edge_loop[e]] = e;}
+  }
+  for (uint32_t k = 0; k < N; k++) {chain[k] = g->chain_edge[k];}
+  LFX_HIP(c, hipMemcpyAsync(g->node_begin.p, begin, sizeof(uint32_t) * ((size_t)N + 1u), hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(g->inc.p, inc, sizeof(uint32_t) * 2u * (size_t)E, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(g->d_chain_edge.p, chain, sizeof(uint32_t) * N, hipMemcpyHostToDevice, st));
+  if (L) {LFX_HIP(c, hipMemcpyAsync(g->loop_edge.p, loops, sizeof(uint32_t) * L, hipMemcpyHostToDevice, st));}
+  g->topology_stale = false;
+  return LFX_OK;
+}
+
+// r, w, rho and the Jacobians of every edge, the gradient and P's blocks, chi^2 into record[slot]
+int launch_linearize(lfx_ctx * c, const lfx::PgArgs & a, uint32_t slot, bool with_step, hipStream_t st)
+{
+  {
+    Timed t(c, kSlotPgLinearize, st);
+    hipLaunchKernelGGL(lfx::pose_graph_linearize_kernel, dim3((a.n_edges + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  {
+    Timed t(c, kSlotPgNode, st);
+    hipLaunchKernelGGL(lfx::pose_graph_node_kernel, dim3(a.n_nodes), dim3(lfx::kPgWave), 0, st, a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  {
+    Timed t(c, kSlotPgReduce, st);
+    hipLaunchKernelGGL(lfx::pose_graph_reduce_kernel, dim3(1), dim3(lfx::kPgThreads), 0, st, a, slot, with_step ? 1 : 0);
+  }
+  LFX_HIP(c, hipGetLastError());
+  return LFX_OK;
+}
+
+// one Gauss-Newton step from the linearisation that is on the device: factor P, solve, S, the step, the poses moved
+int launch_step(lfx_ctx * c, const lfx::PgArgs & a, hipStream_t st)
+{
+  const uint32_t n = 6u * a.n_loop, P = lfx::kPgPanel;
+  {
+    Timed t(c, kSlotPgChainFactor, st);
+    hipLaunchKernelGGL(lfx::pose_graph_chain_factor_kernel, dim3(1), dim3(lfx::kPgWave), 0, st, a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  {
+    Timed t(c, kSlotPgChainSolve, st);
+    hipLaunchKernelGGL(lfx::pose_graph_chain_solve_kernel, dim3((n + 1u + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  if (n) {
+    {
+      Timed t(c, kSlotPgAssemble, st);
+      hipLaunchKernelGGL(lfx::pose_graph_s_assemble_kernel, dim3((n + 1u + lfx::kPgThreads - 1u) / lfx::kPgThreads, n), dim3(lfx::kPgThreads), 0, st, a);
+    }
+    LFX_HIP(c, hipGetLastError());
+    // blocked right-looking Cholesky, a sequence of launches: the number of panels is known here
+    for (uint32_t p0 = 0; p0 < n; p0 += P) {
+      const uint32_t nb = std::min(P, n - p0);
+      {
+        Timed t(c, kSlotPgDiag, st);
+        hipLaunchKernelGGL(lfx::pose_graph_s_diag_kernel, dim3(1), dim3(lfx::kPgThreads), 0, st, a, p0, nb);
+      }
+      LFX_HIP(c, hipGetLastError());
+      if (p0 + P >= n) {break;}                        // (nothing below a last panel, full or not)
+      const uint32_t below = n - (p0 + P);
+      {
+        Timed t(c, kSlotPgPanel, st);
+        hipLaunchKernelGGL(lfx::pose_graph_s_panel_kernel, dim3((below + lfx::kPgThreads - 1u) / lfx::kPgThreads), dim3(lfx::kPgThreads), 0, st, a, p0);
+      }
+      LFX_HIP(c, hipGetLastError());
+      const uint32_t tiles = (below + lfx::kPgTile - 1u) / lfx::kPgTile;
+      {
+        Timed t(c, kSlotPgUpdate, st);
+        hipLaunchKernelGGL(lfx::pose_graph_s_update_kernel, dim3(tiles, tiles), dim3(lfx::kPgThreads), 0, st, a, p0);
+      }
+      LFX_HIP(c, hipGetLastError());
+    }
+    {
+      Timed t(c, kSlotPgSolve, st);
+      hipLaunchKernelGGL(lfx::pose_graph_s_solve_kernel, dim3(1), dim3(lfx::kPgThreads), 0, st, a);
+    }
+    LFX_HIP(c, hipGetLastError());
+  }
+  {
+    Timed t(c, kSlotPgStep, st);
+    hipLaunchKernelGGL(lfx::pose_graph_step_kernel, dim3(a.n_nodes), dim3(n > 64u ? lfx::kPgThreads : lfx::kPgWave), 0, st, a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  return LFX_OK;
+}
+
+int check_config(lfx_ctx * c, const lfx_pose_graph_config * f)
+{
+  if (f->max_nodes < 1u || f->max_edges < 1u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_nodes and max_edges must be >= 1");}
+  if (f->max_loop_edges > LFX_POSE_GRAPH_MAX_LOOP_EDGES) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_loop_edges must be <= 10000");}
+  if (f->max_iter < 1u || f->max_iter > 1000u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be in 1 .. 1000");}
+  if (!std::isfinite(f->damping) || f->damping < 0.0 || !std::isfinite(f->tolerance) || f->tolerance < 0.0 || !std::isfinite(f->huber_delta) ||
+    !(f->huber_delta > 0.0))
+  {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "damping and tolerance must be finite and >= 0, huber_delta finite and > 0");
+  }
+  return LFX_OK;
+}
+
+// the edges' values at the poses on the device (after a refused or diverged call put the initial poses back)
+int relinearize(lfx_ctx * c, lfx_pose_graph * g, const lfx::PgArgs & a, hipStream_t st)
+{
+  LFX_HIP(c, hipMemsetAsync(g->status.p, 0, sizeof(uint32_t), st));
+  return launch_linearize(c, a, 0u, false, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+void lfx_pose_graph_default_config(lfx_pose_graph_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_pose_graph_config{};
+  config->max_loop_edges = 512u;
+  config->max_iter = 10u;
+  config->damping = 1e-6;
+  config->tolerance = 1e-9;
+  config->huber_delta = 3.0;
+}
+
+int lfx_pose_graph_create(lfx_ctx * c, const lfx_pose_graph_config * config, lfx_pose_graph ** out)
+{
+  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!config || !out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "config and out are required");}
+  const int rc = check_config(c, config);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  lfx_pose_graph * g = new (std::nothrow) lfx_pose_graph();
+  if (!g) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph");}
+  g->device = c->device;
+  g->cfg = *config;
+  const size_t N = config->max_nodes, E = config->max_edges, L = config->max_loop_edges, n = 6u * L;
+  g->ldy_cap = ldy_of(config->max_loop_edges);
+  auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_pose_graph_destroy(g); return fail(c, code, why);};
+  uint64_t bytes = 0;
+  bool ok = true;
+  auto get = [&](auto & buf, size_t count) {
+      ok = ok && buf.alloc(count) == hipSuccess;
+      bytes += (uint64_t)count * sizeof(*buf.p);
+    };
+  get(g->poses, 12u * N); get(g->backup, 12u * N); get(g->d_fixed, N); get(g->edges, E); get(g->lin, (size_t)lfx::kPgLin * E);
+  get(g->loop_j, 72u * std::max<size_t>(L, 1u)); get(g->node_begin, N + 1u); get(g->inc, 2u * E); get(g->d_chain_edge, N);
+  get(g->loop_edge, std::max<size_t>(L, 1u)); get(g->grad, 6u * N); get(g->diag, 36u * N); get(g->off, 36u * N); get(g->fac_l, 36u * N);
+  get(g->fac_m, 36u * N); get(g->y, 6u * N * g->ldy_cap); get(g->s, std::max<size_t>(n * n, 1u)); get(g->z, std::max<size_t>(n, 1u));
+  get(g->step_max, N); get(g->status, 1u); get(g->record, (size_t)config->max_iter + 2u);
+  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's " + std::to_string(bytes) + " bytes");}
+  g->device_bytes = bytes;
+  if (g->h_record.reserve(sizeof(lfx::PgRecord) * ((size_t)config->max_iter + 2u)) != hipSuccess) {
+    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's status record");
+  }
+  if (g->h_poses.reserve(sizeof(double) * 12u * N) != hipSuccess) {
+    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's staging block");
+  }
+  if (hipEventCreateWithFlags(&g->tail, hipEventDisableTiming) != hipSuccess) {
+    g->tail = nullptr;
+    return give_up(LFX_ERR_HIP, "cannot create the pose graph's event");
+  }
+  g->edge_i.reserve(E); g->edge_j.reserve(E); g->edge_loop.reserve(E);
+  g->chain_edge.reserve(N); g->fixed.reserve(N);
+  *out = g;
+  return LFX_OK;
+}
+
+void lfx_pose_graph_destroy(lfx_pose_graph * g)
+{
+  if (!g) {return;}
+  (void)hipSetDevice(g->device);
+  if (g->tail) {(void)hipEventSynchronize(g->tail); (void)hipEventDestroy(g->tail);}
+  delete g;
+}
+
+int lfx_pose_graph_info(const lfx_pose_graph * g, lfx_pose_graph_info_t * info)
+{
+  if (!g || !info) {return LFX_ERR_INVALID_ARGUMENT;}
+  info->n_nodes = g->n_nodes; info->n_edges = g->n_edges; info->n_chain = g->n_chain; info->n_loop = g->n_loop;
+  info->device_bytes = g->device_bytes;
+  return LFX_OK;
+}
+
+int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * poses, uint32_t n, uint32_t * first_id, void * stream)
+{
+  if (!c || !g || (n && !poses)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!finite_all(poses, 12u * (size_t)n)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
+  if (n > g->cfg.max_nodes - g->n_nodes) {
+    return fail(c, LFX_ERR_CAPACITY, "the pose graph holds " + std::to_string(g->n_nodes) + " of " + std::to_string(g->cfg.max_nodes) +
+             " nodes: no room for " + std::to_string(n) + " more");
+  }
+  if (first_id) {*first_id = g->n_nodes;}
+  if (n == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  const uint32_t first = g->n_nodes;
+  std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * n);
+  g->fixed.resize((size_t)first + n, 0);
+  g->chain_edge.resize((size_t)first + n, lfx::kPgNone);
+  g->fixed[0] = 1;
+  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * n, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + first, g->fixed.data() + first, n, hipMemcpyHostToDevice, st));
+  g->n_nodes += n;
+  g->topology_stale = true;
+  g->linearised = false;
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int fixed, void * stream)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (node >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "node " + std::to_string(node) + " is not in the graph");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  g->fixed[node] = (node == 0u || fixed) ? 1 : 0;
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, st));
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_graph_edge * edges, uint32_t n, void * stream)
+{
+  if (!c || !g || (n && !edges)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  // every edge is checked, and the chain / loop split of the call worked out, before anything is touched
+  std::vector<uint32_t> loop_of(n, lfx::kPgNone);
+  std::vector<uint8_t> chain_new(n ? g->n_nodes : 0u, 0);  // nodes whose chain edge is one of this call's
+  uint32_t loops = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const lfx_pose_graph_edge & e = edges[k];
+    const std::string which = "edge " + std::to_string(k) + " of the call: ";
+    if (e.i >= g->n_nodes || e.j >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "an end that is not a node of the graph");}
+    if (e.i == e.j) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "i == j");}
+    if (e.flags & ~LFX_EDGE_ROBUST) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "unknown flags");}
+    if (!finite_all(e.z, 12) || !finite_all(e.information, 36)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "a value that is not finite");}
+    double top = 0.0;
+    for (int i = 0; i < 36; i++) {top = std::max(top, std::fabs(e.information[i]));}
+    for (int r = 0; r < 6; r++) {
+      for (int q = 0; q < r; q++) {
+        if (std::fabs(e.information[6 * r + q] - e.information[6 * q + r]) > 1e-9 * top) {
+          return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "the information matrix is not symmetric");
+        }
+      }
+    }
+    const bool chain = e.j == e.i + 1u && g->chain_edge[e.i] == lfx::kPgNone && !chain_new[e.i];
+    if (chain) {chain_new[e.i] = 1;} else {loop_of[k] = g->n_loop + loops++;}
+  }
+  if (n > g->cfg.max_edges - g->n_edges) {
+    return fail(c, LFX_ERR_CAPACITY, "the pose graph holds " + std::to_string(g->n_edges) + " of " + std::to_string(g->cfg.max_edges) +
+             " edges: no room for " + std::to_string(n) + " more");
+  }
+  if (loops > g->cfg.max_loop_edges - g->n_loop) {
+    return fail(c, LFX_ERR_CAPACITY, "the pose graph holds " + std::to_string(g->n_loop) + " of " + std::to_string(g->cfg.max_loop_edges) +
+             " loop edges: no room for " + std::to_string(loops) + " more");
+  }
+  if (n == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  g->stage_edges.resize(n);
+  for (uint32_t k = 0; k < n; k++) {
+    lfx::PgEdge & d = g->stage_edges[k];
+    d.i = edges[k].i; d.j = edges[k].j; d.flags = edges[k].flags; d.loop = loop_of[k];
+    std::memcpy(d.z, edges[k].z, sizeof(d.z));
+    std::memcpy(d.omega, edges[k].information, sizeof(d.omega));
+  }
+  LFX_HIP(c, hipMemcpyAsync(g->edges.p + g->n_edges, g->stage_edges.data(), sizeof(lfx::PgEdge) * n, hipMemcpyHostToDevice, st));
+  for (uint32_t k = 0; k < n; k++) {
+    g->edge_i.push_back(edges[k].i); g->edge_j.push_back(edges[k].j); g->edge_loop.push_back(loop_of[k]);
+    if (loop_of[k] == lfx::kPgNone) {g->chain_edge[edges[k].i] = g->n_edges + k; g->n_chain++;}
+  }
+  g->n_edges += n;
+  g->n_loop += loops;
+  g->topology_stale = true;
+  g->linearised = false;
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_result * result, void * stream)
+{
+  if (!c || !g || !result) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (g->n_edges == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph has no edges");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (g->topology_stale) {
+    const int ru = upload_topology(c, g, st);
+    if (ru != LFX_OK) {return ru;}
+  }
+  int rc = order_behind(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  const lfx::PgArgs a = args_of(g);
+  const size_t pose_bytes = sizeof(double) * 12u * g->n_nodes;
+  LFX_HIP(c, hipMemcpyAsync(g->backup.p, g->poses.p, pose_bytes, hipMemcpyDeviceToDevice, st));
+  LFX_HIP(c, hipMemsetAsync(g->status.p, 0, sizeof(uint32_t), st));
+  rc = launch_linearize(c, a, 0u, false, st);
+  if (rc != LFX_OK) {return rc;}
+  const lfx::PgRecord * rec = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p);
+  uint32_t it = 0;
+  bool converged = false, refused = false;
+  while (it < g->cfg.max_iter) {
+    it++;
+    rc = launch_step(c, a, st);
+    if (rc != LFX_OK) {return rc;}
+    rc = launch_linearize(c, a, it, true, st);
+    if (rc != LFX_OK) {return rc;}
+    // the iteration's only wait: its record (chi^2 at the new poses, the largest step, the status word)
+    LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord) * ((size_t)it + 1u), hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipStreamSynchronize(st));
+    if (rec[it].status != lfx::kPgOk) {refused = true; break;}
+    if (rec[it].max_step < g->cfg.tolerance) {converged = true; break;}
+    if (!(rec[it].max_step == rec[it].max_step)) {break;}          // (not a number: nothing more to learn)
+  }
+  *result = lfx_pose_graph_result{};
+  result->n_chain = g->n_chain;
+  result->n_loop = g->n_loop;
+  result->chi2_initial = rec[0].chi2;
+  const double first = rec[0].chi2, last = rec[it].chi2;
+  const bool diverged = !refused && (!(last == last) || !(rec[it].max_step == rec[it].max_step) || last > first + 1e-12 * std::max(1.0, first));
+  if (refused || diverged) {
+    LFX_HIP(c, hipMemcpyAsync(g->poses.p, g->backup.p, pose_bytes, hipMemcpyDeviceToDevice, st));
+    rc = relinearize(c, g, a, st);
+    if (rc != LFX_OK) {return rc;}
+    LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord), hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipStreamSynchronize(st));
+    result->code = refused ? LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE : LFX_POSE_GRAPH_DIVERGED;
+    result->iterations = refused ? (int32_t)it - 1 : (int32_t)it;
+    result->chi2_final = first;
+    result->max_step = refused ? 0.0 : rec[it].max_step;
+    result->n_robust_downweighted = rec[0].n_down;
+  } else {
+    result->code = converged ? LFX_POSE_GRAPH_CONVERGED : LFX_POSE_GRAPH_MAX_ITERATIONS;
+    result->iterations = (int32_t)it;
+    result->chi2_final = last;
+    result->max_step = rec[it].max_step;
+    result->n_robust_downweighted = rec[it].n_down;
+  }
+  g->linearised = true;
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_poses(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * poses_out, void * stream)
+{
+  if (!c || !g || (count && !poses_out)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
+  if (count == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = order_behind(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemcpyAsync(poses_out, g->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  return LFX_OK;
+}
+
+int lfx_pose_graph_set_poses(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, uint32_t count, const double * poses, void * stream)
+{
+  if (!c || !g || (count && !poses)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
+  if (!finite_all(poses, 12u * (size_t)count)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
+  if (count == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * count);
+  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
+  g->linearised = false;
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_view(lfx_ctx * c, const lfx_pose_graph * g, const double ** d_poses, uint32_t * n_nodes, void * stream)
+{
+  if (!c || !g || !d_poses || !n_nodes) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rc = order_behind(c, g, static_cast<hipStream_t>(stream));
+  if (rc != LFX_OK) {return rc;}
+  *d_poses = g->poses.p;
+  *n_nodes = g->n_nodes;
+  return LFX_OK;
+}
+
+int lfx_pose_graph_edge_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * rho, double * w, void * stream)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (first > g->n_edges || count > g->n_edges - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "edges outside the pose graph");}
+  if (!g->linearised) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the graph has changed since the last lfx_pose_graph_optimize");}
+  if (count == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = settle(c, g);
+  if (rc != LFX_OK) {return rc;}
+  g->stage_lin.resize((size_t)lfx::kPgLin * count);
+  LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->lin.p + (size_t)lfx::kPgLin * first, sizeof(double) * lfx::kPgLin * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (uint32_t e = 0; e < count; e++) {
+    if (w) {w[e] = g->stage_lin[(size_t)lfx::kPgLin * e + 12u];}
+    if (rho) {rho[e] = g->stage_lin[(size_t)lfx::kPgLin * e + 13u];}
+  }
+  return LFX_OK;
+}
+
+#ifdef LFX_TEST_HOOKS
+// Test infrastructure (the test-hooks build only): the graph linearised where it stands -- per edge r [E][6] (may be NULL),
+// per node the gradient [N][6], chi^2 -- and lfx_pose_graph_edge_chi2 opened for those values.
+int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_out, double * grad_out, double * chi2_out, void * stream)
+{
+  if (!c || !g || !grad_out || !chi2_out || g->n_edges == 0u) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (g->topology_stale) {
+    const int ru = upload_topology(c, g, st);
+    if (ru != LFX_OK) {return ru;}
+  }
+  int rc = order_behind(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  const lfx::PgArgs a = args_of(g);
+  rc = relinearize(c, g, a, st);
+  if (rc != LFX_OK) {return rc;}
+  std::vector<double> lin((size_t)lfx::kPgLin * g->n_edges);
+  LFX_HIP(c, hipMemcpyAsync(lin.data(), g->lin.p, sizeof(double) * lin.size(), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipMemcpyAsync(grad_out, g->grad.p, sizeof(double) * 6u * g->n_nodes, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (uint32_t e = 0; r_out && e < g->n_edges; e++) {std::memcpy(r_out + 6u * (size_t)e, lin.data() + (size_t)lfx::kPgLin * e, sizeof(double) * 6u);}
+  *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
+  g->linearised = true;
+  return done(c, g, st);
+}
+#endif
+
+}  // extern "C"

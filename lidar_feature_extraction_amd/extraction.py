@@ -503,6 +503,10 @@ class FeatureExtraction:
             capacity, C.c_void_p(int(stream))), self._L)
         return (edge, surface, offsets, kept) if counts else (edge, surface, offsets)
 
+    def pose_graph(self, max_nodes, max_edges, config=None, **fields):
+        """lfx_pose_graph_create: a pose graph of the given capacities on this context's device."""
+        return PoseGraph(self, max_nodes, max_edges, config, **fields)
+
     def place_db(self, capacity, config=None):
         """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
         return PlaceDb(self, capacity, config)
@@ -1328,6 +1332,136 @@ class PlaceDb:
     def close(self):
         if self.handle:
             self._L.lfx_place_db_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pose_graph_config(config=None, **fields):
+    """lfx_pose_graph_config: the defaults (lfx_pose_graph_default_config) with the given fields replaced.  config: None, a
+    dict of fields, or a B.PoseGraphConfig (copied)."""
+    cfg = B.PoseGraphConfig()
+    if isinstance(config, B.PoseGraphConfig):
+        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        config = None
+    else:
+        B.load().lfx_pose_graph_default_config(C.byref(cfg))
+    for k, v in dict(config or {}, **fields).items():
+        if k not in dict(B.PoseGraphConfig._fields_):
+            raise TypeError("unknown pose-graph setting %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def edge_information(pose_j, report_information):
+    """lfx_pose_graph_edge_information: an alignment report's information ([6][6]; a in the scan's frame, b in the map frame)
+    in a pose-graph edge's residual coordinates, B H B^T with B = blkdiag(I, R_j^T).  Host only."""
+    p = np.ascontiguousarray(pose_j, np.float64).reshape(12)
+    h = np.ascontiguousarray(report_information, np.float64).reshape(36)
+    out = np.zeros(36)
+    rc = B.load().lfx_pose_graph_edge_information(C.c_void_p(p.ctypes.data), C.c_void_p(h.ctypes.data), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "lfx_pose_graph_edge_information")
+    return out.reshape(6, 6)
+
+
+def pose_graph_edges(i, j, z, information, flags=0):
+    """Edges as the records lfx_pose_graph_add_edges takes (B.POSE_GRAPH_EDGE_DTYPE): i, j [n], z [n][3][4] or [n][12],
+    information [n][6][6], flags one value or [n]."""
+    i = np.atleast_1d(np.asarray(i))
+    e = np.zeros(len(i), B.POSE_GRAPH_EDGE_DTYPE)
+    e["i"], e["j"], e["flags"] = i, np.atleast_1d(np.asarray(j)), flags
+    e["z"] = np.asarray(z, np.float64).reshape(len(i), 12)
+    e["information"] = np.asarray(information, np.float64).reshape(len(i), 36)
+    return e
+
+
+class PoseGraph:
+    """lfx_pose_graph: poses (nodes) and relative-pose measurements (edges) on the device, optimised there by Gauss-Newton with
+    the chain-and-loop solver (include/lfx.h, the pose graph section).  Poses are [3][4] = [R | t] float64; node 0 is fixed."""
+
+    def __init__(self, fx, max_nodes, max_edges, config=None, **fields):
+        self._fx = fx
+        self._L = fx._L
+        self.config = pose_graph_config(config, max_nodes=int(max_nodes), max_edges=int(max_edges), **fields)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_pose_graph_create(fx._ctx, C.byref(self.config), C.byref(h)), self._L)
+        self.handle = h
+
+    def _check(self, rc):
+        B.check(self._fx._ctx, rc, self._L)
+
+    def info(self):
+        i = B.PoseGraphInfo()
+        self._check(self._L.lfx_pose_graph_info(self.handle, C.byref(i)))
+        return dict(n_nodes=int(i.n_nodes), n_edges=int(i.n_edges), n_chain=int(i.n_chain), n_loop=int(i.n_loop),
+                    device_bytes=int(i.device_bytes))
+
+    def __len__(self):
+        return self.info()["n_nodes"]
+
+    def add_nodes(self, poses, stream=0):
+        """lfx_pose_graph_add_nodes: poses [n][3][4] appended; the id of the first."""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        first = C.c_uint32(0)
+        self._check(self._L.lfx_pose_graph_add_nodes(self._fx._ctx, self.handle, C.c_void_p(p.ctypes.data if len(p) else None), len(p),
+                                                     C.byref(first), C.c_void_p(int(stream))))
+        return int(first.value)
+
+    def set_fixed(self, node, fixed=True, stream=0):
+        self._check(self._L.lfx_pose_graph_set_fixed(self._fx._ctx, self.handle, int(node), int(bool(fixed)), C.c_void_p(int(stream))))
+
+    def add_edges(self, edges, stream=0):
+        """lfx_pose_graph_add_edges: records of B.POSE_GRAPH_EDGE_DTYPE (pose_graph_edges builds them)."""
+        e = np.ascontiguousarray(edges, B.POSE_GRAPH_EDGE_DTYPE).reshape(-1)
+        self._check(self._L.lfx_pose_graph_add_edges(self._fx._ctx, self.handle, C.c_void_p(e.ctypes.data if len(e) else None), len(e),
+                                                     C.c_void_p(int(stream))))
+
+    def add_edge(self, i, j, z, information, robust=False, stream=0):
+        self.add_edges(pose_graph_edges([i], [j], [z], [information], B.EDGE_ROBUST if robust else 0), stream)
+
+    def optimize(self, stream=0):
+        """lfx_pose_graph_optimize: a dict of the result's fields (code: B.POSE_GRAPH_*).  Synchronous."""
+        r = B.PoseGraphResult()
+        self._check(self._L.lfx_pose_graph_optimize(self._fx._ctx, self.handle, C.byref(r), C.c_void_p(int(stream))))
+        return dict(code=int(r.code), iterations=int(r.iterations), chi2_initial=float(r.chi2_initial), chi2_final=float(r.chi2_final),
+                    max_step=float(r.max_step), n_chain=int(r.n_chain), n_loop=int(r.n_loop),
+                    n_robust_downweighted=int(r.n_robust_downweighted))
+
+    def poses(self, first=0, count=None, stream=0):
+        """lfx_pose_graph_poses: nodes first .. first + count - 1 as [count][3][4] float64 on the host."""
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), 3, 4))
+        self._check(self._L.lfx_pose_graph_poses(self._fx._ctx, self.handle, int(first), count, C.c_void_p(out.ctypes.data if out.size else None),
+                                                 C.c_void_p(int(stream))))
+        return out
+
+    def set_poses(self, poses, first=0, stream=0):
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self._check(self._L.lfx_pose_graph_set_poses(self._fx._ctx, self.handle, int(first), len(p), C.c_void_p(p.ctypes.data if len(p) else None),
+                                                     C.c_void_p(int(stream))))
+
+    def view(self, stream=0):
+        """lfx_pose_graph_view: (device address of [n_nodes][12] float64, n_nodes), current behind `stream`."""
+        ptr, n = C.c_void_p(), C.c_uint32(0)
+        self._check(self._L.lfx_pose_graph_view(self._fx._ctx, self.handle, C.byref(ptr), C.byref(n), C.c_void_p(int(stream))))
+        return int(ptr.value or 0), int(n.value)
+
+    def edge_chi2(self, first=0, count=None, stream=0):
+        """lfx_pose_graph_edge_chi2: (rho [count], w [count]) at the poses the last optimize left."""
+        count = self.info()["n_edges"] - int(first) if count is None else int(count)
+        rho, w = np.zeros(max(count, 0)), np.zeros(max(count, 0))
+        self._check(self._L.lfx_pose_graph_edge_chi2(self._fx._ctx, self.handle, int(first), count, C.c_void_p(rho.ctypes.data if count else None),
+                                                     C.c_void_p(w.ctypes.data if count else None), C.c_void_p(int(stream))))
+        return rho, w
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_pose_graph_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
