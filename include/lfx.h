@@ -1253,6 +1253,113 @@ int lfx_pose_graph_edge_chi2(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t
  * every sum of three terms is (a0 b0 + a1 b1) + a2 b2.  out may be report_information. */
 int lfx_pose_graph_edge_information(const double pose_j[12], const double report_information[36], double out[36]);
 
+/* --- the keyframe store: sensor-frame clouds on the device, world maps written from them at the poses of the moment ------ */
+/* What lets a map follow a pose graph.  lfx_mapper and lfx_odometry keep their clouds already in the world, so a corrected
+ * pose cannot reach them; the store keeps every keyframe's records as the sensor saw them and one pose per keyframe, and a
+ * world cloud is a pure function of the two: each coordinate ((r0*x + r1*y) + r2*z) + t in double, rounded once to float, the
+ * 4th float copied -- lfx_mapper_add's arithmetic, so a build equals, byte for byte, a fresh mapper (thresholds 0) fed the
+ * same clouds and poses.
+ *   RECORDS  per kind (LFX_KEYFRAMES_EDGE, LFX_KEYFRAMES_SURFACE) records of 4 floats in the sensor frame, packed back to back
+ *            in keyframe order; copied in as they are (16 bytes moved, no arithmetic: -0.0 and NaN payloads stay).
+ *   BEGINS   per kind begin[max_keyframes + 1], 64-bit, the exclusive prefix of the counts: keyframe k is records begin[k] ..
+ *            begin[k + 1] - 1.  The host keeps a mirror, so no call waits to learn a size.
+ *   POSES    [max_keyframes][12] doubles, [R | t] row-major: lfx_pose_graph_view's layout.
+ * Keyframe ids are 0, 1, 2 .. in order of addition; a caller that adds graph nodes in step has id == node id.  An empty cloud
+ * is a keyframe with count 0.  lfx_keyframes_create allocates everything on the device (the records at max_points[kind], the
+ * tables, the submap's workspace and a scratch of min(2^20, max(max_points)) records for lfx_keyframes_save); no later call
+ * allocates device memory (pinned host blocks grow with the largest call).
+ * ORDER: every call is ordered behind the store's earlier calls, whichever streams they used (one event, waited for on the
+ * call's stream and recorded behind the call).  The caller keeps alive, until `stream` has passed the call: the device
+ * clouds given to lfx_keyframes_add, the pose array given to lfx_keyframes_follow, and d_out of lfx_keyframes_build (which
+ * returns before the cloud is written).  d_out is device memory or a pinned block (lfx_host_alloc), which the host reads once
+ * `stream` has passed.  Host arrays are copied before a call returns.  Nothing orders a LATER write of the
+ * caller's own to those buffers behind the call: that is the caller's. */
+#define LFX_KEYFRAMES_EDGE 0
+#define LFX_KEYFRAMES_SURFACE 1
+#define LFX_KEYFRAMES_NO_ID 0xFFFFFFFFu
+typedef struct lfx_keyframes lfx_keyframes;
+typedef struct lfx_keyframes_config {
+  uint32_t max_keyframes;    /* 1 .. 2^30 */
+  uint32_t reserved;         /* 0 */
+  uint64_t max_points[2];    /* records per kind, 1 .. 2^40 */
+} lfx_keyframes_config;
+typedef struct lfx_keyframes_info_t {
+  uint32_t n_keyframes, max_keyframes;
+  uint64_t n_points[2], max_points[2];
+  uint64_t device_bytes;     /* everything lfx_keyframes_create allocated on the device */
+} lfx_keyframes_info_t;
+typedef struct lfx_keyframes_store_view {
+  const float *points[2];    /* device: the sensor-frame records of each kind */
+  const uint64_t *begin[2];  /* device: [n_keyframes + 1] */
+  const double *poses;       /* device: [n_keyframes][12] */
+  uint32_t n_keyframes, reserved;
+  uint64_t n_points[2];      /* the host's counts: begin[kind][n_keyframes] */
+} lfx_keyframes_store_view;
+/* n device clouds of one kind, addressed as lfx_mapper_add addresses its clouds: cloud s is d_count[s * count_stride] records
+ * from record d_begin[s] of d_points; total_points the extent of d_points in records.  The last device batch's edge clouds
+ * are {view.edge_points, view.scan_begin, view.scan_info + 2, 4, capacity}; its surface clouds the same with + 3. */
+typedef struct lfx_keyframes_clouds {
+  const float *d_points;
+  const uint32_t *d_begin, *d_count;
+  uint32_t count_stride, reserved;
+  uint64_t total_points;
+} lfx_keyframes_clouds;
+typedef struct lfx_keyframes_submap_result {
+  uint32_t n_selected;            /* keyframes of the window within the radius */
+  uint32_t n_written_keyframes;   /* of those, the ones written: all of them unless truncated */
+  uint64_t n_points;              /* records written to d_out */
+  uint32_t first_id, last_id;     /* the first and the last keyframe written; LFX_KEYFRAMES_NO_ID where none was */
+  int32_t truncated;              /* 1: a selected keyframe did not fit capacity_points; it and every later one is left out */
+  uint32_t reserved;
+} lfx_keyframes_submap_result;
+/* all zero: the caller sets every field */
+void lfx_keyframes_default_config(lfx_keyframes_config *config);
+/* A config outside the ranges above is LFX_ERR_INVALID_ARGUMENT, a failed allocation LFX_ERR_OUT_OF_MEMORY with nothing left
+ * allocated. */
+int lfx_keyframes_create(lfx_ctx *ctx, const lfx_keyframes_config *config, lfx_keyframes **out);
+void lfx_keyframes_destroy(lfx_keyframes *keyframes);
+int lfx_keyframes_info(const lfx_keyframes *keyframes, lfx_keyframes_info_t *info);
+/* The store where it lives.  The addresses are valid until the store is destroyed; the contents are current behind `stream`
+ * once the store's earlier calls have passed (the call queues that wait), as lfx_pose_graph_view's are. */
+int lfx_keyframes_view(lfx_ctx *ctx, const lfx_keyframes *keyframes, lfx_keyframes_store_view *view, void *stream);
+/* n keyframes: keyframe first_id + s is edge cloud s and surface cloud s at poses[s] (host, [n][12], finite); *first_id (may
+ * be NULL) the id of the first.  One wait (both kinds' counts and begins), then one copy launch per kind.  Checked before
+ * anything is changed: NULL pointers, n 0, count_stride 0, a pose that is not finite and a cloud past total_points are
+ * LFX_ERR_INVALID_ARGUMENT; more keyframes than max_keyframes or more records than max_points[kind] LFX_ERR_CAPACITY --
+ * the store is as it was and nothing is left queued. */
+int lfx_keyframes_add(lfx_ctx *ctx, lfx_keyframes *keyframes, const lfx_keyframes_clouds *edge, const lfx_keyframes_clouds *surface,
+                      uint32_t n, const double *poses, uint32_t *first_id, void *stream);
+/* One keyframe from host memory (either cloud may be empty), staged through the store's pinned block and copied from there
+ * straight into place; *id (may be NULL) its id.  No wait unless the store's previous call still reads that block. */
+int lfx_keyframes_add_host(lfx_ctx *ctx, lfx_keyframes *keyframes, const float *edge, uint32_t n_edge, const float *surface,
+                           uint32_t n_surface, const double pose[12], uint32_t *id, void *stream);
+/* Keyframes first .. first + count - 1: their poses overwritten from the host (finite), or copied to the host (synchronous). */
+int lfx_keyframes_set_poses(lfx_ctx *ctx, lfx_keyframes *keyframes, uint32_t first, uint32_t count, const double *poses, void *stream);
+int lfx_keyframes_poses(lfx_ctx *ctx, const lfx_keyframes *keyframes, uint32_t first, uint32_t count, double *poses_out, void *stream);
+/* The call that makes the maps follow the graph: d_poses[k] -> keyframe k for k in [first, first + count), device to device
+ * from a [.][12] double array such as the one lfx_pose_graph_view returns (taken on the same `stream`, it is current).
+ * Asynchronous, no host copy; the poses are not inspected. */
+int lfx_keyframes_follow(lfx_ctx *ctx, lfx_keyframes *keyframes, const double *d_poses, uint32_t first, uint32_t count, void *stream);
+/* The world cloud of keyframes [first, first + count) of `kind` at the store's current poses to d_out, in keyframe order then
+ * record order; *n_out, from the host's mirror, its records.  No wait; asynchronous.  More records than capacity_points is
+ * LFX_ERR_CAPACITY with *n_out = the records needed, nothing queued.  count 0, or keyframes that are all empty: LFX_OK,
+ * *n_out = 0, no launch (d_out may be NULL). */
+int lfx_keyframes_build(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind, uint32_t first, uint32_t count, float *d_out,
+                        uint64_t capacity_points, uint64_t *n_out, void *stream);
+/* The local map around a point, selected on the device (the poses live there): keyframe k of [first, first + count) is
+ * selected iff (dx^2 + dy^2) + dz^2 <= radius^2, the sums in double in that order, d = t_k - center.  The selected keyframes
+ * are written to d_out in ascending id, each whole, as lfx_keyframes_build writes them; writing stops before the first that
+ * would pass capacity_points.  One wait, for *result.  Nothing selected (or only empty keyframes): n_points 0 and no launch.
+ * The window [first, first + count) is how a loop closer leaves the recent keyframes out.  A centre or radius that is not
+ * finite, or a negative radius, is LFX_ERR_INVALID_ARGUMENT. */
+int lfx_keyframes_submap(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind, const double center[3], double radius, uint32_t first,
+                         uint32_t count, float *d_out, uint64_t capacity_points, lfx_keyframes_submap_result *result, void *stream);
+/* dirname/edge.pcd and dirname/surface.pcd of the whole store at the current poses through lfx_pcd_write, named and written
+ * as lfx_odometry_save's; an empty kind writes nothing (written[kind] = 0).  CHUNKED: the world cloud is built into the
+ * store's scratch min(2^20, max(max_points)) records at a time (a chunk may begin and end inside a keyframe) and copied down
+ * chunk by chunk, so a save needs no second copy of the records on the device.  Synchronous. */
+int lfx_keyframes_save(lfx_ctx *ctx, const lfx_keyframes *keyframes, const char *dirname, int written[2], void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lfx.h"
@@ -865,6 +866,116 @@ private:
   }
   const FeatureExtraction & fx_;
   lfx_pose_graph * graph_ = nullptr;
+};
+
+// The keyframe store (lfx_keyframes): every keyframe's edge and surface records in the SENSOR frame and one pose per
+// keyframe on the device of `fx`, which must outlive it; world clouds are written from the two at the poses of the moment,
+// so a map follows a PoseGraph: Follow(graph), then Build, Submap or Save.  Keyframe ids count from 0 in order of addition
+// (add graph nodes in step and id == node id).  Poses are 12 doubles [R | t] row-major; clouds are records of 4 floats.
+class Keyframes
+{
+public:
+  enum Kind {kEdge = LFX_KEYFRAMES_EDGE, kSurface = LFX_KEYFRAMES_SURFACE};
+  Keyframes(const FeatureExtraction & fx, std::uint32_t max_keyframes, std::uint64_t max_edge_points, std::uint64_t max_surface_points)
+  : fx_(fx)
+  {
+    lfx_keyframes_config config;
+    lfx_keyframes_default_config(&config);
+    config.max_keyframes = max_keyframes;
+    config.max_points[0] = max_edge_points;
+    config.max_points[1] = max_surface_points;
+    Check(lfx_keyframes_create(fx.handle(), &config, &store_));
+  }
+  ~Keyframes() {lfx_keyframes_destroy(store_);}
+  Keyframes(const Keyframes &) = delete;
+  Keyframes & operator=(const Keyframes &) = delete;
+
+  // both clouds of every scan the FeatureExtraction was last given (still on the device), one pose (12 doubles) per scan;
+  // the id of the first keyframe added
+  std::uint32_t Add(const std::vector<double> & poses, void * stream = nullptr)
+  {
+    lfx_device_view view{};
+    Check(lfx_device_results(fx_.handle(), &view));
+    if (poses.size() != 12 * static_cast<std::size_t>(view.batch)) {Check(LFX_ERR_INVALID_ARGUMENT);}
+    const lfx_keyframes_clouds edge{view.edge_points, view.scan_begin, view.scan_info + 2, 4, 0, fx_.CloudCapacity()};
+    const lfx_keyframes_clouds surface{view.surface_points, view.scan_begin, view.scan_info + 3, 4, 0, fx_.CloudCapacity()};
+    std::uint32_t first = 0;
+    Check(lfx_keyframes_add(fx_.handle(), store_, &edge, &surface, view.batch, poses.data(), &first, stream));
+    return first;
+  }
+  // one keyframe received from elsewhere (4 floats per point; either cloud may be empty); its id
+  std::uint32_t AddHost(const std::vector<float> & edge, const std::vector<float> & surface, const double pose[12], void * stream = nullptr)
+  {
+    std::uint32_t id = 0;
+    Check(lfx_keyframes_add_host(fx_.handle(), store_, edge.data(), static_cast<std::uint32_t>(edge.size() / 4u), surface.data(),
+      static_cast<std::uint32_t>(surface.size() / 4u), pose, &id, stream));
+    return id;
+  }
+  // every keyframe that is a node of `graph` takes the node's pose, device to device
+  void Follow(const PoseGraph & graph, void * stream = nullptr)
+  {
+    std::uint32_t n = 0;
+    const double * d_poses = graph.View(&n, stream);
+    const std::uint32_t have = Info().n_keyframes;
+    Check(lfx_keyframes_follow(fx_.handle(), store_, d_poses, 0, n < have ? n : have, stream));
+  }
+  void SetPoses(std::uint32_t first, const std::vector<double> & poses, void * stream = nullptr)
+  {
+    Check(poses.size() % 12u == 0u ? lfx_keyframes_set_poses(fx_.handle(), store_, first, static_cast<std::uint32_t>(poses.size() / 12u), poses.data(), stream) :
+      LFX_ERR_INVALID_ARGUMENT);
+  }
+  std::vector<double> Poses(std::uint32_t first, std::uint32_t count, void * stream = nullptr) const
+  {
+    std::vector<double> out(static_cast<std::size_t>(count) * 12u);
+    Check(lfx_keyframes_poses(fx_.handle(), store_, first, count, out.data(), stream));
+    return out;
+  }
+  // the world cloud of keyframes [first, first + count) at the current poses to d_out (device, capacity_points records);
+  // its records.  Returns before the cloud is written: read it behind `stream`.
+  std::uint64_t Build(Kind kind, std::uint32_t first, std::uint32_t count, float * d_out, std::uint64_t capacity_points, void * stream = nullptr) const
+  {
+    std::uint64_t n = 0;
+    Check(lfx_keyframes_build(fx_.handle(), store_, kind, first, count, d_out, capacity_points, &n, stream));
+    return n;
+  }
+  // the records Build would write (from the host's mirror; nothing is queued)
+  std::uint64_t Points(Kind kind, std::uint32_t first, std::uint32_t count) const
+  {
+    std::uint64_t n = 0;
+    const int rc = lfx_keyframes_build(fx_.handle(), store_, kind, first, count, nullptr, 0, &n, nullptr);
+    if (rc != LFX_ERR_CAPACITY) {Check(rc);}
+    return n;
+  }
+  // the keyframes of [first, first + count) within `radius` of `center`, written whole in ascending id to d_out
+  lfx_keyframes_submap_result Submap(Kind kind, const double center[3], double radius, std::uint32_t first, std::uint32_t count, float * d_out,
+    std::uint64_t capacity_points, void * stream = nullptr) const
+  {
+    lfx_keyframes_submap_result r;
+    Check(lfx_keyframes_submap(fx_.handle(), store_, kind, center, radius, first, count, d_out, capacity_points, &r, stream));
+    return r;
+  }
+  // dirname/edge.pcd and dirname/surface.pcd at the current poses; which of the two were written
+  std::pair<bool, bool> Save(const std::string & dirname, void * stream = nullptr) const
+  {
+    int written[2] = {0, 0};
+    Check(lfx_keyframes_save(fx_.handle(), store_, dirname.c_str(), written, stream));
+    return {written[0] != 0, written[1] != 0};
+  }
+  lfx_keyframes_info_t Info() const
+  {
+    lfx_keyframes_info_t i;
+    lfx_keyframes_info(store_, &i);
+    return i;
+  }
+  lfx_keyframes * handle() const {return store_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_keyframes * store_ = nullptr;
 };
 
 }  // namespace lfx

@@ -226,6 +226,36 @@ POSE_GRAPH_EDGE_DTYPE = [("i", "<u4"), ("j", "<u4"), ("flags", "<u4"), ("reserve
 """lfx_pose_graph_edge as a numpy record (400 bytes)."""
 
 
+class KeyframesConfig(C.Structure):
+    """lfx_keyframes_config: the capacities a keyframe store is allocated for ([0] edge, [1] surface records)."""
+    _fields_ = [("max_keyframes", C.c_uint32), ("reserved", C.c_uint32), ("max_points", C.c_uint64 * 2)]
+
+
+class KeyframesInfo(C.Structure):
+    _fields_ = [("n_keyframes", C.c_uint32), ("max_keyframes", C.c_uint32), ("n_points", C.c_uint64 * 2), ("max_points", C.c_uint64 * 2),
+                ("device_bytes", C.c_uint64)]
+
+
+class KeyframesStoreView(C.Structure):
+    _fields_ = [("points", C.c_void_p * 2), ("begin", C.c_void_p * 2), ("poses", C.c_void_p), ("n_keyframes", C.c_uint32),
+                ("reserved", C.c_uint32), ("n_points", C.c_uint64 * 2)]
+
+
+class KeyframesClouds(C.Structure):
+    """lfx_keyframes_clouds: n device clouds of one kind, addressed as lfx_mapper_add addresses its clouds."""
+    _fields_ = [("d_points", C.c_void_p), ("d_begin", C.c_void_p), ("d_count", C.c_void_p), ("count_stride", C.c_uint32),
+                ("reserved", C.c_uint32), ("total_points", C.c_uint64)]
+
+
+class KeyframesSubmapResult(C.Structure):
+    _fields_ = [("n_selected", C.c_uint32), ("n_written_keyframes", C.c_uint32), ("n_points", C.c_uint64), ("first_id", C.c_uint32),
+                ("last_id", C.c_uint32), ("truncated", C.c_int32), ("reserved", C.c_uint32)]
+
+
+KEYFRAMES_EDGE, KEYFRAMES_SURFACE = 0, 1
+KEYFRAMES_NO_ID = 0xFFFFFFFF
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -262,6 +292,9 @@ EXPORTS = [
     "lfx_pose_graph_default_config", "lfx_pose_graph_create", "lfx_pose_graph_destroy", "lfx_pose_graph_info", "lfx_pose_graph_add_nodes",
     "lfx_pose_graph_set_fixed", "lfx_pose_graph_add_edges", "lfx_pose_graph_optimize", "lfx_pose_graph_poses", "lfx_pose_graph_set_poses",
     "lfx_pose_graph_view", "lfx_pose_graph_edge_chi2", "lfx_pose_graph_edge_information",
+    "lfx_keyframes_default_config", "lfx_keyframes_create", "lfx_keyframes_destroy", "lfx_keyframes_info", "lfx_keyframes_view",
+    "lfx_keyframes_add", "lfx_keyframes_add_host", "lfx_keyframes_set_poses", "lfx_keyframes_poses", "lfx_keyframes_follow",
+    "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -448,6 +481,22 @@ def load(test_hooks=False):
     L.lfx_pose_graph_view.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(u32), vp]
     L.lfx_pose_graph_edge_chi2.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.lfx_pose_graph_edge_information.argtypes = [vp, vp, vp]
+    pkf, pkc = C.POINTER(KeyframesConfig), C.POINTER(KeyframesClouds)
+    L.lfx_keyframes_default_config.argtypes = [pkf]
+    L.lfx_keyframes_default_config.restype = None
+    L.lfx_keyframes_create.argtypes = [vp, pkf, C.POINTER(vp)]
+    L.lfx_keyframes_destroy.argtypes = [vp]
+    L.lfx_keyframes_destroy.restype = None
+    L.lfx_keyframes_info.argtypes = [vp, C.POINTER(KeyframesInfo)]
+    L.lfx_keyframes_view.argtypes = [vp, vp, C.POINTER(KeyframesStoreView), vp]
+    L.lfx_keyframes_add.argtypes = [vp, vp, pkc, pkc, u32, vp, C.POINTER(u32), vp]
+    L.lfx_keyframes_add_host.argtypes = [vp, vp, vp, u32, vp, u32, vp, C.POINTER(u32), vp]
+    L.lfx_keyframes_set_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_keyframes_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_keyframes_follow.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.lfx_keyframes_build.argtypes = [vp, vp, i32, u32, u32, vp, u64, p64, vp]
+    L.lfx_keyframes_submap.argtypes = [vp, vp, i32, vp, C.c_double, u32, u32, vp, u64, C.POINTER(KeyframesSubmapResult), vp]
+    L.lfx_keyframes_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
     L.lfx_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.lfx_kernel_name.argtypes = [i32]
     L.lfx_kernel_name.restype = C.c_char_p

@@ -1,0 +1,219 @@
+// lfx_kernels_keyframes.hpp -- the device side of the keyframe store (lfx_keyframes.hip): sensor-frame records copied in as
+// they are, world clouds written from them at the store's current poses, and the selection of a submap around a point.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "lfx_kernels_transform.hpp"
+
+namespace lfx
+{
+
+constexpr int kKfThreads = 256;
+constexpr int kKfPerLane = 4;                                    // whole 16-byte records per lane
+constexpr uint32_t kKfRun = kKfThreads * kKfPerLane;             // source records per workgroup of the transform: 1024
+constexpr uint32_t kKfWave = 64;
+constexpr uint64_t kKfNone = ~0ull;                              // out_begin of a keyframe that is not written
+constexpr uint32_t kKfNoId = 0xFFFFFFFFu;
+
+// One cloud of an add: `count` records from record `src` of the caller's points to record `dst` of the store; its
+// workgroups are [first_block, first_block + ceil(count / kKfThreads)).  MapAppendEntry without the pose: 32 bytes.
+struct KfCopyEntry
+{
+  uint64_t dst;
+  uint32_t src, count, first_block, pad[3];
+};
+static_assert(sizeof(KfCopyEntry) == 32, "KfCopyEntry is 32 bytes");
+
+// The clouds of one add into the store, bit for bit (-0.0, NaN payloads and all: 16 bytes moved as integers, no
+// arithmetic).  Workgroups map to (cloud, chunk) as map_append_kernel's do.
+__global__ __launch_bounds__(kKfThreads) void keyframes_copy_kernel(
+  const KfCopyEntry * __restrict__ table, uint32_t n_entries, const uint4 * __restrict__ src, uint4 * __restrict__ dst)
+{
+  const uint32_t b = blockIdx.x;
+  uint32_t lo = 0u, hi = n_entries;         // table[lo].first_block <= b < table[hi].first_block
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (table[mid].first_block <= b) {lo = mid;} else {hi = mid;}
+  }
+  const KfCopyEntry * e = table + lo;
+  const uint32_t i = (b - e->first_block) * kKfThreads + threadIdx.x;
+  if (i < e->count) {
+    dst[e->dst + i] = src[(size_t)e->src + i];
+  }
+}
+
+// What a transform launch works on: the source records [rec_lo, rec_hi) of one kind, which lie in the keyframes
+// [k_lo, k_hi): begin[k_lo] <= rec_lo and rec_hi <= begin[k_hi].
+struct KfRange
+{
+  uint64_t rec_lo, rec_hi;
+  uint32_t k_lo, k_hi, first, pad;          // first: out_begin is indexed k - first (selected form)
+};
+
+// World records from sensor-frame records at the store's poses.  Workgroup b has the kKfRun consecutive source records
+// from rec_lo + b kKfRun; lane t of it the records t, t + 256, t + 512, t + 768 of the run, each one 16-byte load and one
+// 16-byte store.  The keyframe of the run's first record comes from a binary search over `begin`, uniform over the
+// workgroup; each wave then walks forward to the keyframe of the first of the 64 records it has in a step (past empty
+// keyframes: a while) and keeps that keyframe's pose until it has walked on.  Where a step's 64 records lie in more
+// than one keyframe every lane searches for its own.  Plain form: record i goes to dst[i - rec_lo].  Selected form:
+// record i of keyframe k goes to dst[out_begin[k - first] + (i - begin[k])], nowhere if that is kKfNone, and a run
+// without a written keyframe returns before it loads a record.  No LDS, no atomics.  (Every array is its own
+// parameter, const and restrict: what lets the uniform loads of `begin` and `poses` go through the scalar cache.)
+template<bool kSelected>
+__global__ __launch_bounds__(kKfThreads) void keyframes_transform_kernel(
+  const float4 * __restrict__ src, const uint64_t * __restrict__ begin, const double * __restrict__ poses,
+  const uint64_t * __restrict__ out_begin, float4 * __restrict__ dst, const KfRange a)
+{
+  const uint64_t run = a.rec_lo + (uint64_t)blockIdx.x * kKfRun;
+  const uint64_t run_end = run + kKfRun < a.rec_hi ? run + kKfRun : a.rec_hi;
+  uint32_t lo = a.k_lo, hi = a.k_hi;        // begin[lo] <= run < begin[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (begin[mid] <= run) {lo = mid;} else {hi = mid;}
+  }
+  uint32_t k = lo;                          // (the last keyframe that begins at or before `run`: it is not empty)
+  if (kSelected) {
+    bool any = false;
+    for (uint32_t q = k; q < a.k_hi && begin[q] < run_end; q++) {
+      any = any || out_begin[q - a.first] != kKfNone;
+    }
+    if (!any) {return;}
+  }
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & (kKfWave - 1u);
+  float4 p[kKfPerLane];
+#pragma unroll
+  for (int j = 0; j < kKfPerLane; j++) {
+    const uint64_t i = run + (uint32_t)(j * kKfThreads) + threadIdx.x;
+    p[j] = i < run_end ? src[i] : float4{0.f, 0.f, 0.f, 0.f};
+  }
+  uint32_t loaded = kKfNoId;
+  double m[12] = {};
+#pragma unroll
+  for (int j = 0; j < kKfPerLane; j++) {
+    const uint64_t iw = run + (uint32_t)(j * kKfThreads) + wave * kKfWave;   // the step's first record: uniform over the wave
+    if (iw >= run_end) {break;}
+    while (begin[k + 1u] <= iw) {k++;}     // (iw < rec_hi <= begin[k_hi]: k stays below k_hi)
+    const uint64_t step_end = iw + kKfWave < run_end ? iw + kKfWave : run_end;
+    const uint64_t i = iw + lane;
+    if (begin[k + 1u] >= step_end) {
+      // one keyframe for the whole step: its pose through the scalar path, reloaded only when the wave has walked on
+      if (k != loaded) {
+#pragma unroll
+        for (int q = 0; q < 12; q++) {m[q] = poses[12u * (size_t)k + q];}
+        loaded = k;
+      }
+      uint64_t o = i - a.rec_lo;
+      if (kSelected) {
+        const uint64_t ob = out_begin[k - a.first];
+        if (ob == kKfNone) {continue;}
+        o = ob + (i - begin[k]);
+      }
+      if (i < step_end) {dst[o] = pcl_transform_record(m, p[j]);}
+    } else if (i < step_end) {
+      // a boundary inside the step: the last keyframe that begins at or before this lane's record
+      uint32_t l = k, h = a.k_hi;
+      while (h - l > 1u) {
+        const uint32_t mid = l + ((h - l) >> 1);
+        if (begin[mid] <= i) {l = mid;} else {h = mid;}
+      }
+      uint64_t o = i - a.rec_lo;
+      if (kSelected) {
+        const uint64_t ob = out_begin[l - a.first];
+        if (ob == kKfNone) {continue;}
+        o = ob + (i - begin[l]);
+      }
+      dst[o] = pcl_transform_record(poses + 12u * (size_t)l, p[j]);
+    }
+  }
+}
+
+// flag[k] = keyframe first + k lies within `radius` of the centre: (dx^2 + dy^2) + dz^2 <= r2 in double, in that order
+// (the units are compiled with -ffp-contract=off), d = t - centre.  One thread per keyframe of the window.
+__global__ __launch_bounds__(kKfThreads) void keyframes_flag_kernel(
+  const double * __restrict__ poses, uint32_t first, uint32_t count, double cx, double cy, double cz, double r2,
+  uint8_t * __restrict__ flag)
+{
+  const uint32_t k = blockIdx.x * kKfThreads + threadIdx.x;
+  if (k >= count) {return;}
+  const double * t = poses + 12u * (size_t)(first + k);
+  const double dx = t[3] - cx, dy = t[7] - cy, dz = t[11] - cz;
+  flag[k] = ((dx * dx + dy * dy) + dz * dz <= r2) ? 1 : 0;
+}
+
+struct KfPlanRecord                         // lfx_keyframes_submap_result, as the plan writes it
+{
+  uint32_t n_selected, n_written;
+  uint64_t n_points;
+  uint32_t first_id, last_id;
+  int32_t truncated;
+  uint32_t pad;
+};
+static_assert(sizeof(KfPlanRecord) == 32, "the plan's record is the header's result");
+
+// One workgroup.  e[k] = the exclusive sum of flag x count over the window; keyframe k is written iff it is flagged and
+// e[k] + count[k] <= capacity (the sum only grows: nothing behind the first keyframe that does not fit is written);
+// out_begin[k] = e[k] for a written keyframe, kKfNone otherwise.  Integer sums: the same store gives the same bytes.
+// Every thread has a contiguous share of the window, sums it, the shares' sums are scanned in LDS, and a second pass
+// over the share writes out_begin.
+__global__ __launch_bounds__(kKfThreads) void keyframes_plan_kernel(
+  const uint8_t * __restrict__ flag, const uint64_t * __restrict__ begin, uint32_t first, uint32_t count, uint64_t capacity,
+  uint64_t * __restrict__ out_begin, KfPlanRecord * __restrict__ record)
+{
+  __shared__ uint64_t s_sum[kKfThreads], s_points[kKfThreads];
+  __shared__ uint32_t s_selected[kKfThreads], s_written[kKfThreads], s_first[kKfThreads], s_last[kKfThreads];
+  const uint32_t t = threadIdx.x;
+  const uint32_t share = (count + kKfThreads - 1u) / kKfThreads;
+  const uint32_t lo = t * share < count ? t * share : count, hi = lo + share < count ? lo + share : count;
+  uint64_t sum = 0;
+  for (uint32_t k = lo; k < hi; k++) {
+    if (flag[k]) {sum += begin[first + k + 1u] - begin[first + k];}
+  }
+  s_sum[t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1u; d < kKfThreads; d <<= 1) {     // inclusive scan of the shares' sums
+    const uint64_t v = t >= d ? s_sum[t - d] : 0u;
+    __syncthreads();
+    s_sum[t] += v;
+    __syncthreads();
+  }
+  uint64_t e = s_sum[t] - sum, points = 0;
+  uint32_t selected = 0, written = 0, first_id = kKfNoId, last_id = kKfNoId;
+  for (uint32_t k = lo; k < hi; k++) {
+    uint64_t ob = kKfNone;
+    if (flag[k]) {
+      const uint64_t c = begin[first + k + 1u] - begin[first + k];
+      selected++;
+      if (e + c <= capacity) {
+        ob = e;
+        written++;
+        points = e + c;
+        if (first_id == kKfNoId) {first_id = first + k;}
+        last_id = first + k;
+      }
+      e += c;
+    }
+    out_begin[k] = ob;
+  }
+  s_points[t] = points; s_selected[t] = selected; s_written[t] = written; s_first[t] = first_id; s_last[t] = last_id;
+  __syncthreads();
+  if (t == 0u) {
+    KfPlanRecord r{};
+    r.first_id = kKfNoId; r.last_id = kKfNoId;
+    for (uint32_t q = 0; q < kKfThreads; q++) {       // ascending shares: ascending ids
+      r.n_selected += s_selected[q];
+      r.n_written += s_written[q];
+      if (s_written[q]) {
+        r.n_points = s_points[q];
+        if (r.first_id == kKfNoId) {r.first_id = s_first[q];}
+        r.last_id = s_last[q];
+      }
+    }
+    r.truncated = r.n_written < r.n_selected ? 1 : 0;
+    *record = r;
+  }
+}
+
+}  // namespace lfx

@@ -1,0 +1,523 @@
+// lfx_keyframes.hip -- the keyframe store (include/lfx.h, the keyframe store section; lfx_kernels_keyframes.hpp): every
+// keyframe's edge and surface records kept on the device in the SENSOR frame, one pose per keyframe beside them, and world
+// clouds written from the two at the poses of the moment -- so that a map follows a pose graph's corrections.  The host
+// mirrors the begin tables (the exclusive prefix of the counts): what a call needs to size a launch or refuse a request it
+// knows without a wait.  Everything on the device is allocated by lfx_keyframes_create.
+#include "lfx_internal.hpp"
+#include "lfx_kernels_keyframes.hpp"
+
+#include <algorithm>
+#include <cstdint>
+
+using namespace lfx_host;
+
+static_assert(sizeof(lfx::KfPlanRecord) == sizeof(lfx_keyframes_submap_result), "the plan writes the caller's record");
+static_assert(lfx::kKfNoId == LFX_KEYFRAMES_NO_ID, "the kernels' missing id is the header's");
+
+struct lfx_keyframes
+{
+  int device = 0;
+  lfx_keyframes_config cfg{};
+  uint32_t n = 0;                        // keyframes
+  std::vector<uint64_t> begin[2];        // the host's mirror of the begin tables: [n + 1]
+  uint64_t device_bytes = 0;
+  uint64_t chunk = 0;                    // records of `scratch`
+  DevBuf<float4> records[2];
+  DevBuf<uint64_t> d_begin[2];
+  DevBuf<double> poses;
+  DevBuf<lfx::KfCopyEntry> table[2];     // an add's clouds, uploaded from the pinned block
+  DevBuf<uint8_t> flag;                  // the submap's selection, its plan and its record
+  DevBuf<uint64_t> out_begin;
+  DevBuf<lfx::KfPlanRecord> record;
+  DevBuf<float4> scratch;                // lfx_keyframes_save: one chunk of a world cloud
+  PinnedBuf readback;                    // the counts and begins an add reads back; the submap's record
+  PinnedBuf upload;                      // what goes up (tables, begins, poses, a host keyframe's records): rewritten only
+                                         // once the store's last queued call has passed
+  mutable hipEvent_t tail = nullptr;     // recorded behind the last call that touched the store, on its stream
+  mutable bool pending = false;
+};
+
+namespace
+{
+constexpr uint32_t kInitialClouds = 64;
+constexpr uint64_t kSaveChunk = (uint64_t)1 << 20;
+
+size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
+
+bool finite_all(const double * v, size_t n)
+{
+  for (size_t i = 0; i < n; i++) {
+    if (!std::isfinite(v[i])) {return false;}
+  }
+  return true;
+}
+
+int check_store(lfx_ctx * c, const lfx_keyframes * s)
+{
+  if (s->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the keyframe store lives on another device");}
+  return LFX_OK;
+}
+
+// `st` behind the store's last call; after the call's own work: done()
+int order_behind(lfx_ctx * c, const lfx_keyframes * s, hipStream_t st)
+{
+  if (s->pending) {LFX_HIP(c, hipStreamWaitEvent(st, s->tail, 0));}
+  return LFX_OK;
+}
+int done(lfx_ctx * c, const lfx_keyframes * s, hipStream_t st)
+{
+  LFX_HIP(c, hipEventRecord(s->tail, st));
+  s->pending = true;
+  return LFX_OK;
+}
+// the pinned upload block may be rewritten
+int settle(lfx_ctx * c, const lfx_keyframes * s)
+{
+  if (s->pending) {LFX_HIP(c, hipEventSynchronize(s->tail)); s->pending = false;}
+  return LFX_OK;
+}
+
+int check_range(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, uint32_t count)
+{
+  if (first > s->n || count > s->n - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "keyframes outside the store");}
+  return LFX_OK;
+}
+
+int check_kind(lfx_ctx * c, int kind)
+{
+  if (kind != LFX_KEYFRAMES_EDGE && kind != LFX_KEYFRAMES_SURFACE) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "kind must be LFX_KEYFRAMES_EDGE or LFX_KEYFRAMES_SURFACE");}
+  return LFX_OK;
+}
+
+// the world records of source records [lo, hi), which lie in keyframes [k_lo, k_hi), to d_out (plain form) or to where
+// out_begin says (selected form, indexed from `first`)
+int launch_transform(lfx_ctx * c, const lfx_keyframes * s, int kind, uint64_t lo, uint64_t hi, uint32_t k_lo, uint32_t k_hi, bool selected,
+  uint32_t first, float * d_out, hipStream_t st)
+{
+  const uint64_t blocks = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
+  if (blocks > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "too many records for one launch");}
+  lfx::KfRange a{};
+  a.rec_lo = lo; a.rec_hi = hi; a.k_lo = k_lo; a.k_hi = k_hi; a.first = first;
+  if (selected) {
+    hipLaunchKernelGGL(lfx::keyframes_transform_kernel<true>, dim3((uint32_t)blocks), dim3(lfx::kKfThreads), 0, st, s->records[kind].p,
+      s->d_begin[kind].p, s->poses.p, s->out_begin.p, reinterpret_cast<float4 *>(d_out), a);
+  } else {
+    hipLaunchKernelGGL(lfx::keyframes_transform_kernel<false>, dim3((uint32_t)blocks), dim3(lfx::kKfThreads), 0, st, s->records[kind].p,
+      s->d_begin[kind].p, s->poses.p, s->out_begin.p, reinterpret_cast<float4 *>(d_out), a);
+  }
+  LFX_HIP(c, hipGetLastError());
+  return LFX_OK;
+}
+
+// n keyframes whose records lie on the device (src[kind], addressed by begin / count) and whose poses lie in the pinned
+// block at `pose_at`: tables, begins and poses go up, one copy launch per kind; then the mirror is extended.  The caller has
+// checked the capacities and settled the store.
+struct KindPlan
+{
+  const uint4 * src = nullptr;
+  const uint32_t * begin = nullptr, * count = nullptr;   // host, [n]
+};
+
+int append(lfx_ctx * c, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, size_t pose_at, size_t table_at, hipStream_t st)
+{
+  uint8_t * up = s->upload.p;
+  size_t at = table_at;
+  const int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {
+    lfx::KfCopyEntry * tab = reinterpret_cast<lfx::KfCopyEntry *>(up + at);
+    at += round64(sizeof(lfx::KfCopyEntry) * n);
+    uint64_t * nb = reinterpret_cast<uint64_t *>(up + at);
+    at += round64(sizeof(uint64_t) * n);
+    uint64_t dst = s->begin[kind][s->n];
+    uint32_t entries = 0, blocks = 0;
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t cnt = plan[kind].count[k];
+      if (cnt) {
+        lfx::KfCopyEntry e{};
+        e.dst = dst; e.src = plan[kind].begin[k]; e.count = cnt; e.first_block = blocks;
+        tab[entries++] = e;
+        blocks += (cnt + lfx::kKfThreads - 1u) / lfx::kKfThreads;
+      }
+      dst += cnt;
+      nb[k] = dst;
+    }
+    LFX_HIP(c, hipMemcpyAsync(s->d_begin[kind].p + s->n + 1u, nb, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+    if (entries) {
+      LFX_HIP(c, hipMemcpyAsync(s->table[kind].p, tab, sizeof(lfx::KfCopyEntry) * entries, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(lfx::keyframes_copy_kernel, dim3(blocks), dim3(lfx::kKfThreads), 0, st, s->table[kind].p, entries, plan[kind].src,
+        reinterpret_cast<uint4 *>(s->records[kind].p));
+      LFX_HIP(c, hipGetLastError());
+    }
+  }
+  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)s->n, up + pose_at, sizeof(double) * 12u * n, hipMemcpyHostToDevice, st));
+  // the call stands: commit
+  for (int kind = 0; kind < 2; kind++) {
+    uint64_t dst = s->begin[kind][s->n];
+    for (uint32_t k = 0; k < n; k++) {dst += plan[kind].count[k]; s->begin[kind].push_back(dst);}
+  }
+  s->n += n;
+  return done(c, s, st);
+}
+
+// what an add of n keyframes needs of the pinned upload block: [poses][per kind: table, begins]
+size_t upload_bytes(uint32_t n) {return round64(sizeof(double) * 12u * n) + 2u * (round64(sizeof(lfx::KfCopyEntry) * n) + round64(sizeof(uint64_t) * n));}
+
+// the keyframes and records an add would bring fit
+int check_room(lfx_ctx * c, const lfx_keyframes * s, uint32_t n, const uint64_t add[2])
+{
+  if (n > s->cfg.max_keyframes - s->n) {
+    return fail(c, LFX_ERR_CAPACITY, "the store holds " + std::to_string(s->n) + " of " + std::to_string(s->cfg.max_keyframes) +
+             " keyframes: no room for " + std::to_string(n) + " more");
+  }
+  for (int kind = 0; kind < 2; kind++) {
+    if (add[kind] > s->cfg.max_points[kind] - s->begin[kind][s->n]) {
+      return fail(c, LFX_ERR_CAPACITY, std::string("the store holds ") + std::to_string(s->begin[kind][s->n]) + " of " +
+               std::to_string(s->cfg.max_points[kind]) + (kind ? " surface" : " edge") + " records: no room for " + std::to_string(add[kind]) + " more");
+    }
+  }
+  return LFX_OK;
+}
+
+int save_kind(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::string & path, hipStream_t st)
+{
+  const uint64_t total = s->begin[kind][s->n];
+  std::vector<float> host(4u * (size_t)total);
+  for (uint64_t lo = 0; lo < total; lo += s->chunk) {
+    const uint64_t hi = std::min(total, lo + s->chunk);
+    // (the scratch is reused: the copy down and the next chunk's kernel follow each other on the stream)
+    const int rc = launch_transform(c, s, kind, lo, hi, 0u, s->n, false, 0u, reinterpret_cast<float *>(s->scratch.p), st);
+    if (rc != LFX_OK) {return rc;}
+    LFX_HIP(c, hipMemcpyAsync(host.data() + 4u * (size_t)lo, s->scratch.p, sizeof(float4) * (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
+  }
+  LFX_HIP(c, hipStreamSynchronize(st));
+  char msg[512];
+  const int rc = lfx_pcd_write(path.c_str(), host.data(), total, msg, sizeof(msg));
+  if (rc != LFX_OK) {return fail(c, rc, msg);}
+  return LFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void lfx_keyframes_default_config(lfx_keyframes_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_keyframes_config{};
+}
+
+int lfx_keyframes_create(lfx_ctx * c, const lfx_keyframes_config * config, lfx_keyframes ** out)
+{
+  if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!config || !out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "config and out are required");}
+  if (config->max_keyframes < 1u || config->max_keyframes > (1u << 30)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_keyframes must be in 1 .. 2^30");}
+  for (int kind = 0; kind < 2; kind++) {
+    if (config->max_points[kind] < 1u || config->max_points[kind] > ((uint64_t)1 << 40)) {
+      return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_points must be in 1 .. 2^40 for both kinds");
+    }
+  }
+  LFX_HIP(c, hipSetDevice(c->device));
+  lfx_keyframes * s = new (std::nothrow) lfx_keyframes();
+  if (!s) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store");}
+  s->device = c->device;
+  s->cfg = *config;
+  const size_t K = config->max_keyframes;
+  s->chunk = std::min<uint64_t>(kSaveChunk, std::max(config->max_points[0], config->max_points[1]));
+  auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_keyframes_destroy(s); return fail(c, code, why);};
+  uint64_t bytes = 0;
+  bool ok = true;
+  auto get = [&](auto & buf, size_t count) {
+      ok = ok && buf.alloc(count) == hipSuccess;
+      bytes += (uint64_t)count * sizeof(*buf.p);
+    };
+  for (int kind = 0; kind < 2; kind++) {get(s->records[kind], config->max_points[kind]); get(s->d_begin[kind], K + 1u); get(s->table[kind], K);}
+  get(s->poses, 12u * K); get(s->flag, K); get(s->out_begin, K); get(s->record, 1u); get(s->scratch, s->chunk);
+  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's " + std::to_string(bytes) + " bytes");}
+  s->device_bytes = bytes;
+  for (int kind = 0; kind < 2; kind++) {
+    // begin[0] = 0; every entry behind the last keyframe's reads as "no record lies here" (all ones) until an add writes it
+    if (hipMemset(s->d_begin[kind].p, 0xFF, sizeof(uint64_t) * (K + 1u)) != hipSuccess || hipMemset(s->d_begin[kind].p, 0, sizeof(uint64_t)) != hipSuccess) {
+      return give_up(LFX_ERR_HIP, "cannot clear the begin tables");
+    }
+    s->begin[kind].reserve(K + 1u);
+    s->begin[kind].push_back(0u);
+  }
+  if (s->readback.reserve(2u * sizeof(uint32_t) * (5u * kInitialClouds) + sizeof(lfx::KfPlanRecord)) != hipSuccess ||
+    s->upload.reserve(upload_bytes(kInitialClouds)) != hipSuccess)
+  {
+    return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's pinned blocks");
+  }
+  if (hipEventCreateWithFlags(&s->tail, hipEventDisableTiming) != hipSuccess) {
+    s->tail = nullptr;
+    return give_up(LFX_ERR_HIP, "cannot create the keyframe store's event");
+  }
+  *out = s;
+  return LFX_OK;
+}
+
+void lfx_keyframes_destroy(lfx_keyframes * s)
+{
+  if (!s) {return;}
+  (void)hipSetDevice(s->device);
+  if (s->tail) {(void)hipEventSynchronize(s->tail); (void)hipEventDestroy(s->tail);}
+  delete s;
+}
+
+int lfx_keyframes_info(const lfx_keyframes * s, lfx_keyframes_info_t * info)
+{
+  if (!s || !info) {return LFX_ERR_INVALID_ARGUMENT;}
+  *info = lfx_keyframes_info_t{};
+  info->n_keyframes = s->n;
+  info->max_keyframes = s->cfg.max_keyframes;
+  for (int kind = 0; kind < 2; kind++) {info->n_points[kind] = s->begin[kind][s->n]; info->max_points[kind] = s->cfg.max_points[kind];}
+  info->device_bytes = s->device_bytes;
+  return LFX_OK;
+}
+
+int lfx_keyframes_view(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes_store_view * view, void * stream)
+{
+  if (!c || !s || !view) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rc = order_behind(c, s, static_cast<hipStream_t>(stream));
+  if (rc != LFX_OK) {return rc;}
+  *view = lfx_keyframes_store_view{};
+  for (int kind = 0; kind < 2; kind++) {
+    view->points[kind] = reinterpret_cast<const float *>(s->records[kind].p);
+    view->begin[kind] = s->d_begin[kind].p;
+    view->n_points[kind] = s->begin[kind][s->n];
+  }
+  view->poses = s->poses.p;
+  view->n_keyframes = s->n;
+  return LFX_OK;
+}
+
+int lfx_keyframes_add(lfx_ctx * c, lfx_keyframes * s, const lfx_keyframes_clouds * edge, const lfx_keyframes_clouds * surface, uint32_t n,
+  const double * poses, uint32_t * first_id, void * stream)
+{
+  if (!c || !s || !edge || !surface || !poses) {return LFX_ERR_INVALID_ARGUMENT;}
+  const lfx_keyframes_clouds * in[2] = {edge, surface};
+  for (int kind = 0; kind < 2; kind++) {
+    if (!in[kind]->d_points || !in[kind]->d_begin || !in[kind]->d_count) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_points, d_begin and d_count are required");}
+    if (in[kind]->count_stride == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "count_stride must be >= 1");}
+  }
+  if (n == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n must be >= 1");}
+  if (!finite_all(poses, 12u * (size_t)n)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t none[2] = {0u, 0u};
+  int rc = check_room(c, s, n, none);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // both kinds' counts (strided spans, read whole) and begins back in one wait: the call's only one
+  size_t span[2], need = 0;
+  for (int kind = 0; kind < 2; kind++) {span[kind] = (size_t)(n - 1u) * in[kind]->count_stride + 1u; need += sizeof(uint32_t) * (span[kind] + n);}
+  LFX_HIP(c, s->readback.reserve(need));
+  uint32_t * h_count[2], * h_begin[2];
+  uint32_t * at = reinterpret_cast<uint32_t *>(s->readback.p);
+  for (int kind = 0; kind < 2; kind++) {
+    h_count[kind] = at; at += span[kind];
+    h_begin[kind] = at; at += n;
+    LFX_HIP(c, hipMemcpyAsync(h_count[kind], in[kind]->d_count, sizeof(uint32_t) * span[kind], hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipMemcpyAsync(h_begin[kind], in[kind]->d_begin, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+  }
+  LFX_HIP(c, hipStreamSynchronize(st));
+  std::vector<uint32_t> count[2];
+  uint64_t add[2] = {0u, 0u}, blocks[2] = {0u, 0u};
+  for (int kind = 0; kind < 2; kind++) {
+    count[kind].resize(n);
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t cnt = h_count[kind][(size_t)k * in[kind]->count_stride];
+      if ((uint64_t)h_begin[kind][k] + cnt > in[kind]->total_points) {
+        return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(kind ? "surface" : "edge") + " cloud " + std::to_string(k) + " (records " +
+                 std::to_string(h_begin[kind][k]) + " + " + std::to_string(cnt) + ") runs past total_points (" + std::to_string(in[kind]->total_points) + ")");
+      }
+      count[kind][k] = cnt;
+      add[kind] += cnt;
+      blocks[kind] += (cnt + lfx::kKfThreads - 1u) / lfx::kKfThreads;
+    }
+    if (blocks[kind] > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "the call adds too many records for one launch");}
+  }
+  rc = check_room(c, s, n, add);
+  if (rc != LFX_OK) {return rc;}
+  rc = settle(c, s);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, s->upload.reserve(upload_bytes(n)));
+  std::memcpy(s->upload.p, poses, sizeof(double) * 12u * n);
+  KindPlan plan[2];
+  for (int kind = 0; kind < 2; kind++) {
+    plan[kind].src = reinterpret_cast<const uint4 *>(in[kind]->d_points);
+    plan[kind].begin = h_begin[kind];
+    plan[kind].count = count[kind].data();
+  }
+  const uint32_t first = s->n;
+  rc = append(c, s, plan, n, 0u, round64(sizeof(double) * 12u * n), st);
+  if (rc == LFX_OK && first_id) {*first_id = first;}
+  return rc;
+}
+
+int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, uint32_t n_edge, const float * surface, uint32_t n_surface,
+  const double pose[12], uint32_t * id, void * stream)
+{
+  if (!c || !s || !pose || (n_edge && !edge) || (n_surface && !surface)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!finite_all(pose, 12u)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t add[2] = {n_edge, n_surface};
+  int rc = check_room(c, s, 1u, add);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = settle(c, s);
+  if (rc != LFX_OK) {return rc;}
+  // the pinned block: [pose][the two new begins][edge records][surface records]; copied up from there, straight into place
+  const size_t head = 128u, e_bytes = sizeof(float4) * (size_t)n_edge, s_bytes = sizeof(float4) * (size_t)n_surface;
+  LFX_HIP(c, s->upload.reserve(head + e_bytes + s_bytes));
+  uint8_t * up = s->upload.p;
+  std::memcpy(up, pose, sizeof(double) * 12u);
+  uint64_t * nb = reinterpret_cast<uint64_t *>(up + 96u);
+  const float * src[2] = {edge, surface};
+  const size_t bytes[2] = {e_bytes, s_bytes}, where[2] = {head, head + e_bytes};
+  rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {
+    const uint64_t at = s->begin[kind][s->n];
+    nb[kind] = at + add[kind];
+    if (bytes[kind]) {
+      std::memcpy(up + where[kind], src[kind], bytes[kind]);
+      LFX_HIP(c, hipMemcpyAsync(s->records[kind].p + at, up + where[kind], bytes[kind], hipMemcpyHostToDevice, st));
+    }
+    LFX_HIP(c, hipMemcpyAsync(s->d_begin[kind].p + s->n + 1u, nb + kind, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  }
+  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)s->n, up, sizeof(double) * 12u, hipMemcpyHostToDevice, st));
+  for (int kind = 0; kind < 2; kind++) {s->begin[kind].push_back(nb[kind]);}
+  if (id) {*id = s->n;}
+  s->n += 1u;
+  return done(c, s, st);
+}
+
+int lfx_keyframes_set_poses(lfx_ctx * c, lfx_keyframes * s, uint32_t first, uint32_t count, const double * poses, void * stream)
+{
+  if (!c || !s || (count && !poses)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!finite_all(poses, 12u * (size_t)count)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
+  if (count == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, s);
+  if (rs != LFX_OK) {return rs;}
+  LFX_HIP(c, s->upload.reserve(sizeof(double) * 12u * count));
+  std::memcpy(s->upload.p, poses, sizeof(double) * 12u * count);
+  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, s->upload.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
+  return done(c, s, st);
+}
+
+int lfx_keyframes_poses(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, uint32_t count, double * poses_out, void * stream)
+{
+  if (!c || !s || (count && !poses_out)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (count == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemcpyAsync(poses_out, s->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  return LFX_OK;
+}
+
+int lfx_keyframes_follow(lfx_ctx * c, lfx_keyframes * s, const double * d_poses, uint32_t first, uint32_t count, void * stream)
+{
+  if (!c || !s || (count && !d_poses)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (count == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, st));
+  return done(c, s, st);
+}
+
+int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t first, uint32_t count, float * d_out, uint64_t capacity_points,
+  uint64_t * n_out, void * stream)
+{
+  if (!c || !s || !n_out) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
+  if (hi - lo > capacity_points) {
+    *n_out = hi - lo;
+    return fail(c, LFX_ERR_CAPACITY, "the keyframes hold " + std::to_string(hi - lo) + " records: more than capacity_points (" + std::to_string(capacity_points) + ")");
+  }
+  *n_out = hi - lo;
+  if (hi == lo) {return LFX_OK;}
+  if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  rc = launch_transform(c, s, kind, lo, hi, first, first + count, false, first, d_out, st);
+  if (rc != LFX_OK) {return rc;}
+  return done(c, s, st);
+}
+
+int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const double center[3], double radius, uint32_t first, uint32_t count,
+  float * d_out, uint64_t capacity_points, lfx_keyframes_submap_result * result, void * stream)
+{
+  if (!c || !s || !center || !result) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!finite_all(center, 3u) || !std::isfinite(radius) || radius < 0.0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the centre must be finite, the radius finite and >= 0");}
+  *result = lfx_keyframes_submap_result{};
+  result->first_id = result->last_id = LFX_KEYFRAMES_NO_ID;
+  if (count == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  hipLaunchKernelGGL(lfx::keyframes_flag_kernel, dim3((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), dim3(lfx::kKfThreads), 0, st, s->poses.p, first,
+    count, center[0], center[1], center[2], radius * radius, s->flag.p);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::keyframes_plan_kernel, dim3(1), dim3(lfx::kKfThreads), 0, st, s->flag.p, s->d_begin[kind].p, first, count, capacity_points,
+    s->out_begin.p, s->record.p);
+  LFX_HIP(c, hipGetLastError());
+  // the call's only wait: the plan's record (the caller needs n_points to hand the cloud on; the launch below its range)
+  lfx::KfPlanRecord * rec = reinterpret_cast<lfx::KfPlanRecord *>(s->readback.p);
+  LFX_HIP(c, hipMemcpyAsync(rec, s->record.p, sizeof(lfx::KfPlanRecord), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  std::memcpy(result, rec, sizeof(*result));
+  result->reserved = 0u;
+  if (result->n_points > 0u) {
+    if (!d_out) {(void)done(c, s, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    const uint32_t k_lo = result->first_id, k_hi = result->last_id + 1u;
+    rc = launch_transform(c, s, kind, s->begin[kind][k_lo], s->begin[kind][k_hi], k_lo, k_hi, true, first, d_out, st);
+    if (rc != LFX_OK) {return rc;}
+  }
+  return done(c, s, st);
+}
+
+int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirname, int written[2], void * stream)
+{
+  if (!c || !s || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  written[0] = written[1] = 0;
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const std::string dir(dirname);
+  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
+  int rc = order_behind(c, s, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {
+    if (s->begin[kind][s->n] == 0u) {continue;}
+    rc = save_kind(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), st);
+    if (rc != LFX_OK) {return rc;}
+    written[kind] = 1;
+  }
+  return LFX_OK;
+}
+
+}  // extern "C"

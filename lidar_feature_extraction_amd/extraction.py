@@ -507,6 +507,11 @@ class FeatureExtraction:
         """lfx_pose_graph_create: a pose graph of the given capacities on this context's device."""
         return PoseGraph(self, max_nodes, max_edges, config, **fields)
 
+    def keyframes(self, max_keyframes, max_points):
+        """lfx_keyframes_create: a keyframe store of the given capacities (max_points: one value for both kinds or
+        (edge, surface) records) on this context's device."""
+        return Keyframes(self, max_keyframes, max_points)
+
     def place_db(self, capacity, config=None):
         """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
         return PlaceDb(self, capacity, config)
@@ -1462,6 +1467,180 @@ class PoseGraph:
     def close(self):
         if self.handle:
             self._L.lfx_pose_graph_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Keyframes:
+    """lfx_keyframes: every keyframe's edge and surface records on the device in the SENSOR frame with one pose per keyframe,
+    and world clouds written from the two at the poses of the moment (include/lfx.h, the keyframe store section) -- what makes
+    a map follow a pose graph.  kind: 'edge' / 'surface' (or B.KEYFRAMES_EDGE / _SURFACE).  Poses are [3][4] = [R | t] float64;
+    keyframe ids count from 0 in order of addition."""
+
+    KINDS = {"edge": B.KEYFRAMES_EDGE, "surface": B.KEYFRAMES_SURFACE, B.KEYFRAMES_EDGE: B.KEYFRAMES_EDGE, B.KEYFRAMES_SURFACE: B.KEYFRAMES_SURFACE}
+
+    def __init__(self, fx, max_keyframes, max_points):
+        self._fx = fx
+        self._L = fx._L
+        cfg = B.KeyframesConfig()
+        self._L.lfx_keyframes_default_config(C.byref(cfg))
+        cfg.max_keyframes = int(max_keyframes)
+        mp = (max_points, max_points) if np.isscalar(max_points) else tuple(max_points)
+        cfg.max_points[0], cfg.max_points[1] = int(mp[0]), int(mp[1])
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_keyframes_create(fx._ctx, C.byref(cfg), C.byref(h)), self._L)
+        self.handle = h
+        self.config = cfg
+
+    def _check(self, rc):
+        B.check(self._fx._ctx, rc, self._L)
+
+    @classmethod
+    def _kind(cls, kind):
+        if kind not in cls.KINDS:
+            raise ValueError("kind must be 'edge' or 'surface'")
+        return cls.KINDS[kind]
+
+    def info(self):
+        i = B.KeyframesInfo()
+        self._check(self._L.lfx_keyframes_info(self.handle, C.byref(i)))
+        return dict(n_keyframes=int(i.n_keyframes), max_keyframes=int(i.max_keyframes), n_points=(int(i.n_points[0]), int(i.n_points[1])),
+                    max_points=(int(i.max_points[0]), int(i.max_points[1])), device_bytes=int(i.device_bytes))
+
+    def __len__(self):
+        return self.info()["n_keyframes"]
+
+    def view(self, stream=0):
+        """lfx_keyframes_view: the device addresses of the records and begin tables ([0] edge, [1] surface) and of the poses,
+        current behind `stream`, and the host's counts."""
+        v = B.KeyframesStoreView()
+        self._check(self._L.lfx_keyframes_view(self._fx._ctx, self.handle, C.byref(v), C.c_void_p(int(stream))))
+        return dict(points=(v.points[0] or 0, v.points[1] or 0), begin=(v.begin[0] or 0, v.begin[1] or 0), poses=v.poses or 0,
+                    n_keyframes=int(v.n_keyframes), n_points=(int(v.n_points[0]), int(v.n_points[1])))
+
+    @staticmethod
+    def clouds(d_points, d_begin, d_count, count_stride, total_points):
+        """lfx_keyframes_clouds: device clouds addressed as Mapper.add addresses them."""
+        return B.KeyframesClouds(C.c_void_p(int(d_points)), C.c_void_p(int(d_begin)), C.c_void_p(int(d_count)), int(count_stride), 0, int(total_points))
+
+    def add(self, edge, surface, poses, stream=0):
+        """lfx_keyframes_add: edge and surface are Keyframes.clouds(...) of n clouds each, poses [n][3][4]; the id of the first
+        keyframe added."""
+        pm = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        first = C.c_uint32(0)
+        self._check(self._L.lfx_keyframes_add(self._fx._ctx, self.handle, C.byref(edge), C.byref(surface), len(pm),
+                                              C.c_void_p(pm.ctypes.data if len(pm) else None), C.byref(first), C.c_void_p(int(stream))))
+        return int(first.value)
+
+    def add_batch(self, poses, stream=0):
+        """Both clouds of every scan of the last device batch, one pose per scan (as Mapper.add_batch takes one kind)."""
+        v = self._fx.device_view()
+        cap = self._fx.max_points_per_scan * self._fx.max_batch
+        info = int(v.scan_info)
+        pm = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        if len(pm) != v.batch:
+            raise ValueError("expected %d poses of 3 x 4" % v.batch)
+        return self.add(self.clouds(v.edge_points, v.scan_begin, info + 8, 4, cap), self.clouds(v.surface_points, v.scan_begin, info + 12, 4, cap),
+                        pm, stream)
+
+    def add_host(self, edge_points, surface_points, pose, stream=0):
+        """lfx_keyframes_add_host: one keyframe from host clouds ([n, 4] float32 each, either may be empty); its id."""
+        e = np.ascontiguousarray(edge_points, np.float32).reshape(-1, 4)
+        s = np.ascontiguousarray(surface_points, np.float32).reshape(-1, 4)
+        pm = np.ascontiguousarray(pose, np.float64).reshape(12)
+        kid = C.c_uint32(0)
+        self._check(self._L.lfx_keyframes_add_host(
+            self._fx._ctx, self.handle, C.c_void_p(e.ctypes.data if len(e) else None), len(e), C.c_void_p(s.ctypes.data if len(s) else None), len(s),
+            C.c_void_p(pm.ctypes.data), C.byref(kid), C.c_void_p(int(stream))))
+        return int(kid.value)
+
+    def set_poses(self, poses, first=0, stream=0):
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self._check(self._L.lfx_keyframes_set_poses(self._fx._ctx, self.handle, int(first), len(p), C.c_void_p(p.ctypes.data if len(p) else None),
+                                                    C.c_void_p(int(stream))))
+
+    def poses(self, first=0, count=None, stream=0):
+        """lfx_keyframes_poses: keyframes first .. first + count - 1 as [count][3][4] float64 on the host."""
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), 3, 4))
+        self._check(self._L.lfx_keyframes_poses(self._fx._ctx, self.handle, int(first), count, C.c_void_p(out.ctypes.data if out.size else None),
+                                                C.c_void_p(int(stream))))
+        return out
+
+    def follow(self, graph_or_pointer, first=0, count=None, stream=0):
+        """lfx_keyframes_follow: the poses of keyframes [first, first + count) taken, device to device, from a PoseGraph (its
+        view on `stream`) or from the device address of a [.][12] float64 array."""
+        if isinstance(graph_or_pointer, PoseGraph):
+            ptr, n = graph_or_pointer.view(stream)
+            count = min(n, len(self)) - int(first) if count is None else int(count)
+        else:
+            ptr = int(graph_or_pointer)
+            count = len(self) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_keyframes_follow(self._fx._ctx, self.handle, C.c_void_p(ptr), int(first), count, C.c_void_p(int(stream))))
+
+    def build(self, kind, first=0, count=None, d_out=None, capacity_points=None, stream=0):
+        """lfx_keyframes_build: the world cloud of keyframes [first, first + count) at the current poses.  Without d_out: a new
+        torch tensor [n, 4] float32 on the device, written behind `stream`.  With d_out (a device address of capacity_points
+        records): the number of records."""
+        import torch
+        kind = self._kind(kind)
+        count = len(self) - int(first) if count is None else int(count)
+        n = C.c_uint64(0)
+        if d_out is not None:
+            self._check(self._L.lfx_keyframes_build(self._fx._ctx, self.handle, kind, int(first), count, C.c_void_p(int(d_out) or None),
+                                                    int(capacity_points), C.byref(n), C.c_void_p(int(stream))))
+            return int(n.value)
+        need = self._range_points(kind, first, count)
+        out = torch.empty((need, 4), dtype=torch.float32, device=torch.device("cuda", self._fx.device))
+        self._check(self._L.lfx_keyframes_build(self._fx._ctx, self.handle, kind, int(first), count, C.c_void_p(out.data_ptr() if need else None),
+                                                need, C.byref(n), C.c_void_p(int(stream))))
+        return out
+
+    def submap(self, kind, center, radius, first=0, count=None, d_out=None, capacity_points=None, stream=0):
+        """lfx_keyframes_submap: the keyframes of [first, first + count) within `radius` of `center`, written whole in
+        ascending id until capacity_points.  Returns (cloud, result): result the dict of lfx_keyframes_submap_result; cloud a
+        torch tensor [n_points, 4] (a view of a new tensor of capacity_points records, default the whole window's) or,
+        with d_out, None."""
+        import torch
+        kind = self._kind(kind)
+        count = len(self) - int(first) if count is None else int(count)
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        out = None
+        if d_out is None:
+            capacity_points = self._range_points(kind, first, count) if capacity_points is None else int(capacity_points)
+            out = torch.empty((capacity_points, 4), dtype=torch.float32, device=torch.device("cuda", self._fx.device))
+            d_out = out.data_ptr() if capacity_points else 0
+        r = B.KeyframesSubmapResult()
+        self._check(self._L.lfx_keyframes_submap(self._fx._ctx, self.handle, kind, C.c_void_p(c.ctypes.data), float(radius), int(first), count,
+                                                 C.c_void_p(int(d_out) or None), int(capacity_points), C.byref(r), C.c_void_p(int(stream))))
+        res = dict(n_selected=int(r.n_selected), n_written_keyframes=int(r.n_written_keyframes), n_points=int(r.n_points),
+                   first_id=None if r.first_id == B.KEYFRAMES_NO_ID else int(r.first_id),
+                   last_id=None if r.last_id == B.KEYFRAMES_NO_ID else int(r.last_id), truncated=bool(r.truncated))
+        return (None if out is None else out[:res["n_points"]]), res
+
+    def _range_points(self, kind, first, count):
+        """the records of keyframes [first, first + count) of `kind`, from the host's mirror: a build without room, which
+        queues nothing and reports the records needed"""
+        n = C.c_uint64(0)
+        rc = self._L.lfx_keyframes_build(self._fx._ctx, self.handle, kind, int(first), int(count), None, 0, C.byref(n), None)
+        if rc != B.ERR_CAPACITY:
+            self._check(rc)
+        return int(n.value)
+
+    def save(self, dirname, stream=0):
+        """lfx_keyframes_save: dirname/edge.pcd and dirname/surface.pcd at the current poses; (edge written, surface written)."""
+        w = (C.c_int32 * 2)(0, 0)
+        self._check(self._L.lfx_keyframes_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
+        return bool(w[0]), bool(w[1])
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_keyframes_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
