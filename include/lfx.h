@@ -1159,7 +1159,8 @@ int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t e
  * r = (phi, t_E):
  *   R_E = R_Z^T R_i^T R_j,  d = R_i^T (t_j - t_i),  t_E = R_Z^T (d - t_Z),  phi = Log(R_E)
  *   Log: v = (R21 - R12, R02 - R20, R10 - R01) / 2, theta = atan2(|v|, (trace - 1) / 2), phi = v theta / |v|, and phi = v
- *   where |v| < 1e-10.  Valid for theta < 3 rad.
+ *   where |v| < 1e-10.  Valid for theta < 3 rad; phi's rounding error grows as 1 / sin theta beyond a right angle (against a
+ *   50-digit reference, in spacings of the largest term summed on the way to r: 0.8 up to 2.5 rad, 3 at 2.9, 1.8 at 2.99).
  * Its Jacobians dr / d delta_i and dr / d delta_j, with Jri = J_r^-1(phi) = I + [phi]x / 2 + c [phi]x^2,
  * c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), c = 1 / 12 + theta^2 / 720 for theta < 1e-4:
  *   A_j = [[Jri, 0], [0, R_Z^T R_i^T]]      A_i = [[-Jri R_j^T R_i, 0], [R_Z^T [d]x, -R_Z^T R_i^T]]
@@ -1171,7 +1172,8 @@ int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t e
  * exceeds the initial one (by more than its rounding, 1e-12 max(1, chi^2): a consistent graph starts and ends at 1e-30),
  * or is not a number, the initial poses are restored: LFX_POSE_GRAPH_DIVERGED.  Rotations stay
  * orthonormal, |R^T R - I| <= 1e-12 after any number of iterations: every step re-orthonormalises the rotation it moved,
- * R <- R (3 I - R^T R) / 2 (one step of the polar iteration; no quaternion is kept).
+ * R <- R (3 I - R^T R) / 2 (one step of the polar iteration; no quaternion is kept).  A node whose increment is exactly 0
+ * (no edge touches it) is not moved: its pose stays as it is, byte for byte.
  * THE SOLVER: the chain is the first edge with j == i + 1 for each i; every other edge is a loop edge --
  * backward edges, duplicates and edges between distant nodes among them.  P = lambda I + the chain edges' blocks is block-
  * tridiagonal in node order (a fixed node has the identity and no coupling); with J the loop edges' rows H = P + J^T W J, and

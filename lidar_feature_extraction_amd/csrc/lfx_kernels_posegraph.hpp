@@ -590,6 +590,9 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_step_kernel(PgArgs a)
   }
   if (a.fixed[k]) {a.step_max[k] = 0.0; return;}
   a.step_max[k] = top;
+  // a step of exactly zero (a node no edge touches) moves nothing: the polar step below would still round the rotation
+  // again, and the pose would not come back as it went in
+  if (top == 0.0) {return;}
   double * p = a.poses + 12 * (size_t)k;
   const double th2 = pg_dot3(d[0], d[0], d[1], d[1], d[2], d[2]), th = sqrt(th2);
   // Exp(a) = I + A [a]x + B [a]x^2

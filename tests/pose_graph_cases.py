@@ -1,7 +1,10 @@
-"""The graphs of the pose-graph tests (tests/test_pose_graph_expect.py on the host, tests/test_pose_graph_gpu.py and
-tests/test_pose_graph_cpp_gpu.py on the device): generators, the list of one-step shapes, and the measured floor between the
-two ways to one step."""
+"""The graphs of the pose-graph tests (tests/test_pose_graph_expect.py on the host, tests/test_pose_graph_gpu.py,
+tests/test_pose_graph_streams_gpu.py and tests/test_pose_graph_cpp_gpu.py on the device): generators, the list of one-step
+shapes and the measured floor between the two ways to one step, the extra shapes with a config of their own, the stages of
+the graph that grows, and the 50-digit reference of the residual (tests/golden/pose_graph_residual_reference.json)."""
 import functools
+import json
+import os
 
 import numpy as np
 
@@ -107,6 +110,150 @@ def step_shapes():
     return out
 
 
+def remeasure(g, e, flags=0, shift=(0.0, 0.0, 0.0), from_start=False):
+    """Edge e of the graph g given `flags` and its measured translation moved by `shift` (metres, in the frame of node i).
+    from_start: the measurement is first replaced by the one the START poses agree with, so that the edge's residual at the
+    start is the shift alone: s = sqrt(r^T Omega r) is then chosen, not met."""
+    ed = g["edges"][e]
+    Z = between(g["poses"][int(ed["i"])], g["poses"][int(ed["j"])]) if from_start else np.reshape(ed["z"], (3, 4)).copy()
+    Z[:, 3] += np.asarray(shift, np.float64)
+    g["edges"][e]["z"] = Z.reshape(12)
+    g["edges"][e]["flags"] = flags
+
+
+def robust_chain_graph(name, fixed=(), huber_delta=3.0):
+    """24 nodes, a whole chain (edge k is k -> k + 1), loops (2, 15) = edge 23 and (20, 6) = edge 24.  Robust and 1 m, 0.7 m
+    and 1 m off: the adjacent chain edges 7 and 8 and loop edge 23 (sigma_t = 0.01 m: s of 70 .. 100).  Robust and measured
+    from the start: chain edge 12, 1 mm off (s about 0.1: w = 1 under every huber_delta used), and chain edge 16, 15 mm off
+    (s about 1.5: w = 1 under huber_delta = 3, below 1 under 0.5)."""
+    g = graph(24, loops=[(2, 15), (20, 6)], seed=50, fixed=fixed, start=(0.004, 0.01))
+    remeasure(g, 7, R.ROBUST, (1.0, 0.0, 0.0))
+    remeasure(g, 8, R.ROBUST, (0.0, 0.7, 0.0))
+    remeasure(g, 23, R.ROBUST, (0.0, 0.0, 1.0))
+    remeasure(g, 12, R.ROBUST, (0.001, 0.0, 0.0), from_start=True)
+    remeasure(g, 16, R.ROBUST, (0.015, 0.0, 0.0), from_start=True)
+    g.update(name=name, huber_delta=huber_delta)
+    return g
+
+
+ROBUST_OUTLIERS, ROBUST_INLIER, ROBUST_BETWEEN = (7, 8, 23), 12, 16       # edges of robust_chain_graph()
+DAMPINGS = (("damping_0", 0.0), ("damping_1e-2", 1e-2), ("damping_10", 10.0))
+
+
+def damping_graph():
+    """24 nodes, a whole chain, two loops, a start half a metre off: the one graph the dampings are run at"""
+    return graph(24, loops=[(2, 15), (20, 6)], seed=51, start=(0.1, 0.5))
+
+
+@functools.lru_cache(maxsize=None)
+def extra_step_shapes():
+    """More one-step shapes, each with its own config (huber_delta, damping) and fixed nodes: down-weighted CHAIN edges, a
+    second huber_delta, three dampings, a last node without an edge.  A list of its own: floor() takes its maximum over
+    step_shapes() and the circles, and these are held to that floor, which they must not move
+    (tests/test_pose_graph_expect.py asserts that each shape's own difference lies below it)."""
+    out = [robust_chain_graph("robust_chain_pair"), robust_chain_graph("robust_chain_beside_fixed", fixed=(9,)),
+           robust_chain_graph("huber_half", huber_delta=0.5)]
+    for name, damping in DAMPINGS:
+        out.append(dict(damping_graph(), name=name, damping=damping))
+    # the chain edge 18 -> 19 is missing and no loop touches node 19: P's last block is lambda I, the gradient there is 0
+    out.append(dict(graph(20, loops=[(3, 14), (16, 5)], missing=(18,), seed=52), name="dangling_last_node"))
+    for g in out:
+        g.setdefault("huber_delta", 3.0)
+        g.setdefault("damping", 1e-6)
+    return out
+
+
+def config_of(g):
+    """the solver's config of a shape (the defaults where it has none of its own)"""
+    return dict(damping=g.get("damping", 1e-6), huber_delta=g.get("huber_delta", 3.0))
+
+
+@functools.lru_cache(maxsize=None)
+def extra_first_steps():
+    """name -> (delta of the first dense step, its linearisation), each extra shape under its own config"""
+    return {g["name"]: R.dense_step(g["poses"], g["edges"], g["fixed"], **config_of(g)) for g in extra_step_shapes()}
+
+
+@functools.lru_cache(maxsize=None)
+def extra_differences():
+    """name -> the shape's own woodbury_step - dense_step, under its own config"""
+    seen = {}
+    for g in extra_step_shapes():
+        dense, lin = extra_first_steps()[g["name"]]
+        seen[g["name"]] = float(np.abs(R.woodbury_step(g["poses"], g["edges"], g["fixed"], lin=lin, **config_of(g)) - dense).max())
+    return seen
+
+
+def all_step_shapes():
+    return {g["name"]: g for g in step_shapes() + list(extra_step_shapes())}
+
+
+@functools.lru_cache(maxsize=None)
+def one_iteration(name):
+    """The restatement's (poses, result, (rho, w)) after ONE iteration of the shape `name` (old or extra) under its config:
+    what the device's code and n_robust_downweighted of a max_iter = 1 run are held to."""
+    g = all_step_shapes()[name]
+    return R.optimize(g["poses"], g["edges"], g["fixed"], max_iter=1, **config_of(g))
+
+
+def robust_s(edges, rho, w, huber_delta):
+    """s = sqrt(r^T Omega r) of the robust edges, from what lfx_pose_graph_edge_chi2 reports: sqrt(rho) where w = 1,
+    huber_delta / w beyond"""
+    rho, w = np.asarray(rho), np.asarray(w)
+    s = np.where(w < 1.0, huber_delta / np.where(w < 1.0, w, 1.0), np.sqrt(np.maximum(rho, 0.0)))
+    return s[(edges["flags"] & R.ROBUST) != 0]
+
+
+def growth_graph():
+    """The 48-node graph of the growth test (tests/test_pose_graph_gpu.py grows it in four stages): every chain edge, three
+    loops of which (25, 4) runs backward into the first part, and a second edge on (40, 41), robust and 0.5 m off.
+    (poses, {name: edge records})"""
+    g = graph(48, loops=[(2, 13), (18, 30), (25, 4), (35, 10)], duplicate=[(40, 41)], seed=53)
+    e = g["edges"]
+    remeasure(g, 51, R.ROBUST, (0.5, 0.0, 0.0))
+    return g["poses"], dict(chain=e[:47], loop_a=e[47:48], loop_b=e[48:50], loop_c=e[50:51], second_40_41=e[51:52])
+
+
+def growth_stages():
+    """The growth test's four stages as (nodes in the graph, the add_edges calls of the stage, fixed nodes at its optimise).
+    Stage 3: the robust second edge on (40, 41) and the loop (35, 10) arrive in a call of their own BEFORE the chain edges,
+    so by the header's rule that edge on (40, 41) is the chain edge and the plain one, later, a loop edge; 35 -> 36 arrives
+    behind a loop edge on node 35; the edge into node 47 is left out until stage 4."""
+    _, e = growth_graph()
+    chain = e["chain"]
+    return [(16, [np.concatenate([chain[:15], e["loop_a"]])], ()),
+            (32, [np.concatenate([chain[15:31], e["loop_b"]])], ()),
+            (48, [np.concatenate([e["second_40_41"], e["loop_c"]]), chain[31:46]], (20,)),
+            (48, [chain[46:47]], ())]
+
+
+REFERENCE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_graph_residual_reference.json")
+
+
+@functools.lru_cache(maxsize=None)
+def residual_reference():
+    """tests/golden/pose_graph_residual_reference.json (tools/pose_graph_reference.py wrote it, 50 digits, rounded once):
+    a list of (angle as text, Ti, Tj, Z [3][4], r [6])"""
+    with open(REFERENCE_PATH) as f:
+        doc = json.load(f)
+
+    def arr(c, k, shape):
+        return np.array([float.fromhex(v) for v in c[k]]).reshape(shape)
+
+    return [(c["angle"], arr(c, "Ti", (3, 4)), arr(c, "Tj", (3, 4)), arr(c, "Z", (3, 4)), arr(c, "r", 6)) for c in doc["cases"]]
+
+
+def residual_reference_graph():
+    """The reference's cases as one graph: case c is the edge 2 c -> 2 c + 1 between its own two poses, the doubles of the
+    file, with a full information matrix; every second edge robust."""
+    rng = np.random.default_rng(78)
+    poses, rows = [], []
+    for c, (_angle, Ti, Tj, Z, _r) in enumerate(residual_reference()):
+        poses += [Ti, Tj]
+        rows.append((2 * c, 2 * c + 1, Z, information(rng, 0.05, 0.1), R.ROBUST if c % 2 else 0))
+    return dict(poses=np.array(poses), edges=edges_of(rows), fixed=(), name="residual_reference")
+
+
 def circle(N, L, seed, radius=20.0, noise=(0.002, 0.01), laps=2, false_loop=None, robust=False):
     """Two laps of a circle: chained noisy odometry edges, the start their composition from the true first pose, and L loop
     edges from a node of the first lap to the node at the same place in the second.  false_loop: that loop edge measures a
@@ -157,10 +304,16 @@ def circle_results():
 
 
 @functools.lru_cache(maxsize=None)
+def false_loop_runs():
+    """the restatement's (poses, result, (rho, w)) for false_loop_cases(), by name"""
+    return {name: R.optimize(g["poses"], g["edges"], max_iter=20, huber_delta=3.0)
+            for name, g in zip(("robust", "plain", "clean"), false_loop_cases())}
+
+
+@functools.lru_cache(maxsize=None)
 def false_loop_results():
     """the restatement's worst position error for false_loop_cases(), by name"""
-    return {name: worst_error(R.optimize(g["poses"], g["edges"], max_iter=20, huber_delta=3.0)[0], g["truth"])
-            for name, g in zip(("robust", "plain", "clean"), false_loop_cases())}
+    return {name: worst_error(false_loop_runs()[name][0], g["truth"]) for name, g in zip(("robust", "plain", "clean"), false_loop_cases())}
 
 
 @functools.lru_cache(maxsize=None)

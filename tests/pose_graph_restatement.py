@@ -166,11 +166,11 @@ def exp_rotation(a):
 
 
 def retract(poses, delta, fixed=()):
-    """R <- R Exp(a), t <- t + b, then R <- R (3 I - R^T R) / 2; fixed nodes stay."""
+    """R <- R Exp(a), t <- t + b, then R <- R (3 I - R^T R) / 2; fixed nodes stay, and so does a node whose step is 0."""
     poses = np.array(poses, np.float64).reshape(-1, 3, 4)
     fixed = set(int(k) for k in fixed) | {0}
     for k in range(len(poses)):
-        if k in fixed:
+        if k in fixed or not np.any(delta[k]):
             continue
         R = poses[k, :, :3] @ exp_rotation(delta[k, :3])
         poses[k, :, :3] = R @ (1.5 * np.eye(3) - 0.5 * (R.T @ R))

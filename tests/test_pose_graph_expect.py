@@ -10,6 +10,7 @@ there P is held by lambda = 1e-6 alone along six directions, so P^-1 carries 1e6
 (tests/pose_graph_cases.py floors()), both no larger than the one figure over all shapes."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -140,6 +141,168 @@ def test_the_solvers_statement_against_the_dense_step():
     g = [s for s in K.step_shapes() if s["name"] == "two_edges_on_one_pair"][0]
     chain, loops = R.split_edges(g["edges"], 16)
     assert (chain >= 0).sum() == 15 and len(loops) == 4 and chain[3] == 3 and loops[0] == 15
+
+
+def _tolerance(name, want):
+    """what the device's one-step test allows a shape: 16 x the floor of its class, or 1e-12 of the step"""
+    return max(16.0 * K.floor_of(name), 1e-12 * float(np.abs(want).max()))
+
+
+def test_the_extra_shapes_lie_below_the_floor_they_are_held_to():
+    """Each extra shape's own woodbury - dense difference, under its own config, is no larger than the floor of the class it
+    is held to on the device (all of them the whole-chain class: K.floor_of knows no other name of theirs), so the
+    restatement alone cannot eat the margin.  The last node of dangling_last_node has no edge: P's last block is lambda I,
+    well conditioned, and the shape is in the whole-chain class BECAUSE its difference says so (the missing edge 31 -> 32
+    of the gap class splits a chain that loops then hold together through lambda alone).
+    Measured here: 5.1e-15, 3.6e-15 and 1.8e-14 at the robust shapes, 3.4e-14, 1.1e-13 and 5.9e-14 at damping 0, 1e-2
+    and 10, 2.2e-15 at the dangling node; the floors are 1.3e-10 and 1.7e-7 as before."""
+    whole, gap = K.floors()
+    print("floors: whole chains %.2e; the missing chain edge %.2e" % (whole, gap))
+    assert whole < 1e-9 and gap < 1e-5                                # (as test_the_solvers_statement_against_the_dense_step holds them)
+    assert not set(K.extra_differences()) & set(g["name"] for g in K.step_shapes() + K.circles())
+    for g in K.extra_step_shapes():
+        diff, want = K.extra_differences()[g["name"]], K.extra_first_steps()[g["name"]][0]
+        _, res, _ = K.one_iteration(g["name"])
+        print("%-28s woodbury - dense %.2e, max |delta| %.5f, damping %g, huber_delta %g; one iteration: code %d, %d down-weighted" % (
+            g["name"], diff, np.abs(want).max(), g["damping"], g["huber_delta"], res["code"], res["n_robust_downweighted"]))
+        assert K.floor_of(g["name"]) == whole and diff <= whole
+        assert res["code"] == R.MAX_ITERATIONS                       # (not DIVERGED: the device's step would be taken back)
+    g = K.all_step_shapes()["dangling_last_node"]
+    want = K.extra_first_steps()["dangling_last_node"][0]
+    chain, loops = R.split_edges(g["edges"], 20)
+    assert chain[18] < 0 and not any(19 in (int(g["edges"][e]["i"]), int(g["edges"][e]["j"])) for e in range(len(g["edges"])))
+    assert not np.any(want[19]) and np.abs(want[18]).max() > 1e-3
+    assert K.one_iteration("dangling_last_node")[0][19].tobytes() == g["poses"][19].tobytes()
+
+
+def test_the_robust_shapes_have_the_weights_they_are_there_for():
+    """robust_chain_pair: the adjacent chain edges 7 and 8 and loop edge 23 start with w < 0.1, the robust chain edge 12 with
+    w == 1; beside the fixed node 9 the down-weighted edge 8 ends at it; under huber_delta = 0.5 edge 16 has 0.5 < s <= 3,
+    so the two thresholds give different weights.  No robust edge's s lies within 1e-9 (relative) of its huber_delta, at
+    the start or where a count is taken, so that rounding cannot flip a reported n_robust_downweighted."""
+    for g in K.extra_step_shapes()[:3]:
+        lin = K.extra_first_steps()[g["name"]][1]
+        chain, loops = R.split_edges(g["edges"], 24)
+        robust = np.flatnonzero(g["edges"]["flags"] & R.ROBUST)
+        print("%-26s huber_delta %g: w of the robust edges %s = %s" % (g["name"], g["huber_delta"], robust.tolist(), np.round(lin["w"][robust], 5).tolist()))
+        assert robust.tolist() == sorted(K.ROBUST_OUTLIERS + (K.ROBUST_INLIER, K.ROBUST_BETWEEN))
+        assert all(chain[e] == e for e in (7, 8, 12, 16)) and 23 in loops
+        assert (lin["w"][list(K.ROBUST_OUTLIERS)] < 0.1).all() and lin["w"][K.ROBUST_INLIER] == 1.0
+        assert (lin["w"][g["edges"]["flags"] == 0] == 1.0).all()
+    pair, beside, half = K.extra_step_shapes()[:3]
+    assert beside["fixed"] == (9,) and int(beside["edges"][8]["j"]) == 9 and beside["edges"].tobytes() == pair["edges"].tobytes()
+    s = K.robust_s(half["edges"], *(K.extra_first_steps()["huber_half"][1][k] for k in ("rho", "w")), 0.5)
+    w3, w05 = (K.extra_first_steps()[n][1]["w"] for n in ("robust_chain_pair", "huber_half"))
+    print("huber_half: s of the robust edges %s; w at 3.0 %s, at 0.5 %s" % (np.round(s, 4).tolist(), np.round(w3[w3 < 1], 5).tolist(), np.round(w05[w05 < 1], 5).tolist()))
+    assert half["edges"].tobytes() == pair["edges"].tobytes() and ((s > 0.5) & (s <= 3.0)).any()
+    assert w3[K.ROBUST_BETWEEN] == 1.0 and 0.3 < w05[K.ROBUST_BETWEEN] < 0.4 and (w05[list(K.ROBUST_OUTLIERS)] < w3[list(K.ROBUST_OUTLIERS)] / 5.9).all()
+    # the step the weights lead to differs by far more than the tolerance
+    d3, d05 = (K.extra_first_steps()[n][0] for n in ("robust_chain_pair", "huber_half"))
+    assert np.abs(d3 - d05).max() > 1e3 * _tolerance("huber_half", d05)
+    # the counts: no s near its threshold
+    seen = []
+    for g in K.extra_step_shapes():
+        lin = K.extra_first_steps()[g["name"]][1]
+        _, res, (rho, w) = K.one_iteration(g["name"])
+        assert res["n_robust_downweighted"] == int((w < 1.0).sum())
+        seen += [(g["name"], g["huber_delta"], K.robust_s(g["edges"], lin["rho"], lin["w"], g["huber_delta"])),
+                 (g["name"] + " after one iteration", g["huber_delta"], K.robust_s(g["edges"], rho, w, g["huber_delta"]))]
+    for name, g in zip(("robust", "plain", "clean"), K.false_loop_cases()):
+        _, res, (rho, w) = K.false_loop_runs()[name]
+        seen.append(("false loop, " + name, 3.0, K.robust_s(g["edges"], rho, w, 3.0)))
+        print("false loop, %s: %d down-weighted" % (name, res["n_robust_downweighted"]))
+    for name, delta, s in seen:
+        if len(s):
+            near = float(np.abs(s / delta - 1.0).min())
+            print("%-44s closest robust s to huber_delta: %.3e relative" % (name, near))
+            assert near > 1e-9
+    assert K.one_iteration("robust_chain_pair")[1]["n_robust_downweighted"] == 3 and K.one_iteration("huber_half")[1]["n_robust_downweighted"] == 4
+    assert K.false_loop_runs()["robust"][1]["n_robust_downweighted"] >= 1
+
+
+def test_the_dampings_move_the_dense_step():
+    """The dense step of the damping graph at lambda = 1e-6 against the step at each damping of the device's cases: where the
+    two differ by more than the tolerance, a device that ignored its config's damping would fail the case.  Measured:
+    max |delta| 1.32334 at 0 and at 1e-6, 1.32327 at 1e-2, 1.26220 at 10; the steps differ from the one at 1e-6 by 1.4e-8
+    (damping 0), 1.4e-4 (1e-2) and 1.1e-1 (10) against a tolerance of 2.1e-9.  damping_0 is 6.6 tolerances from 1e-6: too
+    close to rest a mutation on, so it is kept as a case that runs and matches (lambda = 0: P is held by the edges alone)
+    and only 1e-2 and 10, asserted to lie more than 1000 tolerances away, carry the mutation."""
+    g = K.damping_graph()
+    usual = R.dense_step(g["poses"], g["edges"], g["fixed"])[0]
+    for name, damping in K.DAMPINGS:
+        want = K.extra_first_steps()[name][0]
+        apart, tol = float(np.abs(want - usual).max()), _tolerance(name, want)
+        print("%-14s max |delta| %.5f; apart from the step at 1e-6 by %.3e; tolerance %.3e" % (name, np.abs(want).max(), apart, tol))
+        if damping > 0.0:
+            assert apart > 1e3 * tol
+
+
+def test_the_growth_stages_on_the_restatement():
+    """The growth test's stages run on the restatement (tests/test_pose_graph_gpu.py grows the device's graph the same way):
+    the split of every stage is the one the header's rule gives, the robust second edge on (40, 41) IS the chain edge and
+    is down-weighted, and every stage's first step lies below the whole-chain floor, which the device's is held to."""
+    poses, _ = K.growth_graph()
+    whole = K.floors()[0]
+    cur, edges = np.zeros((0, 3, 4)), np.zeros(0, K.EDGE)
+    for stage, (n, calls, fixed) in enumerate(K.growth_stages(), 1):
+        cur = np.concatenate([cur, poses[len(cur):n]])
+        edges = np.concatenate([edges] + calls)
+        chain, loops = R.split_edges(edges, n)
+        dense, lin = R.dense_step(cur, edges, fixed)
+        diff = float(np.abs(R.woodbury_step(cur, edges, fixed, lin=lin) - dense).max())
+        before = cur
+        cur, res, (rho, w) = R.optimize(cur, edges, fixed)
+        print("stage %d: %d nodes, %d chain and %d loop edges, fixed %s; woodbury - dense %.2e, max |delta| %.4f; code %d after %d iterations, %d down-weighted" % (
+            stage, n, (chain >= 0).sum(), len(loops), fixed, diff, np.abs(dense).max(), res["code"], res["iterations"], res["n_robust_downweighted"]))
+        assert diff <= whole and res["code"] == R.CONVERGED
+        if stage == 3:
+            assert chain[40] == 34 and int(edges[34]["flags"]) == R.ROBUST and chain[46] < 0 and lin["w"][34] < 0.1
+            assert [int(edges[e]["i"]) for e in loops[-2:]] == [35, 40] and (chain >= 0).sum() == 46 and len(loops) == 5
+            assert cur[20].tobytes() == before[20].tobytes() and cur[47].tobytes() == before[47].tobytes()
+        if stage == 4:
+            assert (chain >= 0).sum() == 47 and chain[46] == 51 and np.abs(cur[20] - before[20]).max() > 1e-6
+        near = np.abs(K.robust_s(edges, rho, w, 3.0) / 3.0 - 1.0)
+        assert not len(near) or near.min() > 1e-9
+
+
+REFERENCE_UNITS = {"to 2.5 rad": 0.78, "beyond": 3.0}            # measured (below), in spacings of the largest term
+
+
+def test_the_residual_against_the_50_digit_reference():
+    """r = (Log(R_E), t_E) of the restatement (products rounded, as the device's) against tools/pose_graph_reference.py: mpmath at 50 digits,
+    Log through the nearest rotation's quaternion, not the header's formula.  The error is counted in spacings of the
+    largest term summed on the way to r (Arith.mark("r"): 2.6 .. 7.3 here, metres).  Measured, rotation / translation part:
+      0 rad 0.06 / 0.56    1e-12 0.04 / 0.78    1e-7 0.03 / 0.38    9.9e-5 0.05 / 0.45    1.01e-4 0.07 / 0.25
+      1e-2  0.04 / 0.12    1.0   0.25 / 0.50    2.5  0.50 / 0.31    2.9    3.00 / 0.25    2.99    1.75 / 0.62
+    Up to 2.5 rad nothing exceeds 0.78; at 2.9 and 2.99 rad the rotation part is 3 to 6 times its error at 2.5 rad, which is
+    the 1 / sin theta (4.2 and 6.6) by which v / |v| loses its direction near pi: in line with the formula's conditioning,
+    no defect, and now said beside the header's "Valid for theta < 3 rad".  Asserted: 16 x the measured worst of each range."""
+    cases = K.residual_reference()
+    assert [c[0] for c in cases] == ["0", "1e-12", "1e-7", "9.9e-5", "1.01e-4", "1e-2", "1.0", "2.5", "2.9", "2.99"]
+    try:
+        import mpmath  # noqa: F401
+    except ImportError:
+        print("mpmath is not here: the file is taken as it is")
+    else:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("pose_graph_reference", os.path.join(os.path.dirname(K.REFERENCE_PATH), "..", "..", "tools", "pose_graph_reference.py"))
+        tool = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(tool)
+        with open(K.REFERENCE_PATH) as f:
+            assert f.read() == tool.text(), "tests/golden/pose_graph_residual_reference.json is not what tools/pose_graph_reference.py writes"
+    failed = []
+    for angle, Ti, Tj, Z, want in cases:
+        ar = R.Arith()
+        got = np.array(R.edge_terms(Ti, Tj, Z, np.eye(6), 0, 3.0, ar)[0])
+        unit = np.spacing(ar.seen["r"])
+        rot, trans = np.abs(got - want)[:3].max() / unit, np.abs(got - want)[3:].max() / unit
+        allowed = 16.0 * REFERENCE_UNITS["to 2.5 rad" if float(angle) <= 2.5 else "beyond"]
+        print("residual angle %-8s (%.17g): rotation part %.2f, translation part %.2f spacings of the largest term %.3f; allowed %.1f" % (
+            angle, np.linalg.norm(want[:3]), rot, trans, ar.seen["r"], allowed))
+        assert abs(np.linalg.norm(want[:3]) - float(angle)) <= 1e-15 + 4e-16 * float(angle) and 0.1 < np.linalg.norm(want[3:]) < 3.0
+        if not max(rot, trans) <= allowed:
+            failed.append(angle)
+    assert not failed, failed
 
 
 def test_the_circles_meet_the_conditions_their_seed_was_chosen_by():
