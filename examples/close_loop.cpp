@@ -1,6 +1,7 @@
 // close_loop.cpp -- loop closing without scans: a sensor drives two laps of a circle; its odometry steps carry noise, so the
 // chained poses drift; a few loop closures tie the second lap to the first; lfx::PoseGraph optimises the poses on the device.
-// Every pose here comes from pose arithmetic (lfx_motion_between and a product), none from a scan.
+// Every pose here comes from pose arithmetic (lfx_motion_between and a product), none from a scan; close_loop_scans.cpp is
+// the same loop from scans, its closures found and verified by lfx::LoopCloser.
 //
 //   close_loop [N [L [OUT]]]
 //     N     nodes (default 256), two laps of a circle of radius 20 m

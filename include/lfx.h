@@ -1068,6 +1068,29 @@ int lfx_place_db_download(lfx_ctx *ctx, const lfx_place_db *db, uint32_t first, 
  * Synchronous.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, n_queries 0, k outside 1 .. 16, a range past the index's size. */
 int lfx_place_db_query(lfx_ctx *ctx, const lfx_place_db *db, const float *d_desc, uint32_t n_queries, uint32_t first,
                        uint32_t count, uint32_t k, lfx_place_match *matches, void *stream);
+/* The same query with a gate of its own per query, decided on the device: entry e is ELIGIBLE for query q iff
+ * e < gates[q].limit and it passes the position test (dx*dx + dy*dy) + dz*dz <= radius*radius, d = the translation of
+ * d_poses[e] minus the translation of d_poses[gates[q].pose], all in double, unfused, in that order -- the rule and the
+ * arithmetic of lfx_keyframes_submap's selection.  The test is skipped (every e < limit is eligible) where d_poses is NULL or
+ * gates[q].pose == LFX_PLACE_NO_POSE; a radius of +inf passes every finite pose.  d_poses: device, [.][12] doubles as the
+ * keyframe store and the pose graph keep them, entry e's pose at d_poses[e]; it must hold every entry below the largest
+ * limit and every gates[q].pose, and is read on `stream`.  matches [n_queries][k]: the k best ELIGIBLE entries, each with
+ * exactly the (entry, shift, distance, yaw) lfx_place_db_query gives for that pair, ascending distance, equal distances by
+ * the lower entry; slots beyond the eligible entries are UINT32_MAX, 0, +inf, 0.  n_eligible (may be NULL) [n_queries]: the
+ * eligible entries of each query.  Distance work is done for eligible pairs only: a gate pass writes each query's eligible
+ * entries in ascending order (a fixed order: the same inputs give the same list), the comparison and the selection run
+ * over those lists, whose lengths stay on the device and nothing waits before the final copy.  The comparison's launch is
+ * sized from the largest limit: without poses a workgroup to each tile of it, as lfx_place_db_query's; with poses at most
+ * about 8 192 workgroups in all, each walking every n-th tile of one pass up to its list's end.  Synchronous; ordered behind the index's last add.  LFX_ERR_INVALID_ARGUMENT, before anything is queued:
+ * NULL ctx, db, d_desc, gates or matches, n_queries outside 1 .. 65535, k outside 1 .. 16, a limit above the index's size, a
+ * radius that is NaN or negative. */
+#define LFX_PLACE_NO_POSE 0xFFFFFFFFu
+typedef struct lfx_place_gate { uint32_t limit; uint32_t pose; } lfx_place_gate;
+int lfx_place_db_query_gated(lfx_ctx *ctx, const lfx_place_db *db, const float *d_desc, uint32_t n_queries,
+                             const lfx_place_gate *gates /* host [n_queries] */,
+                             const double *d_poses /* device [.][12]; entry e's pose is d_poses[e]; may be NULL */,
+                             double radius, uint32_t k, lfx_place_match *matches /* host [n_queries][k] */,
+                             uint32_t *n_eligible /* host [n_queries], may be NULL */, void *stream);
 
 /* --- segmentation: ground, clusters and clutter from a range image; feature clouds filtered by it ----------------------- */
 /* "Is this feature on the road, on an object, or on a leaf?"  No reference counterpart; the model is LeGO-LOAM's image
@@ -1361,6 +1384,118 @@ int lfx_keyframes_submap(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind,
  * store's scratch min(2^20, max(max_points)) records at a time (a chunk may begin and end inside a keyframe) and copied down
  * chunk by chunk, so a save needs no second copy of the records on the device.  Synchronous. */
 int lfx_keyframes_save(lfx_ctx *ctx, const lfx_keyframes *keyframes, const char *dirname, int written[2], void *stream);
+
+/* --- the loop closer: revisits found, verified and closed over a store, an index and a graph ------------------------------ */
+/* What joins the sections above.  No reference counterpart; the model is LIO-SAM's loop-closure thread (Shan et al., IROS 2020)
+ * with Scan Context as the detector.  THE CONTRACT: keyframe id == place entry == graph node id -- the caller adds a keyframe to
+ * the store, its descriptor to the index and its pose to the graph in step.  A call that names a keyframe >= min(store size,
+ * index size, graph nodes) is LFX_ERR_INVALID_ARGUMENT and nothing is touched.  The closer keeps the three handles and owns
+ * none of them: they outlive it.  It adds no kernel of its own: every step below is a public call of this header, and its
+ * results are those calls' bytes.
+ *
+ * DETECT of keyframes first .. first + count - 1: one lfx_place_db_query_gated, the query descriptors the index's own entries
+ * first .., gates[q] = { limit = q >= min_gap ? q - min_gap + 1 : 0 (e + min_gap <= q), pose = q }, d_poses the store's pose
+ * array, radius = search_radius, k = n_candidates.  Matches with distance > max_distance are turned into the empty match
+ * (UINT32_MAX, 0, +inf, 0).
+ *
+ * VERIFY of query keyframe q against a candidate (c = entry, yaw), c + min_gap <= q:
+ *   1. lfx_keyframes_submap of each kind into the closer's buffers (submap_capacity[kind] records): centre = the translation
+ *      of keyframe c's current pose, submap_radius, window [max(c - w, 0), min(c + w, q - min_gap) + 1), w =
+ *      submap_half_window.  truncated is reported in the closure and is no error.
+ *   2. lfx_map_create on each submap with map_cell_size; both maps are destroyed before the call returns.  (The maps allocate
+ *      as lfx_map_create does today: per call.  Everything else the closer uses on the device is allocated by
+ *      lfx_loop_closer_create: the submap buffers, the downsample output, the count words.)
+ *   3. lfx_voxel_downsample of q's surface records as the store holds them (sensor frame) at surface_leaf -- 0: no
+ *      downsample; a cloud PCL would hand back unfiltered (status 1) is used as stored.  The edge records are used as stored.
+ *   4. lfx_scan_to_map_align_report, one cloud, n_neighbors, max_iter, initial = pose_c x Rz(yaw) (the place index's
+ *      convention): R = R_c Rz, (r0 cos + r1 sin, -r0 sin + r1 cos, r2) per row, t = t_c.
+ * ACCEPTED iff all of, tested in this order (reason: the first that fails): neither submap and neither cloud of q is empty;
+ * the align code is a success or LFX_ALIGN_MAX_ITERATION; report.valid; report.rank == 6; !(reject_degenerate &&
+ * report.degenerate); rms_edge <= max_rms_edge; rms_surface <= max_rms_surface; (n_edge_inliers + n_surface_inliers) /
+ * (n_edge + n_surface) >= min_inlier_share; where scale_by_sigma2: sigma2 finite and > 0.  The thresholds on rms and inliers
+ * have NO MEASURED DEFAULT and ship permissive (+inf, +inf, 0); DESIGN.md section 7 records what the test drive showed.
+ * THE EDGE of a closure that ran an alignment with a valid report (accepted or not): i = c, j = q, flags LFX_EDGE_ROBUST,
+ * Z = lfx_motion_between(pose_c, result.pose), Omega = lfx_pose_graph_edge_information(result.pose, report.information),
+ * every entry divided by sigma2 where scale_by_sigma2.  Otherwise the edge is all zero.
+ *
+ * UPDATE of keyframes first .. first + count - 1: one detect; per keyframe, verify its candidates best first, stopping at the
+ * first accepted or after max_verify; all accepted edges in one lfx_pose_graph_add_edges (LFX_ERR_CAPACITY: the call returns
+ * that code, the closures are filled, the graph is untouched); if any went in, lfx_pose_graph_optimize; if its code is
+ * CONVERGED or MAX_ITERATIONS, lfx_keyframes_follow from lfx_pose_graph_view for all nodes.  Every verification of the call
+ * sees the poses from before the optimisation.  With no accepted closure neither the graph nor the store is written.
+ * closures[s] is the last verification of keyframe first + s; a keyframe without a candidate has reason
+ * LFX_LOOP_NO_CANDIDATE, candidate UINT32_MAX and every other byte 0.  All calls are synchronous. */
+#define LFX_LOOP_ACCEPTED 0
+#define LFX_LOOP_NO_CANDIDATE 1         /* update: detect left the keyframe no candidate */
+#define LFX_LOOP_EMPTY_QUERY 2          /* the query keyframe has no edge or no surface record */
+#define LFX_LOOP_EMPTY_SUBMAP 3         /* a submap of either kind has no record */
+#define LFX_LOOP_ALIGN_FAILED 4         /* the align code is neither a success nor LFX_ALIGN_MAX_ITERATION */
+#define LFX_LOOP_NO_REPORT 5            /* !report.valid */
+#define LFX_LOOP_RANK 6                 /* report.rank != 6 */
+#define LFX_LOOP_DEGENERATE 7
+#define LFX_LOOP_RMS_EDGE 8
+#define LFX_LOOP_RMS_SURFACE 9
+#define LFX_LOOP_INLIERS 10
+#define LFX_LOOP_SIGMA2 11
+typedef struct lfx_loop_closer lfx_loop_closer;
+typedef struct lfx_loop_closer_config {
+  uint32_t min_gap;              /* 50: a candidate c of q has c + min_gap <= q; >= 1 */
+  uint32_t n_candidates;         /* 3; 1 .. 16 */
+  uint32_t max_verify;           /* 1; >= 1 */
+  uint32_t submap_half_window;   /* 25 (LIO-SAM: historyKeyframeSearchNum) */
+  double search_radius;          /* 15.0 (LIO-SAM: historyKeyframeSearchRadius); >= 0, +inf: descriptors alone */
+  double max_distance;           /* 0.2: the Scan Context distance above which a candidate is dropped; <= keeps */
+  double submap_radius;          /* 25.0; >= 0, finite */
+  uint64_t submap_capacity[2];   /* records of the edge / surface submap buffer; the caller sets them, 1 .. 2^32 - 1 */
+  float map_cell_size;           /* 1.0 */
+  float surface_leaf;            /* 1.0; 0: no downsample */
+  uint32_t n_neighbors;          /* 15 */
+  int32_t max_iter;              /* 20 */
+  double max_rms_edge, max_rms_surface;   /* +inf, +inf: no measured default */
+  double min_inlier_share;       /* 0: no measured default */
+  int32_t reject_degenerate;     /* 1 */
+  int32_t scale_by_sigma2;       /* 1 */
+  uint64_t downsample_capacity;  /* records of the downsample output: the most surface records a QUERY keyframe may have where
+                                    surface_leaf > 0 (one with more is LFX_ERR_CAPACITY); <= 2^32 - 1.  0, the default: the
+                                    store's max_points[1] or 2^20, whichever is less.  Nothing is allocated, and no keyframe
+                                    is too large, where surface_leaf is 0 */
+} lfx_loop_closer_config;
+typedef struct lfx_loop_closure {
+  uint32_t query, candidate;     /* q, c */
+  int32_t accepted, reason;      /* reason: LFX_LOOP_* */
+  lfx_place_match match;         /* the candidate as it was given */
+  lfx_align_result result;
+  lfx_align_report report;
+  lfx_keyframes_submap_result submap[2];
+  lfx_pose_graph_edge edge;
+} lfx_loop_closure;
+typedef struct lfx_loop_closer_result {
+  uint32_t n_detected;           /* keyframes of the range with at least one candidate */
+  uint32_t n_verified;           /* verifications run */
+  uint32_t n_accepted;           /* closures accepted: the edges that went into the graph */
+  int32_t followed;              /* 1: the store's poses were taken from the graph */
+  lfx_pose_graph_result graph;   /* of lfx_pose_graph_optimize; all zero where it did not run */
+} lfx_loop_closer_result;
+typedef struct lfx_loop_closer_info_t {
+  uint64_t device_bytes;         /* everything lfx_loop_closer_create allocated on the device */
+} lfx_loop_closer_info_t;
+void lfx_loop_closer_default_config(lfx_loop_closer_config *config);
+/* A config outside the ranges above, or a store, an index or a graph of another device than ctx's, is
+ * LFX_ERR_INVALID_ARGUMENT, a failed allocation LFX_ERR_OUT_OF_MEMORY with nothing left allocated. */
+int lfx_loop_closer_create(lfx_ctx *ctx, const lfx_loop_closer_config *config, lfx_keyframes *keyframes, lfx_place_db *db,
+                           lfx_pose_graph *graph, lfx_loop_closer **out);
+void lfx_loop_closer_destroy(lfx_loop_closer *closer);
+int lfx_loop_closer_info(const lfx_loop_closer *closer, lfx_loop_closer_info_t *info);
+/* candidates host [count][n_candidates]; n_eligible host [count], may be NULL. */
+int lfx_loop_closer_detect(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t first, uint32_t count, lfx_place_match *candidates,
+                           uint32_t *n_eligible, void *stream);
+/* LFX_ERR_INVALID_ARGUMENT also for a candidate without an entry, with entry + min_gap > query_id or with a yaw that is not
+ * finite. */
+int lfx_loop_closer_verify(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t query_id, const lfx_place_match *candidate,
+                           lfx_loop_closure *out, void *stream);
+/* closures host [count]; result may be NULL. */
+int lfx_loop_closer_update(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t first, uint32_t count, lfx_loop_closure *closures,
+                           lfx_loop_closer_result *result, void *stream);
 
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device

@@ -768,6 +768,22 @@ public:
   {
     return Query(d_desc, n_queries, k, 0, Size());
   }
+  // the same with a gate per query (lfx_place_db_query_gated): entry e is eligible for query q iff e < gates[q].limit and,
+  // where d_poses is given and gates[q].pose is not LFX_PLACE_NO_POSE, its pose lies within `radius` of pose gates[q].pose;
+  // n_eligible (may be null) takes the eligible entries of each query
+  std::vector<lfx_place_match> QueryGated(
+    const float * d_desc, const std::vector<lfx_place_gate> & gates, const double * d_poses, double radius, std::uint32_t k = 1,
+    std::vector<std::uint32_t> * n_eligible = nullptr, void * stream = nullptr) const
+  {
+    const std::uint32_t n_queries = static_cast<std::uint32_t>(gates.size());
+    std::vector<lfx_place_match> out(gates.size() * k);
+    if (n_eligible) {n_eligible->assign(gates.size(), 0u);}
+    const int rc = lfx_place_db_query_gated(fx_.handle(), db_, d_desc, n_queries, gates.data(), d_poses, radius, k, out.data(),
+        n_eligible ? n_eligible->data() : nullptr, stream);
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+    return out;
+  }
+  lfx_place_db * handle() const {return db_;}
 
 private:
   const FeatureExtraction & fx_;
@@ -976,6 +992,69 @@ private:
   }
   const FeatureExtraction & fx_;
   lfx_keyframes * store_ = nullptr;
+};
+
+// The loop closer (lfx_loop_closer): revisits found in a PlaceDb, verified against submaps of a Keyframes store and closed in
+// a PoseGraph, all three on the device of `fx` and all of them outliving it.  THE CONTRACT: keyframe id == place entry ==
+// graph node id (add to the three in step).  Update(first, count) is the whole loop: detect, verify, add the accepted edges,
+// optimise, make the store follow.  The thresholds on rms and inliers ship permissive (no measured default).
+class LoopCloser
+{
+public:
+  static lfx_loop_closer_config DefaultConfig(std::uint64_t edge_submap_capacity, std::uint64_t surface_submap_capacity)
+  {
+    lfx_loop_closer_config c;
+    lfx_loop_closer_default_config(&c);
+    c.submap_capacity[0] = edge_submap_capacity;
+    c.submap_capacity[1] = surface_submap_capacity;
+    return c;
+  }
+  LoopCloser(const FeatureExtraction & fx, const lfx_loop_closer_config & config, Keyframes & keyframes, PlaceDb & db, PoseGraph & graph)
+  : fx_(fx), config_(config)
+  {
+    Check(lfx_loop_closer_create(fx.handle(), &config, keyframes.handle(), db.handle(), graph.handle(), &closer_));
+  }
+  ~LoopCloser() {lfx_loop_closer_destroy(closer_);}
+  LoopCloser(const LoopCloser &) = delete;
+  LoopCloser & operator=(const LoopCloser &) = delete;
+
+  // the candidates of keyframes first .. first + count - 1: [count][n_candidates], best first, the empty match where none is left
+  std::vector<lfx_place_match> Detect(std::uint32_t first, std::uint32_t count, std::vector<std::uint32_t> * n_eligible = nullptr, void * stream = nullptr)
+  {
+    std::vector<lfx_place_match> out(static_cast<std::size_t>(count) * config_.n_candidates);
+    if (n_eligible) {n_eligible->assign(count, 0u);}
+    Check(lfx_loop_closer_detect(fx_.handle(), closer_, first, count, out.data(), n_eligible ? n_eligible->data() : nullptr, stream));
+    return out;
+  }
+  lfx_loop_closure Verify(std::uint32_t query_id, const lfx_place_match & candidate, void * stream = nullptr)
+  {
+    lfx_loop_closure out;
+    Check(lfx_loop_closer_verify(fx_.handle(), closer_, query_id, &candidate, &out, stream));
+    return out;
+  }
+  // closures: one per keyframe of the range (its last verification)
+  lfx_loop_closer_result Update(std::uint32_t first, std::uint32_t count, std::vector<lfx_loop_closure> & closures, void * stream = nullptr)
+  {
+    lfx_loop_closer_result r;
+    closures.resize(count);
+    Check(lfx_loop_closer_update(fx_.handle(), closer_, first, count, closures.data(), &r, stream));
+    return r;
+  }
+  lfx_loop_closer_info_t Info() const
+  {
+    lfx_loop_closer_info_t i;
+    lfx_loop_closer_info(closer_, &i);
+    return i;
+  }
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_loop_closer_config config_;
+  lfx_loop_closer * closer_ = nullptr;
 };
 
 }  // namespace lfx

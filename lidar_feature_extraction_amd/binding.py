@@ -256,6 +256,43 @@ KEYFRAMES_EDGE, KEYFRAMES_SURFACE = 0, 1
 KEYFRAMES_NO_ID = 0xFFFFFFFF
 
 
+class PlaceGate(C.Structure):
+    """lfx_place_gate: the entries one query of lfx_place_db_query_gated may match (e < limit, near pose `pose`)."""
+    _fields_ = [("limit", C.c_uint32), ("pose", C.c_uint32)]
+
+
+PLACE_NO_POSE = 0xFFFFFFFF
+
+
+class LoopCloserConfig(C.Structure):
+    """lfx_loop_closer_config: which revisits are looked for, what they are aligned against, and what is accepted."""
+    _fields_ = [("min_gap", C.c_uint32), ("n_candidates", C.c_uint32), ("max_verify", C.c_uint32), ("submap_half_window", C.c_uint32),
+                ("search_radius", C.c_double), ("max_distance", C.c_double), ("submap_radius", C.c_double),
+                ("submap_capacity", C.c_uint64 * 2), ("map_cell_size", C.c_float), ("surface_leaf", C.c_float),
+                ("n_neighbors", C.c_uint32), ("max_iter", C.c_int32), ("max_rms_edge", C.c_double), ("max_rms_surface", C.c_double),
+                ("min_inlier_share", C.c_double), ("reject_degenerate", C.c_int32), ("scale_by_sigma2", C.c_int32),
+                ("downsample_capacity", C.c_uint64)]
+
+
+class LoopClosure(C.Structure):
+    """lfx_loop_closure: one verification -- the candidate, the alignment and its report, both submaps, the edge."""
+    _fields_ = [("query", C.c_uint32), ("candidate", C.c_uint32), ("accepted", C.c_int32), ("reason", C.c_int32), ("match", PlaceMatch),
+                ("result", AlignResult), ("report", AlignReport), ("submap", KeyframesSubmapResult * 2), ("edge", PoseGraphEdge)]
+
+
+class LoopCloserResult(C.Structure):
+    _fields_ = [("n_detected", C.c_uint32), ("n_verified", C.c_uint32), ("n_accepted", C.c_uint32), ("followed", C.c_int32),
+                ("graph", PoseGraphResult)]
+
+
+class LoopCloserInfo(C.Structure):
+    _fields_ = [("device_bytes", C.c_uint64)]
+
+
+(LOOP_ACCEPTED, LOOP_NO_CANDIDATE, LOOP_EMPTY_QUERY, LOOP_EMPTY_SUBMAP, LOOP_ALIGN_FAILED, LOOP_NO_REPORT, LOOP_RANK, LOOP_DEGENERATE,
+ LOOP_RMS_EDGE, LOOP_RMS_SURFACE, LOOP_INLIERS, LOOP_SIGMA2) = range(12)
+
+
 class DeviceView(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_rings", C.c_uint32), ("ring_capacity", C.c_uint32)] + \
         [(n, C.c_void_p) for n in (
@@ -287,7 +324,9 @@ EXPORTS = [
     "lfx_trajectory_segments", "lfx_trajectory_from_gyro", "lfx_deskew_batch_trajectory", "lfx_odometry_update_batch_trajectory",
     "lfx_scan_context_default_config", "lfx_scan_context_tables", "lfx_scan_context_batch", "lfx_place_db_create",
     "lfx_place_db_destroy", "lfx_place_db_add", "lfx_place_db_add_host", "lfx_place_db_size", "lfx_place_db_download",
-    "lfx_place_db_query",
+    "lfx_place_db_query", "lfx_place_db_query_gated",
+    "lfx_loop_closer_default_config", "lfx_loop_closer_create", "lfx_loop_closer_destroy", "lfx_loop_closer_info", "lfx_loop_closer_detect",
+    "lfx_loop_closer_verify", "lfx_loop_closer_update",
     "lfx_segment_default_config", "lfx_segment_tables", "lfx_segment_batch", "lfx_pack_features_segmented",
     "lfx_pose_graph_default_config", "lfx_pose_graph_create", "lfx_pose_graph_destroy", "lfx_pose_graph_info", "lfx_pose_graph_add_nodes",
     "lfx_pose_graph_set_fixed", "lfx_pose_graph_add_edges", "lfx_pose_graph_optimize", "lfx_pose_graph_poses", "lfx_pose_graph_set_poses",
@@ -497,6 +536,17 @@ def load(test_hooks=False):
     L.lfx_keyframes_build.argtypes = [vp, vp, i32, u32, u32, vp, u64, p64, vp]
     L.lfx_keyframes_submap.argtypes = [vp, vp, i32, vp, C.c_double, u32, u32, vp, u64, C.POINTER(KeyframesSubmapResult), vp]
     L.lfx_keyframes_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
+    L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
+    plc = C.POINTER(LoopCloserConfig)
+    L.lfx_loop_closer_default_config.argtypes = [plc]
+    L.lfx_loop_closer_default_config.restype = None
+    L.lfx_loop_closer_create.argtypes = [vp, plc, vp, vp, vp, C.POINTER(vp)]
+    L.lfx_loop_closer_destroy.argtypes = [vp]
+    L.lfx_loop_closer_destroy.restype = None
+    L.lfx_loop_closer_info.argtypes = [vp, C.POINTER(LoopCloserInfo)]
+    L.lfx_loop_closer_detect.argtypes = [vp, vp, u32, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
+    L.lfx_loop_closer_verify.argtypes = [vp, vp, u32, C.POINTER(PlaceMatch), C.POINTER(LoopClosure), vp]
+    L.lfx_loop_closer_update.argtypes = [vp, vp, u32, u32, C.POINTER(LoopClosure), C.POINTER(LoopCloserResult), vp]
     L.lfx_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.lfx_kernel_name.argtypes = [i32]
     L.lfx_kernel_name.restype = C.c_char_p

@@ -488,6 +488,10 @@ struct CloudSpan
 void launch_feature_offsets(const uint32_t * edge_counts, const uint32_t * surface_counts, uint32_t stride, uint32_t batch,
   uint32_t * d_offsets, hipStream_t st);
 
+// lfx_place.hip: where an index keeps its descriptors on the device ([entries][*cells] floats, cells = R * S) -- a loop
+// closer's detect queries the index with its own entries (lfx_loopclose.hip)
+const float * place_db_entries(const lfx_place_db * db, uint32_t * cells);
+
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
   const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,

@@ -1,10 +1,12 @@
 // lfx_place.hip -- place recognition (include/lfx.h, the place recognition section; lfx_kernels_place.hpp):
 // lfx_scan_context_batch, the descriptors of the last device batch's scans from its input records, and lfx_place_db, the
-// index that compares query descriptors with every entry under every column shift.  The descriptor's tables come from
+// index that compares query descriptors with every entry of a range -- or, gated, with the entries below a limit whose pose
+// lies near the query's -- under every column shift.  The descriptor's tables come from
 // lfx_scan_context_tables (lfx_pose.cpp) and from nowhere else.
 #include "lfx_internal.hpp"
 #include "lfx_kernels_place.hpp"
 
+#include <algorithm>
 #include <cstdint>
 
 using namespace lfx_host;
@@ -22,6 +24,10 @@ struct lfx_place_db
   mutable DevBuf<uint32_t> best_shift;
   mutable DevBuf<lfx::PlaceMatchDevice> matches;
   mutable PinnedBuf h_matches;
+  // the gated query's: the gates, the lists of eligible entries ([queries][largest limit]) and their lengths
+  mutable DevBuf<lfx::PlaceGate> gates;
+  mutable DevBuf<uint32_t> list, n_eligible;
+  mutable PinnedBuf h_gates, h_eligible;
   hipEvent_t added = nullptr;                // recorded behind the last add's copy and norms
   bool add_pending = false;
 };
@@ -71,12 +77,26 @@ int take_slot(lfx_ctx * c, size_t doubles, size_t keys, lfx_ctx::PlaceSlot *& sl
   return LFX_OK;
 }
 
-// place_compare_kernel may ask for more dynamic LDS than a kernel gets unasked (82 KB at R = 40, S = 120)
+// the comparison kernels may ask for more dynamic LDS than a kernel gets unasked (82 KB at R = 40, S = 120)
 int allow_compare_lds(lfx_ctx * c)
 {
-  LFX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::place_compare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-    (int)lfx::place_compare_lds(LFX_SCAN_CONTEXT_MAX_RINGS, LFX_SCAN_CONTEXT_MAX_SECTORS)));
+  const int most = (int)lfx::place_compare_lds(LFX_SCAN_CONTEXT_MAX_RINGS, LFX_SCAN_CONTEXT_MAX_SECTORS);
+  LFX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::place_compare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+  LFX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(lfx::place_compare_gated_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, most));
   return LFX_OK;
+}
+
+// the device's matches as the caller's: the yaw of each shift
+void write_matches(const lfx::PlaceMatchDevice * got, size_t n_matches, uint32_t S, lfx_place_match * matches)
+{
+  const double step = (2.0 * M_PI) / (double)S;
+  for (size_t i = 0; i < n_matches; i++) {
+    lfx_place_match & m = matches[i];
+    m.entry = got[i].entry;
+    m.shift = got[i].shift;
+    m.distance = got[i].distance;
+    m.yaw = got[i].entry == UINT32_MAX ? 0.0 : (2u * got[i].shift <= S ? (double)got[i].shift * step : ((double)got[i].shift - (double)S) * step);
+  }
 }
 
 int launch_norms(lfx_ctx * c, const float * d_desc, double * d_norms, uint32_t n, const lfx_scan_context_config & cfg, hipStream_t st)
@@ -115,6 +135,12 @@ int check_add(lfx_ctx * c, const lfx_place_db * db, uint32_t n)
   return LFX_OK;
 }
 }  // namespace
+
+const float * lfx_host::place_db_entries(const lfx_place_db * db, uint32_t * cells)
+{
+  *cells = cells_of(db->cfg);
+  return db->desc.p;
+}
 
 extern "C" {
 
@@ -275,19 +301,84 @@ int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_des
     LFX_HIP(c, hipGetLastError());
   }
   hipLaunchKernelGGL(lfx::place_select_kernel, dim3(n_queries), dim3(lfx::kPlaceThreads), 0, st, db->best_distance.p, db->best_shift.p, count, first, k,
-    db->matches.p);
+    db->matches.p, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
   LFX_HIP(c, hipGetLastError());
   LFX_HIP(c, hipMemcpyAsync(db->h_matches.p, db->matches.p, sizeof(lfx::PlaceMatchDevice) * n_matches, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
-  const lfx::PlaceMatchDevice * got = reinterpret_cast<const lfx::PlaceMatchDevice *>(db->h_matches.p);
-  const double step = (2.0 * M_PI) / (double)S;
-  for (size_t i = 0; i < n_matches; i++) {
-    lfx_place_match & m = matches[i];
-    m.entry = got[i].entry;
-    m.shift = got[i].shift;
-    m.distance = got[i].distance;
-    m.yaw = got[i].entry == UINT32_MAX ? 0.0 : (2u * got[i].shift <= S ? (double)got[i].shift * step : ((double)got[i].shift - (double)S) * step);
+  write_matches(reinterpret_cast<const lfx::PlaceMatchDevice *>(db->h_matches.p), n_matches, S, matches);
+  return LFX_OK;
+}
+
+int lfx_place_db_query_gated(lfx_ctx * c, const lfx_place_db * db, const float * d_desc, uint32_t n_queries, const lfx_place_gate * gates,
+  const double * d_poses, double radius, uint32_t k, lfx_place_match * matches, uint32_t * n_eligible, void * stream)
+{
+  if (!c || !db || !d_desc || !gates || !matches) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_db(c, db) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (n_queries == 0 || n_queries > 65535u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_queries must be in 1 .. 65535");}
+  if (k < 1u || k > LFX_PLACE_MAX_MATCHES) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "k must be in 1 .. 16");}
+  if (!(radius >= 0.0)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "radius must be >= 0 (+inf: no position test)");}
+  uint32_t stride = 0;                                   // the largest limit: what the lists and the launches are sized by
+  for (uint32_t q = 0; q < n_queries; q++) {
+    if (gates[q].limit > db->n) {
+      return fail(c, LFX_ERR_INVALID_ARGUMENT, "gate " + std::to_string(q) + ": limit " + std::to_string(gates[q].limit) + " is above the index's " +
+               std::to_string(db->n) + " entries");
+    }
+    stride = std::max(stride, gates[q].limit);
   }
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t R = db->cfg.n_rings, S = db->cfg.n_sectors;
+  const size_t pairs = (size_t)n_queries * stride, n_matches = (size_t)n_queries * k;
+  if (hold(db->query_norms, (size_t)n_queries * S) != hipSuccess || hold(db->best_distance, pairs) != hipSuccess ||
+    hold(db->best_shift, pairs) != hipSuccess || hold(db->list, pairs) != hipSuccess || hold(db->matches, n_matches) != hipSuccess ||
+    hold(db->gates, n_queries) != hipSuccess || hold(db->n_eligible, n_queries) != hipSuccess ||
+    db->h_matches.reserve(sizeof(lfx::PlaceMatchDevice) * n_matches) != hipSuccess ||
+    db->h_gates.reserve(sizeof(lfx::PlaceGate) * n_queries) != hipSuccess || db->h_eligible.reserve(sizeof(uint32_t) * n_queries) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
+  }
+  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  // (the call is synchronous: the pinned blocks are free again when it returns)
+  static_assert(sizeof(lfx::PlaceGate) == sizeof(lfx_place_gate), "the kernel's gate is the header's");
+  std::memcpy(db->h_gates.p, gates, sizeof(lfx::PlaceGate) * n_queries);
+  LFX_HIP(c, hipMemcpyAsync(db->gates.p, db->h_gates.p, sizeof(lfx::PlaceGate) * n_queries, hipMemcpyHostToDevice, st));
+  lfx_scan_context_config cfg = db->cfg;
+  const int rn = launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st);
+  if (rn != LFX_OK) {return rn;}
+  hipLaunchKernelGGL(lfx::place_gate_kernel, dim3(n_queries), dim3(lfx::kPlaceThreads), 0, st, db->gates.p, d_poses, radius * radius, stride, db->list.p,
+    db->n_eligible.p);
+  LFX_HIP(c, hipGetLastError());
+  if (stride) {
+    lfx::PlaceCompareArgs a{};
+    a.query = d_desc; a.query_norms = db->query_norms.p;
+    a.entries = db->desc.p; a.entry_norms = db->norms.p;
+    a.best_distance = db->best_distance.p; a.best_shift = db->best_shift.p;
+    a.count = stride; a.R = R; a.S = S;
+    // The lists' lengths stay on the device, so the launch is sized by the bound.  Where every entry below the limit is
+    // eligible: lfx_place_db_query's tiles, a workgroup to each.  With the position test, which leaves short lists: tiles of
+    // one pass, so that a short list spreads over workgroups, and at most about 8 192 workgroups in all, each taking every
+    // gridDim.x-th tile up to its list's end (64 queries against 65 536 entries would start a million workgroups otherwise,
+    // nearly all of them with nothing to do).
+    a.tile = lfx::place_tile(S, pairs);
+    uint32_t per_query = (stride + a.tile - 1u) / a.tile;
+    if (d_poses) {
+      a.tile = lfx::place_pass_entries(S);
+      per_query = std::min((stride + a.tile - 1u) / a.tile, std::max(8192u / n_queries, 1u));
+    }
+    const dim3 grid(per_query, n_queries);
+    hipLaunchKernelGGL(lfx::place_compare_gated_kernel, grid, dim3(lfx::kPlaceThreads), (uint32_t)lfx::place_compare_lds(R, S), st, a,
+      static_cast<const uint32_t *>(db->list.p), static_cast<const uint32_t *>(db->n_eligible.p), stride);
+    LFX_HIP(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(lfx::place_select_kernel, dim3(n_queries), dim3(lfx::kPlaceThreads), 0, st, db->best_distance.p, db->best_shift.p, stride, 0u, k,
+    db->matches.p, static_cast<const uint32_t *>(db->list.p), static_cast<const uint32_t *>(db->n_eligible.p));
+  LFX_HIP(c, hipGetLastError());
+  LFX_HIP(c, hipMemcpyAsync(db->h_eligible.p, db->n_eligible.p, sizeof(uint32_t) * n_queries, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipMemcpyAsync(db->h_matches.p, db->matches.p, sizeof(lfx::PlaceMatchDevice) * n_matches, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  write_matches(reinterpret_cast<const lfx::PlaceMatchDevice *>(db->h_matches.p), n_matches, S, matches);
+  if (n_eligible) {std::memcpy(n_eligible, db->h_eligible.p, sizeof(uint32_t) * n_queries);}
   return LFX_OK;
 }
 

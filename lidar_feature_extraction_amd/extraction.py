@@ -516,6 +516,11 @@ class FeatureExtraction:
         """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
         return PlaceDb(self, capacity, config)
 
+    def loop_closer(self, keyframes, place_db, graph, config=None, **fields):
+        """lfx_loop_closer_create: a loop closer over a Keyframes store, a PlaceDb and a PoseGraph of this context (keyframe id
+        == place entry == graph node id); the fields of lfx_loop_closer_config as keywords (submap_capacity is required)."""
+        return LoopCloser(self, keyframes, place_db, graph, config, **fields)
+
     def download(self, scan, stream=0):
         r = B.ScanResult()
         B.check(self._ctx, self._L.lfx_download_scan(self._ctx, scan, C.c_void_p(int(stream)), C.byref(r)), self._L)
@@ -1331,8 +1336,29 @@ class PlaceDb:
         query of k dicts, ascending distance, equal distances by the lower entry.  Synchronous."""
         res = self.query_raw(d_desc, n_queries, k, first, count, stream)
         k = int(k)
-        return [[dict(entry=None if m.entry == B.PLACE_NO_ENTRY else int(m.entry), shift=int(m.shift), distance=float(m.distance),
-                      yaw=float(m.yaw)) for m in res[q * k:(q + 1) * k]] for q in range(int(n_queries))]
+        return [[_match(m) for m in res[q * k:(q + 1) * k]] for q in range(int(n_queries))]
+
+    def query_gated_raw(self, d_desc, gates, d_poses=0, radius=float("inf"), k=1, stream=0):
+        """lfx_place_db_query_gated as it returns: (a B.PlaceMatch array [len(gates) * k], n_eligible uint32 [len(gates)]).
+        gates: (limit, pose) pairs, pose None = B.PLACE_NO_POSE; d_poses: the device address of [.][12] float64 (or a device
+        tensor), 0 = no position test."""
+        ptr = d_desc.data_ptr() if hasattr(d_desc, "data_ptr") else int(d_desc)
+        pp = d_poses.data_ptr() if hasattr(d_poses, "data_ptr") else int(d_poses or 0)
+        g = (B.PlaceGate * max(len(gates), 1))(*[B.PlaceGate(int(lim), B.PLACE_NO_POSE if pose is None else int(pose)) for lim, pose in gates])
+        res = (B.PlaceMatch * max(len(gates) * int(k), 1))()
+        n_eligible = np.zeros(max(len(gates), 1), np.uint32)
+        B.check(self._fx._ctx, self._L.lfx_place_db_query_gated(
+            self._fx._ctx, self.handle, C.c_void_p(ptr or None), len(gates), g, C.c_void_p(pp or None), float(radius), int(k), res,
+            n_eligible.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(int(stream))), self._L)
+        return res, n_eligible[:len(gates)]
+
+    def query_gated(self, d_desc, gates, d_poses=0, radius=float("inf"), k=1, stream=0):
+        """The k best ELIGIBLE entries for each query: entry e is eligible for query q iff e < gates[q][0] and, where d_poses is
+        given and gates[q][1] is not None, the translation of d_poses[e] lies within `radius` of that of d_poses[gates[q][1]].
+        Returns (a list per query of k dicts as query gives them, n_eligible per query).  Synchronous."""
+        res, n_eligible = self.query_gated_raw(d_desc, gates, d_poses, radius, k, stream)
+        k = int(k)
+        return [[_match(m) for m in res[q * k:(q + 1) * k]] for q in range(len(gates))], [int(n) for n in n_eligible]
 
     def close(self):
         if self.handle:
@@ -1344,6 +1370,11 @@ class PlaceDb:
             self.close()
         except Exception:
             pass
+
+
+def _match(m):
+    """lfx_place_match as a dict (entry None: the empty match)"""
+    return dict(entry=None if m.entry == B.PLACE_NO_ENTRY else int(m.entry), shift=int(m.shift), distance=float(m.distance), yaw=float(m.yaw))
 
 
 def pose_graph_config(config=None, **fields):
@@ -1641,6 +1672,127 @@ class Keyframes:
     def close(self):
         if self.handle:
             self._L.lfx_keyframes_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def loop_closer_config(config=None, **fields):
+    """lfx_loop_closer_config: the defaults (lfx_loop_closer_default_config) with the given fields replaced.  config: None, a
+    dict of fields, or a B.LoopCloserConfig (copied).  submap_capacity: one number or (edge, surface)."""
+    cfg = B.LoopCloserConfig()
+    if isinstance(config, B.LoopCloserConfig):
+        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        config = None
+    else:
+        B.load().lfx_loop_closer_default_config(C.byref(cfg))
+    for k, v in dict(config or {}, **fields).items():
+        if k not in dict(B.LoopCloserConfig._fields_):
+            raise TypeError("unknown loop-closer setting %r" % k)
+        if k == "submap_capacity":
+            v = (v, v) if np.isscalar(v) else tuple(v)
+            cfg.submap_capacity[0], cfg.submap_capacity[1] = int(v[0]), int(v[1])
+        else:
+            setattr(cfg, k, v)
+    return cfg
+
+
+class LoopCloser:
+    """lfx_loop_closer: revisits found in a PlaceDb, verified against submaps of a Keyframes store and closed in a PoseGraph
+    (include/lfx.h, the loop closer section).  Keyframe id == place entry == graph node id.  The three outlive the closer."""
+
+    REASONS = ("accepted", "no_candidate", "empty_query", "empty_submap", "align_failed", "no_report", "rank", "degenerate", "rms_edge",
+               "rms_surface", "inliers", "sigma2")
+
+    def __init__(self, fx, keyframes, place_db, graph, config=None, **fields):
+        self._fx = fx
+        self._L = fx._L
+        self.config = loop_closer_config(config, **fields)
+        self.keyframes, self.place_db, self.graph = keyframes, place_db, graph
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_loop_closer_create(fx._ctx, C.byref(self.config), keyframes.handle, place_db.handle, graph.handle, C.byref(h)),
+                self._L)
+        self.handle = h
+
+    def _check(self, rc):
+        B.check(self._fx._ctx, rc, self._L)
+
+    def info(self):
+        i = B.LoopCloserInfo()
+        self._check(self._L.lfx_loop_closer_info(self.handle, C.byref(i)))
+        return dict(device_bytes=int(i.device_bytes))
+
+    def detect_raw(self, first, count, stream=0):
+        """lfx_loop_closer_detect as it returns: (a B.PlaceMatch array [count * n_candidates], n_eligible uint32 [count])."""
+        k = int(self.config.n_candidates)
+        res = (B.PlaceMatch * max(int(count) * k, 1))()
+        n_eligible = np.zeros(max(int(count), 1), np.uint32)
+        self._check(self._L.lfx_loop_closer_detect(self._fx._ctx, self.handle, int(first), int(count), res,
+                                                   n_eligible.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(int(stream))))
+        return res, n_eligible[:max(int(count), 0)]
+
+    def detect(self, first, count, stream=0):
+        """The candidates of keyframes first .. first + count - 1: (a list per keyframe of n_candidates match dicts, best first,
+        entry None where none is left; n_eligible per keyframe)."""
+        res, n_eligible = self.detect_raw(first, count, stream)
+        k = int(self.config.n_candidates)
+        return [[_match(m) for m in res[q * k:(q + 1) * k]] for q in range(int(count))], [int(n) for n in n_eligible]
+
+    @staticmethod
+    def _candidate(candidate):
+        if isinstance(candidate, B.PlaceMatch):
+            return candidate
+        entry = B.PLACE_NO_ENTRY if candidate["entry"] is None else int(candidate["entry"])
+        return B.PlaceMatch(entry, int(candidate.get("shift", 0)), float(candidate.get("distance", 0.0)), float(candidate["yaw"]))
+
+    def verify_raw(self, query_id, candidate, stream=0):
+        """lfx_loop_closer_verify as it returns: a B.LoopClosure.  candidate: a B.PlaceMatch or a match dict."""
+        out = B.LoopClosure()
+        m = self._candidate(candidate)
+        self._check(self._L.lfx_loop_closer_verify(self._fx._ctx, self.handle, int(query_id), C.byref(m), C.byref(out), C.c_void_p(int(stream))))
+        return out
+
+    def closure(self, c):
+        """A B.LoopClosure as a dict: query, candidate, accepted, reason (a name of REASONS), match, result, report, submap (a
+        pair of dicts), edge (a B.POSE_GRAPH_EDGE_DTYPE record), raw (the record's bytes)."""
+        edge = np.frombuffer(bytes(c.edge), B.POSE_GRAPH_EDGE_DTYPE)[0]
+        sub = [dict(n_selected=int(r.n_selected), n_written_keyframes=int(r.n_written_keyframes), n_points=int(r.n_points),
+                    first_id=None if r.first_id == B.KEYFRAMES_NO_ID else int(r.first_id),
+                    last_id=None if r.last_id == B.KEYFRAMES_NO_ID else int(r.last_id), truncated=bool(r.truncated)) for r in c.submap]
+        return dict(query=int(c.query), candidate=None if c.candidate == B.PLACE_NO_ENTRY else int(c.candidate), accepted=bool(c.accepted),
+                    reason=self.REASONS[c.reason], match=_match(c.match), result=self._fx._align_results([c.result])[0],
+                    report=self._fx._align_reports([c.report])[0], submap=sub, edge=edge, raw=bytes(c))
+
+    def verify(self, query_id, candidate, stream=0):
+        return self.closure(self.verify_raw(query_id, candidate, stream))
+
+    def update_raw(self, first, count, stream=0):
+        """lfx_loop_closer_update as it returns: (rc, a B.LoopClosure array [count], a B.LoopCloserResult) -- rc so that a
+        caller can look at the closures of a call that ended with B.ERR_CAPACITY."""
+        closures = (B.LoopClosure * max(int(count), 1))()
+        result = B.LoopCloserResult()
+        rc = self._L.lfx_loop_closer_update(self._fx._ctx, self.handle, int(first), int(count), closures, C.byref(result), C.c_void_p(int(stream)))
+        return rc, closures, result
+
+    def update(self, first, count, stream=0):
+        """Detect, verify, add the accepted edges, optimise, make the store follow: (a closure dict per keyframe, a dict of
+        n_detected, n_verified, n_accepted, followed and graph -- PoseGraph.optimize's dict, None where it did not run)."""
+        rc, closures, r = self.update_raw(first, count, stream)
+        self._check(rc)
+        g = r.graph
+        graph = dict(code=int(g.code), iterations=int(g.iterations), chi2_initial=float(g.chi2_initial), chi2_final=float(g.chi2_final),
+                     max_step=float(g.max_step), n_chain=int(g.n_chain), n_loop=int(g.n_loop),
+                     n_robust_downweighted=int(g.n_robust_downweighted)) if r.n_accepted else None
+        return ([self.closure(c) for c in closures[:int(count)]],
+                dict(n_detected=int(r.n_detected), n_verified=int(r.n_verified), n_accepted=int(r.n_accepted), followed=bool(r.followed), graph=graph))
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_loop_closer_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
