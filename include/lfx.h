@@ -1177,7 +1177,8 @@ int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t e
 /* --- pose graph: past poses corrected by loop closures, optimised on the device ------------------------------------------ */
 /* The problem.  NODE k: a pose [R | t], 12 doubles row-major.  Its increment is delta = (a, b), ordered as
  * lfx_align_report.information orders it: R <- R Exp(a), t <- t + b -- the rotation first and in the node's own frame, the
- * translation in the world frame.  Node 0 is always fixed; others may be flagged fixed (lfx_pose_graph_set_fixed).
+ * translation in the world frame.  Node 0 is fixed unless lfx_pose_graph_release_first frees it (PRIORS, below); others may
+ * be flagged fixed (lfx_pose_graph_set_fixed).
  * EDGE (i, j, Z = [R_Z | t_Z], Omega 6 x 6 row-major symmetric positive definite, flags): Z measures T_i^-1 T_j.  Its residual
  * r = (phi, t_E):
  *   R_E = R_Z^T R_i^T R_j,  d = R_i^T (t_j - t_i),  t_E = R_Z^T (d - t_Z),  phi = Log(R_E)
@@ -1196,7 +1197,7 @@ int lfx_pack_features_segmented(lfx_ctx *ctx, const uint8_t *d_class, uint32_t e
  * or is not a number, the initial poses are restored: LFX_POSE_GRAPH_DIVERGED.  Rotations stay
  * orthonormal, |R^T R - I| <= 1e-12 after any number of iterations: every step re-orthonormalises the rotation it moved,
  * R <- R (3 I - R^T R) / 2 (one step of the polar iteration; no quaternion is kept).  A node whose increment is exactly 0
- * (no edge touches it) is not moved: its pose stays as it is, byte for byte.
+ * (no edge and no prior touches it) is not moved: its pose stays as it is, byte for byte.
  * THE SOLVER: the chain is the first edge with j == i + 1 for each i; every other edge is a loop edge --
  * backward edges, duplicates and edges between distant nodes among them.  P = lambda I + the chain edges' blocks is block-
  * tridiagonal in node order (a fixed node has the identity and no coupling); with J the loop edges' rows H = P + J^T W J, and
@@ -1249,14 +1250,16 @@ int lfx_pose_graph_info(const lfx_pose_graph *graph, lfx_pose_graph_info_t *info
 /* n poses on the host ([n][12]) appended as nodes; *first_id (may be NULL) = the id of the first.  A pose that is not finite is
  * LFX_ERR_INVALID_ARGUMENT, more nodes than max_nodes LFX_ERR_CAPACITY: nothing changed, nothing queued. */
 int lfx_pose_graph_add_nodes(lfx_ctx *ctx, lfx_pose_graph *graph, const double *poses, uint32_t n, uint32_t *first_id, void *stream);
-/* Node `node` held where it is (fixed != 0) or free again.  Node 0 stays fixed whatever is asked. */
+/* Node `node` held where it is (fixed != 0) or free again.  Node 0 stays fixed whatever is asked, unless
+ * lfx_pose_graph_release_first released it: then it is held or free as asked here. */
 int lfx_pose_graph_set_fixed(lfx_ctx *ctx, lfx_pose_graph *graph, uint32_t node, int fixed, void *stream);
 /* n edges on the host appended.  Checked before anything is touched: i == j, an id that is not a node, flags beyond
  * LFX_EDGE_ROBUST, Z or Omega not finite, Omega not symmetric are LFX_ERR_INVALID_ARGUMENT; more edges than max_edges, or more
  * loop edges than max_loop_edges, LFX_ERR_CAPACITY. */
 int lfx_pose_graph_add_edges(lfx_ctx *ctx, lfx_pose_graph *graph, const lfx_pose_graph_edge *edges, uint32_t n, void *stream);
 /* Gauss-Newton to the config's tolerance; synchronous (the host reads one small record per iteration).  Returns LFX_OK
- * whenever the optimiser ran, whatever result->code says; a graph without edges is LFX_ERR_INVALID_ARGUMENT.  Ordered behind
+ * whenever the optimiser ran, whatever result->code says; a graph with neither edges nor priors is LFX_ERR_INVALID_ARGUMENT
+ * (priors alone are enough).  Ordered behind
  * every earlier call on this graph, whichever streams they used. */
 int lfx_pose_graph_optimize(lfx_ctx *ctx, lfx_pose_graph *graph, lfx_pose_graph_result *result, void *stream);
 /* Nodes first .. first + count - 1 copied to the host ([count][12]); synchronous. */
@@ -1277,6 +1280,58 @@ int lfx_pose_graph_edge_chi2(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t
  * residual coordinates: Omega = B H B^T, B = blkdiag(I, R_j^T), pose_j the scan's pose the report was made at.  Host only;
  * every sum of three terms is (a0 b0 + a1 b1) + a2 b2.  out may be report_information. */
 int lfx_pose_graph_edge_information(const double pose_j[12], const double report_information[36], double out[36]);
+
+/* PRIORS: unary terms, each on one node -- an absolute fix (GNSS, a surveyed marker, a pose from lfx_localize_batch against an
+ * older map).  A prior adds A^T w Omega A to its node's diagonal block of P and A^T w Omega r to its gradient, nothing else:
+ * the chain factor, the chain solve, S and the step are as above, the cost is O(priors) and does not grow with the loop edges.
+ * POSE PRIOR (Z = [R_Z | t_Z], Omega 6 x 6): Z measures T_node.  By definition the edge (i, node, Z, Omega) with T_i the
+ * identity, through the same device routine as an edge's r and A_j:
+ *   R_E = R_Z^T R_k,  t_E = R_Z^T (t_k - t_Z),  phi = Log(R_E),  r = (phi, t_E),  A = [[Jri, 0], [0, R_Z^T]]
+ * POSITION PRIOR (LFX_PRIOR_POSITION; t_Z, Omega_t 3 x 3 symmetric positive semi-definite, lever l): t_Z measures the world
+ * position of the point l of the node's frame (an antenna metres from the lidar; with l != 0, positions alone make the heading
+ * observable):
+ *   r = (0, 0, 0, t_k + R_k l - t_Z)  in the world frame,  A = [[0, 0], [-R_k [l]x, I]]
+ * every sum of three terms (a0 b0 + a1 b1) + a2 b2.  Omega_t is the lower right 3 x 3 of `information`.
+ * COST AND WEIGHTS as an edge's: rho = r^T Omega r; with LFX_PRIOR_ROBUST Huber on s = sqrt(r^T Omega r) with the config's
+ * huber_delta, Omega entering as w Omega.  chi2_initial and chi2_final are the sum over edges and priors.  A prior on a fixed
+ * node counts in chi^2 and in nothing else.  A prior whose Omega is indefinite shows as a chain pivot that is not positive:
+ * LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE, the poses untouched.  A node that no edge touches but a prior does moves to its prior.
+ * lfx_pose_graph_result and lfx_pose_graph_info_t do not know priors: n_robust_downweighted counts edges only
+ * (lfx_pose_graph_prior_info has the priors').  A graph without priors computes, byte for byte, what it computed before priors
+ * existed; a graph with priors gives the same bytes however its priors and edges were split and interleaved over calls. */
+#define LFX_PRIOR_ROBUST   1u   /* Huber with the graph's huber_delta, as LFX_EDGE_ROBUST */
+#define LFX_PRIOR_POSITION 2u   /* a position fix; without it a full pose */
+typedef struct lfx_pose_graph_prior {
+  uint32_t node, flags;
+  double z[12];              /* pose: Z = [R_Z | t_Z] measures T_node.  position: only t_Z (z[3], z[7], z[11]) is read */
+  double information[36];    /* pose: Omega 6 x 6, checked as an edge's.  position: its lower right 3 x 3, the rest must be 0 */
+  double lever[3];           /* position: the antenna in the node's frame; pose: must be 0 */
+} lfx_pose_graph_prior;      /* 416 bytes */
+typedef struct lfx_pose_graph_prior_info_t {
+  uint32_t n_priors, max_priors;   /* added so far; reserved by lfx_pose_graph_reserve_priors (0: nothing reserved) */
+  uint32_t n_downweighted;         /* priors with w < 1 at the poses the last lfx_pose_graph_optimize left */
+  uint32_t reserved;               /* 0 */
+  double chi2;                     /* the priors' share of that optimise's chi2_final */
+} lfx_pose_graph_prior_info_t;
+/* Room for max_priors priors: the priors, their linearisation and the per-node lists.  Called once, before the first prior.
+ * lfx_pose_graph_config cannot grow (lfx_loop_closer_result embeds the graph's structs), so the capacity comes through this
+ * call: the one exception to "no later call allocates"; lfx_pose_graph_info's device_bytes grows by what was allocated.  A
+ * second call, or max_priors == 0, is LFX_ERR_INVALID_ARGUMENT; a failed allocation LFX_ERR_OUT_OF_MEMORY, the graph as it was. */
+int lfx_pose_graph_reserve_priors(lfx_ctx *ctx, lfx_pose_graph *graph, uint32_t max_priors);
+/* n priors on the host appended.  Checked before anything is touched: a node that is not in the graph, unknown flags, a value
+ * that is not finite, Omega not symmetric (an edge's rule: 1e-9 of its largest entry), a position prior with information outside
+ * its block, a pose prior with a lever are LFX_ERR_INVALID_ARGUMENT; more priors than reserved LFX_ERR_CAPACITY (nothing
+ * reserved: a capacity of 0). */
+int lfx_pose_graph_add_priors(lfx_ctx *ctx, lfx_pose_graph *graph, const lfx_pose_graph_prior *priors, uint32_t n, void *stream);
+/* released != 0: node 0 is free from now on, unless lfx_pose_graph_set_fixed(0, 1) says otherwise; released == 0: fixed again
+ * whatever is asked.  A graph that never calls this behaves as described above, set_fixed(0, 0) included.  A free first node
+ * lets measurements turn and shift the trajectory as a whole; without a prior (or a loop to a fixed node) nothing but lambda
+ * holds it, and what the optimiser then returns is the caller's affair. */
+int lfx_pose_graph_release_first(lfx_ctx *ctx, lfx_pose_graph *graph, int released, void *stream);
+/* Per prior, as lfx_pose_graph_edge_chi2 per edge, with the same refusals (before the first optimise; after nodes, edges,
+ * priors or poses were written since).  An outlier fix under LFX_PRIOR_ROBUST shows as the smallest w. */
+int lfx_pose_graph_prior_chi2(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t first, uint32_t count, double *rho, double *w, void *stream);
+int lfx_pose_graph_prior_info(const lfx_pose_graph *graph, lfx_pose_graph_prior_info_t *info);
 
 /* --- the keyframe store: sensor-frame clouds on the device, world maps written from them at the poses of the moment ------ */
 /* What lets a map follow a pose graph.  lfx_mapper and lfx_odometry keep their clouds already in the world, so a corrected

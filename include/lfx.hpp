@@ -792,8 +792,10 @@ private:
 };
 
 // The pose graph (lfx_pose_graph): keyframe poses as nodes, odometry steps and loop closures as edges, optimised on the
-// device of `fx`, which must outlive it.  Poses are 12 doubles [R | t] row-major; node 0 is fixed.  An edge's information
-// comes from an alignment report through EdgeInformation, its measurement from lfx_motion_between.
+// device of `fx`, which must outlive it.  Poses are 12 doubles [R | t] row-major; node 0 is fixed unless ReleaseFirst frees
+// it.  An edge's information comes from an alignment report through EdgeInformation, its measurement from
+// lfx_motion_between.  Absolute fixes of single nodes (GNSS positions with a lever arm, poses against an older map) are
+// priors: ReservePriors once, then AddPriors.
 class PoseGraph
 {
 public:
@@ -871,6 +873,28 @@ public:
   {
     lfx_pose_graph_info_t i;
     lfx_pose_graph_info(graph_, &i);
+    return i;
+  }
+  // priors (absolute fixes of single nodes): room for max_priors of them, once, before the first
+  void ReservePriors(std::uint32_t max_priors) {Check(lfx_pose_graph_reserve_priors(fx_.handle(), graph_, max_priors));}
+  void AddPriors(const std::vector<lfx_pose_graph_prior> & priors, void * stream = nullptr)
+  {
+    Check(lfx_pose_graph_add_priors(fx_.handle(), graph_, priors.data(), static_cast<std::uint32_t>(priors.size()), stream));
+  }
+  // node 0 free from now on (SetFixed(0) still holds it); without a prior nothing but the damping holds a free first node
+  void ReleaseFirst(bool released = true, void * stream = nullptr) {Check(lfx_pose_graph_release_first(fx_.handle(), graph_, released ? 1 : 0, stream));}
+  // per prior rho and w at the poses the last Optimize left
+  void PriorChi2(std::vector<double> & rho, std::vector<double> & w, void * stream = nullptr) const
+  {
+    const std::uint32_t n = PriorInfo().n_priors;
+    rho.resize(n);
+    w.resize(n);
+    Check(lfx_pose_graph_prior_chi2(fx_.handle(), graph_, 0, n, rho.data(), w.data(), stream));
+  }
+  lfx_pose_graph_prior_info_t PriorInfo() const
+  {
+    lfx_pose_graph_prior_info_t i;
+    lfx_pose_graph_prior_info(graph_, &i);
     return i;
   }
   lfx_pose_graph * handle() const {return graph_;}

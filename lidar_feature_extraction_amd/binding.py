@@ -226,6 +226,22 @@ POSE_GRAPH_EDGE_DTYPE = [("i", "<u4"), ("j", "<u4"), ("flags", "<u4"), ("reserve
 """lfx_pose_graph_edge as a numpy record (400 bytes)."""
 
 
+class PoseGraphPrior(C.Structure):
+    """lfx_pose_graph_prior: an absolute fix of one node, a full pose or (PRIOR_POSITION) a position with a lever arm."""
+    _fields_ = [("node", C.c_uint32), ("flags", C.c_uint32), ("z", C.c_double * 12), ("information", C.c_double * 36),
+                ("lever", C.c_double * 3)]
+
+
+class PoseGraphPriorInfo(C.Structure):
+    _fields_ = [("n_priors", C.c_uint32), ("max_priors", C.c_uint32), ("n_downweighted", C.c_uint32), ("reserved", C.c_uint32),
+                ("chi2", C.c_double)]
+
+
+PRIOR_ROBUST, PRIOR_POSITION = 1, 2
+POSE_GRAPH_PRIOR_DTYPE = [("node", "<u4"), ("flags", "<u4"), ("z", "<f8", 12), ("information", "<f8", 36), ("lever", "<f8", 3)]
+"""lfx_pose_graph_prior as a numpy record (416 bytes)."""
+
+
 class KeyframesConfig(C.Structure):
     """lfx_keyframes_config: the capacities a keyframe store is allocated for ([0] edge, [1] surface records)."""
     _fields_ = [("max_keyframes", C.c_uint32), ("reserved", C.c_uint32), ("max_points", C.c_uint64 * 2)]
@@ -331,6 +347,8 @@ EXPORTS = [
     "lfx_pose_graph_default_config", "lfx_pose_graph_create", "lfx_pose_graph_destroy", "lfx_pose_graph_info", "lfx_pose_graph_add_nodes",
     "lfx_pose_graph_set_fixed", "lfx_pose_graph_add_edges", "lfx_pose_graph_optimize", "lfx_pose_graph_poses", "lfx_pose_graph_set_poses",
     "lfx_pose_graph_view", "lfx_pose_graph_edge_chi2", "lfx_pose_graph_edge_information",
+    "lfx_pose_graph_reserve_priors", "lfx_pose_graph_add_priors", "lfx_pose_graph_release_first", "lfx_pose_graph_prior_chi2",
+    "lfx_pose_graph_prior_info",
     "lfx_keyframes_default_config", "lfx_keyframes_create", "lfx_keyframes_destroy", "lfx_keyframes_info", "lfx_keyframes_view",
     "lfx_keyframes_add", "lfx_keyframes_add_host", "lfx_keyframes_set_poses", "lfx_keyframes_poses", "lfx_keyframes_follow",
     "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save",
@@ -520,6 +538,11 @@ def load(test_hooks=False):
     L.lfx_pose_graph_view.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(u32), vp]
     L.lfx_pose_graph_edge_chi2.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.lfx_pose_graph_edge_information.argtypes = [vp, vp, vp]
+    L.lfx_pose_graph_reserve_priors.argtypes = [vp, vp, u32]
+    L.lfx_pose_graph_add_priors.argtypes = [vp, vp, vp, u32, vp]
+    L.lfx_pose_graph_release_first.argtypes = [vp, vp, i32, vp]
+    L.lfx_pose_graph_prior_chi2.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.lfx_pose_graph_prior_info.argtypes = [vp, C.POINTER(PoseGraphPriorInfo)]
     pkf, pkc = C.POINTER(KeyframesConfig), C.POINTER(KeyframesClouds)
     L.lfx_keyframes_default_config.argtypes = [pkf]
     L.lfx_keyframes_default_config.restype = None

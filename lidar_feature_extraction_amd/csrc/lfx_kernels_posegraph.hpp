@@ -5,9 +5,13 @@
 //   y0 = P^-1 (-g),  Y = P^-1 Jt^T,  S = I + Jt Y,  delta = y0 - Y S^-1 (Jt y0)
 // which is the step of S = W^-1 + J Y (lfx.h) with both sides of S multiplied by sqrt(w) C^T: S has no eigenvalue below 1.
 //
+// Priors (unary terms: lfx.h, PRIORS) touch P's diagonal blocks and the gradient only: a kernel of their own linearises them,
+// the per-node assembly walks a node's priors after its edges, the reduction passes over them after the edges.  Every loop
+// over priors runs zero times for a graph without them, which therefore computes, byte for byte, what it always did.
+//
 // No floating-point atomic anywhere: every sum has a fixed order (an edge's sums are one thread's, a node's gradient walks
-// the node's incidence list in edge order, the reductions are a strided pass per thread and a tree), so the same inputs give
-// the same bytes.  A pivot that is not positive sets the status word; every kernel but the linearisation and the reduction returns at
+// the node's incidence list in edge order and then its priors in prior order, the reductions are a strided pass per thread
+// and a tree), so the same inputs give the same bytes.  A pivot that is not positive sets the status word; every kernel but the linearisation and the reduction returns at
 // once when it is set.  Built with contraction off, as the rest of the library.
 #pragma once
 
@@ -21,8 +25,11 @@ constexpr int kPgWave = 64;              // the chain kernels and the per-node a
 constexpr int kPgPanel = 48;             // panel width of the S factor (8 loop edges)
 constexpr int kPgTile = 16;              // the trailing update's tile
 constexpr int kPgLin = 88;               // doubles of an edge's linearisation: r[6], q[6] = w Omega r, w, rho, 2 spare, A_i[36], A_j[36]
+constexpr int kPgPlin = 52;              // doubles of a prior's linearisation: r[6], q[6] = w Omega r, w, rho, 2 spare, A[36]
 constexpr uint32_t kPgNone = 0xFFFFFFFFu;
 constexpr uint32_t kPgEdgeRobust = 1u;   // LFX_EDGE_ROBUST
+constexpr uint32_t kPgPriorRobust = 1u;  // LFX_PRIOR_ROBUST
+constexpr uint32_t kPgPriorPosition = 2u;  // LFX_PRIOR_POSITION
 enum PgStatus : uint32_t {kPgOk = 0, kPgChainPivot = 1, kPgLoopInformation = 2, kPgLoopPivot = 3};
 
 struct PgEdge                            // lfx_pose_graph_edge as the device holds it (400 bytes)
@@ -31,10 +38,19 @@ struct PgEdge                            // lfx_pose_graph_edge as the device ho
   double z[12];
   double omega[36];
 };
+struct PgPrior                           // lfx_pose_graph_prior as the caller wrote it (416 bytes)
+{
+  uint32_t node, flags;
+  double z[12];
+  double omega[36];                      // a position prior's block in the lower right, zeros outside it
+  double lever[3];
+};
 struct PgRecord                          // what the host reads once per iteration
 {
   double chi2, max_step;
   uint32_t status, n_down;
+  double chi2_prior;                     // the priors' share of chi2
+  uint32_t n_down_prior, spare;
 };
 
 struct PgArgs
@@ -58,6 +74,10 @@ struct PgArgs
   PgRecord * record;
   uint32_t n_nodes, n_edges, n_loop, ldy;
   double huber_delta, damping;
+  const PgPrior * priors;                // [P]
+  double * plin;                         // [P][kPgPlin]
+  const uint32_t * prior_begin, * prior_inc;   // node k's priors prior_inc[prior_begin[k] .. prior_begin[k + 1]), in prior order
+  uint32_t n_priors;
 };
 
 // ---------------------------------------------------------------------------------------------- small fixed-size arithmetic
@@ -94,20 +114,14 @@ __device__ inline bool pg_chol6(double * a)
 }
 
 // ---------------------------------------------------------------------------------------------- 1. linearise
-// One thread per edge: r, w, rho, q = w Omega r, A_i, A_j (lfx.h states them); a loop edge also gets its whitened rows.
-// Not gated on the status word, which this kernel itself may set (a loop edge's information without a Cholesky factor): every
-// edge's values are written whatever another workgroup found, so chi^2 and lfx_pose_graph_edge_chi2 never depend on the order
-// the workgroups ran in.
-__global__ __launch_bounds__(kPgWave) void pose_graph_linearize_kernel(PgArgs a)
+// An edge's r = (phi, t_E) and its Jacobians A_i, A_j at the poses pi, pj ([R | t], 12 doubles each) under the measurement z.
+// The one routine of every relative-pose term: an edge passes its two nodes, a pose prior the identity and its node.
+__device__ inline void pg_edge_terms(const double * pi, const double * pj, const double * z, double * res, double * Ai, double * Aj)
 {
-  const uint32_t e = blockIdx.x * kPgWave + threadIdx.x;
-  if (e >= a.n_edges) {return;}
-  const PgEdge & ed = a.edges[e];
-  const double * pi = a.poses + 12 * (size_t)ed.i, * pj = a.poses + 12 * (size_t)ed.j;
   double Ri[9], Rj[9], Rz[9], ti[3], tj[3], tz[3];
   for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) {Ri[3 * r + c] = pi[4 * r + c]; Rj[3 * r + c] = pj[4 * r + c]; Rz[3 * r + c] = ed.z[4 * r + c];}
-    ti[r] = pi[4 * r + 3]; tj[r] = pj[4 * r + 3]; tz[r] = ed.z[4 * r + 3];
+    for (int c = 0; c < 3; c++) {Ri[3 * r + c] = pi[4 * r + c]; Rj[3 * r + c] = pj[4 * r + c]; Rz[3 * r + c] = z[4 * r + c];}
+    ti[r] = pi[4 * r + 3]; tj[r] = pj[4 * r + 3]; tz[r] = z[4 * r + 3];
   }
   double M[9], RE[9], RzRi[9], d[3], tE[3];
   pg_tmul3(Ri, Rj, M);                 // R_i^T R_j
@@ -137,7 +151,6 @@ __global__ __launch_bounds__(kPgWave) void pose_graph_linearize_kernel(PgArgs a)
       Jri[3 * r + c] = ((r == c ? 1.0 : 0.0) + 0.5 * px[3 * r + c]) + cc * p2;
     }
   }
-  double Ai[36], Aj[36];
   for (int k = 0; k < 36; k++) {Ai[k] = 0.0; Aj[k] = 0.0;}
   const double dx[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
   for (int r = 0; r < 3; r++) {
@@ -150,22 +163,42 @@ __global__ __launch_bounds__(kPgWave) void pose_graph_linearize_kernel(PgArgs a)
       Ai[6 * (3 + r) + 3 + c] = -RzRi[3 * r + c];
     }
   }
-  const double res[6] = {phi[0], phi[1], phi[2], tE[0], tE[1], tE[2]};
-  double q[6], s2 = 0.0;
+  for (int r = 0; r < 3; r++) {res[r] = phi[r]; res[3 + r] = tE[r];}
+}
+
+// q = Omega r, rho = r^T Omega r and w = 1, or Huber's where `robust` and s = sqrt(r^T Omega r) lies beyond huber_delta:
+// the cost and the weight of every term, edge or prior.  q comes back unweighted.
+__device__ inline void pg_weigh(const double * omega, const double * res, bool robust, double huber_delta, double * q, double & w, double & rho)
+{
+  double s2 = 0.0;
   for (int r = 0; r < 6; r++) {
     double acc = 0.0;
-    for (int c = 0; c < 6; c++) {acc += ed.omega[6 * r + c] * res[c];}
+    for (int c = 0; c < 6; c++) {acc += omega[6 * r + c] * res[c];}
     q[r] = acc;
   }
   for (int r = 0; r < 6; r++) {s2 += res[r] * q[r];}
-  double w = 1.0, rho = s2;
-  if (ed.flags & kPgEdgeRobust) {
+  w = 1.0; rho = s2;
+  if (robust) {
     const double s = sqrt(s2 > 0.0 ? s2 : 0.0);
-    if (s > a.huber_delta) {
-      w = a.huber_delta / s;
-      rho = 2.0 * a.huber_delta * s - a.huber_delta * a.huber_delta;
+    if (s > huber_delta) {
+      w = huber_delta / s;
+      rho = 2.0 * huber_delta * s - huber_delta * huber_delta;
     }
   }
+}
+
+// One thread per edge: r, w, rho, q = w Omega r, A_i, A_j (lfx.h states them); a loop edge also gets its whitened rows.
+// Not gated on the status word, which this kernel itself may set (a loop edge's information without a Cholesky factor): every
+// edge's values are written whatever another workgroup found, so chi^2 and lfx_pose_graph_edge_chi2 never depend on the order
+// the workgroups ran in.
+__global__ __launch_bounds__(kPgWave) void pose_graph_linearize_kernel(PgArgs a)
+{
+  const uint32_t e = blockIdx.x * kPgWave + threadIdx.x;
+  if (e >= a.n_edges) {return;}
+  const PgEdge & ed = a.edges[e];
+  double res[6], Ai[36], Aj[36], q[6], w, rho;
+  pg_edge_terms(a.poses + 12 * (size_t)ed.i, a.poses + 12 * (size_t)ed.j, ed.z, res, Ai, Aj);
+  pg_weigh(ed.omega, res, (ed.flags & kPgEdgeRobust) != 0u, a.huber_delta, q, w, rho);
   double * out = a.lin + (size_t)kPgLin * e;
   for (int r = 0; r < 6; r++) {out[r] = res[r]; out[6 + r] = w * q[r];}
   out[12] = w; out[13] = rho; out[14] = 0.0; out[15] = 0.0;
@@ -187,6 +220,40 @@ __global__ __launch_bounds__(kPgWave) void pose_graph_linearize_kernel(PgArgs a)
       }
     }
   }
+}
+
+// One thread per prior: r, q = w Omega r, w, rho and A, the Jacobian by the node's increment (lfx.h states both kinds).
+// A pose prior is the edge from the identity to its node, through pg_edge_terms; a position prior is written out here.  Not
+// gated on the status word, as the edges' kernel: chi^2 and lfx_pose_graph_prior_chi2 hold whatever else was found.
+__global__ __launch_bounds__(kPgWave) void pose_graph_prior_kernel(PgArgs a)
+{
+  const uint32_t p = blockIdx.x * kPgWave + threadIdx.x;
+  if (p >= a.n_priors) {return;}
+  const PgPrior & pr = a.priors[p];
+  const double * pk = a.poses + 12 * (size_t)pr.node;
+  double res[6], A[36], q[6], w, rho;
+  if (pr.flags & kPgPriorPosition) {
+    const double l[3] = {pr.lever[0], pr.lever[1], pr.lever[2]};
+    const double lx[9] = {0.0, -l[2], l[1], l[2], 0.0, -l[0], -l[1], l[0], 0.0};
+    for (int k = 0; k < 36; k++) {A[k] = 0.0;}
+    for (int r = 0; r < 3; r++) {
+      res[r] = 0.0;
+      res[3 + r] = (pk[4 * r + 3] + pg_dot3(pk[4 * r], l[0], pk[4 * r + 1], l[1], pk[4 * r + 2], l[2])) - pr.z[4 * r + 3];
+      for (int c = 0; c < 3; c++) {
+        A[6 * (3 + r) + c] = -pg_dot3(pk[4 * r], lx[c], pk[4 * r + 1], lx[3 + c], pk[4 * r + 2], lx[6 + c]);   // -R_k [l]x
+        A[6 * (3 + r) + 3 + c] = r == c ? 1.0 : 0.0;
+      }
+    }
+  } else {
+    const double identity[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    double Ai[36];
+    pg_edge_terms(identity, pk, pr.z, res, Ai, A);
+  }
+  pg_weigh(pr.omega, res, (pr.flags & kPgPriorRobust) != 0u, a.huber_delta, q, w, rho);
+  double * out = a.plin + (size_t)kPgPlin * p;
+  for (int r = 0; r < 6; r++) {out[r] = res[r]; out[6 + r] = w * q[r];}
+  out[12] = w; out[13] = rho; out[14] = 0.0; out[15] = 0.0;
+  for (int k = 0; k < 36; k++) {out[16 + k] = A[k];}
 }
 
 // One wave per node: lanes 0 .. 35 the entries (r, c) of P's blocks (k, k) and (k + 1, k), lanes 0 .. 5 the gradient.
@@ -223,6 +290,13 @@ __global__ __launch_bounds__(kPgWave) void pose_graph_node_kernel(PgArgs a)
         dd += pg_at_w_b(L + 16, a.edges[ce].omega, L[12], L + 16, r, c);
         if (!a.fixed[k + 1u]) {oo = pg_at_w_b(L + 52, a.edges[ce].omega, L[12], L + 16, r, c);}
       }
+      if (a.n_priors) {                                // the node's priors, in prior order: the diagonal block alone
+        for (uint32_t t = a.prior_begin[k]; t < a.prior_begin[k + 1u]; t++) {
+          const uint32_t p = a.prior_inc[t];
+          const double * L = a.plin + (size_t)kPgPlin * p;
+          dd += pg_at_w_b(L + 16, a.priors[p].omega, L[12], L + 16, r, c);
+        }
+      }
     }
     a.diag[(size_t)36 * k + lane] = dd;
     a.off[(size_t)36 * k + lane] = oo;
@@ -238,12 +312,21 @@ __global__ __launch_bounds__(kPgWave) void pose_graph_node_kernel(PgArgs a)
         for (int m = 0; m < 6; m++) {acc += A[6 * m + lane] * L[6 + m];}
         g += acc;
       }
+      if (a.n_priors) {
+        for (uint32_t t = a.prior_begin[k]; t < a.prior_begin[k + 1u]; t++) {
+          const double * L = a.plin + (size_t)kPgPlin * a.prior_inc[t];
+          double acc = 0.0;
+          for (int m = 0; m < 6; m++) {acc += L[16 + 6 * m + lane] * L[6 + m];}
+          g += acc;
+        }
+      }
     }
     a.grad[(size_t)6 * k + lane] = g;
   }
 }
 
-// chi^2, the largest step and the count of down-weighted edges: a strided pass per thread, then a tree, one workgroup.
+// chi^2 (edges, then priors), the largest step and the count of down-weighted edges: a strided pass per thread, then a tree,
+// one workgroup.  The priors' own share and count are reduced apart, by the same tree once more, where there are priors.
 // Always runs: it is what carries the status word to the host.
 __global__ __launch_bounds__(kPgThreads) void pose_graph_reduce_kernel(PgArgs a, uint32_t slot, int with_step)
 {
@@ -257,6 +340,15 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_reduce_kernel(PgArgs a,
     s += L[13];
     n += L[12] < 1.0 ? 1u : 0u;
   }
+  // ... then over the priors, into the same sum; their own share and their own count beside it
+  double sp = 0.0;
+  uint32_t np = 0;
+  for (uint32_t p = t; p < a.n_priors; p += kPgThreads) {
+    const double * L = a.plin + (size_t)kPgPlin * p;
+    s += L[13];
+    sp += L[13];
+    np += L[12] < 1.0 ? 1u : 0u;
+  }
   if (with_step) {
     for (uint32_t k = t; k < a.n_nodes; k += kPgThreads) {m = pg_max(m, a.step_max[k]);}
   }
@@ -266,9 +358,24 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_reduce_kernel(PgArgs a,
     if (t < h) {sum[t] += sum[t + h]; top[t] = pg_max(top[t], top[t + h]); cnt[t] += cnt[t + h];}
     __syncthreads();
   }
+  const double all = sum[0];
+  const uint32_t edges_down = cnt[0];
+  double share = 0.0;
+  uint32_t down = 0;
+  if (a.n_priors) {                                     // (uniform) the same tree once more, for the priors' own figures
+    __syncthreads();
+    sum[t] = sp; cnt[t] = np;
+    __syncthreads();
+    for (uint32_t h = kPgThreads / 2; h > 0; h >>= 1) {
+      if (t < h) {sum[t] += sum[t + h]; cnt[t] += cnt[t + h];}
+      __syncthreads();
+    }
+    share = sum[0]; down = cnt[0];
+  }
   if (t == 0) {
     PgRecord r;
-    r.chi2 = sum[0]; r.max_step = top[0]; r.status = *a.status; r.n_down = cnt[0];
+    r.chi2 = all; r.max_step = top[0]; r.status = *a.status; r.n_down = edges_down;
+    r.chi2_prior = share; r.n_down_prior = down; r.spare = 0u;
     a.record[slot] = r;
   }
 }

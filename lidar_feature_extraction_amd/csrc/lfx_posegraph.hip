@@ -1,7 +1,8 @@
 // lfx_posegraph.hip -- the pose graph (include/lfx.h, the pose graph section; lfx_kernels_posegraph.hpp): nodes and edges
 // kept on the device, Gauss-Newton over them with the chain-and-loop solver.  The host keeps what it needs to check a call
 // before anything is queued (the edges' ends, which nodes are fixed) and builds the node -> (edge, side) incidence lists,
-// stable by edge id, whenever edges were added.  Everything is allocated by lfx_pose_graph_create.
+// stable by edge id, whenever edges were added, and the node -> prior lists beside them.  Everything is allocated by
+// lfx_pose_graph_create, but the priors' four blocks: lfx_pose_graph_reserve_priors (the config's ABI is closed).
 #include "lfx_internal.hpp"
 #include "lfx_kernels_posegraph.hpp"
 
@@ -12,26 +13,36 @@ using namespace lfx_host;
 
 static_assert(sizeof(lfx::PgEdge) == sizeof(lfx_pose_graph_edge) && sizeof(lfx::PgEdge) == 400, "an edge goes up as the caller wrote it, but for one word");
 static_assert(lfx::kPgEdgeRobust == LFX_EDGE_ROBUST, "the kernels' flag is the header's");
+static_assert(sizeof(lfx_pose_graph_prior) == 416 && sizeof(lfx::PgPrior) == 416, "a prior goes up as the caller wrote it");
+static_assert(lfx::kPgPriorRobust == LFX_PRIOR_ROBUST && lfx::kPgPriorPosition == LFX_PRIOR_POSITION, "the kernels' flags are the header's");
 
 struct lfx_pose_graph
 {
   int device = 0;
   lfx_pose_graph_config cfg{};
   uint32_t n_nodes = 0, n_edges = 0, n_chain = 0, n_loop = 0, ldy_cap = 0;
+  uint32_t n_priors = 0, max_priors = 0;  // max_priors: what lfx_pose_graph_reserve_priors allocated (0: nothing yet)
+  uint32_t prior_down = 0;               // of the last optimise: the priors with w < 1 and their share of chi2_final
+  double prior_chi2 = 0.0;
+  bool released = false, first_fixed = false;   // lfx_pose_graph_release_first; what set_fixed(0, .) asked last
   uint64_t device_bytes = 0;
   // the host's copy of the topology
-  std::vector<uint32_t> edge_i, edge_j, edge_loop, chain_edge;
+  std::vector<uint32_t> edge_i, edge_j, edge_loop, chain_edge, prior_node;
   std::vector<uint8_t> fixed;
   bool topology_stale = true;            // edges or nodes were added since the lists went up
   bool linearised = false;               // lin holds the edges' values at the poses the last optimise left
   // what goes up: rewritten only once the graph's last queued call has passed
   std::vector<lfx::PgEdge> stage_edges;
-  std::vector<uint32_t> stage_lists;
+  std::vector<uint32_t> stage_lists, stage_prior_lists;
+  std::vector<lfx::PgPrior> stage_priors;
   mutable std::vector<double> stage_lin;
   DevBuf<double> poses, backup, lin, loop_j, grad, diag, off, fac_l, fac_m, y, s, z, step_max;
   DevBuf<uint8_t> d_fixed;
   DevBuf<lfx::PgEdge> edges;
   DevBuf<uint32_t> node_begin, inc, d_chain_edge, loop_edge, status;
+  DevBuf<lfx::PgPrior> priors;           // these four by lfx_pose_graph_reserve_priors
+  DevBuf<double> plin;
+  DevBuf<uint32_t> prior_begin, prior_inc;
   DevBuf<lfx::PgRecord> record;
   PinnedBuf h_record;
   PinnedBuf h_poses;                     // poses on their way up ([max_nodes][12]): pinned, so that the copy is queued and the call returns
@@ -92,6 +103,7 @@ lfx::PgArgs args_of(lfx_pose_graph * g)
   a.y = g->y.p; a.s = g->s.p; a.z = g->z.p; a.step_max = g->step_max.p; a.status = g->status.p; a.record = g->record.p;
   a.n_nodes = g->n_nodes; a.n_edges = g->n_edges; a.n_loop = g->n_loop; a.ldy = ldy_of(g->n_loop);
   a.huber_delta = g->cfg.huber_delta; a.damping = g->cfg.damping;
+  a.priors = g->priors.p; a.plin = g->plin.p; a.prior_begin = g->prior_begin.p; a.prior_inc = g->prior_inc.p; a.n_priors = g->n_priors;
   return a;
 }
 
@@ -114,9 +126,20 @@ int upload_topology(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
   }
   for (uint32_t k = 0; k < N; k++) {chain[k] = g->chain_edge[k];}
   LFX_HIP(c, hipMemcpyAsync(g->node_begin.p, begin, sizeof(uint32_t) * ((size_t)N + 1u), hipMemcpyHostToDevice, st));
-  LFX_HIP(c, hipMemcpyAsync(g->inc.p, inc, sizeof(uint32_t) * 2u * (size_t)E, hipMemcpyHostToDevice, st));
+  if (E) {LFX_HIP(c, hipMemcpyAsync(g->inc.p, inc, sizeof(uint32_t) * 2u * (size_t)E, hipMemcpyHostToDevice, st));}
   LFX_HIP(c, hipMemcpyAsync(g->d_chain_edge.p, chain, sizeof(uint32_t) * N, hipMemcpyHostToDevice, st));
   if (L) {LFX_HIP(c, hipMemcpyAsync(g->loop_edge.p, loops, sizeof(uint32_t) * L, hipMemcpyHostToDevice, st));}
+  if (const uint32_t P = g->n_priors) {           // prior_begin [N + 1], prior_inc [P]: every node's list in prior order
+    std::vector<uint32_t> & v = g->stage_prior_lists;
+    v.assign((size_t)N + 1u + P, 0u);
+    uint32_t * pb = v.data(), * pi = pb + N + 1u;
+    for (uint32_t p = 0; p < P; p++) {pb[g->prior_node[p] + 1u]++;}
+    for (uint32_t k = 0; k < N; k++) {pb[k + 1u] += pb[k];}
+    std::vector<uint32_t> pat(pb, pb + N);
+    for (uint32_t p = 0; p < P; p++) {pi[pat[g->prior_node[p]]++] = p;}
+    LFX_HIP(c, hipMemcpyAsync(g->prior_begin.p, pb, sizeof(uint32_t) * ((size_t)N + 1u), hipMemcpyHostToDevice, st));
+    LFX_HIP(c, hipMemcpyAsync(g->prior_inc.p, pi, sizeof(uint32_t) * P, hipMemcpyHostToDevice, st));
+  }
   g->topology_stale = false;
   return LFX_OK;
 }
@@ -125,8 +148,13 @@ int upload_topology(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
 int launch_linearize(lfx_ctx * c, const lfx::PgArgs & a, uint32_t slot, bool with_step, hipStream_t st)
 {
   {
-    Timed t(c, kSlotPgLinearize, st);
-    hipLaunchKernelGGL(lfx::pose_graph_linearize_kernel, dim3((a.n_edges + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+    Timed t(c, kSlotPgLinearize, st);             // (the priors' kernel inside the edges' span: the slots stay as they are)
+    if (a.n_edges) {
+      hipLaunchKernelGGL(lfx::pose_graph_linearize_kernel, dim3((a.n_edges + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+    }
+    if (a.n_priors) {
+      hipLaunchKernelGGL(lfx::pose_graph_prior_kernel, dim3((a.n_priors + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+    }
   }
   LFX_HIP(c, hipGetLastError());
   {
@@ -311,7 +339,7 @@ int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * pos
   std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * n);
   g->fixed.resize((size_t)first + n, 0);
   g->chain_edge.resize((size_t)first + n, lfx::kPgNone);
-  g->fixed[0] = 1;
+  if (first == 0u) {g->fixed[0] = (!g->released || g->first_fixed) ? 1 : 0;}
   LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * n, hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + first, g->fixed.data() + first, n, hipMemcpyHostToDevice, st));
   g->n_nodes += n;
@@ -329,7 +357,8 @@ int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rs = settle(c, g);
   if (rs != LFX_OK) {return rs;}
-  g->fixed[node] = (node == 0u || fixed) ? 1 : 0;
+  if (node == 0u) {g->first_fixed = fixed != 0;}
+  g->fixed[node] = ((node == 0u && !g->released) || fixed) ? 1 : 0;
   LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, st));
   return done(c, g, st);
 }
@@ -397,7 +426,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
 {
   if (!c || !g || !result) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (g->n_edges == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph has no edges");}
+  if (g->n_edges == 0u && g->n_priors == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph has no edges");}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (g->topology_stale) {
@@ -445,12 +474,14 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
     result->chi2_final = first;
     result->max_step = refused ? 0.0 : rec[it].max_step;
     result->n_robust_downweighted = rec[0].n_down;
+    g->prior_down = rec[0].n_down_prior; g->prior_chi2 = rec[0].chi2_prior;
   } else {
     result->code = converged ? LFX_POSE_GRAPH_CONVERGED : LFX_POSE_GRAPH_MAX_ITERATIONS;
     result->iterations = (int32_t)it;
     result->chi2_final = last;
     result->max_step = rec[it].max_step;
     result->n_robust_downweighted = rec[it].n_down;
+    g->prior_down = rec[it].n_down_prior; g->prior_chi2 = rec[it].chi2_prior;
   }
   g->linearised = true;
   return done(c, g, st);
@@ -521,6 +552,131 @@ int lfx_pose_graph_edge_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t fir
   return LFX_OK;
 }
 
+int lfx_pose_graph_reserve_priors(lfx_ctx * c, lfx_pose_graph * g, uint32_t max_priors)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (max_priors == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_priors must be >= 1");}
+  if (g->max_priors != 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph's priors are reserved already");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const size_t P = max_priors, N = g->cfg.max_nodes;
+  DevBuf<lfx::PgPrior> priors;
+  DevBuf<double> plin;
+  DevBuf<uint32_t> begin, inc;
+  const uint64_t bytes = (uint64_t)P * sizeof(lfx::PgPrior) + (uint64_t)P * lfx::kPgPlin * sizeof(double) + (uint64_t)(N + 1u + P) * sizeof(uint32_t);
+  if (priors.alloc(P) != hipSuccess || plin.alloc((size_t)lfx::kPgPlin * P) != hipSuccess || begin.alloc(N + 1u) != hipSuccess ||
+    inc.alloc(P) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the priors' " + std::to_string(bytes) + " bytes");     // (the four free themselves)
+  }
+  g->priors = std::move(priors); g->plin = std::move(plin); g->prior_begin = std::move(begin); g->prior_inc = std::move(inc);
+  g->prior_node.reserve(P);
+  g->max_priors = max_priors;
+  g->device_bytes += bytes;
+  return LFX_OK;
+}
+
+int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_graph_prior * priors, uint32_t n, void * stream)
+{
+  if (!c || !g || (n && !priors)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  for (uint32_t k = 0; k < n; k++) {                // every prior is checked before anything is touched
+    const lfx_pose_graph_prior & p = priors[k];
+    const std::string which = "prior " + std::to_string(k) + " of the call: ";
+    if (p.node >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "a node that is not in the graph");}
+    if (p.flags & ~(LFX_PRIOR_ROBUST | LFX_PRIOR_POSITION)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "unknown flags");}
+    if (!finite_all(p.z, 12) || !finite_all(p.information, 36) || !finite_all(p.lever, 3)) {
+      return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "a value that is not finite");
+    }
+    double top = 0.0;
+    for (int i = 0; i < 36; i++) {top = std::max(top, std::fabs(p.information[i]));}
+    for (int r = 0; r < 6; r++) {
+      for (int q = 0; q < r; q++) {
+        if (std::fabs(p.information[6 * r + q] - p.information[6 * q + r]) > 1e-9 * top) {
+          return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "the information matrix is not symmetric");
+        }
+      }
+    }
+    if (p.flags & LFX_PRIOR_POSITION) {
+      for (int i = 0; i < 36; i++) {
+        if ((i / 6 < 3 || i % 6 < 3) && p.information[i] != 0.0) {
+          return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "a position prior with information outside its lower right 3 x 3 block");
+        }
+      }
+    } else if (p.lever[0] != 0.0 || p.lever[1] != 0.0 || p.lever[2] != 0.0) {
+      return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "a pose prior with a lever");
+    }
+  }
+  if (n > g->max_priors - g->n_priors) {
+    return fail(c, LFX_ERR_CAPACITY, "the pose graph holds " + std::to_string(g->n_priors) + " of " + std::to_string(g->max_priors) +
+             " priors (lfx_pose_graph_reserve_priors): no room for " + std::to_string(n) + " more");
+  }
+  if (n == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  g->stage_priors.resize(n);
+  for (uint32_t k = 0; k < n; k++) {
+    lfx::PgPrior & d = g->stage_priors[k];
+    d.node = priors[k].node; d.flags = priors[k].flags;
+    std::memcpy(d.z, priors[k].z, sizeof(d.z));
+    std::memcpy(d.omega, priors[k].information, sizeof(d.omega));
+    std::memcpy(d.lever, priors[k].lever, sizeof(d.lever));
+  }
+  LFX_HIP(c, hipMemcpyAsync(g->priors.p + g->n_priors, g->stage_priors.data(), sizeof(lfx::PgPrior) * n, hipMemcpyHostToDevice, st));
+  for (uint32_t k = 0; k < n; k++) {g->prior_node.push_back(priors[k].node);}
+  g->n_priors += n;
+  g->topology_stale = true;
+  g->linearised = false;
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, void * stream)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  g->released = released != 0;
+  if (g->n_nodes == 0u) {return LFX_OK;}            // (lfx_pose_graph_add_nodes writes node 0's flag)
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rs = settle(c, g);
+  if (rs != LFX_OK) {return rs;}
+  g->fixed[0] = (!g->released || g->first_fixed) ? 1 : 0;
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p, g->fixed.data(), 1, hipMemcpyHostToDevice, st));
+  return done(c, g, st);
+}
+
+int lfx_pose_graph_prior_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * rho, double * w, void * stream)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (first > g->n_priors || count > g->n_priors - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "priors outside the pose graph");}
+  if (!g->linearised) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the graph has changed since the last lfx_pose_graph_optimize");}
+  if (count == 0) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = settle(c, g);
+  if (rc != LFX_OK) {return rc;}
+  g->stage_lin.resize((size_t)lfx::kPgPlin * count);
+  LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->plin.p + (size_t)lfx::kPgPlin * first, sizeof(double) * lfx::kPgPlin * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (uint32_t p = 0; p < count; p++) {
+    if (w) {w[p] = g->stage_lin[(size_t)lfx::kPgPlin * p + 12u];}
+    if (rho) {rho[p] = g->stage_lin[(size_t)lfx::kPgPlin * p + 13u];}
+  }
+  return LFX_OK;
+}
+
+int lfx_pose_graph_prior_info(const lfx_pose_graph * g, lfx_pose_graph_prior_info_t * info)
+{
+  if (!g || !info) {return LFX_ERR_INVALID_ARGUMENT;}
+  info->n_priors = g->n_priors; info->max_priors = g->max_priors; info->n_downweighted = g->prior_down; info->reserved = 0u;
+  info->chi2 = g->prior_chi2;
+  return LFX_OK;
+}
+
 #ifdef LFX_TEST_HOOKS
 // Test infrastructure (the test-hooks build only): the graph linearised where it stands -- per edge r [E][6] (may be NULL),
 // per node the gradient [N][6], chi^2 -- and lfx_pose_graph_edge_chi2 opened for those values.
@@ -544,6 +700,33 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
   LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord), hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
   for (uint32_t e = 0; r_out && e < g->n_edges; e++) {std::memcpy(r_out + 6u * (size_t)e, lin.data() + (size_t)lfx::kPgLin * e, sizeof(double) * 6u);}
+  *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
+  g->linearised = true;
+  return done(c, g, st);
+}
+
+// ... and the same for a graph with priors (edges or none): per prior r [P][6] (may be NULL), per node the gradient of edges
+// and priors [N][6], chi^2 of both; lfx_pose_graph_prior_chi2 and lfx_pose_graph_edge_chi2 opened for those values.
+int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_out, double * grad_out, double * chi2_out, void * stream)
+{
+  if (!c || !g || !grad_out || !chi2_out || g->n_priors == 0u) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (g->topology_stale) {
+    const int ru = upload_topology(c, g, st);
+    if (ru != LFX_OK) {return ru;}
+  }
+  int rc = order_behind(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  const lfx::PgArgs a = args_of(g);
+  rc = relinearize(c, g, a, st);
+  if (rc != LFX_OK) {return rc;}
+  std::vector<double> lin((size_t)lfx::kPgPlin * g->n_priors);
+  LFX_HIP(c, hipMemcpyAsync(lin.data(), g->plin.p, sizeof(double) * lin.size(), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipMemcpyAsync(grad_out, g->grad.p, sizeof(double) * 6u * g->n_nodes, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (uint32_t p = 0; r_out && p < g->n_priors; p++) {std::memcpy(r_out + 6u * (size_t)p, lin.data() + (size_t)lfx::kPgPlin * p, sizeof(double) * 6u);}
   *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
   g->linearised = true;
   return done(c, g, st);

@@ -1416,9 +1416,36 @@ def pose_graph_edges(i, j, z, information, flags=0):
     return e
 
 
+def pose_graph_priors(node, z, information, lever=None, position=False, robust=False):
+    """Priors as the records lfx_pose_graph_add_priors takes (B.POSE_GRAPH_PRIOR_DTYPE): node [n]; position False: z [n][3][4]
+    or [n][12], information [n][6][6]; position True: z [n][3] (the fix) or [n][12], information [n][3][3] (placed in the
+    lower right block) or [n][6][6], lever [n][3] or one [3] (None: zero).  position and robust: one value or [n]."""
+    node = np.atleast_1d(np.asarray(node))
+    n = len(node)
+    p = np.zeros(n, B.POSE_GRAPH_PRIOR_DTYPE)
+    position = np.broadcast_to(np.asarray(position, bool), (n,))
+    p["node"] = node
+    p["flags"] = np.where(position, B.PRIOR_POSITION, 0) | np.where(np.broadcast_to(np.asarray(robust, bool), (n,)), B.PRIOR_ROBUST, 0)
+    z = np.asarray(z, np.float64).reshape(n, -1)
+    if z.shape[1] == 3:
+        p["z"][:, [3, 7, 11]] = z
+    else:
+        p["z"] = z.reshape(n, 12)
+    om = np.asarray(information, np.float64).reshape(n, -1)
+    if om.shape[1] == 9:
+        full = np.zeros((n, 6, 6))
+        full[:, 3:, 3:] = om.reshape(n, 3, 3)
+        om = full.reshape(n, 36)
+    p["information"] = om.reshape(n, 36)
+    if lever is not None:
+        p["lever"] = np.broadcast_to(np.asarray(lever, np.float64), (n, 3))
+    return p
+
+
 class PoseGraph:
     """lfx_pose_graph: poses (nodes) and relative-pose measurements (edges) on the device, optimised there by Gauss-Newton with
-    the chain-and-loop solver (include/lfx.h, the pose graph section).  Poses are [3][4] = [R | t] float64; node 0 is fixed."""
+    the chain-and-loop solver (include/lfx.h, the pose graph section).  Poses are [3][4] = [R | t] float64; node 0 is fixed
+    unless release_first frees it.  Absolute fixes of single nodes are priors: reserve_priors once, then add_priors."""
 
     def __init__(self, fx, max_nodes, max_edges, config=None, **fields):
         self._fx = fx
@@ -1494,6 +1521,37 @@ class PoseGraph:
         self._check(self._L.lfx_pose_graph_edge_chi2(self._fx._ctx, self.handle, int(first), count, C.c_void_p(rho.ctypes.data if count else None),
                                                      C.c_void_p(w.ctypes.data if count else None), C.c_void_p(int(stream))))
         return rho, w
+
+    def reserve_priors(self, max_priors):
+        """lfx_pose_graph_reserve_priors: room for max_priors priors; once, before the first prior."""
+        self._check(self._L.lfx_pose_graph_reserve_priors(self._fx._ctx, self.handle, int(max_priors)))
+
+    def add_priors(self, priors, stream=0):
+        """lfx_pose_graph_add_priors: records of B.POSE_GRAPH_PRIOR_DTYPE (pose_graph_priors builds them)."""
+        p = np.ascontiguousarray(priors, B.POSE_GRAPH_PRIOR_DTYPE).reshape(-1)
+        self._check(self._L.lfx_pose_graph_add_priors(self._fx._ctx, self.handle, C.c_void_p(p.ctypes.data if len(p) else None), len(p),
+                                                      C.c_void_p(int(stream))))
+
+    def add_prior(self, node, z, information, lever=None, position=False, robust=False, stream=0):
+        self.add_priors(pose_graph_priors([node], [z], [information], None if lever is None else [lever], position, robust), stream)
+
+    def release_first(self, released=True, stream=0):
+        """lfx_pose_graph_release_first: node 0 free (unless set_fixed(0) holds it), or fixed again."""
+        self._check(self._L.lfx_pose_graph_release_first(self._fx._ctx, self.handle, int(bool(released)), C.c_void_p(int(stream))))
+
+    def prior_chi2(self, first=0, count=None, stream=0):
+        """lfx_pose_graph_prior_chi2: (rho [count], w [count]) at the poses the last optimize left."""
+        count = self.prior_info()["n_priors"] - int(first) if count is None else int(count)
+        rho, w = np.zeros(max(count, 0)), np.zeros(max(count, 0))
+        self._check(self._L.lfx_pose_graph_prior_chi2(self._fx._ctx, self.handle, int(first), count, C.c_void_p(rho.ctypes.data if count else None),
+                                                      C.c_void_p(w.ctypes.data if count else None), C.c_void_p(int(stream))))
+        return rho, w
+
+    def prior_info(self):
+        i = B.PoseGraphPriorInfo()
+        self._check(self._L.lfx_pose_graph_prior_info(self.handle, C.byref(i)))
+        return dict(n_priors=int(i.n_priors), max_priors=int(i.max_priors), n_downweighted=int(i.n_downweighted), reserved=int(i.reserved),
+                    chi2=float(i.chi2))
 
     def close(self):
         if self.handle:
