@@ -1101,9 +1101,6 @@ void lfx_destroy(lfx_ctx * c)
   if (c->copy_stream) {(void)hipStreamSynchronize(c->copy_stream);}
   for (auto & sp : c->spans) {(void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b);}
   for (auto & ev : c->free_events) {(void)hipEventDestroy(ev);}
-  for (auto & ds : c->deskew_slots) {
-    if (ds.used) {(void)hipEventSynchronize(ds.used); (void)hipEventDestroy(ds.used);}
-  }
   for (auto & sl : c->slots) {
     if (sl.uploaded) {(void)hipEventDestroy(sl.uploaded);}
     if (sl.done) {(void)hipEventDestroy(sl.done);}
@@ -1111,7 +1108,8 @@ void lfx_destroy(lfx_ctx * c)
   }
   if (c->copy_stream) {(void)hipStreamDestroy(c->copy_stream);}
   if (c->stream) {(void)hipStreamDestroy(c->stream);}
-  // the buffers go with the context; the two raw pinned blocks behind them, as ever (a batch's last kernel writes h_counters)
+  // the buffers go with the context, each ring's slots behind their events (Tail: the device is still current); the two raw
+  // pinned blocks behind them, as ever (a batch's last kernel writes h_counters)
   uint32_t * const h_counters = c->h_counters, * const h_status = c->h_status;
   delete c;
   if (h_counters) {(void)hipHostFree(h_counters);}

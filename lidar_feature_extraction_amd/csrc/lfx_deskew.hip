@@ -46,16 +46,15 @@ int check_call(lfx_ctx * c, const lfx_time_field * time, const void * motions, c
 
 // The ring's next slot with room for `doubles` on both sides, the kernel that read it last (kDeskewSlots calls ago, on
 // whichever stream: long done) waited for.  Without the memory: LFX_ERR_OUT_OF_MEMORY, the runtime's word for it as the
-// error text, for the caller to put its own in front of.  A failure leaves the slot valid, with an event and what memory it
-// had or none, and the ring where it was.
+// error text, for the caller to put its own in front of.  A failure leaves the slot valid, with what memory it had or none,
+// and the ring where it was.
 int take_slot(lfx_ctx * c, size_t doubles, lfx_ctx::DeskewSlot *& slot)
 {
   LFX_HIP(c, hipSetDevice(c->device));
   slot = &c->deskew_slots[c->deskew_next];
-  if (!slot->used) {LFX_HIP(c, hipEventCreateWithFlags(&slot->used, hipEventDisableTiming));}
-  LFX_HIP(c, hipEventSynchronize(slot->used));
-  hipError_t e = slot->h.reserve(sizeof(double) * doubles);
-  if (e == hipSuccess) {e = hold(slot->d, doubles);}
+  hipError_t e;
+  const int rs = slot->take(c, doubles, e);
+  if (rs != LFX_OK) {return rs;}
   if (e != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, hipGetErrorString(e));}
   c->deskew_next = (c->deskew_next + 1u) % lfx_ctx::kDeskewSlots;
   return LFX_OK;
@@ -92,8 +91,7 @@ int launch(lfx_ctx * c, const Forms<Args> & forms, int src, uint32_t n, const Ar
   const dim3 grid(n >= 32u ? 8u : 32u, n);
   hipLaunchKernelGGL(forms[src], grid, dim3(lfx::kDeskewThreads), 0, st, a);
   LFX_HIP(c, hipGetLastError());
-  LFX_HIP(c, hipEventRecord(slot.used, st));
-  return LFX_OK;
+  return slot.used.done(c, st);
 }
 }  // namespace
 

@@ -158,6 +158,52 @@ struct PinnedBuf
 };
 static_assert(!std::is_copy_constructible_v<PinnedBuf> && !std::is_copy_assignable_v<PinnedBuf>, "a pinned block has one owner");
 
+// The event behind the last call queued on an object, on whichever stream that went to, and whether anything has waited
+// for it since; owned as a DevBuf is.  Another stream is put behind it (order_behind), a call records it behind its own
+// work (done, which creates it on first use), and the host waits for it before it rewrites a pinned block or a staging
+// buffer that the call reads (settle).  An owner declares its Tail AFTER the buffers it guards: members go in reverse
+// order, so the event is waited for before they are freed.  The state is mutable: calls that only read an object take it
+// const and still order themselves.  (Defined behind lfx_ctx, whose error text they write.)
+struct Tail
+{
+  mutable hipEvent_t event = nullptr;
+  mutable bool pending = false;
+  Tail() = default;
+  Tail(const Tail &) = delete;
+  Tail & operator=(const Tail &) = delete;
+  Tail(Tail && o) noexcept : event(o.event), pending(o.pending) {o.event = nullptr; o.pending = false;}
+  Tail & operator=(Tail && o) noexcept
+  {
+    if (this != &o) {release(); event = o.event; pending = o.pending; o.event = nullptr; o.pending = false;}
+    return *this;
+  }
+  ~Tail() {release();}
+  int order_behind(lfx_ctx * c, hipStream_t st) const;
+  int done(lfx_ctx * c, hipStream_t st) const;
+  int settle(lfx_ctx * c) const;
+  void release()
+  {
+    if (event) {(void)hipEventSynchronize(event); (void)hipEventDestroy(event);}
+    event = nullptr;
+    pending = false;
+  }
+};
+static_assert(!std::is_copy_constructible_v<Tail> && !std::is_copy_assignable_v<Tail>, "a tail event has one owner");
+
+// One slot of a ring that a call's table of constants goes out through: the pinned block it is written to, the device table
+// it is copied to, and the event behind the kernels that read either -- so that a call never rewrites a block or a table
+// still in use, whichever streams the calls are on.  A slot is sized by the calls that took it and grows on demand.
+struct TableSlot
+{
+  PinnedBuf h;
+  DevBuf<double> d;
+  Tail used;
+  // The kernels that used the slot last (a ring's length of calls ago: long done) waited for, then room for `doubles` on
+  // both sides.  LFX_ERR_HIP where the wait fails; what an allocation answered comes back in `mem`, for the caller to word.
+  // A failure leaves the slot valid, with what memory it had or none; the caller advances its ring after success.
+  int take(lfx_ctx * c, size_t doubles, hipError_t & mem);
+};
+
 // The kernel slots of lfx_kernel_times, in the order of the comment on LFX_N_KERNELS (lfx.h); kKernelNames (lfx_api.hip) is
 // written in this order
 enum KernelSlot : int
@@ -275,38 +321,22 @@ struct lfx_ctx
   uint32_t loc_guess[2] = {0u, 0u};                // longest edge / downsampled surface cloud of the previous lfx_localize_batch
 
   // lfx_deskew_batch, lfx_deskew_batch_trajectory (lfx_deskew.hip): a call's table of constants goes out through the next of
-  // a ring of kDeskewSlots slots, each a pinned block, a device table and an event behind the kernel that reads it, so that a
-  // call never rewrites a block or a table still in use, whichever streams the calls are on.  A slot is sized by the calls
-  // that took it and grows on demand.  deskewed_in_place: the last batch's clouds have been de-skewed in place (a second
-  // de-skew would correct them twice); run_batch lifts it
+  // a ring of kDeskewSlots table slots (TableSlot; `used` is recorded behind the kernel that read d).  deskewed_in_place: the
+  // last batch's clouds have been de-skewed in place (a second de-skew would correct them twice); run_batch lifts it
   static constexpr uint32_t kDeskewSlots = 8;
-  struct DeskewSlot
-  {
-    lfx_host::PinnedBuf h;
-    lfx_host::DevBuf<double> d;
-    hipEvent_t used = nullptr;           // recorded behind the kernel that read d
-  };
+  using DeskewSlot = lfx_host::TableSlot;
   DeskewSlot deskew_slots[kDeskewSlots];
   uint32_t deskew_next = 0;
   bool deskewed_in_place = false;
 
   // lfx_scan_context_batch (lfx_place.hip): a call's tables go out as the de-skew's do, through the next of a ring of slots,
-  // each a pinned block, a device table, the call's cell keys ([scans][R * S] u32) and an event behind the kernels that use
-  // them.  A slot owns its event (the context's destruction waits for it and lets it go).
+  // each with the call's cell keys ([scans][R * S] u32) beside the table (`used` is recorded behind the kernel that turned
+  // the keys into the caller's floats; declared first, the keys go after it has been waited for).
   static constexpr uint32_t kPlaceSlots = 4;
   struct PlaceSlot
   {
-    lfx_host::PinnedBuf h;
-    lfx_host::DevBuf<double> d;
     lfx_host::DevBuf<uint32_t> keys;
-    hipEvent_t used = nullptr;           // recorded behind the kernel that turned keys into the caller's floats
-    PlaceSlot() = default;
-    PlaceSlot(const PlaceSlot &) = delete;
-    PlaceSlot & operator=(const PlaceSlot &) = delete;
-    ~PlaceSlot()
-    {
-      if (used) {(void)hipEventSynchronize(used); (void)hipEventDestroy(used);}
-    }
+    lfx_host::TableSlot table;
   };
   PlaceSlot place_slots[kPlaceSlots];
   uint32_t place_next = 0;
@@ -331,14 +361,7 @@ struct lfx_ctx
     lfx_host::DevBuf<uint32_t> parent, csize, crowmax, pack_counts;
     Table tables[kSegTables];
     uint32_t table_next = 0;             // the slot the next unseen config takes
-    hipEvent_t used = nullptr;
-    SegmentWork() = default;
-    SegmentWork(const SegmentWork &) = delete;
-    SegmentWork & operator=(const SegmentWork &) = delete;
-    ~SegmentWork()
-    {
-      if (used) {(void)hipEventSynchronize(used); (void)hipEventDestroy(used);}
-    }
+    lfx_host::Tail used;
   };
   SegmentWork seg;
 
@@ -437,6 +460,108 @@ inline int fail(lfx_ctx * ctx, int code, const std::string & msg)
 {
   if (ctx) {ctx->err = msg;}
   return code;
+}
+
+inline int Tail::order_behind(lfx_ctx * c, hipStream_t st) const
+{
+  if (pending) {LFX_HIP(c, hipStreamWaitEvent(st, event, 0));}
+  return LFX_OK;
+}
+inline int Tail::done(lfx_ctx * c, hipStream_t st) const
+{
+  if (!event) {LFX_HIP(c, hipEventCreateWithFlags(&event, hipEventDisableTiming));}
+  LFX_HIP(c, hipEventRecord(event, st));
+  pending = true;
+  return LFX_OK;
+}
+inline int Tail::settle(lfx_ctx * c) const
+{
+  if (pending) {LFX_HIP(c, hipEventSynchronize(event)); pending = false;}
+  return LFX_OK;
+}
+
+inline int TableSlot::take(lfx_ctx * c, size_t doubles, hipError_t & mem)
+{
+  const int rs = used.settle(c);
+  if (rs != LFX_OK) {return rs;}
+  mem = h.reserve(sizeof(double) * doubles);
+  if (mem == hipSuccess) {mem = hold(d, doubles);}
+  return LFX_OK;
+}
+
+// an object made on one device handed to a context of another: `what` names it ("the mapper", ...)
+inline int check_device(lfx_ctx * c, int device, const char * what)
+{
+  if (device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(what) + " lives on another device");}
+  return LFX_OK;
+}
+
+inline bool finite_all(const double * v, size_t n)
+{
+  for (size_t i = 0; i < n; i++) {
+    if (!std::isfinite(v[i])) {return false;}
+  }
+  return true;
+}
+
+// the parts of a pinned block start on 64-byte boundaries (tables of doubles; a copy up starts aligned)
+inline size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
+
+// One list of n clouds on the device, as the stores' add and insert calls are handed it: cloud s is d_count[s *
+// count_stride] records from record d_begin[s] of total_points.  name: what a refusal calls the list ("", "edge ", "surface ")
+struct CloudList
+{
+  const uint32_t * d_begin = nullptr, * d_count = nullptr;
+  uint32_t count_stride = 1;
+  uint64_t total_points = 0;
+  const char * name = "";
+};
+// the counts (a strided span, read whole) and begins of n clouds as read_lists reads one list back
+inline size_t readback_bytes(uint32_t n, uint32_t stride) {return sizeof(uint32_t) * ((size_t)(n - 1) * stride + 1 + n);}
+
+// The begins and counts of the n clouds of each of n_lists lists (1 or 2) into begin[l] / count[l], through `pinned`
+// (readback_bytes of each list, one behind the other): every copy queued on st, then one wait, the calling call's only
+// one.  A cloud that runs past its list's total_points is refused.
+inline int read_lists(lfx_ctx * c, const CloudList * lists, int n_lists, uint32_t n, uint8_t * pinned, std::vector<uint32_t> * begin,
+  std::vector<uint32_t> * count, hipStream_t st)
+{
+  const uint32_t * h_count[2];
+  uint32_t * at = reinterpret_cast<uint32_t *>(pinned);
+  for (int l = 0; l < n_lists; l++) {
+    const size_t span = (size_t)(n - 1) * lists[l].count_stride + 1;
+    h_count[l] = at;
+    LFX_HIP(c, hipMemcpyAsync(at, lists[l].d_count, sizeof(uint32_t) * span, hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipMemcpyAsync(at + span, lists[l].d_begin, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    at += span + n;
+  }
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (int l = 0; l < n_lists; l++) {
+    const uint32_t * h_begin = h_count[l] + (size_t)(n - 1) * lists[l].count_stride + 1;
+    begin[l].assign(h_begin, h_begin + n);
+    count[l].resize(n);
+    for (uint32_t s = 0; s < n; s++) {
+      count[l][s] = h_count[l][(size_t)s * lists[l].count_stride];
+      if ((uint64_t)begin[l][s] + count[l][s] > lists[l].total_points) {
+        return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(lists[l].name) + "cloud " + std::to_string(s) + " (records " + std::to_string(begin[l][s]) +
+                 " + " + std::to_string(count[l][s]) + ") runs past total_points (" + std::to_string(lists[l].total_points) + ")");
+      }
+    }
+  }
+  return LFX_OK;
+}
+
+// The pinned block of a store whose calls read lists back into [0, pin_table) and send their table of entries up from
+// pin_table on: room for a read-back of `need` bytes and `entries` entries of `entry_bytes` behind it.  The block may move,
+// so what was queued behind `tail` is waited for first: nothing may still read the table in it.
+inline int grow_readback(lfx_ctx * c, const Tail & tail, PinnedBuf & pinned, size_t & pin_table, size_t need, size_t entry_bytes, size_t entries)
+{
+  if (need <= pin_table) {return LFX_OK;}
+  const int rs = tail.settle(c);
+  if (rs != LFX_OK) {return rs;}
+  const size_t at = round64(need);
+  LFX_HIP(c, pinned.reserve(at + entry_bytes * entries));
+  pin_table = at;
+  return LFX_OK;
 }
 
 // the calls that work on the last batch: the caller's arrays are sized by ITS count (one pose after a batch of 16 would be

@@ -33,8 +33,8 @@ struct lfx_keyframes
   PinnedBuf readback;                    // the counts and begins an add reads back; the submap's record
   PinnedBuf upload;                      // what goes up (tables, begins, poses, a host keyframe's records): rewritten only
                                          // once the store's last queued call has passed
-  mutable hipEvent_t tail = nullptr;     // recorded behind the last call that touched the store, on its stream
-  mutable bool pending = false;
+  Tail tail;                             // behind the last call that touched the store: order_behind before a call's own
+                                         // work, done after it; settle before the pinned upload block is rewritten
 };
 
 namespace
@@ -42,40 +42,7 @@ namespace
 constexpr uint32_t kInitialClouds = 64;
 constexpr uint64_t kSaveChunk = (uint64_t)1 << 20;
 
-size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
-
-bool finite_all(const double * v, size_t n)
-{
-  for (size_t i = 0; i < n; i++) {
-    if (!std::isfinite(v[i])) {return false;}
-  }
-  return true;
-}
-
-int check_store(lfx_ctx * c, const lfx_keyframes * s)
-{
-  if (s->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the keyframe store lives on another device");}
-  return LFX_OK;
-}
-
-// `st` behind the store's last call; after the call's own work: done()
-int order_behind(lfx_ctx * c, const lfx_keyframes * s, hipStream_t st)
-{
-  if (s->pending) {LFX_HIP(c, hipStreamWaitEvent(st, s->tail, 0));}
-  return LFX_OK;
-}
-int done(lfx_ctx * c, const lfx_keyframes * s, hipStream_t st)
-{
-  LFX_HIP(c, hipEventRecord(s->tail, st));
-  s->pending = true;
-  return LFX_OK;
-}
-// the pinned upload block may be rewritten
-int settle(lfx_ctx * c, const lfx_keyframes * s)
-{
-  if (s->pending) {LFX_HIP(c, hipEventSynchronize(s->tail)); s->pending = false;}
-  return LFX_OK;
-}
+int check_store(lfx_ctx * c, const lfx_keyframes * s) {return check_device(c, s->device, "the keyframe store");}
 
 int check_range(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, uint32_t count)
 {
@@ -122,7 +89,7 @@ int append(lfx_ctx * c, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, s
 {
   uint8_t * up = s->upload.p;
   size_t at = table_at;
-  const int rc = order_behind(c, s, st);
+  const int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   for (int kind = 0; kind < 2; kind++) {
     lfx::KfCopyEntry * tab = reinterpret_cast<lfx::KfCopyEntry *>(up + at);
@@ -157,7 +124,7 @@ int append(lfx_ctx * c, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, s
     for (uint32_t k = 0; k < n; k++) {dst += plan[kind].count[k]; s->begin[kind].push_back(dst);}
   }
   s->n += n;
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 // what an add of n keyframes needs of the pinned upload block: [poses][per kind: table, begins]
@@ -248,10 +215,6 @@ int lfx_keyframes_create(lfx_ctx * c, const lfx_keyframes_config * config, lfx_k
   {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's pinned blocks");
   }
-  if (hipEventCreateWithFlags(&s->tail, hipEventDisableTiming) != hipSuccess) {
-    s->tail = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the keyframe store's event");
-  }
   *out = s;
   return LFX_OK;
 }
@@ -260,7 +223,6 @@ void lfx_keyframes_destroy(lfx_keyframes * s)
 {
   if (!s) {return;}
   (void)hipSetDevice(s->device);
-  if (s->tail) {(void)hipEventSynchronize(s->tail); (void)hipEventDestroy(s->tail);}
   delete s;
 }
 
@@ -280,7 +242,7 @@ int lfx_keyframes_view(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes_store
   if (!c || !s || !view) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = order_behind(c, s, static_cast<hipStream_t>(stream));
+  const int rc = s->tail.order_behind(c, static_cast<hipStream_t>(stream));
   if (rc != LFX_OK) {return rc;}
   *view = lfx_keyframes_store_view{};
   for (int kind = 0; kind < 2; kind++) {
@@ -310,45 +272,32 @@ int lfx_keyframes_add(lfx_ctx * c, lfx_keyframes * s, const lfx_keyframes_clouds
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // both kinds' counts (strided spans, read whole) and begins back in one wait: the call's only one
-  size_t span[2], need = 0;
-  for (int kind = 0; kind < 2; kind++) {span[kind] = (size_t)(n - 1u) * in[kind]->count_stride + 1u; need += sizeof(uint32_t) * (span[kind] + n);}
-  LFX_HIP(c, s->readback.reserve(need));
-  uint32_t * h_count[2], * h_begin[2];
-  uint32_t * at = reinterpret_cast<uint32_t *>(s->readback.p);
+  // both kinds' counts and begins back in one wait: the call's only one
+  const CloudList lists[2] = {{edge->d_begin, edge->d_count, edge->count_stride, edge->total_points, "edge "},
+    {surface->d_begin, surface->d_count, surface->count_stride, surface->total_points, "surface "}};
+  LFX_HIP(c, s->readback.reserve(readback_bytes(n, edge->count_stride) + readback_bytes(n, surface->count_stride)));
+  std::vector<uint32_t> begin[2], count[2];
+  rc = read_lists(c, lists, 2, n, s->readback.p, begin, count, st);
+  if (rc != LFX_OK) {return rc;}
+  uint64_t add[2] = {0u, 0u};
   for (int kind = 0; kind < 2; kind++) {
-    h_count[kind] = at; at += span[kind];
-    h_begin[kind] = at; at += n;
-    LFX_HIP(c, hipMemcpyAsync(h_count[kind], in[kind]->d_count, sizeof(uint32_t) * span[kind], hipMemcpyDeviceToHost, st));
-    LFX_HIP(c, hipMemcpyAsync(h_begin[kind], in[kind]->d_begin, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-  }
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::vector<uint32_t> count[2];
-  uint64_t add[2] = {0u, 0u}, blocks[2] = {0u, 0u};
-  for (int kind = 0; kind < 2; kind++) {
-    count[kind].resize(n);
+    uint64_t blocks = 0u;
     for (uint32_t k = 0; k < n; k++) {
-      const uint32_t cnt = h_count[kind][(size_t)k * in[kind]->count_stride];
-      if ((uint64_t)h_begin[kind][k] + cnt > in[kind]->total_points) {
-        return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(kind ? "surface" : "edge") + " cloud " + std::to_string(k) + " (records " +
-                 std::to_string(h_begin[kind][k]) + " + " + std::to_string(cnt) + ") runs past total_points (" + std::to_string(in[kind]->total_points) + ")");
-      }
-      count[kind][k] = cnt;
-      add[kind] += cnt;
-      blocks[kind] += (cnt + lfx::kKfThreads - 1u) / lfx::kKfThreads;
+      add[kind] += count[kind][k];
+      blocks += (count[kind][k] + lfx::kKfThreads - 1u) / lfx::kKfThreads;
     }
-    if (blocks[kind] > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "the call adds too many records for one launch");}
+    if (blocks > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "the call adds too many records for one launch");}
   }
   rc = check_room(c, s, n, add);
   if (rc != LFX_OK) {return rc;}
-  rc = settle(c, s);
+  rc = s->tail.settle(c);
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, s->upload.reserve(upload_bytes(n)));
   std::memcpy(s->upload.p, poses, sizeof(double) * 12u * n);
   KindPlan plan[2];
   for (int kind = 0; kind < 2; kind++) {
     plan[kind].src = reinterpret_cast<const uint4 *>(in[kind]->d_points);
-    plan[kind].begin = h_begin[kind];
+    plan[kind].begin = begin[kind].data();
     plan[kind].count = count[kind].data();
   }
   const uint32_t first = s->n;
@@ -368,7 +317,7 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = settle(c, s);
+  rc = s->tail.settle(c);
   if (rc != LFX_OK) {return rc;}
   // the pinned block: [pose][the two new begins][edge records][surface records]; copied up from there, straight into place
   const size_t head = 128u, e_bytes = sizeof(float4) * (size_t)n_edge, s_bytes = sizeof(float4) * (size_t)n_surface;
@@ -378,7 +327,7 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   uint64_t * nb = reinterpret_cast<uint64_t *>(up + 96u);
   const float * src[2] = {edge, surface};
   const size_t bytes[2] = {e_bytes, s_bytes}, where[2] = {head, head + e_bytes};
-  rc = order_behind(c, s, st);
+  rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   for (int kind = 0; kind < 2; kind++) {
     const uint64_t at = s->begin[kind][s->n];
@@ -393,7 +342,7 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   for (int kind = 0; kind < 2; kind++) {s->begin[kind].push_back(nb[kind]);}
   if (id) {*id = s->n;}
   s->n += 1u;
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 int lfx_keyframes_set_poses(lfx_ctx * c, lfx_keyframes * s, uint32_t first, uint32_t count, const double * poses, void * stream)
@@ -405,12 +354,12 @@ int lfx_keyframes_set_poses(lfx_ctx * c, lfx_keyframes * s, uint32_t first, uint
   if (count == 0u) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, s);
+  const int rs = s->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   LFX_HIP(c, s->upload.reserve(sizeof(double) * 12u * count));
   std::memcpy(s->upload.p, poses, sizeof(double) * 12u * count);
   LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, s->upload.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 int lfx_keyframes_poses(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, uint32_t count, double * poses_out, void * stream)
@@ -421,7 +370,7 @@ int lfx_keyframes_poses(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, ui
   if (count == 0u) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = order_behind(c, s, st);
+  const int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipMemcpyAsync(poses_out, s->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -436,10 +385,10 @@ int lfx_keyframes_follow(lfx_ctx * c, lfx_keyframes * s, const double * d_poses,
   if (count == 0u) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = order_behind(c, s, st);
+  const int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, st));
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t first, uint32_t count, float * d_out, uint64_t capacity_points,
@@ -458,11 +407,11 @@ int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t
   if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = order_behind(c, s, st);
+  int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   rc = launch_transform(c, s, kind, lo, hi, first, first + count, false, first, d_out, st);
   if (rc != LFX_OK) {return rc;}
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const double center[3], double radius, uint32_t first, uint32_t count,
@@ -477,7 +426,7 @@ int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const d
   if (count == 0u) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = order_behind(c, s, st);
+  int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   hipLaunchKernelGGL(lfx::keyframes_flag_kernel, dim3((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), dim3(lfx::kKfThreads), 0, st, s->poses.p, first,
     count, center[0], center[1], center[2], radius * radius, s->flag.p);
@@ -492,12 +441,12 @@ int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const d
   std::memcpy(result, rec, sizeof(*result));
   result->reserved = 0u;
   if (result->n_points > 0u) {
-    if (!d_out) {(void)done(c, s, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
     const uint32_t k_lo = result->first_id, k_hi = result->last_id + 1u;
     rc = launch_transform(c, s, kind, s->begin[kind][k_lo], s->begin[kind][k_hi], k_lo, k_hi, true, first, d_out, st);
     if (rc != LFX_OK) {return rc;}
   }
-  return done(c, s, st);
+  return s->tail.done(c, st);
 }
 
 int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirname, int written[2], void * stream)
@@ -509,7 +458,7 @@ int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirnam
   hipStream_t st = static_cast<hipStream_t>(stream);
   const std::string dir(dirname);
   const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
-  int rc = order_behind(c, s, st);
+  int rc = s->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   for (int kind = 0; kind < 2; kind++) {
     if (s->begin[kind][s->n] == 0u) {continue;}

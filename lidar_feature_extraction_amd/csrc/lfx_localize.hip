@@ -191,7 +191,7 @@ int lfx_map_nearest(
   if (k == 0 || k > (uint32_t)lfx::kNearestMax || m->index.n < k) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "k must be in [1, 16] and the map must hold that many points");
   }
-  if (m->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the map lives on another device");}
+  if (check_device(c, m->device, "the map") != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (n_queries == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -245,7 +245,7 @@ int lfx_scan_to_map_residuals(
   if (n_neighbors == 0 || n_neighbors > (uint32_t)lfx::kNearestMax || map->index.n < n_neighbors || (kind == LFX_RESIDUAL_SURFACE && n_neighbors < 3)) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [1, 16] (>= 3 for planes) and the map must hold that many points");
   }
-  if (map->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the map lives on another device");}
+  if (check_device(c, map->device, "the map") != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (max_points_per_cloud == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   lfx::MapPose P;
@@ -490,7 +490,9 @@ int align_clouds(
   if (n_neighbors < 3 || n_neighbors > (uint32_t)lfx::kNearestMax || edge_map->index.n < n_neighbors || surface_map->index.n < n_neighbors) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [3, 16] and both maps must hold that many points");
   }
-  if (edge_map->device != c->device || surface_map->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a map lives on another device");}
+  if (check_device(c, edge_map->device, "a map") != LFX_OK || check_device(c, surface_map->device, "a map") != LFX_OK) {
+    return LFX_ERR_INVALID_ARGUMENT;
+  }
   LFX_HIP(c, hipSetDevice(c->device));
   AlignProblem pr;
   pr.edge_map = edge_map; pr.surface_map = surface_map;

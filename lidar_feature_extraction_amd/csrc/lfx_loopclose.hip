@@ -44,9 +44,9 @@ int common_size(lfx_ctx * c, const lfx_loop_closer * lc, uint32_t & n)
 
 int check_range(lfx_ctx * c, const lfx_loop_closer * lc, uint32_t first, uint32_t count)
 {
-  if (lc->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the loop closer lives on another device");}
   uint32_t n = 0;
-  const int rc = common_size(c, lc, n);
+  int rc = check_device(c, lc->device, "the loop closer");
+  if (rc == LFX_OK) {rc = common_size(c, lc, n);}
   if (rc != LFX_OK) {return rc;}
   if (count == 0 || first >= n || count > n - first) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "keyframes " + std::to_string(first) + " .. + " + std::to_string(count) + " are not all below " +

@@ -23,42 +23,14 @@ struct lfx_mapper
   // written again before `uploaded` (recorded behind the previous call's upload and append) has passed.
   PinnedBuf pinned;
   size_t pin_table = 0;
-  hipEvent_t uploaded = nullptr;
-  bool upload_pending = false;
+  Tail uploaded;
 };
 
 namespace
 {
 constexpr uint32_t kInitialEntries = 64;
 
-// the table part of the pinned block starts on a 64-byte boundary (MapAppendEntry holds doubles; the copy up starts aligned)
-size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
-
-// the counts (a strided span) and begins of n clouds as a call reads them back
-size_t readback_bytes(uint32_t n, uint32_t stride) {return sizeof(uint32_t) * ((size_t)(n - 1) * stride + 1 + n);}
-
-int check(lfx_ctx * c, const lfx_mapper * m)
-{
-  if (m->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the mapper lives on another device");}
-  return LFX_OK;
-}
-
-// the previous call's upload and append have passed (the pinned table and the staged cloud may be written again)
-int settle(lfx_ctx * c, lfx_mapper * m)
-{
-  if (!m->upload_pending) {return LFX_OK;}
-  LFX_HIP(c, hipEventSynchronize(m->uploaded));
-  m->upload_pending = false;
-  return LFX_OK;
-}
-
-bool finite_poses(const double * poses, uint32_t n)
-{
-  for (size_t i = 0; i < 12 * (size_t)n; i++) {
-    if (!std::isfinite(poses[i])) {return false;}
-  }
-  return true;
-}
+int check(lfx_ctx * c, const lfx_mapper * m) {return check_device(c, m->device, "the mapper");}
 
 // MapBuilder::Callback for n clouds whose begins and counts are known on the host (src: the records they address).
 // Decides every outcome, then grows the map if it must and queues one map_append_kernel; all or nothing.
@@ -99,7 +71,8 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
       return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot grow the map to " + std::to_string(want) + " records");
     }
     // (the previous call's append may be queued on another stream: the copy reads the map behind it)
-    if (m->upload_pending) {LFX_HIP(c, hipStreamWaitEvent(st, m->uploaded, 0));}
+    const int rb = m->uploaded.order_behind(c, st);
+    if (rb != LFX_OK) {return rb;}
     if (m->n) {LFX_HIP(c, hipMemcpyAsync(grown.p, m->map.p, sizeof(float4) * m->n, hipMemcpyDeviceToDevice, st));}
     // (growth is rare: the copy has read the old map before it goes)
     LFX_HIP(c, hipStreamSynchronize(st));
@@ -110,13 +83,13 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
     if (m->table.n < na) {
       DevBuf<lfx::MapAppendEntry> t;
       if (t.alloc(na + na / 2) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's table");}
-      const int rs = settle(c, m);           // (the previous append may still read the old table)
+      const int rs = m->uploaded.settle(c);  // (the previous append may still read the old table)
       if (rs != LFX_OK) {return rs;}
       m->table = std::move(t);
     }
     const size_t bytes = sizeof(lfx::MapAppendEntry) * na;
     LFX_HIP(c, m->pinned.reserve(m->pin_table + bytes));
-    const int rs = settle(c, m);
+    const int rs = m->uploaded.settle(c);    // (the previous call's upload has passed: the pinned table may be written again)
     if (rs != LFX_OK) {return rs;}
     lfx::MapAppendEntry * tab = reinterpret_cast<lfx::MapAppendEntry *>(m->pinned.p + m->pin_table);
     uint64_t at = m->n;
@@ -136,8 +109,8 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
     LFX_HIP(c, hipMemcpyAsync(m->table.p, tab, bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lfx::map_append_kernel, dim3(first), dim3(lfx::kMapAppendThreads), 0, st, m->table.p, (uint32_t)na, src, m->map.p);
     LFX_HIP(c, hipGetLastError());
-    LFX_HIP(c, hipEventRecord(m->uploaded, st));
-    m->upload_pending = true;
+    const int rd = m->uploaded.done(c, st);
+    if (rd != LFX_OK) {return rd;}
   }
   // the call stands: commit
   if (!added.empty()) {std::memcpy(m->last, poses + 12 * (size_t)added.back(), sizeof(m->last));}
@@ -198,10 +171,6 @@ int lfx_mapper_create(lfx_ctx * c, const lfx_mapper_config * cfg, lfx_mapper ** 
   if (m->pinned.reserve(m->pin_table + sizeof(lfx::MapAppendEntry) * kInitialEntries) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's pinned block");
   }
-  if (hipEventCreateWithFlags(&m->uploaded, hipEventDisableTiming) != hipSuccess) {
-    m->uploaded = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the mapper's event");
-  }
   *out = m;
   return LFX_OK;
 }
@@ -210,7 +179,6 @@ void lfx_mapper_destroy(lfx_mapper * m)
 {
   if (!m) {return;}
   (void)hipSetDevice(m->device);
-  if (m->uploaded) {(void)hipEventSynchronize(m->uploaded); (void)hipEventDestroy(m->uploaded);}
   delete m;
 }
 
@@ -219,32 +187,18 @@ int lfx_mapper_add(lfx_ctx * c, lfx_mapper * m, const float * d_points, const ui
 {
   if (!c || !m || !d_points || !d_begin || !d_count || !poses || !outcomes) {return LFX_ERR_INVALID_ARGUMENT;}
   if (n_clouds == 0 || count_stride == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_clouds and count_stride must be >= 1");}
-  if (!finite_poses(poses, n_clouds)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the poses must be finite");}
+  if (!finite_all(poses, 12 * (size_t)n_clouds)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the poses must be finite");}
   if (check(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // the counts (a strided span, read whole) and the begins back in one wait: the call's only one
-  const size_t span = (size_t)(n_clouds - 1) * count_stride + 1;
-  const size_t need = readback_bytes(n_clouds, count_stride);
-  if (need > m->pin_table) {
-    const int rs = settle(c, m);             // (the block moves: nothing may still read the table in it)
-    if (rs != LFX_OK) {return rs;}
-    const size_t at = round64(need);
-    LFX_HIP(c, m->pinned.reserve(at + sizeof(lfx::MapAppendEntry) * std::max<size_t>(n_clouds, kInitialEntries)));
-    m->pin_table = at;
-  }
-  uint32_t * h_count = reinterpret_cast<uint32_t *>(m->pinned.p), * h_begin = h_count + span;
-  LFX_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint32_t) * span, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipMemcpyAsync(h_begin, d_begin, sizeof(uint32_t) * n_clouds, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::vector<uint32_t> begin(h_begin, h_begin + n_clouds), count(n_clouds);
-  for (uint32_t s = 0; s < n_clouds; s++) {
-    count[s] = h_count[(size_t)s * count_stride];
-    if ((uint64_t)begin[s] + count[s] > total_points) {
-      return fail(c, LFX_ERR_INVALID_ARGUMENT, "cloud " + std::to_string(s) + " (records " + std::to_string(begin[s]) + " + " +
-               std::to_string(count[s]) + ") runs past total_points (" + std::to_string(total_points) + ")");
-    }
-  }
+  // the counts and the begins back in one wait: the call's only one
+  int rc = grow_readback(c, m->uploaded, m->pinned, m->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::MapAppendEntry),
+    std::max<size_t>(n_clouds, kInitialEntries));
+  if (rc != LFX_OK) {return rc;}
+  const CloudList list{d_begin, d_count, count_stride, total_points, ""};
+  std::vector<uint32_t> begin, count;
+  rc = read_lists(c, &list, 1, n_clouds, m->pinned.p, &begin, &count, st);
+  if (rc != LFX_OK) {return rc;}
   return add_clouds(c, m, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses, outcomes, st);
 }
 
@@ -252,7 +206,7 @@ int lfx_mapper_add_host(lfx_ctx * c, lfx_mapper * m, const float * points, uint3
   uint8_t * outcome, void * stream)
 {
   if (!c || !m || !pose || !outcome || (n_points && !points)) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (!finite_poses(pose, 1)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose must be finite");}
+  if (!finite_all(pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose must be finite");}
   if (check(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -266,7 +220,7 @@ int lfx_mapper_add_host(lfx_ctx * c, lfx_mapper * m, const float * points, uint3
       return add_clouds(c, m, nullptr, &zero, &n_points, 1, pose, outcome, st);
     }
   }
-  const int rs = settle(c, m);               // (the previous append may still read the staged cloud)
+  const int rs = m->uploaded.settle(c);      // (the previous append may still read the staged cloud)
   if (rs != LFX_OK) {return rs;}
   if (hold(m->staged, n_points) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the cloud");}
   LFX_HIP(c, hipMemcpyAsync(m->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, st));
@@ -296,7 +250,8 @@ int lfx_mapper_save(lfx_ctx * c, const lfx_mapper * m, const char * path, int * 
   if (m->n == 0) {return LFX_OK;}            // "Map is empty! Quit without exporting to a file"
   LFX_HIP(c, hipSetDevice(c->device));
   // (the last append may be queued on another stream: the map is read behind it)
-  if (m->upload_pending) {LFX_HIP(c, hipStreamWaitEvent(static_cast<hipStream_t>(stream), m->uploaded, 0));}
+  const int rb = m->uploaded.order_behind(c, static_cast<hipStream_t>(stream));
+  if (rb != LFX_OK) {return rb;}
   const int rc = save_cloud(c, reinterpret_cast<const float *>(m->map.p), m->n, path, static_cast<hipStream_t>(stream));
   if (rc != LFX_OK) {return rc;}
   *written = 1;

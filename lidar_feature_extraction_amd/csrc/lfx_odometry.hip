@@ -30,10 +30,7 @@ struct lfx_odometry
   uint64_t added = 0, dropped = 0, compactions = 0;
   lfx_map * emap = nullptr, * smap = nullptr;   // the window maps (map_rebuild)
   DevBuf<uint32_t> bounds;                   // [2][6]: what odometry_append_kernel reduces into
-  // The work a call leaves queued behind it (the last append, the bounds' copy to the pinned block) is waited for by the
-  // next rebuild, or by the next call before it touches the scratch: `tail` is recorded behind it
-  hipEvent_t tail = nullptr;
-  bool tail_pending = false, bounds_queued = false;
+  bool bounds_queued = false;                // the last append's bounds are on their way to the pinned block (settle)
   DevBuf<uint32_t> words;                    // [0] 0 (begin / row begin of a single cloud), [1] n_edge, [2] n_surface, [3] downsampled, [4] status
   DevBuf<float> down;                        // downsampled surface clouds of a batch, then their counts and statuses
   DevBuf<float4> staged;                     // lfx_odometry_update_host: the two clouds, edge first
@@ -45,6 +42,9 @@ struct lfx_odometry
   double recent[2][12] = {};
   uint32_t n_recent = 0;
   DevBuf<float4> dsk_edge, dsk_surface;
+  // The work a call leaves queued behind it (the last append, the bounds' copy to the pinned block) is waited for by the
+  // next rebuild, or by the next call before it touches the scratch: `tail` is recorded behind it
+  Tail tail;
   uint32_t n_scans() const {return (uint32_t)box.size();}
 };
 
@@ -99,10 +99,8 @@ int compact(lfx_ctx * c, lfx_odometry * o, hipStream_t st)
 // waited since)
 int settle(lfx_ctx * c, lfx_odometry * o)
 {
-  if (!o->tail_pending) {return LFX_OK;}
-  LFX_HIP(c, hipEventSynchronize(o->tail));
-  o->tail_pending = false;
-  if (!o->bounds_queued) {return LFX_OK;}
+  const int rs = o->tail.settle(c);
+  if (rs != LFX_OK || !o->bounds_queued) {return rs;}
   o->bounds_queued = false;
   const uint32_t * h = pinned_words(o) + kPinBounds;
   std::array<Box, 2> & b = o->box.back();
@@ -136,8 +134,8 @@ int append(lfx_ctx * c, lfx_odometry * o, int how, const double pose[12], const 
   o->off_e.push_back(at_e + ne);
   o->off_s.push_back(at_s + ns);
   o->box.push_back(std::array<Box, 2>{});
-  LFX_HIP(c, hipEventRecord(o->tail, st));
-  o->tail_pending = true;
+  rc = o->tail.done(c, st);
+  if (rc != LFX_OK) {return rc;}
   o->bounds_queued = ne + ns > 0;
   o->added++;
   return LFX_OK;
@@ -226,11 +224,7 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
   return LFX_OK;
 }
 
-int check(lfx_ctx * c, const lfx_odometry * o)
-{
-  if (o->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the odometry lives on another device");}
-  return LFX_OK;
-}
+int check(lfx_ctx * c, const lfx_odometry * o) {return check_device(c, o->device, "the odometry");}
 
 // What the de-skewing batch calls do once their arguments are checked: every scan of the last batch through
 // lfx_odometry_update, its clouds de-skewed just ahead of it by queue(s), which queues scan s's de-skew into dsk_edge /
@@ -299,9 +293,7 @@ int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odomet
   {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the store's capacities must be in [1, 2^32 - 1] points");
   }
-  for (int i = 0; i < 12; i++) {
-    if (!std::isfinite(cfg->initial_pose[i])) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
-  }
+  if (!finite_all(cfg->initial_pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
   LFX_HIP(c, hipSetDevice(c->device));
   lfx_odometry * o = new (std::nothrow) lfx_odometry();
   if (!o) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry");}
@@ -319,10 +311,6 @@ int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odomet
   if (o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)std::max(c->max_batch, 1u))) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's pinned block");
   }
-  if (hipEventCreateWithFlags(&o->tail, hipEventDisableTiming) != hipSuccess) {
-    o->tail = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the odometry's event");
-  }
   hipError_t e = hipMemset(o->words.p, 0, 8 * sizeof(uint32_t));
   if (e == hipSuccess) {e = hipDeviceSynchronize();}
   if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
@@ -334,10 +322,10 @@ void lfx_odometry_destroy(lfx_odometry * o)
 {
   if (!o) {return;}
   (void)hipSetDevice(o->device);
-  if (o->tail) {(void)hipEventSynchronize(o->tail); (void)hipEventDestroy(o->tail);}
-  lfx_map_destroy(o->emap);
-  lfx_map_destroy(o->smap);
-  delete o;
+  lfx_map * const emap = o->emap, * const smap = o->smap;
+  delete o;                                  // (waits for the tail: the window maps go after it, as the buffers do)
+  lfx_map_destroy(emap);
+  lfx_map_destroy(smap);
 }
 
 int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, lfx_odometry_result * results, void * stream)

@@ -28,19 +28,14 @@ struct lfx_place_db
   mutable DevBuf<lfx::PlaceGate> gates;
   mutable DevBuf<uint32_t> list, n_eligible;
   mutable PinnedBuf h_gates, h_eligible;
-  hipEvent_t added = nullptr;                // recorded behind the last add's copy and norms
-  bool add_pending = false;
+  Tail added;                                // behind the last add's copy and norms
 };
 
 namespace
 {
 uint32_t cells_of(const lfx_scan_context_config & cfg) {return cfg.n_rings * cfg.n_sectors;}
 
-int check_db(lfx_ctx * c, const lfx_place_db * db)
-{
-  if (db->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the place index lives on another device");}
-  return LFX_OK;
-}
+int check_db(lfx_ctx * c, const lfx_place_db * db) {return check_device(c, db->device, "the place index");}
 
 // the config's tables as the kernel takes them (sc_table_doubles), or what lfx_scan_context_tables refuses
 int write_tables(lfx_ctx * c, const lfx_scan_context_config * cfg, double * out)
@@ -64,10 +59,9 @@ int take_slot(lfx_ctx * c, size_t doubles, size_t keys, lfx_ctx::PlaceSlot *& sl
 {
   LFX_HIP(c, hipSetDevice(c->device));
   slot = &c->place_slots[c->place_next];
-  if (!slot->used) {LFX_HIP(c, hipEventCreateWithFlags(&slot->used, hipEventDisableTiming));}
-  LFX_HIP(c, hipEventSynchronize(slot->used));
-  hipError_t e = slot->h.reserve(sizeof(double) * doubles);
-  if (e == hipSuccess) {e = hold(slot->d, doubles);}
+  hipError_t e;
+  const int rs = slot->table.take(c, doubles, e);
+  if (rs != LFX_OK) {return rs;}
   if (e == hipSuccess) {e = hold(slot->keys, keys);}
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -114,13 +108,14 @@ int add_device(lfx_ctx * c, lfx_place_db * db, const float * d_desc, uint32_t n,
   const size_t cells = cells_of(db->cfg);
   float * dst = db->desc.p + (size_t)db->n * cells;
   // (the add before may be queued on another stream: the event below then stands for both)
-  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  const int rb = db->added.order_behind(c, st);
+  if (rb != LFX_OK) {return rb;}
   // (hipMemcpyDefault: d_desc may be pinned host memory, lfx_host_alloc, which a kernel writes as it writes device memory)
   LFX_HIP(c, hipMemcpyAsync(dst, d_desc, sizeof(float) * cells * n, hipMemcpyDefault, st));
   const int rc = launch_norms(c, dst, db->norms.p + (size_t)db->n * db->cfg.n_sectors, n, db->cfg, st);
   if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipEventRecord(db->added, st));
-  db->add_pending = true;
+  const int rd = db->added.done(c, st);
+  if (rd != LFX_OK) {return rd;}
   db->n += n;
   return LFX_OK;
 }
@@ -160,14 +155,14 @@ int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uin
   lfx_ctx::PlaceSlot * slot;
   const int rs = take_slot(c, doubles, total, slot);
   if (rs != LFX_OK) {return rs;}
-  std::memcpy(slot->h.p, table, sizeof(double) * doubles);
-  LFX_HIP(c, hipMemcpyAsync(slot->d.p, slot->h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
+  std::memcpy(slot->table.h.p, table, sizeof(double) * doubles);
+  LFX_HIP(c, hipMemcpyAsync(slot->table.d.p, slot->table.h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipMemsetAsync(slot->keys.p, 0, sizeof(uint32_t) * total, st));
   lfx::ScanContextArgs a{};
   a.pts = static_cast<const uint8_t *>(c->last_points);
   a.L = c->layout;
   a.scan_begin = c->scan_begin.p;
-  a.table = slot->d.p;
+  a.table = slot->table.d.p;
   a.keys = slot->keys.p;
   a.R = R; a.S = S;
   const lfx::Layout & L = c->layout;
@@ -179,8 +174,7 @@ int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uin
   hipLaunchKernelGGL(lfx::scan_context_finish_kernel, dim3((uint32_t)((total + lfx::kPlaceThreads - 1) / lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
     slot->keys.p, d_desc_out, total, cfg->sensor_height);
   LFX_HIP(c, hipGetLastError());
-  LFX_HIP(c, hipEventRecord(slot->used, st));
-  return LFX_OK;
+  return slot->table.used.done(c, st);
 }
 
 int lfx_place_db_create(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32_t capacity, lfx_place_db ** out)
@@ -203,10 +197,6 @@ int lfx_place_db_create(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32
   if (db->desc.alloc((size_t)capacity * cells_of(*cfg)) != hipSuccess || db->norms.alloc((size_t)capacity * cfg->n_sectors) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the place index's descriptors");
   }
-  if (hipEventCreateWithFlags(&db->added, hipEventDisableTiming) != hipSuccess) {
-    db->added = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the place index's event");
-  }
   *out = db;
   return LFX_OK;
 }
@@ -215,7 +205,6 @@ void lfx_place_db_destroy(lfx_place_db * db)
 {
   if (!db) {return;}
   (void)hipSetDevice(db->device);
-  if (db->added) {(void)hipEventSynchronize(db->added); (void)hipEventDestroy(db->added);}
   delete db;
 }
 
@@ -236,7 +225,8 @@ int lfx_place_db_add_host(lfx_ctx * c, lfx_place_db * db, const float * desc, ui
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // (the add before may still read the staged descriptors, on whichever stream)
-  if (db->add_pending) {LFX_HIP(c, hipEventSynchronize(db->added)); db->add_pending = false;}
+  const int rs = db->added.settle(c);
+  if (rs != LFX_OK) {return rs;}
   const size_t floats = (size_t)n * cells_of(db->cfg);
   if (hold(db->staged, floats) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the descriptors");}
   LFX_HIP(c, hipMemcpyAsync(db->staged.p, desc, sizeof(float) * floats, hipMemcpyHostToDevice, st));
@@ -259,7 +249,8 @@ int lfx_place_db_download(lfx_ctx * c, const lfx_place_db * db, uint32_t first, 
   if (count == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  const int rb = db->added.order_behind(c, st);
+  if (rb != LFX_OK) {return rb;}
   const size_t cells = cells_of(db->cfg);
   LFX_HIP(c, hipMemcpyAsync(desc_out, db->desc.p + (size_t)first * cells, sizeof(float) * cells * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -285,7 +276,8 @@ int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_des
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
   }
-  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  const int rb = db->added.order_behind(c, st);
+  if (rb != LFX_OK) {return rb;}
   lfx_scan_context_config cfg = db->cfg;
   const int rn = launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st);
   if (rn != LFX_OK) {return rn;}
@@ -338,7 +330,8 @@ int lfx_place_db_query_gated(lfx_ctx * c, const lfx_place_db * db, const float *
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
   }
-  if (db->add_pending) {LFX_HIP(c, hipStreamWaitEvent(st, db->added, 0));}
+  const int rb = db->added.order_behind(c, st);
+  if (rb != LFX_OK) {return rb;}
   // (the call is synchronous: the pinned blocks are free again when it returns)
   static_assert(sizeof(lfx::PlaceGate) == sizeof(lfx_place_gate), "the kernel's gate is the header's");
   std::memcpy(db->h_gates.p, gates, sizeof(lfx::PlaceGate) * n_queries);

@@ -46,8 +46,8 @@ struct lfx_pose_graph
   DevBuf<lfx::PgRecord> record;
   PinnedBuf h_record;
   PinnedBuf h_poses;                     // poses on their way up ([max_nodes][12]): pinned, so that the copy is queued and the call returns
-  mutable hipEvent_t tail = nullptr;     // recorded behind the last call that touched the graph, on its stream
-  mutable bool pending = false;
+  Tail tail;                             // behind the last call that touched the graph: order_behind before a call's own
+                                         // work, done after it; settle before the host's staging vectors are rewritten
 };
 
 namespace
@@ -59,38 +59,7 @@ struct Timed : TimedSpan                 // whenever profiling is on: the sampli
   : TimedSpan(c, c->profiling, k, s) {}
 };
 
-bool finite_all(const double * v, size_t n)
-{
-  for (size_t i = 0; i < n; i++) {
-    if (!std::isfinite(v[i])) {return false;}
-  }
-  return true;
-}
-
-int check_graph(lfx_ctx * c, const lfx_pose_graph * g)
-{
-  if (g->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph lives on another device");}
-  return LFX_OK;
-}
-
-// `st` behind the graph's last call; after the call's own work: done()
-int order_behind(lfx_ctx * c, const lfx_pose_graph * g, hipStream_t st)
-{
-  if (g->pending) {LFX_HIP(c, hipStreamWaitEvent(st, g->tail, 0));}
-  return LFX_OK;
-}
-int done(lfx_ctx * c, const lfx_pose_graph * g, hipStream_t st)
-{
-  LFX_HIP(c, hipEventRecord(g->tail, st));
-  g->pending = true;
-  return LFX_OK;
-}
-// the host's staging vectors may be rewritten
-int settle(lfx_ctx * c, const lfx_pose_graph * g)
-{
-  if (g->pending) {LFX_HIP(c, hipEventSynchronize(g->tail)); g->pending = false;}
-  return LFX_OK;
-}
+int check_graph(lfx_ctx * c, const lfx_pose_graph * g) {return check_device(c, g->device, "the pose graph");}
 
 uint32_t ldy_of(uint32_t n_loop) {return (6u * n_loop + 1u + 7u) & ~7u;}
 
@@ -111,7 +80,7 @@ lfx::PgArgs args_of(lfx_pose_graph * g)
 int upload_topology(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
 {
   const uint32_t N = g->n_nodes, E = g->n_edges, L = g->n_loop;
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   std::vector<uint32_t> & w = g->stage_lists;
   w.assign((size_t)N + 1u + 2u * (size_t)E + N + L, 0u);
@@ -294,10 +263,6 @@ int lfx_pose_graph_create(lfx_ctx * c, const lfx_pose_graph_config * config, lfx
   if (g->h_poses.reserve(sizeof(double) * 12u * N) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's staging block");
   }
-  if (hipEventCreateWithFlags(&g->tail, hipEventDisableTiming) != hipSuccess) {
-    g->tail = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the pose graph's event");
-  }
   g->edge_i.reserve(E); g->edge_j.reserve(E); g->edge_loop.reserve(E);
   g->chain_edge.reserve(N); g->fixed.reserve(N);
   *out = g;
@@ -308,7 +273,6 @@ void lfx_pose_graph_destroy(lfx_pose_graph * g)
 {
   if (!g) {return;}
   (void)hipSetDevice(g->device);
-  if (g->tail) {(void)hipEventSynchronize(g->tail); (void)hipEventDestroy(g->tail);}
   delete g;
 }
 
@@ -333,7 +297,7 @@ int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * pos
   if (n == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   const uint32_t first = g->n_nodes;
   std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * n);
@@ -345,7 +309,7 @@ int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * pos
   g->n_nodes += n;
   g->topology_stale = true;
   g->linearised = false;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int fixed, void * stream)
@@ -355,12 +319,12 @@ int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int
   if (node >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "node " + std::to_string(node) + " is not in the graph");}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   if (node == 0u) {g->first_fixed = fixed != 0;}
   g->fixed[node] = ((node == 0u && !g->released) || fixed) ? 1 : 0;
   LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, st));
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_graph_edge * edges, uint32_t n, void * stream)
@@ -401,7 +365,7 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
   if (n == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   g->stage_edges.resize(n);
   for (uint32_t k = 0; k < n; k++) {
@@ -419,7 +383,7 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
   g->n_loop += loops;
   g->topology_stale = true;
   g->linearised = false;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_result * result, void * stream)
@@ -433,7 +397,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
     const int ru = upload_topology(c, g, st);
     if (ru != LFX_OK) {return ru;}
   }
-  int rc = order_behind(c, g, st);
+  int rc = g->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   const lfx::PgArgs a = args_of(g);
   const size_t pose_bytes = sizeof(double) * 12u * g->n_nodes;
@@ -484,7 +448,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
     g->prior_down = rec[it].n_down_prior; g->prior_chi2 = rec[it].chi2_prior;
   }
   g->linearised = true;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_poses(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * poses_out, void * stream)
@@ -495,7 +459,7 @@ int lfx_pose_graph_poses(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, 
   if (count == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = order_behind(c, g, st);
+  const int rc = g->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipMemcpyAsync(poses_out, g->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -511,12 +475,12 @@ int lfx_pose_graph_set_poses(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, ui
   if (count == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * count);
   LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
   g->linearised = false;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_view(lfx_ctx * c, const lfx_pose_graph * g, const double ** d_poses, uint32_t * n_nodes, void * stream)
@@ -524,7 +488,7 @@ int lfx_pose_graph_view(lfx_ctx * c, const lfx_pose_graph * g, const double ** d
   if (!c || !g || !d_poses || !n_nodes) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = order_behind(c, g, static_cast<hipStream_t>(stream));
+  const int rc = g->tail.order_behind(c, static_cast<hipStream_t>(stream));
   if (rc != LFX_OK) {return rc;}
   *d_poses = g->poses.p;
   *n_nodes = g->n_nodes;
@@ -540,7 +504,7 @@ int lfx_pose_graph_edge_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t fir
   if (count == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = settle(c, g);
+  int rc = g->tail.settle(c);
   if (rc != LFX_OK) {return rc;}
   g->stage_lin.resize((size_t)lfx::kPgLin * count);
   LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->lin.p + (size_t)lfx::kPgLin * first, sizeof(double) * lfx::kPgLin * count, hipMemcpyDeviceToHost, st));
@@ -615,7 +579,7 @@ int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gr
   if (n == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   g->stage_priors.resize(n);
   for (uint32_t k = 0; k < n; k++) {
@@ -630,7 +594,7 @@ int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gr
   g->n_priors += n;
   g->topology_stale = true;
   g->linearised = false;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, void * stream)
@@ -641,11 +605,11 @@ int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, 
   if (g->n_nodes == 0u) {return LFX_OK;}            // (lfx_pose_graph_add_nodes writes node 0's flag)
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = settle(c, g);
+  const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   g->fixed[0] = (!g->released || g->first_fixed) ? 1 : 0;
   LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p, g->fixed.data(), 1, hipMemcpyHostToDevice, st));
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 int lfx_pose_graph_prior_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * rho, double * w, void * stream)
@@ -657,7 +621,7 @@ int lfx_pose_graph_prior_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t fi
   if (count == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = settle(c, g);
+  int rc = g->tail.settle(c);
   if (rc != LFX_OK) {return rc;}
   g->stage_lin.resize((size_t)lfx::kPgPlin * count);
   LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->plin.p + (size_t)lfx::kPgPlin * first, sizeof(double) * lfx::kPgPlin * count, hipMemcpyDeviceToHost, st));
@@ -689,7 +653,7 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
     const int ru = upload_topology(c, g, st);
     if (ru != LFX_OK) {return ru;}
   }
-  int rc = order_behind(c, g, st);
+  int rc = g->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   const lfx::PgArgs a = args_of(g);
   rc = relinearize(c, g, a, st);
@@ -702,7 +666,7 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
   for (uint32_t e = 0; r_out && e < g->n_edges; e++) {std::memcpy(r_out + 6u * (size_t)e, lin.data() + (size_t)lfx::kPgLin * e, sizeof(double) * 6u);}
   *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
   g->linearised = true;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 
 // ... and the same for a graph with priors (edges or none): per prior r [P][6] (may be NULL), per node the gradient of edges
@@ -716,7 +680,7 @@ int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double 
     const int ru = upload_topology(c, g, st);
     if (ru != LFX_OK) {return ru;}
   }
-  int rc = order_behind(c, g, st);
+  int rc = g->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   const lfx::PgArgs a = args_of(g);
   rc = relinearize(c, g, a, st);
@@ -729,7 +693,7 @@ int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double 
   for (uint32_t p = 0; r_out && p < g->n_priors; p++) {std::memcpy(r_out + 6u * (size_t)p, lin.data() + (size_t)lfx::kPgPlin * p, sizeof(double) * 6u);}
   *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
   g->linearised = true;
-  return done(c, g, st);
+  return g->tail.done(c, st);
 }
 #endif
 

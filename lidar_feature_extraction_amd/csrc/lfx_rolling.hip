@@ -53,8 +53,7 @@ struct lfx_rolling_map
   // up.  The table part is not written again before `tail` (recorded behind the previous insert) has passed.
   PinnedBuf pinned;
   size_t pin_table = 0;
-  hipEvent_t tail = nullptr;
-  bool tail_pending = false;
+  Tail tail;
 };
 
 namespace
@@ -62,38 +61,10 @@ namespace
 constexpr uint32_t kInitialEntries = 64;
 constexpr uint64_t kMaxSlots = (uint64_t)1 << 31;
 
-size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
-size_t readback_bytes(uint32_t n, uint32_t stride) {return sizeof(uint32_t) * ((size_t)(n - 1) * stride + 1 + n);}
-
 int check(lfx_ctx * c, const lfx_rolling_map * rm, int kind)
 {
   if (kind != LFX_ROLLING_EDGE && kind != LFX_ROLLING_SURFACE) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "kind must be LFX_ROLLING_EDGE or LFX_ROLLING_SURFACE");}
-  if (rm->device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the rolling map lives on another device");}
-  return LFX_OK;
-}
-
-// the previous insert has passed (the pinned table and the staged cloud may be written again)
-int settle(lfx_ctx * c, lfx_rolling_map * rm)
-{
-  if (!rm->tail_pending) {return LFX_OK;}
-  LFX_HIP(c, hipEventSynchronize(rm->tail));
-  rm->tail_pending = false;
-  return LFX_OK;
-}
-
-// work queued on `st` runs behind the previous insert, whichever stream that went to
-int order_behind(lfx_ctx * c, const lfx_rolling_map * rm, hipStream_t st)
-{
-  if (rm->tail_pending) {LFX_HIP(c, hipStreamWaitEvent(st, rm->tail, 0));}
-  return LFX_OK;
-}
-
-bool finite_all(const double * v, size_t n)
-{
-  for (size_t i = 0; i < n; i++) {
-    if (!std::isfinite(v[i])) {return false;}
-  }
-  return true;
+  return check_device(c, rm->device, "the rolling map");
 }
 
 // The clouds of one insert whose begins and counts are known on the host: the table of the non-empty ones with their
@@ -115,12 +86,12 @@ int insert_clouds(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float4 * sr
   if (rm->table.n < na) {
     DevBuf<lfx::RollInsertEntry> t;
     if (t.alloc(na + na / 2) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the rolling map's table");}
-    const int rs = settle(c, rm);            // (the previous insert may still read the old table)
+    const int rs = rm->tail.settle(c);       // (the previous insert may still read the old table)
     if (rs != LFX_OK) {return rs;}
     rm->table = std::move(t);
   }
   const size_t bytes = sizeof(lfx::RollInsertEntry) * na;
-  int rs = settle(c, rm);
+  int rs = rm->tail.settle(c);               // (the previous insert has passed: the pinned table may be written again)
   if (rs != LFX_OK) {return rs;}
   LFX_HIP(c, rm->pinned.reserve(rm->pin_table + bytes));
   lfx::RollInsertEntry * tab = reinterpret_cast<lfx::RollInsertEntry *>(rm->pinned.p + rm->pin_table);
@@ -148,9 +119,7 @@ int insert_clouds(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float4 * sr
   hipLaunchKernelGGL(lfx::rolling_claim_kernel, dim3(first), dim3(lfx::kRollThreads), 0, st, v, rm->table.p, (uint32_t)na, src, s.epoch, s.counters.p);
   hipLaunchKernelGGL(lfx::rolling_commit_kernel, dim3(first), dim3(lfx::kRollThreads), 0, st, v, rm->table.p, (uint32_t)na, src, s.epoch, s.counters.p);
   LFX_HIP(c, hipGetLastError());
-  LFX_HIP(c, hipEventRecord(rm->tail, st));
-  rm->tail_pending = true;
-  return LFX_OK;
+  return rm->tail.done(c, st);
 }
 
 // the voxel of a coordinate given in metres as a double, clamped to the voxels a key can name
@@ -183,7 +152,7 @@ int extract_box(lfx_ctx * c, const lfx_rolling_map * rm, int kind, const lfx::Ro
   const Store & s = rm->store[kind];
   const uint32_t n_blocks = (uint32_t)(((uint64_t)box.cells + lfx::kRollCells - 1u) / lfx::kRollCells);
   const lfx::RollStore v = s.view();
-  int rc = order_behind(c, rm, st);
+  int rc = rm->tail.order_behind(c, st);     // (the previous insert may be queued on another stream)
   if (rc != LFX_OK) {return rc;}
   hipLaunchKernelGGL(lfx::rolling_block_count_kernel, dim3(n_blocks), dim3(lfx::kRollThreads), 0, st, v, box, rm->partial.p);
   hipLaunchKernelGGL(lfx::rolling_partial_scan_kernel, dim3(1), dim3(lfx::kRollThreads), 0, st, rm->partial.p, n_blocks, rm->total.p);
@@ -364,10 +333,6 @@ int lfx_rolling_map_create(lfx_ctx * c, const lfx_rolling_map_config * cfg, lfx_
   rm->emap = map_new(c->device);
   rm->smap = map_new(c->device);
   if (!rm->emap || !rm->smap) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the match maps");}
-  if (hipEventCreateWithFlags(&rm->tail, hipEventDisableTiming) != hipSuccess) {
-    rm->tail = nullptr;
-    return give_up(LFX_ERR_HIP, "cannot create the rolling map's event");
-  }
   // key 0: never written; stamp 0: older than every bid
   hipError_t e = hipMemset(rm->zero.p, 0, 4 * sizeof(uint32_t));
   for (int k = 0; k < 2 && e == hipSuccess; k++) {
@@ -386,10 +351,10 @@ void lfx_rolling_map_destroy(lfx_rolling_map * rm)
 {
   if (!rm) {return;}
   (void)hipSetDevice(rm->device);
-  if (rm->tail) {(void)hipEventSynchronize(rm->tail); (void)hipEventDestroy(rm->tail);}
-  lfx_map_destroy(rm->emap);
-  lfx_map_destroy(rm->smap);
-  delete rm;
+  lfx_map * const emap = rm->emap, * const smap = rm->smap;
+  delete rm;                                 // (waits for the tail: the match maps go after it, as the buffers do)
+  lfx_map_destroy(emap);
+  lfx_map_destroy(smap);
 }
 
 int lfx_rolling_map_recenter(lfx_rolling_map * rm, const double center[3])
@@ -419,30 +384,16 @@ int lfx_rolling_map_insert(lfx_ctx * c, lfx_rolling_map * rm, int kind, const fl
   if (check(c, rm, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = order_behind(c, rm, st);
+  int rc = rm->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
-  // the counts (a strided span, read whole) and the begins back in one wait: the call's only one
-  const size_t span = (size_t)(n_clouds - 1) * count_stride + 1;
-  const size_t need = readback_bytes(n_clouds, count_stride);
-  if (need > rm->pin_table) {
-    rc = settle(c, rm);                      // (the block moves: nothing may still read the table in it)
-    if (rc != LFX_OK) {return rc;}
-    const size_t at = round64(need);
-    LFX_HIP(c, rm->pinned.reserve(at + sizeof(lfx::RollInsertEntry) * std::max<size_t>(n_clouds, kInitialEntries)));
-    rm->pin_table = at;
-  }
-  uint32_t * h_count = reinterpret_cast<uint32_t *>(rm->pinned.p), * h_begin = h_count + span;
-  LFX_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint32_t) * span, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipMemcpyAsync(h_begin, d_begin, sizeof(uint32_t) * n_clouds, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::vector<uint32_t> begin(h_begin, h_begin + n_clouds), count(n_clouds);
-  for (uint32_t s = 0; s < n_clouds; s++) {
-    count[s] = h_count[(size_t)s * count_stride];
-    if ((uint64_t)begin[s] + count[s] > total_points) {
-      return fail(c, LFX_ERR_INVALID_ARGUMENT, "cloud " + std::to_string(s) + " (records " + std::to_string(begin[s]) + " + " +
-               std::to_string(count[s]) + ") runs past total_points (" + std::to_string(total_points) + ")");
-    }
-  }
+  // the counts and the begins back in one wait: the call's only one
+  rc = grow_readback(c, rm->tail, rm->pinned, rm->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::RollInsertEntry),
+    std::max<size_t>(n_clouds, kInitialEntries));
+  if (rc != LFX_OK) {return rc;}
+  const CloudList list{d_begin, d_count, count_stride, total_points, ""};
+  std::vector<uint32_t> begin, count;
+  rc = read_lists(c, &list, 1, n_clouds, rm->pinned.p, &begin, &count, st);
+  if (rc != LFX_OK) {return rc;}
   return insert_clouds(c, rm, kind, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses, st);
 }
 
@@ -455,7 +406,7 @@ int lfx_rolling_map_insert_host(lfx_ctx * c, lfx_rolling_map * rm, int kind, con
   if (n_points == 0) {return LFX_OK;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = settle(c, rm);                    // (the previous insert may still read the staged cloud)
+  int rc = rm->tail.settle(c);               // (the previous insert may still read the staged cloud)
   if (rc != LFX_OK) {return rc;}
   if (hold(rm->staged, n_points) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the cloud");}
   LFX_HIP(c, hipMemcpyAsync(rm->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, st));
@@ -488,7 +439,7 @@ int lfx_rolling_map_view(lfx_ctx * c, const lfx_rolling_map * rm, lfx_rolling_ma
   if (check(c, rm, LFX_ROLLING_EDGE) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = order_behind(c, rm, st);
+  int rc = rm->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   lfx_rolling_map_view_t out{};
   uint64_t * h = reinterpret_cast<uint64_t *>(rm->pinned.p);

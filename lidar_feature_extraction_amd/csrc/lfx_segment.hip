@@ -18,11 +18,12 @@ uint32_t blocks_for(size_t n) {return (uint32_t)((n + lfx::kSegThreads - 1) / lf
 int take_workspace(lfx_ctx * c, size_t cells, hipStream_t st)
 {
   lfx_ctx::SegmentWork & w = c->seg;
-  if (!w.used) {LFX_HIP(c, hipEventCreateWithFlags(&w.used, hipEventDisableTiming));}
-  LFX_HIP(c, hipStreamWaitEvent(st, w.used, 0));
+  int rc = w.used.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
   if (w.image.n < cells) {
     // (growing frees what the call before may still use; to the size asked for and no further: the budget is the most it takes)
-    LFX_HIP(c, hipEventSynchronize(w.used));
+    rc = w.used.settle(c);
+    if (rc != LFX_OK) {return rc;}
     if (hold(w.image, cells, true) != hipSuccess || hold(w.cell, cells, true) != hipSuccess || hold(w.parent, cells, true) != hipSuccess ||
       hold(w.csize, cells, true) != hipSuccess || hold(w.crowmax, cells, true) != hipSuccess)
     {
@@ -45,7 +46,10 @@ int put_tables(lfx_ctx * c, const lfx_segment_config & cfg, const std::vector<do
   }
   lfx_ctx::SegmentWork::Table & t = w.tables[w.table_next];
   const size_t bytes = sizeof(double) * table.size();
-  if (t.columns) {LFX_HIP(c, hipEventSynchronize(w.used));}         // (a refill: what read the slot, and its block, is done)
+  if (t.columns) {                           // (a refill: what read the slot, and its block, is done)
+    const int rs = w.used.settle(c);
+    if (rs != LFX_OK) {return rs;}
+  }
   t.columns = 0;
   if (t.h.reserve(bytes) != hipSuccess || hold(t.d, table.size()) != hipSuccess) {
     (void)hipGetLastError();
@@ -53,7 +57,8 @@ int put_tables(lfx_ctx * c, const lfx_segment_config & cfg, const std::vector<do
   }
   std::memcpy(t.h.p, table.data(), bytes);
   LFX_HIP(c, hipMemcpyAsync(t.d.p, t.h.p, bytes, hipMemcpyHostToDevice, st));
-  LFX_HIP(c, hipEventRecord(w.used, st));
+  const int rd = w.used.done(c, st);
+  if (rd != LFX_OK) {return rd;}
   t.columns = cfg.n_columns;
   t.row_step = cfg.row_step;
   w.table_next = (w.table_next + 1u) % lfx_ctx::SegmentWork::kSegTables;
@@ -129,8 +134,7 @@ int lfx_segment_batch(lfx_ctx * c, const lfx_segment_config * cfg, uint32_t n_sc
     hipLaunchKernelGGL(xyz16 ? lfx::segment_record_kernel<true> : lfx::segment_record_kernel<false>, by_scan, threads, 0, st, a);
     LFX_HIP(c, hipGetLastError());
   }
-  LFX_HIP(c, hipEventRecord(w.used, st));
-  return LFX_OK;
+  return w.used.done(c, st);
 }
 
 int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t edge_mask, uint32_t surface_mask, float * d_edge_out,
@@ -148,10 +152,11 @@ int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t e
     a.counts = d_counts_out;
   } else {
     // (the context's own: calls on different streams take them one behind the other, as the images)
-    if (!w.used) {LFX_HIP(c, hipEventCreateWithFlags(&w.used, hipEventDisableTiming));}
-    LFX_HIP(c, hipStreamWaitEvent(st, w.used, 0));
+    int rc = w.used.order_behind(c, st);
+    if (rc != LFX_OK) {return rc;}
     if (w.pack_counts.n < 2u * (size_t)batch) {
-      LFX_HIP(c, hipEventSynchronize(w.used));
+      rc = w.used.settle(c);
+      if (rc != LFX_OK) {return rc;}
       if (hold(w.pack_counts, 2u * (size_t)batch) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the filtered pack's counts");
@@ -172,8 +177,7 @@ int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t e
   launch_feature_offsets(a.counts, a.counts + batch, 1u, batch, d_offsets_out, st);
   hipLaunchKernelGGL(lfx::segment_pack_kernel, grid, threads, 0, st, a);
   LFX_HIP(c, hipGetLastError());
-  if (!d_counts_out) {LFX_HIP(c, hipEventRecord(w.used, st));}
-  return LFX_OK;
+  return d_counts_out ? LFX_OK : w.used.done(c, st);
 }
 
 }  // extern "C"
