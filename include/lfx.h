@@ -459,7 +459,15 @@ int lfx_map_nearest(lfx_ctx *ctx, const lfx_map *map, const double *d_queries, u
  * doubles per point, row-major.  n_neighbors <= 16 (the localizer uses 15).  Exact nearest-neighbour search (the
  * reference's nanoflann KD-tree is exact too).  PARITY UNPINNED: Eigen's and nanoflann's arithmetic is not available
  * here; tolerance-level agreement with the CPU restatement, edge rows up to the sign of the principal direction (see
- * DESIGN.md).  Asynchronous. */
+ * DESIGN.md).  Asynchronous.
+ * The principal direction u is found in closed form; with l1 >= l2 >= l3 the covariance's eigenvalues and kappa =
+ * l1 / (l1 - l2), |sin(u, the true direction)| <= 2^-53 (8 kappa + 4 kappa^2) (linear for line-like neighbourhoods,
+ * quadratic for nearly round discs: below what half a float32 spacing of the map's coordinates moves the direction for
+ * kappa < 1e8), |u| = 1 to 4 x 2^-53, and the row's Hat block is Hat(2 u) exactly, wherever the map lies.  An isotropic
+ * neighbourhood (l1 = l3: one point, +-e_i, a cube's corners) gives the row of u = (0, 0, 1).
+ * The quaternion q of the pose is Eigen::Quaterniond(Matrix3d)'s: trace > 0 -> w > 0; otherwise the component of the
+ * largest diagonal entry is the positive one (the first of equal entries) -- that fixes q's sign and with it the sign of
+ * the four quaternion columns of every row.  (tests/test_rows_gpu.py holds all of this against a 50-digit reference.) */
 #define LFX_RESIDUAL_EDGE 0
 #define LFX_RESIDUAL_SURFACE 1
 int lfx_scan_to_map_residuals(lfx_ctx *ctx, int kind, const lfx_map *map, const double pose[12], uint32_t n_neighbors,

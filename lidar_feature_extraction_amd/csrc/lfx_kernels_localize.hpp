@@ -475,7 +475,9 @@ __device__ __forceinline__ void row_from_neighbours(
     for (int a = 0; a < 6; a++) {c[a] /= nk;}
     const D3 u = principal_direction(c);
     const D3 p1{mx - u.x, my - u.y, mz - u.z}, p2{mx + u.x, my + u.y, mz + u.z};
-    const D3 e = d3_sub(p2, p1);
+    // p2 - p1 is 2 u; taken from the rounded p1 and p2 it would lose the direction to the spacing of the mean's coordinates
+    // (2^-53 |mean| in u: 4 000 times the closed form's own error five kilometres from the origin)
+    const D3 e{2. * u.x, 2. * u.y, 2. * u.z};
     const double K[9] = {0., -e.z, e.y, e.z, 0., -e.x, -e.y, e.x, 0.};       // Hat(p2 - p1)
     double * J = J_out;
 #pragma unroll
