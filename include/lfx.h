@@ -1448,6 +1448,116 @@ int lfx_keyframes_submap(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind,
  * chunk by chunk, so a save needs no second copy of the records on the device.  Synchronous. */
 int lfx_keyframes_save(lfx_ctx *ctx, const lfx_keyframes *keyframes, const char *dirname, int written[2], void *stream);
 
+/* --- visibility votes: records that moved while the map was recorded, found from the keyframes that looked through them --- */
+/* "Was this record still there when the sensor came by again?"  No reference counterpart; the model is Removert (Kim and Kim,
+ * IROS 2020) and the visibility checks of ERASOR-style cleaners, over what the keyframe store already holds: sensor-frame
+ * records and one pose per keyframe (best after lfx_loop_closer_update).  If keyframe v looked through the place where
+ * keyframe k left a record and saw something clearly farther away, the record was not there when v looked.
+ * THE DEFAULTS are Removert's or a numpy prototype's on a synthetic room; NONE IS MEASURED on real data, and neither is the
+ * occupancy of images built from real feature clouds (lfx_visibility_result.occupied_cells is there so a caller sees it).
+ * LIMITS: feature records only (the store holds nothing else); a viewer whose centre cell is empty gives no evidence; an
+ * object that never moves while it is observed stays.
+ *
+ * Tables (lfx_visibility_tables, host only, the ONLY source: the device is given exactly these values):
+ *   col_cos[m], col_sin[m]: lfx_segment_tables' values for W columns;
+ *   row_tan[j] = tan((double)elev_min + (double)j * (double)elev_step), j = 0 .. H.
+ * All arithmetic below is in double, unfused, on floats.
+ *
+ * Cell of a point (x, y, z), doubles:
+ *   - skipped if a coordinate is not finite, or if x*x + y*y == 0;
+ *   - rho = sqrt(x*x + y*y), r = sqrt((x*x + y*y) + z*z); skipped if r < (double)min_range or r >= (double)max_range;
+ *   - column: the segmentation's bisection: m0 = y >= 0 ? W/2 : 0;  cross(m) = col_cos[m]*y - col_sin[m]*x;
+ *       lo = 0, hi = W/2 - 1; while (lo < hi) { mid = (lo + hi + 1) >> 1; if (cross(m0 + mid) >= 0) lo = mid; else hi = mid - 1; }
+ *     column = m0 + lo;
+ *   - row: skipped if z < row_tan[0]*rho or z >= row_tan[H]*rho (one rounded product, one comparison); otherwise the largest
+ *     j < H with z >= row_tan[j]*rho: lo = 0, hi = H - 1; while (lo < hi) { mid = (lo + hi + 1) >> 1;
+ *     if (z >= row_tan[mid]*rho) lo = mid; else hi = mid - 1; }  row = lo.  No atan2 and no asin anywhere.
+ * Image of viewer v, from v's own stored records of both kinds in the sensor frame as stored: cell (row, column) holds the
+ *   least (float)r of the records that fall into it; a cell without a record is empty.  A minimum over a set: whatever the
+ *   schedule.
+ * Vote of viewer v on record p of target keyframe k.  The pair qualifies when k != v, both lie in the call's window
+ *   [first, first + count), and (dx^2 + dy^2) + dz^2 <= radius^2 between the two poses' translations (lfx_keyframes_submap's
+ *   rule and order).  Then
+ *     w = the float world record lfx_keyframes_build writes for p;  d = (double)w - t_v (three subtractions);
+ *     q_x = (R00*dx + R10*dy) + R20*dz, q_y = (R01*dx + R11*dy) + R21*dz, q_z = (R02*dx + R12*dy) + R22*dz, R = R_v;
+ *     the cell and r_q of q as above -- q skipped: no vote;  m = max((double)margin_abs, (double)margin_rel * r_q);
+ *     centre cell empty: no vote;
+ *     an occupied cell with value R of the window -- rows row-guard .. row+guard clipped to [0, H), columns col-guard ..
+ *       col+guard taken mod W -- OBJECTS iff (double)R <= r_q + m; empty cells do not object;
+ *     THROUGH: no cell of the window objects.   AGREE: r_q - m <= (double)R_centre && (double)R_centre <= r_q + m.
+ *   The two exclude each other; a record that gets neither is occluded from v.
+ * Per record: through and agree, the counts over all qualifying viewers; a window holds at most LFX_VISIBILITY_MAX_WINDOW
+ *   keyframes, so both fit 16 bits.  The vote word is through | agree << 16.  DYNAMIC (flag byte 1, otherwise 0) iff
+ *   through >= min_through && (uint64)agree * agree_weight < through.  A record of a keyframe without viewers has word 0 and
+ *   flag 0.  Every count is an integer: the same store, poses and config give the same bytes whatever the schedule and
+ *   however the viewers are chunked. */
+#define LFX_VISIBILITY_MAX_WINDOW 65536u
+#define LFX_VISIBILITY_SCRATCH_WORDS (1u << 22)
+typedef struct lfx_visibility lfx_visibility;
+typedef struct lfx_visibility_config {
+  uint32_t n_rows;              /* H: 32; 1 .. 128 */
+  uint32_t n_columns;           /* W: 360; even, 4 .. 4096 */
+  float elev_min, elev_step;    /* -0.43633232 (-25 degrees), 0.027270770 (50 degrees / 32); elev_step > 0, elev_min > -pi/2,
+                                   elev_min + H * elev_step < pi/2 (in double) */
+  float min_range, max_range;   /* 1.0, 100.0; 0 < min_range < max_range, finite */
+  float radius;                 /* 15.0; finite, >= 0: a viewer lies within it of the target keyframe */
+  float margin_abs, margin_rel; /* 0.3, 0.02; finite, >= 0 */
+  uint32_t guard;               /* 1; 0 .. 2: the window is (2 guard + 1)^2 cells */
+  uint32_t min_through;         /* 2; >= 1 */
+  uint32_t agree_weight;        /* 1; >= 0 */
+  uint32_t reserved;            /* 0 */
+} lfx_visibility_config;
+typedef struct lfx_visibility_info_t {
+  lfx_visibility_config config;
+  uint32_t max_window, max_resident_images;
+  uint64_t device_bytes;        /* everything lfx_visibility_create allocated on the device */
+} lfx_visibility_info_t;
+typedef struct lfx_visibility_result {
+  uint64_t n_pairs;             /* ordered pairs (k, v) of non-empty keyframes of the window that qualify */
+  uint64_t n_records[2];        /* per kind: the window's records, */
+  uint64_t n_voted[2];          /*   those with a vote word != 0, */
+  uint64_t n_dynamic[2];        /*   those flagged; all counted on the device */
+  uint64_t occupied_cells;      /* of the viewers' images (the window's non-empty keyframes), */
+  uint64_t total_cells;         /*   of their H * W cells each */
+  uint32_t n_viewer_chunks;     /* ceil(non-empty keyframes of the window / max_resident_images) */
+  uint32_t reserved;
+} lfx_visibility_result;
+void lfx_visibility_default_config(lfx_visibility_config *config);
+/* host only, no context.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, every field outside the ranges above, reserved != 0. */
+int lfx_visibility_tables(const lfx_visibility_config *config, double *col_cos /*[W]*/, double *col_sin /*[W]*/, double *row_tan /*[H+1]*/);
+/* Everything on the device is allocated here: the images (max_resident_images x H x W words), the tables, the viewer list,
+ * the counters, LFX_VISIBILITY_SCRATCH_WORDS vote words for callers that pass no d_votes, and a pinned block; no later call
+ * allocates device memory.  1 <= max_resident_images <= max_window <= LFX_VISIBILITY_MAX_WINDOW.  A window with more non-
+ * empty keyframes than max_resident_images is processed in chunks of that many viewers, in ascending id and in stream order.
+ * LFX_ERR_INVALID_ARGUMENT: what lfx_visibility_tables refuses and capacities outside that; LFX_ERR_OUT_OF_MEMORY with nothing
+ * left allocated. */
+int lfx_visibility_create(lfx_ctx *ctx, const lfx_visibility_config *config, uint32_t max_window, uint32_t max_resident_images,
+                          lfx_visibility **out);
+void lfx_visibility_destroy(lfx_visibility *visibility);
+int lfx_visibility_info(const lfx_visibility *visibility, lfx_visibility_info_t *info);
+/* The votes of keyframes [first, first + count) on each other.  d_votes[kind][i] (u32, an entry may be NULL) and
+ * d_flags[kind][i] (u8, required) are addressed by the STORE's record index of the kind, begin[kind][first] <= i <
+ * begin[kind][first + count]; nothing outside that is touched.  Ordered behind the store's earlier calls through the store's
+ * event, as every store call is, and behind this object's earlier runs; recorded behind itself on both.  One wait, for
+ * *result.  Between chunks of viewers a record's counts live in its own vote word -- no atomic touches a vote -- which is
+ * d_votes[kind][i] or, where that is NULL, the object's own LFX_VISIBILITY_SCRATCH_WORDS words (edge records first): a run
+ * that needs more than one chunk, passes a NULL d_votes entry and has more records of those kinds than that is
+ * LFX_ERR_CAPACITY (pass d_votes, or keep more images resident).  LFX_ERR_INVALID_ARGUMENT, before anything is queued: NULL
+ * pointers, a window past the store, count > max_window.  count 0, or only empty keyframes: LFX_OK, *result zero, no launch. */
+int lfx_visibility_run(lfx_ctx *ctx, lfx_visibility *visibility, const lfx_keyframes *keyframes, uint32_t first, uint32_t count,
+                       uint32_t *const d_votes[2], uint8_t *const d_flags[2], lfx_visibility_result *result, void *stream);
+/* lfx_keyframes_build with the records whose flag byte is non-zero left out and the order kept: d_flags[i] (u8, device) is
+ * addressed by the store's record index of `kind`, as lfx_visibility_run writes it; a kept record is byte for byte what
+ * lfx_keyframes_build writes.  d_begin_out (device, [count + 1], may be NULL): the exclusive prefix of the kept counts per
+ * keyframe -- narrowed to 32 bits, with its differences, what lfx_mapper_add and lfx_keyframes_add take.  One wait, for
+ * *n_out (the kept records are counted on the device).  More kept records than capacity_points is LFX_ERR_CAPACITY with
+ * *n_out = the records needed and no record written.  count 0, or keyframes that are all empty: LFX_OK, *n_out = 0,
+ * d_begin_out zero.  The counts per 1 024 records live in a table lfx_keyframes_create allocates (8 bytes per 1 024 records
+ * of the larger max_points). */
+int lfx_keyframes_build_masked(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind, uint32_t first, uint32_t count,
+                               const uint8_t *d_flags, float *d_out, uint64_t capacity_points, uint64_t *d_begin_out,
+                               uint64_t *n_out, void *stream);
+
 /* --- the loop closer: revisits found, verified and closed over a store, an index and a graph ------------------------------ */
 /* What joins the sections above.  No reference counterpart; the model is LIO-SAM's loop-closure thread (Shan et al., IROS 2020)
  * with Scan Context as the detector.  THE CONTRACT: keyframe id == place entry == graph node id -- the caller adds a keyframe to

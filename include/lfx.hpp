@@ -978,6 +978,16 @@ public:
     Check(lfx_keyframes_build(fx_.handle(), store_, kind, first, count, d_out, capacity_points, &n, stream));
     return n;
   }
+  // Build without the records whose byte of d_flags (device, addressed by the store's record index of `kind`: what
+  // Visibility::Run writes) is non-zero; the kept records.  d_begin_out (device, [count + 1], may be null): the kept records
+  // before each keyframe.  Waits once, for the count.
+  std::uint64_t BuildMasked(Kind kind, std::uint32_t first, std::uint32_t count, const std::uint8_t * d_flags, float * d_out,
+    std::uint64_t capacity_points, std::uint64_t * d_begin_out = nullptr, void * stream = nullptr) const
+  {
+    std::uint64_t n = 0;
+    Check(lfx_keyframes_build_masked(fx_.handle(), store_, kind, first, count, d_flags, d_out, capacity_points, d_begin_out, &n, stream));
+    return n;
+  }
   // the records Build would write (from the host's mirror; nothing is queued)
   std::uint64_t Points(Kind kind, std::uint32_t first, std::uint32_t count) const
   {
@@ -1016,6 +1026,52 @@ private:
   }
   const FeatureExtraction & fx_;
   lfx_keyframes * store_ = nullptr;
+};
+
+// Visibility votes (lfx_visibility): which records of a window of a Keyframes store's keyframes were looked through by the
+// keyframes near them, and the DYNAMIC flag that decides.  None of the defaults is measured on real data.
+class Visibility
+{
+public:
+  static lfx_visibility_config DefaultConfig()
+  {
+    lfx_visibility_config config;
+    lfx_visibility_default_config(&config);
+    return config;
+  }
+  Visibility(const FeatureExtraction & fx, const lfx_visibility_config & config, std::uint32_t max_window, std::uint32_t max_resident_images)
+  : fx_(fx)
+  {
+    Check(lfx_visibility_create(fx.handle(), &config, max_window, max_resident_images, &vis_));
+  }
+  ~Visibility() {lfx_visibility_destroy(vis_);}
+  Visibility(const Visibility &) = delete;
+  Visibility & operator=(const Visibility &) = delete;
+
+  // the votes of keyframes [first, first + count) on each other: d_flags[kind] (device u8, required) and d_votes[kind] (device
+  // u32, either may be null) addressed by the store's record index of the kind.  Waits once, for the result.
+  lfx_visibility_result Run(const Keyframes & keyframes, std::uint32_t first, std::uint32_t count, std::uint32_t * const d_votes[2],
+    std::uint8_t * const d_flags[2], void * stream = nullptr)
+  {
+    lfx_visibility_result r;
+    Check(lfx_visibility_run(fx_.handle(), vis_, keyframes.handle(), first, count, d_votes, d_flags, &r, stream));
+    return r;
+  }
+  lfx_visibility_info_t Info() const
+  {
+    lfx_visibility_info_t i;
+    lfx_visibility_info(vis_, &i);
+    return i;
+  }
+  lfx_visibility * handle() const {return vis_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_visibility * vis_ = nullptr;
 };
 
 // The loop closer (lfx_loop_closer): revisits found in a PlaceDb, verified against submaps of a Keyframes store and closed in

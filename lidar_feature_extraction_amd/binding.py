@@ -272,6 +272,27 @@ KEYFRAMES_EDGE, KEYFRAMES_SURFACE = 0, 1
 KEYFRAMES_NO_ID = 0xFFFFFFFF
 
 
+class VisibilityConfig(C.Structure):
+    """lfx_visibility_config: the range images, the pairs that vote and the decision (include/lfx.h, the visibility section)."""
+    _fields_ = [("n_rows", C.c_uint32), ("n_columns", C.c_uint32), ("elev_min", C.c_float), ("elev_step", C.c_float),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("radius", C.c_float), ("margin_abs", C.c_float),
+                ("margin_rel", C.c_float), ("guard", C.c_uint32), ("min_through", C.c_uint32), ("agree_weight", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class VisibilityInfo(C.Structure):
+    _fields_ = [("config", VisibilityConfig), ("max_window", C.c_uint32), ("max_resident_images", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
+class VisibilityResult(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_records", C.c_uint64 * 2), ("n_voted", C.c_uint64 * 2), ("n_dynamic", C.c_uint64 * 2),
+                ("occupied_cells", C.c_uint64), ("total_cells", C.c_uint64), ("n_viewer_chunks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+VISIBILITY_MAX_WINDOW = 65536
+VISIBILITY_SCRATCH_WORDS = 1 << 22
+
+
 class PlaceGate(C.Structure):
     """lfx_place_gate: the entries one query of lfx_place_db_query_gated may match (e < limit, near pose `pose`)."""
     _fields_ = [("limit", C.c_uint32), ("pose", C.c_uint32)]
@@ -351,7 +372,9 @@ EXPORTS = [
     "lfx_pose_graph_prior_info",
     "lfx_keyframes_default_config", "lfx_keyframes_create", "lfx_keyframes_destroy", "lfx_keyframes_info", "lfx_keyframes_view",
     "lfx_keyframes_add", "lfx_keyframes_add_host", "lfx_keyframes_set_poses", "lfx_keyframes_poses", "lfx_keyframes_follow",
-    "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save",
+    "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save", "lfx_keyframes_build_masked",
+    "lfx_visibility_default_config", "lfx_visibility_tables", "lfx_visibility_create", "lfx_visibility_destroy", "lfx_visibility_info",
+    "lfx_visibility_run",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -559,6 +582,16 @@ def load(test_hooks=False):
     L.lfx_keyframes_build.argtypes = [vp, vp, i32, u32, u32, vp, u64, p64, vp]
     L.lfx_keyframes_submap.argtypes = [vp, vp, i32, vp, C.c_double, u32, u32, vp, u64, C.POINTER(KeyframesSubmapResult), vp]
     L.lfx_keyframes_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
+    L.lfx_keyframes_build_masked.argtypes = [vp, vp, i32, u32, u32, vp, vp, u64, vp, p64, vp]
+    pvc = C.POINTER(VisibilityConfig)
+    L.lfx_visibility_default_config.argtypes = [pvc]
+    L.lfx_visibility_default_config.restype = None
+    L.lfx_visibility_tables.argtypes = [pvc, vp, vp, vp]
+    L.lfx_visibility_create.argtypes = [vp, pvc, u32, u32, C.POINTER(vp)]
+    L.lfx_visibility_destroy.argtypes = [vp]
+    L.lfx_visibility_destroy.restype = None
+    L.lfx_visibility_info.argtypes = [vp, C.POINTER(VisibilityInfo)]
+    L.lfx_visibility_run.argtypes = [vp, vp, vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(VisibilityResult), vp]
     L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     plc = C.POINTER(LoopCloserConfig)
     L.lfx_loop_closer_default_config.argtypes = [plc]

@@ -617,6 +617,20 @@ void launch_feature_offsets(const uint32_t * edge_counts, const uint32_t * surfa
 // closer's detect queries the index with its own entries (lfx_loopclose.hip)
 const float * place_db_entries(const lfx_place_db * db, uint32_t * cells);
 
+// lfx_keyframes.hip: a store as the visibility votes read it (lfx_visibility.hip) -- the device arrays, the host's mirror of
+// the begin tables ([n + 1] per kind) and the store's tail event, which a reader orders itself behind and records
+struct KeyframesAccess
+{
+  int device = 0;
+  uint32_t n = 0;
+  const float4 * records[2] = {nullptr, nullptr};
+  const uint64_t * d_begin[2] = {nullptr, nullptr};
+  const uint64_t * begin[2] = {nullptr, nullptr};
+  const double * poses = nullptr;
+  const Tail * tail = nullptr;
+};
+KeyframesAccess keyframes_access(const lfx_keyframes * s);
+
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
   const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,

@@ -216,4 +216,117 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_plan_kernel(
   }
 }
 
+// --- the masked build: a world cloud without the records whose flag byte is set, the order kept ---------------------------
+// Three launches over the source records [rec_lo, rec_hi) in runs of kKfRun: the kept records of every run counted; the
+// counts turned into their exclusive prefix by one workgroup (the total behind the last); then every run placed from its
+// prefix on.  Inside a run lane t has the kKfPerLane CONSECUTIVE records from 4 t, so that lane order is record order: a
+// lane's place is the run's prefix + the kept records of the lanes before it (ballot and population count within the wave,
+// the waves' sums through LDS) + those of its own before the record.
+
+// the kept records among a lane's four, one bit each, and the lane's place among the run's kept records
+__device__ inline uint32_t kf_mask_lane(const uint8_t * __restrict__ flags, uint64_t base, uint64_t run_end, uint32_t * s_wave, uint32_t & before)
+{
+  uint32_t keep = 0u;
+#pragma unroll
+  for (int j = 0; j < kKfPerLane; j++) {
+    const uint64_t i = base + (uint32_t)j;
+    if (i < run_end && flags[i] == 0u) {keep |= 1u << j;}
+  }
+  const uint32_t mine = __popc(keep), lane = threadIdx.x & (kKfWave - 1u), wave = threadIdx.x >> 6;
+  // inclusive sum over the wave's lanes
+  uint32_t sum = mine;
+#pragma unroll
+  for (int d = 1; d < (int)kKfWave; d <<= 1) {
+    const uint32_t v = __shfl_up(sum, d, kKfWave);
+    if ((int)lane >= d) {sum += v;}
+  }
+  if (lane == kKfWave - 1u) {s_wave[wave] = sum;}
+  __syncthreads();
+  uint32_t waves_before = 0u;
+  for (uint32_t q = 0; q < wave; q++) {waves_before += s_wave[q];}
+  before = waves_before + sum - mine;
+  return keep;
+}
+
+__global__ __launch_bounds__(kKfThreads) void keyframes_mask_count_kernel(
+  const uint8_t * __restrict__ flags, uint64_t rec_lo, uint64_t rec_hi, uint64_t * __restrict__ run_count)
+{
+  __shared__ uint32_t s_wave[kKfThreads / kKfWave];
+  const uint64_t run = rec_lo + (uint64_t)blockIdx.x * kKfRun;
+  const uint64_t run_end = run + kKfRun < rec_hi ? run + kKfRun : rec_hi;
+  uint32_t before;
+  const uint32_t keep = kf_mask_lane(flags, run + (uint64_t)threadIdx.x * kKfPerLane, run_end, s_wave, before);
+  if (threadIdx.x == kKfThreads - 1u) {run_count[blockIdx.x] = before + __popc(keep);}
+}
+
+// One workgroup: run_count[0 .. n_runs) becomes its exclusive prefix, run_count[n_runs] the total.  Shares, an LDS scan of
+// their sums and a second pass, as keyframes_plan_kernel does it.
+__global__ __launch_bounds__(kKfThreads) void keyframes_mask_scan_kernel(uint64_t * __restrict__ run_count, uint32_t n_runs)
+{
+  __shared__ uint64_t s_sum[kKfThreads];
+  const uint32_t t = threadIdx.x;
+  const uint32_t share = (n_runs + kKfThreads - 1u) / kKfThreads;
+  const uint32_t lo = t * share < n_runs ? t * share : n_runs, hi = lo + share < n_runs ? lo + share : n_runs;
+  uint64_t sum = 0;
+  for (uint32_t b = lo; b < hi; b++) {sum += run_count[b];}
+  s_sum[t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1u; d < kKfThreads; d <<= 1) {
+    const uint64_t v = t >= d ? s_sum[t - d] : 0u;
+    __syncthreads();
+    s_sum[t] += v;
+    __syncthreads();
+  }
+  uint64_t e = s_sum[t] - sum;
+  for (uint32_t b = lo; b < hi; b++) {
+    const uint64_t c = run_count[b];
+    run_count[b] = e;
+    e += c;
+  }
+  if (t == kKfThreads - 1u) {run_count[n_runs] = s_sum[t];}
+}
+
+// The kept records of every run to dst, transformed as keyframes_transform_kernel transforms them (every lane searches for
+// the keyframe of each record it keeps: poses of neighbouring lanes are the same lines).
+__global__ __launch_bounds__(kKfThreads) void keyframes_mask_scatter_kernel(
+  const float4 * __restrict__ src, const uint64_t * __restrict__ begin, const double * __restrict__ poses,
+  const uint8_t * __restrict__ flags, const uint64_t * __restrict__ run_begin, float4 * __restrict__ dst, const KfRange a)
+{
+  __shared__ uint32_t s_wave[kKfThreads / kKfWave];
+  const uint64_t run = a.rec_lo + (uint64_t)blockIdx.x * kKfRun;
+  const uint64_t run_end = run + kKfRun < a.rec_hi ? run + kKfRun : a.rec_hi;
+  const uint64_t base = run + (uint64_t)threadIdx.x * kKfPerLane;
+  uint32_t before;
+  const uint32_t keep = kf_mask_lane(flags, base, run_end, s_wave, before);
+  if (keep == 0u) {return;}
+  uint64_t o = run_begin[blockIdx.x] + before;
+  uint32_t l = a.k_lo, h = a.k_hi;            // begin[l] <= base < begin[h]
+  while (h - l > 1u) {
+    const uint32_t mid = l + ((h - l) >> 1);
+    if (begin[mid] <= base) {l = mid;} else {h = mid;}
+  }
+#pragma unroll
+  for (int j = 0; j < kKfPerLane; j++) {
+    if (!(keep & (1u << j))) {continue;}
+    const uint64_t i = base + (uint32_t)j;
+    while (begin[l + 1u] <= i) {l++;}         // (i < rec_hi <= begin[k_hi]: l stays below k_hi)
+    dst[o++] = pcl_transform_record(poses + 12u * (size_t)l, src[i]);
+  }
+}
+
+// One thread per entry of d_begin_out[0 .. count]: the kept records before the first record of keyframe first + j -- the
+// prefix of its run plus the kept records of the run before it.
+__global__ __launch_bounds__(kKfThreads) void keyframes_mask_begin_kernel(
+  const uint8_t * __restrict__ flags, const uint64_t * __restrict__ begin, const uint64_t * __restrict__ run_begin, uint32_t first,
+  uint32_t count, uint64_t rec_lo, uint64_t * __restrict__ begin_out)
+{
+  const uint32_t j = blockIdx.x * kKfThreads + threadIdx.x;
+  if (j > count) {return;}
+  const uint64_t i = begin[first + j];
+  const uint64_t b = (i - rec_lo) / kKfRun;   // (i == rec_hi on a run boundary: run_begin has the total behind the last run)
+  uint64_t o = run_begin[b];
+  for (uint64_t q = rec_lo + b * kKfRun; q < i; q++) {o += flags[q] == 0u ? 1u : 0u;}
+  begin_out[j] = o;
+}
+
 }  // namespace lfx

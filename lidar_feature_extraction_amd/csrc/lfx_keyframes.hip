@@ -30,6 +30,7 @@ struct lfx_keyframes
   DevBuf<uint64_t> out_begin;
   DevBuf<lfx::KfPlanRecord> record;
   DevBuf<float4> scratch;                // lfx_keyframes_save: one chunk of a world cloud
+  DevBuf<uint64_t> mask_runs;            // lfx_keyframes_build_masked: the kept records per run of kKfRun, then their prefix
   PinnedBuf readback;                    // the counts and begins an add reads back; the submap's record
   PinnedBuf upload;                      // what goes up (tables, begins, poses, a host keyframe's records): rewritten only
                                          // once the store's last queued call has passed
@@ -166,6 +167,21 @@ int save_kind(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::string 
 
 }  // namespace
 
+lfx_host::KeyframesAccess lfx_host::keyframes_access(const lfx_keyframes * s)
+{
+  KeyframesAccess a;
+  a.device = s->device;
+  a.n = s->n;
+  for (int kind = 0; kind < 2; kind++) {
+    a.records[kind] = s->records[kind].p;
+    a.d_begin[kind] = s->d_begin[kind].p;
+    a.begin[kind] = s->begin[kind].data();
+  }
+  a.poses = s->poses.p;
+  a.tail = &s->tail;
+  return a;
+}
+
 extern "C" {
 
 void lfx_keyframes_default_config(lfx_keyframes_config * config)
@@ -200,6 +216,7 @@ int lfx_keyframes_create(lfx_ctx * c, const lfx_keyframes_config * config, lfx_k
     };
   for (int kind = 0; kind < 2; kind++) {get(s->records[kind], config->max_points[kind]); get(s->d_begin[kind], K + 1u); get(s->table[kind], K);}
   get(s->poses, 12u * K); get(s->flag, K); get(s->out_begin, K); get(s->record, 1u); get(s->scratch, s->chunk);
+  get(s->mask_runs, (size_t)(std::max(config->max_points[0], config->max_points[1]) / lfx::kKfRun) + 2u);
   if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's " + std::to_string(bytes) + " bytes");}
   s->device_bytes = bytes;
   for (int kind = 0; kind < 2; kind++) {
@@ -411,6 +428,54 @@ int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t
   if (rc != LFX_OK) {return rc;}
   rc = launch_transform(c, s, kind, lo, hi, first, first + count, false, first, d_out, st);
   if (rc != LFX_OK) {return rc;}
+  return s->tail.done(c, st);
+}
+
+int lfx_keyframes_build_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t first, uint32_t count, const uint8_t * d_flags, float * d_out,
+  uint64_t capacity_points, uint64_t * d_begin_out, uint64_t * n_out, void * stream)
+{
+  if (!c || !s || !n_out) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
+  *n_out = 0u;
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hi == lo) {
+    if (d_begin_out) {LFX_HIP(c, hipMemsetAsync(d_begin_out, 0, sizeof(uint64_t) * ((size_t)count + 1u), st));}
+    return LFX_OK;
+  }
+  if (!d_flags) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_flags is required");}
+  const uint64_t runs = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
+  if (runs + 1u > s->mask_runs.n) {return fail(c, LFX_ERR_CAPACITY, "too many records for the masked build's table");}
+  int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  hipLaunchKernelGGL(lfx::keyframes_mask_count_kernel, dim3((uint32_t)runs), dim3(lfx::kKfThreads), 0, st, d_flags, lo, hi, s->mask_runs.p);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::keyframes_mask_scan_kernel, dim3(1), dim3(lfx::kKfThreads), 0, st, s->mask_runs.p, (uint32_t)runs);
+  LFX_HIP(c, hipGetLastError());
+  // the call's only wait: the kept records (the caller needs them to hand the cloud on; the capacity is checked against them)
+  uint64_t * kept = reinterpret_cast<uint64_t *>(s->readback.p);
+  LFX_HIP(c, hipMemcpyAsync(kept, s->mask_runs.p + runs, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  *n_out = *kept;
+  if (*n_out > capacity_points) {
+    (void)s->tail.done(c, st);
+    return fail(c, LFX_ERR_CAPACITY, "the keyframes keep " + std::to_string(*n_out) + " records: more than capacity_points (" + std::to_string(capacity_points) + ")");
+  }
+  if (*n_out > 0u) {
+    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    lfx::KfRange a{};
+    a.rec_lo = lo; a.rec_hi = hi; a.k_lo = first; a.k_hi = first + count; a.first = first;
+    hipLaunchKernelGGL(lfx::keyframes_mask_scatter_kernel, dim3((uint32_t)runs), dim3(lfx::kKfThreads), 0, st, s->records[kind].p, s->d_begin[kind].p,
+      s->poses.p, d_flags, s->mask_runs.p, reinterpret_cast<float4 *>(d_out), a);
+    LFX_HIP(c, hipGetLastError());
+  }
+  if (d_begin_out) {
+    hipLaunchKernelGGL(lfx::keyframes_mask_begin_kernel, dim3(count / lfx::kKfThreads + 1u), dim3(lfx::kKfThreads), 0, st, d_flags, s->d_begin[kind].p,
+      s->mask_runs.p, first, count, lo, d_begin_out);
+    LFX_HIP(c, hipGetLastError());
+  }
   return s->tail.done(c, st);
 }
 

@@ -339,4 +339,46 @@ int lfx_segment_tables(const lfx_segment_config * config, double * col_cos, doub
   return LFX_OK;
 }
 
+// Visibility votes (include/lfx.h, the visibility section): the defaults, and the tables the kernels are given.
+void lfx_visibility_default_config(lfx_visibility_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_visibility_config{};
+  config->n_rows = 32;
+  config->n_columns = 360;
+  config->elev_min = -0.43633232f;
+  config->elev_step = 0.027270770f;
+  config->min_range = 1.0f;
+  config->max_range = 100.0f;
+  config->radius = 15.0f;
+  config->margin_abs = 0.3f;
+  config->margin_rel = 0.02f;
+  config->guard = 1;
+  config->min_through = 2;
+  config->agree_weight = 1;
+}
+
+int lfx_visibility_tables(const lfx_visibility_config * config, double * col_cos, double * col_sin, double * row_tan)
+{
+  if (!config || !col_cos || !col_sin || !row_tan) {return LFX_ERR_INVALID_ARGUMENT;}
+  const lfx_visibility_config & c = *config;
+  const uint32_t H = c.n_rows, W = c.n_columns;
+  if (H < 1u || H > LFX_SEGMENT_MAX_ROWS || W < 4u || W > LFX_SEGMENT_MAX_COLUMNS || (W & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.elev_min) || !std::isfinite(c.elev_step) || !(c.elev_step > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!((double)c.elev_min > -M_PI / 2.0) || !((double)c.elev_min + (double)H * (double)c.elev_step < M_PI / 2.0)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.min_range) || !std::isfinite(c.max_range) || !(c.min_range > 0.0f) || !(c.min_range < c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.radius) || !(c.radius >= 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.margin_abs) || !(c.margin_abs >= 0.0f) || !std::isfinite(c.margin_rel) || !(c.margin_rel >= 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.guard > 2u || c.min_through < 1u || c.reserved != 0u) {return LFX_ERR_INVALID_ARGUMENT;}
+  for (uint32_t m = 0; m < W; m++) {
+    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)W;
+    col_cos[m] = std::cos(angle);
+    col_sin[m] = std::sin(angle);
+  }
+  for (uint32_t j = 0; j <= H; j++) {
+    row_tan[j] = std::tan((double)c.elev_min + (double)j * (double)c.elev_step);
+  }
+  return LFX_OK;
+}
+
 }  // extern "C"

@@ -512,6 +512,11 @@ class FeatureExtraction:
         (edge, surface) records) on this context's device."""
         return Keyframes(self, max_keyframes, max_points)
 
+    def visibility(self, max_window=1024, max_resident_images=None, config=None, **fields):
+        """lfx_visibility_create: visibility votes over windows of up to max_window keyframes, max_resident_images (default:
+        all of them) range images on the device at a time; the fields of lfx_visibility_config as keywords."""
+        return Visibility(self, max_window, max_resident_images, config, **fields)
+
     def place_db(self, capacity, config=None):
         """lfx_place_db_create: a place index of `capacity` scan-context descriptors of `config` on this context's device."""
         return PlaceDb(self, capacity, config)
@@ -791,6 +796,35 @@ def segment_tables(config=None):
     if rc != 0:
         raise B.LfxError(rc, "the segmentation config is refused")
     return cs[:W], sn[:W], consts
+
+
+def visibility_config(config=None, **fields):
+    """lfx_visibility_config: the defaults (lfx_visibility_default_config) with the given fields replaced.  config: None, a
+    dict of fields, or a B.VisibilityConfig (copied)."""
+    cfg = B.VisibilityConfig()
+    if isinstance(config, B.VisibilityConfig):
+        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        config = None
+    else:
+        B.load().lfx_visibility_default_config(C.byref(cfg))
+    for k, v in dict(config or {}, **fields).items():
+        if k not in dict(B.VisibilityConfig._fields_):
+            raise TypeError("unknown visibility setting %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def visibility_tables(config=None):
+    """lfx_visibility_tables: (col_cos [W], col_sin [W], row_tan [H + 1]), float64 -- the tables the visibility kernels are
+    given, and the only source of them.  Host only."""
+    cfg = visibility_config(config)
+    H, W = int(cfg.n_rows), int(cfg.n_columns)
+    # (sized for any config: a refused one writes nothing)
+    cs, sn, rt = np.zeros(max(W, 1)), np.zeros(max(W, 1)), np.zeros(H + 1)
+    rc = B.load().lfx_visibility_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(rt))
+    if rc != 0:
+        raise B.LfxError(rc, "the visibility config is refused")
+    return cs[:W], sn[:W], rt
 
 
 def _msg_buffer():
@@ -1712,6 +1746,30 @@ class Keyframes:
                    last_id=None if r.last_id == B.KEYFRAMES_NO_ID else int(r.last_id), truncated=bool(r.truncated))
         return (None if out is None else out[:res["n_points"]]), res
 
+    def build_masked(self, kind, flags, first=0, count=None, begins=False, d_out=None, capacity_points=None, stream=0):
+        """lfx_keyframes_build_masked: Keyframes.build without the records whose byte of `flags` (a uint8 device tensor or a
+        device address, addressed by the store's record index of `kind`, as Visibility.run returns it) is non-zero.  Without
+        d_out: a torch tensor [n_kept, 4] (a view of a new one of capacity_points records, default the range's).  With
+        d_out: the number of kept records.  begins: also the [count + 1] int64 device tensor of the kept records before each
+        keyframe -- (cloud, begins) or (n, begins)."""
+        import torch
+        kind = self._kind(kind)
+        count = len(self) - int(first) if count is None else int(count)
+        d_flags = flags.data_ptr() if hasattr(flags, "data_ptr") else int(flags)
+        dev = torch.device("cuda", self._fx.device)
+        d_begin = torch.empty(count + 1, dtype=torch.int64, device=dev) if begins else None
+        out = None
+        if d_out is None:
+            capacity_points = self._range_points(kind, first, count) if capacity_points is None else int(capacity_points)
+            out = torch.empty((capacity_points, 4), dtype=torch.float32, device=dev)
+            d_out = out.data_ptr() if capacity_points else 0
+        n = C.c_uint64(0)
+        self._check(self._L.lfx_keyframes_build_masked(
+            self._fx._ctx, self.handle, kind, int(first), count, C.c_void_p(d_flags or None), C.c_void_p(int(d_out) or None), int(capacity_points),
+            C.c_void_p(d_begin.data_ptr() if begins else None), C.byref(n), C.c_void_p(int(stream))))
+        got = int(n.value) if out is None else out[:int(n.value)]
+        return (got, d_begin) if begins else got
+
     def _range_points(self, kind, first, count):
         """the records of keyframes [first, first + count) of `kind`, from the host's mirror: a build without room, which
         queues nothing and reports the records needed"""
@@ -1730,6 +1788,73 @@ class Keyframes:
     def close(self):
         if self.handle:
             self._L.lfx_keyframes_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Visibility:
+    """lfx_visibility: the visibility votes of a window of a Keyframes store's keyframes on each other's records, and the
+    DYNAMIC flag they decide (include/lfx.h, the visibility section).  The fields of lfx_visibility_config as keywords."""
+
+    def __init__(self, fx, max_window=1024, max_resident_images=None, config=None, **fields):
+        self._fx = fx
+        self._L = fx._L
+        cfg = visibility_config(config, **fields)
+        resident = int(max_window) if max_resident_images is None else int(max_resident_images)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_visibility_create(fx._ctx, C.byref(cfg), int(max_window), resident, C.byref(h)), self._L)
+        self.handle = h
+        self.config = cfg
+
+    def _check(self, rc):
+        B.check(self._fx._ctx, rc, self._L)
+
+    def info(self):
+        i = B.VisibilityInfo()
+        self._check(self._L.lfx_visibility_info(self.handle, C.byref(i)))
+        return dict(config={k: getattr(i.config, k) for k, _ in B.VisibilityConfig._fields_}, max_window=int(i.max_window),
+                    max_resident_images=int(i.max_resident_images), device_bytes=int(i.device_bytes))
+
+    @staticmethod
+    def result(r):
+        return dict(n_pairs=int(r.n_pairs), n_viewer_chunks=int(r.n_viewer_chunks), n_records=(int(r.n_records[0]), int(r.n_records[1])),
+                    n_voted=(int(r.n_voted[0]), int(r.n_voted[1])), n_dynamic=(int(r.n_dynamic[0]), int(r.n_dynamic[1])),
+                    occupied_cells=int(r.occupied_cells), total_cells=int(r.total_cells))
+
+    def run(self, keyframes, first=0, count=None, votes=False, flags=None, stream=0):
+        """lfx_visibility_run over keyframes [first, first + count) of `keyframes`.  Returns (flags, votes, result): flags
+        (edge, surface) uint8 device tensors and votes (edge, surface) int32 device tensors (the library's uint32: through |
+        agree << 16) or None, each addressed by the store's record index of its kind and as long as the store's records --
+        only the window's elements are written, the others keep what they held (new tensors: 0); result the dict of
+        lfx_visibility_result.  flags / votes may be given as pairs of tensors to write into; votes False: not wanted."""
+        import torch
+        count = len(keyframes) - int(first) if count is None else int(count)
+        n = keyframes.info()["n_points"]
+        dev = torch.device("cuda", self._fx.device)
+        if flags is None:
+            flags = tuple(torch.zeros(max(n[k], 1), dtype=torch.uint8, device=dev) for k in range(2))
+        if votes is True:
+            votes = tuple(torch.zeros(max(n[k], 1), dtype=torch.int32, device=dev) for k in range(2))
+        elif votes is False or votes is None:
+            votes = None
+        for k in range(2):
+            if flags[k].dtype != torch.uint8 or flags[k].numel() < n[k] or (votes is not None and (votes[k].dtype != torch.int32 or votes[k].numel() < n[k])):
+                raise ValueError("flags are uint8 and votes int32 tensors of at least the store's records of their kind")
+        pf = (C.c_void_p * 2)(flags[0].data_ptr(), flags[1].data_ptr())
+        pv = (C.c_void_p * 2)(votes[0].data_ptr() if votes else None, votes[1].data_ptr() if votes else None)
+        r = B.VisibilityResult()
+        self._check(self._L.lfx_visibility_run(self._fx._ctx, self.handle, keyframes.handle, int(first), count, pv, pf, C.byref(r),
+                                               C.c_void_p(int(stream))))
+        return flags, votes, self.result(r)
+
+    def close(self):
+        if self.handle:
+            self._L.lfx_visibility_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
