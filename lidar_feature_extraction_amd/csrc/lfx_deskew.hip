@@ -87,9 +87,8 @@ template<typename Args>
 int launch(lfx_ctx * c, const Forms<Args> & forms, int src, uint32_t n, const Args & a, lfx_ctx::DeskewSlot & slot, size_t doubles, hipStream_t st)
 {
   LFX_HIP(c, hipMemcpyAsync(slot.d.p, slot.h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
-  // (a scan of 64 x 1800 has about 14 k feature records: 8 workgroups walk them in 7 steps; a few scans get more)
-  const dim3 grid(n >= 32u ? 8u : 32u, n);
-  hipLaunchKernelGGL(forms[src], grid, dim3(lfx::kDeskewThreads), 0, st, a);
+  // (a scan of 64 x 1800 has about 14 k feature records: by_scan_grid's 8 workgroups walk them in 7 steps; a few scans get more)
+  hipLaunchKernelGGL(forms[src], by_scan_grid(n), dim3(lfx::kDeskewThreads), 0, st, a);
   LFX_HIP(c, hipGetLastError());
   return slot.used.done(c, st);
 }

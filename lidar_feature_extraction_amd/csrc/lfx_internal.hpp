@@ -507,6 +507,21 @@ inline bool finite_all(const double * v, size_t n)
 // the parts of a pinned block start on 64-byte boundaries (tables of doubles; a copy up starts aligned)
 inline size_t round64(size_t bytes) {return (bytes + 63u) & ~(size_t)63u;}
 
+// workgroups of `threads` (or tiles of that many items) that cover n items
+inline uint32_t blocks_for(uint64_t n, uint32_t threads) {return (uint32_t)((n + threads - 1u) / threads);}
+
+// The grid of a kernel that walks every scan's records with a grid stride, (chunks, scans): a scan of 64 x 1800 has 115 k
+// input records, which 32 workgroups of 256 walk in 15 steps; large batches fill the device with fewer (the de-skews walk
+// feature records with it, an eighth as many).
+inline dim3 by_scan_grid(uint32_t n_scans) {return dim3(n_scans >= 32u ? 8u : 32u, n_scans);}
+
+// whether the batch's input records are the canonical ones load_xyz<true> reads (lfx_kernels_image.hpp): x, y, z
+// little-endian in the first 12 bytes of 32-byte records that start 16-byte aligned
+inline bool canonical_xyz16(const lfx::Layout & L, const void * pts)
+{
+  return L.step == 32u && L.ox == 0u && L.oy == 4u && L.oz == 8u && !L.be && (reinterpret_cast<uintptr_t>(pts) & 15u) == 0u;
+}
+
 // One list of n clouds on the device, as the stores' add and insert calls are handed it: cloud s is d_count[s *
 // count_stride] records from record d_begin[s] of total_points.  name: what a refusal calls the list ("", "edge ", "surface ")
 struct CloudList

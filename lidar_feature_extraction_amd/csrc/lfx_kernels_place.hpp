@@ -6,7 +6,7 @@
 // gate's lists are written in a fixed order and the only atomics are integer maxima, so the same inputs give the same bytes.
 #pragma once
 
-#include "lfx_kernels_common.hpp"
+#include "lfx_kernels_image.hpp"
 
 #pragma clang fp contract(off)
 
@@ -33,8 +33,9 @@ struct ScanContextArgs
 
 // grid (chunks, scans) as deskew_kernel's; a grid-stride walk over the scan's input records.  A workgroup keeps one array
 // of cells in LDS, each the largest float_order(z) of its records (0: no record -- no float has that key), filled with LDS
-// integer max; its non-empty cells then go to the scan's keys with a global integer max.  XYZ16: the records are the
-// canonical ones (x, y, z little-endian in the first 12 bytes of a 16-byte aligned 32-byte record), read with one load.
+// integer max; its non-empty cells then go to the scan's keys with a global integer max.  XYZ16: load_xyz's
+// (lfx_kernels_image.hpp).  The sector is the COUNT of the half's directions the record has passed (include/lfx.h: the
+// counts are the definition), not azimuth_column's search.
 template<bool XYZ16>
 __global__ __launch_bounds__(kPlaceThreads) void scan_context_kernel(const ScanContextArgs A)
 {
@@ -53,12 +54,7 @@ __global__ __launch_bounds__(kPlaceThreads) void scan_context_kernel(const ScanC
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
     const uint8_t * rec = base + (size_t)k * A.L.step;
     float x, y, z;
-    if (XYZ16) {
-      const float4 v = *reinterpret_cast<const float4 *>(rec);
-      x = v.x; y = v.y; z = v.z;
-    } else {
-      x = load_f32(rec + A.L.ox, A.L.be); y = load_f32(rec + A.L.oy, A.L.be); z = load_f32(rec + A.L.oz, A.L.be);
-    }
+    load_xyz<XYZ16>(rec, A.L, x, y, z);
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) {continue;}
     const double xd = (double)x, yd = (double)y;
     const double r2 = xd * xd + yd * yd;

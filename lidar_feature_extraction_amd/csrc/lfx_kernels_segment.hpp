@@ -7,7 +7,7 @@
 // launches of their own, and the hook loop retries its own atomicMin only.
 #pragma once
 
-#include "lfx_kernels_common.hpp"
+#include "lfx_kernels_image.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,34 +47,20 @@ struct SegmentArgs
   uint32_t * counts_out;                // [scans][4], zeroed in-stream ahead of the launch, or nullptr
 };
 
-// The cell of one record and its range, or kSegNoCell: the header's projection.
+// The cell of one record and its range, or kSegNoCell: the header's projection -- the gates and the column are the shared
+// ones (lfx_kernels_image.hpp), the range comparison and the row (the record's ring slot) are its own.
 template<bool XYZ16>
 __device__ inline uint32_t seg_project(const SegmentArgs & A, const uint8_t * rec, float & x, float & y, float & z, double & r)
 {
-  if (XYZ16) {
-    const float4 v = *reinterpret_cast<const float4 *>(rec);
-    x = v.x; y = v.y; z = v.z;
-  } else {
-    x = load_f32(rec + A.L.ox, A.L.be); y = load_f32(rec + A.L.oy, A.L.be); z = load_f32(rec + A.L.oz, A.L.be);
-  }
-  if (!(isfinite(x) && isfinite(y) && isfinite(z))) {return kSegNoCell;}
+  load_xyz<XYZ16>(rec, A.L, x, y, z);
   uint32_t row = load_ring(rec + A.L.oring, A.L.rtype, A.L.be);
   if (A.ring_slot != nullptr) {row = row < 65536u ? A.ring_slot[row] : 0xFFFFu;}
   if (row >= A.H || row >= A.max_rings) {return kSegNoCell;}
-  const double xd = (double)x, yd = (double)y, zd = (double)z;
-  const double xy2 = xd * xd + yd * yd;
-  if (xy2 == 0.0) {return kSegNoCell;}
-  r = sqrt(xy2 + zd * zd);
+  const double xd = (double)x, yd = (double)y;
+  double xy2;
+  if (!planar_range(xd, yd, (double)z, xy2, r)) {return kSegNoCell;}
   if (r < A.min_range || r >= A.max_range) {return kSegNoCell;}
-  const double * cs = A.table, * sn = A.table + A.W;
-  const uint32_t m0 = y >= 0.0f ? A.W / 2u : 0u;
-  uint32_t lo = 0, hi = A.W / 2u - 1u;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    const double cross = cs[m0 + mid] * yd - sn[m0 + mid] * xd;
-    if (cross >= 0.0) {lo = mid;} else {hi = mid - 1u;}
-  }
-  return row * A.W + m0 + lo;
+  return row * A.W + azimuth_column(A.table, A.table + A.W, A.W, xd, yd, y >= 0.0f);
 }
 
 // grid (chunks, the chunk's scans) as scan_context_kernel's; a grid-stride walk over the scan's input records, each with a
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(kSegThreads) void segment_cell_kernel(const Segment
   if (key != kSegEmpty) {
     const uint32_t s = A.first_scan + i / cells;
     const uint8_t * rec = A.pts + ((size_t)A.scan_begin[s] + (uint32_t)key) * A.L.step;
-    v.x = load_f32(rec + A.L.ox, A.L.be); v.y = load_f32(rec + A.L.oy, A.L.be); v.z = load_f32(rec + A.L.oz, A.L.be);
+    load_xyz<false>(rec, A.L, v.x, v.y, v.z);
     v.w = __uint_as_float(kSegOccupied);
     const double xd = (double)v.x, yd = (double)v.y, zd = (double)v.z;
     A.image[i] = (uint64_t)__double_as_longlong(sqrt((xd * xd + yd * yd) + zd * zd));

@@ -8,6 +8,7 @@
 
 #include <cstdint>
 
+#include "lfx_kernels_image.hpp"
 #include "lfx_kernels_transform.hpp"
 
 namespace lfx
@@ -40,30 +41,23 @@ struct VisArgs
   double min_range, max_range, radius2, margin_abs, margin_rel;
 };
 
-// The cell of a point and its range, or kVisNoCell: the header's rule.
+// The cell of a point and its range, or kVisNoCell: the header's rule -- the gates and the column are the shared ones
+// (lfx_kernels_image.hpp), the range comparison and the row (a search over row_tan) are its own.
 __device__ inline uint32_t vis_cell(const VisArgs & A, const double * __restrict__ table, double x, double y, double z, double & r)
 {
-  if (!(isfinite(x) && isfinite(y) && isfinite(z))) {return kVisNoCell;}
-  const double xy2 = x * x + y * y;
-  if (xy2 == 0.0) {return kVisNoCell;}
-  const double rho = sqrt(xy2);
-  r = sqrt(xy2 + z * z);
+  double xy2;
+  if (!planar_range(x, y, z, xy2, r)) {return kVisNoCell;}
+  const double rho = sqrt(xy2);                     // (beside r's: the two square roots overlap)
   if (r < A.min_range || r >= A.max_range) {return kVisNoCell;}
-  const double * cs = table, * sn = table + A.W, * rt = table + 2u * A.W;
+  const double * rt = table + 2u * A.W;
   if (z < rt[0] * rho || z >= rt[A.H] * rho) {return kVisNoCell;}
-  const uint32_t m0 = y >= 0.0 ? A.W / 2u : 0u;
-  uint32_t lo = 0, hi = A.W / 2u - 1u;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    const double cross = cs[m0 + mid] * y - sn[m0 + mid] * x;
-    if (cross >= 0.0) {lo = mid;} else {hi = mid - 1u;}
-  }
+  const uint32_t col = azimuth_column(table, table + A.W, A.W, x, y, y >= 0.0);
   uint32_t rlo = 0, rhi = A.H - 1u;
   while (rlo < rhi) {
     const uint32_t mid = (rlo + rhi + 1u) >> 1;
     if (z >= rt[mid] * rho) {rlo = mid;} else {rhi = mid - 1u;}
   }
-  return rlo * A.W + m0 + lo;
+  return rlo * A.W + col;
 }
 
 // grid (x, chunk_n): workgroups (., s) walk the records of both kinds of viewer chunk_lo + s with a grid stride, each record

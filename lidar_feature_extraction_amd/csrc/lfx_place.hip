@@ -96,7 +96,7 @@ void write_matches(const lfx::PlaceMatchDevice * got, size_t n_matches, uint32_t
 int launch_norms(lfx_ctx * c, const float * d_desc, double * d_norms, uint32_t n, const lfx_scan_context_config & cfg, hipStream_t st)
 {
   const size_t threads = (size_t)n * cfg.n_sectors;
-  hipLaunchKernelGGL(lfx::place_norms_kernel, dim3((uint32_t)((threads + lfx::kPlaceThreads - 1) / lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
+  hipLaunchKernelGGL(lfx::place_norms_kernel, dim3(blocks_for(threads, lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
     d_desc, d_norms, n, cfg.n_rings, cfg.n_sectors);
   LFX_HIP(c, hipGetLastError());
   return LFX_OK;
@@ -165,13 +165,10 @@ int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uin
   a.table = slot->table.d.p;
   a.keys = slot->keys.p;
   a.R = R; a.S = S;
-  const lfx::Layout & L = c->layout;
-  const bool xyz16 = L.step == 32u && L.ox == 0u && L.oy == 4u && L.oz == 8u && !L.be && (reinterpret_cast<uintptr_t>(a.pts) & 15u) == 0u;
-  // (a scan of 64 x 1800 has 115 k records: 32 workgroups walk them in 15 steps; large batches fill the device with fewer)
-  const dim3 grid(n_scans >= 32u ? 8u : 32u, n_scans);
-  hipLaunchKernelGGL(xyz16 ? lfx::scan_context_kernel<true> : lfx::scan_context_kernel<false>, grid, dim3(lfx::kPlaceThreads), 0, st, a);
+  const bool xyz16 = canonical_xyz16(c->layout, a.pts);
+  hipLaunchKernelGGL(xyz16 ? lfx::scan_context_kernel<true> : lfx::scan_context_kernel<false>, by_scan_grid(n_scans), dim3(lfx::kPlaceThreads), 0, st, a);
   LFX_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(lfx::scan_context_finish_kernel, dim3((uint32_t)((total + lfx::kPlaceThreads - 1) / lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
+  hipLaunchKernelGGL(lfx::scan_context_finish_kernel, dim3(blocks_for(total, lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
     slot->keys.p, d_desc_out, total, cfg->sensor_height);
   LFX_HIP(c, hipGetLastError());
   return slot->table.used.done(c, st);
@@ -288,7 +285,7 @@ int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_des
     a.best_distance = db->best_distance.p; a.best_shift = db->best_shift.p;
     a.count = count; a.R = R; a.S = S;
     a.tile = lfx::place_tile(S, pairs);
-    const dim3 grid((count + a.tile - 1u) / a.tile, n_queries);
+    const dim3 grid(blocks_for(count, a.tile), n_queries);
     hipLaunchKernelGGL(lfx::place_compare_kernel, grid, dim3(lfx::kPlaceThreads), (uint32_t)lfx::place_compare_lds(R, S), st, a);
     LFX_HIP(c, hipGetLastError());
   }
@@ -354,10 +351,10 @@ int lfx_place_db_query_gated(lfx_ctx * c, const lfx_place_db * db, const float *
     // gridDim.x-th tile up to its list's end (64 queries against 65 536 entries would start a million workgroups otherwise,
     // nearly all of them with nothing to do).
     a.tile = lfx::place_tile(S, pairs);
-    uint32_t per_query = (stride + a.tile - 1u) / a.tile;
+    uint32_t per_query = blocks_for(stride, a.tile);
     if (d_poses) {
       a.tile = lfx::place_pass_entries(S);
-      per_query = std::min((stride + a.tile - 1u) / a.tile, std::max(8192u / n_queries, 1u));
+      per_query = std::min(blocks_for(stride, a.tile), std::max(8192u / n_queries, 1u));
     }
     const dim3 grid(per_query, n_queries);
     hipLaunchKernelGGL(lfx::place_compare_gated_kernel, grid, dim3(lfx::kPlaceThreads), (uint32_t)lfx::place_compare_lds(R, S), st, a,

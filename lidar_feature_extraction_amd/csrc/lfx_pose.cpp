@@ -267,6 +267,24 @@ int lfx_pose_graph_edge_information(const double pose_j[12], const double report
   return LFX_OK;
 }
 
+// What the three azimuth-binned subsystems below share (the device's side: lfx_kernels_image.hpp).  Direction m of W is
+// -pi + 2 pi m / W: the first half of the table is the half circle y < 0, the second (from m = W / 2, angle 0) y >= 0.
+static void azimuth_table(uint32_t W, double * cos_out, double * sin_out)
+{
+  for (uint32_t m = 0; m < W; m++) {
+    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)W;
+    cos_out[m] = std::cos(angle);
+    sin_out[m] = std::sin(angle);
+  }
+}
+
+// a range image's rows, columns and ranges: what the segmentation and the visibility votes both ask of a config
+static bool range_image_ok(uint32_t H, uint32_t W, float min_range, float max_range)
+{
+  if (H < 1u || H > LFX_SEGMENT_MAX_ROWS || W < 4u || W > LFX_SEGMENT_MAX_COLUMNS || (W & 1u)) {return false;}
+  return std::isfinite(min_range) && std::isfinite(max_range) && min_range > 0.0f && min_range < max_range;
+}
+
 // Scan-context descriptors (include/lfx.h, the place recognition section): the defaults, and the tables the kernel is given.
 void lfx_scan_context_default_config(lfx_scan_context_config * config)
 {
@@ -286,11 +304,7 @@ int lfx_scan_context_tables(const lfx_scan_context_config * config, double * sec
   if (R < 1u || R > LFX_SCAN_CONTEXT_MAX_RINGS || S < 4u || S > LFX_SCAN_CONTEXT_MAX_SECTORS || (S & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(config->max_radius) || !std::isfinite(config->min_radius) || !std::isfinite(config->sensor_height)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!(config->min_radius >= 0.0f) || !(config->min_radius < config->max_radius)) {return LFX_ERR_INVALID_ARGUMENT;}
-  for (uint32_t m = 0; m < S; m++) {
-    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)S;
-    sector_cos[m] = std::cos(angle);
-    sector_sin[m] = std::sin(angle);
-  }
+  azimuth_table(S, sector_cos, sector_sin);
   for (uint32_t j = 0; j <= R; j++) {
     const double e = ((double)config->max_radius * (double)j) / (double)R;
     ring_r2[j] = e * e;
@@ -322,17 +336,12 @@ int lfx_segment_tables(const lfx_segment_config * config, double * col_cos, doub
   if (!config || !col_cos || !col_sin || !consts) {return LFX_ERR_INVALID_ARGUMENT;}
   const lfx_segment_config & c = *config;
   const uint32_t H = c.n_rows, W = c.n_columns;
-  if (H < 1u || H > LFX_SEGMENT_MAX_ROWS || W < 4u || W > LFX_SEGMENT_MAX_COLUMNS || (W & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!range_image_ok(H, W, c.min_range, c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(c.row_step) || !(c.row_step > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (!std::isfinite(c.min_range) || !std::isfinite(c.max_range) || !(c.min_range > 0.0f) || !(c.min_range < c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!(c.ground_first_row <= c.ground_last_row) || !(c.ground_last_row < H)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(c.ground_tan) || !(c.ground_tan >= 0.0f) || !std::isfinite(c.segment_tan) || !(c.segment_tan > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (c.segment_min_points < 1u || c.small_min_points < 1u || c.small_min_rows < 1u) {return LFX_ERR_INVALID_ARGUMENT;}
-  for (uint32_t m = 0; m < W; m++) {
-    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)W;
-    col_cos[m] = std::cos(angle);
-    col_sin[m] = std::sin(angle);
-  }
+  azimuth_table(W, col_cos, col_sin);
   const double col_step = (2.0 * M_PI) / (double)W, row_step = (double)c.row_step;
   consts[0] = std::sin(col_step); consts[1] = std::cos(col_step);
   consts[2] = std::sin(row_step); consts[3] = std::cos(row_step);
@@ -363,18 +372,13 @@ int lfx_visibility_tables(const lfx_visibility_config * config, double * col_cos
   if (!config || !col_cos || !col_sin || !row_tan) {return LFX_ERR_INVALID_ARGUMENT;}
   const lfx_visibility_config & c = *config;
   const uint32_t H = c.n_rows, W = c.n_columns;
-  if (H < 1u || H > LFX_SEGMENT_MAX_ROWS || W < 4u || W > LFX_SEGMENT_MAX_COLUMNS || (W & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!range_image_ok(H, W, c.min_range, c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(c.elev_min) || !std::isfinite(c.elev_step) || !(c.elev_step > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!((double)c.elev_min > -M_PI / 2.0) || !((double)c.elev_min + (double)H * (double)c.elev_step < M_PI / 2.0)) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (!std::isfinite(c.min_range) || !std::isfinite(c.max_range) || !(c.min_range > 0.0f) || !(c.min_range < c.max_range)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(c.radius) || !(c.radius >= 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!std::isfinite(c.margin_abs) || !(c.margin_abs >= 0.0f) || !std::isfinite(c.margin_rel) || !(c.margin_rel >= 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (c.guard > 2u || c.min_through < 1u || c.reserved != 0u) {return LFX_ERR_INVALID_ARGUMENT;}
-  for (uint32_t m = 0; m < W; m++) {
-    const double angle = -M_PI + ((2.0 * M_PI) * (double)m) / (double)W;
-    col_cos[m] = std::cos(angle);
-    col_sin[m] = std::sin(angle);
-  }
+  azimuth_table(W, col_cos, col_sin);
   for (uint32_t j = 0; j <= H; j++) {
     row_tan[j] = std::tan((double)c.elev_min + (double)j * (double)c.elev_step);
   }

@@ -12,8 +12,6 @@ using namespace lfx_host;
 
 namespace
 {
-uint32_t blocks_for(size_t n) {return (uint32_t)((n + lfx::kSegThreads - 1) / lfx::kSegThreads);}
-
 // the workspace for `cells` cells, the call before waited for on `st`
 int take_workspace(lfx_ctx * c, size_t cells, hipStream_t st)
 {
@@ -115,16 +113,14 @@ int lfx_segment_batch(lfx_ctx * c, const lfx_segment_config * cfg, uint32_t n_sc
   a.segment_min_points = cfg->segment_min_points; a.small_min_points = cfg->small_min_points; a.small_min_rows = cfg->small_min_rows;
   a.image = w.image.p; a.cell = w.cell.p; a.parent = w.parent.p; a.csize = w.csize.p; a.crowmax = w.crowmax.p;
   a.class_out = d_class_out; a.id_out = d_id_out; a.counts_out = d_counts_out;
-  const lfx::Layout & L = c->layout;
-  const bool xyz16 = L.step == 32u && L.ox == 0u && L.oy == 4u && L.oz == 8u && !L.be && (reinterpret_cast<uintptr_t>(a.pts) & 15u) == 0u;
+  const bool xyz16 = canonical_xyz16(c->layout, a.pts);
   const dim3 threads(lfx::kSegThreads);
   for (uint32_t first = 0; first < n_scans; first += chunk_scans) {
     const uint32_t scans = std::min(chunk_scans, n_scans - first);
     const uint32_t total = (uint32_t)(cells * scans);        // (at most the budget, or one image: below 2^32 either way)
     a.first_scan = first;
     LFX_HIP(c, hipMemsetAsync(w.image.p, 0xFF, sizeof(uint64_t) * total, st));
-    // (a scan of 64 x 1800 has 115 k records: 32 workgroups walk them in 15 steps; large chunks fill the device with fewer)
-    const dim3 by_scan(scans >= 32u ? 8u : 32u, scans), by_cell(blocks_for(total));
+    const dim3 by_scan = by_scan_grid(scans), by_cell(blocks_for(total, lfx::kSegThreads));
     hipLaunchKernelGGL(xyz16 ? lfx::segment_project_kernel<true> : lfx::segment_project_kernel<false>, by_scan, threads, 0, st, a);
     hipLaunchKernelGGL(lfx::segment_cell_kernel, by_cell, threads, 0, st, a, total);
     hipLaunchKernelGGL(lfx::segment_ground_kernel, by_cell, threads, 0, st, a, total);

@@ -113,7 +113,7 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
   for (uint32_t k = first; k < first + count; k++) {
     n_viewers += (ks.begin[0][k + 1u] > ks.begin[0][k] || ks.begin[1][k + 1u] > ks.begin[1][k]) ? 1u : 0u;
   }
-  const uint32_t M = v->max_resident, n_chunks = (n_viewers + M - 1u) / M;
+  const uint32_t M = v->max_resident, n_chunks = blocks_for(n_viewers, M);
   // where the vote words live between chunks: the caller's, or the object's own (edge records first)
   uint32_t * words[2] = {d_votes[0], d_votes[1]};
   uint64_t word_off[2] = {0u, 0u};
@@ -131,7 +131,7 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
     }
   }
   for (int kind = 0; kind < 2; kind++) {
-    if ((hi[kind] - lo[kind] + lfx::kVisThreads - 1u) / lfx::kVisThreads > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "too many records for one launch");}
+    if (hi[kind] - lo[kind] > 0x7FFFFFFFull * lfx::kVisThreads) {return fail(c, LFX_ERR_CAPACITY, "too many records for one launch");}
   }
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -156,7 +156,7 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
   A.min_range = (double)v->cfg.min_range; A.max_range = (double)v->cfg.max_range;
   A.radius2 = (double)v->cfg.radius * (double)v->cfg.radius;
   A.margin_abs = (double)v->cfg.margin_abs; A.margin_rel = (double)v->cfg.margin_rel;
-  hipLaunchKernelGGL(lfx::visibility_pairs_kernel, dim3((n_viewers + lfx::kVisThreads - 1u) / lfx::kVisThreads), dim3(lfx::kVisThreads), 0, st, A);
+  hipLaunchKernelGGL(lfx::visibility_pairs_kernel, dim3(blocks_for(n_viewers, lfx::kVisThreads)), dim3(lfx::kVisThreads), 0, st, A);
   LFX_HIP(c, hipGetLastError());
   for (uint32_t chunk = 0; chunk < n_chunks; chunk++) {
     A.chunk_lo = chunk * M;
@@ -167,13 +167,13 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
     LFX_HIP(c, hipMemsetAsync(v->images.p, 0xFF, sizeof(uint32_t) * cells, st));
     hipLaunchKernelGGL(lfx::visibility_image_kernel, dim3(kImageBlocks, A.chunk_n), dim3(lfx::kVisThreads), 0, st, A);
     LFX_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(lfx::visibility_occupied_kernel, dim3((uint32_t)((cells + lfx::kVisThreads - 1u) / lfx::kVisThreads)), dim3(lfx::kVisThreads), 0, st, A, cells);
+    hipLaunchKernelGGL(lfx::visibility_occupied_kernel, dim3(blocks_for(cells, lfx::kVisThreads)), dim3(lfx::kVisThreads), 0, st, A, cells);
     LFX_HIP(c, hipGetLastError());
     for (int kind = 0; kind < 2; kind++) {
       if (hi[kind] == lo[kind]) {continue;}
-      const uint32_t blocks = (uint32_t)((hi[kind] - lo[kind] + lfx::kVisThreads - 1u) / lfx::kVisThreads);
-      hipLaunchKernelGGL(lfx::visibility_vote_kernel, dim3(blocks), dim3(lfx::kVisThreads), 0, st, A, ks.records[kind], ks.d_begin[kind], ks.poses,
-        v->table.p, v->viewers.p, v->images.p, kind, lo[kind], hi[kind], words[kind], word_off[kind], d_flags[kind]);
+      hipLaunchKernelGGL(lfx::visibility_vote_kernel, dim3(blocks_for(hi[kind] - lo[kind], lfx::kVisThreads)), dim3(lfx::kVisThreads), 0, st, A,
+        ks.records[kind], ks.d_begin[kind], ks.poses, v->table.p, v->viewers.p, v->images.p, kind, lo[kind], hi[kind], words[kind],
+        word_off[kind], d_flags[kind]);
       LFX_HIP(c, hipGetLastError());
     }
   }

@@ -740,91 +740,70 @@ def trajectory_from_gyro(times, rates, bias=None, velocity=None):
     return out
 
 
-def scan_context_config(config=None, **fields):
-    """lfx_scan_context_config: the defaults (lfx_scan_context_default_config) with the given fields replaced.  config: None,
-    a dict of fields, or a B.ScanContextConfig (copied)."""
-    cfg = B.ScanContextConfig()
-    if isinstance(config, B.ScanContextConfig):
+def _config(struct, default_name, what, config, fields):
+    """What the *_config functions share: a new `struct` holding the defaults (the library's default_name) with the given
+    fields replaced.  config: None, a dict of fields, or a `struct` (copied); `what` names the settings in a refusal."""
+    cfg = struct()
+    if isinstance(config, struct):
         C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
         config = None
     else:
-        B.load().lfx_scan_context_default_config(C.byref(cfg))
+        getattr(B.load(), default_name)(C.byref(cfg))
     for k, v in dict(config or {}, **fields).items():
-        if k not in dict(B.ScanContextConfig._fields_):
-            raise TypeError("unknown scan-context setting %r" % k)
+        if k not in dict(struct._fields_):
+            raise TypeError("unknown %s setting %r" % (what, k))
         setattr(cfg, k, v)
     return cfg
+
+
+def _tables(tables_name, what, cfg, W, n_last):
+    """What the *_tables functions share: (cos [W], sin [W], the config's third table [n_last]), float64, from the library's
+    tables_name.  The arrays are sized for any config: a refused one must not write past them before it is refused -- it
+    writes nothing."""
+    cs, sn, last = np.zeros(max(W, 1)), np.zeros(max(W, 1)), np.zeros(n_last)
+    rc = getattr(B.load(), tables_name)(C.byref(cfg), _pd(cs), _pd(sn), _pd(last))
+    if rc != 0:
+        raise B.LfxError(rc, "the %s config is refused" % what)
+    return cs[:W], sn[:W], last
+
+
+def scan_context_config(config=None, **fields):
+    """lfx_scan_context_config: the defaults (lfx_scan_context_default_config) with the given fields replaced.  config: None,
+    a dict of fields, or a B.ScanContextConfig (copied)."""
+    return _config(B.ScanContextConfig, "lfx_scan_context_default_config", "scan-context", config, fields)
 
 
 def scan_context_tables(config=None):
     """lfx_scan_context_tables: (sector_cos [S], sector_sin [S], ring_r2 [R + 1]), float64 -- the tables the descriptor kernel is
     given, and the only source of them.  Host only."""
     cfg = scan_context_config(config)
-    S, R = int(cfg.n_sectors), int(cfg.n_rings)
-    # (sized for any config: a refused one must not write past the arrays before it is refused -- it writes nothing)
-    cs, sn, r2 = np.zeros(max(S, 1)), np.zeros(max(S, 1)), np.zeros(R + 1)
-    rc = B.load().lfx_scan_context_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(r2))
-    if rc != 0:
-        raise B.LfxError(rc, "the scan-context config is refused")
-    return cs[:S], sn[:S], r2
+    return _tables("lfx_scan_context_tables", "scan-context", cfg, int(cfg.n_sectors), int(cfg.n_rings) + 1)
 
 
 def segment_config(config=None, **fields):
     """lfx_segment_config: the defaults (lfx_segment_default_config) with the given fields replaced.  config: None, a dict of
     fields, or a B.SegmentConfig (copied)."""
-    cfg = B.SegmentConfig()
-    if isinstance(config, B.SegmentConfig):
-        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        config = None
-    else:
-        B.load().lfx_segment_default_config(C.byref(cfg))
-    for k, v in dict(config or {}, **fields).items():
-        if k not in dict(B.SegmentConfig._fields_):
-            raise TypeError("unknown segmentation setting %r" % k)
-        setattr(cfg, k, v)
-    return cfg
+    return _config(B.SegmentConfig, "lfx_segment_default_config", "segmentation", config, fields)
 
 
 def segment_tables(config=None):
     """lfx_segment_tables: (col_cos [W], col_sin [W], consts [4]), float64 -- the tables the segmentation kernels are given, and
     the only source of them.  Host only."""
     cfg = segment_config(config)
-    W = int(cfg.n_columns)
-    # (sized for any config: a refused one writes nothing)
-    cs, sn, consts = np.zeros(max(W, 1)), np.zeros(max(W, 1)), np.zeros(4)
-    rc = B.load().lfx_segment_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(consts))
-    if rc != 0:
-        raise B.LfxError(rc, "the segmentation config is refused")
-    return cs[:W], sn[:W], consts
+    return _tables("lfx_segment_tables", "segmentation", cfg, int(cfg.n_columns), 4)
 
 
 def visibility_config(config=None, **fields):
     """lfx_visibility_config: the defaults (lfx_visibility_default_config) with the given fields replaced.  config: None, a
     dict of fields, or a B.VisibilityConfig (copied)."""
-    cfg = B.VisibilityConfig()
-    if isinstance(config, B.VisibilityConfig):
-        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        config = None
-    else:
-        B.load().lfx_visibility_default_config(C.byref(cfg))
-    for k, v in dict(config or {}, **fields).items():
-        if k not in dict(B.VisibilityConfig._fields_):
-            raise TypeError("unknown visibility setting %r" % k)
-        setattr(cfg, k, v)
-    return cfg
+    return _config(B.VisibilityConfig, "lfx_visibility_default_config", "visibility", config, fields)
 
 
 def visibility_tables(config=None):
     """lfx_visibility_tables: (col_cos [W], col_sin [W], row_tan [H + 1]), float64 -- the tables the visibility kernels are
     given, and the only source of them.  Host only."""
     cfg = visibility_config(config)
-    H, W = int(cfg.n_rows), int(cfg.n_columns)
-    # (sized for any config: a refused one writes nothing)
-    cs, sn, rt = np.zeros(max(W, 1)), np.zeros(max(W, 1)), np.zeros(H + 1)
-    rc = B.load().lfx_visibility_tables(C.byref(cfg), _pd(cs), _pd(sn), _pd(rt))
-    if rc != 0:
-        raise B.LfxError(rc, "the visibility config is refused")
-    return cs[:W], sn[:W], rt
+    return _tables("lfx_visibility_tables", "visibility", cfg, int(cfg.n_columns), int(cfg.n_rows) + 1)
 
 
 def _msg_buffer():
@@ -901,8 +880,31 @@ def _download(L, ptr, n_records, stream=0):
     return out
 
 
-class ScanMap:
+class _Handle:
+    """What the classes over an object of the library share: `handle` (set by their __init__, after _fx and _L), the check
+    of a return code against the context's message, and close() -- the destroy call named by _destroy, once."""
+
+    _destroy = None
+
+    def _check(self, rc):
+        B.check(self._fx._ctx, rc, self._L)
+
+    def close(self):
+        if self.handle:
+            getattr(self._L, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ScanMap(_Handle):
     """lfx_map: the index a scan is matched against -- the place of the reference's KDTreeEigen (kdtree.hpp:50-71)."""
+
+    _destroy = "lfx_map_destroy"
 
     def __init__(self, fx, d_points, n_points, cell_size=1.0, stream=0, host_points=None):
         self._fx = fx
@@ -934,21 +936,12 @@ class ScanMap:
             self._fx._ctx, self.handle, C.c_void_p(int(d_queries)), int(n_queries), int(k), C.c_void_p(int(d_neighbours)),
             C.c_void_p(int(d_squared_distances)), C.c_void_p(int(d_indices)), C.c_void_p(int(stream))))
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_map_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Odometry:
+class Odometry(_Handle):
     """lfx_odometry: scan-to-local-map odometry -- Odometry<..., EdgeSurfaceMap, EdgeSurfaceScan> (odometry.hpp:52-63) with the
     store and the window maps on the device.  Poses are 3 x 4 [R | t] (point_to_map)."""
+
+    _destroy = "lfx_odometry_destroy"
 
     def __init__(self, fx, reports=False, **config):
         self._fx = fx
@@ -1076,22 +1069,13 @@ class Odometry:
         B.check(self._fx._ctx, self._L.lfx_odometry_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
         return bool(w[0]), bool(w[1])
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_odometry_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Mapper:
+class Mapper(_Handle):
     """lfx_mapper: MapBuilder<PointType> (map.hpp:95-153) with its map on the device -- per cloud: empty -> EMPTY; the pose too
     close to the last added pose (PoseDiffIsSufficientlySmall) -> TOO_CLOSE; else ADDED, the cloud transformed by its pose
     appended to the map.  Poses are 3 x 4 [R | t].  Outcomes: binding.KEYFRAME_ADDED / _EMPTY / _TOO_CLOSE."""
+
+    _destroy = "lfx_mapper_destroy"
 
     def __init__(self, fx, **config):
         self._fx = fx
@@ -1164,22 +1148,13 @@ class Mapper:
         B.check(self._fx._ctx, self._L.lfx_mapper_save(self._fx._ctx, self.handle, os.fsencode(path), C.byref(w), C.c_void_p(int(stream))))
         return bool(w.value)
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_mapper_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RollingMap:
+class RollingMap(_Handle):
     """lfx_rolling_map: one point per voxel in a window that follows the vehicle, an edge store and a surface store (kind:
     'edge' / 'surface' or binding.ROLLING_EDGE / ROLLING_SURFACE).  Inserts keep the first point of a voxel (lowest (cloud,
     index) of the call that first reaches it); extract cuts a box out in ascending (vz, vy, vx).  Poses are 3 x 4 [R | t]."""
+
+    _destroy = "lfx_rolling_map_destroy"
 
     KINDS = {"edge": B.ROLLING_EDGE, "surface": B.ROLLING_SURFACE}
 
@@ -1302,23 +1277,14 @@ class RollingMap:
         B.check(self._fx._ctx, self._L.lfx_rolling_map_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
         return bool(w[0]), bool(w[1])
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_rolling_map_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlaceDb:
+class PlaceDb(_Handle):
     """lfx_place_db: scan-context descriptors of one config on the device, compared with a query under every column shift.
     Entries are numbered in insertion order.  A match is a dict: entry (None where the range held fewer than k entries),
     shift, distance, yaw -- a sensor that revisits the entry's place turned by +yaw about z gives that shift, so the revisit's
     initial pose is the entry's pose times Rz(yaw)."""
+
+    _destroy = "lfx_place_db_destroy"
 
     def __init__(self, fx, capacity, config=None):
         self._fx = fx
@@ -1394,17 +1360,6 @@ class PlaceDb:
         k = int(k)
         return [[_match(m) for m in res[q * k:(q + 1) * k]] for q in range(len(gates))], [int(n) for n in n_eligible]
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_place_db_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _match(m):
     """lfx_place_match as a dict (entry None: the empty match)"""
@@ -1414,17 +1369,7 @@ def _match(m):
 def pose_graph_config(config=None, **fields):
     """lfx_pose_graph_config: the defaults (lfx_pose_graph_default_config) with the given fields replaced.  config: None, a
     dict of fields, or a B.PoseGraphConfig (copied)."""
-    cfg = B.PoseGraphConfig()
-    if isinstance(config, B.PoseGraphConfig):
-        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        config = None
-    else:
-        B.load().lfx_pose_graph_default_config(C.byref(cfg))
-    for k, v in dict(config or {}, **fields).items():
-        if k not in dict(B.PoseGraphConfig._fields_):
-            raise TypeError("unknown pose-graph setting %r" % k)
-        setattr(cfg, k, v)
-    return cfg
+    return _config(B.PoseGraphConfig, "lfx_pose_graph_default_config", "pose-graph", config, fields)
 
 
 def edge_information(pose_j, report_information):
@@ -1476,10 +1421,12 @@ def pose_graph_priors(node, z, information, lever=None, position=False, robust=F
     return p
 
 
-class PoseGraph:
+class PoseGraph(_Handle):
     """lfx_pose_graph: poses (nodes) and relative-pose measurements (edges) on the device, optimised there by Gauss-Newton with
     the chain-and-loop solver (include/lfx.h, the pose graph section).  Poses are [3][4] = [R | t] float64; node 0 is fixed
     unless release_first frees it.  Absolute fixes of single nodes are priors: reserve_priors once, then add_priors."""
+
+    _destroy = "lfx_pose_graph_destroy"
 
     def __init__(self, fx, max_nodes, max_edges, config=None, **fields):
         self._fx = fx
@@ -1488,9 +1435,6 @@ class PoseGraph:
         h = C.c_void_p()
         B.check(fx._ctx, self._L.lfx_pose_graph_create(fx._ctx, C.byref(self.config), C.byref(h)), self._L)
         self.handle = h
-
-    def _check(self, rc):
-        B.check(self._fx._ctx, rc, self._L)
 
     def info(self):
         i = B.PoseGraphInfo()
@@ -1587,23 +1531,14 @@ class PoseGraph:
         return dict(n_priors=int(i.n_priors), max_priors=int(i.max_priors), n_downweighted=int(i.n_downweighted), reserved=int(i.reserved),
                     chi2=float(i.chi2))
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_pose_graph_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Keyframes:
+class Keyframes(_Handle):
     """lfx_keyframes: every keyframe's edge and surface records on the device in the SENSOR frame with one pose per keyframe,
     and world clouds written from the two at the poses of the moment (include/lfx.h, the keyframe store section) -- what makes
     a map follow a pose graph.  kind: 'edge' / 'surface' (or B.KEYFRAMES_EDGE / _SURFACE).  Poses are [3][4] = [R | t] float64;
     keyframe ids count from 0 in order of addition."""
+
+    _destroy = "lfx_keyframes_destroy"
 
     KINDS = {"edge": B.KEYFRAMES_EDGE, "surface": B.KEYFRAMES_SURFACE, B.KEYFRAMES_EDGE: B.KEYFRAMES_EDGE, B.KEYFRAMES_SURFACE: B.KEYFRAMES_SURFACE}
 
@@ -1619,9 +1554,6 @@ class Keyframes:
         B.check(fx._ctx, self._L.lfx_keyframes_create(fx._ctx, C.byref(cfg), C.byref(h)), self._L)
         self.handle = h
         self.config = cfg
-
-    def _check(self, rc):
-        B.check(self._fx._ctx, rc, self._L)
 
     @classmethod
     def _kind(cls, kind):
@@ -1785,21 +1717,12 @@ class Keyframes:
         self._check(self._L.lfx_keyframes_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
         return bool(w[0]), bool(w[1])
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_keyframes_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Visibility:
+class Visibility(_Handle):
     """lfx_visibility: the visibility votes of a window of a Keyframes store's keyframes on each other's records, and the
     DYNAMIC flag they decide (include/lfx.h, the visibility section).  The fields of lfx_visibility_config as keywords."""
+
+    _destroy = "lfx_visibility_destroy"
 
     def __init__(self, fx, max_window=1024, max_resident_images=None, config=None, **fields):
         self._fx = fx
@@ -1810,9 +1733,6 @@ class Visibility:
         B.check(fx._ctx, self._L.lfx_visibility_create(fx._ctx, C.byref(cfg), int(max_window), resident, C.byref(h)), self._L)
         self.handle = h
         self.config = cfg
-
-    def _check(self, rc):
-        B.check(self._fx._ctx, rc, self._L)
 
     def info(self):
         i = B.VisibilityInfo()
@@ -1852,41 +1772,25 @@ class Visibility:
                                                C.c_void_p(int(stream))))
         return flags, votes, self.result(r)
 
-    def close(self):
-        if self.handle:
-            self._L.lfx_visibility_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def loop_closer_config(config=None, **fields):
     """lfx_loop_closer_config: the defaults (lfx_loop_closer_default_config) with the given fields replaced.  config: None, a
     dict of fields, or a B.LoopCloserConfig (copied).  submap_capacity: one number or (edge, surface)."""
-    cfg = B.LoopCloserConfig()
-    if isinstance(config, B.LoopCloserConfig):
-        C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        config = None
-    else:
-        B.load().lfx_loop_closer_default_config(C.byref(cfg))
-    for k, v in dict(config or {}, **fields).items():
-        if k not in dict(B.LoopCloserConfig._fields_):
-            raise TypeError("unknown loop-closer setting %r" % k)
-        if k == "submap_capacity":
-            v = (v, v) if np.isscalar(v) else tuple(v)
-            cfg.submap_capacity[0], cfg.submap_capacity[1] = int(v[0]), int(v[1])
-        else:
-            setattr(cfg, k, v)
+    if not isinstance(config, B.LoopCloserConfig):
+        config, fields = None, dict(config or {}, **fields)
+    capacity = fields.pop("submap_capacity", None)
+    cfg = _config(B.LoopCloserConfig, "lfx_loop_closer_default_config", "loop-closer", config, fields)
+    if capacity is not None:
+        v = (capacity, capacity) if np.isscalar(capacity) else tuple(capacity)
+        cfg.submap_capacity[0], cfg.submap_capacity[1] = int(v[0]), int(v[1])
     return cfg
 
 
-class LoopCloser:
+class LoopCloser(_Handle):
     """lfx_loop_closer: revisits found in a PlaceDb, verified against submaps of a Keyframes store and closed in a PoseGraph
     (include/lfx.h, the loop closer section).  Keyframe id == place entry == graph node id.  The three outlive the closer."""
+
+    _destroy = "lfx_loop_closer_destroy"
 
     REASONS = ("accepted", "no_candidate", "empty_query", "empty_submap", "align_failed", "no_report", "rank", "degenerate", "rms_edge",
                "rms_surface", "inliers", "sigma2")
@@ -1900,9 +1804,6 @@ class LoopCloser:
         B.check(fx._ctx, self._L.lfx_loop_closer_create(fx._ctx, C.byref(self.config), keyframes.handle, place_db.handle, graph.handle, C.byref(h)),
                 self._L)
         self.handle = h
-
-    def _check(self, rc):
-        B.check(self._fx._ctx, rc, self._L)
 
     def info(self):
         i = B.LoopCloserInfo()
@@ -1972,14 +1873,3 @@ class LoopCloser:
                      n_robust_downweighted=int(g.n_robust_downweighted)) if r.n_accepted else None
         return ([self.closure(c) for c in closures[:int(count)]],
                 dict(n_detected=int(r.n_detected), n_verified=int(r.n_verified), n_accepted=int(r.n_accepted), followed=bool(r.followed), graph=graph))
-
-    def close(self):
-        if self.handle:
-            self._L.lfx_loop_closer_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
