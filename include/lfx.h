@@ -1341,6 +1341,49 @@ int lfx_pose_graph_release_first(lfx_ctx *ctx, lfx_pose_graph *graph, int releas
 int lfx_pose_graph_prior_chi2(lfx_ctx *ctx, const lfx_pose_graph *graph, uint32_t first, uint32_t count, double *rho, double *w, void *stream);
 int lfx_pose_graph_prior_info(const lfx_pose_graph *graph, lfx_pose_graph_prior_info_t *info);
 
+/* COVARIANCES: how well the optimised nodes are known.  H is the matrix of the solver's last linearisation, sum A^T w Omega A
+ * over edges and priors with the Huber weights at the poses the last lfx_pose_graph_optimize left, and
+ *   Sigma = (H + lambda I)^-1  over the free nodes, lambda the config's damping:
+ * the matrix the solver factors, nothing else.  It is over the node increments (a, b) as ordered above -- a the rotation in
+ * the node's own frame, b the translation in the world frame, lfx_align_report.information's ordering -- so
+ * lfx_align_covariance_ros(pose_k, Sigma_kk, out) applies to a node's marginal unchanged.  A node nothing constrains has
+ * Sigma_kk = I / lambda.  A fixed node has no increment: every block of Sigma in its row or column is exactly 0.0 (not the
+ * identity P carries there).  Sigma is as good as the Omega that were fed: nothing is rescaled by chi^2 / dof.
+ * HOW: with H + lambda I = P + Jt^T Jt as in THE SOLVER, Sigma = P^-1 - V V^T, V = Y L_S^-T, S = I + Jt Y = L_S L_S^T;
+ * (P^-1)(k, k) and the blocks beside it come from the selected inverse of the chain factor.  All FP64, no floating-point
+ * atomic, every sum in a fixed order: the same graph gives the same bytes, however its edges were split over calls, whichever
+ * stream is used, whatever range or pairs are asked for.  Cost: the solve for V is (6 L)^2 / 2 * 6 N multiply-adds. */
+/* Allocates what the two calls below need: three [max_nodes][36] blocks of doubles (Sigma_kk, the chain factor's inverse
+ * diagonal, its transfer blocks), a status word, and the ids and cross blocks of the 64 pairs one launch takes
+ * (64 x (36 doubles + 2 ids)); Y is solved in place.  lfx_pose_graph_info's device_bytes grows by that amount.  As
+ * lfx_pose_graph_reserve_priors, an exception to "no later call allocates", for the same reason: the config cannot grow.  A
+ * second call is LFX_ERR_INVALID_ARGUMENT; a failed allocation LFX_ERR_OUT_OF_MEMORY, the graph as it was.  A graph that never
+ * reserves holds the memory it always did and computes the bytes it always did. */
+int lfx_pose_graph_reserve_marginals(lfx_ctx *ctx, lfx_pose_graph *graph);
+/* Sigma_kk of nodes first .. first + count - 1 ([count][36], row-major, exactly symmetric: the lower triangle is computed and
+ * mirrored).  Synchronous.  The first call after an optimise does the whole graph's work once and keeps all blocks on the
+ * device; later calls only copy, until the graph is next written (add_nodes, add_edges, add_priors, set_poses, set_fixed,
+ * release_first, optimize).  The poses are never touched, and the next optimise computes what it would have computed.
+ * *code: LFX_POSE_GRAPH_CONVERGED (0), or LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE where a pivot was not positive (damping 0 and a
+ * node nothing holds): cov_out is then untouched.  LFX_ERR_INVALID_ARGUMENT: before lfx_pose_graph_reserve_marginals; wherever
+ * lfx_pose_graph_edge_chi2 refuses (before the first optimise; nodes, edges, priors or poses written since) and after
+ * set_fixed or release_first since (H holds the flags of the optimise); a range outside the nodes. */
+int lfx_pose_graph_marginals(lfx_ctx *ctx, lfx_pose_graph *graph, uint32_t first, uint32_t count, double *cov_out, int32_t *code,
+                             void *stream);
+/* For each pair (i, j) of pairs[n][2], i != j in either order: out[p] = [[Sigma_ii, Sigma_ij], [Sigma_ji, Sigma_jj]], 12 x 12
+ * row-major, Sigma_ji = Sigma_ij^T exactly, the diagonal blocks byte for byte those of lfx_pose_graph_marginals.  The same
+ * refusals, code and caching (the marginals are computed if they are not there yet).  i == j or an id that is not a node is
+ * LFX_ERR_INVALID_ARGUMENT with nothing written.  Between nodes a chain apart the chain part of Sigma_ij is a product of
+ * j - i 6 x 6 blocks, one wave per pair: the cost grows with the distance. */
+int lfx_pose_graph_joint_covariances(lfx_ctx *ctx, lfx_pose_graph *graph, const uint32_t *pairs, uint32_t n, double *out,
+                                     int32_t *code, void *stream);
+/* The covariance of the residual r of an edge (i, j, Z = T_i^-1 T_j) at the current poses, from lfx_pose_graph_joint_covariances'
+ * block of (i, j): r changes by A_i delta_i + A_j delta_j, so out = [A_i A_j] joint [A_i A_j]^T, with A_i, A_j those above at
+ * phi = 0: Jri = I, R_Z^T R_i^T = R_j^T, R_Z^T = R_j^T R_i, d = R_i^T (t_j - t_i).  Its inverse is in the coordinates of an
+ * edge's Omega: a loop candidate Z' passes a gate when r(Z')^T out^-1 r(Z') <= chi^2.  Host only, as
+ * lfx_pose_graph_edge_information; every sum of three terms is (a0 b0 + a1 b1) + a2 b2; exactly symmetric. */
+int lfx_pose_graph_relative_covariance(const double pose_i[12], const double pose_j[12], const double joint[144], double out[36]);
+
 /* --- the keyframe store: sensor-frame clouds on the device, world maps written from them at the poses of the moment ------ */
 /* What lets a map follow a pose graph.  lfx_mapper and lfx_odometry keep their clouds already in the world, so a corrected
  * pose cannot reach them; the store keeps every keyframe's records as the sensor saw them and one pose per keyframe, and a

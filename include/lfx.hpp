@@ -883,6 +883,36 @@ public:
   }
   // node 0 free from now on (SetFixed(0) still holds it); without a prior nothing but the damping holds a free first node
   void ReleaseFirst(bool released = true, void * stream = nullptr) {Check(lfx_pose_graph_release_first(fx_.handle(), graph_, released ? 1 : 0, stream));}
+  // covariances of the optimised nodes (lfx.h, COVARIANCES): room for them, once; then per node Sigma_kk (count x 36
+  // doubles) and per pair (i, j) the 12 x 12 joint block (pairs: i0, j0, i1, j1, ...; n x 144 doubles).  `code` (may be
+  // null) takes LFX_POSE_GRAPH_CONVERGED or _NOT_POSITIVE_DEFINITE; without it the latter throws.
+  void ReserveMarginals() {Check(lfx_pose_graph_reserve_marginals(fx_.handle(), graph_));}
+  std::vector<double> Marginals(std::uint32_t first, std::uint32_t count, std::int32_t * code = nullptr, void * stream = nullptr)
+  {
+    std::vector<double> out(static_cast<std::size_t>(count) * 36u);
+    std::int32_t got = 0;
+    Check(lfx_pose_graph_marginals(fx_.handle(), graph_, first, count, out.data(), &got, stream));
+    Coded(got, code);
+    return out;
+  }
+  std::vector<double> Marginals() {return Marginals(0, Info().n_nodes);}
+  std::vector<double> JointCovariances(const std::vector<std::uint32_t> & pairs, std::int32_t * code = nullptr, void * stream = nullptr)
+  {
+    std::vector<double> out(pairs.size() / 2u * 144u);
+    std::int32_t got = 0;
+    Check(pairs.size() % 2u == 0u ? lfx_pose_graph_joint_covariances(fx_.handle(), graph_, pairs.data(), static_cast<std::uint32_t>(pairs.size() / 2u),
+      out.data(), &got, stream) : LFX_ERR_INVALID_ARGUMENT);
+    Coded(got, code);
+    return out;
+  }
+  // the covariance of the residual of an edge (i, j) at the current poses, from the pair's joint block
+  // (lfx_pose_graph_relative_covariance): its inverse gates a loop candidate
+  static std::vector<double> RelativeCovariance(const double pose_i[12], const double pose_j[12], const double joint[144])
+  {
+    std::vector<double> out(36);
+    if (lfx_pose_graph_relative_covariance(pose_i, pose_j, joint, out.data()) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "null argument");}
+    return out;
+  }
   // per prior rho and w at the poses the last Optimize left
   void PriorChi2(std::vector<double> & rho, std::vector<double> & w, void * stream = nullptr) const
   {
@@ -903,6 +933,10 @@ private:
   void Check(int rc) const
   {
     if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  static void Coded(std::int32_t got, std::int32_t * code)
+  {
+    if (code) {*code = got;} else if (got != LFX_POSE_GRAPH_CONVERGED) {throw Error(LFX_ERR_INVALID_ARGUMENT, "H + lambda I is not positive definite");}
   }
   const FeatureExtraction & fx_;
   lfx_pose_graph * graph_ = nullptr;

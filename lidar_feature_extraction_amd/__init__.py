@@ -11,7 +11,7 @@ from .extraction import time_field_from_fields, motion_between, motion_twist, mo
 from .extraction import trajectory_segments, trajectory_from_gyro  # noqa: F401
 from .extraction import PlaceDb, scan_context_config, scan_context_tables  # noqa: F401
 from .extraction import segment_config, segment_tables  # noqa: F401
-from .extraction import PoseGraph, pose_graph_config, pose_graph_edges, pose_graph_priors, edge_information  # noqa: F401
+from .extraction import PoseGraph, pose_graph_config, pose_graph_edges, pose_graph_priors, edge_information, relative_covariance  # noqa: F401
 from .extraction import Keyframes  # noqa: F401
 from .extraction import LoopCloser, loop_closer_config  # noqa: F401
 from .extraction import Visibility, visibility_config, visibility_tables  # noqa: F401

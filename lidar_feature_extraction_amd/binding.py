@@ -370,6 +370,7 @@ EXPORTS = [
     "lfx_pose_graph_view", "lfx_pose_graph_edge_chi2", "lfx_pose_graph_edge_information",
     "lfx_pose_graph_reserve_priors", "lfx_pose_graph_add_priors", "lfx_pose_graph_release_first", "lfx_pose_graph_prior_chi2",
     "lfx_pose_graph_prior_info",
+    "lfx_pose_graph_reserve_marginals", "lfx_pose_graph_marginals", "lfx_pose_graph_joint_covariances", "lfx_pose_graph_relative_covariance",
     "lfx_keyframes_default_config", "lfx_keyframes_create", "lfx_keyframes_destroy", "lfx_keyframes_info", "lfx_keyframes_view",
     "lfx_keyframes_add", "lfx_keyframes_add_host", "lfx_keyframes_set_poses", "lfx_keyframes_poses", "lfx_keyframes_follow",
     "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save", "lfx_keyframes_build_masked",
@@ -566,6 +567,10 @@ def load(test_hooks=False):
     L.lfx_pose_graph_release_first.argtypes = [vp, vp, i32, vp]
     L.lfx_pose_graph_prior_chi2.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.lfx_pose_graph_prior_info.argtypes = [vp, C.POINTER(PoseGraphPriorInfo)]
+    L.lfx_pose_graph_reserve_marginals.argtypes = [vp, vp]
+    L.lfx_pose_graph_marginals.argtypes = [vp, vp, u32, u32, vp, C.POINTER(i32), vp]
+    L.lfx_pose_graph_joint_covariances.argtypes = [vp, vp, vp, u32, vp, C.POINTER(i32), vp]
+    L.lfx_pose_graph_relative_covariance.argtypes = [vp, vp, vp, vp]
     pkf, pkc = C.POINTER(KeyframesConfig), C.POINTER(KeyframesClouds)
     L.lfx_keyframes_default_config.argtypes = [pkf]
     L.lfx_keyframes_default_config.restype = None

@@ -727,4 +727,241 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_step_kernel(PgArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------------------------- 6. covariances
+// Sigma = (H + lambda I)^-1 = P^-1 - V V^T with V = Y L_S^-T (Woodbury on H = P + Jt^T Jt, S = I + Jt Y = L_S L_S^T), from
+// the factor, Y and L_S that kernels 2 to 4 leave (lfx_posegraph.hip runs them once more, on the final linearisation).
+// What is new: the selected inverse of the chain factor, the rows of Y solved against L_S in place, and the 6 x 6 products.
+// The same rules as above: no atomic, every sum in a fixed order, every kernel returns at once when the status word is set.
+struct PgMargArgs
+{
+  double * ginv;                         // [N][36]: G_k = (P^-1)(k, k), exactly symmetric
+  double * tblk;                         // [N][36]: T_k = -L_k^-T M_k^T, so that (P^-1)(k, m) = T_k (P^-1)(k + 1, m) for m > k
+  double * cov;                          // [N][36]: Sigma_kk
+  const uint32_t * pairs;                // [n][2]: i < j
+  double * cross;                        // [n][36]: Sigma_ij
+};
+
+constexpr int kPgRows = 64;              // the rows of Y one workgroup of the solve takes
+constexpr int kPgCols = 32;              // the columns of one pass of its trailing update
+constexpr int kPgPairs = 64;             // the pairs of one launch of the joint kernel
+
+// The selected inverse of P = (L, M)(L, M)^T, backward over the nodes, one wave, lane (r, c) one entry as in the factor:
+//   G_{N-1} = L^-T L^-1,  T_k = -L_k^-T M_k^T,  G_k = L_k^-T L_k^-1 + T_k G_{k+1} T_k^T
+// L_k^-1 is every lane's own 6 x 6 triangular inverse in registers (fac_l's diagonal already holds 1 / L(r, r)); the
+// products go through LDS.  Lane (r, c) and lane (c, r) evaluate the same expression, so G is symmetric bit for bit.  The
+// blocks of node k - 1 are loaded while node k's are worked on.
+__global__ __launch_bounds__(kPgWave) void pose_graph_chain_inverse_kernel(PgArgs a, PgMargArgs g)
+{
+  __shared__ double Ll[36], Ml[36], Il[36], Tl[36], Gl[36], Xl[36];
+  const uint32_t lane = threadIdx.x, N = a.n_nodes;
+  if (*a.status != kPgOk || N == 0u) {return;}
+  const bool on = lane < 36u;
+  const int r = on ? (int)lane / 6 : 0, c = on ? (int)lane % 6 : 0;
+  const int hi = r > c ? r : c, lo = r > c ? c : r;
+  double ln = on ? a.fac_l[(size_t)36 * (N - 1u) + lane] : 0.0, mn = on ? a.fac_m[(size_t)36 * (N - 1u) + lane] : 0.0;
+  for (uint32_t k = N; k-- > 0u; ) {
+    const bool last = k + 1u == N;
+    if (on) {Ll[lane] = ln; Ml[lane] = mn;}
+    if (on && k > 0u) {ln = a.fac_l[(size_t)36 * (k - 1u) + lane]; mn = a.fac_m[(size_t)36 * (k - 1u) + lane];}
+    __syncthreads();
+    double L[36], I[36];
+    for (int i = 0; i < 6; i++) {
+      for (int j = 0; j <= i; j++) {L[6 * i + j] = Ll[6 * i + j];}
+    }
+    // L^-1, column by column: I(j, j) = 1 / L(j, j), I(i, j) = -(sum_{j <= m < i} L(i, m) I(m, j)) / L(i, i)
+    double mine = 0.0;
+    for (int j = 0; j < 6; j++) {
+      I[7 * j] = L[7 * j];
+      for (int i = j + 1; i < 6; i++) {
+        double v = 0.0;
+        for (int m = j; m < i; m++) {v += L[6 * i + m] * I[6 * m + j];}
+        I[6 * i + j] = -v * L[7 * i];
+      }
+      for (int i = j; i < 6; i++) {mine = (i == r && j == c) ? I[6 * i + j] : mine;}
+    }
+    if (on) {Il[lane] = mine;}                        // (zero above the diagonal)
+    __syncthreads();
+    double t = 0.0, w = 0.0;
+    if (on) {
+      // T(r, c) = -sum_{m >= r} L^-1(m, r) M(c, m);  W(hi, lo) = sum_{m >= hi} L^-1(m, hi) L^-1(m, lo)
+      if (!last) {
+        for (int m = r; m < 6; m++) {t += Il[6 * m + r] * Ml[6 * c + m];}
+        t = -t;
+      }
+      for (int m = hi; m < 6; m++) {w += Il[6 * m + hi] * Il[6 * m + lo];}
+      Tl[lane] = t;
+    }
+    __syncthreads();
+    if (on && !last) {                                  // X = T G_{k+1}
+      double x = 0.0;
+      for (int m = 0; m < 6; m++) {x += Tl[6 * r + m] * Gl[6 * m + c];}
+      Xl[lane] = x;
+    }
+    __syncthreads();
+    if (on) {
+      double v = w;
+      if (!last) {
+        double u = 0.0;
+        for (int m = 0; m < 6; m++) {u += Xl[6 * hi + m] * Tl[6 * lo + m];}
+        v = w + u;
+      }
+      g.ginv[(size_t)36 * k + lane] = v;
+      g.tblk[(size_t)36 * k + lane] = t;
+      Gl[lane] = v;                                     // (everyone read G_{k+1} before the barrier above)
+    }
+    __syncthreads();
+  }
+}
+
+// V = Y(:, 1 .. 6 L) L_S^-T in place: every row v of Y solves v L_S^T = y, a forward substitution of length 6 L that no other
+// row takes part in.  A workgroup takes kPgRows rows and walks L_S in panels of kPgPanel columns: the tile's panel columns
+// and the panel's diagonal block go to LDS, one thread per row solves its 48 entries there (rows per lane, in LDS, where a
+// row stride of 49 doubles keeps 32 lanes on 32 bank pairs); then the trailing update of the tile's remaining columns,
+// kPgCols at a pass, with COLUMNS per lane: consecutive lanes read and write consecutive doubles of one row of Y, whose rows
+// start one double past a multiple of eight and so can be walked along, not across.  An entry's sums have one
+// order whatever the tile it falls in.
+__global__ __launch_bounds__(kPgThreads) void pose_graph_y_solve_kernel(PgArgs a)
+{
+  __shared__ double V[kPgRows][kPgPanel + 1], Lp[kPgPanel][kPgPanel + 1], Ls[kPgCols][kPgPanel + 1];
+  const uint32_t n = 6u * a.n_loop, rows = 6u * a.n_nodes, t = threadIdx.x, row0 = blockIdx.x * kPgRows;
+  if (*a.status != kPgOk || row0 >= rows) {return;}
+  const size_t ld = a.ldy;
+  for (uint32_t p0 = 0; p0 < n; p0 += kPgPanel) {
+    const uint32_t nb = n - p0 < (uint32_t)kPgPanel ? n - p0 : (uint32_t)kPgPanel;
+    for (uint32_t i = t; i < kPgRows * kPgPanel; i += kPgThreads) {
+      const uint32_t rr = i / kPgPanel, m = i % kPgPanel;
+      V[rr][m] = (row0 + rr < rows && m < nb) ? a.y[(size_t)(row0 + rr) * ld + 1u + p0 + m] : 0.0;
+    }
+    for (uint32_t i = t; i < kPgPanel * kPgPanel; i += kPgThreads) {
+      const uint32_t rr = i / kPgPanel, m = i % kPgPanel;
+      Lp[rr][m] = (rr < nb && m <= rr) ? a.s[(size_t)(p0 + rr) * n + p0 + m] : (rr == m ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    if (t < (uint32_t)kPgRows) {
+      double x[kPgPanel];
+      for (int cc = 0; cc < kPgPanel; cc++) {x[cc] = V[t][cc];}
+      for (int cc = 0; cc < kPgPanel; cc++) {
+        double v = x[cc];
+        for (int m = 0; m < cc; m++) {v -= x[m] * Lp[cc][m];}
+        x[cc] = v / Lp[cc][cc];
+      }
+      for (int cc = 0; cc < kPgPanel; cc++) {V[t][cc] = x[cc];}
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kPgRows * kPgPanel; i += kPgThreads) {
+      const uint32_t rr = i / kPgPanel, m = i % kPgPanel;
+      if (row0 + rr < rows && m < nb) {a.y[(size_t)(row0 + rr) * ld + 1u + p0 + m] = V[rr][m];}
+    }
+    // y(row, c) -= sum_m v(row, p0 + m) L_S(c, p0 + m) for c >= p0 + 48 (there are such columns behind a full panel only)
+    const uint32_t tc = t % kPgCols, tr = t / kPgCols;
+    for (uint32_t c0 = p0 + kPgPanel; c0 < n; c0 += kPgCols) {
+      __syncthreads();                                  // (the previous pass has read Ls)
+      for (uint32_t i = t; i < kPgCols * kPgPanel; i += kPgThreads) {
+        const uint32_t cc = i / kPgPanel, m = i % kPgPanel;
+        Ls[cc][m] = c0 + cc < n ? a.s[(size_t)(c0 + cc) * n + p0 + m] : 0.0;
+      }
+      __syncthreads();
+      constexpr int kPer = kPgRows / (kPgThreads / kPgCols);   // 8 rows per thread, kPgThreads / kPgCols apart
+      double acc[kPer];
+      for (int q = 0; q < kPer; q++) {acc[q] = 0.0;}
+      for (int m = 0; m < kPgPanel; m++) {
+        const double l = Ls[tc][m];
+        for (int q = 0; q < kPer; q++) {acc[q] += V[tr + (kPgThreads / kPgCols) * q][m] * l;}
+      }
+      if (c0 + tc < n) {
+        for (int q = 0; q < kPer; q++) {
+          const uint32_t row = row0 + tr + (kPgThreads / kPgCols) * q;
+          if (row < rows) {a.y[(size_t)row * ld + 1u + c0 + tc] -= acc[q];}
+        }
+      }
+    }
+    __syncthreads();                                    // (V, Lp and Ls are rewritten by the next panel)
+  }
+}
+
+// One workgroup per node: Sigma_kk = G_k - V_k V_k^T, V_k the node's six solved rows.  21 dot products of length 6 L, a
+// strided pass per thread and a tree, then the lower triangle mirrored.  Zeros for a fixed node.
+__global__ __launch_bounds__(kPgThreads) void pose_graph_marginal_kernel(PgArgs a, PgMargArgs g)
+{
+  __shared__ double part[21][kPgThreads];
+  const uint32_t k = blockIdx.x, t = threadIdx.x, n = 6u * a.n_loop, T = blockDim.x;
+  if (*a.status != kPgOk || k >= a.n_nodes) {return;}
+  const size_t ld = a.ldy;
+  double acc[21];
+  for (int i = 0; i < 21; i++) {acc[i] = 0.0;}
+  for (uint32_t q = t; q < n; q += T) {
+    double v[6];
+    for (int r = 0; r < 6; r++) {v[r] = a.y[((size_t)6 * k + r) * ld + 1u + q];}
+    int i = 0;
+    for (int r = 0; r < 6; r++) {
+      for (int c = 0; c <= r; c++) {acc[i++] += v[r] * v[c];}
+    }
+  }
+  for (int i = 0; i < 21; i++) {part[i][t] = acc[i];}
+  __syncthreads();
+  for (uint32_t h = T / 2; h > 0; h >>= 1) {
+    if (t < h) {
+      for (int i = 0; i < 21; i++) {part[i][t] += part[i][t + h];}
+    }
+    __syncthreads();
+  }
+  if (t >= 36u) {return;}
+  const uint32_t r = t / 6u, c = t % 6u, hi = r > c ? r : c, lo = r > c ? c : r;
+  const double v = g.ginv[(size_t)36 * k + 6u * hi + lo] - part[hi * (hi + 1u) / 2u + lo][0];
+  g.cov[(size_t)36 * k + t] = a.fixed[k] ? 0.0 : v;
+}
+
+// One wave per pair (i, j), i < j: Sigma_ij = (T_i T_{i+1} ... T_{j-1}) G_j - V_i V_j^T.  The product runs from the right,
+// X <- T_k X for k = j - 1 down to i, one 6 x 6 product per node between the two, lane (r, c) one entry.  The 36 dot products
+// of length 6 L: a strided pass per lane (lane t the columns t, t + 64, ...: six rows of each node read along), then a tree.
+// Zeros where either node is fixed.
+__global__ __launch_bounds__(kPgWave) void pose_graph_joint_kernel(PgArgs a, PgMargArgs g, uint32_t n_pairs)
+{
+  __shared__ double part[36][kPgWave];
+  __shared__ double Xl[36], Tl[36];
+  const uint32_t p = blockIdx.x, lane = threadIdx.x, n = 6u * a.n_loop;
+  if (*a.status != kPgOk || p >= n_pairs) {return;}
+  const uint32_t i = g.pairs[2u * p], j = g.pairs[2u * p + 1u];
+  if (i >= j || j >= a.n_nodes) {return;}              // (the host sends sorted pairs of nodes; nothing else is walked)
+  const bool on = lane < 36u;
+  const int r = on ? (int)lane / 6 : 0, c = on ? (int)lane % 6 : 0;
+  if (a.fixed[i] || a.fixed[j]) {
+    if (on) {g.cross[(size_t)36 * p + lane] = 0.0;}
+    return;
+  }
+  const size_t ld = a.ldy;
+  double acc[36];
+  for (int m = 0; m < 36; m++) {acc[m] = 0.0;}
+  for (uint32_t q = lane; q < n; q += kPgWave) {
+    double vi[6], vj[6];
+    for (int m = 0; m < 6; m++) {vi[m] = a.y[((size_t)6 * i + m) * ld + 1u + q]; vj[m] = a.y[((size_t)6 * j + m) * ld + 1u + q];}
+    for (int rr = 0; rr < 6; rr++) {
+      for (int cc = 0; cc < 6; cc++) {acc[6 * rr + cc] += vi[rr] * vj[cc];}
+    }
+  }
+  for (int m = 0; m < 36; m++) {part[m][lane] = acc[m];}
+  if (on) {Xl[lane] = g.ginv[(size_t)36 * j + lane];}
+  __syncthreads();
+  for (uint32_t h = kPgWave / 2; h > 0; h >>= 1) {
+    if (lane < h) {
+      for (int m = 0; m < 36; m++) {part[m][lane] += part[m][lane + h];}
+    }
+    __syncthreads();
+  }
+  double tn = on ? g.tblk[(size_t)36 * (j - 1u) + lane] : 0.0;
+  for (uint32_t k = j; k-- > i; ) {
+    if (on) {Tl[lane] = tn;}
+    if (on && k > i) {tn = g.tblk[(size_t)36 * (k - 1u) + lane];}
+    __syncthreads();
+    double x = 0.0;
+    if (on) {
+      for (int m = 0; m < 6; m++) {x += Tl[6 * r + m] * Xl[6 * m + c];}
+    }
+    __syncthreads();                                    // (everyone has read Xl)
+    if (on) {Xl[lane] = x;}
+    __syncthreads();
+  }
+  if (on) {g.cross[(size_t)36 * p + lane] = Xl[lane] - part[lane][0];}
+}
+
 }  // namespace lfx

@@ -267,6 +267,51 @@ int lfx_pose_graph_edge_information(const double pose_j[12], const double report
   return LFX_OK;
 }
 
+// The covariance of the residual of an edge (i, j, Z = T_i^-1 T_j) at the current poses, from the two nodes' joint covariance
+// (include/lfx.h): out = [A_i A_j] joint [A_i A_j]^T with the Jacobians at phi = 0, where Jri = I, R_Z^T R_i^T = R_j^T and
+// R_Z^T = R_j^T R_i.  Every sum of three terms is (a0 b0 + a1 b1) + a2 b2; the sums over the twelve increments run left to
+// right; the lower triangle is computed and mirrored.
+int lfx_pose_graph_relative_covariance(const double pose_i[12], const double pose_j[12], const double joint[144], double out[36])
+{
+  if (!pose_i || !pose_j || !joint || !out) {return LFX_ERR_INVALID_ARGUMENT;}
+  auto Ri = [&](int r, int c) {return pose_i[4 * r + c];};
+  auto Rj = [&](int r, int c) {return pose_j[4 * r + c];};
+  const double dt[3] = {pose_j[3] - pose_i[3], pose_j[7] - pose_i[7], pose_j[11] - pose_i[11]};
+  double d[3], M[9], dx[9];                           // d = R_i^T (t_j - t_i), M = R_j^T R_i = R_Z^T
+  for (int r = 0; r < 3; r++) {d[r] = (Ri(0, r) * dt[0] + Ri(1, r) * dt[1]) + Ri(2, r) * dt[2];}
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) {M[3 * r + c] = (Rj(0, r) * Ri(0, c) + Rj(1, r) * Ri(1, c)) + Rj(2, r) * Ri(2, c);}
+  }
+  dx[0] = 0.0; dx[1] = -d[2]; dx[2] = d[1]; dx[3] = d[2]; dx[4] = 0.0; dx[5] = -d[0]; dx[6] = -d[1]; dx[7] = d[0]; dx[8] = 0.0;
+  double A[72] = {0.0};                               // [A_i A_j], 6 x 12
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) {
+      A[12 * r + c] = -M[3 * r + c];
+      A[12 * (3 + r) + c] = (M[3 * r] * dx[c] + M[3 * r + 1] * dx[3 + c]) + M[3 * r + 2] * dx[6 + c];
+      A[12 * (3 + r) + 3 + c] = -Rj(c, r);
+      A[12 * r + 6 + c] = r == c ? 1.0 : 0.0;
+      A[12 * (3 + r) + 9 + c] = Rj(c, r);
+    }
+  }
+  double AS[72];                                      // A joint
+  for (int r = 0; r < 6; r++) {
+    for (int c = 0; c < 12; c++) {
+      double acc = 0.0;
+      for (int m = 0; m < 12; m++) {acc += A[12 * r + m] * joint[12 * m + c];}
+      AS[12 * r + c] = acc;
+    }
+  }
+  for (int r = 0; r < 6; r++) {
+    for (int c = 0; c <= r; c++) {
+      double acc = 0.0;
+      for (int m = 0; m < 12; m++) {acc += AS[12 * r + m] * A[12 * c + m];}
+      out[6 * r + c] = acc;
+      out[6 * c + r] = acc;
+    }
+  }
+  return LFX_OK;
+}
+
 // What the three azimuth-binned subsystems below share (the device's side: lfx_kernels_image.hpp).  Direction m of W is
 // -pi + 2 pi m / W: the first half of the table is the half circle y < 0, the second (from m = W / 2, angle 0) y >= 0.
 static void azimuth_table(uint32_t W, double * cos_out, double * sin_out)

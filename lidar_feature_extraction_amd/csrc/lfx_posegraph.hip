@@ -2,7 +2,9 @@
 // kept on the device, Gauss-Newton over them with the chain-and-loop solver.  The host keeps what it needs to check a call
 // before anything is queued (the edges' ends, which nodes are fixed) and builds the node -> (edge, side) incidence lists,
 // stable by edge id, whenever edges were added, and the node -> prior lists beside them.  Everything is allocated by
-// lfx_pose_graph_create, but the priors' four blocks: lfx_pose_graph_reserve_priors (the config's ABI is closed).
+// lfx_pose_graph_create, but the priors' four blocks: lfx_pose_graph_reserve_priors (the config's ABI is closed), and the
+// covariances' six: lfx_pose_graph_reserve_marginals.  The covariances (lfx_pose_graph_marginals, _joint_covariances) are
+// computed once after an optimise, from the linearisation it leaves, and kept until the graph is next written.
 #include "lfx_internal.hpp"
 #include "lfx_kernels_posegraph.hpp"
 
@@ -44,6 +46,16 @@ struct lfx_pose_graph
   DevBuf<double> plin;
   DevBuf<uint32_t> prior_begin, prior_inc;
   DevBuf<lfx::PgRecord> record;
+  // the covariances (lfx_pose_graph_reserve_marginals allocates them): G_k, T_k, Sigma_kk, a status word of their own, and
+  // one launch's pairs with their cross blocks
+  DevBuf<double> ginv, tblk, cov, cross;
+  DevBuf<uint32_t> pairs, mstatus;
+  bool marg_reserved = false;
+  bool marg_current = false;             // cov holds every node's block of the last optimise's linearisation (marg_code says how it went)
+  bool fixed_stale = false;              // set_fixed or release_first since the last linearisation: H on the device is another graph's
+  int32_t marg_code = 0;
+  std::vector<double> stage_cov, stage_cross;
+  std::vector<uint32_t> stage_pairs;
   PinnedBuf h_record;
   PinnedBuf h_poses;                     // poses on their way up ([max_nodes][12]): pinned, so that the copy is queued and the call returns
   Tail tail;                             // behind the last call that touched the graph: order_behind before a call's own
@@ -215,6 +227,77 @@ int relinearize(lfx_ctx * c, lfx_pose_graph * g, const lfx::PgArgs & a, hipStrea
   return launch_linearize(c, a, 0u, false, st);
 }
 
+// The front half of launch_step once more, on the linearisation that is on the device, for the covariances: factor P, solve
+// for Y, assemble and factor S -- no solve for z and no step, so the poses are never touched (y0 and z are scratch here).
+// A launcher of its own: launch_step stays as it is, and so do the bytes an optimise computes.
+int launch_factor(lfx_ctx * c, const lfx::PgArgs & a, hipStream_t st)
+{
+  const uint32_t n = 6u * a.n_loop, P = lfx::kPgPanel;
+  hipLaunchKernelGGL(lfx::pose_graph_chain_factor_kernel, dim3(1), dim3(lfx::kPgWave), 0, st, a);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::pose_graph_chain_solve_kernel, dim3((n + 1u + lfx::kPgWave - 1u) / lfx::kPgWave), dim3(lfx::kPgWave), 0, st, a);
+  LFX_HIP(c, hipGetLastError());
+  if (n == 0u) {return LFX_OK;}
+  hipLaunchKernelGGL(lfx::pose_graph_s_assemble_kernel, dim3((n + 1u + lfx::kPgThreads - 1u) / lfx::kPgThreads, n), dim3(lfx::kPgThreads), 0, st, a);
+  LFX_HIP(c, hipGetLastError());
+  for (uint32_t p0 = 0; p0 < n; p0 += P) {
+    hipLaunchKernelGGL(lfx::pose_graph_s_diag_kernel, dim3(1), dim3(lfx::kPgThreads), 0, st, a, p0, std::min(P, n - p0));
+    LFX_HIP(c, hipGetLastError());
+    if (p0 + P >= n) {break;}
+    const uint32_t below = n - (p0 + P), tiles = (below + lfx::kPgTile - 1u) / lfx::kPgTile;
+    hipLaunchKernelGGL(lfx::pose_graph_s_panel_kernel, dim3((below + lfx::kPgThreads - 1u) / lfx::kPgThreads), dim3(lfx::kPgThreads), 0, st, a, p0);
+    LFX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(lfx::pose_graph_s_update_kernel, dim3(tiles, tiles), dim3(lfx::kPgThreads), 0, st, a, p0);
+    LFX_HIP(c, hipGetLastError());
+  }
+  return LFX_OK;
+}
+
+lfx::PgMargArgs marg_args_of(lfx_pose_graph * g)
+{
+  lfx::PgMargArgs m{};
+  m.ginv = g->ginv.p; m.tblk = g->tblk.p; m.cov = g->cov.p; m.pairs = g->pairs.p; m.cross = g->cross.p;
+  return m;
+}
+
+// what lfx_pose_graph_marginals and lfx_pose_graph_joint_covariances both refuse
+int check_marginals(lfx_ctx * c, const lfx_pose_graph * g)
+{
+  if (!g->marg_reserved) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "lfx_pose_graph_reserve_marginals has not been called");}
+  if (!g->linearised || g->fixed_stale) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the graph has changed since the last lfx_pose_graph_optimize");}
+  return LFX_OK;
+}
+
+// Every node's Sigma_kk on the device (cov), G_k, T_k and V beside it for the joint blocks: the whole graph's work, once per
+// optimise.  Synchronous: the status word comes back.  The kernels run on the covariances' own status word.
+int ensure_marginals(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
+{
+  if (g->marg_current) {return g->tail.order_behind(c, st);}
+  int rc = g->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  lfx::PgArgs a = args_of(g);
+  a.status = g->mstatus.p;
+  const lfx::PgMargArgs m = marg_args_of(g);
+  const uint32_t n = 6u * a.n_loop;
+  LFX_HIP(c, hipMemsetAsync(g->mstatus.p, 0, sizeof(uint32_t), st));
+  rc = launch_factor(c, a, st);
+  if (rc != LFX_OK) {return rc;}
+  hipLaunchKernelGGL(lfx::pose_graph_chain_inverse_kernel, dim3(1), dim3(lfx::kPgWave), 0, st, a, m);
+  LFX_HIP(c, hipGetLastError());
+  if (n) {
+    hipLaunchKernelGGL(lfx::pose_graph_y_solve_kernel, dim3((6u * a.n_nodes + lfx::kPgRows - 1u) / lfx::kPgRows), dim3(lfx::kPgThreads), 0, st, a);
+    LFX_HIP(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(lfx::pose_graph_marginal_kernel, dim3(a.n_nodes), dim3(n > 64u ? lfx::kPgThreads : lfx::kPgWave), 0, st, a, m);
+  LFX_HIP(c, hipGetLastError());
+  uint32_t * word = reinterpret_cast<uint32_t *>(g->h_record.p);
+  LFX_HIP(c, hipMemcpyAsync(word, g->mstatus.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  g->marg_code = *word == lfx::kPgOk ? LFX_POSE_GRAPH_CONVERGED : LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE;
+  g->marg_current = true;
+  return g->tail.done(c, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -309,6 +392,7 @@ int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * pos
   g->n_nodes += n;
   g->topology_stale = true;
   g->linearised = false;
+  g->marg_current = false;
   return g->tail.done(c, st);
 }
 
@@ -322,6 +406,8 @@ int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int
   const int rs = g->tail.settle(c);
   if (rs != LFX_OK) {return rs;}
   if (node == 0u) {g->first_fixed = fixed != 0;}
+  g->marg_current = false;
+  g->fixed_stale = true;
   g->fixed[node] = ((node == 0u && !g->released) || fixed) ? 1 : 0;
   LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, st));
   return g->tail.done(c, st);
@@ -383,6 +469,7 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
   g->n_loop += loops;
   g->topology_stale = true;
   g->linearised = false;
+  g->marg_current = false;
   return g->tail.done(c, st);
 }
 
@@ -400,6 +487,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
   int rc = g->tail.order_behind(c, st);
   if (rc != LFX_OK) {return rc;}
   const lfx::PgArgs a = args_of(g);
+  g->marg_current = false;
   const size_t pose_bytes = sizeof(double) * 12u * g->n_nodes;
   LFX_HIP(c, hipMemcpyAsync(g->backup.p, g->poses.p, pose_bytes, hipMemcpyDeviceToDevice, st));
   LFX_HIP(c, hipMemsetAsync(g->status.p, 0, sizeof(uint32_t), st));
@@ -448,6 +536,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
     g->prior_down = rec[it].n_down_prior; g->prior_chi2 = rec[it].chi2_prior;
   }
   g->linearised = true;
+  g->fixed_stale = false;
   return g->tail.done(c, st);
 }
 
@@ -480,6 +569,7 @@ int lfx_pose_graph_set_poses(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, ui
   std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * count);
   LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
   g->linearised = false;
+  g->marg_current = false;
   return g->tail.done(c, st);
 }
 
@@ -594,6 +684,7 @@ int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gr
   g->n_priors += n;
   g->topology_stale = true;
   g->linearised = false;
+  g->marg_current = false;
   return g->tail.done(c, st);
 }
 
@@ -602,6 +693,8 @@ int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, 
   if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   g->released = released != 0;
+  g->marg_current = false;
+  g->fixed_stale = true;
   if (g->n_nodes == 0u) {return LFX_OK;}            // (lfx_pose_graph_add_nodes writes node 0's flag)
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -641,6 +734,105 @@ int lfx_pose_graph_prior_info(const lfx_pose_graph * g, lfx_pose_graph_prior_inf
   return LFX_OK;
 }
 
+int lfx_pose_graph_reserve_marginals(lfx_ctx * c, lfx_pose_graph * g)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (g->marg_reserved) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph's covariances are reserved already");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const size_t N = g->cfg.max_nodes, K = lfx::kPgPairs;
+  DevBuf<double> ginv, tblk, cov, cross;
+  DevBuf<uint32_t> pairs, status;
+  const uint64_t bytes = (uint64_t)(3u * 36u * N + 36u * K) * sizeof(double) + (uint64_t)(2u * K + 1u) * sizeof(uint32_t);
+  if (ginv.alloc(36u * N) != hipSuccess || tblk.alloc(36u * N) != hipSuccess || cov.alloc(36u * N) != hipSuccess ||
+    cross.alloc(36u * K) != hipSuccess || pairs.alloc(2u * K) != hipSuccess || status.alloc(1u) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the covariances' " + std::to_string(bytes) + " bytes");     // (the six free themselves)
+  }
+  g->ginv = std::move(ginv); g->tblk = std::move(tblk); g->cov = std::move(cov); g->cross = std::move(cross);
+  g->pairs = std::move(pairs); g->mstatus = std::move(status);
+  g->marg_reserved = true;
+  g->marg_current = false;
+  g->device_bytes += bytes;
+  return LFX_OK;
+}
+
+int lfx_pose_graph_marginals(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, uint32_t count, double * cov_out, int32_t * code, void * stream)
+{
+  if (!c || !g || !code || (count && !cov_out)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  int rc = check_marginals(c, g);
+  if (rc != LFX_OK) {return rc;}
+  if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = ensure_marginals(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  *code = g->marg_code;
+  if (g->marg_code != LFX_POSE_GRAPH_CONVERGED || count == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipMemcpyAsync(cov_out, g->cov.p + 36u * (size_t)first, sizeof(double) * 36u * count, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  return LFX_OK;
+}
+
+int lfx_pose_graph_joint_covariances(lfx_ctx * c, lfx_pose_graph * g, const uint32_t * pairs, uint32_t n, double * out, int32_t * code, void * stream)
+{
+  if (!c || !g || !code || (n && (!pairs || !out))) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  int rc = check_marginals(c, g);
+  if (rc != LFX_OK) {return rc;}
+  for (uint32_t p = 0; p < n; p++) {                  // every pair is checked before anything is queued or written
+    const uint32_t i = pairs[2u * p], j = pairs[2u * p + 1u];
+    const std::string which = "pair " + std::to_string(p) + " of the call: ";
+    if (i >= g->n_nodes || j >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "an id that is not a node of the graph");}
+    if (i == j) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "i == j");}
+  }
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = ensure_marginals(c, g, st);
+  if (rc != LFX_OK) {return rc;}
+  *code = g->marg_code;
+  if (g->marg_code != LFX_POSE_GRAPH_CONVERGED || n == 0u) {return LFX_OK;}
+  rc = g->tail.settle(c);                             // (the staging vectors below are the graph's)
+  if (rc != LFX_OK) {return rc;}
+  lfx::PgArgs a = args_of(g);
+  a.status = g->mstatus.p;
+  const lfx::PgMargArgs m = marg_args_of(g);
+  g->stage_cov.resize((size_t)36 * g->n_nodes);
+  LFX_HIP(c, hipMemcpyAsync(g->stage_cov.data(), g->cov.p, sizeof(double) * g->stage_cov.size(), hipMemcpyDeviceToHost, st));
+  g->stage_pairs.resize(2u * (size_t)lfx::kPgPairs);
+  g->stage_cross.resize(36u * (size_t)lfx::kPgPairs);
+  for (uint32_t p0 = 0; p0 < n; p0 += lfx::kPgPairs) {
+    const uint32_t np = std::min<uint32_t>(lfx::kPgPairs, n - p0);
+    for (uint32_t p = 0; p < np; p++) {
+      const uint32_t i = pairs[2u * (p0 + p)], j = pairs[2u * (p0 + p) + 1u];
+      g->stage_pairs[2u * p] = std::min(i, j); g->stage_pairs[2u * p + 1u] = std::max(i, j);
+    }
+    LFX_HIP(c, hipMemcpyAsync(g->pairs.p, g->stage_pairs.data(), sizeof(uint32_t) * 2u * np, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(lfx::pose_graph_joint_kernel, dim3(np), dim3(lfx::kPgWave), 0, st, a, m, np);
+    LFX_HIP(c, hipGetLastError());
+    LFX_HIP(c, hipMemcpyAsync(g->stage_cross.data(), g->cross.p, sizeof(double) * 36u * np, hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipStreamSynchronize(st));
+    for (uint32_t p = 0; p < np; p++) {
+      const uint32_t i = pairs[2u * (p0 + p)], j = pairs[2u * (p0 + p) + 1u];
+      const double * x = g->stage_cross.data() + 36u * (size_t)p;      // Sigma(min, max)
+      const double * di = g->stage_cov.data() + 36u * (size_t)i, * dj = g->stage_cov.data() + 36u * (size_t)j;
+      double * o = out + 144u * (size_t)(p0 + p);
+      for (int r = 0; r < 6; r++) {
+        for (int q = 0; q < 6; q++) {
+          const double ij = i < j ? x[6 * r + q] : x[6 * q + r];       // Sigma_ij(r, q)
+          o[12 * r + q] = di[6 * r + q];
+          o[12 * r + 6 + q] = ij;
+          o[12 * (6 + q) + r] = ij;
+          o[12 * (6 + r) + 6 + q] = dj[6 * r + q];
+        }
+      }
+    }
+  }
+  return LFX_OK;
+}
+
 #ifdef LFX_TEST_HOOKS
 // Test infrastructure (the test-hooks build only): the graph linearised where it stands -- per edge r [E][6] (may be NULL),
 // per node the gradient [N][6], chi^2 -- and lfx_pose_graph_edge_chi2 opened for those values.
@@ -666,6 +858,8 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
   for (uint32_t e = 0; r_out && e < g->n_edges; e++) {std::memcpy(r_out + 6u * (size_t)e, lin.data() + (size_t)lfx::kPgLin * e, sizeof(double) * 6u);}
   *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
   g->linearised = true;
+  g->marg_current = false;
+  g->fixed_stale = false;
   return g->tail.done(c, st);
 }
 
@@ -693,6 +887,8 @@ int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double 
   for (uint32_t p = 0; r_out && p < g->n_priors; p++) {std::memcpy(r_out + 6u * (size_t)p, lin.data() + (size_t)lfx::kPgPlin * p, sizeof(double) * 6u);}
   *chi2_out = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p)->chi2;
   g->linearised = true;
+  g->marg_current = false;
+  g->fixed_stale = false;
   return g->tail.done(c, st);
 }
 #endif

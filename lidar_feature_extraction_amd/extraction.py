@@ -1384,6 +1384,20 @@ def edge_information(pose_j, report_information):
     return out.reshape(6, 6)
 
 
+def relative_covariance(pose_i, pose_j, joint):
+    """lfx_pose_graph_relative_covariance: the covariance [6][6] of the residual of an edge (i, j, Z = T_i^-1 T_j) at the current
+    poses, from the pair's [12][12] block of PoseGraph.joint_covariances.  Its inverse gates a loop candidate.  Host only."""
+    pi = np.ascontiguousarray(pose_i, np.float64).reshape(12)
+    pj = np.ascontiguousarray(pose_j, np.float64).reshape(12)
+    s = np.ascontiguousarray(joint, np.float64).reshape(144)
+    out = np.zeros(36)
+    rc = B.load().lfx_pose_graph_relative_covariance(C.c_void_p(pi.ctypes.data), C.c_void_p(pj.ctypes.data), C.c_void_p(s.ctypes.data),
+                                                     C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "lfx_pose_graph_relative_covariance")
+    return out.reshape(6, 6)
+
+
 def pose_graph_edges(i, j, z, information, flags=0):
     """Edges as the records lfx_pose_graph_add_edges takes (B.POSE_GRAPH_EDGE_DTYPE): i, j [n], z [n][3][4] or [n][12],
     information [n][6][6], flags one value or [n]."""
@@ -1524,6 +1538,38 @@ class PoseGraph(_Handle):
         self._check(self._L.lfx_pose_graph_prior_chi2(self._fx._ctx, self.handle, int(first), count, C.c_void_p(rho.ctypes.data if count else None),
                                                       C.c_void_p(w.ctypes.data if count else None), C.c_void_p(int(stream))))
         return rho, w
+
+    def reserve_marginals(self):
+        """lfx_pose_graph_reserve_marginals: room for the covariances; once."""
+        self._check(self._L.lfx_pose_graph_reserve_marginals(self._fx._ctx, self.handle))
+
+    def marginals(self, first=0, count=None, stream=0, out=None, return_code=False):
+        """lfx_pose_graph_marginals: Sigma_kk of nodes first .. first + count - 1 as [count][6][6] float64, over the increments
+        (a, b) of include/lfx.h.  A matrix that is not positive definite raises B.LfxError unless return_code, which returns
+        (array, code) with the array (`out`, where given) untouched."""
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), 6, 6)) if out is None else out
+        code = C.c_int(0)
+        self._check(self._L.lfx_pose_graph_marginals(self._fx._ctx, self.handle, int(first), count, C.c_void_p(out.ctypes.data if out.size else None),
+                                                     C.byref(code), C.c_void_p(int(stream))))
+        return self._coded(out, code, return_code)
+
+    def joint_covariances(self, pairs, stream=0, out=None, return_code=False):
+        """lfx_pose_graph_joint_covariances: pairs [n][2] -> [n][12][12] float64, [[Sigma_ii, Sigma_ij], [Sigma_ji, Sigma_jj]]."""
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        out = np.zeros((len(p), 12, 12)) if out is None else out
+        code = C.c_int(0)
+        self._check(self._L.lfx_pose_graph_joint_covariances(self._fx._ctx, self.handle, C.c_void_p(p.ctypes.data if len(p) else None), len(p),
+                                                             C.c_void_p(out.ctypes.data if out.size else None), C.byref(code), C.c_void_p(int(stream))))
+        return self._coded(out, code, return_code)
+
+    @staticmethod
+    def _coded(out, code, return_code):
+        if return_code:
+            return out, int(code.value)
+        if code.value != B.POSE_GRAPH_CONVERGED:
+            raise B.LfxError(B.ERR_INVALID_ARGUMENT, "H + lambda I is not positive definite")
+        return out
 
     def prior_info(self):
         i = B.PoseGraphPriorInfo()

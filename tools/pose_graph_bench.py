@@ -2,7 +2,7 @@
 and per kernel (lfx_kernel_times: HIP events around every launch, profiling on), one JSON line per size.
 
     python tools/pose_graph_bench.py [--sizes 1000x10,10000x100,10000x512] [--runs 3] [--out FILE]
-                                     [--priors P [--pose [--anchored]]]
+                                     [--priors P [--pose [--anchored]]] [--marginals]
 
 The graph: radius 20 m, chained odometry with noise 0.002 rad / 0.01 m, the start its composition, loop closures from the first
 lap to the second.  Every run starts from the same chained poses (set_poses), so the iterations are the same each time.
@@ -11,7 +11,10 @@ share_chain_factor: the sequential block factorisation's part of the kernels' ti
 with --pose, P robust pose fixes instead (0.01 rad, 0.05 m).  --anchored (with --pose): the same fixes as the graph had to
 take them before priors existed -- an extra fixed node at the identity first, every id shifted by one, every fix an edge
 from that node: P - 1 more loop edges.  (A position fix has no anchored form: its Omega = blkdiag(0, Omega_t) is singular,
-and a loop edge's information must have a Cholesky factor.)"""
+and a loop edge's information must have a Cholesky factor.)
+--marginals: beside every timed optimise, the covariances that follow it (wall clock): marginals_first_ms, the first
+lfx_pose_graph_marginals call, which does the whole graph's work and copies every block; marginals_again_ms, the same call
+once more (a copy); joint_64_ms, 64 pairs half a trajectory apart (i, i + N / 2), the longest products there are."""
 import argparse
 import json
 import os
@@ -91,6 +94,7 @@ def main():
     ap.add_argument("--priors", type=int, default=0)
     ap.add_argument("--pose", action="store_true")
     ap.add_argument("--anchored", action="store_true")
+    ap.add_argument("--marginals", action="store_true")
     a = ap.parse_args()
     if a.anchored and not (a.priors and a.pose):
         ap.error("--anchored needs --priors and --pose")
@@ -124,7 +128,14 @@ def main():
             if a.priors:
                 pg.reserve_priors(len(nodes))
                 pg.add_priors(priors)
+        if a.marginals:
+            pg.reserve_marginals()
+            base = (np.arange(64) * (n // 2)) // 64
+            pairs = np.stack([base, base + n // 2], axis=1).astype(np.uint32)
         res = pg.optimize()                         # (warm: the kernels' first launches)
+        if a.marginals:
+            pg.marginals()
+            pg.joint_covariances(pairs)
         err = lambda p: float(np.linalg.norm(p[:, :, 3] - truth[:, :, 3], axis=1).max())     # noqa: E731
         line = dict(nodes=n, loop_edges=res["n_loop"], priors=pg.prior_info()["n_priors"], anchored=bool(a.anchored), code=res["code"], iterations=res["iterations"], chi2_initial=res["chi2_initial"],
                     chi2_final=res["chi2_final"], worst_error_before_m=err(start), worst_error_after_m=err(pg.poses()),
@@ -135,6 +146,12 @@ def main():
             t0 = time.perf_counter()
             pg.optimize()
             line["call_ms"].append(round(1e3 * (time.perf_counter() - t0), 3))
+            if a.marginals:
+                for key, call in (("marginals_first_ms", pg.marginals), ("marginals_again_ms", pg.marginals),
+                                  ("joint_64_ms", lambda: pg.joint_covariances(pairs))):
+                    t0 = time.perf_counter()
+                    call()
+                    line.setdefault(key, []).append(round(1e3 * (time.perf_counter() - t0), 3))
         for _ in range(a.runs):
             pg.set_poses(start)
             fx._L.lfx_set_profiling(fx._ctx, 1)
