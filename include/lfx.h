@@ -560,7 +560,8 @@ typedef struct lfx_align_report {
   double eigenvalues[6];    /* of H, ascending */
   double eigenvectors[36];  /* row k: the unit eigenvector of eigenvalues[k]; sign: its largest-magnitude component > 0 */
   double covariance[36];    /* sigma2 * sum_k v_k v_k^T / max(eigenvalues[k], floor),  floor = 1e-9 * eigenvalues[5]: finite,
-                               and LARGE along a direction the scan does not constrain */
+                               and LARGE along a direction the scan does not constrain.  "Finite" holds where sigma2 is:
+                               where sigma2 is NaN every entry is NaN, valid stays 1 and every other field is as defined */
   double sigma2;            /* sum_i w_i e_i / (sum_i w_i dim_i - 6): weighted residual variance; dim_i = 3 for an edge
                                residual and 1 for a surface one; NaN where the denominator is <= 0 */
   double min_eigenvalue_d;  /* smallest eigenvalue of the 7 x 7 D = sum_i J_i^T J_i: what IsDegenerate compares with 0.1 */

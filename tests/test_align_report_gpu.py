@@ -7,7 +7,8 @@ Bounds (none of them from what the device gives): counts equal; the scalar sums 
 Frobenius norm -- both sides see the same rows, what is left is the order of ~10^4 additions (n * 2^-53 ~ 1e-12) and fused
 against unfused products, while a real fault (a wrong weight, a row left out) shows in the third digit; eigenvalues to
 1e-12 * the largest against numpy on the device's own H (the Jacobi stop is 2^-50 ~ 1e-15); the covariance to
-1e3 * 2^-53 * cond(H) * |C|."""
+1e3 * 2^-53 * cond(H) * |C|; and beside these, bit for bit, eigenvalues, eigenvectors, covariance and rank against the float64
+restatement of the device's algorithm (tests/align_report_reference.py; the report's edges: tests/test_align_report_edges_gpu.py)."""
 import ctypes as C
 import os
 import subprocess
@@ -15,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.align_report_reference import mismatches
 from tests.report_restatement import FLOOR, covariance_from, restate
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +123,9 @@ def _check(rep, want, what, inliers=True):
     for k in range(6):
         assert vec[k][np.argmax(np.abs(vec[k]))] > 0, (what, k)
     assert figures["covariance / bound"] <= 1.0, (what, figures)
+    # and, stricter: eigenvalues, eigenvectors, covariance and rank are the bytes of the float64 restatement of the device's
+    # algorithm on the record's own information and sigma2 (tests/align_report_reference.py)
+    assert not mismatches(rep), (what, mismatches(rep))
     assert rep["covariance"].tobytes() == np.ascontiguousarray(rep["covariance"].T).tobytes(), what
     assert rep["information"].tobytes() == np.ascontiguousarray(rep["information"].T).tobytes(), what
     assert rep["rank"] == int((lam > FLOOR * lam[5]).sum()) == rank_np, what
