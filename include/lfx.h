@@ -1399,7 +1399,7 @@ int lfx_pose_graph_relative_covariance(const double pose_i[12], const double pos
  * Keyframe ids are 0, 1, 2 .. in order of addition; a caller that adds graph nodes in step has id == node id.  An empty cloud
  * is a keyframe with count 0.  lfx_keyframes_create allocates everything on the device (the records at max_points[kind], the
  * tables, the submap's workspace and a scratch of min(2^20, max(max_points)) records for lfx_keyframes_save); no later call
- * allocates device memory (pinned host blocks grow with the largest call).
+ * allocates device memory (pinned host blocks grow with the largest call) but lfx_keyframes_reserve_flags, once.
  * ORDER: every call is ordered behind the store's earlier calls, whichever streams they used (one event, waited for on the
  * call's stream and recorded behind the call).  The caller keeps alive, until `stream` has passed the call: the device
  * clouds given to lfx_keyframes_add, the pose array given to lfx_keyframes_follow, and d_out of lfx_keyframes_build (which
@@ -1602,6 +1602,64 @@ int lfx_keyframes_build_masked(lfx_ctx *ctx, const lfx_keyframes *keyframes, int
                                const uint8_t *d_flags, float *d_out, uint64_t capacity_points, uint64_t *d_begin_out,
                                uint64_t *n_out, void *stream);
 
+/* --- flags kept in the store: the masked submap and the masked save --------------------------------------------------------- */
+/* One byte per record and kind that BELONGS to the store, so that lfx_keyframes_submap_masked, lfx_keyframes_save_masked and a
+ * loop closer (lfx_loop_closer_set_masked) leave the flagged records out without a second store.  A NON-ZERO byte leaves the
+ * record out: lfx_keyframes_build_masked's rule.  The bytes are addressed by the store's record index of the kind, exactly as
+ * lfx_visibility_run and lfx_keyframes_build_masked address d_flags, so both take the pointers lfx_keyframes_flags returns:
+ *   lfx_visibility_run(.., d_flags = the two pointers, ..) writes the store's flags in place;
+ *   lfx_keyframes_build_masked(.., d_flags = the kind's pointer, ..) builds under them.
+ * Both already order themselves behind the store's earlier calls through the store's event and record it behind themselves,
+ * so a masked call queued after them, on whichever stream, sees what they wrote.
+ * RESERVE, as lfx_pose_graph_reserve_priors / _reserve_marginals: one call after lfx_keyframes_create, before or after
+ * keyframes were added, allocates max_points[kind] bytes per kind, zeroed, and two 8-byte words per keyframe of max_keyframes
+ * for the masked submap; no later call allocates device memory.  Idempotent.  LFX_ERR_OUT_OF_MEMORY leaves the store as it
+ * was, without flags.  A store that never reserves is untouched: every other call is as it was, byte for byte and launch
+ * for launch.
+ * CONTRACT: the reserve zeroes everything; bytes at or past n_points[kind] are the store's and stay zero --
+ * lfx_keyframes_set_flags, _clear_flags and lfx_visibility_run write inside records only, and a caller that writes through
+ * lfx_keyframes_flags keeps to that.  Before the reserve, lfx_keyframes_flags, _set_flags, _clear_flags, _submap_masked and
+ * _save_masked are LFX_ERR_INVALID_ARGUMENT with nothing queued. */
+typedef struct lfx_keyframes_flags_info_t {
+  int32_t reserved;          /* 1: lfx_keyframes_reserve_flags has run */
+  uint32_t pad;
+  uint64_t device_bytes;     /* what the reserve allocated on the device (not part of lfx_keyframes_info_t.device_bytes) */
+  uint64_t n_flagged[2];     /* records of the store with a non-zero byte, counted on the device */
+} lfx_keyframes_flags_info_t;
+int lfx_keyframes_reserve_flags(lfx_ctx *ctx, lfx_keyframes *keyframes, void *stream);
+/* The two device addresses ([0] edge, [1] surface), valid until the store is destroyed; the contents are current behind
+ * `stream` once the store's earlier calls have passed (the call queues that wait), as lfx_keyframes_view's are. */
+int lfx_keyframes_flags(lfx_ctx *ctx, lfx_keyframes *keyframes, uint8_t *d_flags[2], void *stream);
+/* The flag bytes of keyframes [first, first + count) of `kind` copied device to device from d_src, which is addressed by the
+ * store's record index as above: only d_src[begin[first] .. begin[first + count]) is read -- for a binder with a detector of
+ * its own, such as segmentation classes.  lfx_keyframes_clear_flags zeroes the same range.  Both are asynchronous and
+ * ordered through the store's event, as every store call is; keyframes without records: LFX_OK, nothing queued (d_src may
+ * be NULL). */
+int lfx_keyframes_set_flags(lfx_ctx *ctx, lfx_keyframes *keyframes, int kind, uint32_t first, uint32_t count, const uint8_t *d_src,
+                            void *stream);
+int lfx_keyframes_clear_flags(lfx_ctx *ctx, lfx_keyframes *keyframes, int kind, uint32_t first, uint32_t count, void *stream);
+/* n_flagged over the store's records: integer sums on the device, one wait.  Without a reserve the record is all zero and
+ * the call is LFX_OK. */
+int lfx_keyframes_flags_info(lfx_ctx *ctx, const lfx_keyframes *keyframes, lfx_keyframes_flags_info_t *info, void *stream);
+/* lfx_keyframes_submap over the store's own flags.  Selection: lfx_keyframes_submap's, unchanged.  A selected keyframe
+ * contributes its KEPT records in record order, each byte for byte what lfx_keyframes_build writes for it.  With kept[k] the
+ * kept records of keyframe k, a selected keyframe is written iff the exclusive sum of kept over the selected keyframes before
+ * it, plus kept[k], is <= capacity_points; nothing behind the first keyframe that does not fit is written.  A selected
+ * keyframe whose records are all flagged is written with 0 records and counts in n_written_keyframes, as an empty keyframe
+ * does.  *result has lfx_keyframes_submap's meanings; n_points counts kept records.  One wait, for *result; nothing selected,
+ * or nothing kept: no scatter launch (d_out may be NULL).  Every refusal is lfx_keyframes_submap's, and before the reserve
+ * LFX_ERR_INVALID_ARGUMENT.  Only integer counts and prefixes decide a record's place (no atomic): the same store, flags,
+ * poses and arguments give the same bytes.  Flags and records are read only of the 1 024-record runs of the window that hold
+ * a record of a selected keyframe: the cost follows the selected records, not the window. */
+int lfx_keyframes_submap_masked(lfx_ctx *ctx, const lfx_keyframes *keyframes, int kind, const double center[3], double radius,
+                                uint32_t first, uint32_t count, float *d_out, uint64_t capacity_points,
+                                lfx_keyframes_submap_result *result, void *stream);
+/* lfx_keyframes_save with the store's flagged records left out: the same file names, lfx_pcd_write and chunking through the
+ * store's scratch (a chunk may begin and end inside a keyframe; one wait per chunk, for its kept count).  Each file holds
+ * exactly what lfx_keyframes_build_masked of the whole store under the store's flags holds; a kind that is empty or whose
+ * records are all flagged writes no file (written[kind] = 0).  Synchronous. */
+int lfx_keyframes_save_masked(lfx_ctx *ctx, const lfx_keyframes *keyframes, const char *dirname, int written[2], void *stream);
+
 /* --- the loop closer: revisits found, verified and closed over a store, an index and a graph ------------------------------ */
 /* What joins the sections above.  No reference counterpart; the model is LIO-SAM's loop-closure thread (Shan et al., IROS 2020)
  * with Scan Context as the detector.  THE CONTRACT: keyframe id == place entry == graph node id -- the caller adds a keyframe to
@@ -1618,7 +1676,8 @@ int lfx_keyframes_build_masked(lfx_ctx *ctx, const lfx_keyframes *keyframes, int
  * VERIFY of query keyframe q against a candidate (c = entry, yaw), c + min_gap <= q:
  *   1. lfx_keyframes_submap of each kind into the closer's buffers (submap_capacity[kind] records): centre = the translation
  *      of keyframe c's current pose, submap_radius, window [max(c - w, 0), min(c + w, q - min_gap) + 1), w =
- *      submap_half_window.  truncated is reported in the closure and is no error.
+ *      submap_half_window.  truncated is reported in the closure and is no error.  (lfx_loop_closer_set_masked(closer, 1):
+ *      lfx_keyframes_submap_masked in its place, and submap[kind] carries kept counts.)
  *   2. lfx_map_create on each submap with map_cell_size; both maps are destroyed before the call returns.  (The maps allocate
  *      as lfx_map_create does today: per call.  Everything else the closer uses on the device is allocated by
  *      lfx_loop_closer_create: the submap buffers, the downsample output, the count words.)
@@ -1703,6 +1762,14 @@ int lfx_loop_closer_create(lfx_ctx *ctx, const lfx_loop_closer_config *config, l
                            lfx_pose_graph *graph, lfx_loop_closer **out);
 void lfx_loop_closer_destroy(lfx_loop_closer *closer);
 int lfx_loop_closer_info(const lfx_loop_closer *closer, lfx_loop_closer_info_t *info);
+/* Verify against clean submaps (lfx_loop_closer_config cannot grow, so the switch is a pair of calls).  0, the default: every
+ * byte as described above.  1: step 1 of VERIFY calls lfx_keyframes_submap_masked where it calls lfx_keyframes_submap, and
+ * nothing else changes -- closure.submap[kind] then carries kept counts.  Setting 1 on a closer whose store has no flags
+ * reserved is LFX_ERR_INVALID_ARGUMENT and the closer stays as it was.  The QUERY keyframe's own clouds are used as stored,
+ * flagged records and all: a mover in one scan is a minority of rows under the robust weights, while a submap stacks up to
+ * 2 submap_half_window + 1 keyframes of trails. */
+int lfx_loop_closer_set_masked(lfx_loop_closer *closer, int masked);
+int lfx_loop_closer_get_masked(const lfx_loop_closer *closer, int *masked);
 /* candidates host [count][n_candidates]; n_eligible host [count], may be NULL. */
 int lfx_loop_closer_detect(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t first, uint32_t count, lfx_place_match *candidates,
                            uint32_t *n_eligible, void *stream);

@@ -1045,6 +1045,45 @@ public:
     Check(lfx_keyframes_save(fx_.handle(), store_, dirname.c_str(), written, stream));
     return {written[0] != 0, written[1] != 0};
   }
+  // Flags kept in the store (lfx.h, the section behind lfx_keyframes_build_masked): one byte per record and kind, non-zero
+  // leaves the record out.  ReserveFlags once, before or after keyframes were added; Flags gives the two device arrays,
+  // addressed by the store's record index -- what Visibility::Run and BuildMasked take as d_flags.
+  void ReserveFlags(void * stream = nullptr) {Check(lfx_keyframes_reserve_flags(fx_.handle(), store_, stream));}
+  std::pair<std::uint8_t *, std::uint8_t *> Flags(void * stream = nullptr)
+  {
+    std::uint8_t * d[2] = {nullptr, nullptr};
+    Check(lfx_keyframes_flags(fx_.handle(), store_, d, stream));
+    return {d[0], d[1]};
+  }
+  // the flag bytes of keyframes [first, first + count) from d_src (device, addressed by the store's record index), or zeroed
+  void SetFlags(Kind kind, std::uint32_t first, std::uint32_t count, const std::uint8_t * d_src, void * stream = nullptr)
+  {
+    Check(lfx_keyframes_set_flags(fx_.handle(), store_, kind, first, count, d_src, stream));
+  }
+  void ClearFlags(Kind kind, std::uint32_t first, std::uint32_t count, void * stream = nullptr)
+  {
+    Check(lfx_keyframes_clear_flags(fx_.handle(), store_, kind, first, count, stream));
+  }
+  lfx_keyframes_flags_info_t FlagsInfo(void * stream = nullptr) const
+  {
+    lfx_keyframes_flags_info_t i;
+    Check(lfx_keyframes_flags_info(fx_.handle(), store_, &i, stream));
+    return i;
+  }
+  // Submap and Save without the records the store's flags leave out; n_points counts kept records
+  lfx_keyframes_submap_result SubmapMasked(Kind kind, const double center[3], double radius, std::uint32_t first, std::uint32_t count,
+    float * d_out, std::uint64_t capacity_points, void * stream = nullptr) const
+  {
+    lfx_keyframes_submap_result r;
+    Check(lfx_keyframes_submap_masked(fx_.handle(), store_, kind, center, radius, first, count, d_out, capacity_points, &r, stream));
+    return r;
+  }
+  std::pair<bool, bool> SaveMasked(const std::string & dirname, void * stream = nullptr) const
+  {
+    int written[2] = {0, 0};
+    Check(lfx_keyframes_save_masked(fx_.handle(), store_, dirname.c_str(), written, stream));
+    return {written[0] != 0, written[1] != 0};
+  }
   lfx_keyframes_info_t Info() const
   {
     lfx_keyframes_info_t i;
@@ -1159,6 +1198,19 @@ public:
     lfx_loop_closer_info_t i;
     lfx_loop_closer_info(closer_, &i);
     return i;
+  }
+  // verify against submaps without the store's flagged records (the store has reserved flags: Keyframes::ReserveFlags); the
+  // query keyframe's own clouds are used as stored
+  void SetMasked(bool masked = true)
+  {
+    const int rc = lfx_loop_closer_set_masked(closer_, masked ? 1 : 0);
+    if (rc != LFX_OK) {throw Error(rc, "SetMasked: the closer's store has no flags reserved");}
+  }
+  bool Masked() const
+  {
+    int m = 0;
+    lfx_loop_closer_get_masked(closer_, &m);
+    return m != 0;
   }
 
 private:

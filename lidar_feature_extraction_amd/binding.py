@@ -268,6 +268,11 @@ class KeyframesSubmapResult(C.Structure):
                 ("last_id", C.c_uint32), ("truncated", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class KeyframesFlagsInfo(C.Structure):
+    """lfx_keyframes_flags_info_t: the flags a store keeps (lfx_keyframes_reserve_flags) and how many are set."""
+    _fields_ = [("reserved", C.c_int32), ("pad", C.c_uint32), ("device_bytes", C.c_uint64), ("n_flagged", C.c_uint64 * 2)]
+
+
 KEYFRAMES_EDGE, KEYFRAMES_SURFACE = 0, 1
 KEYFRAMES_NO_ID = 0xFFFFFFFF
 
@@ -363,7 +368,7 @@ EXPORTS = [
     "lfx_place_db_destroy", "lfx_place_db_add", "lfx_place_db_add_host", "lfx_place_db_size", "lfx_place_db_download",
     "lfx_place_db_query", "lfx_place_db_query_gated",
     "lfx_loop_closer_default_config", "lfx_loop_closer_create", "lfx_loop_closer_destroy", "lfx_loop_closer_info", "lfx_loop_closer_detect",
-    "lfx_loop_closer_verify", "lfx_loop_closer_update",
+    "lfx_loop_closer_verify", "lfx_loop_closer_update", "lfx_loop_closer_set_masked", "lfx_loop_closer_get_masked",
     "lfx_segment_default_config", "lfx_segment_tables", "lfx_segment_batch", "lfx_pack_features_segmented",
     "lfx_pose_graph_default_config", "lfx_pose_graph_create", "lfx_pose_graph_destroy", "lfx_pose_graph_info", "lfx_pose_graph_add_nodes",
     "lfx_pose_graph_set_fixed", "lfx_pose_graph_add_edges", "lfx_pose_graph_optimize", "lfx_pose_graph_poses", "lfx_pose_graph_set_poses",
@@ -374,6 +379,8 @@ EXPORTS = [
     "lfx_keyframes_default_config", "lfx_keyframes_create", "lfx_keyframes_destroy", "lfx_keyframes_info", "lfx_keyframes_view",
     "lfx_keyframes_add", "lfx_keyframes_add_host", "lfx_keyframes_set_poses", "lfx_keyframes_poses", "lfx_keyframes_follow",
     "lfx_keyframes_build", "lfx_keyframes_submap", "lfx_keyframes_save", "lfx_keyframes_build_masked",
+    "lfx_keyframes_reserve_flags", "lfx_keyframes_flags", "lfx_keyframes_set_flags", "lfx_keyframes_clear_flags", "lfx_keyframes_flags_info",
+    "lfx_keyframes_submap_masked", "lfx_keyframes_save_masked",
     "lfx_visibility_default_config", "lfx_visibility_tables", "lfx_visibility_create", "lfx_visibility_destroy", "lfx_visibility_info",
     "lfx_visibility_run",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
@@ -588,6 +595,13 @@ def load(test_hooks=False):
     L.lfx_keyframes_submap.argtypes = [vp, vp, i32, vp, C.c_double, u32, u32, vp, u64, C.POINTER(KeyframesSubmapResult), vp]
     L.lfx_keyframes_save.argtypes = [vp, vp, C.c_char_p, C.POINTER(i32), vp]
     L.lfx_keyframes_build_masked.argtypes = [vp, vp, i32, u32, u32, vp, vp, u64, vp, p64, vp]
+    L.lfx_keyframes_reserve_flags.argtypes = [vp, vp, vp]
+    L.lfx_keyframes_flags.argtypes = [vp, vp, C.POINTER(vp), vp]
+    L.lfx_keyframes_set_flags.argtypes = [vp, vp, i32, u32, u32, vp, vp]
+    L.lfx_keyframes_clear_flags.argtypes = [vp, vp, i32, u32, u32, vp]
+    L.lfx_keyframes_flags_info.argtypes = [vp, vp, C.POINTER(KeyframesFlagsInfo), vp]
+    L.lfx_keyframes_submap_masked.argtypes = L.lfx_keyframes_submap.argtypes
+    L.lfx_keyframes_save_masked.argtypes = L.lfx_keyframes_save.argtypes
     pvc = C.POINTER(VisibilityConfig)
     L.lfx_visibility_default_config.argtypes = [pvc]
     L.lfx_visibility_default_config.restype = None
@@ -605,6 +619,8 @@ def load(test_hooks=False):
     L.lfx_loop_closer_destroy.argtypes = [vp]
     L.lfx_loop_closer_destroy.restype = None
     L.lfx_loop_closer_info.argtypes = [vp, C.POINTER(LoopCloserInfo)]
+    L.lfx_loop_closer_set_masked.argtypes = [vp, i32]
+    L.lfx_loop_closer_get_masked.argtypes = [vp, C.POINTER(i32)]
     L.lfx_loop_closer_detect.argtypes = [vp, vp, u32, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     L.lfx_loop_closer_verify.argtypes = [vp, vp, u32, C.POINTER(PlaceMatch), C.POINTER(LoopClosure), vp]
     L.lfx_loop_closer_update.argtypes = [vp, vp, u32, u32, C.POINTER(LoopClosure), C.POINTER(LoopCloserResult), vp]

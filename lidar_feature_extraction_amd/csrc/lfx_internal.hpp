@@ -638,6 +638,7 @@ struct KeyframesAccess
 {
   int device = 0;
   uint32_t n = 0;
+  bool has_flags = false;               // lfx_keyframes_reserve_flags has run
   const float4 * records[2] = {nullptr, nullptr};
   const uint64_t * d_begin[2] = {nullptr, nullptr};
   const uint64_t * begin[2] = {nullptr, nullptr};

@@ -157,7 +157,9 @@ static_assert(sizeof(KfPlanRecord) == 32, "the plan's record is the header's res
 // e[k] + count[k] <= capacity (the sum only grows: nothing behind the first keyframe that does not fit is written);
 // out_begin[k] = e[k] for a written keyframe, kKfNone otherwise.  Integer sums: the same store gives the same bytes.
 // Every thread has a contiguous share of the window, sums it, the shares' sums are scanned in LDS, and a second pass
-// over the share writes out_begin.
+// over the share writes out_begin.  kKept (the masked submap): the counts are not begin's differences but the kept
+// records per keyframe of the window, and `begin` is that table, indexed from the window's first keyframe.
+template<bool kKept>
 __global__ __launch_bounds__(kKfThreads) void keyframes_plan_kernel(
   const uint8_t * __restrict__ flag, const uint64_t * __restrict__ begin, uint32_t first, uint32_t count, uint64_t capacity,
   uint64_t * __restrict__ out_begin, KfPlanRecord * __restrict__ record)
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_plan_kernel(
   const uint32_t lo = t * share < count ? t * share : count, hi = lo + share < count ? lo + share : count;
   uint64_t sum = 0;
   for (uint32_t k = lo; k < hi; k++) {
-    if (flag[k]) {sum += begin[first + k + 1u] - begin[first + k];}
+    if (flag[k]) {sum += kKept ? begin[k] : begin[first + k + 1u] - begin[first + k];}
   }
   s_sum[t] = sum;
   __syncthreads();
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_plan_kernel(
   for (uint32_t k = lo; k < hi; k++) {
     uint64_t ob = kKfNone;
     if (flag[k]) {
-      const uint64_t c = begin[first + k + 1u] - begin[first + k];
+      const uint64_t c = kKept ? begin[k] : begin[first + k + 1u] - begin[first + k];
       selected++;
       if (e + c <= capacity) {
         ob = e;
@@ -327,6 +329,141 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_mask_begin_kernel(
   uint64_t o = run_begin[b];
   for (uint64_t q = rec_lo + b * kKfRun; q < i; q++) {o += flags[q] == 0u ? 1u : 0u;}
   begin_out[j] = o;
+}
+
+// --- the masked submap: the selected keyframes of a window without their flagged records -------------------------------
+// Over the window's source records [rec_lo, rec_hi) = [begin[first], begin[first + count)) in runs of kKfRun, after
+// keyframes_flag_kernel: the kept records of every run that touches a selected keyframe counted (the other runs count 0 and
+// load no flag); keyframes_mask_scan_kernel turns the counts into G, the kept prefix at every run's first record; per
+// selected keyframe G(begin[k]) and the kept records G(begin[k + 1]) - G(begin[k]); keyframes_plan_kernel<true> over the
+// kept counts; then record i of written keyframe k goes to out_begin[k] + (G(i) - G(begin[k])).  Integer counts and
+// prefixes only, no atomic: the same store, flags, poses and arguments give the same bytes.
+
+// the keyframe that holds record `run` of [begin[k_lo], begin[k_hi]): the last that begins at or before it (it is not empty)
+__device__ inline uint32_t kf_keyframe_of(const uint64_t * __restrict__ begin, uint32_t k_lo, uint32_t k_hi, uint64_t run)
+{
+  uint32_t lo = k_lo, hi = k_hi;
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (begin[mid] <= run) {lo = mid;} else {hi = mid;}
+  }
+  return lo;
+}
+
+// run_count[b] = the kept records of run b where a selected keyframe has records in it (or begins in it), 0 otherwise --
+// and then no flag is loaded.  a.first = a.k_lo: the window, which `selected` is indexed from.
+__global__ __launch_bounds__(kKfThreads) void keyframes_submask_count_kernel(
+  const uint8_t * __restrict__ flags, const uint64_t * __restrict__ begin, const uint8_t * __restrict__ selected,
+  uint64_t * __restrict__ run_count, const KfRange a)
+{
+  __shared__ uint32_t s_wave[kKfThreads / kKfWave];
+  const uint64_t run = a.rec_lo + (uint64_t)blockIdx.x * kKfRun;
+  const uint64_t run_end = run + kKfRun < a.rec_hi ? run + kKfRun : a.rec_hi;
+  bool any = false;
+  for (uint32_t q = kf_keyframe_of(begin, a.k_lo, a.k_hi, run); q < a.k_hi && begin[q] < run_end; q++) {
+    any = any || selected[q - a.first] != 0u;
+  }
+  if (!any) {                                 // (uniform over the workgroup: nobody is left at the barrier)
+    if (threadIdx.x == 0u) {run_count[blockIdx.x] = 0u;}
+    return;
+  }
+  uint32_t before;
+  const uint32_t keep = kf_mask_lane(flags, run + (uint64_t)threadIdx.x * kKfPerLane, run_end, s_wave, before);
+  if (threadIdx.x == kKfThreads - 1u) {run_count[blockIdx.x] = before + __popc(keep);}
+}
+
+// G(i), by one wave: the kept records of the counted runs before record i -- the prefix of its run plus the kept records
+// of the run before it, as keyframes_mask_begin_kernel has it (i == rec_hi on a run boundary reads the total behind the
+// last run).  Lane l counts the records l, l + 64, .. of the run below i, at most 16 of them; the lanes' counts are summed
+// by a butterfly of shuffles, which leaves the sum in every lane (integers: the order does not matter).
+__device__ inline uint64_t kf_kept_before(const uint8_t * __restrict__ flags, const uint64_t * __restrict__ run_begin, uint64_t rec_lo, uint64_t i,
+  uint32_t lane)
+{
+  const uint64_t b = (i - rec_lo) / kKfRun;
+  uint32_t n = 0u;
+  for (uint64_t q = rec_lo + b * kKfRun + lane; q < i; q += kKfWave) {n += flags[q] == 0u ? 1u : 0u;}
+#pragma unroll
+  for (int d = (int)kKfWave / 2; d >= 1; d >>= 1) {n += __shfl_xor(n, d, kKfWave);}
+  return run_begin[b] + n;
+}
+
+// One WAVE per keyframe of the window (four to a workgroup): kept_begin[j] = G(begin[first + j]) and kept[j] = the kept
+// records of keyframe first + j, both 0 for a keyframe that is not selected or is empty -- no flag of such a keyframe's runs
+// is loaded.
+__global__ __launch_bounds__(kKfThreads) void keyframes_submask_kept_kernel(
+  const uint8_t * __restrict__ flags, const uint64_t * __restrict__ begin, const uint8_t * __restrict__ selected,
+  const uint64_t * __restrict__ run_begin, uint32_t first, uint32_t count, uint64_t rec_lo, uint64_t * __restrict__ kept_begin,
+  uint64_t * __restrict__ kept)
+{
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & (kKfWave - 1u);
+  const uint32_t j = blockIdx.x * (kKfThreads / kKfWave) + wave;
+  if (j >= count) {return;}                  // (uniform over the wave, as everything below but the lanes' counts)
+  const uint64_t lo = begin[first + j], hi = begin[first + j + 1u];
+  uint64_t g = 0u, n = 0u;
+  if (selected[j] != 0u && hi > lo) {
+    g = kf_kept_before(flags, run_begin, rec_lo, lo, lane);
+    n = kf_kept_before(flags, run_begin, rec_lo, hi, lane) - g;
+  }
+  if (lane == 0u) {
+    kept_begin[j] = g;
+    kept[j] = n;
+  }
+}
+
+// The kept records of the written keyframes to dst.  Workgroup b has run run0 + b of the count pass; lane t the four
+// consecutive records from 4 t (kf_mask_lane: lane order is record order), so a wave has 256 consecutive records.  A
+// run without a written keyframe returns before it loads a flag or a record.  Where a wave's records lie in one keyframe
+// (found by a walk that is uniform over the wave) its pose, out_begin and kept_begin come through the scalar path;
+// otherwise every lane walks from the wave's keyframe to its own records'.
+__global__ __launch_bounds__(kKfThreads) void keyframes_submask_scatter_kernel(
+  const float4 * __restrict__ src, const uint64_t * __restrict__ begin, const double * __restrict__ poses,
+  const uint8_t * __restrict__ flags, const uint64_t * __restrict__ run_begin, const uint64_t * __restrict__ out_begin,
+  const uint64_t * __restrict__ kept_begin, float4 * __restrict__ dst, uint32_t run0, const KfRange a)
+{
+  __shared__ uint32_t s_wave[kKfThreads / kKfWave];
+  const uint32_t b = run0 + blockIdx.x;
+  const uint64_t run = a.rec_lo + (uint64_t)b * kKfRun;
+  const uint64_t run_end = run + kKfRun < a.rec_hi ? run + kKfRun : a.rec_hi;
+  uint32_t k = kf_keyframe_of(begin, a.k_lo, a.k_hi, run);
+  bool any = false;
+  for (uint32_t q = k; q < a.k_hi && begin[q] < run_end; q++) {
+    any = any || out_begin[q - a.first] != kKfNone;
+  }
+  if (!any) {return;}
+  const uint64_t base = run + (uint64_t)threadIdx.x * kKfPerLane;
+  uint32_t before;
+  const uint32_t keep = kf_mask_lane(flags, base, run_end, s_wave, before);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t iw = run + (uint64_t)wave * (kKfWave * kKfPerLane);          // the wave's first record
+  if (iw >= run_end) {return;}
+  const uint64_t wave_end = iw + kKfWave * kKfPerLane < run_end ? iw + kKfWave * kKfPerLane : run_end;
+  while (begin[k + 1u] <= iw) {k++;}          // (iw < rec_hi <= begin[k_hi]: k stays below k_hi)
+  const uint64_t g = run_begin[b] + before;   // G(base)
+  if (begin[k + 1u] >= wave_end) {
+    const uint64_t ob = out_begin[k - a.first];
+    if (ob == kKfNone || keep == 0u) {return;}
+    double m[12];
+#pragma unroll
+    for (int q = 0; q < 12; q++) {m[q] = poses[12u * (size_t)k + q];}
+    uint64_t o = ob + (g - kept_begin[k - a.first]);
+#pragma unroll
+    for (int j = 0; j < kKfPerLane; j++) {
+      if (keep & (1u << j)) {dst[o++] = pcl_transform_record(m, src[base + (uint32_t)j]);}
+    }
+  } else {
+    if (keep == 0u) {return;}
+    uint32_t l = kf_keyframe_of(begin, k, a.k_hi, base);   // (begin[k] <= iw <= base < run_end)
+    uint32_t n = 0u;                          // the lane's kept records before record j
+#pragma unroll
+    for (int j = 0; j < kKfPerLane; j++) {
+      if (!(keep & (1u << j))) {continue;}
+      const uint64_t i = base + (uint32_t)j;
+      while (begin[l + 1u] <= i) {l++;}       // (i < rec_hi <= begin[k_hi])
+      const uint64_t ob = out_begin[l - a.first];
+      if (ob != kKfNone) {dst[ob + (g + n - kept_begin[l - a.first])] = pcl_transform_record(poses + 12u * (size_t)l, src[i]);}
+      n++;
+    }
+  }
 }
 
 }  // namespace lfx

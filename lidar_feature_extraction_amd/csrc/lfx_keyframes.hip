@@ -31,6 +31,10 @@ struct lfx_keyframes
   DevBuf<lfx::KfPlanRecord> record;
   DevBuf<float4> scratch;                // lfx_keyframes_save: one chunk of a world cloud
   DevBuf<uint64_t> mask_runs;            // lfx_keyframes_build_masked: the kept records per run of kKfRun, then their prefix
+  bool has_flags = false;                // lfx_keyframes_reserve_flags: the next four, allocated there and nowhere else
+  uint64_t flag_bytes = 0;
+  DevBuf<uint8_t> flags[2];              // one byte per record of the kind, addressed as the records are; non-zero: left out
+  DevBuf<uint64_t> kept_begin, kept;     // lfx_keyframes_submap_masked: per keyframe of the window, G(begin[k]) and the kept records
   PinnedBuf readback;                    // the counts and begins an add reads back; the submap's record
   PinnedBuf upload;                      // what goes up (tables, begins, poses, a host keyframe's records): rewritten only
                                          // once the store's last queued call has passed
@@ -165,6 +169,59 @@ int save_kind(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::string 
   return LFX_OK;
 }
 
+int check_flags(lfx_ctx * c, const lfx_keyframes * s)
+{
+  if (!s->has_flags) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the store has no flags: lfx_keyframes_reserve_flags comes first");}
+  return LFX_OK;
+}
+
+// the kept records of the source records [lo, hi) under `flags`, counted per run into mask_runs and scanned there (what
+// keyframes_mask_scatter_kernel places from); the total is copied to *h_total, pinned, behind them.  No wait.
+int launch_mask_count(lfx_ctx * c, const lfx_keyframes * s, const uint8_t * flags, uint64_t lo, uint64_t hi, uint64_t * h_total, hipStream_t st)
+{
+  const uint64_t runs = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
+  if (runs + 1u > s->mask_runs.n) {return fail(c, LFX_ERR_CAPACITY, "too many records for the masked build's table");}
+  hipLaunchKernelGGL(lfx::keyframes_mask_count_kernel, dim3((uint32_t)runs), dim3(lfx::kKfThreads), 0, st, flags, lo, hi, s->mask_runs.p);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::keyframes_mask_scan_kernel, dim3(1), dim3(lfx::kKfThreads), 0, st, s->mask_runs.p, (uint32_t)runs);
+  LFX_HIP(c, hipGetLastError());
+  LFX_HIP(c, hipMemcpyAsync(h_total, s->mask_runs.p + runs, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  return LFX_OK;
+}
+
+// save_kind without the store's flagged records: per chunk of source records the kept ones counted (one wait: where the
+// chunk's records go on the host), placed in the scratch by the masked build's scatter and copied down.  *kept: the file's
+// records; none kept, no file.
+int save_kind_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::string & path, uint64_t * kept, hipStream_t st)
+{
+  const uint64_t total = s->begin[kind][s->n];
+  std::vector<float> host(4u * (size_t)total);
+  uint64_t * h_kept = reinterpret_cast<uint64_t *>(s->readback.p);
+  uint64_t at = 0u;
+  for (uint64_t lo = 0; lo < total; lo += s->chunk) {
+    const uint64_t hi = std::min(total, lo + s->chunk);
+    const int rc = launch_mask_count(c, s, s->flags[kind].p, lo, hi, h_kept, st);
+    if (rc != LFX_OK) {return rc;}
+    LFX_HIP(c, hipStreamSynchronize(st));
+    const uint64_t n = *h_kept;
+    if (n == 0u) {continue;}
+    lfx::KfRange a{};
+    a.rec_lo = lo; a.rec_hi = hi; a.k_lo = 0u; a.k_hi = s->n;
+    hipLaunchKernelGGL(lfx::keyframes_mask_scatter_kernel, dim3((uint32_t)((hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun)), dim3(lfx::kKfThreads), 0, st,
+      s->records[kind].p, s->d_begin[kind].p, s->poses.p, s->flags[kind].p, s->mask_runs.p, s->scratch.p, a);
+    LFX_HIP(c, hipGetLastError());
+    LFX_HIP(c, hipMemcpyAsync(host.data() + 4u * (size_t)at, s->scratch.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+    at += n;
+  }
+  LFX_HIP(c, hipStreamSynchronize(st));
+  *kept = at;
+  if (at == 0u) {return LFX_OK;}
+  char msg[512];
+  const int rc = lfx_pcd_write(path.c_str(), host.data(), at, msg, sizeof(msg));
+  if (rc != LFX_OK) {return fail(c, rc, msg);}
+  return LFX_OK;
+}
+
 }  // namespace
 
 lfx_host::KeyframesAccess lfx_host::keyframes_access(const lfx_keyframes * s)
@@ -172,6 +229,7 @@ lfx_host::KeyframesAccess lfx_host::keyframes_access(const lfx_keyframes * s)
   KeyframesAccess a;
   a.device = s->device;
   a.n = s->n;
+  a.has_flags = s->has_flags;
   for (int kind = 0; kind < 2; kind++) {
     a.records[kind] = s->records[kind].p;
     a.d_begin[kind] = s->d_begin[kind].p;
@@ -496,7 +554,7 @@ int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const d
   hipLaunchKernelGGL(lfx::keyframes_flag_kernel, dim3((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), dim3(lfx::kKfThreads), 0, st, s->poses.p, first,
     count, center[0], center[1], center[2], radius * radius, s->flag.p);
   LFX_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(lfx::keyframes_plan_kernel, dim3(1), dim3(lfx::kKfThreads), 0, st, s->flag.p, s->d_begin[kind].p, first, count, capacity_points,
+  hipLaunchKernelGGL(lfx::keyframes_plan_kernel<false>, dim3(1), dim3(lfx::kKfThreads), 0, st, s->flag.p, s->d_begin[kind].p, first, count, capacity_points,
     s->out_begin.p, s->record.p);
   LFX_HIP(c, hipGetLastError());
   // the call's only wait: the plan's record (the caller needs n_points to hand the cloud on; the launch below its range)
@@ -530,6 +588,184 @@ int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirnam
     rc = save_kind(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), st);
     if (rc != LFX_OK) {return rc;}
     written[kind] = 1;
+  }
+  return LFX_OK;
+}
+
+// --- flags that belong to the store ----------------------------------------------------------------------------------------------
+
+int lfx_keyframes_reserve_flags(lfx_ctx * c, lfx_keyframes * s, void * stream)
+{
+  if (!c || !s) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (s->has_flags) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  DevBuf<uint8_t> flags[2];
+  DevBuf<uint64_t> kept_begin, kept;
+  const size_t K = s->cfg.max_keyframes;
+  const uint64_t bytes = s->cfg.max_points[0] + s->cfg.max_points[1] + 2u * sizeof(uint64_t) * K;
+  if (flags[0].alloc(s->cfg.max_points[0]) != hipSuccess || flags[1].alloc(s->cfg.max_points[1]) != hipSuccess || kept_begin.alloc(K) != hipSuccess ||
+    kept.alloc(K) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's " + std::to_string(bytes) + " bytes of flags");
+  }
+  int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {LFX_HIP(c, hipMemsetAsync(flags[kind].p, 0, s->cfg.max_points[kind], st));}
+  rc = s->tail.done(c, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {s->flags[kind] = std::move(flags[kind]);}
+  s->kept_begin = std::move(kept_begin);
+  s->kept = std::move(kept);
+  s->flag_bytes = bytes;
+  s->has_flags = true;
+  return LFX_OK;
+}
+
+int lfx_keyframes_flags(lfx_ctx * c, lfx_keyframes * s, uint8_t * d_flags[2], void * stream)
+{
+  if (!c || !s || !d_flags) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  const int rc = s->tail.order_behind(c, static_cast<hipStream_t>(stream));
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {d_flags[kind] = s->flags[kind].p;}
+  return LFX_OK;
+}
+
+int lfx_keyframes_set_flags(lfx_ctx * c, lfx_keyframes * s, int kind, uint32_t first, uint32_t count, const uint8_t * d_src, void * stream)
+{
+  if (!c || !s) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
+  if (hi == lo) {return LFX_OK;}
+  if (!d_src) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_src is required");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemcpyAsync(s->flags[kind].p + lo, d_src + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, st));
+  return s->tail.done(c, st);
+}
+
+int lfx_keyframes_clear_flags(lfx_ctx * c, lfx_keyframes * s, int kind, uint32_t first, uint32_t count, void * stream)
+{
+  if (!c || !s) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
+  if (hi == lo) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  LFX_HIP(c, hipMemsetAsync(s->flags[kind].p + lo, 0, (size_t)(hi - lo), st));
+  return s->tail.done(c, st);
+}
+
+int lfx_keyframes_flags_info(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes_flags_info_t * info, void * stream)
+{
+  if (!c || !s || !info) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  *info = lfx_keyframes_flags_info_t{};
+  if (!s->has_flags) {return LFX_OK;}
+  info->reserved = 1;
+  info->device_bytes = s->flag_bytes;
+  const uint64_t total[2] = {s->begin[0][s->n], s->begin[1][s->n]};
+  if (total[0] == 0u && total[1] == 0u) {return LFX_OK;}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  // both kinds' kept records through the masked build's table, one behind the other; the call's only wait
+  uint64_t * h_kept = reinterpret_cast<uint64_t *>(s->readback.p);
+  for (int kind = 0; kind < 2; kind++) {
+    h_kept[kind] = 0u;
+    if (total[kind] == 0u) {continue;}
+    rc = launch_mask_count(c, s, s->flags[kind].p, 0u, total[kind], h_kept + kind, st);
+    if (rc != LFX_OK) {return rc;}
+  }
+  LFX_HIP(c, hipStreamSynchronize(st));
+  for (int kind = 0; kind < 2; kind++) {info->n_flagged[kind] = total[kind] - h_kept[kind];}
+  return s->tail.done(c, st);
+}
+
+int lfx_keyframes_submap_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, const double center[3], double radius, uint32_t first,
+  uint32_t count, float * d_out, uint64_t capacity_points, lfx_keyframes_submap_result * result, void * stream)
+{
+  if (!c || !s || !center || !result) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_kind(c, kind) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!finite_all(center, 3u) || !std::isfinite(radius) || radius < 0.0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the centre must be finite, the radius finite and >= 0");}
+  *result = lfx_keyframes_submap_result{};
+  result->first_id = result->last_id = LFX_KEYFRAMES_NO_ID;
+  if (count == 0u) {return LFX_OK;}
+  const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
+  const uint64_t runs = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
+  if (runs + 1u > s->mask_runs.n) {return fail(c, LFX_ERR_CAPACITY, "too many records for the masked build's table");}
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  const dim3 per_keyframe((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), threads(lfx::kKfThreads);
+  const uint8_t * flags = s->flags[kind].p;
+  lfx::KfRange a{};
+  a.rec_lo = lo; a.rec_hi = hi; a.k_lo = first; a.k_hi = first + count; a.first = first;
+  hipLaunchKernelGGL(lfx::keyframes_flag_kernel, per_keyframe, threads, 0, st, s->poses.p, first, count, center[0], center[1], center[2], radius * radius,
+    s->flag.p);
+  LFX_HIP(c, hipGetLastError());
+  if (runs > 0u) {
+    hipLaunchKernelGGL(lfx::keyframes_submask_count_kernel, dim3((uint32_t)runs), threads, 0, st, flags, s->d_begin[kind].p, s->flag.p, s->mask_runs.p, a);
+    LFX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(lfx::keyframes_mask_scan_kernel, dim3(1), threads, 0, st, s->mask_runs.p, (uint32_t)runs);
+    LFX_HIP(c, hipGetLastError());
+  }
+  // (a window without records has only empty keyframes: the next kernel reads no prefix)
+  const uint32_t waves = lfx::kKfThreads / lfx::kKfWave;                  // (one wave per keyframe)
+  hipLaunchKernelGGL(lfx::keyframes_submask_kept_kernel, dim3((count + waves - 1u) / waves), threads, 0, st, flags, s->d_begin[kind].p, s->flag.p, s->mask_runs.p, first, count, lo,
+    s->kept_begin.p, s->kept.p);
+  LFX_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(lfx::keyframes_plan_kernel<true>, dim3(1), threads, 0, st, s->flag.p, s->kept.p, first, count, capacity_points, s->out_begin.p,
+    s->record.p);
+  LFX_HIP(c, hipGetLastError());
+  // the call's only wait: the plan's record, as lfx_keyframes_submap's
+  lfx::KfPlanRecord * rec = reinterpret_cast<lfx::KfPlanRecord *>(s->readback.p);
+  LFX_HIP(c, hipMemcpyAsync(rec, s->record.p, sizeof(lfx::KfPlanRecord), hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  std::memcpy(result, rec, sizeof(*result));
+  result->reserved = 0u;
+  if (result->n_points > 0u) {
+    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    // the runs of the count pass that hold the written keyframes' records
+    const uint64_t run0 = (s->begin[kind][result->first_id] - lo) / lfx::kKfRun;
+    const uint64_t run1 = (s->begin[kind][result->last_id + 1u] - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
+    hipLaunchKernelGGL(lfx::keyframes_submask_scatter_kernel, dim3((uint32_t)(run1 - run0)), threads, 0, st, s->records[kind].p, s->d_begin[kind].p,
+      s->poses.p, flags, s->mask_runs.p, s->out_begin.p, s->kept_begin.p, reinterpret_cast<float4 *>(d_out), (uint32_t)run0, a);
+    LFX_HIP(c, hipGetLastError());
+  }
+  return s->tail.done(c, st);
+}
+
+int lfx_keyframes_save_masked(lfx_ctx * c, const lfx_keyframes * s, const char * dirname, int written[2], void * stream)
+{
+  if (!c || !s || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_store(c, s) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  written[0] = written[1] = 0;
+  LFX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const std::string dir(dirname);
+  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
+  int rc = s->tail.order_behind(c, st);
+  if (rc != LFX_OK) {return rc;}
+  for (int kind = 0; kind < 2; kind++) {
+    if (s->begin[kind][s->n] == 0u) {continue;}
+    uint64_t kept = 0u;
+    rc = save_kind_masked(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), &kept, st);
+    if (rc != LFX_OK) {return rc;}
+    written[kind] = kept > 0u ? 1 : 0;
   }
   return LFX_OK;
 }

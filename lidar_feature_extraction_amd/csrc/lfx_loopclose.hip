@@ -1,7 +1,8 @@
 // lfx_loopclose.hip -- the loop closer (include/lfx.h, the loop closer section): host orchestration over the public calls of
 // the place index, the keyframe store, the alignment and the pose graph.  No kernel of its own: what it returns are those
-// calls' bytes, so a caller that composes them by hand gets the same.  The one thing it reads past the public boundary is
-// where the index keeps its descriptors (place_db_entries): a detect's queries are the index's own entries.
+// calls' bytes, so a caller that composes them by hand gets the same.  What it reads past the public boundary: where the
+// index keeps its descriptors (place_db_entries: a detect's queries are the index's own entries), and whether the store has
+// reserved flags (keyframes_access: lfx_loop_closer_set_masked has no context to ask through).
 #include "lfx_internal.hpp"
 
 #include <algorithm>
@@ -16,6 +17,7 @@ struct lfx_loop_closer
   lfx_keyframes * keyframes = nullptr;
   lfx_place_db * db = nullptr;
   lfx_pose_graph * graph = nullptr;
+  bool masked = false;                       // lfx_loop_closer_set_masked: the submaps leave the store's flagged records out
   uint64_t ds_capacity = 0;                  // records of `downsampled`
   uint64_t device_bytes = 0;
   DevBuf<float> submap[2];                   // [submap_capacity[kind]][4]
@@ -132,8 +134,8 @@ int verify_one(lfx_ctx * c, lfx_loop_closer * lc, uint32_t q, const lfx_place_ma
   const uint32_t hi = (uint32_t)std::min<uint64_t>((uint64_t)cnd + w, q - cfg.min_gap);
   const double center[3] = {pose_c[3], pose_c[7], pose_c[11]};
   for (int kind = 0; kind < 2; kind++) {
-    rc = lfx_keyframes_submap(c, lc->keyframes, kind, center, cfg.submap_radius, lo, hi + 1u - lo, lc->submap[kind].p, cfg.submap_capacity[kind],
-        &out->submap[kind], st);
+    rc = (lc->masked ? lfx_keyframes_submap_masked : lfx_keyframes_submap)(c, lc->keyframes, kind, center, cfg.submap_radius, lo, hi + 1u - lo,
+        lc->submap[kind].p, cfg.submap_capacity[kind], &out->submap[kind], st);
     if (rc != LFX_OK) {return rc;}
   }
   uint64_t begin[2], count[2];
@@ -298,6 +300,21 @@ int lfx_loop_closer_info(const lfx_loop_closer * lc, lfx_loop_closer_info_t * in
 {
   if (!lc || !info) {return LFX_ERR_INVALID_ARGUMENT;}
   info->device_bytes = lc->device_bytes;
+  return LFX_OK;
+}
+
+int lfx_loop_closer_set_masked(lfx_loop_closer * lc, int masked)
+{
+  if (!lc) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (masked && !keyframes_access(lc->keyframes).has_flags) {return LFX_ERR_INVALID_ARGUMENT;}
+  lc->masked = masked != 0;
+  return LFX_OK;
+}
+
+int lfx_loop_closer_get_masked(const lfx_loop_closer * lc, int * masked)
+{
+  if (!lc || !masked) {return LFX_ERR_INVALID_ARGUMENT;}
+  *masked = lc->masked ? 1 : 0;
   return LFX_OK;
 }
 

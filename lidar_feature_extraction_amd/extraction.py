@@ -1702,7 +1702,7 @@ class Keyframes(_Handle):
                                                 need, C.byref(n), C.c_void_p(int(stream))))
         return out
 
-    def submap(self, kind, center, radius, first=0, count=None, d_out=None, capacity_points=None, stream=0):
+    def submap(self, kind, center, radius, first=0, count=None, d_out=None, capacity_points=None, stream=0, _call="lfx_keyframes_submap"):
         """lfx_keyframes_submap: the keyframes of [first, first + count) within `radius` of `center`, written whole in
         ascending id until capacity_points.  Returns (cloud, result): result the dict of lfx_keyframes_submap_result; cloud a
         torch tensor [n_points, 4] (a view of a new tensor of capacity_points records, default the whole window's) or,
@@ -1717,8 +1717,8 @@ class Keyframes(_Handle):
             out = torch.empty((capacity_points, 4), dtype=torch.float32, device=torch.device("cuda", self._fx.device))
             d_out = out.data_ptr() if capacity_points else 0
         r = B.KeyframesSubmapResult()
-        self._check(self._L.lfx_keyframes_submap(self._fx._ctx, self.handle, kind, C.c_void_p(c.ctypes.data), float(radius), int(first), count,
-                                                 C.c_void_p(int(d_out) or None), int(capacity_points), C.byref(r), C.c_void_p(int(stream))))
+        self._check(getattr(self._L, _call)(self._fx._ctx, self.handle, kind, C.c_void_p(c.ctypes.data), float(radius), int(first), count,
+                                            C.c_void_p(int(d_out) or None), int(capacity_points), C.byref(r), C.c_void_p(int(stream))))
         res = dict(n_selected=int(r.n_selected), n_written_keyframes=int(r.n_written_keyframes), n_points=int(r.n_points),
                    first_id=None if r.first_id == B.KEYFRAMES_NO_ID else int(r.first_id),
                    last_id=None if r.last_id == B.KEYFRAMES_NO_ID else int(r.last_id), truncated=bool(r.truncated))
@@ -1762,6 +1762,59 @@ class Keyframes(_Handle):
         w = (C.c_int32 * 2)(0, 0)
         self._check(self._L.lfx_keyframes_save(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
         return bool(w[0]), bool(w[1])
+
+    # --- flags kept in the store (include/lfx.h, the section behind lfx_keyframes_build_masked) ---
+    def reserve_flags(self, stream=0):
+        """lfx_keyframes_reserve_flags: one byte per record and kind, zeroed, that the masked calls below read.  Idempotent."""
+        self._check(self._L.lfx_keyframes_reserve_flags(self._fx._ctx, self.handle, C.c_void_p(int(stream))))
+
+    def flags(self, stream=0):
+        """lfx_keyframes_flags: (edge, surface) uint8 device tensors OVER the store's memory, max_points[kind] long, addressed
+        by the store's record index of the kind and current behind `stream` -- what Visibility.run(flags=...) and
+        build_masked take.  They are views: they must not outlive the store."""
+        p = (C.c_void_p * 2)()
+        self._check(self._L.lfx_keyframes_flags(self._fx._ctx, self.handle, p, C.c_void_p(int(stream))))
+        return tuple(_device_bytes(p[k], int(self.config.max_points[k]), self._fx.device, self) for k in range(2))
+
+    def set_flags(self, kind, flags, first=0, count=None, stream=0):
+        """lfx_keyframes_set_flags: the flag bytes of keyframes [first, first + count) copied from `flags` (a uint8 device
+        tensor or a device address), which is addressed by the store's record index of `kind`."""
+        count = len(self) - int(first) if count is None else int(count)
+        d_src = flags.data_ptr() if hasattr(flags, "data_ptr") else int(flags)
+        self._check(self._L.lfx_keyframes_set_flags(self._fx._ctx, self.handle, self._kind(kind), int(first), count, C.c_void_p(d_src or None),
+                                                    C.c_void_p(int(stream))))
+
+    def clear_flags(self, kind, first=0, count=None, stream=0):
+        count = len(self) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_keyframes_clear_flags(self._fx._ctx, self.handle, self._kind(kind), int(first), count, C.c_void_p(int(stream))))
+
+    def flags_info(self, stream=0):
+        i = B.KeyframesFlagsInfo()
+        self._check(self._L.lfx_keyframes_flags_info(self._fx._ctx, self.handle, C.byref(i), C.c_void_p(int(stream))))
+        return dict(reserved=bool(i.reserved), device_bytes=int(i.device_bytes), n_flagged=(int(i.n_flagged[0]), int(i.n_flagged[1])))
+
+    def submap_masked(self, kind, center, radius, first=0, count=None, d_out=None, capacity_points=None, stream=0):
+        """lfx_keyframes_submap_masked: Keyframes.submap without the records the store's flags leave out; the same arguments
+        and the same (cloud, result), n_points counting kept records."""
+        return self.submap(kind, center, radius, first, count, d_out, capacity_points, stream, _call="lfx_keyframes_submap_masked")
+
+    def save_masked(self, dirname, stream=0):
+        """lfx_keyframes_save_masked: Keyframes.save without the flagged records; a kind without a kept record writes no file."""
+        w = (C.c_int32 * 2)(0, 0)
+        self._check(self._L.lfx_keyframes_save_masked(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
+        return bool(w[0]), bool(w[1])
+
+
+def _device_bytes(ptr, n, device, owner):
+    """a uint8 torch tensor over n bytes of device memory at `ptr` that the library owns; `owner` is kept alive with it"""
+    import torch
+
+    class _Span:
+        pass
+    span = _Span()
+    span.owner = owner
+    span.__cuda_array_interface__ = dict(shape=(int(n),), typestr="|u1", data=(int(ptr), False), version=2)
+    return torch.as_tensor(span, device=torch.device("cuda", device))
 
 
 class Visibility(_Handle):
@@ -1855,6 +1908,19 @@ class LoopCloser(_Handle):
         i = B.LoopCloserInfo()
         self._check(self._L.lfx_loop_closer_info(self.handle, C.byref(i)))
         return dict(device_bytes=int(i.device_bytes))
+
+    def set_masked(self, masked=True):
+        """lfx_loop_closer_set_masked: verify against submaps without the store's flagged records (the store has reserved
+        flags: Keyframes.reserve_flags).  The query keyframe's own clouds are used as stored."""
+        rc = self._L.lfx_loop_closer_set_masked(self.handle, int(bool(masked)))
+        if rc != 0:
+            raise B.LfxError(rc, "set_masked: the closer's store has no flags reserved")
+
+    @property
+    def masked(self):
+        m = C.c_int32(0)
+        self._check(self._L.lfx_loop_closer_get_masked(self.handle, C.byref(m)))
+        return bool(m.value)
 
     def detect_raw(self, first, count, stream=0):
         """lfx_loop_closer_detect as it returns: (a B.PlaceMatch array [count * n_candidates], n_eligible uint32 [count])."""

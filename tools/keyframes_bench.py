@@ -1,7 +1,9 @@
 """Times of the keyframe store (lfx_keyframes): a store of N keyframes whose per-keyframe counts come from a real extraction of
 `synth` 64 x 1800 scans, built, cut and moved; one JSON line.
 
-    python tools/keyframes_bench.py [--keyframes 10000] [--scans 64] [--runs 3] [--out FILE]
+    python tools/keyframes_bench.py [--keyframes 10000] [--scans 64] [--runs 3] [--out FILE] [--masked]
+
+  --masked     instead of the figures below: submap_masked over the store's own flags beside submap and build_masked (masked())
 
   build        the whole store of a kind to a device buffer: HIP events around the call, and bytes read plus written (32 per
                record) per second beside lfx_box_calibration's copy rate on the same box
@@ -36,6 +38,64 @@ def circle(n, spacing=2.5):
     return T
 
 
+def masked(a, fx, kf, counts, poses, line, wall):
+    """--masked: the store's own flags at shares 0, 0.05 and 0.5 (drawn per record), and per kind
+      w25          a window of 25 ids, all selected: submap_masked beside submap and build_masked of the same keyframes
+      w1000_all    a window of 1 000 ids, all selected
+      w1000_five   the same window with a radius that selects five keyframes in its middle: the runs of 1 024 records without
+                   a selected keyframe are skipped, so the time should follow the five, not the thousand
+    Medians of --runs, wall clock to the stream's end (each call waits once for its result).  `stages` counts what the
+    masked call queues: launches, and the runs of the window, those counted and those the scatter is launched over."""
+    import torch
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = len(poses)
+    kf.reserve_flags(stream)
+    line["flags_device_bytes"] = kf.flags_info(stream)["device_bytes"]
+    mid = n // 4                                                             # (far from the lap's seam and from the second lap)
+    windows = {"w25": (mid - 12, 25, 1e9), "w1000_all": (mid - 500, 1000, 1e9), "w1000_five": (mid - 500, 1000, 5.1)}
+    rng = np.random.default_rng(5)
+
+    def median(call):
+        call()
+        return float(np.median([wall(call)[0] for _ in range(a.runs)]))
+
+    for kind, name in ((0, "edge"), (1, "surface")):
+        begin = np.concatenate([[0], np.cumsum(counts[:, kind])])
+        out = torch.empty((int(begin[-1]), 4), dtype=torch.float32, device=dev)
+        for share in (0.0, 0.05, 0.5):
+            drawn = torch.from_numpy((rng.random(int(begin[-1])) < share).astype(np.uint8)).to(dev)
+            kf.set_flags(kind, drawn, 0, n, stream)
+            d_flags = kf.flags(stream)[kind]
+            for wname, (first, count, radius) in windows.items():
+                first, count = max(first, 0), min(count, n - max(first, 0))
+                center = poses[min(mid, n - 1), :, 3]
+                args = (kind, center, radius, first, count)
+                room = int(begin[first + count] - begin[first])
+                key = "%s_%s_share_%g" % (wname, name, share)
+                res = kf.submap_masked(*args, d_out=out.data_ptr(), capacity_points=room, stream=stream)[1]
+                line[key] = dict(
+                    submap_masked_us=median(lambda: kf.submap_masked(*args, d_out=out.data_ptr(), capacity_points=room, stream=stream)),
+                    submap_us=median(lambda: kf.submap(*args, d_out=out.data_ptr(), capacity_points=room, stream=stream)),
+                    n_selected=res["n_selected"], n_points=res["n_points"], window_records=room)
+                if wname == "w25":
+                    line[key]["build_masked_us"] = median(lambda: kf.build_masked(kind, d_flags, first, count, d_out=out.data_ptr(),
+                                                                                  capacity_points=room, stream=stream))
+                    line[key]["build_us"] = median(lambda: kf.build(kind, first, count, d_out=out.data_ptr(), capacity_points=room, stream=stream))
+                if share == 0.0:
+                    # the stages: flag, count, scan, kept, plan (5 launches), the record's copy and wait, the scatter
+                    sel = np.linalg.norm(poses[first:first + count, :, 3] - center, axis=1) <= radius
+                    run_of = lambda i: (i - begin[first]) // 1024
+                    ids = first + np.nonzero(sel & (counts[first:first + count, kind] > 0))[0]
+                    counted = set()
+                    for k in ids:
+                        counted.update(range(int(run_of(begin[k])), int(run_of(begin[k + 1] - 1)) + 1))
+                    line[key]["stages"] = dict(launches=6 if res["n_points"] else 5, submap_launches=3 if res["n_points"] else 2,
+                                               window_runs=int(-(-room // 1024)), counted_runs=len(counted),
+                                               scatter_runs=int(run_of(begin[ids[-1] + 1] - 1) - run_of(begin[ids[0]]) + 1) if len(ids) else 0)
+        del out
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -43,6 +103,7 @@ def main():
     ap.add_argument("--scans", type=int, default=64)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--masked", action="store_true", help="time submap_masked beside submap and build_masked, and nothing else")
     a = ap.parse_args()
     rings, cols, n, batch = 64, 1800, a.keyframes, a.scans
     dev = torch.device("cuda", 0)
@@ -94,8 +155,10 @@ def main():
     kf.follow(pg, stream=stream)
     line["follow_us"] = [events(lambda: kf.follow(pg, stream=stream)) for _ in range(a.runs)]
     line["copy_gb_s"] = [round(fx.box_calibration(0, stream)[0], 1) for _ in range(a.runs)]
+    if a.masked:
+        masked(a, fx, kf, counts, poses, line, wall)
     view = kf.view(stream)
-    for kind, name in ((0, "edge"), (1, "surface")):
+    for kind, name in (() if a.masked else ((0, "edge"), (1, "surface"))):
         records = int(total[kind])
         out = torch.empty((records, 4), dtype=torch.float32, device=dev)
         kf.build(kind, 0, n, d_out=out.data_ptr(), capacity_points=records, stream=stream)
