@@ -1781,6 +1781,102 @@ int lfx_loop_closer_verify(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t query
 int lfx_loop_closer_update(lfx_ctx *ctx, lfx_loop_closer *closer, uint32_t first, uint32_t count, lfx_loop_closure *closures,
                            lfx_loop_closer_result *result, void *stream);
 
+/* --- the voxel filter: clouds of any size thinned to one centroid per voxel of a world-anchored grid ------------------------ */
+/* What stands between the world clouds above (lfx_keyframes_build .. _submap_masked, lfx_mapper_view, lfx_odometry_view) and a
+ * file or an lfx_map: every place seen N times holds N layers of records, and every system this stack is modelled on thins its
+ * clouds to a voxel grid before they become a target (LIO-SAM, LeGO-LOAM: leaves 0.2 m for edges, 0.4 m for surfaces -- the
+ * rolling map's).  lfx_voxel_downsample is the reference's per-scan Downsample: one workgroup per cloud and a grid relative to the
+ * cloud's own bounds.  This filter works at any size, incrementally, and its output is a pure function of the input SEQUENCE:
+ * the same records in the same order give the same bytes, whatever the device made of the order in between.
+ *
+ * THE MODEL.  leaf > 0; inv = 1.0f / leaf (float).  A record p = (x, y, z, .):
+ *   VOXEL    per axis v = floorf(p * inv), the product in float: the rolling map's voxel coordinate.  The grid is anchored at
+ *            the world origin, so a voxel is the same voxel whatever else is in the cloud and however it is split over calls.
+ *   SKIPPED  x, y or z not finite: counted in n_nonfinite.  Otherwise a |v| that is not below 2^20 on some axis: n_out_of_range.
+ *   ADDS     1 to its voxel's count and, per axis, the signed integer
+ *              q = (int64) rint((((double)p * (double)inv) - (double)v) * 16777216.0)
+ *            -- separate double operations, no contraction, rint to nearest even -- to the voxel's sum S.  Sums are 64-bit
+ *            two's-complement integer adds and nothing else (no floating-point atomic), so they do not depend on the order of
+ *            arrival; |q| < 1.1 * 2^24, so 2^32 records of one voxel cannot overflow.
+ *   RANK     a record's index among all records handed to the filter since the reset, skipped ones included (the host keeps
+ *            the running base).  A voxel keeps the least rank that reached it, an integer minimum.
+ *   CENTROID per axis (float)((((double)v) + ((double)S / (double)n) * 0x1p-24) / (double)inv), n the count; the 4th float is
+ *            1.0f, as lfx_voxel_downsample writes.  A voxel of one record returns it to within leaf * 2^-25 + 1 ulp.
+ *   ORDER    voxels are written in ascending order of their least rank: the order of first appearance.
+ *   COUNTS   d_counts_out[i] = the count of output voxel i, saturated at 2^32 - 1.
+ *   MIN      a voxel with fewer than min_points (>= 1) records is left out (PCL: MinimumPointsNumberPerVoxel).
+ *
+ * THE TABLE.  2^log2_slots entries of 64 bytes (key, least rank, count, three sums: one line), open addressing with linear
+ * probing from the top log2_slots bits of key * 0x9E3779B97F4A7C15 (key: the rolling map's voxel key).  An insert is a compare-
+ * and-swap on the entry's key -- empty or equal: found, otherwise the next entry -- at most 2^log2_slots probes, then the
+ * record is counted in n_table_full; it never waits on another thread.  Which entry a voxel lands in may depend on the race;
+ * nothing observable does.  Size log2_slots for about twice the voxels expected.  An emit marks the surviving voxels' least
+ * ranks in a bitmap over ranks (max_records bits), scans the words' population counts and writes: no sort, no second pass
+ * over the input.  lfx_voxel_filter_create allocates all of it (64 B per entry, 1 B per 4 ranks, a staging buffer of 2^16
+ * records for lfx_voxel_filter_add_host); no later call allocates device memory.  Calls are ordered through one event behind
+ * the filter's last call, whatever streams they were given. */
+typedef struct lfx_voxel_filter lfx_voxel_filter;
+typedef struct lfx_voxel_filter_config {
+  uint32_t log2_slots;    /* 4 .. 30: the table has 2^log2_slots voxel entries */
+  uint32_t reserved;      /* 0 */
+  uint64_t max_records;   /* 1 .. 2^40: ranks a filter can hand out between two resets */
+} lfx_voxel_filter_config;
+typedef struct lfx_voxel_filter_result {
+  uint64_t n_records;       /* ranks handed out since the reset */
+  uint64_t n_accumulated;   /* records that reached a voxel */
+  uint64_t n_nonfinite;     /* skipped: x, y or z not finite */
+  uint64_t n_out_of_range;  /* skipped: a voxel coordinate not below 2^20 in size */
+  uint64_t n_table_full;    /* skipped: no entry left for their voxel */
+  uint64_t n_voxels;        /* occupied entries */
+  uint64_t n_written;       /* voxels written by this emit (count >= min_points) */
+} lfx_voxel_filter_result;
+typedef struct lfx_voxel_filter_info_t {
+  uint64_t slots, max_records;
+  uint64_t n_records;        /* ranks handed out since the reset (the host's count) */
+  uint64_t device_bytes;     /* everything lfx_voxel_filter_create allocated on the device */
+  float leaf;                /* of the last reset; 0 before the first */
+  uint32_t reserved;
+} lfx_voxel_filter_info_t;
+/* All zero: the caller sets every field. */
+void lfx_voxel_filter_default_config(lfx_voxel_filter_config *config);
+/* A config outside the ranges above is LFX_ERR_INVALID_ARGUMENT, a failed allocation LFX_ERR_OUT_OF_MEMORY with nothing left
+ * allocated. */
+int lfx_voxel_filter_create(lfx_ctx *ctx, const lfx_voxel_filter_config *config, lfx_voxel_filter **out);
+void lfx_voxel_filter_destroy(lfx_voxel_filter *filter);
+int lfx_voxel_filter_info(const lfx_voxel_filter *filter, lfx_voxel_filter_info_t *info);
+/* Empties the table and sets the leaf (finite, > 0, 1.0f / leaf finite and > 0); ranks restart at 0.  Asynchronous.  Every
+ * other call below is LFX_ERR_INVALID_ARGUMENT before the first reset. */
+int lfx_voxel_filter_reset(lfx_ctx *ctx, lfx_voxel_filter *filter, float leaf, void *stream);
+/* n_points records of 4 floats on the device (lfx_voxel_filter_add) or on the host (_add_host, which goes up in chunks of 2^16
+ * records through a pinned block and waits for the chunk before); asynchronous, the records are read behind `stream`.  More
+ * records than max_records leaves room for: LFX_ERR_CAPACITY with nothing queued.  n_points 0: LFX_OK, nothing queued. */
+int lfx_voxel_filter_add(lfx_ctx *ctx, lfx_voxel_filter *filter, const float *d_points, uint64_t n_points, void *stream);
+int lfx_voxel_filter_add_host(lfx_ctx *ctx, lfx_voxel_filter *filter, const float *points, uint64_t n_points, void *stream);
+/* The voxels with at least min_points records to d_out (device, capacity_points records of 4 floats) in the order above, their
+ * counts to d_counts_out (device u32, may be NULL).  One wait, for *result.  n_table_full != 0, or n_written > capacity_points:
+ * LFX_ERR_CAPACITY with *result filled and nothing written to d_out -- a silently thinned map is worse than an error.  The
+ * table is not consumed: more adds and another emit are legal, which is how a map grows keyframe by keyframe.  min_points 0
+ * or a missing result is LFX_ERR_INVALID_ARGUMENT before anything is touched; d_out may be NULL where nothing is written. */
+int lfx_voxel_filter_emit(lfx_ctx *ctx, lfx_voxel_filter *filter, uint32_t min_points, float *d_out, uint64_t capacity_points,
+                          uint32_t *d_counts_out, lfx_voxel_filter_result *result, void *stream);
+/* The keyframe store straight into the filter: one launch over the store's SENSOR-frame records of keyframes [first, first +
+ * count) of `kind`, each read once, transformed with lfx_keyframes_build's arithmetic at the store's current poses and
+ * accumulated -- no world cloud is written.  masked != 0 leaves out the records the store's flags leave out (before
+ * lfx_keyframes_reserve_flags: LFX_ERR_INVALID_ARGUMENT).  Every source record of the range takes a rank, flagged or not, and
+ * ranks are monotone in build order: a following emit gives byte for byte what lfx_voxel_filter_add of lfx_keyframes_build's
+ * (masked: lfx_keyframes_build_masked's under the store's flags) output gives.  Asynchronous, ordered behind the store's and
+ * the filter's earlier calls.  Keyframes outside the store, a wrong kind: LFX_ERR_INVALID_ARGUMENT; more records than
+ * max_records leaves room for: LFX_ERR_CAPACITY; nothing queued either way. */
+int lfx_voxel_filter_add_keyframes(lfx_ctx *ctx, lfx_voxel_filter *filter, const lfx_keyframes *keyframes, int kind, uint32_t first,
+                                   uint32_t count, int masked, void *stream);
+/* lfx_keyframes_save through the filter: per kind a reset with leaf[kind], lfx_voxel_filter_add_keyframes over the whole store
+ * (masked as there), an emit with min_points in chunks through the store's scratch, and dirname/edge.pcd, dirname/surface.pcd
+ * through lfx_pcd_write.  A kind that is empty or of which no voxel survives writes no file (written[kind] = 0).  A full
+ * table, or a kind with more records than the filter's max_records: LFX_ERR_CAPACITY.  The filter is left holding the last
+ * kind written.  Synchronous. */
+int lfx_keyframes_save_filtered(lfx_ctx *ctx, const lfx_keyframes *keyframes, lfx_voxel_filter *filter, const float leaf[2],
+                                uint32_t min_points, int masked, const char *dirname, int written[2], void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

@@ -942,6 +942,8 @@ private:
   lfx_pose_graph * graph_ = nullptr;
 };
 
+class VoxelFilter;
+
 // The keyframe store (lfx_keyframes): every keyframe's edge and surface records in the SENSOR frame and one pose per
 // keyframe on the device of `fx`, which must outlive it; world clouds are written from the two at the poses of the moment,
 // so a map follows a PoseGraph: Follow(graph), then Build, Submap or Save.  Keyframe ids count from 0 in order of addition
@@ -1084,6 +1086,11 @@ public:
     Check(lfx_keyframes_save_masked(fx_.handle(), store_, dirname.c_str(), written, stream));
     return {written[0] != 0, written[1] != 0};
   }
+  // Save through a VoxelFilter (defined behind it): per kind one centroid per voxel of its leaf with at least min_points
+  // records, in the order of first appearance; masked: without the records the store's flags leave out.  A kind of which no
+  // voxel survives writes no file.
+  std::pair<bool, bool> SaveFiltered(VoxelFilter & filter, const std::string & dirname, float edge_leaf = 0.2f, float surface_leaf = 0.4f,
+    std::uint32_t min_points = 1, bool masked = false, void * stream = nullptr) const;
   lfx_keyframes_info_t Info() const
   {
     lfx_keyframes_info_t i;
@@ -1100,6 +1107,78 @@ private:
   const FeatureExtraction & fx_;
   lfx_keyframes * store_ = nullptr;
 };
+
+// The voxel filter (lfx_voxel_filter): clouds of any size thinned to one centroid per voxel of a grid anchored at the world
+// origin, on the device of `fx`, which must outlive it.  Reset(leaf), then Add / AddKeyframes as often as wanted, then Emit;
+// the output is a pure function of the sequence of records (the order of first appearance, centroids from integer sums).
+// log2_slots: the table has 2^log2_slots voxel entries -- about twice the voxels expected; max_records: the records between
+// two resets.
+class VoxelFilter
+{
+public:
+  VoxelFilter(const FeatureExtraction & fx, std::uint32_t log2_slots, std::uint64_t max_records)
+  : fx_(fx)
+  {
+    lfx_voxel_filter_config config;
+    lfx_voxel_filter_default_config(&config);
+    config.log2_slots = log2_slots;
+    config.max_records = max_records;
+    Check(lfx_voxel_filter_create(fx.handle(), &config, &filter_));
+  }
+  ~VoxelFilter() {lfx_voxel_filter_destroy(filter_);}
+  VoxelFilter(const VoxelFilter &) = delete;
+  VoxelFilter & operator=(const VoxelFilter &) = delete;
+
+  void Reset(float leaf, void * stream = nullptr) {Check(lfx_voxel_filter_reset(fx_.handle(), filter_, leaf, stream));}
+  // n_points records of 4 floats on the device; read behind `stream`
+  void Add(const float * d_points, std::uint64_t n_points, void * stream = nullptr)
+  {
+    Check(lfx_voxel_filter_add(fx_.handle(), filter_, d_points, n_points, stream));
+  }
+  void AddHost(const std::vector<float> & points, void * stream = nullptr)
+  {
+    Check(lfx_voxel_filter_add_host(fx_.handle(), filter_, points.data(), points.size() / 4u, stream));
+  }
+  // keyframes [first, first + count) of a store at its current poses, straight from its sensor-frame records
+  void AddKeyframes(const Keyframes & keyframes, Keyframes::Kind kind, std::uint32_t first, std::uint32_t count, bool masked = false,
+    void * stream = nullptr)
+  {
+    Check(lfx_voxel_filter_add_keyframes(fx_.handle(), filter_, keyframes.handle(), kind, first, count, masked ? 1 : 0, stream));
+  }
+  // the voxels with at least min_points records to d_out (device, capacity_points records), their counts to d_counts_out
+  // (device, may be null).  Waits once, for the result; a full table or too small a capacity throws with nothing written.
+  lfx_voxel_filter_result Emit(std::uint32_t min_points, float * d_out, std::uint64_t capacity_points, std::uint32_t * d_counts_out = nullptr,
+    void * stream = nullptr)
+  {
+    lfx_voxel_filter_result r;
+    Check(lfx_voxel_filter_emit(fx_.handle(), filter_, min_points, d_out, capacity_points, d_counts_out, &r, stream));
+    return r;
+  }
+  lfx_voxel_filter_info_t Info() const
+  {
+    lfx_voxel_filter_info_t i;
+    lfx_voxel_filter_info(filter_, &i);
+    return i;
+  }
+  lfx_voxel_filter * handle() const {return filter_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_voxel_filter * filter_ = nullptr;
+};
+
+inline std::pair<bool, bool> Keyframes::SaveFiltered(VoxelFilter & filter, const std::string & dirname, float edge_leaf, float surface_leaf,
+  std::uint32_t min_points, bool masked, void * stream) const
+{
+  int written[2] = {0, 0};
+  const float leaf[2] = {edge_leaf, surface_leaf};
+  Check(lfx_keyframes_save_filtered(fx_.handle(), store_, filter.handle(), leaf, min_points, masked ? 1 : 0, dirname.c_str(), written, stream));
+  return {written[0] != 0, written[1] != 0};
+}
 
 // Visibility votes (lfx_visibility): which records of a window of a Keyframes store's keyframes were looked through by the
 // keyframes near them, and the DYNAMIC flag that decides.  None of the defaults is measured on real data.

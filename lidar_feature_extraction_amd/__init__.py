@@ -15,4 +15,5 @@ from .extraction import PoseGraph, pose_graph_config, pose_graph_edges, pose_gra
 from .extraction import Keyframes  # noqa: F401
 from .extraction import LoopCloser, loop_closer_config  # noqa: F401
 from .extraction import Visibility, visibility_config, visibility_tables  # noqa: F401
+from .extraction import VoxelFilter  # noqa: F401
 from .synth import POINT_DTYPE, SENSORS, make_scan, make_batch, make_sequence, make_sweep, make_sweep_trajectory, concat  # noqa: F401

@@ -277,6 +277,21 @@ KEYFRAMES_EDGE, KEYFRAMES_SURFACE = 0, 1
 KEYFRAMES_NO_ID = 0xFFFFFFFF
 
 
+class VoxelFilterConfig(C.Structure):
+    """lfx_voxel_filter_config: 2^log2_slots voxel entries, max_records ranks between two resets."""
+    _fields_ = [("log2_slots", C.c_uint32), ("reserved", C.c_uint32), ("max_records", C.c_uint64)]
+
+
+class VoxelFilterResult(C.Structure):
+    """lfx_voxel_filter_result: what an emit reports about the records since the reset and the voxels it wrote."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_accumulated", "n_nonfinite", "n_out_of_range", "n_table_full", "n_voxels", "n_written")]
+
+
+class VoxelFilterInfo(C.Structure):
+    _fields_ = [("slots", C.c_uint64), ("max_records", C.c_uint64), ("n_records", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("leaf", C.c_float), ("reserved", C.c_uint32)]
+
+
 class VisibilityConfig(C.Structure):
     """lfx_visibility_config: the range images, the pairs that vote and the decision (include/lfx.h, the visibility section)."""
     _fields_ = [("n_rows", C.c_uint32), ("n_columns", C.c_uint32), ("elev_min", C.c_float), ("elev_step", C.c_float),
@@ -383,6 +398,8 @@ EXPORTS = [
     "lfx_keyframes_submap_masked", "lfx_keyframes_save_masked",
     "lfx_visibility_default_config", "lfx_visibility_tables", "lfx_visibility_create", "lfx_visibility_destroy", "lfx_visibility_info",
     "lfx_visibility_run",
+    "lfx_voxel_filter_default_config", "lfx_voxel_filter_create", "lfx_voxel_filter_destroy", "lfx_voxel_filter_info", "lfx_voxel_filter_reset",
+    "lfx_voxel_filter_add", "lfx_voxel_filter_add_host", "lfx_voxel_filter_emit", "lfx_voxel_filter_add_keyframes", "lfx_keyframes_save_filtered",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -611,6 +628,19 @@ def load(test_hooks=False):
     L.lfx_visibility_destroy.restype = None
     L.lfx_visibility_info.argtypes = [vp, C.POINTER(VisibilityInfo)]
     L.lfx_visibility_run.argtypes = [vp, vp, vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(VisibilityResult), vp]
+    pvf = C.POINTER(VoxelFilterConfig)
+    L.lfx_voxel_filter_default_config.argtypes = [pvf]
+    L.lfx_voxel_filter_default_config.restype = None
+    L.lfx_voxel_filter_create.argtypes = [vp, pvf, C.POINTER(vp)]
+    L.lfx_voxel_filter_destroy.argtypes = [vp]
+    L.lfx_voxel_filter_destroy.restype = None
+    L.lfx_voxel_filter_info.argtypes = [vp, C.POINTER(VoxelFilterInfo)]
+    L.lfx_voxel_filter_reset.argtypes = [vp, vp, C.c_float, vp]
+    L.lfx_voxel_filter_add.argtypes = [vp, vp, vp, u64, vp]
+    L.lfx_voxel_filter_add_host.argtypes = [vp, vp, vp, u64, vp]
+    L.lfx_voxel_filter_emit.argtypes = [vp, vp, u32, vp, u64, vp, C.POINTER(VoxelFilterResult), vp]
+    L.lfx_voxel_filter_add_keyframes.argtypes = [vp, vp, vp, i32, u32, u32, i32, vp]
+    L.lfx_keyframes_save_filtered.argtypes = [vp, vp, vp, C.POINTER(C.c_float), u32, i32, C.c_char_p, C.POINTER(i32), vp]
     L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     plc = C.POINTER(LoopCloserConfig)
     L.lfx_loop_closer_default_config.argtypes = [plc]

@@ -632,8 +632,9 @@ void launch_feature_offsets(const uint32_t * edge_counts, const uint32_t * surfa
 // closer's detect queries the index with its own entries (lfx_loopclose.hip)
 const float * place_db_entries(const lfx_place_db * db, uint32_t * cells);
 
-// lfx_keyframes.hip: a store as the visibility votes read it (lfx_visibility.hip) -- the device arrays, the host's mirror of
-// the begin tables ([n + 1] per kind) and the store's tail event, which a reader orders itself behind and records
+// lfx_keyframes.hip: a store as the visibility votes (lfx_visibility.hip) and the voxel filter (lfx_voxelfilter.hip) read it
+// -- the device arrays, the host's mirror of the begin tables ([n + 1] per kind) and the store's tail event, which a reader
+// orders itself behind and records
 struct KeyframesAccess
 {
   int device = 0;
@@ -643,6 +644,9 @@ struct KeyframesAccess
   const uint64_t * d_begin[2] = {nullptr, nullptr};
   const uint64_t * begin[2] = {nullptr, nullptr};
   const double * poses = nullptr;
+  const uint8_t * flags[2] = {nullptr, nullptr};   // the store's own flags (has_flags)
+  float4 * scratch = nullptr;           // lfx_keyframes_save's chunk of a world cloud: `chunk` records
+  uint64_t chunk = 0;
   const Tail * tail = nullptr;
 };
 KeyframesAccess keyframes_access(const lfx_keyframes * s);

@@ -6,17 +6,11 @@
 
 #include <cstdint>
 
+#include "lfx_kernels_kfrange.hpp"
 #include "lfx_kernels_transform.hpp"
 
 namespace lfx
 {
-
-constexpr int kKfThreads = 256;
-constexpr int kKfPerLane = 4;                                    // whole 16-byte records per lane
-constexpr uint32_t kKfRun = kKfThreads * kKfPerLane;             // source records per workgroup of the transform: 1024
-constexpr uint32_t kKfWave = 64;
-constexpr uint64_t kKfNone = ~0ull;                              // out_begin of a keyframe that is not written
-constexpr uint32_t kKfNoId = 0xFFFFFFFFu;
 
 // One cloud of an add: `count` records from record `src` of the caller's points to record `dst` of the store; its
 // workgroups are [first_block, first_block + ceil(count / kKfThreads)).  MapAppendEntry without the pose: 32 bytes.
@@ -44,14 +38,6 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_copy_kernel(
     dst[e->dst + i] = src[(size_t)e->src + i];
   }
 }
-
-// What a transform launch works on: the source records [rec_lo, rec_hi) of one kind, which lie in the keyframes
-// [k_lo, k_hi): begin[k_lo] <= rec_lo and rec_hi <= begin[k_hi].
-struct KfRange
-{
-  uint64_t rec_lo, rec_hi;
-  uint32_t k_lo, k_hi, first, pad;          // first: out_begin is indexed k - first (selected form)
-};
 
 // World records from sensor-frame records at the store's poses.  Workgroup b has the kKfRun consecutive source records
 // from rec_lo + b kKfRun; lane t of it the records t, t + 256, t + 512, t + 768 of the run, each one 16-byte load and one
@@ -338,17 +324,6 @@ __global__ __launch_bounds__(kKfThreads) void keyframes_mask_begin_kernel(
 // selected keyframe G(begin[k]) and the kept records G(begin[k + 1]) - G(begin[k]); keyframes_plan_kernel<true> over the
 // kept counts; then record i of written keyframe k goes to out_begin[k] + (G(i) - G(begin[k])).  Integer counts and
 // prefixes only, no atomic: the same store, flags, poses and arguments give the same bytes.
-
-// the keyframe that holds record `run` of [begin[k_lo], begin[k_hi]): the last that begins at or before it (it is not empty)
-__device__ inline uint32_t kf_keyframe_of(const uint64_t * __restrict__ begin, uint32_t k_lo, uint32_t k_hi, uint64_t run)
-{
-  uint32_t lo = k_lo, hi = k_hi;
-  while (hi - lo > 1u) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (begin[mid] <= run) {lo = mid;} else {hi = mid;}
-  }
-  return lo;
-}
 
 // run_count[b] = the kept records of run b where a selected keyframe has records in it (or begins in it), 0 otherwise --
 // and then no flag is loaded.  a.first = a.k_lo: the window, which `selected` is indexed from.

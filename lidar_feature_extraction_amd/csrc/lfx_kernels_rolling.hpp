@@ -9,13 +9,12 @@
 #include <cstdint>
 
 #include "lfx_kernels_transform.hpp"
+#include "lfx_kernels_voxel.hpp"
 
 namespace lfx
 {
 
-constexpr int kRollThreads = 256;
 constexpr int kRollCells = 4 * kRollThreads;      // cells of a box one workgroup of the extraction looks at
-constexpr float kRollVoxelLimit = 1048576.f;      // |voxel| < 2^20 per axis: 21 bits of the key
 
 // One store as the kernels see it.  o: the window's first voxel per axis; n: its size in voxels.
 struct RollStore
@@ -26,21 +25,6 @@ struct RollStore
   uint32_t n[3];
   float inv;                                      // 1.0f / leaf
 };
-
-// The voxel coordinate of p along one axis: floorf(p * inv); false where that is not finite or not below 2^20 in size
-__host__ __device__ inline bool roll_voxel(float p, float inv, int32_t & v)
-{
-  const float f = floorf(p * inv);
-  if (!(fabsf(f) < kRollVoxelLimit)) {return false;}
-  v = (int32_t)f;
-  return true;
-}
-
-__host__ __device__ inline uint64_t roll_key(int32_t vx, int32_t vy, int32_t vz)
-{
-  return (1ull << 63) | (uint64_t)((uint32_t)vx & 0x1FFFFFu) | ((uint64_t)((uint32_t)vy & 0x1FFFFFu) << 21) |
-         ((uint64_t)((uint32_t)vz & 0x1FFFFFu) << 42);
-}
 
 // v mod n, the non-negative one
 __host__ __device__ inline uint32_t roll_mod(int32_t v, uint32_t n)
@@ -94,20 +78,6 @@ __device__ inline int roll_locate(const RollStore & s, const RollInsertEntry * _
 }
 
 __device__ inline uint64_t roll_stamp(uint32_t epoch, uint32_t rank) {return ((uint64_t)epoch << 32) | (uint64_t)(0xFFFFFFFFu - rank);}
-
-// how many threads of the workgroup say `flag`, into counters[word]: a ballot per wave, one atomic per workgroup
-__device__ inline void roll_count(bool flag, uint32_t * sh, unsigned long long * counter)
-{
-  const uint32_t n = (uint32_t)__popcll(__ballot(flag));
-  if ((threadIdx.x & 63) == 0) {sh[threadIdx.x >> 6] = n;}
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < kRollThreads / 64; w++) {t += sh[w];}
-    if (t) {atomicAdd(counter, (unsigned long long)t);}
-  }
-  __syncthreads();
-}
 
 // Insert, first launch: every record that falls in a voxel of the window that is not live bids for the voxel's slot with
 // (epoch, lowest rank wins).  The epoch is the store's count of insert calls: a bid of this call beats every older stamp,
@@ -163,31 +133,6 @@ __device__ inline bool roll_live(const RollStore & s, const RollBox & box, uint3
   const int32_t vx = box.lo[0] + (int32_t)x, vy = box.lo[1] + (int32_t)y, vz = box.lo[2] + (int32_t)z;
   slot = roll_slot(s, vx, vy, vz);
   return s.keys[slot] == roll_key(vx, vy, vz);
-}
-
-// exclusive scan of one value per thread over the workgroup; sh: 2 * (kRollThreads / 64) + 1 words; the total in `total`
-__device__ inline uint32_t roll_block_scan(uint32_t v, uint32_t * sh, uint32_t & total)
-{
-  constexpr int W = kRollThreads / 64;
-  const int tid = threadIdx.x;
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
-    if ((tid & 63) >= off) {incl += o;}
-  }
-  if ((tid & 63) == 63) {sh[tid >> 6] = incl;}
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t run = 0;
-    for (int w = 0; w < W; w++) {sh[W + w] = run; run += sh[w];}
-    sh[2 * W] = run;
-  }
-  __syncthreads();
-  total = sh[2 * W];
-  const uint32_t r = sh[W + (tid >> 6)] + incl - v;
-  __syncthreads();
-  return r;
 }
 
 // Extraction, first launch: live cells per workgroup (kRollCells cells, 4 consecutive ones per thread)

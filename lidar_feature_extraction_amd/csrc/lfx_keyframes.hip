@@ -234,8 +234,11 @@ lfx_host::KeyframesAccess lfx_host::keyframes_access(const lfx_keyframes * s)
     a.records[kind] = s->records[kind].p;
     a.d_begin[kind] = s->d_begin[kind].p;
     a.begin[kind] = s->begin[kind].data();
+    a.flags[kind] = s->flags[kind].p;
   }
   a.poses = s->poses.p;
+  a.scratch = s->scratch.p;
+  a.chunk = s->chunk;
   a.tail = &s->tail;
   return a;
 }

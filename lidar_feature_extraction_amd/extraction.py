@@ -512,6 +512,11 @@ class FeatureExtraction:
         (edge, surface) records) on this context's device."""
         return Keyframes(self, max_keyframes, max_points)
 
+    def voxel_filter(self, log2_slots, max_records):
+        """lfx_voxel_filter_create: a voxel filter of 2^log2_slots voxel entries (about twice the voxels expected) that can take
+        max_records records between two resets, on this context's device."""
+        return VoxelFilter(self, log2_slots, max_records)
+
     def visibility(self, max_window=1024, max_resident_images=None, config=None, **fields):
         """lfx_visibility_create: visibility votes over windows of up to max_window keyframes, max_resident_images (default:
         all of them) range images on the device at a time; the fields of lfx_visibility_config as keywords."""
@@ -1803,6 +1808,91 @@ class Keyframes(_Handle):
         w = (C.c_int32 * 2)(0, 0)
         self._check(self._L.lfx_keyframes_save_masked(self._fx._ctx, self.handle, os.fsencode(dirname), w, C.c_void_p(int(stream))))
         return bool(w[0]), bool(w[1])
+
+    def save_filtered(self, voxel_filter, dirname, leaf=(0.2, 0.4), min_points=1, masked=False, stream=0):
+        """lfx_keyframes_save_filtered: Keyframes.save through a VoxelFilter -- per kind one centroid per voxel of leaf[kind]
+        (edge, surface) with at least min_points records, in the order of first appearance; masked: without the records the
+        store's flags leave out.  A kind without a surviving voxel writes no file."""
+        w = (C.c_int32 * 2)(0, 0)
+        lf = (C.c_float * 2)(float(leaf[0]), float(leaf[1]))
+        self._check(self._L.lfx_keyframes_save_filtered(self._fx._ctx, self.handle, voxel_filter.handle, lf, int(min_points), int(bool(masked)),
+                                                        os.fsencode(dirname), w, C.c_void_p(int(stream))))
+        return bool(w[0]), bool(w[1])
+
+
+class VoxelFilter(_Handle):
+    """lfx_voxel_filter: clouds of any size thinned to one centroid per voxel of a grid anchored at the world origin
+    (include/lfx.h, the voxel filter section): reset(leaf), add / add_keyframes as often as wanted, emit.  The output is a
+    pure function of the sequence of records: the order of first appearance, centroids from integer sums."""
+
+    _destroy = "lfx_voxel_filter_destroy"
+
+    def __init__(self, fx, log2_slots, max_records):
+        self._fx = fx
+        self._L = fx._L
+        cfg = B.VoxelFilterConfig()
+        self._L.lfx_voxel_filter_default_config(C.byref(cfg))
+        cfg.log2_slots = int(log2_slots)
+        cfg.max_records = int(max_records)
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_voxel_filter_create(fx._ctx, C.byref(cfg), C.byref(h)), self._L)
+        self.handle = h
+        self.config = cfg
+
+    def info(self):
+        i = B.VoxelFilterInfo()
+        self._check(self._L.lfx_voxel_filter_info(self.handle, C.byref(i)))
+        return dict(slots=int(i.slots), max_records=int(i.max_records), n_records=int(i.n_records), leaf=float(i.leaf),
+                    device_bytes=int(i.device_bytes))
+
+    def reset(self, leaf, stream=0):
+        """lfx_voxel_filter_reset: the table emptied, the leaf set, ranks from 0 again."""
+        self._check(self._L.lfx_voxel_filter_reset(self._fx._ctx, self.handle, float(leaf), C.c_void_p(int(stream))))
+
+    def add(self, points, n_points=None, stream=0):
+        """lfx_voxel_filter_add / _add_host: records of 4 floats -- a float32 device tensor [n, 4], a device address with
+        n_points, or a host array [n, 4] (which goes through the host call)."""
+        if hasattr(points, "data_ptr"):
+            n = points.shape[0] if n_points is None else int(n_points)
+            self._check(self._L.lfx_voxel_filter_add(self._fx._ctx, self.handle, C.c_void_p(points.data_ptr() if n else None), n, C.c_void_p(int(stream))))
+        elif isinstance(points, (int, np.integer)):
+            self._check(self._L.lfx_voxel_filter_add(self._fx._ctx, self.handle, C.c_void_p(int(points) or None), int(n_points), C.c_void_p(int(stream))))
+        else:
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+            self._check(self._L.lfx_voxel_filter_add_host(self._fx._ctx, self.handle, C.c_void_p(p.ctypes.data if len(p) else None), len(p),
+                                                          C.c_void_p(int(stream))))
+
+    def add_keyframes(self, keyframes, kind, first=0, count=None, masked=False, stream=0):
+        """lfx_voxel_filter_add_keyframes: keyframes [first, first + count) of a Keyframes store at its current poses, straight
+        from the store's sensor-frame records; masked: without the records the store's flags leave out."""
+        count = len(keyframes) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_voxel_filter_add_keyframes(self._fx._ctx, self.handle, keyframes.handle, Keyframes._kind(kind), int(first), count,
+                                                           int(bool(masked)), C.c_void_p(int(stream))))
+
+    @staticmethod
+    def result(r):
+        return {n: int(getattr(r, n)) for n, _ in B.VoxelFilterResult._fields_}
+
+    def emit_raw(self, min_points, d_out, capacity_points, d_counts_out=0, stream=0):
+        """lfx_voxel_filter_emit into device addresses: (return code, result dict) -- LFX_ERR_CAPACITY comes back with the
+        result filled, so nothing is raised here."""
+        r = B.VoxelFilterResult()
+        rc = self._L.lfx_voxel_filter_emit(self._fx._ctx, self.handle, int(min_points), C.c_void_p(int(d_out) or None), int(capacity_points),
+                                           C.c_void_p(int(d_counts_out) or None), C.byref(r), C.c_void_p(int(stream)))
+        return rc, self.result(r)
+
+    def emit(self, min_points=1, capacity_points=None, counts=False, stream=0):
+        """lfx_voxel_filter_emit: (cloud, result) or (cloud, counts, result) -- cloud a torch tensor [n_written, 4] float32 (a
+        view of a new one of capacity_points records, default the records added), counts its uint32 counts as int32 bits."""
+        import torch
+        dev = torch.device("cuda", self._fx.device)
+        cap = self.info()["n_records"] if capacity_points is None else int(capacity_points)
+        out = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+        cnt = torch.empty(cap, dtype=torch.int32, device=dev) if counts else None
+        rc, res = self.emit_raw(min_points, out.data_ptr() if cap else 0, cap, cnt.data_ptr() if counts and cap else 0, stream)
+        self._check(rc)
+        n = res["n_written"]
+        return (out[:n], cnt[:n], res) if counts else (out[:n], res)
 
 
 def _device_bytes(ptr, n, device, owner):
