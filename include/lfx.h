@@ -1877,6 +1877,165 @@ int lfx_voxel_filter_add_keyframes(lfx_ctx *ctx, lfx_voxel_filter *filter, const
 int lfx_keyframes_save_filtered(lfx_ctx *ctx, const lfx_keyframes *keyframes, lfx_voxel_filter *filter, const float leaf[2],
                                 uint32_t min_points, int masked, const char *dirname, int written[2], void *stream);
 
+/* --- occupancy grids: 2-D free / occupied / unknown maps rendered from scans by ray casting --------------------------------- */
+/* What planners, costmaps, map_server and nav_msgs/OccupancyGrid consume.  No reference counterpart; the model is the ray-cast
+ * grid of Cartographer, slam_toolbox and gmapping, with OctoMap's log-odds.  Two steps: every scan is reduced ONCE, from the
+ * batch's input records (the free-space evidence is there and nowhere else: a store of feature records cannot feed this), to
+ * a virtual 2-D scan of W beams kept on the device with one pose per scan; the grid is then rendered from all kept beams at
+ * the poses of the moment -- after a loop closure the poses follow the graph (lfx_occupancy_follow) and the grid is rendered
+ * again without any scan being read again.  All arithmetic below is in double, unfused, on the floats read through the
+ * context's lfx_layout, unless stated otherwise.  The same beams and poses give the same bytes, whatever the schedule.
+ *
+ * CONFIG.  origin_x, origin_y: the world coordinates of the lower-left corner of cell (0, 0).  z_min, z_max: the obstacle band,
+ *   on the height above the sensor in world axes.  chunk_scans: the scans whose per-scan vote sets the workspace holds at once.
+ *   inv_res = 1.0 / (double)resolution; ceil(max_range * inv_res) must be at most 32768.  The column tables col_cos[m],
+ *   col_sin[m] = cos, sin of -M_PI + ((2.0 * M_PI) * (double)m) / (double)W come from lfx_occupancy_tables (host only, the ONLY
+ *   source: the device is given exactly these values; the same table as the segmentation's).
+ *
+ * REDUCE (lfx_occupancy_add_batch).  Record i of scan s (i: its index in the scan's input) with the scan's pose [R | t]:
+ *   - skipped if x, y or z is not finite, if x*x + y*y == 0, or if r = sqrt((x*x + y*y) + z*z) has r < (double)min_range or
+ *     r >= (double)max_range;
+ *   - levelled direction: dx = (r0*x + r1*y) + r2*z, dy and dz likewise with rows 1 and 2 of R (the translation is not added);
+ *     h2 = dx*dx + dy*dy; skipped if h2 == 0; kf = (float)h2;
+ *   - column m: the segmentation's bisection over col_cos / col_sin with (dx, dy) for (x, y), upper half iff dy >= 0.0;
+ *   - class: with a class array (d_class, addressed by scan_begin[s] + i as lfx_segment_batch writes it) the record passes a mask
+ *     iff bit (1 << class) is set in it (a byte above 3 passes neither); without one it passes both masks;
+ *   - OBSTACLE candidate iff (double)z_min <= dz && dz <= (double)z_max and it passes obstacle_mask: the column's obstacle winner
+ *     has the least kf, equal floats go to the lower i;
+ *   - CLEAR candidate: any other record that passed the gates and passes clear_mask: the column's clear winner has the greatest
+ *     kf, equal floats go to the lower i.
+ *   Beam (s, m), 16 bytes {x, y, z, kind}: with an obstacle winner its sensor-frame x, y, z (copied bit for bit) and
+ *   LFX_OCCUPANCY_HIT; otherwise with a clear winner its x, y, z and LFX_OCCUPANCY_CLEAR; otherwise 0, 0, 0 and
+ *   LFX_OCCUPANCY_NONE.  Two 64-bit integer atomics (a minimum and a maximum over a key of kf's bits and the index) do this in
+ *   one pass over the records; no floating-point atomic is used anywhere.
+ *
+ * RENDER (lfx_occupancy_render).  For scan k at the pose the store holds NOW:
+ *   - origin cell: ox = floor((t_x - origin_x) * inv_res), oy likewise;
+ *   - end cell of each beam of kind != NONE: wx = ((r0*x + r1*y) + r2*z) + t_x (lfx_keyframes_build's sum without the rounding
+ *     to float), ex = floor((wx - origin_x) * inv_res); wy, ey likewise (z enters only through R);
+ *   - a beam one of whose four cell coordinates is not finite or not below 2^30 in size is skipped (n_skipped_beams):
+ *     lfx_occupancy_follow does not inspect poses;
+ *   - the line: integer Bresenham from (ox, oy) to (ex, ey) in 64-bit integers: ax = |ex-ox|, ay = |ey-oy|, sx, sy the signs,
+ *     err = ax - ay; visit (x, y), stop when it is the end cell; e2 = 2*err; if (e2 > -ay) { err -= ay; x += sx; }
+ *     if (e2 < ax) { err += ax; y += sy; } -- max(ax, ay) + 1 cells.  The cells before the end cell are PASSED, the last one is
+ *     the END.  Cells outside the grid are left out silently: the ray is clipped, not dropped;
+ *   - votes, at most one per cell and scan: a cell is OCCUPIED in scan k if it is the END of at least one HIT beam of k;
+ *     otherwise FREE in k if any beam of k passed it or it is the END of a CLEAR beam (a hit beats a miss within a scan: a
+ *     neighbouring beam that grazes a wall cell does not erase the wall).  hits[cell] += 1 for OCCUPIED, misses[cell] += 1 for
+ *     FREE, both uint32.  The counts are a pure function of the beams and poses rendered; they do not depend on chunk_scans,
+ *     the launch shape, the stream or the order of arrival.
+ *   A render accumulates; lfx_occupancy_clear zeroes the counts and the counters.  A full re-render is a clear and a render of
+ *   (0, n_scans).
+ *
+ * EMIT (lfx_occupancy_emit).  Per cell n = hits + misses; n < min_observations: -1.  Otherwise
+ *   L = clamp((int64)hits * w_hit - (int64)misses * w_miss, l_min, l_max) and the cell is lut[L - l_min],
+ *   lut[j] = (int8) rint(100.0 / (1.0 + exp(-(double)(l_min + j) / 100.0))) from lfx_occupancy_emit_table (host only, the ONLY
+ *   source: the device is handed these bytes).  The defaults are OctoMap's log-odds in hundredths.  The output is int8
+ *   [height][width], row 0 the lowest y: nav_msgs/OccupancyGrid.data.
+ *
+ * LIMITS.  The 2-D projection (the height band, the column) happens at the rotation of the pose the scan was added with: a
+ * later rotation correction moves the end points but does not re-decide the band.  One vote per cell and scan, however many
+ * beams cross the cell.  Feature-only stores (the keyframe store, the maps) cannot feed it.
+ *
+ * THE OBJECT.  lfx_occupancy_create allocates everything on the device: [max_scans][W] beams, [max_scans][12] double poses,
+ * the two count arrays, the reduce's [chunk_scans][W][2] keys and the render's two bitmaps per scan of a chunk over a window of
+ * side 2 * ceil(max_range * inv_res) + 5 cells around the scan's origin cell; no later call allocates device memory.  Calls
+ * are ordered through one event behind the object's last call, whatever streams they were given (the keyframe store's rule,
+ * with the same promises about caller-owned buffers).  LFX_ERR_INVALID_ARGUMENT and LFX_ERR_CAPACITY are returned before
+ * anything is queued and leave the object as it was. */
+#define LFX_OCCUPANCY_NONE 0
+#define LFX_OCCUPANCY_HIT 1
+#define LFX_OCCUPANCY_CLEAR 2
+#define LFX_OCCUPANCY_MAX_BEAMS 4096
+#define LFX_OCCUPANCY_MAX_SIDE 16384
+typedef struct lfx_occupancy lfx_occupancy;
+typedef struct lfx_occupancy_config {
+  uint32_t n_beams;             /* W: 1800; even, 4 .. 4096 */
+  uint32_t max_scans;           /* the caller sets it; 1 .. 2^24 */
+  uint32_t width, height;       /* cells; the caller sets them; 1 .. 16384 */
+  float resolution;             /* metres per cell; the caller sets it; finite, > 0 */
+  float min_range, max_range;   /* 1.0, 100.0; 0 < min_range < max_range <= 65536 */
+  float z_min, z_max;           /* -1.5, 0.5; finite, z_min <= z_max */
+  uint32_t chunk_scans;         /* 32; 1 .. 1024 */
+  double origin_x, origin_y;    /* the caller sets them; finite */
+} lfx_occupancy_config;
+typedef struct lfx_occupancy_emit_config {
+  int32_t w_hit, w_miss;        /* 85, 40; 1 .. 1000 */
+  int32_t l_min, l_max;         /* -200, 350; l_min < l_max, l_max - l_min <= 4096 */
+  uint32_t min_observations;    /* 1; >= 1 */
+  uint32_t reserved;            /* 0 */
+} lfx_occupancy_emit_config;
+typedef struct lfx_occupancy_info_t {
+  uint32_t n_scans, max_scans, n_beams, width, height, chunk_scans;
+  uint32_t window;              /* the side of a scan's window in cells */
+  uint32_t reserved;
+  uint64_t device_bytes;        /* everything lfx_occupancy_create allocated on the device */
+} lfx_occupancy_info_t;
+typedef struct lfx_occupancy_view_t {
+  const float *beams;           /* device [n_scans][W][4]: x, y, z and the kind's bits */
+  const double *poses;          /* device [n_scans][12] */
+  const uint32_t *hits, *misses;   /* device [height][width] */
+  uint32_t n_scans, reserved;
+} lfx_occupancy_view_t;
+typedef struct lfx_occupancy_counters_t {   /* of the renders since the last clear */
+  uint64_t n_hit_beams, n_clear_beams;      /* beams cast, by kind */
+  uint64_t n_skipped_beams;                 /* beams left out for a cell coordinate that is not finite or too large */
+  uint64_t n_occupied_votes, n_free_votes;
+  uint64_t n_window_miss;                   /* cells of the grid that fell outside their scan's window (guarded, not written): 0
+                                               for poses whose rotation is one */
+} lfx_occupancy_counters_t;
+void lfx_occupancy_default_config(lfx_occupancy_config *config);
+/* host only, no context: the column tables the kernels are given.  LFX_ERR_INVALID_ARGUMENT: NULL arguments and every field
+ * outside the ranges above. */
+int lfx_occupancy_tables(const lfx_occupancy_config *config, double *col_cos /*[W]*/, double *col_sin /*[W]*/);
+void lfx_occupancy_emit_default_config(lfx_occupancy_emit_config *config);
+/* host only: the emit's look-up table.  LFX_ERR_INVALID_ARGUMENT as above. */
+int lfx_occupancy_emit_table(const lfx_occupancy_emit_config *config, int8_t *lut /*[l_max - l_min + 1]*/);
+/* What lfx_occupancy_tables refuses is LFX_ERR_INVALID_ARGUMENT, a failed allocation LFX_ERR_OUT_OF_MEMORY with nothing left
+ * allocated. */
+int lfx_occupancy_create(lfx_ctx *ctx, const lfx_occupancy_config *config, lfx_occupancy **out);
+void lfx_occupancy_destroy(lfx_occupancy *grid);
+int lfx_occupancy_info(const lfx_occupancy *grid, lfx_occupancy_info_t *info);
+/* The device arrays, current behind `stream`. */
+int lfx_occupancy_view(lfx_ctx *ctx, const lfx_occupancy *grid, lfx_occupancy_view_t *view, void *stream);
+/* The scans of the last device batch (whose INPUT records must still be alive, as for lfx_segment_batch) reduced to beams and
+ * appended as scans *first_id .., each with its pose: poses host [n_scans][12], one per scan of the batch.  select (host
+ * [n_scans], may be NULL) leaves out the scans whose byte is 0 -- keyframes are a subset of scans.  d_class (device, may be
+ * NULL): lfx_segment_batch's classes for this batch, with obstacle_mask / clear_mask over LFX_SEG_*.  Asynchronous; the records
+ * and classes are read behind `stream`: a caller that hands the context its next scans (lfx_extract uploads into the same
+ * buffer on the context's own stream) waits for `stream` first, as after lfx_segment_batch.  LFX_ERR_INVALID_ARGUMENT: NULL ctx, grid or poses, a pose that is not finite, no batch
+ * yet, n_scans not the last batch's, a mask bit above 3; LFX_ERR_CAPACITY: more scans selected than max_scans leaves room
+ * for. */
+int lfx_occupancy_add_batch(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t n_scans, const double *poses, const uint8_t *select,
+                            const uint8_t *d_class, uint32_t obstacle_mask, uint32_t clear_mask, uint32_t *first_id, void *stream);
+/* The keyframe store's calls of these names: host poses in (finite) and out (synchronous), and poses taken device to device
+ * from d_poses[first .. first + count) -- a pose graph's view -- without being inspected. */
+int lfx_occupancy_set_poses(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t first, uint32_t count, const double *poses, void *stream);
+int lfx_occupancy_poses(lfx_ctx *ctx, const lfx_occupancy *grid, uint32_t first, uint32_t count, double *poses_out, void *stream);
+int lfx_occupancy_follow(lfx_ctx *ctx, lfx_occupancy *grid, const double *d_poses, uint32_t first, uint32_t count, void *stream);
+/* Zeroes the counts and the counters; asynchronous. */
+int lfx_occupancy_clear(lfx_ctx *ctx, lfx_occupancy *grid, void *stream);
+/* The votes of scans [first, first + count) at their current poses added to the counts; asynchronous.  Scans outside the
+ * store: LFX_ERR_INVALID_ARGUMENT. */
+int lfx_occupancy_render(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t first, uint32_t count, void *stream);
+/* Synchronous: the counters of the renders since the last clear. */
+int lfx_occupancy_counters(lfx_ctx *ctx, const lfx_occupancy *grid, lfx_occupancy_counters_t *counters, void *stream);
+/* The grid as int8 [height][width] to out: device memory or a pinned block (lfx_host_alloc); asynchronous.  A new emit config's
+ * table goes up from a pinned block of the object's, after a wait for the object's last call; the config of the call before
+ * is not sent again.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, what lfx_occupancy_emit_table refuses. */
+int lfx_occupancy_emit(lfx_ctx *ctx, lfx_occupancy *grid, const lfx_occupancy_emit_config *config, int8_t *out, void *stream);
+/* host only, no context: dirname/map.pgm (P5, maxval 255, the top row the highest y; a cell of -1 is 205, a cell >=
+ * occupied_percent 0, a cell <= free_percent 254, anything else 205) and dirname/map.yaml (image: map.pgm, resolution, origin:
+ * [x, y, 0.0], negate: 0, occupied_thresh and free_thresh as percent / 100; doubles as %.17g) as map_server reads them.
+ * LFX_ERR_INVALID_ARGUMENT: NULL arguments, w or h outside 1 .. 16384, a resolution that is not finite and > 0, an origin that is
+ * not finite, percents that are not 0 <= free_percent < occupied_percent <= 100; LFX_ERR_FILE: a file cannot be written. */
+int lfx_occupancy_write_map(const char *dirname, const int8_t *grid, uint32_t w, uint32_t h, float resolution, double origin_x,
+                            double origin_y, int occupied_percent, int free_percent);
+/* An emit through a pinned block of the object's (host memory, allocated on first use) and lfx_occupancy_write_map of it with the
+ * grid's own resolution and origin.  Synchronous. */
+int lfx_occupancy_save(lfx_ctx *ctx, lfx_occupancy *grid, const lfx_occupancy_emit_config *config, const char *dirname,
+                       int occupied_percent, int free_percent, void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

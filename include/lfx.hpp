@@ -1180,6 +1180,101 @@ inline std::pair<bool, bool> Keyframes::SaveFiltered(VoxelFilter & filter, const
   return {written[0] != 0, written[1] != 0};
 }
 
+// A 2-D occupancy grid (lfx_occupancy) on the device of `fx`, which must outlive it: Add reduces the scans the
+// FeatureExtraction was last given to W beams each and keeps them with one pose per scan; Render casts the kept beams through
+// the grid at the poses of the moment (SetPoses / Follow move them; Clear and Render again after a loop closure: no scan is
+// read again); Emit gives nav_msgs/OccupancyGrid.data and Save the map.pgm / map.yaml pair map_server reads.
+class OccupancyGrid
+{
+public:
+  static lfx_occupancy_config DefaultConfig() {lfx_occupancy_config c; lfx_occupancy_default_config(&c); return c;}
+  static lfx_occupancy_emit_config DefaultEmitConfig() {lfx_occupancy_emit_config c; lfx_occupancy_emit_default_config(&c); return c;}
+  // config: DefaultConfig() with max_scans, width, height, resolution, origin_x and origin_y set
+  OccupancyGrid(const FeatureExtraction & fx, const lfx_occupancy_config & config)
+  : fx_(fx), config_(config)
+  {
+    Check(lfx_occupancy_create(fx.handle(), &config, &grid_));
+  }
+  ~OccupancyGrid() {lfx_occupancy_destroy(grid_);}
+  OccupancyGrid(const OccupancyGrid &) = delete;
+  OccupancyGrid & operator=(const OccupancyGrid &) = delete;
+
+  // every scan the FeatureExtraction was last given, one pose (12 doubles) per scan; d_class: FeatureExtraction::Segment's
+  // classes for them, or null; select: empty, or one byte per scan, 0 leaving the scan out (keyframes are a subset of scans);
+  // the id of the first scan added.  Returns before the records are read: they must stay on the device until `stream` has
+  // passed the call -- FeatureExtraction::BatchStatus(stream) before the next scan is handed to the extraction.
+  std::uint32_t Add(const std::vector<double> & poses, const std::uint8_t * d_class = nullptr, std::uint32_t obstacle_mask = 15u,
+    std::uint32_t clear_mask = 15u, void * stream = nullptr, const std::vector<std::uint8_t> & select = {})
+  {
+    std::uint32_t first = 0;
+    const bool sized = poses.size() % 12u == 0u && (select.empty() || select.size() == poses.size() / 12u);
+    Check(sized ? lfx_occupancy_add_batch(fx_.handle(), grid_, static_cast<std::uint32_t>(poses.size() / 12u), poses.data(),
+      select.empty() ? nullptr : select.data(), d_class, obstacle_mask, clear_mask, &first, stream) : LFX_ERR_INVALID_ARGUMENT);
+    return first;
+  }
+  // every scan that is a node of `graph` takes the node's pose, device to device
+  void Follow(const PoseGraph & graph, void * stream = nullptr)
+  {
+    std::uint32_t n = 0;
+    const double * d_poses = graph.View(&n, stream);
+    const std::uint32_t have = Info().n_scans;
+    Check(lfx_occupancy_follow(fx_.handle(), grid_, d_poses, 0, n < have ? n : have, stream));
+  }
+  void SetPoses(std::uint32_t first, const std::vector<double> & poses, void * stream = nullptr)
+  {
+    Check(poses.size() % 12u == 0u ? lfx_occupancy_set_poses(fx_.handle(), grid_, first, static_cast<std::uint32_t>(poses.size() / 12u), poses.data(), stream) :
+      LFX_ERR_INVALID_ARGUMENT);
+  }
+  std::vector<double> Poses(std::uint32_t first, std::uint32_t count, void * stream = nullptr) const
+  {
+    std::vector<double> out(static_cast<std::size_t>(count) * 12u);
+    Check(lfx_occupancy_poses(fx_.handle(), grid_, first, count, out.data(), stream));
+    return out;
+  }
+  void Clear(void * stream = nullptr) {Check(lfx_occupancy_clear(fx_.handle(), grid_, stream));}
+  void Render(std::uint32_t first, std::uint32_t count, void * stream = nullptr) {Check(lfx_occupancy_render(fx_.handle(), grid_, first, count, stream));}
+  // a full re-render: every kept scan at its current pose
+  void RenderAll(void * stream = nullptr)
+  {
+    Clear(stream);
+    Render(0, Info().n_scans, stream);
+  }
+  lfx_occupancy_counters_t Counters(void * stream = nullptr) const
+  {
+    lfx_occupancy_counters_t r;
+    Check(lfx_occupancy_counters(fx_.handle(), grid_, &r, stream));
+    return r;
+  }
+  // int8 [height][width], row 0 the lowest y, to device memory or a pinned block (FeatureExtraction::PinnedFloats); returns
+  // before it is written: read it behind `stream`
+  void Emit(std::int8_t * out, const lfx_occupancy_emit_config & config = DefaultEmitConfig(), void * stream = nullptr)
+  {
+    Check(lfx_occupancy_emit(fx_.handle(), grid_, &config, out, stream));
+  }
+  void Save(const std::string & dirname, int occupied_percent = 65, int free_percent = 25, const lfx_occupancy_emit_config & config = DefaultEmitConfig(),
+    void * stream = nullptr)
+  {
+    Check(lfx_occupancy_save(fx_.handle(), grid_, &config, dirname.c_str(), occupied_percent, free_percent, stream));
+  }
+  lfx_occupancy_info_t Info() const
+  {
+    lfx_occupancy_info_t i;
+    lfx_occupancy_info(grid_, &i);
+    return i;
+  }
+  const lfx_occupancy_config & Config() const {return config_;}
+  lfx_occupancy * handle() const {return grid_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_occupancy_config config_;
+  lfx_occupancy * grid_ = nullptr;
+};
+
 // Visibility votes (lfx_visibility): which records of a window of a Keyframes store's keyframes were looked through by the
 // keyframes near them, and the DYNAMIC flag that decides.  None of the defaults is measured on real data.
 class Visibility

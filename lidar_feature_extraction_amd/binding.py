@@ -292,6 +292,38 @@ class VoxelFilterInfo(C.Structure):
                 ("leaf", C.c_float), ("reserved", C.c_uint32)]
 
 
+class OccupancyConfig(C.Structure):
+    """lfx_occupancy_config: the virtual scan (W beams), the grid (cells, resolution, origin), the gates and the height band."""
+    _fields_ = [("n_beams", C.c_uint32), ("max_scans", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("resolution", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("chunk_scans", C.c_uint32), ("origin_x", C.c_double), ("origin_y", C.c_double)]
+
+
+class OccupancyEmitConfig(C.Structure):
+    """lfx_occupancy_emit_config: the log-odds weights and clamps (hundredths) and the observations a known cell needs."""
+    _fields_ = [("w_hit", C.c_int32), ("w_miss", C.c_int32), ("l_min", C.c_int32), ("l_max", C.c_int32), ("min_observations", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class OccupancyInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_scans", "max_scans", "n_beams", "width", "height", "chunk_scans", "window", "reserved")] + \
+        [("device_bytes", C.c_uint64)]
+
+
+class OccupancyView(C.Structure):
+    _fields_ = [("beams", C.c_void_p), ("poses", C.c_void_p), ("hits", C.c_void_p), ("misses", C.c_void_p), ("n_scans", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class OccupancyCounters(C.Structure):
+    """lfx_occupancy_counters_t: what the renders since the last clear cast and voted."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_hit_beams", "n_clear_beams", "n_skipped_beams", "n_occupied_votes", "n_free_votes", "n_window_miss")]
+
+
+OCCUPANCY_NONE, OCCUPANCY_HIT, OCCUPANCY_CLEAR = 0, 1, 2
+OCCUPANCY_MAX_BEAMS, OCCUPANCY_MAX_SIDE = 4096, 16384
+
+
 class VisibilityConfig(C.Structure):
     """lfx_visibility_config: the range images, the pairs that vote and the decision (include/lfx.h, the visibility section)."""
     _fields_ = [("n_rows", C.c_uint32), ("n_columns", C.c_uint32), ("elev_min", C.c_float), ("elev_step", C.c_float),
@@ -400,6 +432,10 @@ EXPORTS = [
     "lfx_visibility_run",
     "lfx_voxel_filter_default_config", "lfx_voxel_filter_create", "lfx_voxel_filter_destroy", "lfx_voxel_filter_info", "lfx_voxel_filter_reset",
     "lfx_voxel_filter_add", "lfx_voxel_filter_add_host", "lfx_voxel_filter_emit", "lfx_voxel_filter_add_keyframes", "lfx_keyframes_save_filtered",
+    "lfx_occupancy_default_config", "lfx_occupancy_tables", "lfx_occupancy_emit_default_config", "lfx_occupancy_emit_table",
+    "lfx_occupancy_create", "lfx_occupancy_destroy", "lfx_occupancy_info", "lfx_occupancy_view", "lfx_occupancy_add_batch",
+    "lfx_occupancy_set_poses", "lfx_occupancy_poses", "lfx_occupancy_follow", "lfx_occupancy_clear", "lfx_occupancy_render",
+    "lfx_occupancy_counters", "lfx_occupancy_emit", "lfx_occupancy_write_map", "lfx_occupancy_save",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -641,6 +677,28 @@ def load(test_hooks=False):
     L.lfx_voxel_filter_emit.argtypes = [vp, vp, u32, vp, u64, vp, C.POINTER(VoxelFilterResult), vp]
     L.lfx_voxel_filter_add_keyframes.argtypes = [vp, vp, vp, i32, u32, u32, i32, vp]
     L.lfx_keyframes_save_filtered.argtypes = [vp, vp, vp, C.POINTER(C.c_float), u32, i32, C.c_char_p, C.POINTER(i32), vp]
+    poc, poe = C.POINTER(OccupancyConfig), C.POINTER(OccupancyEmitConfig)
+    L.lfx_occupancy_default_config.argtypes = [poc]
+    L.lfx_occupancy_default_config.restype = None
+    L.lfx_occupancy_tables.argtypes = [poc, vp, vp]
+    L.lfx_occupancy_emit_default_config.argtypes = [poe]
+    L.lfx_occupancy_emit_default_config.restype = None
+    L.lfx_occupancy_emit_table.argtypes = [poe, vp]
+    L.lfx_occupancy_create.argtypes = [vp, poc, C.POINTER(vp)]
+    L.lfx_occupancy_destroy.argtypes = [vp]
+    L.lfx_occupancy_destroy.restype = None
+    L.lfx_occupancy_info.argtypes = [vp, C.POINTER(OccupancyInfo)]
+    L.lfx_occupancy_view.argtypes = [vp, vp, C.POINTER(OccupancyView), vp]
+    L.lfx_occupancy_add_batch.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, C.POINTER(u32), vp]
+    L.lfx_occupancy_set_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_occupancy_poses.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.lfx_occupancy_follow.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.lfx_occupancy_clear.argtypes = [vp, vp, vp]
+    L.lfx_occupancy_render.argtypes = [vp, vp, u32, u32, vp]
+    L.lfx_occupancy_counters.argtypes = [vp, vp, C.POINTER(OccupancyCounters), vp]
+    L.lfx_occupancy_emit.argtypes = [vp, vp, poe, vp, vp]
+    L.lfx_occupancy_write_map.argtypes = [C.c_char_p, vp, u32, u32, C.c_float, C.c_double, C.c_double, i32, i32]
+    L.lfx_occupancy_save.argtypes = [vp, vp, poe, C.c_char_p, i32, i32, vp]
     L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     plc = C.POINTER(LoopCloserConfig)
     L.lfx_loop_closer_default_config.argtypes = [plc]

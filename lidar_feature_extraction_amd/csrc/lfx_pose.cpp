@@ -430,4 +430,64 @@ int lfx_visibility_tables(const lfx_visibility_config * config, double * col_cos
   return LFX_OK;
 }
 
+// Occupancy grids (include/lfx.h, the occupancy section): the defaults, the column tables and the emit's look-up table.
+void lfx_occupancy_default_config(lfx_occupancy_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_occupancy_config{};
+  config->n_beams = 1800;
+  config->min_range = 1.0f;
+  config->max_range = 100.0f;
+  config->z_min = -1.5f;
+  config->z_max = 0.5f;
+  config->chunk_scans = 32;
+}
+
+int lfx_occupancy_tables(const lfx_occupancy_config * config, double * col_cos, double * col_sin)
+{
+  if (!config || !col_cos || !col_sin) {return LFX_ERR_INVALID_ARGUMENT;}
+  const lfx_occupancy_config & c = *config;
+  const uint32_t W = c.n_beams;
+  if (W < 4u || W > LFX_OCCUPANCY_MAX_BEAMS || (W & 1u)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.max_scans < 1u || c.max_scans > (1u << 24)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.width < 1u || c.width > LFX_OCCUPANCY_MAX_SIDE || c.height < 1u || c.height > LFX_OCCUPANCY_MAX_SIDE) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.resolution) || !(c.resolution > 0.0f)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.origin_x) || !std::isfinite(c.origin_y)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!std::isfinite(c.min_range) || !std::isfinite(c.max_range) || !(c.min_range > 0.0f) || !(c.min_range < c.max_range) || !(c.max_range <= 65536.0f)) {
+    return LFX_ERR_INVALID_ARGUMENT;
+  }
+  if (!std::isfinite(c.z_min) || !std::isfinite(c.z_max) || !(c.z_min <= c.z_max)) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.chunk_scans < 1u || c.chunk_scans > 1024u) {return LFX_ERR_INVALID_ARGUMENT;}
+  const double inv_res = 1.0 / (double)c.resolution;
+  if (!(std::ceil((double)c.max_range * inv_res) <= 32768.0)) {return LFX_ERR_INVALID_ARGUMENT;}
+  azimuth_table(W, col_cos, col_sin);
+  return LFX_OK;
+}
+
+void lfx_occupancy_emit_default_config(lfx_occupancy_emit_config * config)
+{
+  if (!config) {return;}
+  *config = lfx_occupancy_emit_config{};
+  config->w_hit = 85;
+  config->w_miss = 40;
+  config->l_min = -200;
+  config->l_max = 350;
+  config->min_observations = 1;
+}
+
+int lfx_occupancy_emit_table(const lfx_occupancy_emit_config * config, int8_t * lut)
+{
+  if (!config || !lut) {return LFX_ERR_INVALID_ARGUMENT;}
+  const lfx_occupancy_emit_config & c = *config;
+  if (c.w_hit < 1 || c.w_hit > 1000 || c.w_miss < 1 || c.w_miss > 1000) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (!(c.l_min < c.l_max) || (int64_t)c.l_max - (int64_t)c.l_min > 4096) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (c.min_observations < 1u || c.reserved != 0u) {return LFX_ERR_INVALID_ARGUMENT;}
+  const int64_t n = (int64_t)c.l_max - (int64_t)c.l_min + 1;
+  for (int64_t j = 0; j < n; j++) {
+    const double l = (double)((int64_t)c.l_min + j);
+    lut[j] = (int8_t)std::rint(100.0 / (1.0 + std::exp(-l / 100.0)));
+  }
+  return LFX_OK;
+}
+
 }  // extern "C"

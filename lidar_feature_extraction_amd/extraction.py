@@ -517,6 +517,12 @@ class FeatureExtraction:
         max_records records between two resets, on this context's device."""
         return VoxelFilter(self, log2_slots, max_records)
 
+    def occupancy_grid(self, width, height, resolution, origin=(0.0, 0.0), max_scans=1024, config=None, **fields):
+        """lfx_occupancy_create: a 2-D occupancy grid of width x height cells of `resolution` metres whose cell (0, 0) has its
+        lower-left corner at `origin`, with room for max_scans scans' beams, on this context's device; the other fields of
+        lfx_occupancy_config as keywords."""
+        return OccupancyGrid(self, width, height, resolution, origin, max_scans, config, **fields)
+
     def visibility(self, max_window=1024, max_resident_images=None, config=None, **fields):
         """lfx_visibility_create: visibility votes over windows of up to max_window keyframes, max_resident_images (default:
         all of them) range images on the device at a time; the fields of lfx_visibility_config as keywords."""
@@ -809,6 +815,51 @@ def visibility_tables(config=None):
     given, and the only source of them.  Host only."""
     cfg = visibility_config(config)
     return _tables("lfx_visibility_tables", "visibility", cfg, int(cfg.n_columns), int(cfg.n_rows) + 1)
+
+
+def occupancy_config(config=None, **fields):
+    """lfx_occupancy_config: the defaults (lfx_occupancy_default_config; the grid's size, resolution, origin and max_scans are
+    the caller's) with the given fields replaced.  config: None, a dict of fields, or a B.OccupancyConfig (copied)."""
+    return _config(B.OccupancyConfig, "lfx_occupancy_default_config", "occupancy", config, fields)
+
+
+def occupancy_tables(config):
+    """lfx_occupancy_tables: (col_cos [W], col_sin [W]), float64 -- the column tables the reduce kernel is given, and the only
+    source of them.  Host only."""
+    cfg = occupancy_config(config)
+    W = int(cfg.n_beams)
+    cs, sn = np.zeros(max(W, 1)), np.zeros(max(W, 1))
+    rc = B.load().lfx_occupancy_tables(C.byref(cfg), _pd(cs), _pd(sn))
+    if rc != 0:
+        raise B.LfxError(rc, "the occupancy config is refused")
+    return cs[:W], sn[:W]
+
+
+def occupancy_emit_config(config=None, **fields):
+    """lfx_occupancy_emit_config: the defaults (OctoMap's log-odds in hundredths) with the given fields replaced."""
+    return _config(B.OccupancyEmitConfig, "lfx_occupancy_emit_default_config", "occupancy emit", config, fields)
+
+
+def occupancy_emit_table(config=None):
+    """lfx_occupancy_emit_table: the int8 look-up table [l_max - l_min + 1] the emit kernel is handed.  Host only."""
+    cfg = occupancy_emit_config(config)
+    lut = np.zeros(4097, np.int8)
+    rc = B.load().lfx_occupancy_emit_table(C.byref(cfg), C.c_void_p(lut.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "the occupancy emit config is refused")
+    return lut[:int(cfg.l_max) - int(cfg.l_min) + 1].copy()
+
+
+def write_occupancy_map(dirname, grid, resolution, origin=(0.0, 0.0), occupied_percent=65, free_percent=25):
+    """lfx_occupancy_write_map: an int8 grid [height][width] (row 0 the lowest y) as dirname/map.pgm and dirname/map.yaml, the
+    pair map_server reads.  Host only."""
+    g = np.ascontiguousarray(grid, np.int8)
+    if g.ndim != 2:
+        raise ValueError("the grid must be [height][width]")
+    rc = B.load().lfx_occupancy_write_map(os.fsencode(str(dirname)), C.c_void_p(g.ctypes.data if g.size else None), g.shape[1], g.shape[0],
+                                          float(resolution), float(origin[0]), float(origin[1]), int(occupied_percent), int(free_percent))
+    if rc != 0:
+        raise B.LfxError(rc, "cannot write map.pgm / map.yaml in %s" % dirname)
 
 
 def _msg_buffer():
@@ -1905,6 +1956,133 @@ def _device_bytes(ptr, n, device, owner):
     span.owner = owner
     span.__cuda_array_interface__ = dict(shape=(int(n),), typestr="|u1", data=(int(ptr), False), version=2)
     return torch.as_tensor(span, device=torch.device("cuda", device))
+
+
+class OccupancyGrid(_Handle):
+    """lfx_occupancy: a 2-D occupancy grid rendered from scans by ray casting (include/lfx.h, the occupancy section).
+    add_batch reduces the last device batch's scans to W beams each and keeps them with one pose per scan; render casts the
+    kept beams through the grid at the poses of the moment (set_poses / follow move them); emit gives
+    nav_msgs/OccupancyGrid.data.  Poses are [3][4] = [R | t] float64; scan ids count from 0 in order of addition."""
+
+    _destroy = "lfx_occupancy_destroy"
+
+    def __init__(self, fx, width, height, resolution, origin=(0.0, 0.0), max_scans=1024, config=None, **fields):
+        self._fx = fx
+        self._L = fx._L
+        cfg = occupancy_config(config, **dict(dict(width=int(width), height=int(height), resolution=float(resolution), origin_x=float(origin[0]),
+                                                   origin_y=float(origin[1]), max_scans=int(max_scans)), **fields))
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_occupancy_create(fx._ctx, C.byref(cfg), C.byref(h)), self._L)
+        self.handle = h
+        self.config = cfg
+
+    def info(self):
+        i = B.OccupancyInfo()
+        self._check(self._L.lfx_occupancy_info(self.handle, C.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in B.OccupancyInfo._fields_ if n != "reserved"}
+
+    def __len__(self):
+        return self.info()["n_scans"]
+
+    def view(self, stream=0):
+        """lfx_occupancy_view: the device addresses of the beams, the poses and the two count arrays, current behind
+        `stream`, and the number of scans."""
+        v = B.OccupancyView()
+        self._check(self._L.lfx_occupancy_view(self._fx._ctx, self.handle, C.byref(v), C.c_void_p(int(stream))))
+        return dict(beams=v.beams or 0, poses=v.poses or 0, hits=v.hits or 0, misses=v.misses or 0, n_scans=int(v.n_scans))
+
+    def add_batch(self, poses, select=None, classes=None, obstacle_mask=15, clear_mask=15, stream=0):
+        """lfx_occupancy_add_batch: the scans of the last device batch (whose records must still be alive), one pose per
+        scan of the batch; select: None or one flag per scan (0: left out); classes: segment()'s uint8 device tensor for this
+        batch, or None, with the two masks over B.SEG_*.  The id of the first scan added.  Asynchronous: the records are read
+        behind `stream`, which the caller waits for before the context is handed its next scans."""
+        pm = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        sel = None if select is None else np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if sel is not None and len(sel) != len(pm):
+            raise ValueError("select must hold one flag per pose")
+        if classes is not None and (classes.numel() < self._fx.batch_points() or classes.element_size() != 1):
+            raise B.LfxError(B.ERR_INVALID_ARGUMENT, "classes must hold one byte for each of the last batch's records")
+        first = C.c_uint32(0)
+        self._check(self._L.lfx_occupancy_add_batch(
+            self._fx._ctx, self.handle, len(pm), C.c_void_p(pm.ctypes.data if len(pm) else None), C.c_void_p(sel.ctypes.data if sel is not None and len(sel) else None),
+            C.c_void_p((classes.data_ptr() or None) if classes is not None else None), int(obstacle_mask), int(clear_mask), C.byref(first),
+            C.c_void_p(int(stream))))
+        return int(first.value)
+
+    def set_poses(self, poses, first=0, stream=0):
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self._check(self._L.lfx_occupancy_set_poses(self._fx._ctx, self.handle, int(first), len(p), C.c_void_p(p.ctypes.data if len(p) else None),
+                                                    C.c_void_p(int(stream))))
+
+    def poses(self, first=0, count=None, stream=0):
+        """lfx_occupancy_poses: scans first .. first + count - 1 as [count][3][4] float64 on the host."""
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), 3, 4))
+        self._check(self._L.lfx_occupancy_poses(self._fx._ctx, self.handle, int(first), count, C.c_void_p(out.ctypes.data if out.size else None),
+                                                C.c_void_p(int(stream))))
+        return out
+
+    def follow(self, graph_or_pointer, first=0, count=None, stream=0):
+        """lfx_occupancy_follow: the poses of scans [first, first + count) taken, device to device, from a PoseGraph (its view
+        on `stream`) or from the device address of a [.][12] float64 array."""
+        if isinstance(graph_or_pointer, PoseGraph):
+            ptr, n = graph_or_pointer.view(stream)
+            count = min(n, len(self)) - int(first) if count is None else int(count)
+        else:
+            ptr = int(graph_or_pointer)
+            count = len(self) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_occupancy_follow(self._fx._ctx, self.handle, C.c_void_p(ptr), int(first), count, C.c_void_p(int(stream))))
+
+    def clear(self, stream=0):
+        self._check(self._L.lfx_occupancy_clear(self._fx._ctx, self.handle, C.c_void_p(int(stream))))
+
+    def render(self, first=0, count=None, stream=0):
+        """lfx_occupancy_render: the votes of scans [first, first + count) at their current poses added to the counts."""
+        count = len(self) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_occupancy_render(self._fx._ctx, self.handle, int(first), count, C.c_void_p(int(stream))))
+
+    def counters(self, stream=0):
+        r = B.OccupancyCounters()
+        self._check(self._L.lfx_occupancy_counters(self._fx._ctx, self.handle, C.byref(r), C.c_void_p(int(stream))))
+        return {n: int(getattr(r, n)) for n, _ in B.OccupancyCounters._fields_}
+
+    def emit(self, config=None, out=None, stream=0, **fields):
+        """lfx_occupancy_emit: the grid as int8 [height][width], row 0 the lowest y.  out: None = a new int8 device tensor is
+        returned, or the address of device memory or of a pinned block (nothing is returned).  Asynchronous on `stream`."""
+        cfg = occupancy_emit_config(config, **fields)
+        made = None
+        if out is None:
+            import torch
+            made = torch.empty((int(self.config.height), int(self.config.width)), dtype=torch.int8, device=torch.device("cuda", self._fx.device))
+            out = made.data_ptr()
+        self._check(self._L.lfx_occupancy_emit(self._fx._ctx, self.handle, C.byref(cfg), C.c_void_p(int(out) or None), C.c_void_p(int(stream))))
+        return made
+
+    def save(self, dirname, config=None, occupied_percent=65, free_percent=25, stream=0, **fields):
+        """lfx_occupancy_save: dirname/map.pgm and dirname/map.yaml of the grid as it stands.  Synchronous."""
+        cfg = occupancy_emit_config(config, **fields)
+        self._check(self._L.lfx_occupancy_save(self._fx._ctx, self.handle, C.byref(cfg), os.fsencode(str(dirname)), int(occupied_percent),
+                                               int(free_percent), C.c_void_p(int(stream))))
+
+    def _array(self, ptr, shape, dtype, stream):
+        import torch
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        if n == 0:
+            return np.zeros(shape, dtype)
+        torch.cuda.synchronize(self._fx.device)              # (a read-back for inspection: everything queued has landed)
+        return _device_bytes(ptr, n, self._fx.device, self).cpu().numpy().view(dtype).reshape(shape).copy()
+
+    def beams(self, stream=0):
+        """The kept beams on the host: (xyz [n_scans][W][3] float32, kind [n_scans][W] uint32)."""
+        v = self.view(stream)
+        raw = self._array(v["beams"], (v["n_scans"], int(self.config.n_beams), 4), np.float32, stream)
+        return np.ascontiguousarray(raw[..., :3]), np.ascontiguousarray(raw[..., 3]).view(np.uint32)
+
+    def counts(self, stream=0):
+        """(hits, misses) on the host, uint32 [height][width] each."""
+        v = self.view(stream)
+        shape = (int(self.config.height), int(self.config.width))
+        return self._array(v["hits"], shape, np.uint32, stream), self._array(v["misses"], shape, np.uint32, stream)
 
 
 class Visibility(_Handle):
