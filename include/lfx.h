@@ -2036,6 +2036,117 @@ int lfx_occupancy_write_map(const char *dirname, const int8_t *grid, uint32_t w,
 int lfx_occupancy_save(lfx_ctx *ctx, lfx_occupancy *grid, const lfx_occupancy_emit_config *config, const char *dirname,
                        int occupied_percent, int free_percent, void *stream);
 
+/* --- distance fields and costmaps of occupancy grids ------------------------------------------------------------------------ */
+/* What a planner plans on: the squared distance from every cell to the nearest obstacle cell (an ESDF once rooted and scaled)
+ * and nav2's inflated costmap.  No reference counterpart; the models are the exact separable Euclidean distance transform
+ * (Felzenszwalb & Huttenlocher 2012) and costmap_2d::InflationLayer.  Integer arithmetic only up to lfx_distance_metres: the
+ * same grid gives the same bytes, whatever the schedule, and the result is exact for every input -- nothing is propagated
+ * approximately.  Ties need no rule: only the distance is reported.
+ *
+ * SOURCE.  G is int8 [H][W] in lfx_occupancy_emit's format: -1 unknown, 0 .. 100 percent, row 0 the lowest y; 1 <= W, H <=
+ *   LFX_OCCUPANCY_MAX_SIDE.  lfx_distance_from_occupancy takes for G exactly the bytes lfx_occupancy_emit would write with the
+ *   same emit config, computed from the counts in passing: no int8 grid exists in between.
+ *
+ * CLASSES, one byte per cell: LFX_DISTANCE_OBSTACLE iff G >= occupied_percent || (G < 0 && unknown_is_obstacle); otherwise
+ *   LFX_DISTANCE_UNKNOWN iff G < 0; otherwise LFX_DISTANCE_FREE.
+ *
+ * FIELDS, uint32 [H][W].  d2[y][x] = the minimum over OBSTACLE cells (x', y') of (x-x')^2 + (y-y')^2; LFX_DISTANCE_FAR if the
+ *   grid has no obstacle.  With a cap R = max_cells > 0 a minimum above R*R is LFX_DISTANCE_FAR (R*R itself is kept).  i2, only
+ *   with `inside`: the same with the cells that are NOT obstacles for sites, so 0 on them; FAR if there is none, FAR above R*R.
+ *   The largest value is 2 * 16383^2.
+ *
+ * METRES (lfx_distance_metres), float [H][W], res = (double)resolution:
+ *   a cell that is no obstacle: d2 FAR: +INFINITY, otherwise (float)(sqrt((double)d2) * res), the square root correctly rounded;
+ *   an obstacle: without `inside` 0.0f; with it i2 FAR: -INFINITY, otherwise -(float)(sqrt((double)i2) * res).
+ *
+ * COST TABLE (lfx_distance_cost_table: host only, the ONLY source of the decay; the device is handed these bytes).
+ *   Rc = (uint32)ceil((double)inflation_radius / (double)resolution), at most LFX_DISTANCE_MAX_COST_CELLS; n = Rc*Rc + 1;
+ *   lut[0] = 254; for k >= 1 with d = sqrt((double)k) * (double)resolution: d <= (double)inscribed_radius: 253;
+ *   d > (double)inflation_radius: 0; otherwise (uint8)(252.0 * exp(-(double)cost_scaling_factor * (d - (double)inscribed_radius)))
+ *   (truncated: nav2's expression).
+ *
+ * COSTMAP (lfx_distance_costmap), uint8 [H][W]: an OBSTACLE is 254; otherwise an UNKNOWN cell with track_unknown is 255;
+ *   otherwise d2 FAR or d2 > Rc*Rc is 0; otherwise lut[d2].  The last transform must have had max_cells 0 or >= Rc.
+ *
+ * THE OBJECT.  lfx_distance_create allocates everything on the device: the classes, one 64-bit obstacle mask per column and
+ * 64 rows with two carries, the uint16 column distances, d2, i2, the largest cost table (1024^2 + 1 bytes) and four stats
+ * words; no later call allocates device memory.  Calls are ordered through one event behind the object's last call, whatever
+ * streams they were given (the keyframe store's rule, with the same promises about caller-owned buffers).
+ * LFX_ERR_INVALID_ARGUMENT is returned before anything is queued and leaves the object, the last transform's fields included,
+ * as it was: NULL arguments, a config out of range, metres / costmap / stats before any transform, a resolution that is not
+ * finite and > 0.
+ *
+ * LIMITS.  A transform always rebuilds the whole field.  An uncapped transform, or one capped above 64 cells, costs
+ * log2(W) + 1 passes over each row whatever the grid holds; a cap of up to 64 cells takes a search of at most R columns per
+ * cell instead.  The costmap inflates by a circle: no footprint. */
+#define LFX_DISTANCE_FAR 0xFFFFFFFFu
+#define LFX_DISTANCE_FREE 0
+#define LFX_DISTANCE_UNKNOWN 1
+#define LFX_DISTANCE_OBSTACLE 2
+#define LFX_DISTANCE_MAX_COST_CELLS 1024
+typedef struct lfx_distance lfx_distance;
+typedef struct lfx_distance_config {
+  int32_t occupied_percent;     /* 65; 1 .. 100 */
+  uint32_t unknown_is_obstacle; /* 0; 0 / 1 */
+  uint32_t max_cells;           /* R: 0 = uncapped, else 1 .. 32767 */
+  uint32_t inside;              /* 0; 0 / 1: compute i2 */
+  uint32_t reserved;            /* 0 */
+} lfx_distance_config;
+typedef struct lfx_distance_cost_config {
+  float inscribed_radius;       /* 0.22; finite, >= 0 */
+  float inflation_radius;       /* 0.55; finite, >= inscribed_radius */
+  float cost_scaling_factor;    /* 10.0; finite, >= 0 */
+  uint32_t track_unknown;       /* 1; 0 / 1 */
+} lfx_distance_cost_config;
+typedef struct lfx_distance_info_t {
+  uint32_t width, height;
+  uint32_t transformed;         /* whether a transform has run; the next two are its config's */
+  uint32_t max_cells, inside;
+  uint32_t reserved;
+  uint64_t device_bytes;        /* everything lfx_distance_create allocated on the device */
+} lfx_distance_info_t;
+typedef struct lfx_distance_view_t {
+  const uint8_t *classes;       /* device [height][width] */
+  const uint32_t *d2;           /* device [height][width] */
+  const uint32_t *i2;           /* device [height][width]; NULL unless the last transform had `inside` */
+} lfx_distance_view_t;
+typedef struct lfx_distance_stats_t {   /* of the last transform */
+  uint64_t n_obstacle, n_unknown;       /* cells by class */
+  uint64_t n_far;                       /* cells whose d2 is FAR */
+  uint64_t max_d2;                      /* over the cells whose d2 is not FAR; 0 if there is none */
+} lfx_distance_stats_t;
+void lfx_distance_default_config(lfx_distance_config *config);
+void lfx_distance_cost_default_config(lfx_distance_cost_config *config);
+/* host only, no context: n = Rc*Rc + 1.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, a field outside the ranges above, a
+ * resolution that is not finite and > 0, Rc above LFX_DISTANCE_MAX_COST_CELLS. */
+int lfx_distance_cost_table_size(const lfx_distance_cost_config *config, float resolution, uint32_t *n);
+/* host only, no context: the table.  LFX_ERR_INVALID_ARGUMENT as above, and n that is not lfx_distance_cost_table_size's. */
+int lfx_distance_cost_table(const lfx_distance_cost_config *config, float resolution, uint8_t *lut /*[n]*/, uint32_t n);
+/* width and height outside 1 .. LFX_OCCUPANCY_MAX_SIDE: LFX_ERR_INVALID_ARGUMENT; a failed allocation: LFX_ERR_OUT_OF_MEMORY
+ * with nothing left allocated. */
+int lfx_distance_create(lfx_ctx *ctx, uint32_t width, uint32_t height, lfx_distance **out);
+void lfx_distance_destroy(lfx_distance *field);
+int lfx_distance_info(const lfx_distance *field, lfx_distance_info_t *info);
+/* The transform of a device grid, int8 [height][width]; asynchronous, d_grid is read behind `stream`. */
+int lfx_distance_from_grid(lfx_ctx *ctx, lfx_distance *field, const int8_t *d_grid, const lfx_distance_config *config, void *stream);
+/* The transform of an occupancy grid's counts as they stand: the bytes of lfx_occupancy_emit(emit_config) into a buffer and
+ * lfx_distance_from_grid of it.  Ordered behind the occupancy grid's last call, whose event moves behind this read (the store's
+ * rule for a reader); a new emit config's table goes up as for lfx_occupancy_emit.  LFX_ERR_INVALID_ARGUMENT also: a grid whose
+ * width or height is not the field's, what lfx_occupancy_emit_table refuses. */
+int lfx_distance_from_occupancy(lfx_ctx *ctx, lfx_distance *field, lfx_occupancy *grid, const lfx_occupancy_emit_config *emit_config,
+                                const lfx_distance_config *config, void *stream);
+/* The device arrays, current behind `stream`. */
+int lfx_distance_view(lfx_ctx *ctx, const lfx_distance *field, lfx_distance_view_t *view, void *stream);
+/* float [height][width] to out: device memory or a pinned block (lfx_host_alloc); asynchronous. */
+int lfx_distance_metres(lfx_ctx *ctx, lfx_distance *field, float resolution, float *out, void *stream);
+/* uint8 [height][width] to out: device memory or a pinned block; asynchronous.  A new (cost config, resolution)'s table goes up
+ * from a pinned block of the object's, after a wait for the object's last call; the one of the call before is not sent again.
+ * LFX_ERR_INVALID_ARGUMENT also: what lfx_distance_cost_table_size refuses, a last transform with 0 < max_cells < Rc. */
+int lfx_distance_costmap(lfx_ctx *ctx, lfx_distance *field, const lfx_distance_cost_config *config, float resolution, uint8_t *out,
+                         void *stream);
+/* Synchronous: integer reductions, the same numbers whatever the schedule. */
+int lfx_distance_stats(lfx_ctx *ctx, const lfx_distance *field, lfx_distance_stats_t *stats, void *stream);
+
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device
  * routines the fused ring kernel runs.  Optional inputs may be NULL.

@@ -1275,6 +1275,81 @@ private:
   lfx_occupancy * grid_ = nullptr;
 };
 
+// A distance field (lfx_distance) over grids of width x height cells on the device of `fx`, which must outlive it: a
+// transform (FromGrid of an int8 grid on the device, FromOccupancy of an OccupancyGrid's counts as they stand) gives the
+// exact squared distance of every cell to the nearest obstacle cell; Metres and Costmap turn the last transform into an ESDF
+// and into nav2's inflated costs.  After a loop closure: OccupancyGrid::Follow, RenderAll, then one FromOccupancy.
+class DistanceField
+{
+public:
+  static lfx_distance_config DefaultConfig() {lfx_distance_config c; lfx_distance_default_config(&c); return c;}
+  static lfx_distance_cost_config DefaultCostConfig() {lfx_distance_cost_config c; lfx_distance_cost_default_config(&c); return c;}
+  // lfx_distance_cost_table: the bytes the costmap kernel is handed (host only)
+  static std::vector<std::uint8_t> CostTable(const lfx_distance_cost_config & config, float resolution)
+  {
+    std::uint32_t n = 0;
+    if (lfx_distance_cost_table_size(&config, resolution, &n) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "the cost config is refused");}
+    std::vector<std::uint8_t> lut(n);
+    if (lfx_distance_cost_table(&config, resolution, lut.data(), n) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "the cost config is refused");}
+    return lut;
+  }
+  DistanceField(const FeatureExtraction & fx, std::uint32_t width, std::uint32_t height)
+  : fx_(fx)
+  {
+    Check(lfx_distance_create(fx.handle(), width, height, &field_));
+  }
+  ~DistanceField() {lfx_distance_destroy(field_);}
+  DistanceField(const DistanceField &) = delete;
+  DistanceField & operator=(const DistanceField &) = delete;
+
+  // d_grid: int8 [height][width] on the device, lfx_occupancy_emit's format; read behind `stream`
+  void FromGrid(const std::int8_t * d_grid, const lfx_distance_config & config = DefaultConfig(), void * stream = nullptr)
+  {
+    Check(lfx_distance_from_grid(fx_.handle(), field_, d_grid, &config, stream));
+  }
+  // the bytes grid.Emit(emit_config) would write, transformed without being written
+  void FromOccupancy(OccupancyGrid & grid, const lfx_distance_config & config = DefaultConfig(),
+    const lfx_occupancy_emit_config & emit_config = OccupancyGrid::DefaultEmitConfig(), void * stream = nullptr)
+  {
+    Check(lfx_distance_from_occupancy(fx_.handle(), field_, grid.handle(), &emit_config, &config, stream));
+  }
+  // the device arrays, current behind `stream`; i2 is null unless the last transform had `inside`
+  lfx_distance_view_t View(void * stream = nullptr) const
+  {
+    lfx_distance_view_t v;
+    Check(lfx_distance_view(fx_.handle(), field_, &v, stream));
+    return v;
+  }
+  // float / uint8 [height][width] to device memory or a pinned block (FeatureExtraction::PinnedFloats); both return before
+  // the output is written: read it behind `stream`
+  void Metres(float resolution, float * out, void * stream = nullptr) {Check(lfx_distance_metres(fx_.handle(), field_, resolution, out, stream));}
+  void Costmap(float resolution, std::uint8_t * out, const lfx_distance_cost_config & config = DefaultCostConfig(), void * stream = nullptr)
+  {
+    Check(lfx_distance_costmap(fx_.handle(), field_, &config, resolution, out, stream));
+  }
+  lfx_distance_stats_t Stats(void * stream = nullptr) const
+  {
+    lfx_distance_stats_t s;
+    Check(lfx_distance_stats(fx_.handle(), field_, &s, stream));
+    return s;
+  }
+  lfx_distance_info_t Info() const
+  {
+    lfx_distance_info_t i;
+    lfx_distance_info(field_, &i);
+    return i;
+  }
+  lfx_distance * handle() const {return field_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_distance * field_ = nullptr;
+};
+
 // Visibility votes (lfx_visibility): which records of a window of a Keyframes store's keyframes were looked through by the
 // keyframes near them, and the DYNAMIC flag that decides.  None of the defaults is measured on real data.
 class Visibility

@@ -17,4 +17,5 @@ from .extraction import LoopCloser, loop_closer_config  # noqa: F401
 from .extraction import Visibility, visibility_config, visibility_tables  # noqa: F401
 from .extraction import VoxelFilter  # noqa: F401
 from .extraction import OccupancyGrid, occupancy_config, occupancy_tables, occupancy_emit_config, occupancy_emit_table, write_occupancy_map  # noqa: F401
+from .extraction import DistanceField, distance_config, distance_cost_config, distance_cost_table  # noqa: F401
 from .synth import POINT_DTYPE, SENSORS, make_scan, make_batch, make_sequence, make_sweep, make_sweep_trajectory, concat  # noqa: F401

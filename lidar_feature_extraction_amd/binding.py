@@ -321,6 +321,35 @@ class OccupancyCounters(C.Structure):
 
 
 OCCUPANCY_NONE, OCCUPANCY_HIT, OCCUPANCY_CLEAR = 0, 1, 2
+
+
+class DistanceConfig(C.Structure):
+    """lfx_distance_config: what counts as an obstacle, the cap in cells (0: none) and whether the inside field is wanted."""
+    _fields_ = [("occupied_percent", C.c_int32), ("unknown_is_obstacle", C.c_uint32), ("max_cells", C.c_uint32), ("inside", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class DistanceCostConfig(C.Structure):
+    """lfx_distance_cost_config: nav2's inflation layer -- the two radii in metres, the decay and whether unknown cells cost 255."""
+    _fields_ = [("inscribed_radius", C.c_float), ("inflation_radius", C.c_float), ("cost_scaling_factor", C.c_float), ("track_unknown", C.c_uint32)]
+
+
+class DistanceInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "transformed", "max_cells", "inside", "reserved")] + [("device_bytes", C.c_uint64)]
+
+
+class DistanceView(C.Structure):
+    _fields_ = [("classes", C.c_void_p), ("d2", C.c_void_p), ("i2", C.c_void_p)]
+
+
+class DistanceStats(C.Structure):
+    """lfx_distance_stats_t: the last transform's cells by class, its FAR cells and the largest d2 that is not FAR."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_obstacle", "n_unknown", "n_far", "max_d2")]
+
+
+DISTANCE_FAR = 0xFFFFFFFF
+DISTANCE_FREE, DISTANCE_UNKNOWN, DISTANCE_OBSTACLE = 0, 1, 2
+DISTANCE_MAX_COST_CELLS = 1024
 OCCUPANCY_MAX_BEAMS, OCCUPANCY_MAX_SIDE = 4096, 16384
 
 
@@ -436,6 +465,9 @@ EXPORTS = [
     "lfx_occupancy_create", "lfx_occupancy_destroy", "lfx_occupancy_info", "lfx_occupancy_view", "lfx_occupancy_add_batch",
     "lfx_occupancy_set_poses", "lfx_occupancy_poses", "lfx_occupancy_follow", "lfx_occupancy_clear", "lfx_occupancy_render",
     "lfx_occupancy_counters", "lfx_occupancy_emit", "lfx_occupancy_write_map", "lfx_occupancy_save",
+    "lfx_distance_default_config", "lfx_distance_cost_default_config", "lfx_distance_cost_table_size", "lfx_distance_cost_table",
+    "lfx_distance_create", "lfx_distance_destroy", "lfx_distance_info", "lfx_distance_from_grid", "lfx_distance_from_occupancy",
+    "lfx_distance_view", "lfx_distance_metres", "lfx_distance_costmap", "lfx_distance_stats",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -699,6 +731,23 @@ def load(test_hooks=False):
     L.lfx_occupancy_emit.argtypes = [vp, vp, poe, vp, vp]
     L.lfx_occupancy_write_map.argtypes = [C.c_char_p, vp, u32, u32, C.c_float, C.c_double, C.c_double, i32, i32]
     L.lfx_occupancy_save.argtypes = [vp, vp, poe, C.c_char_p, i32, i32, vp]
+    pdc, pdk = C.POINTER(DistanceConfig), C.POINTER(DistanceCostConfig)
+    L.lfx_distance_default_config.argtypes = [pdc]
+    L.lfx_distance_default_config.restype = None
+    L.lfx_distance_cost_default_config.argtypes = [pdk]
+    L.lfx_distance_cost_default_config.restype = None
+    L.lfx_distance_cost_table_size.argtypes = [pdk, C.c_float, C.POINTER(u32)]
+    L.lfx_distance_cost_table.argtypes = [pdk, C.c_float, vp, u32]
+    L.lfx_distance_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+    L.lfx_distance_destroy.argtypes = [vp]
+    L.lfx_distance_destroy.restype = None
+    L.lfx_distance_info.argtypes = [vp, C.POINTER(DistanceInfo)]
+    L.lfx_distance_from_grid.argtypes = [vp, vp, vp, pdc, vp]
+    L.lfx_distance_from_occupancy.argtypes = [vp, vp, vp, poe, pdc, vp]
+    L.lfx_distance_view.argtypes = [vp, vp, C.POINTER(DistanceView), vp]
+    L.lfx_distance_metres.argtypes = [vp, vp, C.c_float, vp, vp]
+    L.lfx_distance_costmap.argtypes = [vp, vp, pdk, C.c_float, vp, vp]
+    L.lfx_distance_stats.argtypes = [vp, vp, C.POINTER(DistanceStats), vp]
     L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     plc = C.POINTER(LoopCloserConfig)
     L.lfx_loop_closer_default_config.argtypes = [plc]

@@ -651,6 +651,21 @@ struct KeyframesAccess
 };
 KeyframesAccess keyframes_access(const lfx_keyframes * s);
 
+// What a reader of an occupancy grid's counts needs (lfx_occupancy.hip; the distance field reads them in place): the two
+// count arrays, the emit's table on the device and the tail event the reader orders itself behind and moves.
+struct OccupancyAccess
+{
+  int device = 0;
+  uint32_t width = 0, height = 0;
+  const uint32_t * hits = nullptr, * misses = nullptr;
+  const int8_t * lut = nullptr;
+  const Tail * tail = nullptr;
+};
+OccupancyAccess occupancy_access(const lfx_occupancy * g);
+// the emit's table of `config` put on the device as lfx_occupancy_emit puts it (nothing is sent for the config of the call
+// before); LFX_ERR_INVALID_ARGUMENT, before anything is queued: what lfx_occupancy_emit_table refuses
+int occupancy_put_table(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & config, hipStream_t st);
+
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
   const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "lfx_kernels_image.hpp"
+#include "lfx_kernels_occvalue.hpp"
 
 #pragma clang fp contract(off)
 
@@ -146,13 +147,6 @@ __device__ inline void occ_set(uint32_t * bits, int64_t bit)
   if (!(*word & mask)) {atomicOr(word, mask);}
 }
 
-// the sum of v over the workgroup's lanes added to *counter: a shuffle tree per wave, one atomic per wave that has any
-__device__ inline void occ_count(unsigned long long * counter, uint32_t v)
-{
-  for (int d = 32; d; d >>= 1) {v += __shfl_down(v, d);}
-  if ((threadIdx.x & 63u) == 0u && v) {atomicAdd(counter, (unsigned long long)v);}
-}
-
 // The walk's state after k steps, 0 <= k <= max(ax, ay), without walking them.  The major axis moves at every step; along
 // it err stays within one major length of its start (x major: ax/2 - ay <= err < 3 ax/2 - ay; y major: ax - 3 ay/2 < err <=
 // ax - ay/2), which leaves one value for the minor steps so far: ceil((2 k minor - major) / (2 major)).  Products stay
@@ -287,26 +281,6 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_fold_kernel(const OccRe
 }
 
 // --- emit -------------------------------------------------------------------------------------------------------------------
-struct OccEmitArgs
-{
-  const uint32_t * hits, * misses;
-  uint64_t cells;
-  int64_t w_hit, w_miss, l_min, l_max;
-  uint32_t min_observations;
-  const int8_t * lut;                   // [l_max - l_min + 1]: lfx_occupancy_emit_table's bytes
-  int8_t * out;                         // device memory or a pinned block
-  bool words;                           // out is 4-byte aligned: four cells leave as one word
-};
-
-__device__ inline int8_t occ_value(const OccEmitArgs & A, uint64_t cell)
-{
-  const uint32_t h = A.hits[cell], m = A.misses[cell];
-  if ((uint64_t)h + (uint64_t)m < (uint64_t)A.min_observations) {return (int8_t)-1;}
-  int64_t l = (int64_t)h * A.w_hit - (int64_t)m * A.w_miss;
-  l = l < A.l_min ? A.l_min : (l > A.l_max ? A.l_max : l);
-  return A.lut[l - A.l_min];
-}
-
 // four consecutive cells per thread
 __global__ __launch_bounds__(kOccThreads) void occupancy_emit_kernel(const OccEmitArgs A)
 {

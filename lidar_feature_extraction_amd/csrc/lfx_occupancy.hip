@@ -90,6 +90,22 @@ int launch_emit(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config 
 }
 }  // namespace
 
+namespace lfx_host
+{
+OccupancyAccess occupancy_access(const lfx_occupancy * g)
+{
+  OccupancyAccess a;
+  a.device = g->device;
+  a.width = g->cfg.width; a.height = g->cfg.height;
+  a.hits = g->hits.p; a.misses = g->misses.p;
+  a.lut = g->lut.p;
+  a.tail = &g->tail;
+  return a;
+}
+
+int occupancy_put_table(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & config, hipStream_t st) {return put_lut(c, g, config, st);}
+}  // namespace lfx_host
+
 extern "C" {
 
 int lfx_occupancy_create(lfx_ctx * c, const lfx_occupancy_config * config, lfx_occupancy ** out)

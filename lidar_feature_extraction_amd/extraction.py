@@ -523,6 +523,10 @@ class FeatureExtraction:
         lfx_occupancy_config as keywords."""
         return OccupancyGrid(self, width, height, resolution, origin, max_scans, config, **fields)
 
+    def distance_field(self, width, height):
+        """lfx_distance_create: a distance field over grids of width x height cells on this context's device."""
+        return DistanceField(self, width, height)
+
     def visibility(self, max_window=1024, max_resident_images=None, config=None, **fields):
         """lfx_visibility_create: visibility votes over windows of up to max_window keyframes, max_resident_images (default:
         all of them) range images on the device at a time; the fields of lfx_visibility_config as keywords."""
@@ -848,6 +852,36 @@ def occupancy_emit_table(config=None):
     if rc != 0:
         raise B.LfxError(rc, "the occupancy emit config is refused")
     return lut[:int(cfg.l_max) - int(cfg.l_min) + 1].copy()
+
+
+def distance_config(config=None, **fields):
+    """lfx_distance_config: the defaults (occupied_percent 65, unknown cells no obstacles, no cap, no inside field) with the
+    given fields replaced."""
+    return _config(B.DistanceConfig, "lfx_distance_default_config", "distance", config, fields)
+
+
+def distance_cost_config(config=None, **fields):
+    """lfx_distance_cost_config: nav2's inflation defaults (0.22 m, 0.55 m, 10.0, unknown cells tracked) with the given
+    fields replaced."""
+    return _config(B.DistanceCostConfig, "lfx_distance_cost_default_config", "distance cost", config, fields)
+
+
+def distance_cost_table(config=None, resolution=0.05, n=None):
+    """lfx_distance_cost_table: the uint8 table [Rc * Rc + 1] the costmap kernel is handed, and the only source of the decay.
+    Host only.  n: the size to ask with (None: lfx_distance_cost_table_size's)."""
+    cfg = distance_cost_config(config)
+    L = B.load()
+    if n is None:
+        size = C.c_uint32(0)
+        rc = L.lfx_distance_cost_table_size(C.byref(cfg), float(resolution), C.byref(size))
+        if rc != 0:
+            raise B.LfxError(rc, "the distance cost config is refused")
+        n = int(size.value)
+    lut = np.zeros(max(int(n), 1), np.uint8)
+    rc = L.lfx_distance_cost_table(C.byref(cfg), float(resolution), C.c_void_p(lut.ctypes.data), int(n))
+    if rc != 0:
+        raise B.LfxError(rc, "the distance cost config is refused")
+    return lut[:int(n)]
 
 
 def write_occupancy_map(dirname, grid, resolution, origin=(0.0, 0.0), occupied_percent=65, free_percent=25):
@@ -2083,6 +2117,95 @@ class OccupancyGrid(_Handle):
         v = self.view(stream)
         shape = (int(self.config.height), int(self.config.width))
         return self._array(v["hits"], shape, np.uint32, stream), self._array(v["misses"], shape, np.uint32, stream)
+
+
+class DistanceField(_Handle):
+    """lfx_distance: the exact squared distance of every cell of an occupancy grid to the nearest obstacle cell, and what
+    planners take from it -- metres (an ESDF) and nav2's inflated costmap (include/lfx.h, the distance section).  A transform
+    (from_grid, from_occupancy) rebuilds the whole field; metres, costmap and stats read the last one."""
+
+    _destroy = "lfx_distance_destroy"
+
+    def __init__(self, fx, width, height):
+        self._fx = fx
+        self._L = fx._L
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_distance_create(fx._ctx, int(width), int(height), C.byref(h)), self._L)
+        self.handle = h
+        self.width, self.height = int(width), int(height)
+
+    def info(self):
+        i = B.DistanceInfo()
+        self._check(self._L.lfx_distance_info(self.handle, C.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in B.DistanceInfo._fields_ if n != "reserved"}
+
+    def from_grid(self, grid, config=None, stream=0, **fields):
+        """lfx_distance_from_grid: the transform of an int8 grid [height][width] in emit's format -- a device tensor or the
+        address of device memory.  Asynchronous: the grid is read behind `stream`."""
+        cfg = distance_config(config, **fields)
+        if hasattr(grid, "data_ptr"):
+            if grid.element_size() != 1 or grid.numel() != self.width * self.height or not grid.is_contiguous():
+                raise ValueError("the grid is a contiguous int8 tensor of height x width cells")
+            grid = grid.data_ptr()
+        self._check(self._L.lfx_distance_from_grid(self._fx._ctx, self.handle, C.c_void_p(int(grid) or None), C.byref(cfg), C.c_void_p(int(stream))))
+
+    def from_occupancy(self, occupancy, emit_config=None, config=None, stream=0, **fields):
+        """lfx_distance_from_occupancy: the transform of an OccupancyGrid's counts as they stand -- the bytes of its emit with
+        emit_config and from_grid of them, without the int8 grid in between."""
+        ecfg = occupancy_emit_config(emit_config)
+        cfg = distance_config(config, **fields)
+        self._check(self._L.lfx_distance_from_occupancy(self._fx._ctx, self.handle, occupancy.handle, C.byref(ecfg), C.byref(cfg),
+                                                        C.c_void_p(int(stream))))
+
+    def view(self, stream=0):
+        """lfx_distance_view: the device addresses of the classes, d2 and i2 (0 without `inside`), current behind `stream`."""
+        v = B.DistanceView()
+        self._check(self._L.lfx_distance_view(self._fx._ctx, self.handle, C.byref(v), C.c_void_p(int(stream))))
+        return dict(classes=v.classes or 0, d2=v.d2 or 0, i2=v.i2 or 0)
+
+    def _new(self, dtype):
+        import torch
+        return torch.empty((self.height, self.width), dtype=dtype, device=torch.device("cuda", self._fx.device))
+
+    def metres(self, resolution, out=None, stream=0):
+        """lfx_distance_metres: float32 [height][width].  out: None = a new device tensor is returned, or the address of
+        device memory or of a pinned block (nothing is returned).  Asynchronous on `stream`."""
+        made = None
+        if out is None:
+            import torch
+            made = self._new(torch.float32)
+            out = made.data_ptr()
+        self._check(self._L.lfx_distance_metres(self._fx._ctx, self.handle, float(resolution), C.c_void_p(int(out) or None), C.c_void_p(int(stream))))
+        return made
+
+    def costmap(self, resolution, config=None, out=None, stream=0, **fields):
+        """lfx_distance_costmap: nav2's costs, uint8 [height][width]; out as for metres."""
+        cfg = distance_cost_config(config, **fields)
+        made = None
+        if out is None:
+            import torch
+            made = self._new(torch.uint8)
+            out = made.data_ptr()
+        self._check(self._L.lfx_distance_costmap(self._fx._ctx, self.handle, C.byref(cfg), float(resolution), C.c_void_p(int(out) or None),
+                                                 C.c_void_p(int(stream))))
+        return made
+
+    def stats(self, stream=0):
+        r = B.DistanceStats()
+        self._check(self._L.lfx_distance_stats(self._fx._ctx, self.handle, C.byref(r), C.c_void_p(int(stream))))
+        return {n: int(getattr(r, n)) for n, _ in B.DistanceStats._fields_}
+
+    def fields(self, stream=0):
+        """The last transform on the host: (classes uint8, d2 uint32, i2 uint32 or None), [height][width] each."""
+        import torch
+        v = self.view(stream)
+        torch.cuda.synchronize(self._fx.device)              # (a read-back for inspection: everything queued has landed)
+        shape = (self.height, self.width)
+
+        def get(ptr, dtype):
+            n = self.width * self.height * np.dtype(dtype).itemsize
+            return _device_bytes(ptr, n, self._fx.device, self).cpu().numpy().view(dtype).reshape(shape).copy()
+        return get(v["classes"], np.uint8), get(v["d2"], np.uint32), (get(v["i2"], np.uint32) if v["i2"] else None)
 
 
 class Visibility(_Handle):
