@@ -121,7 +121,8 @@ typedef struct lfx_config {
 #define LFX_STREAM_NO_GRID 2u      /* records missing or in arbitrary order: the bucketing route from the first batch on */
 #define LFX_STREAM_GRID_WITH_HOLES 3u /* a grid whose invalid returns are (0, 0, 0) records, with drop_zero_points set (what the
                                     * reference's converter filters, convert.py:162-163,192): count the valid returns per ring
-                                    * first and read the grid in place, from the first batch on                          */
+                                    * first and read the grid in place, from the first batch on.  Means nothing (and is
+                                    * dropped) without drop_zero_points or on a context with long rings                  */
 
 #define LFX_OUT_FEATURES 1u        /* always on */
 #define LFX_OUT_LABELS 2u
@@ -2196,7 +2197,11 @@ int lfx_color_points_by_label(const lfx_ctx *ctx, const void *points, size_t n_p
  * `state` in and out = {rings transformed, every scan bucketed, batches until the organised route is tried again, order
  * repair first, grid with holes}, `choice` out = {organised-scan kernel first, with ring transforms, fall-back list entries
  * launched for, one-launch tail, order repair before the first unit pass, rings the second unit pass is launched for, the
- * holes form (count pass first)}.  tests/test_route_choice.py drives it. */
+ * holes form (count pass first)}.  `organised_possible`: bit 0 = the organised-scan kernel can run (ring ids 0 .. n - 1, the
+ * canonical record layout); LFX_ROUTE_NO_HOLES_FORM beside it = the context cannot run the holes form (no zero filter, or
+ * long rings), so the flag is never kept.  tests/test_route_choice.py drives it row by row, tests/test_route_streams.py over
+ * whole streams. */
+#define LFX_ROUTE_NO_HOLES_FORM 2
 #define LFX_ROUTE_REPORT_WORDS 14
 #define LFX_ROUTE_STATE_WORDS 5
 #define LFX_ROUTE_CHOICE_WORDS 7

@@ -145,7 +145,10 @@ constexpr size_t kLongWorkBudget = (size_t)512 << 20;
 //   fb_grid     list entries the bucketing kernels are launched for (they loop where the list turns out longer)
 //   short_tail  bucketing route = bucketing + the workgroup-per-ring kernel (two near-empty launches instead of five)
 //   pre_order   order repair ahead of the first unit pass;  redo_cap  rings the second unit pass is launched for
-RouteChoice choose_route(RouteState & st, const RoutePins & pin, bool organised_possible, uint32_t batch, uint32_t max_rings)
+// holes_possible: the context can run the holes form (zero filter on, no long rings); where it cannot, use_holes is never kept
+// -- a flag whose form never runs would wait for that form's report for ever.
+RouteChoice choose_route(RouteState & st, const RoutePins & pin, bool organised_possible, bool holes_possible, uint32_t batch,
+  uint32_t max_rings)
 {
   RouteChoice ch;
   const uint32_t * rep = st.report;
@@ -169,12 +172,16 @@ RouteChoice choose_route(RouteState & st, const RoutePins & pin, bool organised_
     }
     if (pin.xform >= 0) {st.use_xform = pin.xform != 0;}
     if (pin.holes >= 0) {st.use_holes = pin.holes != 0;}
+    if (!holes_possible) {st.use_holes = false;}         // (a stream hint included: GRID_WITH_HOLES means nothing to such a context)
     if (pin.fused >= 0) {
       fused = pin.fused != 0;
     } else {
       if (was_fused && of) {
-        // (a report from before the transforms were switched on says nothing about the route with them)
-        const bool mostly_not = 4u * fell > of && !(st.use_xform && !cut_ran) && !(st.use_holes && !rep[lfx::kCntHolesRan]);
+        // (a report from before the transforms were switched on says nothing about the route with them; one from before the
+        // holes form likewise -- where that form is what the next batch gets: the transforms win over it below, and rings
+        // turned AND holed are the bucketing route's once the transforms have been tried)
+        const bool holes_next = st.use_holes && !st.use_xform;
+        const bool mostly_not = 4u * fell > of && !(st.use_xform && !cut_ran) && !(holes_next && !rep[lfx::kCntHolesRan]);
         if (mostly_not && !st.bucket_all) {st.retry_in = 16;}
         st.bucket_all = mostly_not;
       }
@@ -339,9 +346,10 @@ int run_batch(lfx_ctx * c, const void * d_points, const uint32_t * n_points, uin
       c->report_taken = end;
     }
   }
-  const RouteChoice choice = choose_route(c->route, c->route_pins, c->fused_possible && canon && chunks != 0, batch, c->max_rings);
+  const bool holes_possible = c->drop_zero != 0u && c->cum16.p != nullptr;
+  const RouteChoice choice = choose_route(c->route, c->route_pins, c->fused_possible && canon && chunks != 0, holes_possible, batch, c->max_rings);
   const bool fused = choice.fused, short_tail = choice.short_tail;
-  const bool holes = choice.holes && c->drop_zero != 0u && c->cum16.p != nullptr;
+  const bool holes = choice.holes && holes_possible;
   const uint32_t fb_grid = choice.fb_grid;             // list entries the bucketing kernels are launched for
   if (chunks == 0) {
     // every scan of the batch is empty: no kernel runs; the result tables say so
@@ -750,7 +758,7 @@ int lfx_route_choice(const uint32_t report[LFX_ROUTE_REPORT_WORDS], uint32_t rep
   std::memcpy(st.report, report, sizeof(st.report));
   st.report_rings = report_rings;
   st.use_xform = state[0] != 0; st.bucket_all = state[1] != 0; st.retry_in = state[2]; st.pre_order = state[3] != 0; st.use_holes = state[4] != 0;
-  const RouteChoice ch = choose_route(st, RoutePins(), organised_possible != 0, batch, max_rings);
+  const RouteChoice ch = choose_route(st, RoutePins(), (organised_possible & 1) != 0, (organised_possible & LFX_ROUTE_NO_HOLES_FORM) == 0, batch, max_rings);
   state[0] = st.use_xform; state[1] = st.bucket_all; state[2] = st.retry_in; state[3] = st.pre_order; state[4] = st.use_holes;
   choice[0] = ch.fused; choice[1] = ch.xform; choice[2] = ch.fb_grid; choice[3] = ch.short_tail; choice[4] = ch.pre_order;
   choice[5] = ch.redo_cap; choice[6] = ch.holes;
