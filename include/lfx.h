@@ -2014,6 +2014,11 @@ int lfx_occupancy_add_batch(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t n_scans,
 int lfx_occupancy_set_poses(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t first, uint32_t count, const double *poses, void *stream);
 int lfx_occupancy_poses(lfx_ctx *ctx, const lfx_occupancy *grid, uint32_t first, uint32_t count, double *poses_out, void *stream);
 int lfx_occupancy_follow(lfx_ctx *ctx, lfx_occupancy *grid, const double *d_poses, uint32_t first, uint32_t count, void *stream);
+/* Drops the store's scans from n_scans on: the next lfx_occupancy_add_batch appends from id n_scans.  The counts are untouched
+ * (what the dropped scans voted stays until a clear).  With it a second small grid (1 x 1 cells) serves as the reducer of live
+ * batches for lfx_grid_match_set_scans_occupancy: truncate(0), add_batch, set_scans_occupancy.  n_scans above the store's:
+ * LFX_ERR_INVALID_ARGUMENT. */
+int lfx_occupancy_truncate(lfx_ctx *ctx, lfx_occupancy *grid, uint32_t n_scans, void *stream);
 /* Zeroes the counts and the counters; asynchronous. */
 int lfx_occupancy_clear(lfx_ctx *ctx, lfx_occupancy *grid, void *stream);
 /* The votes of scans [first, first + count) at their current poses added to the counts; asynchronous.  Scans outside the
@@ -2147,6 +2152,160 @@ int lfx_distance_costmap(lfx_ctx *ctx, lfx_distance *field, const lfx_distance_c
                          void *stream);
 /* Synchronous: integer reductions, the same numbers whatever the schedule. */
 int lfx_distance_stats(lfx_ctx *ctx, const lfx_distance *field, lfx_distance_stats_t *stats, void *stream);
+
+/* --- scan matching in occupancy grids: where a scan is in the map ------------------------------------------------------------ */
+/* What a 2-D stack localises with: the likelihood field of the grid (AMCL's likelihood_field model) scored for arbitrary poses
+ * -- a particle filter's measurement update -- and searched exhaustively over a window of (x, y, yaw) -- Olson's and
+ * Cartographer's correlative scan matcher, for relocalisation, tracking and a 2-D loop check.  No reference counterpart.  The
+ * pose found is the initial pose lfx_localize_batch, the rolling map and lfx_loop_closer_verify ask for
+ * (lfx_grid_match_pose3).  Everything below is double, unfused, unless stated; scores are integers throughout: the same field,
+ * scans and candidates give the same bytes, whatever the schedule.  The device evaluates no trigonometric function.
+ *
+ * CONFIG.  width, height, resolution, origin_x, origin_y with the meaning and ranges of lfx_occupancy_config (lfx_distance
+ *   carries no geometry, so the matcher does); inv_res = 1.0 / (double)resolution.  max_scans 1 .. 1024, max_beams 4 ..
+ *   LFX_OCCUPANCY_MAX_BEAMS, max_half_x and max_half_y 0 .. LFX_GRID_MATCH_MAX_HALF cells, max_half_theta 0 ..
+ *   LFX_GRID_MATCH_MAX_HALF_THETA steps.
+ *
+ * SCORE TABLE (lfx_grid_match_table: host only, the ONLY source; the device is handed these bytes).
+ *   Rs = (uint32)ceil((double)max_distance / (double)resolution), at most LFX_GRID_MATCH_MAX_CELLS; n = Rs*Rs + 1; for k = 0 ..
+ *   Rs*Rs with d = sqrt((double)k) * (double)resolution: d > (double)max_distance: lut[k] = 0; otherwise
+ *   lut[k] = (uint16)rint((double)peak * exp(-(d*d) / ((2.0 * (double)sigma) * (double)sigma))).  A caller may hand any uint16
+ *   table of a legal size (Rs*Rs + 1 entries, Rs in 0 .. 64) instead, fixed-point log-likelihoods for one.
+ *
+ * FIELD (lfx_grid_match_set_field), S uint16 [H][W] from a distance field's d2: S[y][x] = 0 where d2 is LFX_DISTANCE_FAR or
+ *   d2 >= n, otherwise lut[d2].  The last transform must have had max_cells 0 or >= Rs (the costmap's rule).
+ *
+ * SCANS (lfx_grid_match_set_scans).  Beams are lfx_occupancy_view_t.beams; only those whose kind bits are LFX_OCCUPANCY_HIT
+ *   take part.  With the scan's level l[9] (row-major 3 x 3; NULL: identity) and the beam's x, y, z as doubles:
+ *   px = (l0*x + l1*y) + l2*z, py = (l3*x + l4*y) + l5*z; a beam whose px or py is not finite is left out.  n_points[s] is the
+ *   number kept.  The points are a multiset (the sums are integer); they are kept compacted, in beam order.
+ *   lfx_grid_match_set_scans_occupancy takes a store's scans with the rotations of the poses the store holds NOW for levels,
+ *   read on the device: with the stored (t_x, t_y) as candidate at c = 1, s = 0 the cells below are exactly
+ *   lfx_occupancy_render's end cells.
+ *
+ * CANDIDATE.  (tx, ty, c, s): the caller supplies the cosine and the sine.  For a point: wx = (c*px - s*py) + tx,
+ *   wy = (s*px + c*py) + ty, ex = floor((wx - origin_x) * inv_res), ey = floor((wy - origin_y) * inv_res).  A point is OUTSIDE
+ *   and adds 0 if ex or ey is not finite or not below 2^30 in size, or if (ex, ey) is no cell of the grid.
+ *   score = the sum of S[ey][ex] over the scan's points in uint32 (at most 4096 * 65535 < 2^28); inside = the number of
+ *   points whose cell is in the grid.
+ *
+ * SEARCH (lfx_grid_match_search).  Nx = 2*half_x + 1, Ny = 2*half_y + 1, T = 2*half_theta + 1.  The rotations come from
+ *   lfx_grid_match_rotations (host only, the ONLY source: the call computes them and sends them up):
+ *   angle_j = yaw0 + (double)(j - half_theta) * theta_step, c = cos(angle_j), s = sin(angle_j) by the host's libm (half_theta == 0: angle_0 = yaw0, theta_step is not read).  Per
+ *   (scan, j) and point the base cell (bx, by) is the candidate arithmetic with tx = x0, ty = y0.  Candidate (j, iy, ix) scores
+ *   the point at cell (bx + (ix - half_x)*step_cells, by + (iy - half_y)*step_cells): the scan is shifted by WHOLE CELLS (the
+ *   correlative matcher's trick; this is the contract, and not the same as the score at x0 + k*resolution after rounding).  A
+ *   point whose base cell is OUTSIDE by the size rule is outside for every shift.  index = (j*Ny + iy)*Nx + ix; the best is
+ *   the greatest score, equal scores go to the lowest index, found with integer maxima over the 64-bit key
+ *   (score << 32) | (0xFFFFFFFF - index): no floating point anywhere.
+ *
+ * THE OBJECT.  lfx_grid_match_create allocates everything on the device: S, the largest table, [max_scans][max_beams] points
+ *   and their counts, the search's keys and a ring of rotation tables; no later call allocates device memory.  Calls are
+ *   ordered through one event behind the object's last call, whatever streams they were given (the keyframe store's rule, with
+ *   the same promises about caller-owned buffers).  LFX_ERR_INVALID_ARGUMENT and LFX_ERR_CAPACITY are returned before anything
+ *   is queued and leave the object as it was.
+ *
+ * LIMITS.  The search is exhaustive: no multi-resolution branch and bound.  Translation moves in whole cells times step_cells;
+ * sub-cell refinement is the caller's, or the 3-D alignment's that follows.  Only HIT beams score: free-space evidence is
+ * unused.  The level is fixed per scan.  One field per object. */
+#define LFX_GRID_MATCH_MAX_CELLS 64
+#define LFX_GRID_MATCH_MAX_HALF 256
+#define LFX_GRID_MATCH_MAX_HALF_THETA 180
+typedef struct lfx_grid_match lfx_grid_match;
+typedef struct lfx_grid_match_config {
+  uint32_t width, height;       /* cells; the caller sets them; 1 .. 16384 */
+  float resolution;             /* metres per cell; the caller sets it; finite, > 0 */
+  uint32_t max_scans;           /* 64; 1 .. 1024 */
+  uint32_t max_beams;           /* 1800; 4 .. 4096 */
+  uint32_t max_half_x, max_half_y;   /* 50, 50; 0 .. 256 cells */
+  uint32_t max_half_theta;      /* 30; 0 .. 180 steps */
+  double origin_x, origin_y;    /* the caller sets them; finite */
+} lfx_grid_match_config;
+typedef struct lfx_grid_match_table_config {
+  float sigma;                  /* 0.2; finite, > 0 */
+  float max_distance;           /* 2.0 (AMCL's laser_likelihood_max_dist); finite, >= 0 */
+  uint32_t peak;                /* 1000; 1 .. 65535 */
+  uint32_t reserved;            /* 0 */
+} lfx_grid_match_table_config;
+typedef struct lfx_grid_match_search_config {
+  uint32_t half_x, half_y;      /* 10, 10; cells, within the object's maxima */
+  uint32_t step_cells;          /* 1; 1 .. 16 */
+  uint32_t half_theta;          /* 0; within the object's maximum */
+  double theta_step;            /* 0.0; finite and > 0 unless half_theta == 0 */
+} lfx_grid_match_search_config;
+typedef struct lfx_grid_match_info_t {
+  uint32_t width, height, max_scans, max_beams, max_half_x, max_half_y, max_half_theta;
+  uint32_t field_set;           /* whether lfx_grid_match_set_field has run; table_cells is its table's Rs */
+  uint32_t table_cells;
+  uint32_t n_scans, n_beams;    /* of the last lfx_grid_match_set_scans*; 0 before any */
+  uint32_t reserved;
+  uint64_t device_bytes;        /* everything lfx_grid_match_create allocated on the device */
+} lfx_grid_match_info_t;
+typedef struct lfx_grid_match_view_t {
+  const uint16_t *field;        /* device [height][width] */
+  const double *points;         /* device [max_scans][max_beams][2]: scan s's first n_points[s] pairs */
+  const uint32_t *n_points;     /* device [max_scans] */
+} lfx_grid_match_view_t;
+void lfx_grid_match_default_config(lfx_grid_match_config *config);
+void lfx_grid_match_table_default_config(lfx_grid_match_table_config *config);
+void lfx_grid_match_search_default_config(lfx_grid_match_search_config *config);
+/* host only, no context: n = Rs*Rs + 1.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, a field outside the ranges above, a
+ * resolution that is not finite and > 0, Rs above LFX_GRID_MATCH_MAX_CELLS. */
+int lfx_grid_match_table_size(const lfx_grid_match_table_config *config, float resolution, uint32_t *n);
+/* host only, no context: the table.  LFX_ERR_INVALID_ARGUMENT as above, and n that is not lfx_grid_match_table_size's. */
+int lfx_grid_match_table(const lfx_grid_match_table_config *config, float resolution, uint16_t *lut /*[n]*/, uint32_t n);
+/* host only: dims = {Nx, Ny, T}.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, half_x or half_y above LFX_GRID_MATCH_MAX_HALF,
+ * half_theta above LFX_GRID_MATCH_MAX_HALF_THETA, step_cells outside 1 .. 16, with half_theta > 0 a theta_step that is not
+ * finite and > 0. */
+int lfx_grid_match_search_size(const lfx_grid_match_search_config *search, uint32_t dims[3]);
+/* host only: the search's rotations, cs [2*half_theta + 1][2] = {cos, sin} of angle_j.  LFX_ERR_INVALID_ARGUMENT: NULL cs, a
+ * yaw0 that is not finite, half_theta above the maximum, with half_theta > 0 a theta_step that is not finite and > 0. */
+int lfx_grid_match_rotations(double yaw0, uint32_t half_theta, double theta_step, double *cs);
+/* host only: the pose of candidate `index` of a search around centre {x0, y0, yaw0}: pose2 = {x0 + (double)((ix - half_x) *
+ * step_cells) * (double)resolution, y0 + (double)((iy - half_y) * step_cells) * (double)resolution, angle_j}.
+ * LFX_ERR_INVALID_ARGUMENT: what lfx_grid_match_search_size refuses, an index that is not below T*Ny*Nx, a resolution or a
+ * centre that is not finite. */
+int lfx_grid_match_candidate(const lfx_grid_match_search_config *search, float resolution, const double centre[3], uint32_t index,
+                             double pose2[3]);
+/* host only: pose [3][4] = [Rz(yaw) x level | (x, y, z)] of pose2 = {x, y, yaw}; level [9] row-major or NULL = identity.  The
+ * initial pose lfx_localize_batch asks for.  Each element of the product is ((a*b + c*d) + e*f) in this order. */
+int lfx_grid_match_pose3(const double pose2[3], const double *level, double z, double pose[12]);
+/* A config outside the ranges above: LFX_ERR_INVALID_ARGUMENT; a failed allocation: LFX_ERR_OUT_OF_MEMORY with nothing left
+ * allocated. */
+int lfx_grid_match_create(lfx_ctx *ctx, const lfx_grid_match_config *config, lfx_grid_match **out);
+void lfx_grid_match_destroy(lfx_grid_match *matcher);
+int lfx_grid_match_info(const lfx_grid_match *matcher, lfx_grid_match_info_t *info);
+/* The device arrays, current behind `stream`. */
+int lfx_grid_match_view(lfx_ctx *ctx, const lfx_grid_match *matcher, lfx_grid_match_view_t *view, void *stream);
+/* S from the field's d2 and the table lut [n] (host); asynchronous.  The field is read behind its own event, which moves behind
+ * the read (the store's rule for a reader); the table goes up from a pinned block of the object's, after a wait for the
+ * object's last call.  LFX_ERR_INVALID_ARGUMENT: NULL arguments, a field whose sides are not the matcher's, a field without a
+ * transform, n that is not Rs*Rs + 1 for an Rs in 0 .. 64, a last transform with 0 < max_cells < Rs. */
+int lfx_grid_match_set_field(lfx_ctx *ctx, lfx_grid_match *matcher, lfx_distance *field, const uint16_t *lut, uint32_t n, void *stream);
+/* Scans 0 .. n_scans - 1 of the object from d_beams, device [n_scans][n_beams][4] as lfx_occupancy_view_t.beams, read behind
+ * `stream`; levels host [n_scans][9] or NULL = identity (not inspected).  Replaces every scan the object held; asynchronous.
+ * LFX_ERR_INVALID_ARGUMENT: NULL arguments, n_scans 0, n_beams 0; LFX_ERR_CAPACITY: n_scans above max_scans, n_beams above
+ * max_beams. */
+int lfx_grid_match_set_scans(lfx_ctx *ctx, lfx_grid_match *matcher, const float *d_beams, uint32_t n_scans, uint32_t n_beams,
+                             const double *levels, void *stream);
+/* The same of an occupancy store's scans [first, first + count), the levels the rotations of the poses the store holds now
+ * (use_rotation 0: identity).  Ordered behind the store's last call, whose event moves behind this read. */
+int lfx_grid_match_set_scans_occupancy(lfx_ctx *ctx, lfx_grid_match *matcher, lfx_occupancy *grid, uint32_t first, uint32_t count,
+                                       int use_rotation, void *stream);
+/* score and inside of scan `scan` at the P candidates d_candidates, device double [P][4] = {tx, ty, c, s}, to d_score uint32
+ * [P] and d_inside uint32 [P] (may be NULL), all device memory; 1 <= P <= 2^24; asynchronous.  LFX_ERR_INVALID_ARGUMENT also: no
+ * field yet, a scan that is not set. */
+int lfx_grid_match_score(lfx_ctx *ctx, lfx_grid_match *matcher, uint32_t scan, const double *d_candidates, uint32_t n_candidates,
+                         uint32_t *d_score, uint32_t *d_inside, void *stream);
+/* The window of `search` around centres host [n_scans][3] = {x0, y0, yaw0}, one per scan of [first, first + n_scans); outputs
+ * on the device: d_best uint32 [n_scans][4] = {score, index, inside, n_points}; d_slice_best (may be NULL) uint32 [n_scans][T][2]
+ * = {score, index}, the best of each heading under the same tie rule; d_volume (may be NULL) uint32 [n_scans][T][Ny][Nx].
+ * Asynchronous; the rotations go up through a ring of pinned blocks of the object's.  LFX_ERR_INVALID_ARGUMENT also: no field
+ * yet, scans that are not set, a centre that is not finite, what lfx_grid_match_search_size refuses; LFX_ERR_CAPACITY: a
+ * window beyond the object's maxima. */
+int lfx_grid_match_search(lfx_ctx *ctx, lfx_grid_match *matcher, uint32_t first, uint32_t n_scans, const double *centres,
+                          const lfx_grid_match_search_config *search, uint32_t *d_best, uint32_t *d_slice_best, uint32_t *d_volume,
+                          void *stream);
 
 /* --- per-stage entry points (device-backed mirrors of the reference's free functions) ----- */
 /* One ring given as angle-sorted x[n], y[n] host arrays; every stage runs the same device

@@ -10,6 +10,7 @@
 #ifndef LFX_HPP_
 #define LFX_HPP_
 
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -1232,6 +1233,8 @@ public:
     return out;
   }
   void Clear(void * stream = nullptr) {Check(lfx_occupancy_clear(fx_.handle(), grid_, stream));}
+  // drops the kept scans from n_scans on (the counts stay): a small grid as the reducer of live scans starts every batch with Truncate(0)
+  void Truncate(std::uint32_t n_scans, void * stream = nullptr) {Check(lfx_occupancy_truncate(fx_.handle(), grid_, n_scans, stream));}
   void Render(std::uint32_t first, std::uint32_t count, void * stream = nullptr) {Check(lfx_occupancy_render(fx_.handle(), grid_, first, count, stream));}
   // a full re-render: every kept scan at its current pose
   void RenderAll(void * stream = nullptr)
@@ -1348,6 +1351,101 @@ private:
   }
   const FeatureExtraction & fx_;
   lfx_distance * field_ = nullptr;
+};
+
+// A scan matcher over an occupancy grid (lfx_grid_match) on the device of `fx`, which must outlive it: SetField takes a
+// DistanceField's last transform through a score table, SetScans an OccupancyGrid's kept scans; Score rates arbitrary
+// candidate poses (a particle filter's measurement update), Search a window of whole-cell shifts and headings around a centre
+// (relocalisation, tracking, a 2-D loop check).  Candidate and Pose3 turn the index found into the initial pose the 3-D
+// alignment asks for.  Outputs go to device memory or a pinned block (FeatureExtraction::PinnedFloats), read behind `stream`.
+class GridMatcher
+{
+public:
+  struct Best {std::uint32_t score, index, inside, n_points;};
+  static lfx_grid_match_config DefaultConfig() {lfx_grid_match_config c; lfx_grid_match_default_config(&c); return c;}
+  static lfx_grid_match_table_config DefaultTableConfig() {lfx_grid_match_table_config c; lfx_grid_match_table_default_config(&c); return c;}
+  static lfx_grid_match_search_config DefaultSearchConfig() {lfx_grid_match_search_config c; lfx_grid_match_search_default_config(&c); return c;}
+  // lfx_grid_match_table: the values the field kernel is handed (host only)
+  static std::vector<std::uint16_t> Table(const lfx_grid_match_table_config & config, float resolution)
+  {
+    std::uint32_t n = 0;
+    if (lfx_grid_match_table_size(&config, resolution, &n) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "the score table config is refused");}
+    std::vector<std::uint16_t> lut(n);
+    if (lfx_grid_match_table(&config, resolution, lut.data(), n) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "the score table config is refused");}
+    return lut;
+  }
+  // {x, y, yaw} of candidate `index` of a search around `centre` (host only)
+  static std::array<double, 3> Candidate(const lfx_grid_match_search_config & search, float resolution, const std::array<double, 3> & centre, std::uint32_t index)
+  {
+    std::array<double, 3> pose2{};
+    if (lfx_grid_match_candidate(&search, resolution, centre.data(), index, pose2.data()) != LFX_OK) {throw Error(LFX_ERR_INVALID_ARGUMENT, "no such candidate");}
+    return pose2;
+  }
+  // [Rz(yaw) x level | (x, y, z)], 12 doubles; level: 9 doubles or null = identity (host only)
+  static std::array<double, 12> Pose3(const std::array<double, 3> & pose2, const double * level = nullptr, double z = 0.0)
+  {
+    std::array<double, 12> pose{};
+    lfx_grid_match_pose3(pose2.data(), level, z, pose.data());
+    return pose;
+  }
+  // config: DefaultConfig() with width, height, resolution, origin_x and origin_y set
+  GridMatcher(const FeatureExtraction & fx, const lfx_grid_match_config & config)
+  : fx_(fx), config_(config)
+  {
+    Check(lfx_grid_match_create(fx.handle(), &config, &matcher_));
+  }
+  ~GridMatcher() {lfx_grid_match_destroy(matcher_);}
+  GridMatcher(const GridMatcher &) = delete;
+  GridMatcher & operator=(const GridMatcher &) = delete;
+
+  void SetField(DistanceField & field, const std::vector<std::uint16_t> & lut, void * stream = nullptr)
+  {
+    Check(lfx_grid_match_set_field(fx_.handle(), matcher_, field.handle(), lut.data(), static_cast<std::uint32_t>(lut.size()), stream));
+  }
+  void SetField(DistanceField & field, const lfx_grid_match_table_config & table = DefaultTableConfig(), void * stream = nullptr)
+  {
+    SetField(field, Table(table, config_.resolution), stream);
+  }
+  // the store's scans [first, first + count), levelled by the rotations of the poses it holds now (use_rotation) or not at all
+  void SetScans(OccupancyGrid & grid, std::uint32_t first, std::uint32_t count, bool use_rotation = true, void * stream = nullptr)
+  {
+    Check(lfx_grid_match_set_scans_occupancy(fx_.handle(), matcher_, grid.handle(), first, count, use_rotation ? 1 : 0, stream));
+  }
+  // d_beams: device [n_scans][n_beams][4] as lfx_occupancy_view_t.beams; levels: empty, or 9 doubles per scan
+  void SetScans(const float * d_beams, std::uint32_t n_scans, std::uint32_t n_beams, const std::vector<double> & levels = {}, void * stream = nullptr)
+  {
+    Check(levels.empty() || levels.size() == 9u * static_cast<std::size_t>(n_scans) ?
+      lfx_grid_match_set_scans(fx_.handle(), matcher_, d_beams, n_scans, n_beams, levels.empty() ? nullptr : levels.data(), stream) : LFX_ERR_INVALID_ARGUMENT);
+  }
+  // d_candidates: double [n][4] = {tx, ty, cos, sin}; d_score, d_inside (may be null): uint32 [n]
+  void Score(std::uint32_t scan, const double * d_candidates, std::uint32_t n, std::uint32_t * d_score, std::uint32_t * d_inside = nullptr, void * stream = nullptr)
+  {
+    Check(lfx_grid_match_score(fx_.handle(), matcher_, scan, d_candidates, n, d_score, d_inside, stream));
+  }
+  // centres: {x0, y0, yaw0} per scan of [first, first + centres.size() / 3); d_best: uint32 [n][4]; the others may be null
+  void Search(std::uint32_t first, const std::vector<double> & centres, const lfx_grid_match_search_config & search, std::uint32_t * d_best,
+    std::uint32_t * d_slice_best = nullptr, std::uint32_t * d_volume = nullptr, void * stream = nullptr)
+  {
+    Check(centres.size() % 3u == 0u ? lfx_grid_match_search(fx_.handle(), matcher_, first, static_cast<std::uint32_t>(centres.size() / 3u), centres.data(), &search,
+      d_best, d_slice_best, d_volume, stream) : LFX_ERR_INVALID_ARGUMENT);
+  }
+  lfx_grid_match_info_t Info() const
+  {
+    lfx_grid_match_info_t i;
+    lfx_grid_match_info(matcher_, &i);
+    return i;
+  }
+  const lfx_grid_match_config & Config() const {return config_;}
+  lfx_grid_match * handle() const {return matcher_;}
+
+private:
+  void Check(int rc) const
+  {
+    if (rc != LFX_OK) {throw Error(rc, lfx_last_error(fx_.handle()));}
+  }
+  const FeatureExtraction & fx_;
+  lfx_grid_match_config config_;
+  lfx_grid_match * matcher_ = nullptr;
 };
 
 // Visibility votes (lfx_visibility): which records of a window of a Keyframes store's keyframes were looked through by the

@@ -18,4 +18,6 @@ from .extraction import Visibility, visibility_config, visibility_tables  # noqa
 from .extraction import VoxelFilter  # noqa: F401
 from .extraction import OccupancyGrid, occupancy_config, occupancy_tables, occupancy_emit_config, occupancy_emit_table, write_occupancy_map  # noqa: F401
 from .extraction import DistanceField, distance_config, distance_cost_config, distance_cost_table  # noqa: F401
+from .extraction import GridMatcher, grid_match_config, grid_match_table_config, grid_match_search_config, grid_match_table  # noqa: F401
+from .extraction import grid_match_search_size, grid_match_rotations, grid_match_candidate, grid_match_pose3  # noqa: F401
 from .synth import POINT_DTYPE, SENSORS, make_scan, make_batch, make_sequence, make_sweep, make_sweep_trajectory, concat  # noqa: F401

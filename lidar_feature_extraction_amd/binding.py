@@ -350,6 +350,34 @@ class DistanceStats(C.Structure):
 DISTANCE_FAR = 0xFFFFFFFF
 DISTANCE_FREE, DISTANCE_UNKNOWN, DISTANCE_OBSTACLE = 0, 1, 2
 DISTANCE_MAX_COST_CELLS = 1024
+
+
+class GridMatchConfig(C.Structure):
+    """lfx_grid_match_config: the grid's geometry (lfx_distance carries none), the scans the object holds and the largest window."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_float), ("max_scans", C.c_uint32), ("max_beams", C.c_uint32),
+                ("max_half_x", C.c_uint32), ("max_half_y", C.c_uint32), ("max_half_theta", C.c_uint32), ("origin_x", C.c_double), ("origin_y", C.c_double)]
+
+
+class GridMatchTableConfig(C.Structure):
+    """lfx_grid_match_table_config: the likelihood field's Gaussian -- sigma and reach in metres, the score of distance 0."""
+    _fields_ = [("sigma", C.c_float), ("max_distance", C.c_float), ("peak", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GridMatchSearchConfig(C.Structure):
+    """lfx_grid_match_search_config: the window -- half sides in candidates, the cells between two, headings either side and their step."""
+    _fields_ = [("half_x", C.c_uint32), ("half_y", C.c_uint32), ("step_cells", C.c_uint32), ("half_theta", C.c_uint32), ("theta_step", C.c_double)]
+
+
+class GridMatchInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "max_scans", "max_beams", "max_half_x", "max_half_y", "max_half_theta", "field_set",
+                                          "table_cells", "n_scans", "n_beams", "reserved")] + [("device_bytes", C.c_uint64)]
+
+
+class GridMatchView(C.Structure):
+    _fields_ = [("field", C.c_void_p), ("points", C.c_void_p), ("n_points", C.c_void_p)]
+
+
+GRID_MATCH_MAX_CELLS, GRID_MATCH_MAX_HALF, GRID_MATCH_MAX_HALF_THETA = 64, 256, 180
 OCCUPANCY_MAX_BEAMS, OCCUPANCY_MAX_SIDE = 4096, 16384
 
 
@@ -463,11 +491,15 @@ EXPORTS = [
     "lfx_voxel_filter_add", "lfx_voxel_filter_add_host", "lfx_voxel_filter_emit", "lfx_voxel_filter_add_keyframes", "lfx_keyframes_save_filtered",
     "lfx_occupancy_default_config", "lfx_occupancy_tables", "lfx_occupancy_emit_default_config", "lfx_occupancy_emit_table",
     "lfx_occupancy_create", "lfx_occupancy_destroy", "lfx_occupancy_info", "lfx_occupancy_view", "lfx_occupancy_add_batch",
-    "lfx_occupancy_set_poses", "lfx_occupancy_poses", "lfx_occupancy_follow", "lfx_occupancy_clear", "lfx_occupancy_render",
+    "lfx_occupancy_set_poses", "lfx_occupancy_poses", "lfx_occupancy_follow", "lfx_occupancy_truncate", "lfx_occupancy_clear", "lfx_occupancy_render",
     "lfx_occupancy_counters", "lfx_occupancy_emit", "lfx_occupancy_write_map", "lfx_occupancy_save",
     "lfx_distance_default_config", "lfx_distance_cost_default_config", "lfx_distance_cost_table_size", "lfx_distance_cost_table",
     "lfx_distance_create", "lfx_distance_destroy", "lfx_distance_info", "lfx_distance_from_grid", "lfx_distance_from_occupancy",
     "lfx_distance_view", "lfx_distance_metres", "lfx_distance_costmap", "lfx_distance_stats",
+    "lfx_grid_match_default_config", "lfx_grid_match_table_default_config", "lfx_grid_match_search_default_config", "lfx_grid_match_table_size",
+    "lfx_grid_match_table", "lfx_grid_match_search_size", "lfx_grid_match_rotations", "lfx_grid_match_candidate", "lfx_grid_match_pose3",
+    "lfx_grid_match_create", "lfx_grid_match_destroy", "lfx_grid_match_info", "lfx_grid_match_view", "lfx_grid_match_set_field",
+    "lfx_grid_match_set_scans", "lfx_grid_match_set_scans_occupancy", "lfx_grid_match_score", "lfx_grid_match_search",
     "lfx_route_choice", "lfx_set_log_callback", "lfx_box_calibration", "lfx_gather_counts_slot", "lfx_gather_payload2", "lfx_set_ring_ids",
 ]
 """Every symbol include/lfx.h declares (tests/test_abi.py checks the library exports each)."""
@@ -725,6 +757,7 @@ def load(test_hooks=False):
     L.lfx_occupancy_set_poses.argtypes = [vp, vp, u32, u32, vp, vp]
     L.lfx_occupancy_poses.argtypes = [vp, vp, u32, u32, vp, vp]
     L.lfx_occupancy_follow.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.lfx_occupancy_truncate.argtypes = [vp, vp, u32, vp]
     L.lfx_occupancy_clear.argtypes = [vp, vp, vp]
     L.lfx_occupancy_render.argtypes = [vp, vp, u32, u32, vp]
     L.lfx_occupancy_counters.argtypes = [vp, vp, C.POINTER(OccupancyCounters), vp]
@@ -748,6 +781,26 @@ def load(test_hooks=False):
     L.lfx_distance_metres.argtypes = [vp, vp, C.c_float, vp, vp]
     L.lfx_distance_costmap.argtypes = [vp, vp, pdk, C.c_float, vp, vp]
     L.lfx_distance_stats.argtypes = [vp, vp, C.POINTER(DistanceStats), vp]
+    pgc, pgt, pgs = C.POINTER(GridMatchConfig), C.POINTER(GridMatchTableConfig), C.POINTER(GridMatchSearchConfig)
+    for name, ptr in (("lfx_grid_match_default_config", pgc), ("lfx_grid_match_table_default_config", pgt), ("lfx_grid_match_search_default_config", pgs)):
+        getattr(L, name).argtypes = [ptr]
+        getattr(L, name).restype = None
+    L.lfx_grid_match_table_size.argtypes = [pgt, C.c_float, C.POINTER(u32)]
+    L.lfx_grid_match_table.argtypes = [pgt, C.c_float, vp, u32]
+    L.lfx_grid_match_search_size.argtypes = [pgs, C.POINTER(u32)]
+    L.lfx_grid_match_rotations.argtypes = [C.c_double, u32, C.c_double, vp]
+    L.lfx_grid_match_candidate.argtypes = [pgs, C.c_float, vp, u32, vp]
+    L.lfx_grid_match_pose3.argtypes = [vp, vp, C.c_double, vp]
+    L.lfx_grid_match_create.argtypes = [vp, pgc, C.POINTER(vp)]
+    L.lfx_grid_match_destroy.argtypes = [vp]
+    L.lfx_grid_match_destroy.restype = None
+    L.lfx_grid_match_info.argtypes = [vp, C.POINTER(GridMatchInfo)]
+    L.lfx_grid_match_view.argtypes = [vp, vp, C.POINTER(GridMatchView), vp]
+    L.lfx_grid_match_set_field.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.lfx_grid_match_set_scans.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    L.lfx_grid_match_set_scans_occupancy.argtypes = [vp, vp, vp, u32, u32, i32, vp]
+    L.lfx_grid_match_score.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp]
+    L.lfx_grid_match_search.argtypes = [vp, vp, u32, u32, vp, pgs, vp, vp, vp, vp]
     L.lfx_place_db_query_gated.argtypes = [vp, vp, vp, u32, C.POINTER(PlaceGate), vp, C.c_double, u32, C.POINTER(PlaceMatch), C.POINTER(u32), vp]
     plc = C.POINTER(LoopCloserConfig)
     L.lfx_loop_closer_default_config.argtypes = [plc]

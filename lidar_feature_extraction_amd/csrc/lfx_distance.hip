@@ -108,6 +108,21 @@ lfx::DistOutArgs out_args(const lfx_distance * f, const void * out)
 }
 }  // namespace
 
+namespace lfx_host
+{
+DistanceAccess distance_access(const lfx_distance * f)
+{
+  DistanceAccess a;
+  a.device = f->device;
+  a.width = f->W; a.height = f->H;
+  a.transformed = f->transformed;
+  a.cap = f->cap;
+  a.d2 = f->d2.p;
+  a.tail = &f->tail;
+  return a;
+}
+}  // namespace lfx_host
+
 extern "C" {
 
 int lfx_distance_create(lfx_ctx * c, uint32_t width, uint32_t height, lfx_distance ** out)

@@ -660,8 +660,24 @@ struct OccupancyAccess
   const uint32_t * hits = nullptr, * misses = nullptr;
   const int8_t * lut = nullptr;
   const Tail * tail = nullptr;
+  // ... and a reader of its scans (lfx_gridmatch.hip): the beams [n_scans][n_beams] and the poses [n_scans][12]
+  const uint4 * beams = nullptr;
+  const double * poses = nullptr;
+  uint32_t n_scans = 0, n_beams = 0;
 };
 OccupancyAccess occupancy_access(const lfx_occupancy * g);
+// What a reader of a distance field's d2 needs (lfx_distance.hip; the grid matcher's score field is a look-up of it): the
+// array, the last transform's cap and the tail event the reader orders itself behind and moves.
+struct DistanceAccess
+{
+  int device = 0;
+  uint32_t width = 0, height = 0;
+  bool transformed = false;
+  uint32_t cap = 0;
+  const uint32_t * d2 = nullptr;
+  const Tail * tail = nullptr;
+};
+DistanceAccess distance_access(const lfx_distance * f);
 // the emit's table of `config` put on the device as lfx_occupancy_emit puts it (nothing is sent for the config of the call
 // before); LFX_ERR_INVALID_ARGUMENT, before anything is queued: what lfx_occupancy_emit_table refuses
 int occupancy_put_table(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & config, hipStream_t st);

@@ -100,6 +100,8 @@ OccupancyAccess occupancy_access(const lfx_occupancy * g)
   a.hits = g->hits.p; a.misses = g->misses.p;
   a.lut = g->lut.p;
   a.tail = &g->tail;
+  a.beams = g->beams.p; a.poses = g->poses.p;
+  a.n_scans = g->n; a.n_beams = g->cfg.n_beams;
   return a;
 }
 
@@ -301,6 +303,19 @@ int lfx_occupancy_follow(lfx_ctx * c, lfx_occupancy * g, const double * d_poses,
   if (rc != LFX_OK) {return rc;}
   LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, st));
   return g->tail.done(c, st);
+}
+
+int lfx_occupancy_truncate(lfx_ctx * c, lfx_occupancy * g, uint32_t n_scans, void * stream)
+{
+  if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
+  if (n_scans > g->n) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "the occupancy grid holds " + std::to_string(g->n) + " scans: it cannot be truncated to " + std::to_string(n_scans));
+  }
+  // (nothing is queued: the dropped scans' beams and poses stay where they are until an add writes over them, and every add
+  // waits for the object's last call first -- a reader queued before this call still reads what it was promised)
+  g->n = n_scans;
+  return LFX_OK;
 }
 
 int lfx_occupancy_clear(lfx_ctx * c, lfx_occupancy * g, void * stream)

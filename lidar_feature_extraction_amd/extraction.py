@@ -523,6 +523,10 @@ class FeatureExtraction:
         lfx_occupancy_config as keywords."""
         return OccupancyGrid(self, width, height, resolution, origin, max_scans, config, **fields)
 
+    def grid_matcher(self, width, height, resolution, origin=(0.0, 0.0), config=None, **fields):
+        """lfx_grid_match_create: a scan matcher over grids of width x height cells on this context's device."""
+        return GridMatcher(self, width, height, resolution, origin, config, **fields)
+
     def distance_field(self, width, height):
         """lfx_distance_create: a distance field over grids of width x height cells on this context's device."""
         return DistanceField(self, width, height)
@@ -882,6 +886,83 @@ def distance_cost_table(config=None, resolution=0.05, n=None):
     if rc != 0:
         raise B.LfxError(rc, "the distance cost config is refused")
     return lut[:int(n)]
+
+
+def grid_match_config(config=None, **fields):
+    """lfx_grid_match_config: the defaults (64 scans of 1800 beams, windows of up to 101 x 101 cells and 61 headings; the
+    grid's size, resolution and origin are the caller's) with the given fields replaced."""
+    return _config(B.GridMatchConfig, "lfx_grid_match_default_config", "grid match", config, fields)
+
+
+def grid_match_table_config(config=None, **fields):
+    """lfx_grid_match_table_config: AMCL's likelihood field (sigma 0.2 m, reach 2.0 m) at a peak of 1000, with the given fields
+    replaced."""
+    return _config(B.GridMatchTableConfig, "lfx_grid_match_table_default_config", "grid match table", config, fields)
+
+
+def grid_match_search_config(config=None, **fields):
+    """lfx_grid_match_search_config: a window of 21 x 21 cells and one heading, with the given fields replaced."""
+    return _config(B.GridMatchSearchConfig, "lfx_grid_match_search_default_config", "grid match search", config, fields)
+
+
+def grid_match_table(config=None, resolution=0.05, n=None):
+    """lfx_grid_match_table: the uint16 table [Rs * Rs + 1] the field kernel is handed, and the only source of the decay.
+    Host only.  n: the size to ask with (None: lfx_grid_match_table_size's)."""
+    cfg = grid_match_table_config(config)
+    L = B.load()
+    if n is None:
+        size = C.c_uint32(0)
+        rc = L.lfx_grid_match_table_size(C.byref(cfg), float(resolution), C.byref(size))
+        if rc != 0:
+            raise B.LfxError(rc, "the grid match table config is refused")
+        n = int(size.value)
+    lut = np.zeros(max(int(n), 1), np.uint16)
+    rc = L.lfx_grid_match_table(C.byref(cfg), float(resolution), C.c_void_p(lut.ctypes.data), int(n))
+    if rc != 0:
+        raise B.LfxError(rc, "the grid match table config is refused")
+    return lut[:int(n)]
+
+
+def grid_match_search_size(search=None, **fields):
+    """lfx_grid_match_search_size: (Nx, Ny, T) of a search config.  Host only."""
+    cfg = grid_match_search_config(search, **fields)
+    dims = (C.c_uint32 * 3)()
+    rc = B.load().lfx_grid_match_search_size(C.byref(cfg), dims)
+    if rc != 0:
+        raise B.LfxError(rc, "the grid match search config is refused")
+    return tuple(int(v) for v in dims)
+
+
+def grid_match_rotations(yaw0, half_theta, theta_step):
+    """lfx_grid_match_rotations: float64 [2 * half_theta + 1][2] = (cos, sin) of the search's headings, and the only source of
+    them.  Host only."""
+    cs = np.zeros((2 * min(int(half_theta), B.GRID_MATCH_MAX_HALF_THETA) + 1, 2))
+    rc = B.load().lfx_grid_match_rotations(float(yaw0), int(half_theta), float(theta_step), C.c_void_p(cs.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "the rotations are refused")
+    return cs
+
+
+def grid_match_candidate(search, resolution, centre, index):
+    """lfx_grid_match_candidate: (x, y, yaw) of candidate `index` of a search around centre (x0, y0, yaw0).  Host only."""
+    cfg = grid_match_search_config(search)
+    c3, out = np.ascontiguousarray(centre, np.float64).reshape(3), np.zeros(3)
+    rc = B.load().lfx_grid_match_candidate(C.byref(cfg), float(resolution), C.c_void_p(c3.ctypes.data), int(index), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "the candidate is refused")
+    return out
+
+
+def grid_match_pose3(pose2, level=None, z=0.0):
+    """lfx_grid_match_pose3: [Rz(yaw) x level | (x, y, z)] as [3][4] float64 -- the initial pose the 3-D alignment asks for.
+    level: [3][3] or None = identity.  Host only."""
+    p2, out = np.ascontiguousarray(pose2, np.float64).reshape(3), np.zeros(12)
+    lv = None if level is None else np.ascontiguousarray(level, np.float64).reshape(9)
+    rc = B.load().lfx_grid_match_pose3(C.c_void_p(p2.ctypes.data), C.c_void_p(lv.ctypes.data if lv is not None else None), float(z),
+                                       C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise B.LfxError(rc, "the pose is refused")
+    return out.reshape(3, 4)
 
 
 def write_occupancy_map(dirname, grid, resolution, origin=(0.0, 0.0), occupied_percent=65, free_percent=25):
@@ -2067,6 +2148,11 @@ class OccupancyGrid(_Handle):
             count = len(self) - int(first) if count is None else int(count)
         self._check(self._L.lfx_occupancy_follow(self._fx._ctx, self.handle, C.c_void_p(ptr), int(first), count, C.c_void_p(int(stream))))
 
+    def truncate(self, n_scans=0, stream=0):
+        """lfx_occupancy_truncate: the kept scans from n_scans on are dropped (the counts stay) -- a grid of 1 x 1 cells as the
+        reducer of live scans starts every batch with truncate(0)."""
+        self._check(self._L.lfx_occupancy_truncate(self._fx._ctx, self.handle, int(n_scans), C.c_void_p(int(stream))))
+
     def clear(self, stream=0):
         self._check(self._L.lfx_occupancy_clear(self._fx._ctx, self.handle, C.c_void_p(int(stream))))
 
@@ -2206,6 +2292,123 @@ class DistanceField(_Handle):
             n = self.width * self.height * np.dtype(dtype).itemsize
             return _device_bytes(ptr, n, self._fx.device, self).cpu().numpy().view(dtype).reshape(shape).copy()
         return get(v["classes"], np.uint8), get(v["d2"], np.uint32), (get(v["i2"], np.uint32) if v["i2"] else None)
+
+
+class GridMatcher(_Handle):
+    """lfx_grid_match: where a scan is in an occupancy grid (include/lfx.h, the grid-match section).  set_field turns a
+    DistanceField's last transform into a score field through a table, set_scans keeps scans as levelled 2-D points; score
+    rates arbitrary candidate poses, search a window of whole-cell shifts and headings around a centre.  Outputs are uint32
+    device tensors."""
+
+    _destroy = "lfx_grid_match_destroy"
+
+    def __init__(self, fx, width, height, resolution, origin=(0.0, 0.0), config=None, **fields):
+        self._fx = fx
+        self._L = fx._L
+        cfg = grid_match_config(config, **dict(dict(width=int(width), height=int(height), resolution=float(resolution), origin_x=float(origin[0]),
+                                                    origin_y=float(origin[1])), **fields))
+        h = C.c_void_p()
+        B.check(fx._ctx, self._L.lfx_grid_match_create(fx._ctx, C.byref(cfg), C.byref(h)), self._L)
+        self.handle = h
+        self.config = cfg
+
+    def info(self):
+        i = B.GridMatchInfo()
+        self._check(self._L.lfx_grid_match_info(self.handle, C.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in B.GridMatchInfo._fields_ if n != "reserved"}
+
+    def view(self, stream=0):
+        """lfx_grid_match_view: the device addresses of the field, the points and their counts, current behind `stream`."""
+        v = B.GridMatchView()
+        self._check(self._L.lfx_grid_match_view(self._fx._ctx, self.handle, C.byref(v), C.c_void_p(int(stream))))
+        return dict(field=v.field or 0, points=v.points or 0, n_points=v.n_points or 0)
+
+    def set_field(self, field, table=None, stream=0, **fields):
+        """lfx_grid_match_set_field: the score field of a DistanceField's last transform.  table: None or a dict (the fields of
+        lfx_grid_match_table_config, the table made at the matcher's resolution), or a uint16 array handed as it is."""
+        if table is None or isinstance(table, (dict, B.GridMatchTableConfig)):
+            lut = grid_match_table(grid_match_table_config(table, **fields), float(self.config.resolution))
+        else:
+            lut = np.ascontiguousarray(table, np.uint16).reshape(-1)
+        self._check(self._L.lfx_grid_match_set_field(self._fx._ctx, self.handle, field.handle, C.c_void_p(lut.ctypes.data if len(lut) else None), len(lut),
+                                                     C.c_void_p(int(stream))))
+
+    def set_scans(self, beams, n_scans=None, n_beams=None, levels=None, stream=0):
+        """lfx_grid_match_set_scans: scans 0 .. n - 1 from beams -- a float32 device tensor [n][W][4] as OccupancyGrid.view()'s, or
+        the address of one with n_scans and n_beams; levels: None or [n][3][3] float64."""
+        if hasattr(beams, "data_ptr"):
+            if beams.dim() != 3 or beams.shape[2] != 4 or beams.element_size() != 4 or not beams.is_contiguous():
+                raise ValueError("the beams are a contiguous float32 tensor [n][W][4]")
+            n_scans, n_beams = int(beams.shape[0]), int(beams.shape[1])
+            beams = beams.data_ptr()
+        lv = None if levels is None else np.ascontiguousarray(levels, np.float64).reshape(-1, 9)
+        if lv is not None and len(lv) != int(n_scans):
+            raise ValueError("levels must hold one matrix per scan")
+        self._check(self._L.lfx_grid_match_set_scans(self._fx._ctx, self.handle, C.c_void_p(int(beams) or None), int(n_scans), int(n_beams),
+                                                     C.c_void_p(lv.ctypes.data if lv is not None and len(lv) else None), C.c_void_p(int(stream))))
+
+    def set_scans_occupancy(self, occupancy, first=0, count=None, use_rotation=True, stream=0):
+        """lfx_grid_match_set_scans_occupancy: an OccupancyGrid's scans [first, first + count), levelled by the rotations of the
+        poses it holds now (use_rotation) or not at all."""
+        count = len(occupancy) - int(first) if count is None else int(count)
+        self._check(self._L.lfx_grid_match_set_scans_occupancy(self._fx._ctx, self.handle, occupancy.handle, int(first), count, int(bool(use_rotation)),
+                                                               C.c_void_p(int(stream))))
+
+    def _new(self, shape):
+        import torch
+        return torch.empty(shape, dtype=torch.int32, device=torch.device("cuda", self._fx.device))
+
+    def score(self, scan, candidates, inside=True, stream=0):
+        """lfx_grid_match_score: candidates float64 [P][4] = (tx, ty, cos, sin), a device tensor or a host array (uploaded on the
+        current stream); (score, inside) int32 device tensors [P] holding uint32 bits (inside None if not asked for)."""
+        import torch
+        if not hasattr(candidates, "data_ptr"):
+            candidates = torch.from_numpy(np.ascontiguousarray(candidates, np.float64).reshape(-1, 4)).to(torch.device("cuda", self._fx.device))
+        if candidates.dim() != 2 or candidates.shape[1] != 4 or candidates.element_size() != 8 or not candidates.is_contiguous():
+            raise ValueError("the candidates are a contiguous float64 tensor [P][4]")
+        P = int(candidates.shape[0])
+        sc, ins = self._new((P,)), (self._new((P,)) if inside else None)
+        self._check(self._L.lfx_grid_match_score(self._fx._ctx, self.handle, int(scan), C.c_void_p(candidates.data_ptr() or None), P,
+                                                 C.c_void_p(sc.data_ptr() or None), C.c_void_p(ins.data_ptr() if ins is not None else None),
+                                                 C.c_void_p(int(stream))))
+        return sc, ins
+
+    def search(self, centres, search=None, first=0, slice_best=False, volume=False, stream=0, **fields):
+        """lfx_grid_match_search: centres [n][3] = (x0, y0, yaw0), one per scan of [first, first + n); (best [n][4] = score,
+        index, inside, n_points; slice_best [n][T][2] or None; volume [n][T][Ny][Nx] or None), int32 device tensors holding
+        uint32 bits."""
+        cfg = grid_match_search_config(search, **fields)
+        cs = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+        n = len(cs)
+        Nx, Ny, T = 2 * int(cfg.half_x) + 1, 2 * int(cfg.half_y) + 1, 2 * int(cfg.half_theta) + 1
+        big = max(int(cfg.half_x), int(cfg.half_y)) > B.GRID_MATCH_MAX_HALF or int(cfg.half_theta) > B.GRID_MATCH_MAX_HALF_THETA
+        best = self._new((n, 4))
+        sl = self._new((n, T, 2)) if slice_best and not big else None
+        vol = self._new((n, T, Ny, Nx)) if volume and not big else None
+        self._check(self._L.lfx_grid_match_search(self._fx._ctx, self.handle, int(first), n, C.c_void_p(cs.ctypes.data if n else None), C.byref(cfg),
+                                                  C.c_void_p(best.data_ptr() or None), C.c_void_p(sl.data_ptr() if sl is not None else None),
+                                                  C.c_void_p(vol.data_ptr() if vol is not None else None), C.c_void_p(int(stream))))
+        return best, sl, vol
+
+    def field(self, stream=0):
+        """The score field on the host, uint16 [height][width]."""
+        import torch
+        v = self.view(stream)
+        torch.cuda.synchronize(self._fx.device)              # (a read-back for inspection: everything queued has landed)
+        h, w = int(self.config.height), int(self.config.width)
+        return _device_bytes(v["field"], 2 * h * w, self._fx.device, self).cpu().numpy().view(np.uint16).reshape(h, w).copy()
+
+    def points(self, stream=0):
+        """The kept points on the host: a list of float64 [n_points[s]][2], one per scan set."""
+        import torch
+        v = self.view(stream)
+        torch.cuda.synchronize(self._fx.device)
+        n, B_ = self.info()["n_scans"], int(self.config.max_beams)
+        if n == 0:
+            return []
+        counts = _device_bytes(v["n_points"], 4 * n, self._fx.device, self).cpu().numpy().view(np.uint32)
+        pts = _device_bytes(v["points"], 16 * n * B_, self._fx.device, self).cpu().numpy().view(np.float64).reshape(n, B_, 2)
+        return [pts[s, :int(counts[s])].copy() for s in range(n)]
 
 
 class Visibility(_Handle):
