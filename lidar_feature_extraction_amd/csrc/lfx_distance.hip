@@ -129,9 +129,7 @@ int lfx_distance_create(lfx_ctx * c, uint32_t width, uint32_t height, lfx_distan
 {
   if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "out is required");}
-  if (width < 1u || width > LFX_OCCUPANCY_MAX_SIDE || height < 1u || height > LFX_OCCUPANCY_MAX_SIDE) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "a distance field has width and height in 1 .. 16384");
-  }
+  if (!grid_sides_ok(width, height)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a distance field has width and height in 1 .. 16384");}
   LFX_HIP(c, hipSetDevice(c->device));
   lfx_distance * f = new (std::nothrow) lfx_distance();
   if (!f) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the distance field");}
@@ -140,16 +138,11 @@ int lfx_distance_create(lfx_ctx * c, uint32_t width, uint32_t height, lfx_distan
   f->segments = (height + lfx::kDistSegRows - 1u) / lfx::kDistSegRows;
   const size_t cells = (size_t)width * height, cols = (size_t)f->segments * width;
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_distance_destroy(f); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(f->cls, cells); get(f->mask, cols); get(f->below, cols); get(f->above, cols); get(f->g, cells); get(f->d2, cells); get(f->i2, cells);
-  get(f->lut, kLutBytes); get(f->stats, lfx::kDistStats);
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the distance field's " + std::to_string(bytes) + " bytes");}
-  f->device_bytes = bytes;
+  DevTotal m;
+  m.get(f->cls, cells); m.get(f->mask, cols); m.get(f->below, cols); m.get(f->above, cols); m.get(f->g, cells); m.get(f->d2, cells); m.get(f->i2, cells);
+  m.get(f->lut, kLutBytes); m.get(f->stats, lfx::kDistStats);
+  if (!m.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, m.refusal("the distance field"));}
+  f->device_bytes = m.bytes;
   if (hipMemset(f->stats.p, 0, sizeof(unsigned long long) * lfx::kDistStats) != hipSuccess) {return give_up(LFX_ERR_HIP, "cannot clear the distance field");}
   if (f->upload.reserve(kLutBytes) != hipSuccess || f->readback.reserve(sizeof(lfx_distance_stats_t)) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the distance field's pinned blocks");
@@ -164,12 +157,7 @@ int lfx_distance_create(lfx_ctx * c, uint32_t width, uint32_t height, lfx_distan
   return LFX_OK;
 }
 
-void lfx_distance_destroy(lfx_distance * f)
-{
-  if (!f) {return;}
-  (void)hipSetDevice(f->device);
-  delete f;
-}
+void lfx_distance_destroy(lfx_distance * f) {destroy_on(f);}
 
 int lfx_distance_info(const lfx_distance * f, lfx_distance_info_t * info)
 {
@@ -189,15 +177,13 @@ int lfx_distance_from_grid(lfx_ctx * c, lfx_distance * f, const int8_t * d_grid,
   if (!c || !f || !d_grid || !config) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_field(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!config_ok(*config)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, kConfigRefused);}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
   lfx::DistClassifyArgs a{};
   a.grid = d_grid;
-  rc = transform<false>(c, f, a, *config, st);
-  if (rc != LFX_OK) {return rc;}
-  return f->tail.done(c, st);
+  LFX_TRY(transform<false>(c, f, a, *config, k.st));
+  return k.finish();
 }
 
 int lfx_distance_from_occupancy(lfx_ctx * c, lfx_distance * f, lfx_occupancy * grid, const lfx_occupancy_emit_config * emit_config,
@@ -208,38 +194,25 @@ int lfx_distance_from_occupancy(lfx_ctx * c, lfx_distance * f, lfx_occupancy * g
   if (!config_ok(*config)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, kConfigRefused);}
   const OccupancyAccess src = occupancy_access(grid);
   if (check_device(c, src.device, "the occupancy grid") != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (src.width != f->W || src.height != f->H) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "the occupancy grid is " + std::to_string(src.width) + " x " + std::to_string(src.height) + " cells, the distance field " +
-             std::to_string(f->W) + " x " + std::to_string(f->H));
-  }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = occupancy_put_table(c, grid, *emit_config, st);        // (refuses the emit config before anything is queued)
-  if (rc != LFX_OK) {return rc;}
-  rc = src.tail->order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_same_cells(c, "the occupancy grid", src.width, src.height, "the distance field", f->W, f->H));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(occupancy_put_table(k, grid, *emit_config));            // (refuses the emit config before anything is queued)
+  LFX_TRY(k.behind(*src.tail));
+  LFX_TRY(k.behind(f->tail));
   lfx::DistClassifyArgs a{};
-  a.E.hits = src.hits; a.E.misses = src.misses;
-  a.E.cells = (uint64_t)f->W * f->H;
-  a.E.w_hit = emit_config->w_hit; a.E.w_miss = emit_config->w_miss; a.E.l_min = emit_config->l_min; a.E.l_max = emit_config->l_max;
-  a.E.min_observations = emit_config->min_observations;
-  a.E.lut = src.lut;
-  rc = transform<true>(c, f, a, *config, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = src.tail->done(c, st);                                     // (the counts are read by the first launch; the whole call is behind it)
-  if (rc != LFX_OK) {return rc;}
-  return f->tail.done(c, st);
+  src.emit_args(*emit_config, a.E);
+  LFX_TRY(transform<true>(c, f, a, *config, k.st));
+  return k.finish();            // (the grid's tail too: its counts are read by the first launch; the whole call is behind it)
 }
 
 int lfx_distance_view(lfx_ctx * c, const lfx_distance * f, lfx_distance_view_t * view, void * stream)
 {
   if (!c || !f || !view) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_field(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = f->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(f->tail));
   *view = lfx_distance_view_t{};
   view->classes = f->cls.p;
   view->d2 = f->d2.p;
@@ -253,16 +226,15 @@ int lfx_distance_metres(lfx_ctx * c, lfx_distance * f, float resolution, float *
   if (check_field(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!f->transformed) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the distance field has no transform yet");}
   if (!std::isfinite(resolution) || !(resolution > 0.0f)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the resolution must be finite and > 0");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
   lfx::DistOutArgs a = out_args(f, out);
   a.res = (double)resolution;
   a.metres = out;
-  hipLaunchKernelGGL(lfx::distance_metres_kernel, dim3(blocks_for(a.cells, lfx::kDistThreads)), dim3(lfx::kDistThreads), 0, st, a);
+  hipLaunchKernelGGL(lfx::distance_metres_kernel, dim3(blocks_for(a.cells, lfx::kDistThreads)), dim3(lfx::kDistThreads), 0, k.st, a);
   LFX_HIP(c, hipGetLastError());
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_distance_costmap(lfx_ctx * c, lfx_distance * f, const lfx_distance_cost_config * config, float resolution, uint8_t * out, void * stream)
@@ -280,33 +252,31 @@ int lfx_distance_costmap(lfx_ctx * c, lfx_distance * f, const lfx_distance_cost_
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last transform was capped at " + std::to_string(f->cap) + " cells, the inflation reaches " +
              std::to_string(rc_cells));
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   // the table on the device: the one of the call before is there already (track_unknown is no part of it)
   const bool same = f->lut_n == n && f->lut_res == resolution && f->lut_cfg.inscribed_radius == config->inscribed_radius &&
     f->lut_cfg.inflation_radius == config->inflation_radius && f->lut_cfg.cost_scaling_factor == config->cost_scaling_factor;
   if (!same) {
-    const int rs = f->tail.settle(c);
-    if (rs != LFX_OK) {return rs;}
+    LFX_TRY(k.wait(f->tail));
     if (lfx_distance_cost_table(config, resolution, f->upload.p, n) != LFX_OK) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the cost table is refused");}
     f->lut_n = 0;
-    LFX_HIP(c, hipMemcpyAsync(f->lut.p, f->upload.p, n, hipMemcpyHostToDevice, st));
-    const int rd = f->tail.done(c, st);
-    if (rd != LFX_OK) {return rd;}
+    LFX_TRY(k.take(f->tail));
+    LFX_TRY(send_block(c, f->upload, f->lut.p, nullptr, n, k.st));     // (written in place, into the block lfx_distance_create sized)
+    LFX_TRY(k.record());
     f->lut_cfg = *config;
     f->lut_res = resolution;
     f->lut_n = n;
   }
-  const int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.behind(f->tail));
   lfx::DistOutArgs a = out_args(f, out);
   a.lut = f->lut.p;
   a.rc2 = n - 1u;
   a.track_unknown = config->track_unknown;
   a.cost = out;
-  hipLaunchKernelGGL(lfx::distance_costmap_kernel, dim3(blocks_for((a.cells + 3u) / 4u, lfx::kDistThreads)), dim3(lfx::kDistThreads), 0, st, a);
+  hipLaunchKernelGGL(lfx::distance_costmap_kernel, dim3(blocks_for((a.cells + 3u) / 4u, lfx::kDistThreads)), dim3(lfx::kDistThreads), 0, k.st, a);
   LFX_HIP(c, hipGetLastError());
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_distance_stats(lfx_ctx * c, const lfx_distance * f, lfx_distance_stats_t * stats, void * stream)
@@ -314,12 +284,10 @@ int lfx_distance_stats(lfx_ctx * c, const lfx_distance * f, lfx_distance_stats_t
   if (!c || !f || !stats) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_field(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!f->transformed) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the distance field has no transform yet");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(f->readback.p, f->stats.p, sizeof(*stats), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(f->tail));
+  LFX_TRY(read_block(c, f->readback, f->stats.p, sizeof(*stats), k.st));
   std::memcpy(stats, f->readback.p, sizeof(*stats));
   return LFX_OK;
 }

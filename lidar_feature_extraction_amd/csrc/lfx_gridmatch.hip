@@ -45,7 +45,7 @@ int check_matcher(lfx_ctx * c, const lfx_grid_match * m) {return check_device(c,
 
 bool config_ok(const lfx_grid_match_config & k)
 {
-  if (k.width < 1u || k.width > LFX_OCCUPANCY_MAX_SIDE || k.height < 1u || k.height > LFX_OCCUPANCY_MAX_SIDE) {return false;}
+  if (!grid_sides_ok(k.width, k.height)) {return false;}
   if (!std::isfinite(k.resolution) || !(k.resolution > 0.0f) || !std::isfinite(k.origin_x) || !std::isfinite(k.origin_y)) {return false;}
   if (k.max_scans < 1u || k.max_scans > 1024u || k.max_beams < 4u || k.max_beams > LFX_OCCUPANCY_MAX_BEAMS) {return false;}
   return k.max_half_x <= LFX_GRID_MATCH_MAX_HALF && k.max_half_y <= LFX_GRID_MATCH_MAX_HALF && k.max_half_theta <= LFX_GRID_MATCH_MAX_HALF_THETA;
@@ -87,21 +87,16 @@ int lfx_grid_match_create(lfx_ctx * c, const lfx_grid_match_config * config, lfx
   m->t_max = 2u * config->max_half_theta + 1u;
   const size_t cells = (size_t)config->width * config->height, K = config->max_scans;
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_grid_match_destroy(m); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(m->S, cells); get(m->lut, lfx::kGmMaxTable); get(m->points, K * config->max_beams); get(m->n_points, K); get(m->levels, 9u * K);
-  get(m->keys, K * m->t_max);
-  for (uint32_t k = 0; ok && k < lfx_grid_match::kSlots; k++) {
+  DevTotal t;
+  t.get(m->S, cells); t.get(m->lut, lfx::kGmMaxTable); t.get(m->points, K * config->max_beams); t.get(m->n_points, K); t.get(m->levels, 9u * K);
+  t.get(m->keys, K * m->t_max);
+  for (uint32_t k = 0; t.ok && k < lfx_grid_match::kSlots; k++) {
     hipError_t mem = hipSuccess;
-    ok = m->slots[k].take(c, slot_doubles(config->max_scans, m->t_max), mem) == LFX_OK && mem == hipSuccess;
-    bytes += (uint64_t)m->slots[k].d.n * sizeof(double);
+    t.ok = m->slots[k].take(c, slot_doubles(config->max_scans, m->t_max), mem) == LFX_OK && mem == hipSuccess;
+    t.bytes += (uint64_t)m->slots[k].d.n * sizeof(double);
   }
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the grid matcher's " + std::to_string(bytes) + " bytes");}
-  m->device_bytes = bytes;
+  if (!t.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, t.refusal("the grid matcher"));}
+  m->device_bytes = t.bytes;
   if (hipMemset(m->S.p, 0, sizeof(uint16_t) * cells) != hipSuccess || hipMemset(m->n_points.p, 0, sizeof(uint32_t) * K) != hipSuccess) {
     return give_up(LFX_ERR_HIP, "cannot clear the grid matcher");
   }
@@ -112,12 +107,7 @@ int lfx_grid_match_create(lfx_ctx * c, const lfx_grid_match_config * config, lfx
   return LFX_OK;
 }
 
-void lfx_grid_match_destroy(lfx_grid_match * m)
-{
-  if (!m) {return;}
-  (void)hipSetDevice(m->device);
-  delete m;
-}
+void lfx_grid_match_destroy(lfx_grid_match * m) {destroy_on(m);}
 
 int lfx_grid_match_info(const lfx_grid_match * m, lfx_grid_match_info_t * info)
 {
@@ -137,9 +127,9 @@ int lfx_grid_match_view(lfx_ctx * c, const lfx_grid_match * m, lfx_grid_match_vi
 {
   if (!c || !m || !view) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_matcher(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = m->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(m->tail));
   *view = lfx_grid_match_view_t{};
   view->field = m->S.p;
   view->points = reinterpret_cast<const double *>(m->points.p);
@@ -153,10 +143,7 @@ int lfx_grid_match_set_field(lfx_ctx * c, lfx_grid_match * m, lfx_distance * fie
   if (check_matcher(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const DistanceAccess src = distance_access(field);
   if (check_device(c, src.device, "the distance field") != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  if (src.width != m->cfg.width || src.height != m->cfg.height) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "the distance field is " + std::to_string(src.width) + " x " + std::to_string(src.height) + " cells, the grid matcher " +
-             std::to_string(m->cfg.width) + " x " + std::to_string(m->cfg.height));
-  }
+  LFX_TRY(check_same_cells(c, "the distance field", src.width, src.height, "the grid matcher", m->cfg.width, m->cfg.height));
   if (!src.transformed) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the distance field has no transform yet");}
   uint32_t rs = 0;
   while (rs < LFX_GRID_MATCH_MAX_CELLS && rs * rs + 1u < n) {rs++;}
@@ -164,14 +151,12 @@ int lfx_grid_match_set_field(lfx_ctx * c, lfx_grid_match * m, lfx_distance * fie
   if (src.cap != 0u && src.cap < rs) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last transform was capped at " + std::to_string(src.cap) + " cells, the score table reaches " + std::to_string(rs));
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = m->tail.settle(c);                                     // (the pinned block is rewritten)
-  if (rc != LFX_OK) {return rc;}
-  std::memcpy(m->upload.p, lut, sizeof(uint16_t) * n);
-  rc = src.tail->order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(m->lut.p, m->upload.p, sizeof(uint16_t) * n, hipMemcpyHostToDevice, st));
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(m->tail));                                      // (the pinned block is rewritten)
+  LFX_TRY(k.behind(*src.tail));
+  LFX_TRY(send_block(c, m->upload, m->lut.p, lut, sizeof(uint16_t) * n, st));
   lfx::GmFieldArgs a{};
   a.d2 = src.d2; a.lut = m->lut.p; a.n = n;
   a.cells = (uint64_t)m->cfg.width * m->cfg.height;
@@ -181,9 +166,7 @@ int lfx_grid_match_set_field(lfx_ctx * c, lfx_grid_match * m, lfx_distance * fie
   LFX_HIP(c, hipGetLastError());
   m->field_set = true;
   m->rs = rs;
-  rc = src.tail->done(c, st);
-  if (rc != LFX_OK) {return rc;}
-  return m->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_grid_match_set_scans(lfx_ctx * c, lfx_grid_match * m, const float * d_beams, uint32_t n_scans, uint32_t n_beams, const double * levels, void * stream)
@@ -195,24 +178,20 @@ int lfx_grid_match_set_scans(lfx_ctx * c, lfx_grid_match * m, const float * d_be
     return fail(c, LFX_ERR_CAPACITY, std::to_string(n_scans) + " scans of " + std::to_string(n_beams) + " beams: the grid matcher holds " +
              std::to_string(m->cfg.max_scans) + " of " + std::to_string(m->cfg.max_beams));
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   lfx::GmScanArgs a{};
   a.beams = reinterpret_cast<const uint4 *>(d_beams);
   a.W = n_beams;
   if (levels) {
-    int rc = m->tail.settle(c);                                   // (the pinned block is rewritten)
-    if (rc != LFX_OK) {return rc;}
-    std::memcpy(m->upload.p, levels, sizeof(double) * 9u * n_scans);
-    LFX_HIP(c, hipMemcpyAsync(m->levels.p, m->upload.p, sizeof(double) * 9u * n_scans, hipMemcpyHostToDevice, st));
+    LFX_TRY(k.after(m->tail));                                    // (the pinned block is rewritten)
+    LFX_TRY(send_block(c, m->upload, m->levels.p, levels, sizeof(double) * 9u * n_scans, k.st));
     a.lev = m->levels.p; a.lev_stride = 9u; a.row_stride = 3u;
   } else {
-    const int rc = m->tail.order_behind(c, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(k.behind(m->tail));
   }
-  const int rc = launch_scans(c, m, a, n_scans, st);
-  if (rc != LFX_OK) {return rc;}
-  return m->tail.done(c, st);
+  LFX_TRY(launch_scans(c, m, a, n_scans, k.st));
+  return k.finish();
 }
 
 int lfx_grid_match_set_scans_occupancy(lfx_ctx * c, lfx_grid_match * m, lfx_occupancy * grid, uint32_t first, uint32_t count, int use_rotation, void * stream)
@@ -226,21 +205,16 @@ int lfx_grid_match_set_scans_occupancy(lfx_ctx * c, lfx_grid_match * m, lfx_occu
     return fail(c, LFX_ERR_CAPACITY, std::to_string(count) + " scans of " + std::to_string(src.n_beams) + " beams: the grid matcher holds " +
              std::to_string(m->cfg.max_scans) + " of " + std::to_string(m->cfg.max_beams));
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = src.tail->order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = m->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(*src.tail));
+  LFX_TRY(k.behind(m->tail));
   lfx::GmScanArgs a{};
   a.beams = src.beams + (size_t)first * src.n_beams;
   a.W = src.n_beams;
   if (use_rotation) {a.lev = src.poses + 12u * (size_t)first; a.lev_stride = 12u; a.row_stride = 4u;}
-  rc = launch_scans(c, m, a, count, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = src.tail->done(c, st);
-  if (rc != LFX_OK) {return rc;}
-  return m->tail.done(c, st);
+  LFX_TRY(launch_scans(c, m, a, count, k.st));
+  return k.finish();
 }
 
 int lfx_grid_match_score(lfx_ctx * c, lfx_grid_match * m, uint32_t scan, const double * d_candidates, uint32_t n_candidates, uint32_t * d_score,
@@ -251,19 +225,18 @@ int lfx_grid_match_score(lfx_ctx * c, lfx_grid_match * m, uint32_t scan, const d
   if (!m->field_set) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the grid matcher has no field yet");}
   if (scan >= m->n) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "scan " + std::to_string(scan) + " is not set: the grid matcher holds " + std::to_string(m->n));}
   if (n_candidates < 1u || n_candidates > (1u << 24)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a score call takes 1 .. 2^24 candidates");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = m->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(m->tail));
   lfx::GmScoreArgs a{};
   a.G = m->geom; a.S = m->S.p;
   a.points = m->points.p + (size_t)scan * m->cfg.max_beams;
   a.n_points = m->n_points.p + scan;
   a.cand = d_candidates; a.P = n_candidates;
   a.score = d_score; a.inside = d_inside;
-  hipLaunchKernelGGL(lfx::gridmatch_score_kernel, dim3(blocks_for(n_candidates, lfx::kGmThreads)), dim3(lfx::kGmThreads), 0, st, a);
+  hipLaunchKernelGGL(lfx::gridmatch_score_kernel, dim3(blocks_for(n_candidates, lfx::kGmThreads)), dim3(lfx::kGmThreads), 0, k.st, a);
   LFX_HIP(c, hipGetLastError());
-  return m->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_grid_match_search(lfx_ctx * c, lfx_grid_match * m, uint32_t first, uint32_t n_scans, const double * centres,
@@ -284,14 +257,14 @@ int lfx_grid_match_search(lfx_ctx * c, lfx_grid_match * m, uint32_t first, uint3
              std::to_string(m->cfg.max_half_y) + ", " + std::to_string(m->cfg.max_half_theta) + ")");
   }
   const uint32_t Nx = dims[0], Ny = dims[1], T = dims[2];
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call call(c, stream);
+  hipStream_t st = call.st;
+  LFX_TRY(call.open());
   // the rotations and the centres through the next slot of the ring: its block is free once the search that used it last has passed
   TableSlot & slot = m->slots[m->next];
   hipError_t mem = hipSuccess;
-  int rc = slot.take(c, slot_doubles(n_scans, T), mem);
-  if (rc != LFX_OK) {return rc;}
-  if (mem != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot hold the search's rotations");}
+  LFX_TRY(slot.take(c, slot_doubles(n_scans, T), mem));
+  if (mem != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot hold the search's rotations");}
   double * h_rot = reinterpret_cast<double *>(slot.h.p);
   double * h_centres = h_rot + 2u * (size_t)n_scans * T;
   for (uint32_t k = 0; k < n_scans; k++) {
@@ -301,8 +274,8 @@ int lfx_grid_match_search(lfx_ctx * c, lfx_grid_match * m, uint32_t first, uint3
     h_centres[2u * k] = centres[3u * k];
     h_centres[2u * k + 1u] = centres[3u * k + 1u];
   }
-  rc = m->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(call.behind(m->tail));
+  LFX_TRY(call.take(slot.used));         // (settled by slot.take)
   LFX_HIP(c, hipMemcpyAsync(slot.d.p, slot.h.p, sizeof(double) * slot_doubles(n_scans, T), hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipMemsetAsync(m->keys.p, 0, sizeof(unsigned long long) * (size_t)n_scans * T, st));
   lfx::GmSearchArgs a{};
@@ -321,9 +294,7 @@ int lfx_grid_match_search(lfx_ctx * c, lfx_grid_match * m, uint32_t first, uint3
   hipLaunchKernelGGL(lfx::gridmatch_best_kernel, dim3(n_scans), dim3(lfx::kGmThreads), 0, st, a);
   LFX_HIP(c, hipGetLastError());
   m->next = (m->next + 1u) % lfx_grid_match::kSlots;
-  rc = slot.used.done(c, st);
-  if (rc != LFX_OK) {return rc;}
-  return m->tail.done(c, st);
+  return call.finish();
 }
 
 }  // extern "C"

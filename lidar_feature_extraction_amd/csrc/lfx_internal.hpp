@@ -115,6 +115,30 @@ hipError_t hold(DevBuf<T> & b, size_t need, bool exact = false)
   return b.alloc(exact ? need : need + need / 2);
 }
 
+// What a _create allocates: `ok` while every buffer was given -- after one that was not, no more are asked for, its error is
+// cleared from the runtime, and the sum goes on, so that the refusal names the whole.  device_bytes is `bytes`.
+struct DevTotal
+{
+  bool ok = true;
+  uint64_t bytes = 0;
+  template<typename T>
+  void get(DevBuf<T> & buf, size_t count)
+  {
+    if (ok && buf.alloc(count) != hipSuccess) {ok = false; (void)hipGetLastError();}
+    bytes += (uint64_t)count * sizeof(T);
+  }
+  std::string refusal(const char * whose) const {return std::string("cannot allocate ") + whose + "'s " + std::to_string(bytes) + " bytes";}
+};
+
+// what every _destroy does: the object's device current while its buffers and events go
+template<typename T>
+void destroy_on(T * o)
+{
+  if (!o) {return;}
+  (void)hipSetDevice(o->device);
+  delete o;
+}
+
 struct HostScan          // the per-ring lists of one scan (the large arrays live in the pinned result block)
 {
   std::vector<uint8_t> ring_status;
@@ -401,6 +425,8 @@ struct lfx_ctx
   uint64_t launches[LFX_N_KERNELS] = {};
 };
 
+namespace lfx {struct OccEmitArgs;}     // lfx_kernels_occvalue.hpp
+
 namespace lfx_host
 {
 
@@ -486,6 +512,7 @@ inline int TableSlot::take(lfx_ctx * c, size_t doubles, hipError_t & mem)
   if (rs != LFX_OK) {return rs;}
   mem = h.reserve(sizeof(double) * doubles);
   if (mem == hipSuccess) {mem = hold(d, doubles);}
+  if (mem != hipSuccess) {(void)hipGetLastError();}     // (the caller words `mem`; the runtime's last error is cleared here)
   return LFX_OK;
 }
 
@@ -494,6 +521,122 @@ inline int check_device(lfx_ctx * c, int device, const char * what)
 {
   if (device != c->device) {return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(what) + " lives on another device");}
   return LFX_OK;
+}
+
+#define LFX_TRY(call) \
+  do { \
+    const int rc_ = (call); \
+    if (rc_ != LFX_OK) {return rc_;} \
+  } while (0)
+
+// One call's scope on one stream over the tails of the objects it touches (up to kTails; nothing allocated).  A call opens
+// (the device), puts itself behind each tail -- `behind` on the stream, `after` on the host, where the host is about to
+// rewrite a block the tail guards -- queues its work on `st` and finishes: every tail taken is recorded, in the order taken.
+// A call that leaves early, by whichever return, records them as it goes out of scope, so that the next call on another
+// stream waits for what this one did queue; the call's own error text stays.  `read` orders the stream and `wait` waits on
+// the host, and neither takes anything: the views, and the reads that end in a wait of their own.  `record` records the
+// taken tails in the middle of a call and keeps them: behind a table that went up, before the call orders itself again.
+struct Call
+{
+  static constexpr int kTails = 4;
+  lfx_ctx * c;
+  hipStream_t st;
+  Call(lfx_ctx * ctx, void * stream) : c(ctx), st(static_cast<hipStream_t>(stream)) {}
+  Call(const Call &) = delete;
+  Call & operator=(const Call &) = delete;
+  ~Call()
+  {
+    if (n == 0) {return;}
+    std::string said;                    // (a record that fails here does not reword the failure the call returned with)
+    said.swap(c->err);
+    (void)record();
+    c->err.swap(said);
+  }
+  int open() {LFX_HIP(c, hipSetDevice(c->device)); return LFX_OK;}
+  int behind(const Tail & t) {LFX_TRY(t.order_behind(c, st)); return take(t);}
+  int after(const Tail & t) {LFX_TRY(t.settle(c)); return take(t);}
+  int read(const Tail & t) const {return t.order_behind(c, st);}
+  int wait(const Tail & t) const {return t.settle(c);}
+  int take(const Tail & t)               // (a tail taken twice is recorded once)
+  {
+    for (int i = 0; i < n; i++) {
+      if (taken[i] == &t) {return LFX_OK;}
+    }
+    if (n == kTails) {return fail(c, LFX_ERR_CAPACITY, "a call over more tails than lfx_host::Call holds");}
+    taken[n++] = &t;
+    return LFX_OK;
+  }
+  int record() const
+  {
+    int rc = LFX_OK;
+    for (int i = 0; i < n; i++) {
+      const int r = taken[i]->done(c, st);
+      rc = rc != LFX_OK ? rc : r;
+    }
+    return rc;
+  }
+  int finish()
+  {
+    const int rc = record();
+    n = 0;
+    return rc;
+  }
+  const Tail * taken[kTails] = {};
+  int n = 0;
+};
+
+// a small block of the device down through a pinned block, waited for: counters, stats, a plan's record
+inline int read_block(lfx_ctx * c, const PinnedBuf & pinned, const void * d_src, size_t bytes, hipStream_t st)
+{
+  LFX_HIP(c, hipMemcpyAsync(pinned.p, d_src, bytes, hipMemcpyDeviceToHost, st));
+  LFX_HIP(c, hipStreamSynchronize(st));
+  return LFX_OK;
+}
+// a small table up through a pinned block, which the caller has settled (Call::after); src null: the caller wrote the block
+inline int send_block(lfx_ctx * c, PinnedBuf & up, void * d_dst, const void * src, size_t bytes, hipStream_t st)
+{
+  LFX_HIP(c, up.reserve(bytes));
+  if (src) {std::memcpy(up.p, src, bytes);}
+  LFX_HIP(c, hipMemcpyAsync(d_dst, up.p, bytes, hipMemcpyHostToDevice, st));
+  return LFX_OK;
+}
+
+// An object's pose table, [n][12] doubles on the device behind its tail: entries [first, first + count) set from the host
+// through the object's upload block, read back, or copied from the same entries of another table on the device.  The
+// caller has checked the range and that count is not 0.
+inline int poses_set(Call & k, const Tail & tail, DevBuf<double> & d, PinnedBuf & upload, uint32_t first, uint32_t count, const double * poses)
+{
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(tail));
+  LFX_TRY(send_block(k.c, upload, d.p + 12u * (size_t)first, poses, sizeof(double) * 12u * count, k.st));
+  return k.finish();
+}
+inline int poses_get(Call & k, const Tail & tail, const DevBuf<double> & d, uint32_t first, uint32_t count, double * poses_out)
+{
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(tail));
+  LFX_HIP(k.c, hipMemcpyAsync(poses_out, d.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, k.st));
+  LFX_HIP(k.c, hipStreamSynchronize(k.st));
+  return LFX_OK;
+}
+inline int poses_follow(Call & k, const Tail & tail, DevBuf<double> & d, const double * d_poses, uint32_t first, uint32_t count)
+{
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(tail));
+  LFX_HIP(k.c, hipMemcpyAsync(d.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, k.st));
+  return k.finish();
+}
+
+// the 2-D grids' sides (occupancy grids, distance fields, the grid matcher's field), and two of them that must agree
+inline bool grid_sides_ok(uint32_t width, uint32_t height)
+{
+  return width >= 1u && width <= LFX_OCCUPANCY_MAX_SIDE && height >= 1u && height <= LFX_OCCUPANCY_MAX_SIDE;
+}
+inline int check_same_cells(lfx_ctx * c, const char * a, uint32_t aw, uint32_t ah, const char * b, uint32_t bw, uint32_t bh)
+{
+  if (aw == bw && ah == bh) {return LFX_OK;}
+  return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(a) + " is " + std::to_string(aw) + " x " + std::to_string(ah) + " cells, " + b + " " +
+           std::to_string(bw) + " x " + std::to_string(bh));
 }
 
 inline bool finite_all(const double * v, size_t n)
@@ -651,6 +794,9 @@ struct KeyframesAccess
 };
 KeyframesAccess keyframes_access(const lfx_keyframes * s);
 
+// lfx_odometry.hip: the event behind the store's last append, for lfx_odometry_save (lfx_mapping.hip) to read behind
+const Tail & odometry_tail(const lfx_odometry * o);
+
 // What a reader of an occupancy grid's counts needs (lfx_occupancy.hip; the distance field reads them in place): the two
 // count arrays, the emit's table on the device and the tail event the reader orders itself behind and moves.
 struct OccupancyAccess
@@ -664,6 +810,8 @@ struct OccupancyAccess
   const uint4 * beams = nullptr;
   const double * poses = nullptr;
   uint32_t n_scans = 0, n_beams = 0;
+  // the emit of `cfg` over the counts: everything of `a` but where the bytes go (lfx_occupancy.hip)
+  void emit_args(const lfx_occupancy_emit_config & cfg, lfx::OccEmitArgs & a) const;
 };
 OccupancyAccess occupancy_access(const lfx_occupancy * g);
 // What a reader of a distance field's d2 needs (lfx_distance.hip; the grid matcher's score field is a look-up of it): the
@@ -680,7 +828,7 @@ struct DistanceAccess
 DistanceAccess distance_access(const lfx_distance * f);
 // the emit's table of `config` put on the device as lfx_occupancy_emit puts it (nothing is sent for the config of the call
 // before); LFX_ERR_INVALID_ARGUMENT, before anything is queued: what lfx_occupancy_emit_table refuses
-int occupancy_put_table(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & config, hipStream_t st);
+int occupancy_put_table(Call & k, lfx_occupancy * g, const lfx_occupancy_emit_config & config);
 
 int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,

@@ -90,12 +90,13 @@ struct KindPlan
   const uint32_t * begin = nullptr, * count = nullptr;   // host, [n]
 };
 
-int append(lfx_ctx * c, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, size_t pose_at, size_t table_at, hipStream_t st)
+int append(Call & call, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, size_t pose_at, size_t table_at)
 {
+  lfx_ctx * c = call.c;
+  hipStream_t st = call.st;
   uint8_t * up = s->upload.p;
   size_t at = table_at;
-  const int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(call.behind(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     lfx::KfCopyEntry * tab = reinterpret_cast<lfx::KfCopyEntry *>(up + at);
     at += round64(sizeof(lfx::KfCopyEntry) * n);
@@ -129,7 +130,7 @@ int append(lfx_ctx * c, lfx_keyframes * s, const KindPlan plan[2], uint32_t n, s
     for (uint32_t k = 0; k < n; k++) {dst += plan[kind].count[k]; s->begin[kind].push_back(dst);}
   }
   s->n += n;
-  return s->tail.done(c, st);
+  return call.finish();
 }
 
 // what an add of n keyframes needs of the pinned upload block: [poses][per kind: table, begins]
@@ -269,17 +270,12 @@ int lfx_keyframes_create(lfx_ctx * c, const lfx_keyframes_config * config, lfx_k
   const size_t K = config->max_keyframes;
   s->chunk = std::min<uint64_t>(kSaveChunk, std::max(config->max_points[0], config->max_points[1]));
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_keyframes_destroy(s); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  for (int kind = 0; kind < 2; kind++) {get(s->records[kind], config->max_points[kind]); get(s->d_begin[kind], K + 1u); get(s->table[kind], K);}
-  get(s->poses, 12u * K); get(s->flag, K); get(s->out_begin, K); get(s->record, 1u); get(s->scratch, s->chunk);
-  get(s->mask_runs, (size_t)(std::max(config->max_points[0], config->max_points[1]) / lfx::kKfRun) + 2u);
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's " + std::to_string(bytes) + " bytes");}
-  s->device_bytes = bytes;
+  DevTotal m;
+  for (int kind = 0; kind < 2; kind++) {m.get(s->records[kind], config->max_points[kind]); m.get(s->d_begin[kind], K + 1u); m.get(s->table[kind], K);}
+  m.get(s->poses, 12u * K); m.get(s->flag, K); m.get(s->out_begin, K); m.get(s->record, 1u); m.get(s->scratch, s->chunk);
+  m.get(s->mask_runs, (size_t)(std::max(config->max_points[0], config->max_points[1]) / lfx::kKfRun) + 2u);
+  if (!m.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, m.refusal("the keyframe store"));}
+  s->device_bytes = m.bytes;
   for (int kind = 0; kind < 2; kind++) {
     // begin[0] = 0; every entry behind the last keyframe's reads as "no record lies here" (all ones) until an add writes it
     if (hipMemset(s->d_begin[kind].p, 0xFF, sizeof(uint64_t) * (K + 1u)) != hipSuccess || hipMemset(s->d_begin[kind].p, 0, sizeof(uint64_t)) != hipSuccess) {
@@ -297,12 +293,7 @@ int lfx_keyframes_create(lfx_ctx * c, const lfx_keyframes_config * config, lfx_k
   return LFX_OK;
 }
 
-void lfx_keyframes_destroy(lfx_keyframes * s)
-{
-  if (!s) {return;}
-  (void)hipSetDevice(s->device);
-  delete s;
-}
+void lfx_keyframes_destroy(lfx_keyframes * s) {destroy_on(s);}
 
 int lfx_keyframes_info(const lfx_keyframes * s, lfx_keyframes_info_t * info)
 {
@@ -319,9 +310,9 @@ int lfx_keyframes_view(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes_store
 {
   if (!c || !s || !view) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = s->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(s->tail));
   *view = lfx_keyframes_store_view{};
   for (int kind = 0; kind < 2; kind++) {
     view->points[kind] = reinterpret_cast<const float *>(s->records[kind].p);
@@ -346,17 +337,15 @@ int lfx_keyframes_add(lfx_ctx * c, lfx_keyframes * s, const lfx_keyframes_clouds
   if (!finite_all(poses, 12u * (size_t)n)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const uint64_t none[2] = {0u, 0u};
-  int rc = check_room(c, s, n, none);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  LFX_TRY(check_room(c, s, n, none));
+  Call call(c, stream);
+  LFX_TRY(call.open());
   // both kinds' counts and begins back in one wait: the call's only one
   const CloudList lists[2] = {{edge->d_begin, edge->d_count, edge->count_stride, edge->total_points, "edge "},
     {surface->d_begin, surface->d_count, surface->count_stride, surface->total_points, "surface "}};
   LFX_HIP(c, s->readback.reserve(readback_bytes(n, edge->count_stride) + readback_bytes(n, surface->count_stride)));
   std::vector<uint32_t> begin[2], count[2];
-  rc = read_lists(c, lists, 2, n, s->readback.p, begin, count, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(read_lists(c, lists, 2, n, s->readback.p, begin, count, call.st));
   uint64_t add[2] = {0u, 0u};
   for (int kind = 0; kind < 2; kind++) {
     uint64_t blocks = 0u;
@@ -366,10 +355,8 @@ int lfx_keyframes_add(lfx_ctx * c, lfx_keyframes * s, const lfx_keyframes_clouds
     }
     if (blocks > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "the call adds too many records for one launch");}
   }
-  rc = check_room(c, s, n, add);
-  if (rc != LFX_OK) {return rc;}
-  rc = s->tail.settle(c);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_room(c, s, n, add));
+  LFX_TRY(call.after(s->tail));
   LFX_HIP(c, s->upload.reserve(upload_bytes(n)));
   std::memcpy(s->upload.p, poses, sizeof(double) * 12u * n);
   KindPlan plan[2];
@@ -379,9 +366,9 @@ int lfx_keyframes_add(lfx_ctx * c, lfx_keyframes * s, const lfx_keyframes_clouds
     plan[kind].count = count[kind].data();
   }
   const uint32_t first = s->n;
-  rc = append(c, s, plan, n, 0u, round64(sizeof(double) * 12u * n), st);
-  if (rc == LFX_OK && first_id) {*first_id = first;}
-  return rc;
+  LFX_TRY(append(call, s, plan, n, 0u, round64(sizeof(double) * 12u * n)));
+  if (first_id) {*first_id = first;}
+  return LFX_OK;
 }
 
 int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, uint32_t n_edge, const float * surface, uint32_t n_surface,
@@ -391,12 +378,11 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   if (!finite_all(pose, 12u)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const uint64_t add[2] = {n_edge, n_surface};
-  int rc = check_room(c, s, 1u, add);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = s->tail.settle(c);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_room(c, s, 1u, add));
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(s->tail));
   // the pinned block: [pose][the two new begins][edge records][surface records]; copied up from there, straight into place
   const size_t head = 128u, e_bytes = sizeof(float4) * (size_t)n_edge, s_bytes = sizeof(float4) * (size_t)n_surface;
   LFX_HIP(c, s->upload.reserve(head + e_bytes + s_bytes));
@@ -405,8 +391,7 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   uint64_t * nb = reinterpret_cast<uint64_t *>(up + 96u);
   const float * src[2] = {edge, surface};
   const size_t bytes[2] = {e_bytes, s_bytes}, where[2] = {head, head + e_bytes};
-  rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.behind(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     const uint64_t at = s->begin[kind][s->n];
     nb[kind] = at + add[kind];
@@ -420,7 +405,7 @@ int lfx_keyframes_add_host(lfx_ctx * c, lfx_keyframes * s, const float * edge, u
   for (int kind = 0; kind < 2; kind++) {s->begin[kind].push_back(nb[kind]);}
   if (id) {*id = s->n;}
   s->n += 1u;
-  return s->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_set_poses(lfx_ctx * c, lfx_keyframes * s, uint32_t first, uint32_t count, const double * poses, void * stream)
@@ -430,14 +415,8 @@ int lfx_keyframes_set_poses(lfx_ctx * c, lfx_keyframes * s, uint32_t first, uint
   if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!finite_all(poses, 12u * (size_t)count)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = s->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
-  LFX_HIP(c, s->upload.reserve(sizeof(double) * 12u * count));
-  std::memcpy(s->upload.p, poses, sizeof(double) * 12u * count);
-  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, s->upload.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
-  return s->tail.done(c, st);
+  Call k(c, stream);
+  return poses_set(k, s->tail, s->poses, s->upload, first, count, poses);
 }
 
 int lfx_keyframes_poses(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, uint32_t count, double * poses_out, void * stream)
@@ -446,13 +425,8 @@ int lfx_keyframes_poses(lfx_ctx * c, const lfx_keyframes * s, uint32_t first, ui
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(poses_out, s->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  return LFX_OK;
+  Call k(c, stream);
+  return poses_get(k, s->tail, s->poses, first, count, poses_out);
 }
 
 int lfx_keyframes_follow(lfx_ctx * c, lfx_keyframes * s, const double * d_poses, uint32_t first, uint32_t count, void * stream)
@@ -461,12 +435,8 @@ int lfx_keyframes_follow(lfx_ctx * c, lfx_keyframes * s, const double * d_poses,
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(s->poses.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, st));
-  return s->tail.done(c, st);
+  Call k(c, stream);
+  return poses_follow(k, s->tail, s->poses, d_poses, first, count);
 }
 
 int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t first, uint32_t count, float * d_out, uint64_t capacity_points,
@@ -483,13 +453,11 @@ int lfx_keyframes_build(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t
   *n_out = hi - lo;
   if (hi == lo) {return LFX_OK;}
   if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = launch_transform(c, s, kind, lo, hi, first, first + count, false, first, d_out, st);
-  if (rc != LFX_OK) {return rc;}
-  return s->tail.done(c, st);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
+  LFX_TRY(launch_transform(c, s, kind, lo, hi, first, first + count, false, first, d_out, k.st));
+  return k.finish();
 }
 
 int lfx_keyframes_build_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, uint32_t first, uint32_t count, const uint8_t * d_flags, float * d_out,
@@ -500,8 +468,9 @@ int lfx_keyframes_build_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, u
   if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
   *n_out = 0u;
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
   if (hi == lo) {
     if (d_begin_out) {LFX_HIP(c, hipMemsetAsync(d_begin_out, 0, sizeof(uint64_t) * ((size_t)count + 1u), st));}
     return LFX_OK;
@@ -509,23 +478,19 @@ int lfx_keyframes_build_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, u
   if (!d_flags) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_flags is required");}
   const uint64_t runs = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
   if (runs + 1u > s->mask_runs.n) {return fail(c, LFX_ERR_CAPACITY, "too many records for the masked build's table");}
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.behind(s->tail));
   hipLaunchKernelGGL(lfx::keyframes_mask_count_kernel, dim3((uint32_t)runs), dim3(lfx::kKfThreads), 0, st, d_flags, lo, hi, s->mask_runs.p);
   LFX_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(lfx::keyframes_mask_scan_kernel, dim3(1), dim3(lfx::kKfThreads), 0, st, s->mask_runs.p, (uint32_t)runs);
   LFX_HIP(c, hipGetLastError());
   // the call's only wait: the kept records (the caller needs them to hand the cloud on; the capacity is checked against them)
-  uint64_t * kept = reinterpret_cast<uint64_t *>(s->readback.p);
-  LFX_HIP(c, hipMemcpyAsync(kept, s->mask_runs.p + runs, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  *n_out = *kept;
+  LFX_TRY(read_block(c, s->readback, s->mask_runs.p + runs, sizeof(uint64_t), st));
+  *n_out = *reinterpret_cast<const uint64_t *>(s->readback.p);
   if (*n_out > capacity_points) {
-    (void)s->tail.done(c, st);
     return fail(c, LFX_ERR_CAPACITY, "the keyframes keep " + std::to_string(*n_out) + " records: more than capacity_points (" + std::to_string(capacity_points) + ")");
   }
   if (*n_out > 0u) {
-    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
     lfx::KfRange a{};
     a.rec_lo = lo; a.rec_hi = hi; a.k_lo = first; a.k_hi = first + count; a.first = first;
     hipLaunchKernelGGL(lfx::keyframes_mask_scatter_kernel, dim3((uint32_t)runs), dim3(lfx::kKfThreads), 0, st, s->records[kind].p, s->d_begin[kind].p,
@@ -537,7 +502,7 @@ int lfx_keyframes_build_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, u
       s->mask_runs.p, first, count, lo, d_begin_out);
     LFX_HIP(c, hipGetLastError());
   }
-  return s->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const double center[3], double radius, uint32_t first, uint32_t count,
@@ -550,10 +515,10 @@ int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const d
   *result = lfx_keyframes_submap_result{};
   result->first_id = result->last_id = LFX_KEYFRAMES_NO_ID;
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
   hipLaunchKernelGGL(lfx::keyframes_flag_kernel, dim3((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), dim3(lfx::kKfThreads), 0, st, s->poses.p, first,
     count, center[0], center[1], center[2], radius * radius, s->flag.p);
   LFX_HIP(c, hipGetLastError());
@@ -561,18 +526,15 @@ int lfx_keyframes_submap(lfx_ctx * c, const lfx_keyframes * s, int kind, const d
     s->out_begin.p, s->record.p);
   LFX_HIP(c, hipGetLastError());
   // the call's only wait: the plan's record (the caller needs n_points to hand the cloud on; the launch below its range)
-  lfx::KfPlanRecord * rec = reinterpret_cast<lfx::KfPlanRecord *>(s->readback.p);
-  LFX_HIP(c, hipMemcpyAsync(rec, s->record.p, sizeof(lfx::KfPlanRecord), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::memcpy(result, rec, sizeof(*result));
+  LFX_TRY(read_block(c, s->readback, s->record.p, sizeof(lfx::KfPlanRecord), st));
+  std::memcpy(result, s->readback.p, sizeof(*result));
   result->reserved = 0u;
   if (result->n_points > 0u) {
-    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
     const uint32_t k_lo = result->first_id, k_hi = result->last_id + 1u;
-    rc = launch_transform(c, s, kind, s->begin[kind][k_lo], s->begin[kind][k_hi], k_lo, k_hi, true, first, d_out, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(launch_transform(c, s, kind, s->begin[kind][k_lo], s->begin[kind][k_hi], k_lo, k_hi, true, first, d_out, st));
   }
-  return s->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirname, int written[2], void * stream)
@@ -580,16 +542,14 @@ int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirnam
   if (!c || !s || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   written[0] = written[1] = 0;
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   const std::string dir(dirname);
   const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.read(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     if (s->begin[kind][s->n] == 0u) {continue;}
-    rc = save_kind(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(save_kind(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), k.st));
     written[kind] = 1;
   }
   return LFX_OK;
@@ -602,8 +562,8 @@ int lfx_keyframes_reserve_flags(lfx_ctx * c, lfx_keyframes * s, void * stream)
   if (!c || !s) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (s->has_flags) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   DevBuf<uint8_t> flags[2];
   DevBuf<uint64_t> kept_begin, kept;
   const size_t K = s->cfg.max_keyframes;
@@ -614,11 +574,9 @@ int lfx_keyframes_reserve_flags(lfx_ctx * c, lfx_keyframes * s, void * stream)
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the keyframe store's " + std::to_string(bytes) + " bytes of flags");
   }
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  for (int kind = 0; kind < 2; kind++) {LFX_HIP(c, hipMemsetAsync(flags[kind].p, 0, s->cfg.max_points[kind], st));}
-  rc = s->tail.done(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.behind(s->tail));
+  for (int kind = 0; kind < 2; kind++) {LFX_HIP(c, hipMemsetAsync(flags[kind].p, 0, s->cfg.max_points[kind], k.st));}
+  LFX_TRY(k.finish());
   for (int kind = 0; kind < 2; kind++) {s->flags[kind] = std::move(flags[kind]);}
   s->kept_begin = std::move(kept_begin);
   s->kept = std::move(kept);
@@ -631,9 +589,9 @@ int lfx_keyframes_flags(lfx_ctx * c, lfx_keyframes * s, uint8_t * d_flags[2], vo
 {
   if (!c || !s || !d_flags) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = s->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(s->tail));
   for (int kind = 0; kind < 2; kind++) {d_flags[kind] = s->flags[kind].p;}
   return LFX_OK;
 }
@@ -646,12 +604,11 @@ int lfx_keyframes_set_flags(lfx_ctx * c, lfx_keyframes * s, int kind, uint32_t f
   const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
   if (hi == lo) {return LFX_OK;}
   if (!d_src) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_src is required");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(s->flags[kind].p + lo, d_src + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, st));
-  return s->tail.done(c, st);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
+  LFX_HIP(c, hipMemcpyAsync(s->flags[kind].p + lo, d_src + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, k.st));
+  return k.finish();
 }
 
 int lfx_keyframes_clear_flags(lfx_ctx * c, lfx_keyframes * s, int kind, uint32_t first, uint32_t count, void * stream)
@@ -661,12 +618,11 @@ int lfx_keyframes_clear_flags(lfx_ctx * c, lfx_keyframes * s, int kind, uint32_t
   if (check_range(c, s, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
   if (hi == lo) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemsetAsync(s->flags[kind].p + lo, 0, (size_t)(hi - lo), st));
-  return s->tail.done(c, st);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
+  LFX_HIP(c, hipMemsetAsync(s->flags[kind].p + lo, 0, (size_t)(hi - lo), k.st));
+  return k.finish();
 }
 
 int lfx_keyframes_flags_info(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes_flags_info_t * info, void * stream)
@@ -679,21 +635,20 @@ int lfx_keyframes_flags_info(lfx_ctx * c, const lfx_keyframes * s, lfx_keyframes
   info->device_bytes = s->flag_bytes;
   const uint64_t total[2] = {s->begin[0][s->n], s->begin[1][s->n]};
   if (total[0] == 0u && total[1] == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
   // both kinds' kept records through the masked build's table, one behind the other; the call's only wait
   uint64_t * h_kept = reinterpret_cast<uint64_t *>(s->readback.p);
   for (int kind = 0; kind < 2; kind++) {
     h_kept[kind] = 0u;
     if (total[kind] == 0u) {continue;}
-    rc = launch_mask_count(c, s, s->flags[kind].p, 0u, total[kind], h_kept + kind, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(launch_mask_count(c, s, s->flags[kind].p, 0u, total[kind], h_kept + kind, st));
   }
   LFX_HIP(c, hipStreamSynchronize(st));
   for (int kind = 0; kind < 2; kind++) {info->n_flagged[kind] = total[kind] - h_kept[kind];}
-  return s->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_submap_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, const double center[3], double radius, uint32_t first,
@@ -709,10 +664,10 @@ int lfx_keyframes_submap_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, 
   const uint64_t lo = s->begin[kind][first], hi = s->begin[kind][first + count];
   const uint64_t runs = (hi - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
   if (runs + 1u > s->mask_runs.n) {return fail(c, LFX_ERR_CAPACITY, "too many records for the masked build's table");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(s->tail));
   const dim3 per_keyframe((count + lfx::kKfThreads - 1u) / lfx::kKfThreads), threads(lfx::kKfThreads);
   const uint8_t * flags = s->flags[kind].p;
   lfx::KfRange a{};
@@ -735,13 +690,11 @@ int lfx_keyframes_submap_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, 
     s->record.p);
   LFX_HIP(c, hipGetLastError());
   // the call's only wait: the plan's record, as lfx_keyframes_submap's
-  lfx::KfPlanRecord * rec = reinterpret_cast<lfx::KfPlanRecord *>(s->readback.p);
-  LFX_HIP(c, hipMemcpyAsync(rec, s->record.p, sizeof(lfx::KfPlanRecord), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  std::memcpy(result, rec, sizeof(*result));
+  LFX_TRY(read_block(c, s->readback, s->record.p, sizeof(lfx::KfPlanRecord), st));
+  std::memcpy(result, s->readback.p, sizeof(*result));
   result->reserved = 0u;
   if (result->n_points > 0u) {
-    if (!d_out) {(void)s->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
     // the runs of the count pass that hold the written keyframes' records
     const uint64_t run0 = (s->begin[kind][result->first_id] - lo) / lfx::kKfRun;
     const uint64_t run1 = (s->begin[kind][result->last_id + 1u] - lo + lfx::kKfRun - 1u) / lfx::kKfRun;
@@ -749,7 +702,7 @@ int lfx_keyframes_submap_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, 
       s->poses.p, flags, s->mask_runs.p, s->out_begin.p, s->kept_begin.p, reinterpret_cast<float4 *>(d_out), (uint32_t)run0, a);
     LFX_HIP(c, hipGetLastError());
   }
-  return s->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_save_masked(lfx_ctx * c, const lfx_keyframes * s, const char * dirname, int written[2], void * stream)
@@ -757,17 +710,15 @@ int lfx_keyframes_save_masked(lfx_ctx * c, const lfx_keyframes * s, const char *
   if (!c || !s || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_store(c, s) != LFX_OK || check_flags(c, s) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   written[0] = written[1] = 0;
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   const std::string dir(dirname);
   const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
-  int rc = s->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.read(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     if (s->begin[kind][s->n] == 0u) {continue;}
     uint64_t kept = 0u;
-    rc = save_kind_masked(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), &kept, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(save_kind_masked(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), &kept, k.st));
     written[kind] = kept > 0u ? 1 : 0;
   }
   return LFX_OK;

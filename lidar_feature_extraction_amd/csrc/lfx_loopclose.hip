@@ -289,12 +289,7 @@ int lfx_loop_closer_create(lfx_ctx * c, const lfx_loop_closer_config * cfg, lfx_
   return LFX_OK;
 }
 
-void lfx_loop_closer_destroy(lfx_loop_closer * lc)
-{
-  if (!lc) {return;}
-  (void)hipSetDevice(lc->device);
-  delete lc;
-}
+void lfx_loop_closer_destroy(lfx_loop_closer * lc) {destroy_on(lc);}
 
 int lfx_loop_closer_info(const lfx_loop_closer * lc, lfx_loop_closer_info_t * info)
 {

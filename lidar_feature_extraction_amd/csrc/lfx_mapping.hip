@@ -34,9 +34,11 @@ int check(lfx_ctx * c, const lfx_mapper * m) {return check_device(c, m->device, 
 
 // MapBuilder::Callback for n clouds whose begins and counts are known on the host (src: the records they address).
 // Decides every outcome, then grows the map if it must and queues one map_append_kernel; all or nothing.
-int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t * begin, const uint32_t * count, uint32_t n,
-  const double * poses, uint8_t * outcomes, hipStream_t st)
+int add_clouds(Call & call, lfx_mapper * m, const float4 * src, const uint32_t * begin, const uint32_t * count, uint32_t n,
+  const double * poses, uint8_t * outcomes)
 {
+  lfx_ctx * c = call.c;
+  hipStream_t st = call.st;
   std::vector<uint8_t> out(n);
   std::vector<uint32_t> added;               // indices of the added clouds
   bool has_pose = m->has_pose;
@@ -71,8 +73,7 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
       return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot grow the map to " + std::to_string(want) + " records");
     }
     // (the previous call's append may be queued on another stream: the copy reads the map behind it)
-    const int rb = m->uploaded.order_behind(c, st);
-    if (rb != LFX_OK) {return rb;}
+    LFX_TRY(call.read(m->uploaded));
     if (m->n) {LFX_HIP(c, hipMemcpyAsync(grown.p, m->map.p, sizeof(float4) * m->n, hipMemcpyDeviceToDevice, st));}
     // (growth is rare: the copy has read the old map before it goes)
     LFX_HIP(c, hipStreamSynchronize(st));
@@ -83,14 +84,12 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
     if (m->table.n < na) {
       DevBuf<lfx::MapAppendEntry> t;
       if (t.alloc(na + na / 2) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the mapper's table");}
-      const int rs = m->uploaded.settle(c);  // (the previous append may still read the old table)
-      if (rs != LFX_OK) {return rs;}
+      LFX_TRY(call.after(m->uploaded));      // (the previous append may still read the old table)
       m->table = std::move(t);
     }
     const size_t bytes = sizeof(lfx::MapAppendEntry) * na;
+    LFX_TRY(call.after(m->uploaded));        // (the previous call's upload has passed: the pinned table may move or be written again)
     LFX_HIP(c, m->pinned.reserve(m->pin_table + bytes));
-    const int rs = m->uploaded.settle(c);    // (the previous call's upload has passed: the pinned table may be written again)
-    if (rs != LFX_OK) {return rs;}
     lfx::MapAppendEntry * tab = reinterpret_cast<lfx::MapAppendEntry *>(m->pinned.p + m->pin_table);
     uint64_t at = m->n;
     uint32_t first = 0;
@@ -109,8 +108,7 @@ int add_clouds(lfx_ctx * c, lfx_mapper * m, const float4 * src, const uint32_t *
     LFX_HIP(c, hipMemcpyAsync(m->table.p, tab, bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lfx::map_append_kernel, dim3(first), dim3(lfx::kMapAppendThreads), 0, st, m->table.p, (uint32_t)na, src, m->map.p);
     LFX_HIP(c, hipGetLastError());
-    const int rd = m->uploaded.done(c, st);
-    if (rd != LFX_OK) {return rd;}
+    LFX_TRY(call.finish());
   }
   // the call stands: commit
   if (!added.empty()) {std::memcpy(m->last, poses + 12 * (size_t)added.back(), sizeof(m->last));}
@@ -175,12 +173,7 @@ int lfx_mapper_create(lfx_ctx * c, const lfx_mapper_config * cfg, lfx_mapper ** 
   return LFX_OK;
 }
 
-void lfx_mapper_destroy(lfx_mapper * m)
-{
-  if (!m) {return;}
-  (void)hipSetDevice(m->device);
-  delete m;
-}
+void lfx_mapper_destroy(lfx_mapper * m) {destroy_on(m);}
 
 int lfx_mapper_add(lfx_ctx * c, lfx_mapper * m, const float * d_points, const uint32_t * d_begin, const uint32_t * d_count,
   uint32_t count_stride, uint32_t n_clouds, size_t total_points, const double * poses, uint8_t * outcomes, void * stream)
@@ -189,17 +182,15 @@ int lfx_mapper_add(lfx_ctx * c, lfx_mapper * m, const float * d_points, const ui
   if (n_clouds == 0 || count_stride == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_clouds and count_stride must be >= 1");}
   if (!finite_all(poses, 12 * (size_t)n_clouds)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the poses must be finite");}
   if (check(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   // the counts and the begins back in one wait: the call's only one
-  int rc = grow_readback(c, m->uploaded, m->pinned, m->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::MapAppendEntry),
-    std::max<size_t>(n_clouds, kInitialEntries));
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(grow_readback(c, m->uploaded, m->pinned, m->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::MapAppendEntry),
+    std::max<size_t>(n_clouds, kInitialEntries)));
   const CloudList list{d_begin, d_count, count_stride, total_points, ""};
   std::vector<uint32_t> begin, count;
-  rc = read_lists(c, &list, 1, n_clouds, m->pinned.p, &begin, &count, st);
-  if (rc != LFX_OK) {return rc;}
-  return add_clouds(c, m, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses, outcomes, st);
+  LFX_TRY(read_lists(c, &list, 1, n_clouds, m->pinned.p, &begin, &count, k.st));
+  return add_clouds(k, m, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses, outcomes);
 }
 
 int lfx_mapper_add_host(lfx_ctx * c, lfx_mapper * m, const float * points, uint32_t n_points, const double pose[12],
@@ -208,23 +199,22 @@ int lfx_mapper_add_host(lfx_ctx * c, lfx_mapper * m, const float * points, uint3
   if (!c || !m || !pose || !outcome || (n_points && !points)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!finite_all(pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose must be finite");}
   if (check(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
   const uint32_t zero = 0u;
-  if (n_points == 0) {return add_clouds(c, m, nullptr, &zero, &zero, 1, pose, outcome, st);}
+  if (n_points == 0) {return add_clouds(k, m, nullptr, &zero, &zero, 1, pose, outcome);}
   // staged only where the cloud would be added (nothing is copied for an empty or too-close cloud)
   if (m->n > 0) {
     double dt = 0., dr = 0.;
     lfx_pose_diff(m->last, pose, &dt, &dr);
     if (dt < m->cfg.translation_threshold && dr < m->cfg.rotation_threshold) {
-      return add_clouds(c, m, nullptr, &zero, &n_points, 1, pose, outcome, st);
+      return add_clouds(k, m, nullptr, &zero, &n_points, 1, pose, outcome);
     }
   }
-  const int rs = m->uploaded.settle(c);      // (the previous append may still read the staged cloud)
-  if (rs != LFX_OK) {return rs;}
+  LFX_TRY(k.after(m->uploaded));             // (the previous append may still read the staged cloud)
   if (hold(m->staged, n_points) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the cloud");}
-  LFX_HIP(c, hipMemcpyAsync(m->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, st));
-  return add_clouds(c, m, m->staged.p, &zero, &n_points, 1, pose, outcome, st);
+  LFX_HIP(c, hipMemcpyAsync(m->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, k.st));
+  return add_clouds(k, m, m->staged.p, &zero, &n_points, 1, pose, outcome);
 }
 
 int lfx_mapper_view(const lfx_mapper * m, lfx_mapper_store_view * v)
@@ -248,12 +238,10 @@ int lfx_mapper_save(lfx_ctx * c, const lfx_mapper * m, const char * path, int * 
   if (check(c, m) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   *written = 0;
   if (m->n == 0) {return LFX_OK;}            // "Map is empty! Quit without exporting to a file"
-  LFX_HIP(c, hipSetDevice(c->device));
-  // (the last append may be queued on another stream: the map is read behind it)
-  const int rb = m->uploaded.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rb != LFX_OK) {return rb;}
-  const int rc = save_cloud(c, reinterpret_cast<const float *>(m->map.p), m->n, path, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(m->uploaded));              // (the last append may be queued on another stream: the map is read behind it)
+  LFX_TRY(save_cloud(c, reinterpret_cast<const float *>(m->map.p), m->n, path, k.st));
   *written = 1;
   return LFX_OK;
 }
@@ -263,20 +251,18 @@ int lfx_odometry_save(lfx_ctx * c, const lfx_odometry * o, const char * dirname,
   if (!c || !o || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
   written[0] = written[1] = 0;
   lfx_odometry_store_view v{};
-  int rc = lfx_odometry_view(o, &v);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
+  LFX_TRY(lfx_odometry_view(o, &v));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(odometry_tail(o)));         // (the last append may be queued on another stream: the store is read behind it)
   const std::string dir(dirname);
   const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (v.n_edge) {
-    rc = save_cloud(c, v.edge_points, v.n_edge, dir + sep + "edge.pcd", st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(save_cloud(c, v.edge_points, v.n_edge, dir + sep + "edge.pcd", k.st));
     written[0] = 1;
   }
   if (v.n_surface) {
-    rc = save_cloud(c, v.surface_points, v.n_surface, dir + sep + "surface.pcd", st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(save_cloud(c, v.surface_points, v.n_surface, dir + sep + "surface.pcd", k.st));
     written[1] = 1;
   }
   return LFX_OK;

@@ -56,20 +56,15 @@ const char * kEmitRefused = "the emit config is refused: w_hit and w_miss in 1 .
 
 // the emit's table on the device: the config of the call before is there already; another one's goes up through the pinned
 // block once the object's last call has passed
-int put_lut(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & cfg, hipStream_t st)
+int put_lut(Call & k, lfx_occupancy * g, const lfx_occupancy_emit_config & cfg)
 {
   int8_t lut[4097];
-  if (lfx_occupancy_emit_table(&cfg, lut) != LFX_OK) {return fail(c, LFX_ERR_INVALID_ARGUMENT, kEmitRefused);}
+  if (lfx_occupancy_emit_table(&cfg, lut) != LFX_OK) {return fail(k.c, LFX_ERR_INVALID_ARGUMENT, kEmitRefused);}
   if (g->lut_cfg.w_hit != 0 && std::memcmp(&g->lut_cfg, &cfg, sizeof(cfg)) == 0) {return LFX_OK;}
-  const size_t n = (size_t)((int64_t)cfg.l_max - (int64_t)cfg.l_min + 1);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
-  LFX_HIP(c, g->upload.reserve(sizeof(lut)));
-  std::memcpy(g->upload.p, lut, n);
+  LFX_TRY(k.after(g->tail));
   g->lut_cfg.w_hit = 0;
-  LFX_HIP(c, hipMemcpyAsync(g->lut.p, g->upload.p, n, hipMemcpyHostToDevice, st));
-  const int rd = g->tail.done(c, st);
-  if (rd != LFX_OK) {return rd;}
+  LFX_TRY(send_block(k.c, g->upload, g->lut.p, lut, (size_t)((int64_t)cfg.l_max - (int64_t)cfg.l_min + 1), k.st));
+  LFX_TRY(k.record());
   g->lut_cfg = cfg;
   return LFX_OK;
 }
@@ -77,11 +72,7 @@ int put_lut(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & cf
 int launch_emit(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & cfg, int8_t * out, hipStream_t st)
 {
   lfx::OccEmitArgs a{};
-  a.hits = g->hits.p; a.misses = g->misses.p;
-  a.cells = (uint64_t)g->cfg.width * g->cfg.height;
-  a.w_hit = cfg.w_hit; a.w_miss = cfg.w_miss; a.l_min = cfg.l_min; a.l_max = cfg.l_max;
-  a.min_observations = cfg.min_observations;
-  a.lut = g->lut.p;
+  occupancy_access(g).emit_args(cfg, a);
   a.out = out;
   a.words = (reinterpret_cast<uintptr_t>(out) & 3u) == 0u;
   hipLaunchKernelGGL(lfx::occupancy_emit_kernel, dim3(blocks_for((a.cells + 3u) / 4u, lfx::kOccThreads)), dim3(lfx::kOccThreads), 0, st, a);
@@ -105,7 +96,16 @@ OccupancyAccess occupancy_access(const lfx_occupancy * g)
   return a;
 }
 
-int occupancy_put_table(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config & config, hipStream_t st) {return put_lut(c, g, config, st);}
+void OccupancyAccess::emit_args(const lfx_occupancy_emit_config & cfg, lfx::OccEmitArgs & a) const
+{
+  a.hits = hits; a.misses = misses;
+  a.cells = (uint64_t)width * height;
+  a.w_hit = cfg.w_hit; a.w_miss = cfg.w_miss; a.l_min = cfg.l_min; a.l_max = cfg.l_max;
+  a.min_observations = cfg.min_observations;
+  a.lut = lut;
+}
+
+int occupancy_put_table(Call & k, lfx_occupancy * g, const lfx_occupancy_emit_config & config) {return put_lut(k, g, config);}
 }  // namespace lfx_host
 
 extern "C" {
@@ -132,16 +132,11 @@ int lfx_occupancy_create(lfx_ctx * c, const lfx_occupancy_config * config, lfx_o
   g->words = (uint32_t)((((uint64_t)g->side * (uint64_t)g->side + 31u) / 32u + 3u) & ~(uint64_t)3u);
   const size_t K = config->max_scans, C = config->chunk_scans, cells = (size_t)config->width * config->height;
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_occupancy_destroy(g); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(g->beams, K * W); get(g->poses, 12u * K); get(g->src, K); get(g->table, 2u * (size_t)W); get(g->keys, 2u * C * W);
-  get(g->bits, 2u * C * g->words); get(g->hits, cells); get(g->misses, cells); get(g->counters, lfx::kOccCounters); get(g->lut, 4097u);
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the occupancy grid's " + std::to_string(bytes) + " bytes");}
-  g->device_bytes = bytes;
+  DevTotal m;
+  m.get(g->beams, K * W); m.get(g->poses, 12u * K); m.get(g->src, K); m.get(g->table, 2u * (size_t)W); m.get(g->keys, 2u * C * W);
+  m.get(g->bits, 2u * C * g->words); m.get(g->hits, cells); m.get(g->misses, cells); m.get(g->counters, lfx::kOccCounters); m.get(g->lut, 4097u);
+  if (!m.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, m.refusal("the occupancy grid"));}
+  g->device_bytes = m.bytes;
   if (hipMemset(g->bits.p, 0, sizeof(uint32_t) * 2u * C * g->words) != hipSuccess || hipMemset(g->hits.p, 0, sizeof(uint32_t) * cells) != hipSuccess ||
     hipMemset(g->misses.p, 0, sizeof(uint32_t) * cells) != hipSuccess || hipMemset(g->counters.p, 0, sizeof(unsigned long long) * lfx::kOccCounters) != hipSuccess ||
     hipMemcpy(g->table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice) != hipSuccess)
@@ -155,12 +150,7 @@ int lfx_occupancy_create(lfx_ctx * c, const lfx_occupancy_config * config, lfx_o
   return LFX_OK;
 }
 
-void lfx_occupancy_destroy(lfx_occupancy * g)
-{
-  if (!g) {return;}
-  (void)hipSetDevice(g->device);
-  delete g;
-}
+void lfx_occupancy_destroy(lfx_occupancy * g) {destroy_on(g);}
 
 int lfx_occupancy_info(const lfx_occupancy * g, lfx_occupancy_info_t * info)
 {
@@ -181,9 +171,9 @@ int lfx_occupancy_view(lfx_ctx * c, const lfx_occupancy * g, lfx_occupancy_view_
 {
   if (!c || !g || !view) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = g->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(g->tail));
   *view = lfx_occupancy_view_t{};
   view->beams = reinterpret_cast<const float *>(g->beams.p);
   view->poses = g->poses.p;
@@ -211,10 +201,10 @@ int lfx_occupancy_add_batch(lfx_ctx * c, lfx_occupancy * g, uint32_t n_scans, co
   }
   if (first_id) {*first_id = g->n;}
   if (n == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = g->tail.settle(c);
-  if (rc != LFX_OK) {return rc;}
+  Call call(c, stream);
+  hipStream_t st = call.st;
+  LFX_TRY(call.open());
+  LFX_TRY(call.after(g->tail));
   // the pinned block: [the selected scans' poses][their batch scans]
   const size_t pose_bytes = round64(sizeof(double) * 12u * n);
   LFX_HIP(c, g->upload.reserve(pose_bytes + sizeof(uint32_t) * n));
@@ -256,7 +246,7 @@ int lfx_occupancy_add_batch(lfx_ctx * c, lfx_occupancy * g, uint32_t n_scans, co
     LFX_HIP(c, hipGetLastError());
   }
   g->n += n;
-  return g->tail.done(c, st);
+  return call.finish();
 }
 
 int lfx_occupancy_set_poses(lfx_ctx * c, lfx_occupancy * g, uint32_t first, uint32_t count, const double * poses, void * stream)
@@ -266,14 +256,8 @@ int lfx_occupancy_set_poses(lfx_ctx * c, lfx_occupancy * g, uint32_t first, uint
   if (check_range(c, g, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!finite_all(poses, 12u * (size_t)count)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
-  LFX_HIP(c, g->upload.reserve(sizeof(double) * 12u * count));
-  std::memcpy(g->upload.p, poses, sizeof(double) * 12u * count);
-  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->upload.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
-  return g->tail.done(c, st);
+  Call k(c, stream);
+  return poses_set(k, g->tail, g->poses, g->upload, first, count, poses);
 }
 
 int lfx_occupancy_poses(lfx_ctx * c, const lfx_occupancy * g, uint32_t first, uint32_t count, double * poses_out, void * stream)
@@ -282,13 +266,8 @@ int lfx_occupancy_poses(lfx_ctx * c, const lfx_occupancy * g, uint32_t first, ui
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_range(c, g, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(poses_out, g->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  return LFX_OK;
+  Call k(c, stream);
+  return poses_get(k, g->tail, g->poses, first, count, poses_out);
 }
 
 int lfx_occupancy_follow(lfx_ctx * c, lfx_occupancy * g, const double * d_poses, uint32_t first, uint32_t count, void * stream)
@@ -297,12 +276,8 @@ int lfx_occupancy_follow(lfx_ctx * c, lfx_occupancy * g, const double * d_poses,
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_range(c, g, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, d_poses + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToDevice, st));
-  return g->tail.done(c, st);
+  Call k(c, stream);
+  return poses_follow(k, g->tail, g->poses, d_poses, first, count);
 }
 
 int lfx_occupancy_truncate(lfx_ctx * c, lfx_occupancy * g, uint32_t n_scans, void * stream)
@@ -322,15 +297,15 @@ int lfx_occupancy_clear(lfx_ctx * c, lfx_occupancy * g, void * stream)
 {
   if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(g->tail));
   const size_t cells = (size_t)g->cfg.width * g->cfg.height;
   LFX_HIP(c, hipMemsetAsync(g->hits.p, 0, sizeof(uint32_t) * cells, st));
   LFX_HIP(c, hipMemsetAsync(g->misses.p, 0, sizeof(uint32_t) * cells, st));
   LFX_HIP(c, hipMemsetAsync(g->counters.p, 0, sizeof(unsigned long long) * lfx::kOccCounters, st));
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_occupancy_render(lfx_ctx * c, lfx_occupancy * g, uint32_t first, uint32_t count, void * stream)
@@ -339,10 +314,10 @@ int lfx_occupancy_render(lfx_ctx * c, lfx_occupancy * g, uint32_t first, uint32_
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_range(c, g, first, count) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(g->tail));
   const uint32_t C = g->cfg.chunk_scans;
   lfx::OccRenderArgs a{};
   a.beams = g->beams.p;
@@ -361,19 +336,17 @@ int lfx_occupancy_render(lfx_ctx * c, lfx_occupancy * g, uint32_t first, uint32_
     hipLaunchKernelGGL(lfx::occupancy_fold_kernel, dim3(blocks_for(a.words / 4u, lfx::kOccThreads), a.scans), threads, 0, st, a);
     LFX_HIP(c, hipGetLastError());
   }
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_occupancy_counters(lfx_ctx * c, const lfx_occupancy * g, lfx_occupancy_counters_t * counters, void * stream)
 {
   if (!c || !g || !counters) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(g->readback.p, g->counters.p, sizeof(*counters), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(g->tail));
+  LFX_TRY(read_block(c, g->readback, g->counters.p, sizeof(*counters), k.st));
   std::memcpy(counters, g->readback.p, sizeof(*counters));
   return LFX_OK;
 }
@@ -382,15 +355,12 @@ int lfx_occupancy_emit(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_
 {
   if (!c || !g || !config || !out) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_grid(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = put_lut(c, g, *config, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = launch_emit(c, g, *config, out, st);
-  if (rc != LFX_OK) {return rc;}
-  return g->tail.done(c, st);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(put_lut(k, g, *config));
+  LFX_TRY(k.behind(g->tail));
+  LFX_TRY(launch_emit(c, g, *config, out, k.st));
+  return k.finish();
 }
 
 int lfx_occupancy_save(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_config * config, const char * dirname, int occupied_percent,
@@ -401,21 +371,19 @@ int lfx_occupancy_save(lfx_ctx * c, lfx_occupancy * g, const lfx_occupancy_emit_
   if (free_percent < 0 || !(free_percent < occupied_percent) || occupied_percent > 100) {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the thresholds must be 0 <= free_percent < occupied_percent <= 100");
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = put_lut(c, g, *config, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = g->tail.settle(c);                // (the image block may move)
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(put_lut(k, g, *config));
+  LFX_TRY(k.wait(g->tail));              // (the image block may move)
   const size_t cells = (size_t)g->cfg.width * g->cfg.height;
   if (g->image.reserve(cells) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pinned block of the grid");}
-  rc = launch_emit(c, g, *config, reinterpret_cast<int8_t *>(g->image.p), st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(launch_emit(c, g, *config, reinterpret_cast<int8_t *>(g->image.p), st));
   LFX_HIP(c, hipStreamSynchronize(st));
-  rc = lfx_occupancy_write_map(dirname, reinterpret_cast<const int8_t *>(g->image.p), g->cfg.width, g->cfg.height, g->cfg.resolution, g->cfg.origin_x,
+  const int rc = lfx_occupancy_write_map(dirname, reinterpret_cast<const int8_t *>(g->image.p), g->cfg.width, g->cfg.height, g->cfg.resolution, g->cfg.origin_x,
       g->cfg.origin_y, occupied_percent, free_percent);
   if (rc != LFX_OK) {return fail(c, rc, std::string("cannot write map.pgm and map.yaml in ") + dirname);}
-  return LFX_OK;
+  return k.finish();                     // (the tail once more where a table went up: the call took it there)
 }
 
 }  // extern "C"

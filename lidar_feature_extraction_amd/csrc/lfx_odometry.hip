@@ -262,6 +262,8 @@ int update_deskewed(lfx_ctx * c, lfx_odometry * o, lfx_odometry_result * results
 }
 }  // namespace
 
+const Tail & lfx_host::odometry_tail(const lfx_odometry * o) {return o->tail;}
+
 extern "C" {
 
 void lfx_odometry_default_config(lfx_odometry_config * cfg)

@@ -103,19 +103,16 @@ int launch_norms(lfx_ctx * c, const float * d_desc, double * d_norms, uint32_t n
 }
 
 // n descriptors on the device appended: all or nothing
-int add_device(lfx_ctx * c, lfx_place_db * db, const float * d_desc, uint32_t n, hipStream_t st)
+int add_device(Call & k, lfx_place_db * db, const float * d_desc, uint32_t n)
 {
   const size_t cells = cells_of(db->cfg);
   float * dst = db->desc.p + (size_t)db->n * cells;
-  // (the add before may be queued on another stream: the event below then stands for both)
-  const int rb = db->added.order_behind(c, st);
-  if (rb != LFX_OK) {return rb;}
+  // (the add before may be queued on another stream: the event recorded at the end then stands for both)
+  LFX_TRY(k.behind(db->added));
   // (hipMemcpyDefault: d_desc may be pinned host memory, lfx_host_alloc, which a kernel writes as it writes device memory)
-  LFX_HIP(c, hipMemcpyAsync(dst, d_desc, sizeof(float) * cells * n, hipMemcpyDefault, st));
-  const int rc = launch_norms(c, dst, db->norms.p + (size_t)db->n * db->cfg.n_sectors, n, db->cfg, st);
-  if (rc != LFX_OK) {return rc;}
-  const int rd = db->added.done(c, st);
-  if (rd != LFX_OK) {return rd;}
+  LFX_HIP(k.c, hipMemcpyAsync(dst, d_desc, sizeof(float) * cells * n, hipMemcpyDefault, k.st));
+  LFX_TRY(launch_norms(k.c, dst, db->norms.p + (size_t)db->n * db->cfg.n_sectors, n, db->cfg, k.st));
+  LFX_TRY(k.finish());
   db->n += n;
   return LFX_OK;
 }
@@ -151,10 +148,11 @@ int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uin
   if (!c->last_points) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch's input points are not known");}
   const uint32_t R = cfg->n_rings, S = cfg->n_sectors;
   const size_t doubles = lfx::sc_table_doubles(R, S), total = (size_t)n_scans * R * S;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  hipStream_t st = k.st;
   lfx_ctx::PlaceSlot * slot;
-  const int rs = take_slot(c, doubles, total, slot);
-  if (rs != LFX_OK) {return rs;}
+  LFX_TRY(take_slot(c, doubles, total, slot));
+  LFX_TRY(k.take(slot->table.used));     // (settled by take_slot)
   std::memcpy(slot->table.h.p, table, sizeof(double) * doubles);
   LFX_HIP(c, hipMemcpyAsync(slot->table.d.p, slot->table.h.p, sizeof(double) * doubles, hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipMemsetAsync(slot->keys.p, 0, sizeof(uint32_t) * total, st));
@@ -171,7 +169,7 @@ int lfx_scan_context_batch(lfx_ctx * c, const lfx_scan_context_config * cfg, uin
   hipLaunchKernelGGL(lfx::scan_context_finish_kernel, dim3(blocks_for(total, lfx::kPlaceThreads)), dim3(lfx::kPlaceThreads), 0, st,
     slot->keys.p, d_desc_out, total, cfg->sensor_height);
   LFX_HIP(c, hipGetLastError());
-  return slot->table.used.done(c, st);
+  return k.finish();
 }
 
 int lfx_place_db_create(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32_t capacity, lfx_place_db ** out)
@@ -198,20 +196,16 @@ int lfx_place_db_create(lfx_ctx * c, const lfx_scan_context_config * cfg, uint32
   return LFX_OK;
 }
 
-void lfx_place_db_destroy(lfx_place_db * db)
-{
-  if (!db) {return;}
-  (void)hipSetDevice(db->device);
-  delete db;
-}
+void lfx_place_db_destroy(lfx_place_db * db) {destroy_on(db);}
 
 int lfx_place_db_add(lfx_ctx * c, lfx_place_db * db, const float * d_desc, uint32_t n, void * stream)
 {
   if (!c || !db || (n && !d_desc)) {return LFX_ERR_INVALID_ARGUMENT;}
   const int rc = check_add(c, db, n);
   if (rc != LFX_OK || n == 0) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  return add_device(c, db, d_desc, n, static_cast<hipStream_t>(stream));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  return add_device(k, db, d_desc, n);
 }
 
 int lfx_place_db_add_host(lfx_ctx * c, lfx_place_db * db, const float * desc, uint32_t n, void * stream)
@@ -219,16 +213,14 @@ int lfx_place_db_add_host(lfx_ctx * c, lfx_place_db * db, const float * desc, ui
   if (!c || !db || (n && !desc)) {return LFX_ERR_INVALID_ARGUMENT;}
   const int rc = check_add(c, db, n);
   if (rc != LFX_OK || n == 0) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // (the add before may still read the staged descriptors, on whichever stream)
-  const int rs = db->added.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(db->added));           // (the add before may still read the staged descriptors, on whichever stream)
   const size_t floats = (size_t)n * cells_of(db->cfg);
   if (hold(db->staged, floats) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the descriptors");}
-  LFX_HIP(c, hipMemcpyAsync(db->staged.p, desc, sizeof(float) * floats, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(db->staged.p, desc, sizeof(float) * floats, hipMemcpyHostToDevice, k.st));
   // (pageable memory has been read when the copy returns; a pinned block must not be rewritten before `stream` passes it)
-  return add_device(c, db, db->staged.p, n, st);
+  return add_device(k, db, db->staged.p, n);
 }
 
 int lfx_place_db_size(const lfx_place_db * db, uint32_t * n)
@@ -244,10 +236,10 @@ int lfx_place_db_download(lfx_ctx * c, const lfx_place_db * db, uint32_t first, 
   if (check_db(c, db) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (first > db->n || count > db->n - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "entries outside the place index");}
   if (count == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rb = db->added.order_behind(c, st);
-  if (rb != LFX_OK) {return rb;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(db->added));
   const size_t cells = cells_of(db->cfg);
   LFX_HIP(c, hipMemcpyAsync(desc_out, db->desc.p + (size_t)first * cells, sizeof(float) * cells * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -262,8 +254,9 @@ int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_des
   if (n_queries == 0 || n_queries > 65535u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_queries must be in 1 .. 65535");}
   if (k < 1u || k > LFX_PLACE_MAX_MATCHES) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "k must be in 1 .. 16");}
   if (first > db->n || count > db->n - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "entries outside the place index");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call call(c, stream);
+  hipStream_t st = call.st;
+  LFX_TRY(call.open());
   const uint32_t R = db->cfg.n_rings, S = db->cfg.n_sectors;
   const size_t cells = (size_t)R * S, pairs = (size_t)n_queries * count, n_matches = (size_t)n_queries * k;
   if (hold(db->query_norms, (size_t)n_queries * S) != hipSuccess || hold(db->best_distance, pairs) != hipSuccess ||
@@ -273,11 +266,9 @@ int lfx_place_db_query(lfx_ctx * c, const lfx_place_db * db, const float * d_des
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
   }
-  const int rb = db->added.order_behind(c, st);
-  if (rb != LFX_OK) {return rb;}
+  LFX_TRY(call.read(db->added));
   lfx_scan_context_config cfg = db->cfg;
-  const int rn = launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st);
-  if (rn != LFX_OK) {return rn;}
+  LFX_TRY(launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st));
   if (count) {
     lfx::PlaceCompareArgs a{};
     a.query = d_desc; a.query_norms = db->query_norms.p;
@@ -314,8 +305,9 @@ int lfx_place_db_query_gated(lfx_ctx * c, const lfx_place_db * db, const float *
     }
     stride = std::max(stride, gates[q].limit);
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call call(c, stream);
+  hipStream_t st = call.st;
+  LFX_TRY(call.open());
   const uint32_t R = db->cfg.n_rings, S = db->cfg.n_sectors;
   const size_t pairs = (size_t)n_queries * stride, n_matches = (size_t)n_queries * k;
   if (hold(db->query_norms, (size_t)n_queries * S) != hipSuccess || hold(db->best_distance, pairs) != hipSuccess ||
@@ -327,15 +319,13 @@ int lfx_place_db_query_gated(lfx_ctx * c, const lfx_place_db * db, const float *
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the query's workspace");
   }
-  const int rb = db->added.order_behind(c, st);
-  if (rb != LFX_OK) {return rb;}
+  LFX_TRY(call.read(db->added));
   // (the call is synchronous: the pinned blocks are free again when it returns)
   static_assert(sizeof(lfx::PlaceGate) == sizeof(lfx_place_gate), "the kernel's gate is the header's");
   std::memcpy(db->h_gates.p, gates, sizeof(lfx::PlaceGate) * n_queries);
   LFX_HIP(c, hipMemcpyAsync(db->gates.p, db->h_gates.p, sizeof(lfx::PlaceGate) * n_queries, hipMemcpyHostToDevice, st));
   lfx_scan_context_config cfg = db->cfg;
-  const int rn = launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st);
-  if (rn != LFX_OK) {return rn;}
+  LFX_TRY(launch_norms(c, d_desc, db->query_norms.p, n_queries, cfg, st));
   hipLaunchKernelGGL(lfx::place_gate_kernel, dim3(n_queries), dim3(lfx::kPlaceThreads), 0, st, db->gates.p, d_poses, radius * radius, stride, db->list.p,
     db->n_eligible.p);
   LFX_HIP(c, hipGetLastError());

@@ -89,11 +89,12 @@ lfx::PgArgs args_of(lfx_pose_graph * g)
 }
 
 // the lists the kernels walk: node_begin [N + 1], inc [2 E], chain_edge [N], loop_edge [L], one block
-int upload_topology(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
+int upload_topology(Call & call, lfx_pose_graph * g)
 {
+  lfx_ctx * c = call.c;
+  hipStream_t st = call.st;
   const uint32_t N = g->n_nodes, E = g->n_edges, L = g->n_loop;
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  LFX_TRY(call.after(g->tail));
   std::vector<uint32_t> & w = g->stage_lists;
   w.assign((size_t)N + 1u + 2u * (size_t)E + N + L, 0u);
   uint32_t * begin = w.data(), * inc = begin + N + 1u, * chain = inc + 2u * (size_t)E, * loops = chain + N;
@@ -270,18 +271,18 @@ int check_marginals(lfx_ctx * c, const lfx_pose_graph * g)
 
 // Every node's Sigma_kk on the device (cov), G_k, T_k and V beside it for the joint blocks: the whole graph's work, once per
 // optimise.  Synchronous: the status word comes back.  The kernels run on the covariances' own status word.
-int ensure_marginals(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
+int ensure_marginals(Call & k, lfx_pose_graph * g)
 {
-  if (g->marg_current) {return g->tail.order_behind(c, st);}
-  int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  if (g->marg_current) {return k.read(g->tail);}
+  lfx_ctx * c = k.c;
+  hipStream_t st = k.st;
+  LFX_TRY(k.behind(g->tail));
   lfx::PgArgs a = args_of(g);
   a.status = g->mstatus.p;
   const lfx::PgMargArgs m = marg_args_of(g);
   const uint32_t n = 6u * a.n_loop;
   LFX_HIP(c, hipMemsetAsync(g->mstatus.p, 0, sizeof(uint32_t), st));
-  rc = launch_factor(c, a, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(launch_factor(c, a, st));
   hipLaunchKernelGGL(lfx::pose_graph_chain_inverse_kernel, dim3(1), dim3(lfx::kPgWave), 0, st, a, m);
   LFX_HIP(c, hipGetLastError());
   if (n) {
@@ -290,12 +291,10 @@ int ensure_marginals(lfx_ctx * c, lfx_pose_graph * g, hipStream_t st)
   }
   hipLaunchKernelGGL(lfx::pose_graph_marginal_kernel, dim3(a.n_nodes), dim3(n > 64u ? lfx::kPgThreads : lfx::kPgWave), 0, st, a, m);
   LFX_HIP(c, hipGetLastError());
-  uint32_t * word = reinterpret_cast<uint32_t *>(g->h_record.p);
-  LFX_HIP(c, hipMemcpyAsync(word, g->mstatus.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  g->marg_code = *word == lfx::kPgOk ? LFX_POSE_GRAPH_CONVERGED : LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE;
+  LFX_TRY(read_block(c, g->h_record, g->mstatus.p, sizeof(uint32_t), st));
+  g->marg_code = *reinterpret_cast<const uint32_t *>(g->h_record.p) == lfx::kPgOk ? LFX_POSE_GRAPH_CONVERGED : LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE;
   g->marg_current = true;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 }  // namespace
@@ -317,8 +316,7 @@ int lfx_pose_graph_create(lfx_ctx * c, const lfx_pose_graph_config * config, lfx
 {
   if (!c) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!config || !out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "config and out are required");}
-  const int rc = check_config(c, config);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_config(c, config));
   LFX_HIP(c, hipSetDevice(c->device));
   lfx_pose_graph * g = new (std::nothrow) lfx_pose_graph();
   if (!g) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph");}
@@ -327,19 +325,14 @@ int lfx_pose_graph_create(lfx_ctx * c, const lfx_pose_graph_config * config, lfx
   const size_t N = config->max_nodes, E = config->max_edges, L = config->max_loop_edges, n = 6u * L;
   g->ldy_cap = ldy_of(config->max_loop_edges);
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_pose_graph_destroy(g); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(g->poses, 12u * N); get(g->backup, 12u * N); get(g->d_fixed, N); get(g->edges, E); get(g->lin, (size_t)lfx::kPgLin * E);
-  get(g->loop_j, 72u * std::max<size_t>(L, 1u)); get(g->node_begin, N + 1u); get(g->inc, 2u * E); get(g->d_chain_edge, N);
-  get(g->loop_edge, std::max<size_t>(L, 1u)); get(g->grad, 6u * N); get(g->diag, 36u * N); get(g->off, 36u * N); get(g->fac_l, 36u * N);
-  get(g->fac_m, 36u * N); get(g->y, 6u * N * g->ldy_cap); get(g->s, std::max<size_t>(n * n, 1u)); get(g->z, std::max<size_t>(n, 1u));
-  get(g->step_max, N); get(g->status, 1u); get(g->record, (size_t)config->max_iter + 2u);
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's " + std::to_string(bytes) + " bytes");}
-  g->device_bytes = bytes;
+  DevTotal m;
+  m.get(g->poses, 12u * N); m.get(g->backup, 12u * N); m.get(g->d_fixed, N); m.get(g->edges, E); m.get(g->lin, (size_t)lfx::kPgLin * E);
+  m.get(g->loop_j, 72u * std::max<size_t>(L, 1u)); m.get(g->node_begin, N + 1u); m.get(g->inc, 2u * E); m.get(g->d_chain_edge, N);
+  m.get(g->loop_edge, std::max<size_t>(L, 1u)); m.get(g->grad, 6u * N); m.get(g->diag, 36u * N); m.get(g->off, 36u * N); m.get(g->fac_l, 36u * N);
+  m.get(g->fac_m, 36u * N); m.get(g->y, 6u * N * g->ldy_cap); m.get(g->s, std::max<size_t>(n * n, 1u)); m.get(g->z, std::max<size_t>(n, 1u));
+  m.get(g->step_max, N); m.get(g->status, 1u); m.get(g->record, (size_t)config->max_iter + 2u);
+  if (!m.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, m.refusal("the pose graph"));}
+  g->device_bytes = m.bytes;
   if (g->h_record.reserve(sizeof(lfx::PgRecord) * ((size_t)config->max_iter + 2u)) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the pose graph's status record");
   }
@@ -352,12 +345,7 @@ int lfx_pose_graph_create(lfx_ctx * c, const lfx_pose_graph_config * config, lfx
   return LFX_OK;
 }
 
-void lfx_pose_graph_destroy(lfx_pose_graph * g)
-{
-  if (!g) {return;}
-  (void)hipSetDevice(g->device);
-  delete g;
-}
+void lfx_pose_graph_destroy(lfx_pose_graph * g) {destroy_on(g);}
 
 int lfx_pose_graph_info(const lfx_pose_graph * g, lfx_pose_graph_info_t * info)
 {
@@ -378,22 +366,20 @@ int lfx_pose_graph_add_nodes(lfx_ctx * c, lfx_pose_graph * g, const double * pos
   }
   if (first_id) {*first_id = g->n_nodes;}
   if (n == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(g->tail));
   const uint32_t first = g->n_nodes;
-  std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * n);
   g->fixed.resize((size_t)first + n, 0);
   g->chain_edge.resize((size_t)first + n, lfx::kPgNone);
   if (first == 0u) {g->fixed[0] = (!g->released || g->first_fixed) ? 1 : 0;}
-  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * n, hipMemcpyHostToDevice, st));
-  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + first, g->fixed.data() + first, n, hipMemcpyHostToDevice, st));
+  LFX_TRY(send_block(c, g->h_poses, g->poses.p + 12u * (size_t)first, poses, sizeof(double) * 12u * n, k.st));
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + first, g->fixed.data() + first, n, hipMemcpyHostToDevice, k.st));
   g->n_nodes += n;
   g->topology_stale = true;
   g->linearised = false;
   g->marg_current = false;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int fixed, void * stream)
@@ -401,16 +387,15 @@ int lfx_pose_graph_set_fixed(lfx_ctx * c, lfx_pose_graph * g, uint32_t node, int
   if (!c || !g) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (node >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "node " + std::to_string(node) + " is not in the graph");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(g->tail));
   if (node == 0u) {g->first_fixed = fixed != 0;}
   g->marg_current = false;
   g->fixed_stale = true;
   g->fixed[node] = ((node == 0u && !g->released) || fixed) ? 1 : 0;
-  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, st));
-  return g->tail.done(c, st);
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p + node, g->fixed.data() + node, 1, hipMemcpyHostToDevice, k.st));
+  return k.finish();
 }
 
 int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_graph_edge * edges, uint32_t n, void * stream)
@@ -449,10 +434,9 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
              " loop edges: no room for " + std::to_string(loops) + " more");
   }
   if (n == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call call(c, stream);
+  LFX_TRY(call.open());
+  LFX_TRY(call.after(g->tail));
   g->stage_edges.resize(n);
   for (uint32_t k = 0; k < n; k++) {
     lfx::PgEdge & d = g->stage_edges[k];
@@ -460,7 +444,7 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
     std::memcpy(d.z, edges[k].z, sizeof(d.z));
     std::memcpy(d.omega, edges[k].information, sizeof(d.omega));
   }
-  LFX_HIP(c, hipMemcpyAsync(g->edges.p + g->n_edges, g->stage_edges.data(), sizeof(lfx::PgEdge) * n, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(g->edges.p + g->n_edges, g->stage_edges.data(), sizeof(lfx::PgEdge) * n, hipMemcpyHostToDevice, call.st));
   for (uint32_t k = 0; k < n; k++) {
     g->edge_i.push_back(edges[k].i); g->edge_j.push_back(edges[k].j); g->edge_loop.push_back(loop_of[k]);
     if (loop_of[k] == lfx::kPgNone) {g->chain_edge[edges[k].i] = g->n_edges + k; g->n_chain++;}
@@ -470,7 +454,7 @@ int lfx_pose_graph_add_edges(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gra
   g->topology_stale = true;
   g->linearised = false;
   g->marg_current = false;
-  return g->tail.done(c, st);
+  return call.finish();
 }
 
 int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_result * result, void * stream)
@@ -478,33 +462,26 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
   if (!c || !g || !result) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (g->n_edges == 0u && g->n_priors == 0u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose graph has no edges");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (g->topology_stale) {
-    const int ru = upload_topology(c, g, st);
-    if (ru != LFX_OK) {return ru;}
-  }
-  int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  if (g->topology_stale) {LFX_TRY(upload_topology(k, g));}
+  LFX_TRY(k.behind(g->tail));
   const lfx::PgArgs a = args_of(g);
   g->marg_current = false;
   const size_t pose_bytes = sizeof(double) * 12u * g->n_nodes;
   LFX_HIP(c, hipMemcpyAsync(g->backup.p, g->poses.p, pose_bytes, hipMemcpyDeviceToDevice, st));
   LFX_HIP(c, hipMemsetAsync(g->status.p, 0, sizeof(uint32_t), st));
-  rc = launch_linearize(c, a, 0u, false, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(launch_linearize(c, a, 0u, false, st));
   const lfx::PgRecord * rec = reinterpret_cast<const lfx::PgRecord *>(g->h_record.p);
   uint32_t it = 0;
   bool converged = false, refused = false;
   while (it < g->cfg.max_iter) {
     it++;
-    rc = launch_step(c, a, st);
-    if (rc != LFX_OK) {return rc;}
-    rc = launch_linearize(c, a, it, true, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(launch_step(c, a, st));
+    LFX_TRY(launch_linearize(c, a, it, true, st));
     // the iteration's only wait: its record (chi^2 at the new poses, the largest step, the status word)
-    LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord) * ((size_t)it + 1u), hipMemcpyDeviceToHost, st));
-    LFX_HIP(c, hipStreamSynchronize(st));
+    LFX_TRY(read_block(c, g->h_record, g->record.p, sizeof(lfx::PgRecord) * ((size_t)it + 1u), st));
     if (rec[it].status != lfx::kPgOk) {refused = true; break;}
     if (rec[it].max_step < g->cfg.tolerance) {converged = true; break;}
     if (!(rec[it].max_step == rec[it].max_step)) {break;}          // (not a number: nothing more to learn)
@@ -517,10 +494,8 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
   const bool diverged = !refused && (!(last == last) || !(rec[it].max_step == rec[it].max_step) || last > first + 1e-12 * std::max(1.0, first));
   if (refused || diverged) {
     LFX_HIP(c, hipMemcpyAsync(g->poses.p, g->backup.p, pose_bytes, hipMemcpyDeviceToDevice, st));
-    rc = relinearize(c, g, a, st);
-    if (rc != LFX_OK) {return rc;}
-    LFX_HIP(c, hipMemcpyAsync(g->h_record.p, g->record.p, sizeof(lfx::PgRecord), hipMemcpyDeviceToHost, st));
-    LFX_HIP(c, hipStreamSynchronize(st));
+    LFX_TRY(relinearize(c, g, a, st));
+    LFX_TRY(read_block(c, g->h_record, g->record.p, sizeof(lfx::PgRecord), st));
     result->code = refused ? LFX_POSE_GRAPH_NOT_POSITIVE_DEFINITE : LFX_POSE_GRAPH_DIVERGED;
     result->iterations = refused ? (int32_t)it - 1 : (int32_t)it;
     result->chi2_final = first;
@@ -537,7 +512,7 @@ int lfx_pose_graph_optimize(lfx_ctx * c, lfx_pose_graph * g, lfx_pose_graph_resu
   }
   g->linearised = true;
   g->fixed_stale = false;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_pose_graph_poses(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * poses_out, void * stream)
@@ -546,13 +521,8 @@ int lfx_pose_graph_poses(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, 
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
   if (count == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(poses_out, g->poses.p + 12u * (size_t)first, sizeof(double) * 12u * count, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  return LFX_OK;
+  Call k(c, stream);
+  return poses_get(k, g->tail, g->poses, first, count, poses_out);
 }
 
 int lfx_pose_graph_set_poses(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, uint32_t count, const double * poses, void * stream)
@@ -562,24 +532,22 @@ int lfx_pose_graph_set_poses(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, ui
   if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
   if (!finite_all(poses, 12u * (size_t)count)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a pose that is not finite");}
   if (count == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
-  std::memcpy(g->h_poses.p, poses, sizeof(double) * 12u * count);
-  LFX_HIP(c, hipMemcpyAsync(g->poses.p + 12u * (size_t)first, g->h_poses.p, sizeof(double) * 12u * count, hipMemcpyHostToDevice, st));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(g->tail));
+  LFX_TRY(send_block(c, g->h_poses, g->poses.p + 12u * (size_t)first, poses, sizeof(double) * 12u * count, k.st));
   g->linearised = false;
   g->marg_current = false;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_pose_graph_view(lfx_ctx * c, const lfx_pose_graph * g, const double ** d_poses, uint32_t * n_nodes, void * stream)
 {
   if (!c || !g || !d_poses || !n_nodes) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rc = g->tail.order_behind(c, static_cast<hipStream_t>(stream));
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(g->tail));
   *d_poses = g->poses.p;
   *n_nodes = g->n_nodes;
   return LFX_OK;
@@ -592,10 +560,10 @@ int lfx_pose_graph_edge_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t fir
   if (first > g->n_edges || count > g->n_edges - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "edges outside the pose graph");}
   if (!g->linearised) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the graph has changed since the last lfx_pose_graph_optimize");}
   if (count == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = g->tail.settle(c);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.wait(g->tail));              // (the staging vector is the graph's)
   g->stage_lin.resize((size_t)lfx::kPgLin * count);
   LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->lin.p + (size_t)lfx::kPgLin * first, sizeof(double) * lfx::kPgLin * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -667,10 +635,9 @@ int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gr
              " priors (lfx_pose_graph_reserve_priors): no room for " + std::to_string(n) + " more");
   }
   if (n == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call call(c, stream);
+  LFX_TRY(call.open());
+  LFX_TRY(call.after(g->tail));
   g->stage_priors.resize(n);
   for (uint32_t k = 0; k < n; k++) {
     lfx::PgPrior & d = g->stage_priors[k];
@@ -679,13 +646,13 @@ int lfx_pose_graph_add_priors(lfx_ctx * c, lfx_pose_graph * g, const lfx_pose_gr
     std::memcpy(d.omega, priors[k].information, sizeof(d.omega));
     std::memcpy(d.lever, priors[k].lever, sizeof(d.lever));
   }
-  LFX_HIP(c, hipMemcpyAsync(g->priors.p + g->n_priors, g->stage_priors.data(), sizeof(lfx::PgPrior) * n, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(g->priors.p + g->n_priors, g->stage_priors.data(), sizeof(lfx::PgPrior) * n, hipMemcpyHostToDevice, call.st));
   for (uint32_t k = 0; k < n; k++) {g->prior_node.push_back(priors[k].node);}
   g->n_priors += n;
   g->topology_stale = true;
   g->linearised = false;
   g->marg_current = false;
-  return g->tail.done(c, st);
+  return call.finish();
 }
 
 int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, void * stream)
@@ -696,13 +663,12 @@ int lfx_pose_graph_release_first(lfx_ctx * c, lfx_pose_graph * g, int released, 
   g->marg_current = false;
   g->fixed_stale = true;
   if (g->n_nodes == 0u) {return LFX_OK;}            // (lfx_pose_graph_add_nodes writes node 0's flag)
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rs = g->tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(g->tail));
   g->fixed[0] = (!g->released || g->first_fixed) ? 1 : 0;
-  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p, g->fixed.data(), 1, hipMemcpyHostToDevice, st));
-  return g->tail.done(c, st);
+  LFX_HIP(c, hipMemcpyAsync(g->d_fixed.p, g->fixed.data(), 1, hipMemcpyHostToDevice, k.st));
+  return k.finish();
 }
 
 int lfx_pose_graph_prior_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t first, uint32_t count, double * rho, double * w, void * stream)
@@ -712,10 +678,10 @@ int lfx_pose_graph_prior_chi2(lfx_ctx * c, const lfx_pose_graph * g, uint32_t fi
   if (first > g->n_priors || count > g->n_priors - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "priors outside the pose graph");}
   if (!g->linearised) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the graph has changed since the last lfx_pose_graph_optimize");}
   if (count == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = g->tail.settle(c);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.wait(g->tail));              // (the staging vector is the graph's)
   g->stage_lin.resize((size_t)lfx::kPgPlin * count);
   LFX_HIP(c, hipMemcpyAsync(g->stage_lin.data(), g->plin.p + (size_t)lfx::kPgPlin * first, sizeof(double) * lfx::kPgPlin * count, hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
@@ -762,17 +728,15 @@ int lfx_pose_graph_marginals(lfx_ctx * c, lfx_pose_graph * g, uint32_t first, ui
 {
   if (!c || !g || !code || (count && !cov_out)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  int rc = check_marginals(c, g);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_marginals(c, g));
   if (first > g->n_nodes || count > g->n_nodes - first) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "nodes outside the pose graph");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = ensure_marginals(c, g, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(ensure_marginals(k, g));
   *code = g->marg_code;
   if (g->marg_code != LFX_POSE_GRAPH_CONVERGED || count == 0u) {return LFX_OK;}
-  LFX_HIP(c, hipMemcpyAsync(cov_out, g->cov.p + 36u * (size_t)first, sizeof(double) * 36u * count, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  LFX_HIP(c, hipMemcpyAsync(cov_out, g->cov.p + 36u * (size_t)first, sizeof(double) * 36u * count, hipMemcpyDeviceToHost, k.st));
+  LFX_HIP(c, hipStreamSynchronize(k.st));
   return LFX_OK;
 }
 
@@ -780,22 +744,20 @@ int lfx_pose_graph_joint_covariances(lfx_ctx * c, lfx_pose_graph * g, const uint
 {
   if (!c || !g || !code || (n && (!pairs || !out))) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_graph(c, g) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  int rc = check_marginals(c, g);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_marginals(c, g));
   for (uint32_t p = 0; p < n; p++) {                  // every pair is checked before anything is queued or written
     const uint32_t i = pairs[2u * p], j = pairs[2u * p + 1u];
     const std::string which = "pair " + std::to_string(p) + " of the call: ";
     if (i >= g->n_nodes || j >= g->n_nodes) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "an id that is not a node of the graph");}
     if (i == j) {return fail(c, LFX_ERR_INVALID_ARGUMENT, which + "i == j");}
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = ensure_marginals(c, g, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(ensure_marginals(k, g));
   *code = g->marg_code;
   if (g->marg_code != LFX_POSE_GRAPH_CONVERGED || n == 0u) {return LFX_OK;}
-  rc = g->tail.settle(c);                             // (the staging vectors below are the graph's)
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.wait(g->tail));                           // (the staging vectors below are the graph's)
   lfx::PgArgs a = args_of(g);
   a.status = g->mstatus.p;
   const lfx::PgMargArgs m = marg_args_of(g);
@@ -839,17 +801,13 @@ int lfx_pose_graph_joint_covariances(lfx_ctx * c, lfx_pose_graph * g, const uint
 int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_out, double * grad_out, double * chi2_out, void * stream)
 {
   if (!c || !g || !grad_out || !chi2_out || g->n_edges == 0u) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (g->topology_stale) {
-    const int ru = upload_topology(c, g, st);
-    if (ru != LFX_OK) {return ru;}
-  }
-  int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  if (g->topology_stale) {LFX_TRY(upload_topology(k, g));}
+  LFX_TRY(k.behind(g->tail));
   const lfx::PgArgs a = args_of(g);
-  rc = relinearize(c, g, a, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(relinearize(c, g, a, st));
   std::vector<double> lin((size_t)lfx::kPgLin * g->n_edges);
   LFX_HIP(c, hipMemcpyAsync(lin.data(), g->lin.p, sizeof(double) * lin.size(), hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipMemcpyAsync(grad_out, g->grad.p, sizeof(double) * 6u * g->n_nodes, hipMemcpyDeviceToHost, st));
@@ -860,7 +818,7 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
   g->linearised = true;
   g->marg_current = false;
   g->fixed_stale = false;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 
 // ... and the same for a graph with priors (edges or none): per prior r [P][6] (may be NULL), per node the gradient of edges
@@ -868,17 +826,13 @@ int lfx_test_pose_graph_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_ou
 int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double * r_out, double * grad_out, double * chi2_out, void * stream)
 {
   if (!c || !g || !grad_out || !chi2_out || g->n_priors == 0u) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (g->topology_stale) {
-    const int ru = upload_topology(c, g, st);
-    if (ru != LFX_OK) {return ru;}
-  }
-  int rc = g->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  if (g->topology_stale) {LFX_TRY(upload_topology(k, g));}
+  LFX_TRY(k.behind(g->tail));
   const lfx::PgArgs a = args_of(g);
-  rc = relinearize(c, g, a, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(relinearize(c, g, a, st));
   std::vector<double> lin((size_t)lfx::kPgPlin * g->n_priors);
   LFX_HIP(c, hipMemcpyAsync(lin.data(), g->plin.p, sizeof(double) * lin.size(), hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipMemcpyAsync(grad_out, g->grad.p, sizeof(double) * 6u * g->n_nodes, hipMemcpyDeviceToHost, st));
@@ -889,7 +843,7 @@ int lfx_test_pose_graph_prior_linearize(lfx_ctx * c, lfx_pose_graph * g, double 
   g->linearised = true;
   g->marg_current = false;
   g->fixed_stale = false;
-  return g->tail.done(c, st);
+  return k.finish();
 }
 #endif
 

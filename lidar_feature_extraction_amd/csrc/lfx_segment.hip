@@ -12,16 +12,15 @@ using namespace lfx_host;
 
 namespace
 {
-// the workspace for `cells` cells, the call before waited for on `st`
-int take_workspace(lfx_ctx * c, size_t cells, hipStream_t st)
+// the workspace for `cells` cells, the call before waited for on the call's stream
+int take_workspace(Call & k, size_t cells)
 {
+  lfx_ctx * c = k.c;
   lfx_ctx::SegmentWork & w = c->seg;
-  int rc = w.used.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.behind(w.used));
   if (w.image.n < cells) {
     // (growing frees what the call before may still use; to the size asked for and no further: the budget is the most it takes)
-    rc = w.used.settle(c);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(k.after(w.used));
     if (hold(w.image, cells, true) != hipSuccess || hold(w.cell, cells, true) != hipSuccess || hold(w.parent, cells, true) != hipSuccess ||
       hold(w.csize, cells, true) != hipSuccess || hold(w.crowmax, cells, true) != hipSuccess)
     {
@@ -35,28 +34,25 @@ int take_workspace(lfx_ctx * c, size_t cells, hipStream_t st)
 
 // the config's tables on the device (*d_table): those of a config seen lately are there already; a new config's take the
 // next slot, whose pinned block is rewritten only once every call that used the workspace has passed (the event), and go up
-// on `st` without a wait -- the event is recorded again behind the copy, so a later refill waits for it too
-int put_tables(lfx_ctx * c, const lfx_segment_config & cfg, const std::vector<double> & table, hipStream_t st, const double ** d_table)
+// on the call's stream without a wait -- the event is recorded again behind the copy, so a later refill waits for it too
+int put_tables(Call & k, const lfx_segment_config & cfg, const std::vector<double> & table, const double ** d_table)
 {
+  lfx_ctx * c = k.c;
   lfx_ctx::SegmentWork & w = c->seg;
   for (lfx_ctx::SegmentWork::Table & t : w.tables) {
     if (t.columns == cfg.n_columns && t.row_step == cfg.row_step) {*d_table = t.d.p; return LFX_OK;}
   }
   lfx_ctx::SegmentWork::Table & t = w.tables[w.table_next];
   const size_t bytes = sizeof(double) * table.size();
-  if (t.columns) {                           // (a refill: what read the slot, and its block, is done)
-    const int rs = w.used.settle(c);
-    if (rs != LFX_OK) {return rs;}
-  }
+  if (t.columns) {LFX_TRY(k.after(w.used));}  // (a refill: what read the slot, and its block, is done)
   t.columns = 0;
   if (t.h.reserve(bytes) != hipSuccess || hold(t.d, table.size()) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the segmentation tables");
   }
   std::memcpy(t.h.p, table.data(), bytes);
-  LFX_HIP(c, hipMemcpyAsync(t.d.p, t.h.p, bytes, hipMemcpyHostToDevice, st));
-  const int rd = w.used.done(c, st);
-  if (rd != LFX_OK) {return rd;}
+  LFX_HIP(c, hipMemcpyAsync(t.d.p, t.h.p, bytes, hipMemcpyHostToDevice, k.st));
+  LFX_TRY(k.record());
   t.columns = cfg.n_columns;
   t.row_step = cfg.row_step;
   w.table_next = (w.table_next + 1u) % lfx_ctx::SegmentWork::kSegTables;
@@ -86,17 +82,16 @@ int lfx_segment_batch(lfx_ctx * c, const lfx_segment_config * cfg, uint32_t n_sc
   const int rb = check_last_batch(c, n_scans);
   if (rb != LFX_OK) {return rb;}
   if (!c->last_points) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the last batch's input points are not known");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
   const size_t cells = (size_t)H * W;
   const uint32_t per_chunk = (uint32_t)std::max<size_t>(1, LFX_SEGMENT_BUDGET_CELLS / cells);
   // (the chunk's scans are a grid's y dimension: 65 535 at most, which only images of a few cells reach)
   const uint32_t chunk_scans = std::min(std::min(per_chunk, n_scans), 65535u);
-  const int rw = take_workspace(c, cells * chunk_scans, st);
-  if (rw != LFX_OK) {return rw;}
+  LFX_TRY(take_workspace(k, cells * chunk_scans));
   const double * d_table = nullptr;
-  const int rt = put_tables(c, *cfg, table, st, &d_table);
-  if (rt != LFX_OK) {return rt;}
+  LFX_TRY(put_tables(k, *cfg, table, &d_table));
   lfx_ctx::SegmentWork & w = c->seg;
   if (d_counts_out) {LFX_HIP(c, hipMemsetAsync(d_counts_out, 0, sizeof(uint32_t) * 4u * n_scans, st));}
   lfx::SegmentArgs a{};
@@ -130,7 +125,7 @@ int lfx_segment_batch(lfx_ctx * c, const lfx_segment_config * cfg, uint32_t n_sc
     hipLaunchKernelGGL(xyz16 ? lfx::segment_record_kernel<true> : lfx::segment_record_kernel<false>, by_scan, threads, 0, st, a);
     LFX_HIP(c, hipGetLastError());
   }
-  return w.used.done(c, st);
+  return k.finish();
 }
 
 int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t edge_mask, uint32_t surface_mask, float * d_edge_out,
@@ -139,8 +134,9 @@ int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t e
   if (!c || !d_class || !d_edge_out || !d_surface_out || !d_offsets_out) {return LFX_ERR_INVALID_ARGUMENT;}
   if (c->last_batch == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "no batch has been extracted yet");}
   if ((edge_mask | surface_mask) > 15u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "a class mask has bits 0 .. 3 only");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
   const uint32_t batch = c->last_batch;
   lfx_ctx::SegmentWork & w = c->seg;
   lfx::SegmentPackArgs a{};
@@ -148,11 +144,9 @@ int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t e
     a.counts = d_counts_out;
   } else {
     // (the context's own: calls on different streams take them one behind the other, as the images)
-    int rc = w.used.order_behind(c, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(k.behind(w.used));
     if (w.pack_counts.n < 2u * (size_t)batch) {
-      rc = w.used.settle(c);
-      if (rc != LFX_OK) {return rc;}
+      LFX_TRY(k.after(w.used));
       if (hold(w.pack_counts, 2u * (size_t)batch) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the filtered pack's counts");
@@ -173,7 +167,7 @@ int lfx_pack_features_segmented(lfx_ctx * c, const uint8_t * d_class, uint32_t e
   launch_feature_offsets(a.counts, a.counts + batch, 1u, batch, d_offsets_out, st);
   hipLaunchKernelGGL(lfx::segment_pack_kernel, grid, threads, 0, st, a);
   LFX_HIP(c, hipGetLastError());
-  return d_counts_out ? LFX_OK : w.used.done(c, st);
+  return k.finish();                       // (with the caller's counts the call took no event)
 }
 
 }  // extern "C"

@@ -56,16 +56,11 @@ int lfx_visibility_create(lfx_ctx * c, const lfx_visibility_config * config, uin
   v->max_window = max_window;
   v->max_resident = max_resident_images;
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_visibility_destroy(v); return fail(c, code, why);};
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(v->images, (size_t)max_resident_images * H * W); get(v->table, table.size()); get(v->viewers, max_window);
-  get(v->counters, lfx::kVisCounters); get(v->words, LFX_VISIBILITY_SCRATCH_WORDS);
-  if (!ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the visibility object's " + std::to_string(bytes) + " bytes");}
-  v->device_bytes = bytes;
+  DevTotal m;
+  m.get(v->images, (size_t)max_resident_images * H * W); m.get(v->table, table.size()); m.get(v->viewers, max_window);
+  m.get(v->counters, lfx::kVisCounters); m.get(v->words, LFX_VISIBILITY_SCRATCH_WORDS);
+  if (!m.ok) {return give_up(LFX_ERR_OUT_OF_MEMORY, m.refusal("the visibility object"));}
+  v->device_bytes = m.bytes;
   if (v->pinned.reserve(counters_at(max_window) + sizeof(unsigned long long) * lfx::kVisCounters) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the visibility object's pinned block");
   }
@@ -76,12 +71,7 @@ int lfx_visibility_create(lfx_ctx * c, const lfx_visibility_config * config, uin
   return LFX_OK;
 }
 
-void lfx_visibility_destroy(lfx_visibility * v)
-{
-  if (!v) {return;}
-  (void)hipSetDevice(v->device);
-  delete v;
-}
+void lfx_visibility_destroy(lfx_visibility * v) {destroy_on(v);}
 
 int lfx_visibility_info(const lfx_visibility * v, lfx_visibility_info_t * info)
 {
@@ -133,18 +123,17 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
   for (int kind = 0; kind < 2; kind++) {
     if (hi[kind] - lo[kind] > 0x7FFFFFFFull * lfx::kVisThreads) {return fail(c, LFX_ERR_CAPACITY, "too many records for one launch");}
   }
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = v->tail.settle(c);             // the last run's copy of the list has left the pinned block
-  if (rc != LFX_OK) {return rc;}
+  Call call(c, stream);
+  hipStream_t st = call.st;
+  LFX_TRY(call.open());
+  LFX_TRY(call.after(v->tail));           // the last run's copy of the list has left the pinned block
   uint32_t * list = reinterpret_cast<uint32_t *>(v->pinned.p);
   unsigned long long * back = reinterpret_cast<unsigned long long *>(v->pinned.p + counters_at(v->max_window));
   uint32_t at = 0;
   for (uint32_t k = first; k < first + count; k++) {
     if (ks.begin[0][k + 1u] > ks.begin[0][k] || ks.begin[1][k + 1u] > ks.begin[1][k]) {list[at++] = k;}
   }
-  rc = ks.tail->order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(call.behind(*ks.tail));
   LFX_HIP(c, hipMemcpyAsync(v->viewers.p, list, sizeof(uint32_t) * n_viewers, hipMemcpyHostToDevice, st));
   LFX_HIP(c, hipMemsetAsync(v->counters.p, 0, sizeof(unsigned long long) * lfx::kVisCounters, st));
   const uint32_t H = v->cfg.n_rows, W = v->cfg.n_columns;
@@ -179,10 +168,7 @@ int lfx_visibility_run(lfx_ctx * c, lfx_visibility * v, const lfx_keyframes * ke
   }
   // the call's only wait: the counters
   LFX_HIP(c, hipMemcpyAsync(back, v->counters.p, sizeof(unsigned long long) * lfx::kVisCounters, hipMemcpyDeviceToHost, st));
-  rc = ks.tail->done(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = v->tail.done(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(call.finish());
   LFX_HIP(c, hipStreamSynchronize(st));
   result->n_pairs = back[lfx::kVisPairs];
   for (int kind = 0; kind < 2; kind++) {

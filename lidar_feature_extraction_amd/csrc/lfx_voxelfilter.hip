@@ -85,8 +85,7 @@ int plan_emit(lfx_ctx * c, lfx_voxel_filter * f, uint32_t min_points, lfx_voxel_
   hipLaunchKernelGGL(lfx::voxel_filter_scan_kernel, dim3(1), dim3(lfx::kVfThreads), 0, st, f->tile_before.p, n_tiles, f->counters.p);
   LFX_HIP(c, hipGetLastError());
   const uint64_t * h = reinterpret_cast<const uint64_t *>(f->readback.p);
-  LFX_HIP(c, hipMemcpyAsync(f->readback.p, f->counters.p, sizeof(uint64_t) * lfx::kVfCounters, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  LFX_TRY(read_block(c, f->readback, f->counters.p, sizeof(uint64_t) * lfx::kVfCounters, st));
   *r = lfx_voxel_filter_result{};
   r->n_records = f->base;
   r->n_accumulated = h[lfx::kVfValid] - h[lfx::kVfTableFull];
@@ -139,20 +138,14 @@ int lfx_voxel_filter_create(lfx_ctx * c, const lfx_voxel_filter_config * config,
   f->slots = (uint64_t)1 << config->log2_slots;
   const uint64_t n_words = (config->max_records + 31u) / 32u;
   const uint64_t n_tiles = (n_words + lfx::kVfTileWords - 1u) / lfx::kVfTileWords;
-  uint64_t bytes = 0;
-  bool ok = true;
-  auto get = [&](auto & buf, size_t count) {
-      ok = ok && buf.alloc(count) == hipSuccess;
-      bytes += (uint64_t)count * sizeof(*buf.p);
-    };
-  get(f->table, f->slots); get(f->bitmap, n_words); get(f->word_before, n_words); get(f->tile_before, n_tiles + 1u);
-  get(f->counters, lfx::kVfCounters); get(f->staging, std::min(kHostChunk, config->max_records));
-  if (!ok) {
-    (void)hipGetLastError();
+  DevTotal m;
+  m.get(f->table, f->slots); m.get(f->bitmap, n_words); m.get(f->word_before, n_words); m.get(f->tile_before, n_tiles + 1u);
+  m.get(f->counters, lfx::kVfCounters); m.get(f->staging, std::min(kHostChunk, config->max_records));
+  if (!m.ok) {
     lfx_voxel_filter_destroy(f);
-    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the voxel filter's " + std::to_string(bytes) + " bytes");
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, m.refusal("the voxel filter"));
   }
-  f->device_bytes = bytes;
+  f->device_bytes = m.bytes;
   if (f->readback.reserve(sizeof(uint64_t) * lfx::kVfCounters) != hipSuccess || f->upload.reserve(sizeof(float4) * f->staging.n) != hipSuccess) {
     (void)hipGetLastError();
     lfx_voxel_filter_destroy(f);
@@ -162,12 +155,7 @@ int lfx_voxel_filter_create(lfx_ctx * c, const lfx_voxel_filter_config * config,
   return LFX_OK;
 }
 
-void lfx_voxel_filter_destroy(lfx_voxel_filter * f)
-{
-  if (!f) {return;}
-  (void)hipSetDevice(f->device);
-  delete f;
-}
+void lfx_voxel_filter_destroy(lfx_voxel_filter * f) {destroy_on(f);}
 
 int lfx_voxel_filter_info(const lfx_voxel_filter * f, lfx_voxel_filter_info_t * info)
 {
@@ -186,17 +174,17 @@ int lfx_voxel_filter_reset(lfx_ctx * c, lfx_voxel_filter * f, float leaf, void *
   if (!c || !f) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_filter(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (!good_leaf(leaf)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "leaf must be finite and > 0, and so must 1 / leaf");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
   hipLaunchKernelGGL(lfx::voxel_filter_clear_kernel, dim3(entry_blocks(f)), dim3(lfx::kVfThreads), 0, st, f->table.p, f->slots);
   LFX_HIP(c, hipGetLastError());
   LFX_HIP(c, hipMemsetAsync(f->counters.p, 0, sizeof(unsigned long long) * lfx::kVfCounters, st));
   f->leaf = leaf;
   f->inv = 1.0f / leaf;
   f->base = 0u;
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_voxel_filter_add(lfx_ctx * c, lfx_voxel_filter * f, const float * d_points, uint64_t n_points, void * stream)
@@ -205,16 +193,14 @@ int lfx_voxel_filter_add(lfx_ctx * c, lfx_voxel_filter * f, const float * d_poin
   if (check_filter(c, f) != LFX_OK || check_reset(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (n_points == 0u) {return LFX_OK;}
   if (!d_points) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_points is required");}
-  int rc = check_ranks(c, f, n_points);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  launch_add(f, d_points, n_points, st);
+  LFX_TRY(check_ranks(c, f, n_points));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
+  launch_add(f, d_points, n_points, k.st);
   LFX_HIP(c, hipGetLastError());
   f->base += n_points;
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_voxel_filter_add_host(lfx_ctx * c, lfx_voxel_filter * f, const float * points, uint64_t n_points, void * stream)
@@ -223,23 +209,20 @@ int lfx_voxel_filter_add_host(lfx_ctx * c, lfx_voxel_filter * f, const float * p
   if (check_filter(c, f) != LFX_OK || check_reset(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (n_points == 0u) {return LFX_OK;}
   if (!points) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "points is required");}
-  int rc = check_ranks(c, f, n_points);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  LFX_TRY(check_ranks(c, f, n_points));
+  Call k(c, stream);
+  LFX_TRY(k.open());
   // in chunks of the staging buffer: the pinned block is rewritten once the chunk before has left it, the staging buffer is
-  // the stream's from one chunk to the next
+  // the stream's from one chunk to the next.  The one call that settles and records once per chunk, not once per call: the
+  // tail recorded behind a chunk is what the next chunk's settle waits for before the host writes the block again.
   for (uint64_t lo = 0; lo < n_points; lo += f->staging.n) {
     const uint64_t n = std::min<uint64_t>(f->staging.n, n_points - lo);
-    rc = f->tail.settle(c);
-    if (rc != LFX_OK) {return rc;}
-    std::memcpy(f->upload.p, points + 4u * (size_t)lo, sizeof(float4) * (size_t)n);
-    LFX_HIP(c, hipMemcpyAsync(f->staging.p, f->upload.p, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-    launch_add(f, reinterpret_cast<const float *>(f->staging.p), n, st);
+    LFX_TRY(k.after(f->tail));
+    LFX_TRY(send_block(c, f->upload, f->staging.p, points + 4u * (size_t)lo, sizeof(float4) * (size_t)n, k.st));
+    launch_add(f, reinterpret_cast<const float *>(f->staging.p), n, k.st);
     LFX_HIP(c, hipGetLastError());
     f->base += n;
-    rc = f->tail.done(c, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(k.finish());
   }
   return LFX_OK;
 }
@@ -250,24 +233,20 @@ int lfx_voxel_filter_emit(lfx_ctx * c, lfx_voxel_filter * f, uint32_t min_points
   if (!c || !f || !result) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check_filter(c, f) != LFX_OK || check_reset(c, f) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (min_points < 1u) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "min_points must be >= 1");}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = f->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
-  rc = plan_emit(c, f, min_points, result, st);
-  if (rc != LFX_OK) {return rc;}
-  if (result->n_table_full != 0u) {(void)f->tail.done(c, st); return table_full(c, f, *result);}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
+  LFX_TRY(plan_emit(c, f, min_points, result, k.st));
+  if (result->n_table_full != 0u) {return table_full(c, f, *result);}
   if (result->n_written > capacity_points) {
-    (void)f->tail.done(c, st);
     return fail(c, LFX_ERR_CAPACITY, "the filter holds " + std::to_string(result->n_written) + " voxels to write: more than capacity_points (" +
              std::to_string(capacity_points) + ")");
   }
   if (result->n_written > 0u) {
-    if (!d_out) {(void)f->tail.done(c, st); return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
-    rc = launch_write(c, f, min_points, reinterpret_cast<float4 *>(d_out), d_counts_out, 0u, capacity_points, st);
-    if (rc != LFX_OK) {return rc;}
+    if (!d_out) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "d_out is required");}
+    LFX_TRY(launch_write(c, f, min_points, reinterpret_cast<float4 *>(d_out), d_counts_out, 0u, capacity_points, k.st));
   }
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_voxel_filter_add_keyframes(lfx_ctx * c, lfx_voxel_filter * f, const lfx_keyframes * kf, int kind, uint32_t first, uint32_t count, int masked,
@@ -282,22 +261,19 @@ int lfx_voxel_filter_add_keyframes(lfx_ctx * c, lfx_voxel_filter * f, const lfx_
   if (masked && !ks.has_flags) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the store has no flags: lfx_keyframes_reserve_flags comes first");}
   const uint64_t lo = ks.begin[kind][first], hi = ks.begin[kind][first + count];
   if (hi == lo) {return LFX_OK;}
-  int rc = check_ranks(c, f, hi - lo);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = f->tail.order_behind(c, st);
-  if (rc == LFX_OK) {rc = ks.tail->order_behind(c, st);}
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(check_ranks(c, f, hi - lo));
+  Call k(c, stream);
+  hipStream_t st = k.st;
+  LFX_TRY(k.open());
+  LFX_TRY(k.behind(f->tail));
+  LFX_TRY(k.behind(*ks.tail));
   lfx::KfRange a{};
   a.rec_lo = lo; a.rec_hi = hi; a.k_lo = first; a.k_hi = first + count; a.first = first;
   hipLaunchKernelGGL(lfx::voxel_filter_add_keyframes_kernel, dim3((uint32_t)((hi - lo + lfx::kVfRun - 1u) / lfx::kVfRun)), dim3(lfx::kVfThreads), 0, st,
     f->table.p, f->cfg.log2_slots, f->inv, f->counters.p, ks.records[kind], ks.d_begin[kind], ks.poses, masked ? ks.flags[kind] : nullptr, f->base, a);
   LFX_HIP(c, hipGetLastError());
   f->base += hi - lo;
-  rc = ks.tail->done(c, st);
-  if (rc != LFX_OK) {return rc;}
-  return f->tail.done(c, st);
+  return k.finish();
 }
 
 int lfx_keyframes_save_filtered(lfx_ctx * c, const lfx_keyframes * kf, lfx_voxel_filter * f, const float leaf[2], uint32_t min_points, int masked,

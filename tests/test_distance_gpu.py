@@ -302,6 +302,36 @@ def test_from_occupancy_behind_a_render_on_the_other_stream(hold):
     del d
 
 
+def test_a_clear_on_the_other_stream_waits_for_a_held_from_occupancy(hold):
+    """The reader's half of the two-object call: a from_occupancy queued on a held stream B records the grid's event too, so
+    a clear of the grid issued on A while B is still held does not reach the counts before the transform has read them."""
+    from lidar_feature_extraction_amd import DistanceField
+    fx = S.fx33()
+    g, d = _grid33(fx)
+    g.render(stream=K.stream())
+    df, other = DistanceField(fx, 512, 512), DistanceField(fx, 512, 512)
+    other.from_grid(g.emit(stream=K.stream()), stream=K.stream(), inside=1)
+    want = other.fields(K.stream())
+    assert want[1].min() == 0 and (want[0] == D.OBSTACLE).sum() > 100
+    K.sync()
+    a, b = S.two_streams()
+    hold(b)
+    df.from_occupancy(g, stream=b.cuda_stream, inside=1)
+    e = S.event_behind(b)
+    hold.still_held(e, "distance: from_occupancy on B, clear of its grid on A")
+    g.clear(stream=a.cuda_stream)
+    got = df.fields(b.cuda_stream)
+    K.sync()
+    for name, x, y in zip(("classes", "d2", "i2"), got, want):
+        DC.same_bytes(x, y, ("a held reader", name))
+    hits, misses = g.counts(K.stream())
+    assert not hits.any() and not misses.any()               # (and the clear did run)
+    for o in (other, df, g):
+        o.close()
+    fx.close()
+    del d
+
+
 # --- the outputs --------------------------------------------------------------------------------------------------------------------
 def test_outputs_to_device_pinned_and_unaligned_memory(fx):
     """metres and costmap into device memory, into a pinned block and into a device pointer that is not 4-byte aligned (the

@@ -507,3 +507,31 @@ def test_producers_on_another_stream(fx, hold):
     for o in (m, df, g):
         o.close()
     del d
+
+
+def test_a_transform_on_the_other_stream_waits_for_a_held_set_field(fx, hold):
+    """The reader's half of the two-object call: a set_field queued on a held stream B records the distance field's event
+    too, so a transform of another grid into the same field, issued on A while B is still held, does not reach d2 before the
+    look-up has read it."""
+    from lidar_feature_extraction_amd import DistanceField, grid_match_table
+    cfg = GC.e2e_config()
+    geom = G.geometry(cfg.width, cfg.height, cfg.resolution, cfg.origin_x, cfg.origin_y)
+    d_first = _up(GC.random_grid(cfg.height, cfg.width, 0.01, seed=50))
+    d_second = _up(GC.random_grid(cfg.height, cfg.width, 0.01, seed=51))
+    df = DistanceField(fx, cfg.width, cfg.height)
+    m = _matcher(fx, geom, max_scans=4, max_beams=GC.E2E_BEAMS)
+    df.from_grid(d_first, stream=K.stream())
+    d2 = df.fields(K.stream())[1]
+    K.sync()
+    a, b = S.two_streams()
+    hold(b)
+    m.set_field(df, stream=b.cuda_stream)
+    e = S.event_behind(b)
+    hold.still_held(e, "grid match: set_field on B, a transform into its field on A")
+    df.from_grid(d_second, stream=a.cuda_stream)
+    got = m.field(b.cuda_stream)
+    K.sync()
+    GC.same_bytes(got, G.field(d2, grid_match_table(None, cfg.resolution)), "a held reader: the first transform's field")
+    assert (df.fields(K.stream())[1] != d2).any()            # (and the second transform did run)
+    m.close()
+    df.close()

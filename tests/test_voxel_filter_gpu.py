@@ -15,6 +15,7 @@ import pytest
 from tests import deskew_cases as K
 from tests import keyframes_mask_restatement as KM
 from tests import keyframes_restatement as KR
+from tests import segment_cases as S
 from tests import voxel_filter_restatement as VF
 from tests.test_keyframes_gpu import _device_store, _up
 
@@ -28,6 +29,11 @@ def fx():
     f = K.fx_for(16, 64, 3)
     yield f
     f.close()
+
+
+@pytest.fixture(scope="module")
+def hold():
+    return S.Hold()
 
 
 @pytest.fixture(scope="module")
@@ -446,6 +452,30 @@ def test_add_keyframes_follows_moved_poses_and_refuses_what_it_must(fx, bits):
     assert e.value.code == B.ERR_INVALID_ARGUMENT
     small.close()
     plain.close()
+
+
+def test_set_poses_on_the_other_stream_waits_for_a_held_add_keyframes(fx, hold):
+    """The reader's half of the two-object call: an add_keyframes queued on a held stream B records the store's event too, so
+    a set_poses of other poses issued on A while B is still held does not reach the poses before the add has read them."""
+    store = KR.sphere_case()[0]
+    kf = _device_store(fx, store)
+    n = int(store.begin(KR.EDGE)[-1])
+    vf = fx.voxel_filter(12, n)
+    want = _from_cloud(vf, kf.build(KR.EDGE, stream=K.stream()), KR.EDGE, n)
+    vf.reset(LEAVES[KR.EDGE], K.stream())
+    K.sync()
+    a, b = S.two_streams()
+    hold(b)
+    vf.add_keyframes(kf, KR.EDGE, stream=b.cuda_stream)
+    e = S.event_behind(b)
+    hold.still_held(e, "voxel filter: add_keyframes on B, set_poses of its store on A")
+    kf.set_poses(KR.bits_poses(len(store), 78), 0, a.cuda_stream)
+    got = _emit(vf, n, stream=b.cuda_stream)
+    _same(got, want, "a held reader: the emit of the first poses")
+    moved = _from_store(vf, kf, KR.EDGE, 0, len(store), False, n)
+    assert moved[0] == 0 and moved[2].tobytes() != got[2].tobytes()       # (and the set_poses did land)
+    vf.close()
+    kf.close()
 
 
 def test_save_filtered_writes_the_emitted_clouds(fx, bits, tmp_path):
