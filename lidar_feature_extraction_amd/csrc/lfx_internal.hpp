@@ -711,13 +711,12 @@ inline int read_lists(lfx_ctx * c, const CloudList * lists, int n_lists, uint32_
 // The pinned block of a store whose calls read lists back into [0, pin_table) and send their table of entries up from
 // pin_table on: room for a read-back of `need` bytes and `entries` entries of `entry_bytes` behind it.  The block may move,
 // so what was queued behind `tail` is waited for first: nothing may still read the table in it.
-inline int grow_readback(lfx_ctx * c, const Tail & tail, PinnedBuf & pinned, size_t & pin_table, size_t need, size_t entry_bytes, size_t entries)
+inline int grow_readback(const Call & k, const Tail & tail, PinnedBuf & pinned, size_t & pin_table, size_t need, size_t entry_bytes, size_t entries)
 {
   if (need <= pin_table) {return LFX_OK;}
-  const int rs = tail.settle(c);
-  if (rs != LFX_OK) {return rs;}
+  LFX_TRY(k.wait(tail));
   const size_t at = round64(need);
-  LFX_HIP(c, pinned.reserve(at + entry_bytes * entries));
+  LFX_HIP(k.c, pinned.reserve(at + entry_bytes * entries));
   pin_table = at;
   return LFX_OK;
 }
@@ -834,5 +833,115 @@ int align_clouds(
   lfx_ctx * c, const lfx_map * edge_map, const lfx_map * surface_map, uint32_t n_neighbors, int max_iter, const CloudSpan & edge,
   const CloudSpan & surface, uint32_t n_clouds, const double * initial_poses, lfx_align_result * results, void * stream,
   lfx_align_report * reports = nullptr);
+
+// The front of lfx_localize_batch, lfx_odometry_update_batch and lfx_rolling_map_update_batch: the last batch's surface clouds
+// downsampled once into the caller's buffer (the clouds, a count and a status per scan, then what else the caller keeps
+// there), the scans' lengths left in the caller's pinned block on the way ([batch][2]: edge count, downsampled length),
+// behind the batch's scan_info ([batch][4]) where the caller reads it.
+struct BatchFront
+{
+  float * down = nullptr;
+  uint32_t * down_count = nullptr, * down_status = nullptr;
+  uint32_t * info = nullptr, * lengths = nullptr;
+  // room in `pinned` from word `at` on: [batch][4] info where with_info, then [batch][2] lengths
+  int pin(lfx_ctx * c, PinnedBuf & pinned, size_t at, bool with_info)
+  {
+    const size_t batch = c->last_batch, info_words = with_info ? 4 * batch : 0;
+    LFX_HIP(c, pinned.reserve(sizeof(uint32_t) * (at + info_words + 2 * batch)));
+    uint32_t * const w = reinterpret_cast<uint32_t *>(pinned.p) + at;
+    info = with_info ? w : nullptr;
+    lengths = w + info_words;
+    return LFX_OK;
+  }
+  // every scan's counts on the host: one wait
+  int read_info(lfx_ctx * c, hipStream_t st) const
+  {
+    LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * c->last_batch, hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipStreamSynchronize(st));
+    return LFX_OK;
+  }
+};
+// (words_per_scan: count and status included; `exact`: hold's.  A cloud PCL hands back unfiltered -- a leaf too small for its
+// extent -- is copied.  Waits, in read_info, where with_info, else for nothing.)
+inline int batch_front(lfx_ctx * c, DevBuf<float> & buf, uint32_t words_per_scan, bool exact, PinnedBuf & pinned, size_t at, bool with_info,
+  float leaf, hipStream_t st, BatchFront & f)
+{
+  const uint32_t batch = c->last_batch;
+  const size_t total = c->h_scan_begin[batch];
+  if (hold(buf, 4 * total + words_per_scan * (size_t)batch, exact) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");
+  }
+  LFX_TRY(f.pin(c, pinned, at, with_info));
+  f.down = buf.p;
+  f.down_count = reinterpret_cast<uint32_t *>(f.down + 4 * total);
+  f.down_status = f.down_count + batch;
+  void * d_lengths = nullptr;
+  LFX_HIP(c, hipHostGetDevicePointer(&d_lengths, f.lengths, 0));
+  LFX_TRY(voxel_downsample(c, reinterpret_cast<const float *>(c->surf_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoSurface, 4, batch,
+    total, leaf, f.down, f.down_count, f.down_status, st, true, c->scan_info.p + lfx::kInfoEdge, static_cast<uint32_t *>(d_lengths)));
+  return with_info ? f.read_info(c, st) : LFX_OK;
+}
+
+// One scan's clouds as five device words that the clouds' begin and count arguments point at (lfx_localize_host,
+// lfx_odometry_update, the loop closer's query); an owner keeps kScanWords of them
+enum : uint32_t {kScanZero, kScanEdgeCount, kScanSurfaceCount, kScanDownCount, kScanDownStatus, kScanSent, kScanWords = 8};
+// The words written into h_words (pinned; the caller has waited for what read it last) and queued for d_words, the surface
+// cloud downsampled into d_down where there is one, and both clouds as align_clouds addresses them: sized by their own
+// lengths (a bound on the downsampled one, whose count the kernels read on the device), rows from row_begin.  No wait.
+inline int scan_front(lfx_ctx * c, uint32_t * h_words, uint32_t * d_words, const float * d_edge, uint32_t n_edge, const float * d_surface,
+  uint32_t n_surface, float leaf, float * d_down, const uint32_t * row_begin, hipStream_t st, CloudSpan & edge, CloudSpan & down)
+{
+  h_words[kScanZero] = 0u; h_words[kScanEdgeCount] = n_edge; h_words[kScanSurfaceCount] = n_surface; h_words[kScanDownCount] = 0u; h_words[kScanDownStatus] = 0u;
+  LFX_HIP(c, hipMemcpyAsync(d_words, h_words, sizeof(uint32_t) * kScanSent, hipMemcpyHostToDevice, st));
+  if (n_surface) {
+    LFX_TRY(voxel_downsample(c, d_surface, d_words + kScanZero, d_words + kScanSurfaceCount, 1, 1, n_surface, leaf, d_down,
+      d_words + kScanDownCount, d_words + kScanDownStatus, st, true, d_words + kScanEdgeCount, nullptr));
+  }
+  edge = CloudSpan{d_edge, d_words + kScanZero, d_words + kScanEdgeCount, 1, n_edge, n_edge, row_begin};
+  down = CloudSpan{d_down, d_words + kScanZero, d_words + kScanDownCount, 1, n_surface, n_surface, row_begin};
+  return LFX_OK;
+}
+
+// the identity pose, [R | t] 3 x 4 row-major
+constexpr double kIdentityPose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+
+// the alignment settings the odometry's and the rolling map's configs share (leaf_name: what the config calls the scans' leaf)
+inline int check_align_config(lfx_ctx * c, uint32_t n_neighbors, int max_iter, float leaf, const char * leaf_name, float edge_cell,
+  float surface_cell, const double initial_pose[12])
+{
+  if (n_neighbors < 3 || n_neighbors > 16) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [3, 16]");}
+  if (max_iter < 1) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be >= 1");}
+  if (!(leaf > 0.f) || !std::isfinite(leaf)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, std::string(leaf_name) + " must be > 0");}
+  if (!(edge_cell >= 0.f) || !std::isfinite(edge_cell) || !(surface_cell >= 0.f) || !std::isfinite(surface_cell)) {
+    return fail(c, LFX_ERR_INVALID_ARGUMENT, "edge_cell / surface_cell must be >= 0 (0: no grid)");
+  }
+  if (!finite_all(initial_pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
+  return LFX_OK;
+}
+
+// destroy_on for an owner of maps (emap, smap): they go after the object, whose destructor waits for its tail
+template<typename T>
+void destroy_with_maps(T * o)
+{
+  if (!o) {return;}
+  lfx_map * const emap = o->emap, * const smap = o->smap;
+  destroy_on(o);
+  lfx_map_destroy(emap);
+  lfx_map_destroy(smap);
+}
+
+// the savers' file of a kind (dirname/edge.pcd, dirname/surface.pcd); a host cloud written as PCD, or the writer's message
+inline std::string kind_path(const char * dirname, int kind)
+{
+  const std::string dir(dirname);
+  return dir + ((!dir.empty() && dir.back() == '/') ? "" : "/") + (kind ? "surface.pcd" : "edge.pcd");
+}
+inline int write_pcd(lfx_ctx * c, const std::string & path, const float * points, uint64_t n)
+{
+  char msg[512];
+  const int rc = lfx_pcd_write(path.c_str(), points, n, msg, sizeof(msg));
+  return rc != LFX_OK ? fail(c, rc, msg) : LFX_OK;
+}
 
 }  // namespace lfx_host

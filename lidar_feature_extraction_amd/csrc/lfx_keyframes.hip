@@ -164,10 +164,7 @@ int save_kind(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::string 
     LFX_HIP(c, hipMemcpyAsync(host.data() + 4u * (size_t)lo, s->scratch.p, sizeof(float4) * (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
   }
   LFX_HIP(c, hipStreamSynchronize(st));
-  char msg[512];
-  const int rc = lfx_pcd_write(path.c_str(), host.data(), total, msg, sizeof(msg));
-  if (rc != LFX_OK) {return fail(c, rc, msg);}
-  return LFX_OK;
+  return write_pcd(c, path, host.data(), total);
 }
 
 int check_flags(lfx_ctx * c, const lfx_keyframes * s)
@@ -216,11 +213,7 @@ int save_kind_masked(lfx_ctx * c, const lfx_keyframes * s, int kind, const std::
   }
   LFX_HIP(c, hipStreamSynchronize(st));
   *kept = at;
-  if (at == 0u) {return LFX_OK;}
-  char msg[512];
-  const int rc = lfx_pcd_write(path.c_str(), host.data(), at, msg, sizeof(msg));
-  if (rc != LFX_OK) {return fail(c, rc, msg);}
-  return LFX_OK;
+  return at == 0u ? LFX_OK : write_pcd(c, path, host.data(), at);
 }
 
 }  // namespace
@@ -544,12 +537,10 @@ int lfx_keyframes_save(lfx_ctx * c, const lfx_keyframes * s, const char * dirnam
   written[0] = written[1] = 0;
   Call k(c, stream);
   LFX_TRY(k.open());
-  const std::string dir(dirname);
-  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
   LFX_TRY(k.read(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     if (s->begin[kind][s->n] == 0u) {continue;}
-    LFX_TRY(save_kind(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), k.st));
+    LFX_TRY(save_kind(c, s, kind, kind_path(dirname, kind), k.st));
     written[kind] = 1;
   }
   return LFX_OK;
@@ -712,13 +703,11 @@ int lfx_keyframes_save_masked(lfx_ctx * c, const lfx_keyframes * s, const char *
   written[0] = written[1] = 0;
   Call k(c, stream);
   LFX_TRY(k.open());
-  const std::string dir(dirname);
-  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
   LFX_TRY(k.read(s->tail));
   for (int kind = 0; kind < 2; kind++) {
     if (s->begin[kind][s->n] == 0u) {continue;}
     uint64_t kept = 0u;
-    LFX_TRY(save_kind_masked(c, s, kind, dir + sep + (kind ? "surface.pcd" : "edge.pcd"), &kept, k.st));
+    LFX_TRY(save_kind_masked(c, s, kind, kind_path(dirname, kind), &kept, k.st));
     written[kind] = kept > 0u ? 1 : 0;
   }
   return LFX_OK;

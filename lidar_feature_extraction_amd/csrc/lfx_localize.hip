@@ -562,34 +562,23 @@ int localize_batch(
   LFX_HIP(c, hipSetDevice(c->device));
   const uint32_t batch = c->last_batch;
   const size_t total = c->h_scan_begin[batch];
-  // the clouds, then counts, status and the two tables of row starts
-  if (hold(c->align_surface, 4 * total + 4 * (size_t)batch, true) != hipSuccess) {
-    return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");
-  }
-  float * down = c->align_surface.p;
-  uint32_t * down_count = reinterpret_cast<uint32_t *>(down + 4 * total), * down_status = down_count + batch;
-  uint32_t * d_row3 = down_status + batch, * d_row1 = d_row3 + batch;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // A few scans: nothing is asked of the device before the alignment.  The rows' scratch is sized by a bound (a scan has no
   // more edge points, and no more surface points, than points: 400 bytes per input point), the rows of scan s start where
   // its points do, and the launches are sized by the previous call's longest clouds (the kernels stride over what there is).
   const bool by_bound = 400u * total <= ((size_t)192 << 20);      // (four 64 x 1800 scans; the scratch only ever grows)
-  LFX_HIP(c, c->h_loc.reserve(8 * (size_t)batch));
-  volatile uint32_t * lengths = reinterpret_cast<volatile uint32_t *>(c->h_loc.p);
-  void * d_lengths = nullptr;
-  LFX_HIP(c, hipHostGetDevicePointer(&d_lengths, c->h_loc.p, 0));
-  // Downsample of the surface clouds (where PCL gives a cloud back unfiltered -- leaf too small for its extent -- the rows are
-  // built from all its points: the kernel copies it), the clouds' lengths left in pinned memory on the way
-  const int rc = voxel_downsample(c, reinterpret_cast<const float *>(c->surf_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoSurface, 4,
-    batch, total, surface_leaf, down, down_count, down_status, stream, true, c->scan_info.p + lfx::kInfoEdge, static_cast<uint32_t *>(d_lengths));
-  if (rc != LFX_OK) {return rc;}
+  // the downsampled clouds, then counts, status and the two tables of row starts; the clouds' lengths left in pinned memory
+  BatchFront front;
+  LFX_TRY(batch_front(c, c->align_surface, 4, true, c->h_loc, 0, false, surface_leaf, st, front));
+  uint32_t * d_row3 = front.down_status + batch, * d_row1 = d_row3 + batch;
+  volatile uint32_t * lengths = front.lengths;
   auto remember = [&]() {
       uint32_t e = 0, f = 0;
       for (uint32_t s = 0; s < batch; s++) {e = std::max(e, (uint32_t)lengths[2 * s]); f = std::max(f, (uint32_t)lengths[2 * s + 1]);}
       c->loc_guess[0] = e; c->loc_guess[1] = f;
     };
   CloudSpan edge{reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoEdge, 4};
-  CloudSpan surface{down, c->scan_begin.p, down_count, 1};
+  CloudSpan surface{front.down, c->scan_begin.p, front.down_count, 1};
   if (by_bound) {
     edge.longest = c->loc_guess[0] ? c->loc_guess[0] + c->loc_guess[0] / 8u : 4096u;
     surface.longest = c->loc_guess[1] ? c->loc_guess[1] + c->loc_guess[1] / 8u : 2048u;
@@ -626,33 +615,24 @@ int localize_host(
   }
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // [edge | surface | downsampled surface] records of 4 floats, then begin / count words
-  const size_t ne = n_edge, ns = n_surface, words = 8;
-  if (hold(c->align_surface, 4 * (ne + 2 * ns + 2) + words, true) != hipSuccess) {
+  // [edge | surface | downsampled surface] records of 4 floats, then the scan's words
+  const size_t ne = n_edge, ns = n_surface;
+  if (hold(c->align_surface, 4 * (ne + 2 * ns + 2) + kScanWords, true) != hipSuccess) {
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the scan's clouds");
   }
   float * d_edge = c->align_surface.p, * d_surface = d_edge + 4 * (ne + 1), * d_down = d_surface + 4 * (ns + 1);
   uint32_t * d_words = reinterpret_cast<uint32_t *>(d_down + 4 * ns);
-  // words: [0] begin (0), [1] n_edge, [2] n_surface, [3] downsampled count, [4] downsample status
-  LFX_HIP(c, c->h_align.reserve(sizeof(uint32_t) * words));
+  LFX_HIP(c, c->h_align.reserve(sizeof(uint32_t) * kScanWords));
   uint32_t * h_words = reinterpret_cast<uint32_t *>(c->h_align.p);
-  h_words[0] = 0; h_words[1] = n_edge; h_words[2] = n_surface; h_words[3] = 0; h_words[4] = 0;
-  LFX_HIP(c, hipMemcpyAsync(d_words, h_words, sizeof(uint32_t) * words, hipMemcpyHostToDevice, st));
   if (n_edge) {LFX_HIP(c, hipMemcpyAsync(d_edge, edge_points, sizeof(float) * 4 * ne, hipMemcpyHostToDevice, st));}
-  uint32_t n_down = 0;
-  if (n_surface) {
-    LFX_HIP(c, hipMemcpyAsync(d_surface, surface_points, sizeof(float) * 4 * ns, hipMemcpyHostToDevice, st));
-    // (where PCL gives the cloud back unfiltered the launch copies it, as for lfx_localize_batch)
-    const int rc = voxel_downsample(c, d_surface, d_words, d_words + 2, 1, 1, ns, surface_leaf, d_down, d_words + 3, d_words + 4, stream,
-      true, d_words + 1, nullptr);
-    if (rc != LFX_OK) {return rc;}
-    LFX_HIP(c, hipMemcpyAsync(h_words + 3, d_words + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    LFX_HIP(c, hipStreamSynchronize(st));
-    n_down = h_words[3];
-  } else {
-    LFX_HIP(c, hipStreamSynchronize(st));             // the words have left the pinned block: the alignment stages through it too
-  }
-  const CloudSpan edge{d_edge, d_words, d_words + 1, 1, n_edge, ne}, surface{d_down, d_words, d_words + 3, 1, n_down, ns};
+  if (n_surface) {LFX_HIP(c, hipMemcpyAsync(d_surface, surface_points, sizeof(float) * 4 * ns, hipMemcpyHostToDevice, st));}
+  CloudSpan edge, surface;
+  LFX_TRY(scan_front(c, h_words, d_words, d_edge, n_edge, d_surface, n_surface, surface_leaf, d_down, nullptr, st, edge, surface));
+  // the downsampled count back (one wait); with no surface cloud, the words have left the pinned block: the alignment stages
+  // through it too
+  if (n_surface) {LFX_HIP(c, hipMemcpyAsync(h_words + kScanDownCount, d_words + kScanDownCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st));}
+  LFX_HIP(c, hipStreamSynchronize(st));
+  surface.longest = n_surface ? h_words[kScanDownCount] : 0u;
   return align_clouds(c, edge_map, surface_map, n_neighbors, max_iter, edge, surface, 1, initial_pose, result, stream, report);
 }
 }  // namespace

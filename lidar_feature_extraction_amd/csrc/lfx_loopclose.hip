@@ -22,15 +22,12 @@ struct lfx_loop_closer
   uint64_t device_bytes = 0;
   DevBuf<float> submap[2];                   // [submap_capacity[kind]][4]
   DevBuf<float> downsampled;                 // [ds_capacity][4]: the query's surface cloud after the voxel grid
-  DevBuf<uint32_t> words;                    // kWords: what the clouds' begin / count arguments point at
+  DevBuf<uint32_t> words;                    // kScanWords: what the clouds' begin / count arguments point at
   PinnedBuf h_words;
 };
 
 namespace
 {
-// the device words: a begin of 0, the query's edge and surface counts, the downsample's count and status
-enum : uint32_t {kZero, kEdgeCount, kSurfaceCount, kDownCount, kDownStatus, kWords = 8};
-
 // the smallest of the store's, the index's and the graph's sizes: the ids the contract covers
 int common_size(lfx_ctx * c, const lfx_loop_closer * lc, uint32_t & n)
 {
@@ -95,25 +92,25 @@ int align_query(lfx_ctx * c, lfx_loop_closer * lc, const lfx_map * edge_map, con
 {
   uint32_t * h = reinterpret_cast<uint32_t *>(lc->h_words.p);
   uint32_t * w = lc->words.p;
-  h[kZero] = 0u; h[kEdgeCount] = n_edge; h[kSurfaceCount] = n_surface;
+  h[kScanZero] = 0u; h[kScanEdgeCount] = n_edge; h[kScanSurfaceCount] = n_surface;
   LFX_HIP(c, hipMemcpyAsync(w, h, sizeof(uint32_t) * 3u, hipMemcpyHostToDevice, st));
   const float * scan_surface = surface;
-  const uint32_t * scan_count = w + kSurfaceCount;
+  const uint32_t * scan_count = w + kScanSurfaceCount;
   uint32_t n_scan = n_surface;
   if (lc->cfg.surface_leaf > 0.0f) {
-    const int rd = lfx_voxel_downsample(c, surface, w + kZero, w + kSurfaceCount, 1u, 1u, n_surface, lc->cfg.surface_leaf, lc->downsampled.p,
-        w + kDownCount, w + kDownStatus, st);
+    const int rd = lfx_voxel_downsample(c, surface, w + kScanZero, w + kScanSurfaceCount, 1u, 1u, n_surface, lc->cfg.surface_leaf, lc->downsampled.p,
+        w + kScanDownCount, w + kScanDownStatus, st);
     if (rd != LFX_OK) {return rd;}
-    LFX_HIP(c, hipMemcpyAsync(h + kDownCount, w + kDownCount, sizeof(uint32_t) * 2u, hipMemcpyDeviceToHost, st));
+    LFX_HIP(c, hipMemcpyAsync(h + kScanDownCount, w + kScanDownCount, sizeof(uint32_t) * 2u, hipMemcpyDeviceToHost, st));
     LFX_HIP(c, hipStreamSynchronize(st));
-    if (h[kDownStatus] == 0u) {                          // (1: the leaf is too small for the cloud, which is used as stored)
+    if (h[kScanDownStatus] == 0u) {                          // (1: the leaf is too small for the cloud, which is used as stored)
       scan_surface = lc->downsampled.p;
-      scan_count = w + kDownCount;
-      n_scan = h[kDownCount];
+      scan_count = w + kScanDownCount;
+      n_scan = h[kScanDownCount];
     }
   }
-  return lfx_scan_to_map_align_report(c, edge_map, surface_map, lc->cfg.n_neighbors, lc->cfg.max_iter, edge, w + kZero, w + kEdgeCount, 1u, n_edge,
-           n_edge, scan_surface, w + kZero, scan_count, 1u, n_scan, n_scan, 1u, initial, &out->result, &out->report, st);
+  return lfx_scan_to_map_align_report(c, edge_map, surface_map, lc->cfg.n_neighbors, lc->cfg.max_iter, edge, w + kScanZero, w + kScanEdgeCount, 1u, n_edge,
+           n_edge, scan_surface, w + kScanZero, scan_count, 1u, n_scan, n_scan, 1u, initial, &out->result, &out->report, st);
 }
 
 // one verification; the ids have been checked
@@ -275,8 +272,8 @@ int lfx_loop_closer_create(lfx_ctx * c, const lfx_loop_closer_config * cfg, lfx_
   lc->graph = graph;
   lc->ds_capacity = cfg->surface_leaf > 0.0f ? (cfg->downsample_capacity ? cfg->downsample_capacity : std::min<uint64_t>(ki.max_points[1], 1u << 20)) : 0u;
   if (lc->submap[0].alloc(4u * (size_t)cfg->submap_capacity[0]) != hipSuccess || lc->submap[1].alloc(4u * (size_t)cfg->submap_capacity[1]) != hipSuccess ||
-    (lc->ds_capacity && lc->downsampled.alloc(4u * (size_t)lc->ds_capacity) != hipSuccess) || lc->words.alloc(kWords) != hipSuccess ||
-    lc->h_words.reserve(sizeof(uint32_t) * kWords) != hipSuccess)
+    (lc->ds_capacity && lc->downsampled.alloc(4u * (size_t)lc->ds_capacity) != hipSuccess) || lc->words.alloc(kScanWords) != hipSuccess ||
+    lc->h_words.reserve(sizeof(uint32_t) * kScanWords) != hipSuccess)
   {
     (void)hipGetLastError();
     delete lc;
@@ -284,7 +281,7 @@ int lfx_loop_closer_create(lfx_ctx * c, const lfx_loop_closer_config * cfg, lfx_
   }
   // (every device buffer carries 16 spare bytes behind its elements: DevBuf::alloc)
   const uint64_t buffers = lc->ds_capacity ? 4u : 3u;
-  lc->device_bytes = sizeof(float) * 4u * (cfg->submap_capacity[0] + cfg->submap_capacity[1] + lc->ds_capacity) + sizeof(uint32_t) * kWords + 16u * buffers;
+  lc->device_bytes = sizeof(float) * 4u * (cfg->submap_capacity[0] + cfg->submap_capacity[1] + lc->ds_capacity) + sizeof(uint32_t) * kScanWords + 16u * buffers;
   *out = lc;
   return LFX_OK;
 }

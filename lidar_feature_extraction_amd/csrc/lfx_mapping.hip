@@ -126,10 +126,7 @@ int save_cloud(lfx_ctx * c, const float * d_points, uint64_t n, const std::strin
   std::vector<float> host(4 * (size_t)n);
   LFX_HIP(c, hipMemcpyAsync(host.data(), d_points, sizeof(float) * host.size(), hipMemcpyDeviceToHost, st));
   LFX_HIP(c, hipStreamSynchronize(st));
-  char msg[512];
-  const int rc = lfx_pcd_write(path.c_str(), host.data(), n, msg, sizeof(msg));
-  if (rc != LFX_OK) {return fail(c, rc, msg);}
-  return LFX_OK;
+  return write_pcd(c, path, host.data(), n);
 }
 }  // namespace
 
@@ -185,7 +182,7 @@ int lfx_mapper_add(lfx_ctx * c, lfx_mapper * m, const float * d_points, const ui
   Call k(c, stream);
   LFX_TRY(k.open());
   // the counts and the begins back in one wait: the call's only one
-  LFX_TRY(grow_readback(c, m->uploaded, m->pinned, m->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::MapAppendEntry),
+  LFX_TRY(grow_readback(k, m->uploaded, m->pinned, m->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::MapAppendEntry),
     std::max<size_t>(n_clouds, kInitialEntries)));
   const CloudList list{d_begin, d_count, count_stride, total_points, ""};
   std::vector<uint32_t> begin, count;
@@ -255,14 +252,12 @@ int lfx_odometry_save(lfx_ctx * c, const lfx_odometry * o, const char * dirname,
   Call k(c, stream);
   LFX_TRY(k.open());
   LFX_TRY(k.read(odometry_tail(o)));         // (the last append may be queued on another stream: the store is read behind it)
-  const std::string dir(dirname);
-  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
   if (v.n_edge) {
-    LFX_TRY(save_cloud(c, v.edge_points, v.n_edge, dir + sep + "edge.pcd", k.st));
+    LFX_TRY(save_cloud(c, v.edge_points, v.n_edge, kind_path(dirname, 0), k.st));
     written[0] = 1;
   }
   if (v.n_surface) {
-    LFX_TRY(save_cloud(c, v.surface_points, v.n_surface, dir + sep + "surface.pcd", k.st));
+    LFX_TRY(save_cloud(c, v.surface_points, v.n_surface, kind_path(dirname, 1), k.st));
     written[1] = 1;
   }
   return LFX_OK;

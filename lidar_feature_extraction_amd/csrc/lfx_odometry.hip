@@ -95,12 +95,12 @@ int compact(lfx_ctx * c, lfx_odometry * o, hipStream_t st)
   return LFX_OK;
 }
 
-// the previous call's tail waited for, the last appended scan's bounds into its boxes (a wait only where nothing has
-// waited since)
-int settle(lfx_ctx * c, lfx_odometry * o)
+// the tail waited for on the host and taken (a wait only where nothing has waited since; the call records it, however it
+// leaves), then the last appended scan's bounds folded into its boxes, once
+int settle(Call & call, lfx_odometry * o)
 {
-  const int rs = o->tail.settle(c);
-  if (rs != LFX_OK || !o->bounds_queued) {return rs;}
+  LFX_TRY(call.after(o->tail));
+  if (!o->bounds_queued) {return LFX_OK;}
   o->bounds_queued = false;
   const uint32_t * h = pinned_words(o) + kPinBounds;
   std::array<Box, 2> & b = o->box.back();
@@ -113,13 +113,13 @@ int settle(lfx_ctx * c, lfx_odometry * o)
 }
 
 // EdgeSurfaceMap::Add: both clouds transformed by `pose` behind the store's last scan (after a compaction where `how` says
-// so).  Nothing is waited for: the bounds are read by the next rebuild (settle)
-int append(lfx_ctx * c, lfx_odometry * o, int how, const double pose[12], const float4 * edge, uint32_t ne, const float4 * surface,
-  uint32_t ns, hipStream_t st)
+// so), and the call's record behind it.  Nothing is waited for: the bounds are read by the next rebuild (settle)
+int append(Call & k, lfx_odometry * o, int how, const double pose[12], const float4 * edge, uint32_t ne, const float4 * surface, uint32_t ns)
 {
-  int rc = settle(c, o);                     // (the bounds table is about to be written again)
-  if (rc == LFX_OK && how == 1) {rc = compact(c, o, st);}
-  if (rc != LFX_OK) {return rc;}
+  lfx_ctx * const c = k.c;
+  hipStream_t const st = k.st;
+  LFX_TRY(settle(k, o));                     // (the bounds table is about to be written again)
+  if (how == 1) {LFX_TRY(compact(c, o, st));}
   const uint32_t n = o->n_scans(), at_e = o->off_e[n], at_s = o->off_s[n];
   if (ne + ns) {
     lfx::OdoPose P;
@@ -134,18 +134,17 @@ int append(lfx_ctx * c, lfx_odometry * o, int how, const double pose[12], const 
   o->off_e.push_back(at_e + ne);
   o->off_s.push_back(at_s + ns);
   o->box.push_back(std::array<Box, 2>{});
-  rc = o->tail.done(c, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.finish());
   o->bounds_queued = ne + ns > 0;
   o->added++;
   return LFX_OK;
 }
 
 // one window map over the last w scans of a store
-int rebuild(lfx_ctx * c, lfx_odometry * o, int k, uint32_t w, hipStream_t st)
+int rebuild(Call & call, lfx_odometry * o, int k, uint32_t w)
 {
-  const int rc = settle(c, o);
-  if (rc != LFX_OK) {return rc;}
+  lfx_ctx * const c = call.c;
+  LFX_TRY(settle(call, o));
   const uint32_t n = o->n_scans();
   const std::vector<uint32_t> & off = k ? o->off_s : o->off_e;
   double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
@@ -164,7 +163,7 @@ int rebuild(lfx_ctx * c, lfx_odometry * o, int k, uint32_t w, hipStream_t st)
   }
   const float4 * store = k ? o->surface.p : o->edge.p;
   return map_rebuild(c, k ? o->smap : o->emap, reinterpret_cast<const float *>(store + off[n - w]), off[n] - off[n - w],
-           k ? o->cfg.surface_cell : o->cfg.edge_cell, lo, hi, st);
+           k ? o->cfg.surface_cell : o->cfg.edge_cell, lo, hi, call.st);
 }
 
 struct ScanIn                                // one scan as the append kernel and the alignment read it
@@ -188,8 +187,9 @@ void not_aligned(const double pose[12], lfx_odometry_result * r)
 }
 
 // Odometry::Update for one scan
-int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result * result, hipStream_t st, lfx_align_report * report)
+int step(Call & call, lfx_odometry * o, const ScanIn & in, lfx_odometry_result * result, lfx_align_report * report)
 {
+  lfx_ctx * const c = call.c;
   const int how = room(o, in.n_edge, in.n_surface);
   if (how < 0) {return no_room(c, in.n_edge, in.n_surface);}
   lfx_odometry_result r{};
@@ -204,18 +204,14 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
     if (r.n_edge_map < k || r.n_surface_map < k) {
       not_aligned(pose, &r);                 // (the reference would read nanoflann's uninitialised output)
     } else {
-      int rc = rebuild(c, o, 0, w, st);
-      if (rc == LFX_OK) {rc = rebuild(c, o, 1, w, st);}
-      if (rc == LFX_OK) {
-        rc = align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_cloud, in.down_cloud, 1, o->pose, &r.align, st, report);
-      }
-      if (rc != LFX_OK) {return rc;}
+      LFX_TRY(rebuild(call, o, 0, w));
+      LFX_TRY(rebuild(call, o, 1, w));
+      LFX_TRY(align_clouds(c, o->emap, o->smap, k, o->cfg.max_iter, in.edge_cloud, in.down_cloud, 1, o->pose, &r.align, call.st, report));
       std::memcpy(pose, r.align.pose, sizeof(pose));    // pose_ = update(scan, pose_), whatever the code
       r.aligned = 1;
     }
   }
-  const int rc = append(c, o, how, pose, in.edge, in.n_edge, in.surface, in.n_surface, st);
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(append(call, o, how, pose, in.edge, in.n_edge, in.surface, in.n_surface));
   std::memcpy(o->pose, pose, sizeof(pose));
   std::memcpy(o->recent[0], o->recent[1], sizeof(pose));
   std::memcpy(o->recent[1], pose, sizeof(pose));
@@ -226,38 +222,56 @@ int step(lfx_ctx * c, lfx_odometry * o, const ScanIn & in, lfx_odometry_result *
 
 int check(lfx_ctx * c, const lfx_odometry * o) {return check_device(c, o->device, "the odometry");}
 
-// What the de-skewing batch calls do once their arguments are checked: every scan of the last batch through
-// lfx_odometry_update, its clouds de-skewed just ahead of it by queue(s), which queues scan s's de-skew into dsk_edge /
-// dsk_surface (laid out like the context's clouds) on the stream.
+// the reports of a call over n scans: one per scan, all zero, where reports are on; null where they are off
+lfx_align_report * fresh_reports(lfx_odometry * o, uint32_t n)
+{
+  o->reports.assign(o->reports_on ? n : 0u, lfx_align_report{});
+  return o->reports_on ? o->reports.data() : nullptr;
+}
+
+// Odometry::Update for one scan whose clouds are on the device: lfx_odometry_update behind its checks, and what every
+// other update call runs per scan
+int update_scan(Call & k, lfx_odometry * o, const float * d_edge, uint32_t n_edge, const float * d_surface, uint32_t n_surface,
+  lfx_odometry_result * result, lfx_align_report * report)
+{
+  LFX_TRY(settle(k, o));                     // (the pinned words are about to be written again)
+  if (hold(o->down, 4 * (size_t)n_surface + 4) != hipSuccess) {return fail(k.c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface cloud");}
+  // Nothing is waited for: the downsampled cloud's rows are sized by the cloud's own length, as lfx_localize_batch sizes a
+  // few scans' rows.  (align_clouds wants a pointer for an empty edge cloud too.)
+  ScanIn in;
+  in.edge = reinterpret_cast<const float4 *>(d_edge); in.n_edge = n_edge;
+  in.surface = reinterpret_cast<const float4 *>(d_surface); in.n_surface = n_surface;
+  LFX_TRY(scan_front(k.c, pinned_words(o) + kPinWords, o->words.p, d_edge ? d_edge : o->down.p, n_edge, d_surface, n_surface,
+    o->cfg.surface_leaf, o->down.p, o->words.p, k.st, in.edge_cloud, in.down_cloud));
+  return step(k, o, in, result, report);
+}
+
+// What the de-skewing batch calls do once their arguments are checked: every scan of the last batch through update_scan,
+// its clouds de-skewed just ahead of it by queue(s), which queues scan s's de-skew into dsk_edge / dsk_surface (laid out
+// like the context's clouds) on the stream.
 template<typename Queue>
 int update_deskewed(lfx_ctx * c, lfx_odometry * o, lfx_odometry_result * results, void * stream, Queue queue)
 {
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(settle(k, o));
   const uint32_t batch = c->last_batch;
   const size_t total = c->h_scan_begin[batch];
   if (hold(o->dsk_edge, total + 1) != hipSuccess || hold(o->dsk_surface, total + 1) != hipSuccess) {
     return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the de-skewed clouds");
   }
-  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
-  uint32_t * info = pinned_words(o) + kPinInfo;
-  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
-  // (lfx_odometry_update below writes the pinned block's words and bounds, not the batch's scan_info behind them)
-  std::vector<uint32_t> counts(info, info + 4 * (size_t)batch);
-  std::vector<lfx_align_report> reports(o->reports_on ? batch : 0u, lfx_align_report{});
+  // (update_scan writes the pinned block's words and bounds, not the batch's scan_info behind them)
+  BatchFront f;
+  LFX_TRY(f.pin(c, o->pinned, kPinInfo, true));
+  LFX_TRY(f.read_info(c, k.st));
+  lfx_align_report * const reports = fresh_reports(o, batch);
   for (uint32_t s = 0; s < batch; s++) {
-    int rc = queue(s);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(k.take(o->tail));                // (the de-skew reads and writes the odometry's clouds: behind the call's record too)
+    LFX_TRY(queue(s));
     const uint32_t b = c->h_scan_begin[s];
-    rc = lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), counts[4 * s + lfx::kInfoEdge],
-      reinterpret_cast<const float *>(o->dsk_surface.p + b), counts[4 * s + lfx::kInfoSurface], results + s, stream);
-    if (rc != LFX_OK) {return rc;}
-    if (o->reports_on && !o->reports.empty()) {reports[s] = o->reports[0];}
+    LFX_TRY(update_scan(k, o, reinterpret_cast<const float *>(o->dsk_edge.p + b), f.info[4 * s + lfx::kInfoEdge],
+      reinterpret_cast<const float *>(o->dsk_surface.p + b), f.info[4 * s + lfx::kInfoSurface], results + s, reports ? reports + s : nullptr));
   }
-  o->reports = reports;
   return LFX_OK;
 }
 }  // namespace
@@ -276,26 +290,20 @@ void lfx_odometry_default_config(lfx_odometry_config * cfg)
   cfg->surface_leaf = 1.0f;
   cfg->edge_cell = cfg->surface_cell = 1.0f;
   cfg->edge_capacity_points = cfg->surface_capacity_points = (uint64_t)1 << 22;
-  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  std::memcpy(cfg->initial_pose, identity, sizeof(identity));
+  std::memcpy(cfg->initial_pose, kIdentityPose, sizeof(kIdentityPose));
 }
 
 int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odometry ** out)
 {
   if (!c || !cfg || !out) {return LFX_ERR_INVALID_ARGUMENT;}
   if (cfg->n_local_scans == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_local_scans must be >= 1");}
-  if (cfg->n_neighbors < 3 || cfg->n_neighbors > 16) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [3, 16]");}
-  if (cfg->max_iter < 1) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be >= 1");}
-  if (!(cfg->surface_leaf > 0.f) || !std::isfinite(cfg->surface_leaf)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "surface_leaf must be > 0");}
-  if (!(cfg->edge_cell >= 0.f) || !std::isfinite(cfg->edge_cell) || !(cfg->surface_cell >= 0.f) || !std::isfinite(cfg->surface_cell)) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "edge_cell / surface_cell must be >= 0 (0: no grid)");
-  }
   if (cfg->edge_capacity_points == 0 || cfg->surface_capacity_points == 0 || cfg->edge_capacity_points > 0xFFFFFFFFull ||
     cfg->surface_capacity_points > 0xFFFFFFFFull)
   {
     return fail(c, LFX_ERR_INVALID_ARGUMENT, "the store's capacities must be in [1, 2^32 - 1] points");
   }
-  if (!finite_all(cfg->initial_pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
+  LFX_TRY(check_align_config(c, cfg->n_neighbors, cfg->max_iter, cfg->surface_leaf, "surface_leaf", cfg->edge_cell, cfg->surface_cell,
+    cfg->initial_pose));
   LFX_HIP(c, hipSetDevice(c->device));
   lfx_odometry * o = new (std::nothrow) lfx_odometry();
   if (!o) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry");}
@@ -309,26 +317,18 @@ int lfx_odometry_create(lfx_ctx * c, const lfx_odometry_config * cfg, lfx_odomet
   if (o->edge.alloc(cfg->edge_capacity_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the edge store");}
   if (o->surface.alloc(cfg->surface_capacity_points) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the surface store");}
   if (o->bounds.alloc(12) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's bounds");}
-  if (o->words.alloc(8) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's words");}
+  if (o->words.alloc(kScanWords) != hipSuccess) {return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's words");}
   if (o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)std::max(c->max_batch, 1u))) != hipSuccess) {
     return give_up(LFX_ERR_OUT_OF_MEMORY, "cannot allocate the odometry's pinned block");
   }
-  hipError_t e = hipMemset(o->words.p, 0, 8 * sizeof(uint32_t));
+  hipError_t e = hipMemset(o->words.p, 0, kScanWords * sizeof(uint32_t));
   if (e == hipSuccess) {e = hipDeviceSynchronize();}
   if (e != hipSuccess) {return give_up(LFX_ERR_HIP, hipGetErrorString(e));}
   *out = o;
   return LFX_OK;
 }
 
-void lfx_odometry_destroy(lfx_odometry * o)
-{
-  if (!o) {return;}
-  (void)hipSetDevice(o->device);
-  lfx_map * const emap = o->emap, * const smap = o->smap;
-  delete o;                                  // (waits for the tail: the window maps go after it, as the buffers do)
-  lfx_map_destroy(emap);
-  lfx_map_destroy(smap);
-}
+void lfx_odometry_destroy(lfx_odometry * o) {destroy_with_maps(o);}
 
 int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, lfx_odometry_result * results, void * stream)
 {
@@ -336,38 +336,23 @@ int lfx_odometry_update_batch(lfx_ctx * c, lfx_odometry * o, uint32_t n_scans, l
   const int rb = check_last_batch(c, n_scans);
   if (rb != LFX_OK) {return rb;}
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(settle(k, o));
   const uint32_t batch = c->last_batch;
-  const size_t total = c->h_scan_begin[batch];
-  o->reports.assign(o->reports_on ? batch : 0u, lfx_align_report{});
-  if (hold(o->down, 4 * total + 2 * (size_t)batch) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");}
-  LFX_HIP(c, o->pinned.reserve(sizeof(uint32_t) * (kPinInfo + 6 * (size_t)batch)));
-  float * down = o->down.p;
-  uint32_t * down_count = reinterpret_cast<uint32_t *>(down + 4 * total), * down_status = down_count + batch;
-  uint32_t * info = pinned_words(o) + kPinInfo, * lengths = info + 4 * (size_t)batch;
-  void * d_lengths = nullptr;
-  LFX_HIP(c, hipHostGetDevicePointer(&d_lengths, lengths, 0));
-  // the batch's surface clouds downsampled once (as lfx_localize_batch does: a cloud PCL hands back unfiltered is copied),
-  // and every scan's counts: one wait for the whole batch
-  const int rc = voxel_downsample(c, reinterpret_cast<const float *>(c->surf_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoSurface, 4,
-    batch, total, o->cfg.surface_leaf, down, down_count, down_status, stream, true, c->scan_info.p + lfx::kInfoEdge,
-    static_cast<uint32_t *>(d_lengths));
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  lfx_align_report * const reports = fresh_reports(o, batch);
+  // the batch's surface clouds downsampled once and every scan's counts: one wait for the whole batch
+  BatchFront f;
+  LFX_TRY(batch_front(c, o->down, 2, false, o->pinned, kPinInfo, true, o->cfg.surface_leaf, k.st, f));
   for (uint32_t s = 0; s < batch; s++) {
     ScanIn in;
     const uint32_t b = c->h_scan_begin[s];
-    in.edge = c->edge_pts.p + b; in.n_edge = info[4 * s + lfx::kInfoEdge];
-    in.surface = c->surf_pts.p + b; in.n_surface = info[4 * s + lfx::kInfoSurface];
+    in.edge = c->edge_pts.p + b; in.n_edge = f.info[4 * s + lfx::kInfoEdge];
+    in.surface = c->surf_pts.p + b; in.n_surface = f.info[4 * s + lfx::kInfoSurface];
     in.edge_cloud = single_cloud(o, reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p + s,
       c->scan_info.p + lfx::kInfoEdge + 4 * s, 4, in.n_edge);
-    in.down_cloud = single_cloud(o, down, c->scan_begin.p + s, down_count + s, 1, lengths[2 * s + 1]);
-    const int rc2 = step(c, o, in, results + s, st, o->reports_on ? &o->reports[s] : nullptr);
-    if (rc2 != LFX_OK) {return rc2;}
+    in.down_cloud = single_cloud(o, f.down, c->scan_begin.p + s, f.down_count + s, 1, f.lengths[2 * s + 1]);
+    LFX_TRY(step(k, o, in, results + s, reports ? reports + s : nullptr));
   }
   return LFX_OK;
 }
@@ -377,30 +362,9 @@ int lfx_odometry_update(lfx_ctx * c, lfx_odometry * o, const float * d_edge, uin
 {
   if (!c || !o || !result || (n_edge && !d_edge) || (n_surface && !d_surface)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hold(o->down, 4 * (size_t)n_surface + 4) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface cloud");}
-  // the words go out of the pinned block, which nothing writes again before this call's alignment has waited
-  uint32_t * words = pinned_words(o) + kPinWords;
-  words[0] = 0u; words[1] = n_edge; words[2] = n_surface; words[3] = 0u; words[4] = 0u;
-  LFX_HIP(c, hipMemcpyAsync(o->words.p, words, 5 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (n_surface) {
-    const int rc = voxel_downsample(c, d_surface, o->words.p, o->words.p + 2, 1, 1, n_surface, o->cfg.surface_leaf, o->down.p,
-      o->words.p + 3, o->words.p + 4, stream, true, o->words.p + 1, nullptr);
-    if (rc != LFX_OK) {return rc;}
-  }
-  // Nothing is waited for: the downsampled cloud's rows are sized by the cloud's own length (a bound; the kernels read the
-  // count on the device), as lfx_localize_batch sizes a few scans' rows
-  ScanIn in;
-  const float * any = o->down.p;                // (align_clouds wants a pointer for an empty cloud too)
-  in.edge = reinterpret_cast<const float4 *>(d_edge); in.n_edge = n_edge;
-  in.surface = reinterpret_cast<const float4 *>(d_surface); in.n_surface = n_surface;
-  in.edge_cloud = single_cloud(o, d_edge ? d_edge : any, o->words.p, o->words.p + 1, 1, n_edge);
-  in.down_cloud = single_cloud(o, o->down.p, o->words.p, o->words.p + 3, 1, n_surface);
-  o->reports.assign(o->reports_on ? 1u : 0u, lfx_align_report{});
-  return step(c, o, in, result, st, o->reports_on ? &o->reports[0] : nullptr);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  return update_scan(k, o, d_edge, n_edge, d_surface, n_surface, result, fresh_reports(o, 1));
 }
 
 int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_time_field * time, const double * sweep_times,
@@ -415,10 +379,9 @@ int lfx_odometry_update_batch_deskewed(lfx_ctx * c, lfx_odometry * o, const lfx_
   if (time->source != LFX_TIME_FROM_INDEX && !sweep_times) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "sweep_times is required with a time field");}
   // (recent[] is read per scan: the scan before has been through its update by then)
   return update_deskewed(c, o, results, stream, [&](uint32_t s) {
-             const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
              lfx_sweep sw{};
              double D[12];
-             if (o->n_recent < 2u) {std::memcpy(D, identity, sizeof(D));} else {lfx_motion_between(o->recent[0], o->recent[1], D);}
+             if (o->n_recent < 2u) {std::memcpy(D, kIdentityPose, sizeof(D));} else {lfx_motion_between(o->recent[0], o->recent[1], D);}
              lfx_motion_scale(D, sweep_ratio, sw.motion);
              if (sweep_times) {sw.t0 = sweep_times[2 * s]; sw.t1 = sweep_times[2 * s + 1];}
              return deskew_scans(c, time, &sw, s, 1, to, o->dsk_edge.p, o->dsk_surface.p, static_cast<hipStream_t>(stream));
@@ -447,15 +410,14 @@ int lfx_odometry_update_host(lfx_ctx * c, lfx_odometry * o, const float * edge, 
 {
   if (!c || !o || !result || (n_edge && !edge) || (n_surface && !surface)) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  const int rs = settle(c, o);
-  if (rs != LFX_OK) {return rs;}
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(settle(k, o));                     // (the previous call may still read the staged clouds)
   if (hold(o->staged, (size_t)n_edge + n_surface + 1) != hipSuccess) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the scan's clouds");}
-  if (n_edge) {LFX_HIP(c, hipMemcpyAsync(o->staged.p, edge, sizeof(float4) * n_edge, hipMemcpyHostToDevice, st));}
-  if (n_surface) {LFX_HIP(c, hipMemcpyAsync(o->staged.p + n_edge, surface, sizeof(float4) * n_surface, hipMemcpyHostToDevice, st));}
-  return lfx_odometry_update(c, o, reinterpret_cast<const float *>(o->staged.p), n_edge, reinterpret_cast<const float *>(o->staged.p + n_edge),
-           n_surface, result, stream);
+  if (n_edge) {LFX_HIP(c, hipMemcpyAsync(o->staged.p, edge, sizeof(float4) * n_edge, hipMemcpyHostToDevice, k.st));}
+  if (n_surface) {LFX_HIP(c, hipMemcpyAsync(o->staged.p + n_edge, surface, sizeof(float4) * n_surface, hipMemcpyHostToDevice, k.st));}
+  return update_scan(k, o, reinterpret_cast<const float *>(o->staged.p), n_edge, reinterpret_cast<const float *>(o->staged.p + n_edge),
+           n_surface, result, fresh_reports(o, 1));
 }
 
 int lfx_odometry_add(lfx_ctx * c, lfx_odometry * o, const double pose[12], const float * d_edge, uint32_t n_edge,
@@ -465,9 +427,9 @@ int lfx_odometry_add(lfx_ctx * c, lfx_odometry * o, const double pose[12], const
   if (check(c, o) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   const int how = room(o, n_edge, n_surface);
   if (how < 0) {return no_room(c, n_edge, n_surface);}
-  LFX_HIP(c, hipSetDevice(c->device));
-  return append(c, o, how, pose, reinterpret_cast<const float4 *>(d_edge), n_edge, reinterpret_cast<const float4 *>(d_surface), n_surface,
-           static_cast<hipStream_t>(stream));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  return append(k, o, how, pose, reinterpret_cast<const float4 *>(d_edge), n_edge, reinterpret_cast<const float4 *>(d_surface), n_surface);
 }
 
 int lfx_odometry_set_reports(lfx_odometry * o, int on)

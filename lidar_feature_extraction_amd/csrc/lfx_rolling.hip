@@ -68,17 +68,19 @@ int check(lfx_ctx * c, const lfx_rolling_map * rm, int kind)
 }
 
 // The clouds of one insert whose begins and counts are known on the host: the table of the non-empty ones with their
-// ranks, then the two launches.  All or nothing.
-int insert_clouds(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float4 * src, const uint32_t * begin, const uint32_t * count,
-  uint32_t n, const double * poses, hipStream_t st)
+// ranks, then the two launches and the call's record behind them.  All or nothing.
+int insert_clouds(Call & k, lfx_rolling_map * rm, int kind, const float4 * src, const uint32_t * begin, const uint32_t * count,
+  uint32_t n, const double * poses)
 {
+  lfx_ctx * const c = k.c;
+  hipStream_t const st = k.st;
   Store & s = rm->store[kind];
   uint64_t records = 0, blocks = 0;
   size_t na = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    records += count[k];
-    blocks += (count[k] + lfx::kRollThreads - 1u) / lfx::kRollThreads;
-    na += count[k] ? 1u : 0u;
+  for (uint32_t i = 0; i < n; i++) {
+    records += count[i];
+    blocks += (count[i] + lfx::kRollThreads - 1u) / lfx::kRollThreads;
+    na += count[i] ? 1u : 0u;
   }
   // (a rank is 32 bits and 0xFFFFFFFF - rank must stay above 0)
   if (records > 0xFFFFFFFEull || blocks > 0x7FFFFFFFull) {return fail(c, LFX_ERR_CAPACITY, "the call inserts too many records for one launch");}
@@ -86,28 +88,26 @@ int insert_clouds(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float4 * sr
   if (rm->table.n < na) {
     DevBuf<lfx::RollInsertEntry> t;
     if (t.alloc(na + na / 2) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the rolling map's table");}
-    const int rs = rm->tail.settle(c);       // (the previous insert may still read the old table)
-    if (rs != LFX_OK) {return rs;}
+    LFX_TRY(k.after(rm->tail));              // (the previous insert may still read the old table)
     rm->table = std::move(t);
   }
   const size_t bytes = sizeof(lfx::RollInsertEntry) * na;
-  int rs = rm->tail.settle(c);               // (the previous insert has passed: the pinned table may be written again)
-  if (rs != LFX_OK) {return rs;}
+  LFX_TRY(k.after(rm->tail));                // (the previous insert has passed: the pinned table may be written again)
   LFX_HIP(c, rm->pinned.reserve(rm->pin_table + bytes));
   lfx::RollInsertEntry * tab = reinterpret_cast<lfx::RollInsertEntry *>(rm->pinned.p + rm->pin_table);
   uint32_t first = 0, rank = 0;
   size_t at = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    if (count[k] == 0) {continue;}
+  for (uint32_t i = 0; i < n; i++) {
+    if (count[i] == 0) {continue;}
     lfx::RollInsertEntry e{};
-    std::memcpy(e.m, poses + 12 * (size_t)k, sizeof(e.m));
-    e.src = begin[k];
-    e.count = count[k];
+    std::memcpy(e.m, poses + 12 * (size_t)i, sizeof(e.m));
+    e.src = begin[i];
+    e.count = count[i];
     e.first_block = first;
     e.rank = rank;
     tab[at++] = e;
-    first += (count[k] + lfx::kRollThreads - 1u) / lfx::kRollThreads;
-    rank += count[k];
+    first += (count[i] + lfx::kRollThreads - 1u) / lfx::kRollThreads;
+    rank += count[i];
   }
   if (s.epoch == 0xFFFFFFFFu) {              // the epoch wraps: every stamp back to "older than anything"
     LFX_HIP(c, hipMemsetAsync(s.stamps.p, 0, sizeof(uint64_t) * s.slots, st));
@@ -119,7 +119,7 @@ int insert_clouds(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float4 * sr
   hipLaunchKernelGGL(lfx::rolling_claim_kernel, dim3(first), dim3(lfx::kRollThreads), 0, st, v, rm->table.p, (uint32_t)na, src, s.epoch, s.counters.p);
   hipLaunchKernelGGL(lfx::rolling_commit_kernel, dim3(first), dim3(lfx::kRollThreads), 0, st, v, rm->table.p, (uint32_t)na, src, s.epoch, s.counters.p);
   LFX_HIP(c, hipGetLastError());
-  return rm->tail.done(c, st);
+  return k.finish();
 }
 
 // the voxel of a coordinate given in metres as a double, clamped to the voxels a key can name
@@ -145,15 +145,17 @@ bool clip_box(const Store & s, const int32_t lo[3], const int32_t hi[3], lfx::Ro
   return true;
 }
 
-// the live voxels of a box: counted (d_out null) or written up to `capacity`; the count read back, one wait
-int extract_box(lfx_ctx * c, const lfx_rolling_map * rm, int kind, const lfx::RollBox & box, float4 * d_out, uint64_t capacity,
-  uint64_t * n_points, hipStream_t st)
+// the live voxels of a box: counted (d_out null) or written up to `capacity`; the count read back, one wait.  A read: the
+// stream goes behind the tail and nothing is taken
+int extract_box(const Call & k, const lfx_rolling_map * rm, int kind, const lfx::RollBox & box, float4 * d_out, uint64_t capacity,
+  uint64_t * n_points)
 {
+  lfx_ctx * const c = k.c;
+  hipStream_t const st = k.st;
   const Store & s = rm->store[kind];
   const uint32_t n_blocks = (uint32_t)(((uint64_t)box.cells + lfx::kRollCells - 1u) / lfx::kRollCells);
   const lfx::RollStore v = s.view();
-  int rc = rm->tail.order_behind(c, st);     // (the previous insert may be queued on another stream)
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(k.read(rm->tail));                 // (the previous insert may be queued on another stream)
   hipLaunchKernelGGL(lfx::rolling_block_count_kernel, dim3(n_blocks), dim3(lfx::kRollThreads), 0, st, v, box, rm->partial.p);
   hipLaunchKernelGGL(lfx::rolling_partial_scan_kernel, dim3(1), dim3(lfx::kRollThreads), 0, st, rm->partial.p, n_blocks, rm->total.p);
   if (d_out && capacity) {
@@ -218,7 +220,7 @@ bool wants_recentre(const lfx_rolling_map * rm, const double t[3], bool & ok)
 }
 
 // the box of half extent match_half_extent around t cut out of store `kind` into rm->box[kind] (grown where it must be)
-int cut_box(lfx_ctx * c, lfx_rolling_map * rm, int kind, const double t[3], uint64_t * n, double lo_m[3], double hi_m[3], hipStream_t st)
+int cut_box(const Call & k, lfx_rolling_map * rm, int kind, const double t[3], uint64_t * n, double lo_m[3], double hi_m[3])
 {
   const Store & s = rm->store[kind];
   int32_t vlo[3], vhi[3];
@@ -233,11 +235,10 @@ int cut_box(lfx_ctx * c, lfx_rolling_map * rm, int kind, const double t[3], uint
   lfx::RollBox box{};
   if (!clip_box(s, vlo, vhi, &box)) {return LFX_OK;}
   for (int pass = 0; pass < 2; pass++) {
-    const int rc = extract_box(c, rm, kind, box, rm->box[kind].p, rm->box[kind].n, n, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(extract_box(k, rm, kind, box, rm->box[kind].p, rm->box[kind].n, n));
     if (*n <= rm->box[kind].n) {break;}
     // (the buffer is not in use: extract_box has waited)
-    if (hold(rm->box[kind], *n) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the match box");}
+    if (hold(rm->box[kind], *n) != hipSuccess) {(void)hipGetLastError(); return fail(k.c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the match box");}
   }
   return LFX_OK;
 }
@@ -272,8 +273,7 @@ void lfx_rolling_map_default_config(lfx_rolling_map_config * cfg)
   cfg->max_iter = 20;
   cfg->scan_surface_leaf = 1.0f;
   cfg->edge_cell = cfg->surface_cell = 1.0f;
-  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  std::memcpy(cfg->initial_pose, identity, sizeof(identity));
+  std::memcpy(cfg->initial_pose, kIdentityPose, sizeof(kIdentityPose));
 }
 
 int lfx_rolling_map_create(lfx_ctx * c, const lfx_rolling_map_config * cfg, lfx_rolling_map ** out)
@@ -287,21 +287,15 @@ int lfx_rolling_map_create(lfx_ctx * c, const lfx_rolling_map_config * cfg, lfx_
       return fail(c, LFX_ERR_INVALID_ARGUMENT, "match_half_extent must be >= 0 and finite");
     }
   }
-  if (cfg->n_neighbors < 3 || cfg->n_neighbors > 16) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_neighbors must be in [3, 16]");}
-  if (cfg->max_iter < 1) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "max_iter must be >= 1");}
-  if (!(cfg->scan_surface_leaf > 0.f) || !std::isfinite(cfg->scan_surface_leaf)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "scan_surface_leaf must be > 0");}
-  if (!(cfg->edge_cell >= 0.f) || !std::isfinite(cfg->edge_cell) || !(cfg->surface_cell >= 0.f) || !std::isfinite(cfg->surface_cell)) {
-    return fail(c, LFX_ERR_INVALID_ARGUMENT, "edge_cell / surface_cell must be >= 0 (0: no grid)");
-  }
-  if (!finite_all(cfg->initial_pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "initial_pose must be finite");}
+  LFX_TRY(check_align_config(c, cfg->n_neighbors, cfg->max_iter, cfg->scan_surface_leaf, "scan_surface_leaf", cfg->edge_cell,
+    cfg->surface_cell, cfg->initial_pose));
   LFX_HIP(c, hipSetDevice(c->device));
   lfx_rolling_map * rm = new (std::nothrow) lfx_rolling_map();
   if (!rm) {return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the rolling map");}
   rm->device = c->device;
   rm->cfg = *cfg;
   std::memcpy(rm->pose, cfg->initial_pose, sizeof(rm->pose));
-  const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  std::memcpy(rm->correction, identity, sizeof(identity));
+  std::memcpy(rm->correction, kIdentityPose, sizeof(kIdentityPose));
   auto give_up = [&](int code, const std::string & why) {(void)hipGetLastError(); lfx_rolling_map_destroy(rm); return fail(c, code, why);};
   uint64_t most = 0;
   for (int k = 0; k < 2; k++) {
@@ -347,15 +341,7 @@ int lfx_rolling_map_create(lfx_ctx * c, const lfx_rolling_map_config * cfg, lfx_
   return LFX_OK;
 }
 
-void lfx_rolling_map_destroy(lfx_rolling_map * rm)
-{
-  if (!rm) {return;}
-  (void)hipSetDevice(rm->device);
-  lfx_map * const emap = rm->emap, * const smap = rm->smap;
-  delete rm;                                 // (waits for the tail: the match maps go after it, as the buffers do)
-  lfx_map_destroy(emap);
-  lfx_map_destroy(smap);
-}
+void lfx_rolling_map_destroy(lfx_rolling_map * rm) {destroy_with_maps(rm);}
 
 int lfx_rolling_map_recenter(lfx_rolling_map * rm, const double center[3])
 {
@@ -382,19 +368,16 @@ int lfx_rolling_map_insert(lfx_ctx * c, lfx_rolling_map * rm, int kind, const fl
   if (n_clouds == 0 || count_stride == 0) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "n_clouds and count_stride must be >= 1");}
   if (!finite_all(poses, 12 * (size_t)n_clouds)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the poses must be finite");}
   if (check(c, rm, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = rm->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.read(rm->tail));
   // the counts and the begins back in one wait: the call's only one
-  rc = grow_readback(c, rm->tail, rm->pinned, rm->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::RollInsertEntry),
-    std::max<size_t>(n_clouds, kInitialEntries));
-  if (rc != LFX_OK) {return rc;}
+  LFX_TRY(grow_readback(k, rm->tail, rm->pinned, rm->pin_table, readback_bytes(n_clouds, count_stride), sizeof(lfx::RollInsertEntry),
+    std::max<size_t>(n_clouds, kInitialEntries)));
   const CloudList list{d_begin, d_count, count_stride, total_points, ""};
   std::vector<uint32_t> begin, count;
-  rc = read_lists(c, &list, 1, n_clouds, rm->pinned.p, &begin, &count, st);
-  if (rc != LFX_OK) {return rc;}
-  return insert_clouds(c, rm, kind, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses, st);
+  LFX_TRY(read_lists(c, &list, 1, n_clouds, rm->pinned.p, &begin, &count, k.st));
+  return insert_clouds(k, rm, kind, reinterpret_cast<const float4 *>(d_points), begin.data(), count.data(), n_clouds, poses);
 }
 
 int lfx_rolling_map_insert_host(lfx_ctx * c, lfx_rolling_map * rm, int kind, const float * points, uint32_t n_points,
@@ -404,16 +387,14 @@ int lfx_rolling_map_insert_host(lfx_ctx * c, lfx_rolling_map * rm, int kind, con
   if (!finite_all(pose, 12)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the pose must be finite");}
   if (check(c, rm, kind) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
   if (n_points == 0) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = rm->tail.settle(c);               // (the previous insert may still read the staged cloud)
-  if (rc != LFX_OK) {return rc;}
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  LFX_TRY(k.after(rm->tail));                // (the previous insert may still read the staged cloud)
   if (hold(rm->staged, n_points) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot stage the cloud");}
-  LFX_HIP(c, hipMemcpyAsync(rm->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, st));
+  LFX_HIP(c, hipMemcpyAsync(rm->staged.p, points, sizeof(float4) * n_points, hipMemcpyHostToDevice, k.st));
   const uint32_t zero = 0u;
-  rc = insert_clouds(c, rm, kind, rm->staged.p, &zero, &n_points, 1, pose, st);
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipStreamSynchronize(st));      // (the caller's memory is pageable: it has been read when the call returns)
+  LFX_TRY(insert_clouds(k, rm, kind, rm->staged.p, &zero, &n_points, 1, pose));
+  LFX_HIP(c, hipStreamSynchronize(k.st));      // (the caller's memory is pageable: it has been read when the call returns)
   return LFX_OK;
 }
 
@@ -429,18 +410,19 @@ int lfx_rolling_map_extract(lfx_ctx * c, const lfx_rolling_map * rm, int kind, c
   *n_points = 0;
   lfx::RollBox box{};
   if (!clip_box(s, vlo, vhi, &box)) {return LFX_OK;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  return extract_box(c, rm, kind, box, reinterpret_cast<float4 *>(d_out), capacity_points, n_points, static_cast<hipStream_t>(stream));
+  Call k(c, stream);
+  LFX_TRY(k.open());
+  return extract_box(k, rm, kind, box, reinterpret_cast<float4 *>(d_out), capacity_points, n_points);
 }
 
 int lfx_rolling_map_view(lfx_ctx * c, const lfx_rolling_map * rm, lfx_rolling_map_view_t * v, void * stream)
 {
   if (!c || !rm || !v) {return LFX_ERR_INVALID_ARGUMENT;}
   if (check(c, rm, LFX_ROLLING_EDGE) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = rm->tail.order_behind(c, st);
-  if (rc != LFX_OK) {return rc;}
+  Call call(c, stream);
+  LFX_TRY(call.open());
+  LFX_TRY(call.read(rm->tail));
+  hipStream_t const st = call.st;
   lfx_rolling_map_view_t out{};
   uint64_t * h = reinterpret_cast<uint64_t *>(rm->pinned.p);
   for (int k = 0; k < 2; k++) {
@@ -459,10 +441,7 @@ int lfx_rolling_map_view(lfx_ctx * c, const lfx_rolling_map * rm, lfx_rolling_ma
   }
   for (int k = 0; k < 2; k++) {              // (after the counters have been read out of the pinned block)
     lfx::RollBox box{};
-    if (whole_window(rm->store[k], &box)) {
-      rc = extract_box(c, rm, k, box, nullptr, 0, &out.n_live[k], st);
-      if (rc != LFX_OK) {return rc;}
-    }
+    if (whole_window(rm->store[k], &box)) {LFX_TRY(extract_box(call, rm, k, box, nullptr, 0, &out.n_live[k]));}
   }
   std::memcpy(out.pose, rm->pose, sizeof(out.pose));
   std::memcpy(out.correction, rm->correction, sizeof(out.correction));
@@ -485,24 +464,13 @@ int lfx_rolling_map_update_batch(lfx_ctx * c, lfx_rolling_map * rm, uint32_t n_s
   if (rb != LFX_OK) {return rb;}
   if (odometry_poses && !finite_all(odometry_poses, 12 * (size_t)n_scans)) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the odometry poses must be finite");}
   if (check(c, rm, LFX_ROLLING_EDGE) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Call call(c, stream);
+  LFX_TRY(call.open());
+  hipStream_t const st = call.st;
   const uint32_t batch = c->last_batch, k = rm->cfg.n_neighbors;
-  const size_t total = c->h_scan_begin[batch];
-  if (hold(rm->down, 4 * total + 2 * (size_t)batch) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the downsampled surface clouds");}
-  LFX_HIP(c, rm->h_batch.reserve(sizeof(uint32_t) * 6 * (size_t)batch));
-  float * down = rm->down.p;
-  uint32_t * down_count = reinterpret_cast<uint32_t *>(down + 4 * total), * down_status = down_count + batch;
-  uint32_t * info = reinterpret_cast<uint32_t *>(rm->h_batch.p), * lengths = info + 4 * (size_t)batch;
-  void * d_lengths = nullptr;
-  LFX_HIP(c, hipHostGetDevicePointer(&d_lengths, lengths, 0));
   // the batch's surface clouds downsampled once and every scan's counts, as lfx_odometry_update_batch has them: one wait
-  int rc = voxel_downsample(c, reinterpret_cast<const float *>(c->surf_pts.p), c->scan_begin.p, c->scan_info.p + lfx::kInfoSurface, 4,
-    batch, total, rm->cfg.scan_surface_leaf, down, down_count, down_status, stream, true, c->scan_info.p + lfx::kInfoEdge,
-    static_cast<uint32_t *>(d_lengths));
-  if (rc != LFX_OK) {return rc;}
-  LFX_HIP(c, hipMemcpyAsync(info, c->scan_info.p, sizeof(uint32_t) * 4 * batch, hipMemcpyDeviceToHost, st));
-  LFX_HIP(c, hipStreamSynchronize(st));
+  BatchFront f;
+  LFX_TRY(batch_front(c, rm->down, 2, false, rm->h_batch, 0, true, rm->cfg.scan_surface_leaf, st, f));
   for (uint32_t s = 0; s < batch; s++) {
     lfx_rolling_map_result r{};
     const double * odom = odometry_poses ? odometry_poses + 12 * (size_t)s : nullptr;
@@ -514,16 +482,16 @@ int lfx_rolling_map_update_batch(lfx_ctx * c, lfx_rolling_map * rm, uint32_t n_s
     const double t[3] = {initial[3], initial[7], initial[11]};
     bool ok = true;
     if (wants_recentre(rm, t, ok)) {
-      rc = lfx_rolling_map_recenter(rm, t);
-      if (rc != LFX_OK) {ok = false;}
+      ok = lfx_rolling_map_recenter(rm, t) == LFX_OK;
       r.recentered = 1;
     }
     if (!ok) {return fail(c, LFX_ERR_INVALID_ARGUMENT, "the initial pose of scan " + std::to_string(s) + " lies outside the voxels a map can name");}
     uint64_t ne = 0, ns = 0;
     double elo[3], ehi[3], slo[3], shi[3];
-    rc = cut_box(c, rm, LFX_ROLLING_EDGE, t, &ne, elo, ehi, st);
-    if (rc == LFX_OK) {rc = cut_box(c, rm, LFX_ROLLING_SURFACE, t, &ns, slo, shi, st);}
-    if (rc != LFX_OK) {return rc;}
+    // (what the scan queues from here on stands behind the call's record, however the call leaves)
+    LFX_TRY(call.behind(rm->tail));
+    LFX_TRY(cut_box(call, rm, LFX_ROLLING_EDGE, t, &ne, elo, ehi));
+    LFX_TRY(cut_box(call, rm, LFX_ROLLING_SURFACE, t, &ns, slo, shi));
     r.n_edge_map = (uint32_t)ne;
     r.n_surface_map = (uint32_t)ns;
     bool place = true;
@@ -531,15 +499,13 @@ int lfx_rolling_map_update_batch(lfx_ctx * c, lfx_rolling_map * rm, uint32_t n_s
       std::memcpy(r.align.pose, initial, sizeof(initial));
       r.align.code = LFX_ALIGN_NOT_RUN;
     } else {
-      rc = map_rebuild(c, rm->emap, reinterpret_cast<const float *>(rm->box[0].p), (uint32_t)ne, rm->cfg.edge_cell, elo, ehi, st);
-      if (rc == LFX_OK) {rc = map_rebuild(c, rm->smap, reinterpret_cast<const float *>(rm->box[1].p), (uint32_t)ns, rm->cfg.surface_cell, slo, shi, st);}
-      if (rc != LFX_OK) {return rc;}
-      const uint32_t n_edge = info[4 * s + lfx::kInfoEdge];
+      LFX_TRY(map_rebuild(c, rm->emap, reinterpret_cast<const float *>(rm->box[0].p), (uint32_t)ne, rm->cfg.edge_cell, elo, ehi, st));
+      LFX_TRY(map_rebuild(c, rm->smap, reinterpret_cast<const float *>(rm->box[1].p), (uint32_t)ns, rm->cfg.surface_cell, slo, shi, st));
+      const uint32_t n_edge = f.info[4 * s + lfx::kInfoEdge];
       const CloudSpan edge{reinterpret_cast<const float *>(c->edge_pts.p), c->scan_begin.p + s, c->scan_info.p + lfx::kInfoEdge + 4 * s, 4,
         n_edge, n_edge, rm->zero.p};
-      const CloudSpan surface{down, c->scan_begin.p + s, down_count + s, 1, lengths[2 * s + 1], lengths[2 * s + 1], rm->zero.p};
-      rc = align_clouds(c, rm->emap, rm->smap, k, rm->cfg.max_iter, edge, surface, 1, initial, &r.align, st);
-      if (rc != LFX_OK) {return rc;}
+      const CloudSpan surface{f.down, c->scan_begin.p + s, f.down_count + s, 1, f.lengths[2 * s + 1], f.lengths[2 * s + 1], rm->zero.p};
+      LFX_TRY(align_clouds(c, rm->emap, rm->smap, k, rm->cfg.max_iter, edge, surface, 1, initial, &r.align, st));
       r.aligned = 1;
       if (LFX_ALIGN_SUCCESS(r.align.code)) {
         std::memcpy(pose, r.align.pose, sizeof(pose));
@@ -554,9 +520,8 @@ int lfx_rolling_map_update_batch(lfx_ctx * c, lfx_rolling_map * rm, uint32_t n_s
     }
     if (place) {
       const uint32_t begin = c->h_scan_begin[s];
-      rc = insert_clouds(c, rm, LFX_ROLLING_EDGE, c->edge_pts.p, &begin, info + 4 * s + lfx::kInfoEdge, 1, pose, st);
-      if (rc == LFX_OK) {rc = insert_clouds(c, rm, LFX_ROLLING_SURFACE, c->surf_pts.p, &begin, info + 4 * s + lfx::kInfoSurface, 1, pose, st);}
-      if (rc != LFX_OK) {return rc;}
+      LFX_TRY(insert_clouds(call, rm, LFX_ROLLING_EDGE, c->edge_pts.p, &begin, f.info + 4 * s + lfx::kInfoEdge, 1, pose));
+      LFX_TRY(insert_clouds(call, rm, LFX_ROLLING_SURFACE, c->surf_pts.p, &begin, f.info + 4 * s + lfx::kInfoSurface, 1, pose));
       r.inserted = 1;
     }
     std::memcpy(rm->pose, pose, sizeof(pose));
@@ -570,27 +535,21 @@ int lfx_rolling_map_save(lfx_ctx * c, const lfx_rolling_map * rm, const char * d
   if (!c || !rm || !dirname || !written) {return LFX_ERR_INVALID_ARGUMENT;}
   written[0] = written[1] = 0;
   if (check(c, rm, LFX_ROLLING_EDGE) != LFX_OK) {return LFX_ERR_INVALID_ARGUMENT;}
-  LFX_HIP(c, hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const std::string dir(dirname);
-  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
+  Call call(c, stream);
+  LFX_TRY(call.open());
   for (int k = 0; k < 2; k++) {
     lfx::RollBox box{};
     if (!whole_window(rm->store[k], &box)) {continue;}
     uint64_t n = 0, again = 0;
-    int rc = extract_box(c, rm, k, box, nullptr, 0, &n, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(extract_box(call, rm, k, box, nullptr, 0, &n));
     if (n == 0) {continue;}                  // (as lfx_odometry_save: an empty cloud writes no file)
     DevBuf<float4> cloud;
     if (cloud.alloc(n) != hipSuccess) {(void)hipGetLastError(); return fail(c, LFX_ERR_OUT_OF_MEMORY, "cannot allocate the cloud to save");}
-    rc = extract_box(c, rm, k, box, cloud.p, n, &again, st);
-    if (rc != LFX_OK) {return rc;}
+    LFX_TRY(extract_box(call, rm, k, box, cloud.p, n, &again));
     std::vector<float> host(4 * (size_t)n);
-    LFX_HIP(c, hipMemcpyAsync(host.data(), cloud.p, sizeof(float) * host.size(), hipMemcpyDeviceToHost, st));
-    LFX_HIP(c, hipStreamSynchronize(st));
-    char msg[512];
-    rc = lfx_pcd_write((dir + sep + (k ? "surface.pcd" : "edge.pcd")).c_str(), host.data(), n, msg, sizeof(msg));
-    if (rc != LFX_OK) {return fail(c, rc, msg);}
+    LFX_HIP(c, hipMemcpyAsync(host.data(), cloud.p, sizeof(float) * host.size(), hipMemcpyDeviceToHost, call.st));
+    LFX_HIP(c, hipStreamSynchronize(call.st));
+    LFX_TRY(write_pcd(c, kind_path(dirname, k), host.data(), n));
     written[k] = 1;
   }
   return LFX_OK;

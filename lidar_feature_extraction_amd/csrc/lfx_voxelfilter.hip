@@ -295,8 +295,6 @@ int lfx_keyframes_save_filtered(lfx_ctx * c, const lfx_keyframes * kf, lfx_voxel
   }
   LFX_HIP(c, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const std::string dir(dirname);
-  const std::string sep = (!dir.empty() && dir.back() == '/') ? "" : "/";
   for (int kind = 0; kind < 2; kind++) {
     if (ks.begin[kind][ks.n] == 0u) {continue;}
     int rc = lfx_voxel_filter_reset(c, f, leaf[kind], stream);
@@ -316,9 +314,7 @@ int lfx_keyframes_save_filtered(lfx_ctx * c, const lfx_keyframes * kf, lfx_voxel
       LFX_HIP(c, hipMemcpyAsync(host.data() + 4u * (size_t)lo, ks.scratch, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
     }
     LFX_HIP(c, hipStreamSynchronize(st));
-    char msg[512];
-    rc = lfx_pcd_write((dir + sep + (kind ? "surface.pcd" : "edge.pcd")).c_str(), host.data(), r.n_written, msg, sizeof(msg));
-    if (rc != LFX_OK) {return fail(c, rc, msg);}
+    LFX_TRY(write_pcd(c, kind_path(dirname, kind), host.data(), r.n_written));
     written[kind] = 1;
   }
   return LFX_OK;

@@ -447,3 +447,39 @@ def test_rolling_map_update_chain_over_two_streams():
     assert sum(r["aligned"] for r in one) >= 2 and all(r["inserted"] for r in one), [(r["aligned"], r["inserted"], r["code"]) for r in one]
     assert state2[0].tobytes() == state1[0].tobytes() and state2[1].tobytes() == state1[1].tobytes() and len(state1[0]) > 500 and len(state1[1]) > 500
     assert state2[2]["edge"] == state1[2]["edge"] and state2[2]["surface"] == state1[2]["surface"] and state2[3].tobytes() == state1[3].tobytes()
+
+
+@pytest.mark.gpu
+def test_rolling_map_host_inserts_then_an_update_over_two_streams():
+    """lfx_rolling_map_insert_host of two scans' clouds on A, B, A -- each call rewrites the staged cloud and the pinned
+    table the call before it, on the other stream, read -- then lfx_rolling_map_update_batch of a third scan on B, whose
+    boxes are cut behind the last insert on A.  The result, the whole windows, the view and the pose equal the same four
+    calls on one stream on a fresh map, byte for byte."""
+    from lidar_feature_extraction_amd import make_sequence
+    clouds, _ = make_sequence(3, S.RINGS, S.COLS, seed=8102)
+    a, b = S.two_streams()
+    fx = K.fx_for(S.RINGS, S.COLS, 2)
+    _, got = K.extract(fx, clouds[:2])
+    host = [(np.ascontiguousarray(g.edge_points, np.float32).reshape(-1, 4).copy(), np.ascontiguousarray(g.surface_points, np.float32).reshape(-1, 4).copy())
+            for g in got]
+    d, _ = K.extract(fx, clouds[2:])
+    K.sync()
+
+    def chain(streams):
+        rm = fx.rolling_map(edge_dims=(256, 256, 64), surface_dims=(128, 128, 32))
+        rm.insert_host("edge", host[0][0], None, streams[0])
+        rm.insert_host("surface", host[0][1], None, streams[1])
+        rm.insert_host("edge", host[1][0], None, streams[2])
+        out = rm.update_batch(None, 1, streams[3])
+        K.sync()
+        state = (_whole(rm, "edge"), _whole(rm, "surface"), rm.view(K.stream()), rm.pose())
+        rm.close()
+        return out, state
+
+    one, state1 = chain([K.stream()] * 4)
+    two, state2 = chain([a.cuda_stream, b.cuda_stream, a.cuda_stream, b.cuda_stream])
+    fx.close()
+    assert [_bits(r) for r in two] == [_bits(r) for r in one]
+    assert one[0]["aligned"] and one[0]["inserted"], (one[0]["aligned"], one[0]["inserted"], one[0]["code"])
+    assert state2[0].tobytes() == state1[0].tobytes() and state2[1].tobytes() == state1[1].tobytes() and len(state1[0]) > 500 and len(state1[1]) > 500
+    assert state2[2]["edge"] == state1[2]["edge"] and state2[2]["surface"] == state1[2]["surface"] and state2[3].tobytes() == state1[3].tobytes()

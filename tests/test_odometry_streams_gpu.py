@@ -96,3 +96,85 @@ def test_update_host_on_alternating_streams(scans):
     got = run([a.cuda_stream, b.cuda_stream, a.cuda_stream])
     assert [r[3] for r in want[0]] == [False, True, True] and want[4] == (3, 3)
     assert got == want
+
+
+# --- the batch calls ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def batches():
+    """A context for batches of two scans and four scans of the same sensor."""
+    from lidar_feature_extraction_amd import make_sequence
+    clouds, _ = make_sequence(4, RINGS, COLS, seed=8401)
+    fx = K.fx_for(RINGS, COLS, 2)
+    yield fx, clouds
+    fx.close()
+
+
+@pytest.mark.parametrize("deskewed", [False, True])
+def test_update_batch_on_a_then_b(batches, deskewed):
+    """Two batches of two scans through lfx_odometry_update_batch (lfx_odometry_update_batch_deskewed), the first on A, the
+    second on B.  The second call rewrites the downsampled clouds, the pinned scan_info and the lengths while the first call's
+    last append may still be queued on A; nothing is waited for on the host between the calls (the second extraction is
+    ordered behind A by an event -- the context's clouds are the caller's to keep -- and B behind the extraction).  Results
+    and store equal those of the same calls on one stream."""
+    import torch
+    fx, clouds = batches
+    a, b = S.two_streams()
+
+    def run(streams):
+        odo = fx.odometry(n_local_scans=2)
+        cur, out, keep, last = torch.cuda.current_stream(), [], [], None
+        for i, st in enumerate(streams):
+            if last is not None:
+                cur.wait_stream(last)
+            keep.append(S.device_batch(fx, clouds[2 * i:2 * i + 2]))
+            st.wait_stream(cur)
+            out += odo.update_batch_deskewed(None, None, 1.0, "end", 2, st.cuda_stream) if deskewed else odo.update_batch(2, st.cuda_stream)
+            last = st
+        state = _state(odo, out)
+        odo.close()
+        return state
+
+    want = run([torch.cuda.current_stream()] * 2)
+    got = run([a, b])
+    assert [r[3] for r in want[0]] == [False, True, True, True] and want[4] == (4, 4)
+    assert got == want
+
+
+def test_a_refusal_in_the_middle_of_a_batch(batches, tmp_path):
+    """An edge store one record too small for scans 0 and 1 together: lfx_odometry_update_batch on A appends scan 0 and
+    refuses scan 1 -- LFX_ERR_INVALID_ARGUMENT, "the scan (...) does not fit the odometry's store beside its window" -- with
+    scan 0's append queued behind it.  Then, on B, the view, lfx_odometry_save and one more lfx_odometry_update (scan 2's
+    surface cloud and as many of its edge records as still fit): the result, the files and the store equal those of the
+    same calls on one stream."""
+    import torch
+    from lidar_feature_extraction_amd import binding as B
+    fx, clouds = batches
+    a, b = S.two_streams()
+    _, (g2,) = K.extract(fx, clouds[2:3])
+    e2, s2 = (np.ascontiguousarray(p, np.float32).reshape(-1, 4).copy() for p in (g2.edge_points, g2.surface_points))
+    d, got01 = K.extract(fx, clouds[:2])
+    ne, ns = [len(g.edge_points) for g in got01], [len(g.surface_points) for g in got01]
+    assert ne[1] > 16 and len(e2) > 16
+    e2 = e2[:min(len(e2), ne[1] - 1)]
+    d_e2, d_s2 = torch.from_numpy(e2).to(K.dev()), torch.from_numpy(s2).to(K.dev())
+    K.sync()
+
+    def run(st_batch, st_rest, where):
+        odo = fx.odometry(n_local_scans=2, edge_capacity_points=ne[0] + ne[1] - 1)
+        with pytest.raises(B.LfxError) as err:
+            odo.update_batch(2, st_batch)
+        assert err.value.code == -1 and str(err.value) == (
+            "lfx error -1: the scan (%d edge, %d surface points) does not fit the odometry's store beside its window" % (ne[1], ns[1]))
+        v = odo.view()
+        assert (v["n_scans"], v["n_added"], v["n_edge"], v["n_surface"]) == (1, 1, ne[0], ns[0])
+        where.mkdir()
+        assert odo.save(str(where), st_rest) == (True, True)
+        out = [odo.update(d_e2.data_ptr(), len(d_e2), d_s2.data_ptr(), len(d_s2), st_rest)]
+        state = _state(odo, out), (where / "edge.pcd").read_bytes(), (where / "surface.pcd").read_bytes()
+        odo.close()
+        return state
+
+    want = run(K.stream(), K.stream(), tmp_path / "one")
+    got = run(a.cuda_stream, b.cuda_stream, tmp_path / "two")
+    assert want[0][0][0][3] is True and want[0][4] == (2, 2)
+    assert got == want
